@@ -8,7 +8,7 @@ the reference's ``_sample`` returns them.  One process per GPU; images shard acr
 collective (weak scaling: every rank decodes its own 64-image batch per step).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--dtype bf16|f32]
-                    [--ids-only] [--no-graph] [--no-cpu-baseline]
+                    [--ids-only] [--no-graph] [--no-cpu-baseline] [--dump-outputs DIR]
 
 Prints ONE JSON line on rank 0 (contract in the task brief): metric/value/unit, roofline (MFMA
 bound, algorithmic FLOPs of SURVEY.md §8d over the HIP-event time of the decode launches) and
@@ -32,6 +32,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 ATT_SEED = 1235      # seed 1234 puts an image with zero phrases last: quirk Q1 then NaNs the whole batch
+DUMP_BYTES = 60 * 10 ** 6    # --dump-outputs: .npy payload in all (64 MB with room for the headers)
 
 
 def self_launch(argv, n: int) -> int:
@@ -284,6 +285,13 @@ def _executed(flops_fixed, flops_skippable, active_share, ms, dtype):
     return {"executed_gemm_flops": f, "achieved_executed": round(tf, 2), "frac_executed": round(tf / MFMA_PEAK[dtype], 5)}
 
 
+def _parameter_sample(model, n=1 << 20):
+    """--dump-outputs of the training steps: a fixed, seeded sample of the model's parameters (in named_parameters order, flattened) after the last step."""
+    flat = torch.cat([p.detach().float().reshape(-1) for p in model.parameters()])
+    idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:n].sort().values
+    return flat[idx.to(flat.device)]
+
+
 def run_xe(args, ctx, log, cpu=True):
     """BASELINE config 3: XE training step, batch 64 images x 5 captions per GPU, data-parallel with one flat-bucket
     RCCL all-reduce per step (weak scaling)."""
@@ -328,7 +336,7 @@ def run_xe(args, ctx, log, cpu=True):
     t0 = time.perf_counter()
     e0.record()
     for _ in range(args.steps):
-        loss, _ = tr.step(batch)
+        loss, parts = tr.step(batch)
     e1.record()
     host_ms = (time.perf_counter() - t0) / args.steps * 1e3       # time to ENQUEUE a step (Python + launch overhead)
     _barrier(world)
@@ -372,6 +380,9 @@ def run_xe(args, ctx, log, cpu=True):
                    "sharding": "images by rank; RCCL all-reduce over the live part of the flat fp32 gradient bucket per step"},
         "roofline": roof,
     }
+    if args.dump_outputs:
+        res["config"]["dump_outputs"] = dump_outputs(args.dump_outputs, {"loss": loss, "loss_parts": torch.cat([torch.as_tensor(p).detach().float().reshape(-1).cpu() for p in parts]),
+                                                                          "parameters_sample": _parameter_sample(model)}, log)
     if cpu and world == 1:
         _cpu_leg(res, lambda: cpu_baseline_xe(cfg, sd, spi, budget_s=args.cpu_budget))
     return res
@@ -564,6 +575,9 @@ def run_rl(args, ctx, log, cpu=True):
         loss, rs, rn = tr.rl_step(att, None, score, sample_n=n)
     _barrier(world)
     elapsed = dp.reduce_scalar(time.perf_counter() - t0, "max", device=dev)
+    dumped = None
+    if args.dump_outputs and rank == 0:                        # (before the fast-estimator leg below steps the model further)
+        dumped = dump_outputs(args.dump_outputs, {"loss": loss, "reward_saic": rs, "reward_naic": rn, "parameters_sample": _parameter_sample(model)}, log)
     last_default = dict(tr._last_rl)
     ref_info = {"drawn_rows_vs_gradient_pass_rows_max_abs": last_default.get("reference_gap"), "training_forwards_per_step": last_default.get("training_forwards")}
     # the fast form of rounds 1-4 beside it (opt.bofi_rl_reference_estimator = False: samples from the dropout-free inference engine, ONE gradient pass with
@@ -614,6 +628,8 @@ def run_rl(args, ctx, log, cpu=True):
                                    "fast_estimator = rounds 1-4's form, opt.bofi_rl_reference_estimator = False",
                       "reference_estimator": ref_info, "fast_estimator": fast_info},
            "roofline": roof}
+    if dumped:
+        res["config"]["dump_outputs"] = dumped
     if cpu and world == 1:
         _cpu_leg(res, lambda: cpu_baseline_rl(cfg, sd, n_img, n, budget_s=args.cpu_budget))
     return res
@@ -805,6 +821,24 @@ def run_naic(args, ctx, log, cpu=True, gemm_roofline=True):
     elapsed, dev_ms = spans[len(spans) // 2]
     region_ms = [round(e * 1e3, 3) for e, _ in spans]
     budget_ok = budget_held("timed") and budget_ok
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's launch (it carries C batches).  Its features are the input batches in an order that depends on how many streams were found;
+        # its batches are put back into the order of the input batches, so that the file does not depend on the stream count (with one batch per launch
+        # the launch's images are the last stream's own)
+        last = launches - 1
+        k = last % len(engines)
+        feats = atts2[k] if (last // len(engines)) % 2 else atts[k]
+        o = outs[k]
+        order = torch.arange(feats.size(0), device=dev)
+        if nb > 1:
+            src = [next(j for j in range(nb) if torch.equal(feats[j * args.batch:(j + 1) * args.batch], att[c * args.batch:(c + 1) * args.batch])) for c in range(nb)]
+            order = torch.cat([torch.arange(j * args.batch, (j + 1) * args.batch, device=dev) for j in src])
+        dumped = {name: o[name][order] for name in ("seq", "seq_logprob", "phrase_num", "phrase_length", "phrase_syn") if o.get(name) is not None}
+        dumped["bound_iters"] = o["bound_iters"]
+        dumped = dump_outputs(args.dump_outputs, dumped, log)
+        dumped["what"] = (f"the last timed launch ({C} batch(es) of {args.batch}; batches in input order)"
+                          + ("" if nb > 1 else f"; images of stream {k}, seed {ATT_SEED + 10 * rank + 1000 * k if k else ATT_SEED + 10 * rank}"))
 
     # for the record: the same K steps strictly one at a time (latency view of the same workload), HIP events on the stream
     single_ms = None
@@ -924,6 +958,8 @@ def run_naic(args, ctx, log, cpu=True, gemm_roofline=True):
                    "features_from_pinned_host_ms_per_step": round(pcie_ms, 4) if pcie_ms else None, "features_from_pinned_host_how": pcie_note, "att_feats_seed": ATT_SEED, "batches_reordered_for_q1": moved, "nan_in_output": nan, "sharding": "images by rank, no collective"},
         "roofline": roof,
     }
+    if dumped:
+        res["config"]["dump_outputs"] = dumped
     if world == 1 and gemm_roofline:
         res["roofline_gemm"] = gemm_rooflines(tdt, dev, C)
     log(f"gpu done: {res['value']} images/sec")
@@ -952,6 +988,35 @@ def _compact(res):
     return out
 
 
+def dump_outputs(path, arrays, log):
+    """--dump-outputs: the timed path's outputs of its last step as ``path/<name>.npy`` -- floating arrays as float32 (float64 stays float64), integer and
+    boolean ones as float64 (exact) -- at most DUMP_BYTES in all.  An array that does not fit is cut to a fixed, seeded sample of its rows (first axis; the
+    largest array first).  The inputs are seeded, so two builds run with the same arguments can be compared file for file.  Returns what went where."""
+    host = {}
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        a = a.detach() if isinstance(a, torch.Tensor) else torch.as_tensor(a)
+        a = a.to(torch.float64 if a.dtype == torch.float64 or not a.is_floating_point() else torch.float32)
+        host[name] = a.reshape(1) if a.dim() == 0 else a
+    rows = {}
+    for name in sorted(host, key=lambda n: -host[n].numel() * host[n].element_size()):
+        rest = sum(v.numel() * v.element_size() for k, v in host.items() if k != name)
+        a = host[name]
+        row_bytes = a[0].numel() * a.element_size()
+        if rest + a.numel() * a.element_size() > DUMP_BYTES:
+            keep = max(0, (DUMP_BYTES - rest) // row_bytes)
+            idx = torch.randperm(a.size(0), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            host[name] = a[idx.to(a.device)]
+            rows[name] = idx.tolist()
+    os.makedirs(path, exist_ok=True)
+    import numpy as np
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a.cpu().numpy())
+    log(f"outputs of the last timed step written to {path}: {', '.join(sorted(host))}")
+    return {"dir": path, "shapes": {k: list(v.shape) for k, v in sorted(host.items())}, "sampled_rows": rows}
+
+
 def run_dry(args, ctx, log):
     """BOFI_BENCH_REHEARSAL=dry: `python bench.py --gpus N` with the GPU work of every rank replaced by a sleep -- the multi-rank SHAPE of this script and nothing else
     (self-launch through torch.distributed.run, WORLD_SIZE against --gpus, the process group, images sharded by rank, barrier-bracketed region, the MAX over ranks of
@@ -966,12 +1031,13 @@ def run_dry(args, ctx, log):
     if fail is not None and int(fail) == rank:
         raise RuntimeError(f"rank {rank}: injected failure before the exchange (BOFI_BENCH_DRY_FAIL_RANK)")
     per_step_s = 1e-3 * (1.0 + 0.25 * rank)                                        # the slowest rank sets the job's time
+    # (gloo's own barrier: dist.barrier() asks torch for the accelerator, which starts the HIP runtime -- and opens the GPU -- in every rank)
     if world > 1:
-        dist.barrier()
+        dist.monitored_barrier()
     t0 = time.perf_counter()
     time.sleep(per_step_s * args.steps)
     if world > 1:
-        dist.barrier()
+        dist.monitored_barrier()
     elapsed = dp.reduce_scalar(time.perf_counter() - t0, "max", device=dev)
     mine = torch.tensor([hi - lo], dtype=torch.int64)
     shards = [torch.zeros_like(mine) for _ in range(world)]
@@ -1036,6 +1102,8 @@ def main():
     ap.add_argument("--no-gemm-roofline", action="store_true", help="skip the per-shape GEMM timing (use under rocprofv3 so that the trace holds decodes only)")
     ap.add_argument("--no-secondary", action="store_true", help="headline measurement only (no XE / RL / refinement lines)")
     ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU-oracle work per baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the timed path computed in its last step as "
+                    "DIR/<name>.npy (float32 / float64, at most 64 MB in all: a fixed, seeded sample of the rows of a larger array); the config says what went where")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(sys.argv[1:], args.gpus))
@@ -1066,7 +1134,7 @@ def main():
             print(json.dumps(res), flush=True)
         if world > 1:
             import torch.distributed as dist
-            dist.barrier()
+            dist.monitored_barrier()                            # (run_dry: no rank of the dry walk opens the GPU)
             dist.destroy_process_group()
         return
     if args.mode == "xe":
@@ -1086,19 +1154,19 @@ def main():
             if args.coalesce == 16 and args.steps >= 320:
                 raw["naic_steady_state"] = res                   # (the headline region IS the steady-state shape)
             else:
-                a = copy.copy(args); a.coalesce, a.steps, a.warmup, a.from_host = 16, 320, 64, False
+                a = copy.copy(args); a.coalesce, a.steps, a.warmup, a.from_host, a.dump_outputs = 16, 320, 64, False, None
                 raw["naic_steady_state"] = run_naic(a, ctx, log, False, False)
                 torch.cuda.empty_cache()
-            a = copy.copy(args); a.coalesce, a.steps, a.warmup = 1, 80, 16       # one batch of 64 per launch, 4 launches in flight (round-1 headline form)
+            a = copy.copy(args); a.coalesce, a.steps, a.warmup = 1, 80, 16; a.dump_outputs = None       # one batch of 64 per launch, 4 launches in flight (round-1 headline form)
             raw["naic_one_batch_per_launch"] = run_naic(a, ctx, log, False, False)
             torch.cuda.empty_cache()
-            a = copy.copy(args); a.mode, a.batch, a.steps, a.warmup = "xe", 64, 20, 5
+            a = copy.copy(args); a.mode, a.batch, a.steps, a.warmup = "xe", 64, 20, 5; a.dump_outputs = None
             raw["xe_config3"] = run_xe(a, ctx, log, cpu)
             torch.cuda.empty_cache()
-            a = copy.copy(args); a.mode, a.batch, a.steps, a.warmup = "rl", 10, 10, 3
+            a = copy.copy(args); a.mode, a.batch, a.steps, a.warmup = "rl", 10, 10, 3; a.dump_outputs = None
             raw["rl_config4"] = run_rl(a, ctx, log, cpu)
             torch.cuda.empty_cache()
-            a = copy.copy(args); a.batch, a.refine, a.steps, a.warmup, a.coalesce = 256, 3, 40, 8, 1
+            a = copy.copy(args); a.batch, a.refine, a.steps, a.warmup, a.coalesce = 256, 3, 40, 8, 1; a.dump_outputs = None
             raw["refine_config5"] = run_naic(a, ctx, log, cpu, False)
             _run_cpu_legs(log)                                   # (every GPU leg is through: now the CPU oracle's)
             sec = {k: _compact(v) for k, v in raw.items()}

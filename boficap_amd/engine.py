@@ -417,8 +417,7 @@ class DecodePipeline:
     eval_utils.py:456-460 under tools/eval.py:123).
 
       * ``in_flight`` engine forks on streams that provably overlap, one launch each (default 3: with the copy stream that is the runtime's four
-        hardware queues -- a copy stream that shares a queue with a launch stream: 161 against 210 k images/s, profiles/r05_decode_many.txt; 4 when the
-        process was started with GPU_MAX_HW_QUEUES >= 5).  Launch streams and the copy stream are found by probing for queues of their own;
+        hardware queues -- a copy stream that shares a queue with a launch stream: 161 against 210 k images/s, profiles/r05_decode_many.txt).  Launch streams and the copy stream are found by probing for queues of their own;
       * ``batches_per_launch`` (default 10) consecutive loader batches of one shape ride ONE launch (dynamic batching: quirk Q1 stays per batch, so every
         batch's result is its own decode's -- bit for bit under the same kernel family and hint); ragged batches (region counts given) are padded to the
         next of ``region_buckets`` so that differently clipped batches share launches and captured graphs (the padding is masked by the counts);
@@ -431,9 +430,8 @@ class DecodePipeline:
 
     def __init__(self, engine: "BofiEngine", *, in_flight: Optional[int] = None, batches_per_launch: int = 16, strict_q1: bool = True, stats: bool = True,
                  keep_logprob: bool = False, region_buckets=(36, 48, 64, 80, 100, 128)):
-        if in_flight is None:                                    # 3 launch streams + the copy stream = the runtime's default of 4 hardware queues; a process started
-            import os                                            # with GPU_MAX_HW_QUEUES >= 5 (tools/eval.py sets 8) has room for a fourth launch stream
-            in_flight = 4 if int(os.environ.get("GPU_MAX_HW_QUEUES", "4") or 4) >= 5 else 3
+        if in_flight is None:                                    # 3 launch streams + the copy stream = the runtime's default of 4 hardware queues
+            in_flight = 3
         if in_flight < 1 or batches_per_launch < 1:
             raise hip.BofiHipError("in_flight and batches_per_launch must be >= 1")
         self.root, self.nf, self.bpl = engine, int(in_flight), int(batches_per_launch)

@@ -480,9 +480,10 @@ class XETrainer:
                 self.ops.end_step()
 
     def _arm_dw_stream(self) -> None:
-        """Weight-gradient launches go beside the backward on a stream of their own, `dw_every` problems at a time (xe._DEFER)."""
+        """Weight-gradient launches go beside the backward on a stream of their own, `dw_every` problems at a time (xe._DEFER).  Eager steps
+        only: a captured step keeps them on the capture stream (see the forward's side streams in _forward_backward_armed)."""
         from . import xe
-        if self.dw_every > 0 and self.grouped_dw:
+        if self.dw_every > 0 and self.grouped_dw and not self._capturing():
             if self._dw_stream is None:
                 self._dw_stream = torch.cuda.Stream()
             xe._DEFER["side"], xe._DEFER["every"], xe._DEFER["held"] = self._dw_stream, self.dw_every, []
@@ -507,7 +508,11 @@ class XETrainer:
             if batch.get("row_cap") is not None:               # ... and run the decoder on those rows only
                 # add_token_rows pads the list to a multiple of 256: fewer than 256 rows at its end belong to no caption
                 xe.HINTS["unpadded"] = (batch["row_start"], batch["row_count"], batch["row_cap"], batch["row_pos"], 256)
-                if self._side is not None and xe._WEIGHTS["provider"] is not None and self.ops._tables and not self.ops._pending:
+                # (eager steps only: replaying a step captured with branches on side streams -- these, or the weight-gradient stream of
+                # _arm_dw_stream -- crashed the HIP runtime with a host-side segmentation fault inside the graph launch, though every dependency
+                # was recorded inside the capture; a captured step keeps its work on the capture stream: same results, no overlap)
+                xe.HINTS.pop("streams", None)
+                if self._side is not None and xe._WEIGHTS["provider"] is not None and self.ops._tables and not self.ops._pending and not self._capturing():
                     xe.HINTS["streams"] = self._side
         paired = compact and batch.get("row_cap") is not None and batch.get("pair_src") is not None
         if paired:
@@ -516,6 +521,7 @@ class XETrainer:
             if batch.get("prep_tok2") is not None and batch.get("att_masks") is None and glat_p < 0:
                 xe.HINTS["paired_inputs"] = {k[5:]: batch[k] for k in self._OPT_KEYS if k.startswith("prep_")}
             xe.HINTS.pop("streams", None)
+        forked = xe.HINTS.get("streams") is not None
         outs = self.model(fc, batch["att_feats"], batch["labels"], batch.get("att_masks"), batch["phrase_num"], batch["phrase_length"],
                           batch["phrase_syn"], batch["extend_phrase_syn_seq"], batch["extend_phrase_seq"], batch["extend_phrase_seq_mask"],
                           glat_p)
@@ -547,7 +553,7 @@ class XETrainer:
             loss, parts = xe.criterion_uic(outs, batch["phrase_num"], batch["phrase_length"], batch["phrase_syn"], batch["labels"],
                                            self_dis=self.self_dis)
         loss.backward()
-        if self._side is not None:
+        if forked:
             # the kernels accumulate parameter gradients themselves, so autograd sees no leaf on the side streams and does not
             # join them at the end of backward(): do it here (the optimiser, or the end of a graph capture, comes next)
             main = torch.cuda.current_stream()

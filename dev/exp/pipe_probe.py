@@ -3,7 +3,6 @@ decode j + NS on the stream's second engine fork.
     python dev/exp/pipe_probe.py [launch streams] [loop streams] [launches] [batches per launch]
 Prints images/s of (a) whole decodes, NS in flight (the bench's form) and (b) the pipelined form, same inputs, same engines' kernels."""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")               # (launch + side streams on hardware queues of their own: the runtime's default is 4)
 import torch
 sys.path.insert(0, ".")
 from boficap_amd import weights as W

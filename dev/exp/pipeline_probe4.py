@@ -1,7 +1,6 @@
 """DecodePipeline at 16-20 batches per launch: images/s with the features on the device, in pinned host memory, with and without the host-side results
-(stats / clones), 3 and 4 launches in flight (GPU_MAX_HW_QUEUES=8 set here: launch streams + the copy stream on queues of their own)."""
+(stats / clones), 3 and 4 launches in flight."""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import captioning.models as models

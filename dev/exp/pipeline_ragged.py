@@ -1,7 +1,6 @@
 """decode_many on ragged loader batches (region counts 10 .. 100 per image, every batch clipped to its longest image, masks given):
     python dev/exp/pipeline_ragged.py"""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

@@ -86,3 +86,26 @@ def test_bench_reruns_without_the_iteration_budget_when_a_decode_outruns_it():
     c = d["config"]
     assert c["knobs"].get("BOFI_BOUND_LOOP") == "0" and "five launches" in c["bound_loop"]
     assert c["bound_iterations"] > 3 and c["bound_iterations_enqueued"] == 20 and c["iteration_budget"].startswith("off") and not c["nan_in_output"]
+
+
+def test_bench_dump_outputs_of_the_last_step(tmp_path):
+    """--dump-outputs DIR: the last timed launch's outputs as float32 / float64 .npy files, 64 MB at most (the log-probs cut to a seeded sample of
+    images), batches in input order -- the same files whichever stream the last launch ran on (3 or 4 in flight under one kernel hint)."""
+    import numpy as np
+    flags = ("--steps", "10", "--warmup", "4", "--coalesce", "2", "--hint", "4", "--no-secondary", "--no-cpu-baseline", "--no-gemm-roofline", "--no-from-host")
+    runs = []
+    for nf in ("4", "3"):
+        out = tmp_path / f"inflight{nf}"
+        d = _run(*flags, "--inflight", nf, "--dump-outputs", str(out))
+        assert d["steps"] == 10 and d["ms_per_step"] > 0 and d["config"]["batches_per_launch"] == 2
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["bound_iters.npy", "phrase_length.npy", "phrase_num.npy", "phrase_syn.npy", "seq.npy", "seq_logprob.npy"], files
+        assert sum(p.stat().st_size for p in out.iterdir()) <= 64 * 10 ** 6
+        arrays = {f[:-4]: np.load(out / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert arrays["seq"].shape == (128, 20) and arrays["phrase_num"].shape == (128,)
+        rows = d["config"]["dump_outputs"]["sampled_rows"]["seq_logprob"]
+        assert arrays["seq_logprob"].shape == (len(rows), 20, 9491) and 0 < len(rows) < 128 and rows == sorted(rows)
+        runs.append(arrays)
+    for k in runs[0]:
+        assert np.array_equal(runs[0][k], runs[1][k], equal_nan=True), k

@@ -755,8 +755,8 @@ def test_decoder_over_unpadded_rows_matches_padded(weight_cache, manifest, dtype
 
 @pytest.mark.parametrize("graph", [False, True])
 def test_forward_branches_on_streams_leave_the_step_unchanged(weight_cache, manifest, graph):
-    """SA bound / SA fill / NA bound / NA fill on four HIP streams (forward and, through autograd, backward), eager and as
-    parallel branches of the captured step graph: same loss and gradients as the one-stream step, dropout on."""
+    """SA bound / SA fill / NA bound / NA fill on four HIP streams (forward and, through autograd, backward) in eager steps, and the
+    captured step of the same trainer (its branches on the capture stream): same loss and gradients as the one-stream step, dropout on."""
     from boficap_amd.collate import synthetic_training_batch
     from boficap_amd.trainer import XETrainer
     from boficap_amd.weights import synthetic_att_feats
@@ -789,7 +789,7 @@ def test_forward_branches_on_streams_leave_the_step_unchanged(weight_cache, mani
 def test_weight_gradients_beside_the_backward_leave_the_step_unchanged(weight_cache, manifest, graph):
     """XETrainer.dw_every: the grouped weight-gradient launches started during the backward on a side stream (a few problems at a
     time) against the two launches after the backward: same loss, same gradients up to the order of the float atomics, dropout on,
-    eager and as a forked branch of the captured step graph (two signatures, replays included)."""
+    eager and as the captured step graph, which keeps them on the capture stream (two signatures, replays included)."""
     from boficap_amd.collate import synthetic_training_batch
     from boficap_amd.trainer import XETrainer
     from boficap_amd.weights import synthetic_att_feats

@@ -17,8 +17,6 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-# (before the HIP runtime starts: the pipelined decode keeps 4 launch streams and a copy stream on hardware queues of their own; the runtime's default is 4 queues)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -41,7 +39,7 @@ def main():
                     "launch, features copied from pinned host memory ahead of the launches; 0: one synchronised mode='sample' call per batch as the reference's eval loop "
                     "(eval_utils.py:456-460)")
     ap.add_argument("--batches_per_launch", type=int, default=16)
-    ap.add_argument("--in_flight", type=int, default=4, help="launch streams (this script starts the runtime with 8 hardware queues: launch streams and the copy stream get one each)")
+    ap.add_argument("--in_flight", type=int, default=3, help="launch streams (3 launch streams + the copy stream = the runtime's default of 4 hardware queues)")
     args = ap.parse_args()
 
     import captioning.models as models
