@@ -1,0 +1,245 @@
+// CIDEr-D caption reward (the scorer of captioning/utils/rewards.py:86-131, CiderD of the pyciderevalcap package) on the device.
+//
+// Every row -- a reference caption or a sampled candidate -- becomes a record: its unique n-grams (n = 1..4) as sorted 64-bit keys,
+// their weights tf * (L - log(max(1, df))), the four per-order norms and the row's "length" (its number of bigrams, a quirk of the
+// package kept on purpose).  An n-gram's key packs (id + 1) into 16-bit fields, first token in the highest used field, so keys are
+// exact, and the keys of order k lie in [2^(16(k-1)), 2^(16k)): a sorted record is grouped by order.
+//
+// bofi_cider_refs builds the references' records into global memory (one workgroup per reference row); bofi_cider_score builds each
+// candidate's record in LDS (one workgroup per candidate) and scores it against the records of its image's references.  All
+// arithmetic is fp64; every reduction runs in a fixed order, so results are bit-identical run to run.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "bofi_common.h"
+#include "boficap_hip.h"
+
+namespace {
+
+constexpr int CIDER_ORDERS = 4;
+constexpr int CIDER_MAX_TOKENS = 64;          // 4 * 64 - 6 = 250 n-grams: fits a 256-thread record
+constexpr int CIDER_MAX_ID = 65534;           // (id + 1) must fit a 16-bit field
+constexpr uint64_t KEY_NONE = ~0ull;
+
+__host__ __device__ inline int ngram_count(int T) {
+    int c = 0;
+    for (int k = 1; k <= CIDER_ORDERS; ++k) c += T >= k ? T - k + 1 : 0;
+    return c;
+}
+
+// L - log(max(1, df(key))) from the sorted df table; an n-gram absent from it has df 0, i.e. the value L
+__device__ inline double df_value(uint64_t key, const uint64_t* df_keys, const double* df_vals, int n_df, double L) {
+    int lo = 0, hi = n_df;
+    while (lo < hi) {
+        int mid = (lo + hi) >> 1;
+        if (df_keys[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo < n_df && df_keys[lo] == key ? df_vals[lo] : L;
+}
+
+template <int NT>
+struct RecordLds {
+    uint64_t key[NT];
+    double w[NT];                 // tf on the way, then the weight
+    double part[NT];              // per-n-gram terms of a similarity
+    int scan[NT];
+    int tok[CIDER_MAX_TOKENS];
+    int off[CIDER_ORDERS + 1];    // first unique n-gram of each order; off[4] = number of unique n-grams
+    double norm[CIDER_ORDERS];
+    double length;
+    int T;
+    int bad;
+};
+
+// The record of the T tokens in r.tok (T set, tokens loaded, both visible to the block): sorted unique keys and their weights in
+// r.key / r.w [0, r.off[4]), norms and length.  Every loop is bounded by T or NT.
+template <int NT>
+__device__ void build_record(RecordLds<NT>& r, const uint64_t* df_keys, const double* df_vals, int n_df, double L) {
+    const int t = threadIdx.x;
+    const int T = r.T;
+    const int nG = ngram_count(T);
+    uint64_t key = KEY_NONE;
+    if (t < nG) {                                         // n-gram t: order k at position p
+        int i = t, k = 1;
+        while (k < CIDER_ORDERS && i >= T - k + 1) { i -= T - k + 1; ++k; }
+        key = 0;
+        for (int q = 0; q < k; ++q) key = (key << 16) | (uint64_t)(r.tok[i + q] + 1);
+    }
+    r.key[t] = key;
+    __syncthreads();
+    for (int k = 2; k <= NT; k <<= 1) {                   // bitonic sort, one key per thread
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            const int o = t ^ j;
+            if (o > t) {
+                const uint64_t a = r.key[t], b = r.key[o];
+                if ((a > b) == ((t & k) == 0)) { r.key[t] = b; r.key[o] = a; }
+            }
+            __syncthreads();
+        }
+    }
+    key = r.key[t];
+    const bool head = t < nG && (t == 0 || r.key[t - 1] != key);
+    int tf = 0;
+    if (head)
+        for (int q = t; q < nG && r.key[q] == key; ++q) ++tf;
+    r.scan[t] = head ? 1 : 0;
+    __syncthreads();
+    for (int d = 1; d < NT; d <<= 1) {                    // inclusive scan of the head flags
+        const int v = t >= d ? r.scan[t - d] : 0;
+        __syncthreads();
+        r.scan[t] += v;
+        __syncthreads();
+    }
+    const int nU = r.scan[NT - 1];
+    const int u = r.scan[t] - 1;
+    __syncthreads();                                      // every thread has read its key before the compaction overwrites them
+    if (head) {
+        r.key[u] = key;
+        r.w[u] = (double)tf * df_value(key, df_keys, df_vals, n_df, L);
+        r.part[u] = (double)tf;
+    }
+    __syncthreads();
+    if (t < CIDER_ORDERS) {                               // first unique n-gram of order t + 1 (keys are grouped by order)
+        const uint64_t lo = t == 0 ? 0ull : 1ull << (16 * t);
+        int q = 0;
+        while (q < nU && r.key[q] < lo) ++q;
+        r.off[t] = q;
+    }
+    if (t == CIDER_ORDERS) r.off[t] = nU;
+    __syncthreads();
+    if (t < CIDER_ORDERS) {
+        double s = 0.0;
+        for (int q = r.off[t]; q < r.off[t + 1]; ++q) s += r.w[q] * r.w[q];
+        r.norm[t] = sqrt(s);
+    }
+    if (t == CIDER_ORDERS) {
+        double len = 0.0;
+        for (int q = r.off[1]; q < r.off[2]; ++q) len += r.part[q];
+        r.length = len;
+    }
+    __syncthreads();
+}
+
+// record layout in global memory, per row: keys / weights [stride], off [5] (int), meta [5] = norms, length
+template <int NT>
+__global__ void __launch_bounds__(NT) cider_refs_kernel(const int* ref_tok, const int* ref_len, int width, const uint64_t* df_keys,
+                                                        const double* df_vals, int n_df, double L, uint64_t* rec_keys, double* rec_w,
+                                                        int* rec_off, double* rec_meta, int stride) {
+    __shared__ RecordLds<NT> r;
+    const int row = blockIdx.x, t = threadIdx.x;
+    if (t == 0) r.T = min(max(ref_len[row], 0), width);
+    __syncthreads();
+    if (t < r.T) r.tok[t] = ref_tok[(int64_t)row * width + t];
+    __syncthreads();
+    build_record<NT>(r, df_keys, df_vals, n_df, L);
+    const int nU = r.off[CIDER_ORDERS];
+    for (int q = t; q < stride; q += NT) {
+        rec_keys[(int64_t)row * stride + q] = q < nU ? r.key[q] : KEY_NONE;
+        rec_w[(int64_t)row * stride + q] = q < nU ? r.w[q] : 0.0;
+    }
+    if (t <= CIDER_ORDERS) rec_off[row * (CIDER_ORDERS + 1) + t] = r.off[t];
+    if (t < CIDER_ORDERS) rec_meta[row * (CIDER_ORDERS + 1) + t] = r.norm[t];
+    if (t == CIDER_ORDERS) rec_meta[row * (CIDER_ORDERS + 1) + t] = r.length;
+}
+
+template <int NT>
+__global__ void __launch_bounds__(NT) cider_score_kernel(const int64_t* seq, const int* cand_len, int S, int seq_per_img, const int* ref_start,
+                                                         const uint64_t* df_keys, const double* df_vals, int n_df, double L, double sigma,
+                                                         double weight, const uint64_t* rec_keys, const double* rec_w, const int* rec_off,
+                                                         const double* rec_meta, int stride, float* out, double* out64) {
+    __shared__ RecordLds<NT> r;
+    __shared__ double acc[CIDER_ORDERS];
+    const int j = blockIdx.x, t = threadIdx.x;
+    const int64_t* row = seq + (int64_t)j * S;
+    if (t == 0) {                                         // the token list: up to and including the first 0, else the whole row
+        int T = S, bad = 0;
+        if (cand_len) {
+            T = min(max(cand_len[j], 0), S);
+        } else {
+            for (int q = 0; q < S; ++q)
+                if (row[q] == 0) { T = q + 1; break; }
+        }
+        for (int q = 0; q < T; ++q) bad |= row[q] < 0 || row[q] > CIDER_MAX_ID;
+        r.T = T;
+        r.bad = bad;
+    }
+    if (t < CIDER_ORDERS) acc[t] = 0.0;
+    __syncthreads();
+    if (t < r.T) r.tok[t] = r.bad ? 0 : (int)row[t];
+    __syncthreads();
+    build_record<NT>(r, df_keys, df_vals, n_df, L);
+    const int img = j / seq_per_img;
+    const int r0 = ref_start[img], r1 = ref_start[img + 1];
+    const int nU = r.off[CIDER_ORDERS];
+    const double two_sigma2 = 2.0 * sigma * sigma;
+    for (int ref = r0; ref < r1; ++ref) {                 // the image's references in index order
+        const uint64_t* rk = rec_keys + (int64_t)ref * stride;
+        const double* rw = rec_w + (int64_t)ref * stride;
+        const int n_ref = rec_off[ref * (CIDER_ORDERS + 1) + CIDER_ORDERS];
+        if (t < nU) {                                     // min(w_h, w_r) * w_r; w_r = 0 where the reference lacks the n-gram
+            const uint64_t key = r.key[t];
+            int lo = 0, hi = n_ref;
+            while (lo < hi) {
+                int mid = (lo + hi) >> 1;
+                if (rk[mid] < key) lo = mid + 1; else hi = mid;
+            }
+            const double wr = lo < n_ref && rk[lo] == key ? rw[lo] : 0.0;
+            r.part[t] = fmin(r.w[t], wr) * wr;
+        }
+        __syncthreads();
+        if (t < CIDER_ORDERS) {
+            double val = 0.0;
+            for (int q = r.off[t]; q < r.off[t + 1]; ++q) val += r.part[q];
+            const double nr = rec_meta[ref * (CIDER_ORDERS + 1) + t];
+            if (r.norm[t] != 0.0 && nr != 0.0) val /= r.norm[t] * nr;
+            const double delta = r.length - rec_meta[ref * (CIDER_ORDERS + 1) + CIDER_ORDERS];
+            acc[t] += val * exp(-(delta * delta) / two_sigma2);
+        }
+        __syncthreads();
+    }
+    if (t == 0) {                                         // 10 * mean over the orders / number of references
+        double s = (acc[0] + acc[1] + acc[2] + acc[3]) / (double)CIDER_ORDERS;
+        s = s / (double)(r1 - r0) * 10.0;
+        if (r.bad) s = __builtin_nan("");                 // an id outside [0, 65534] has no key: the score says so
+        s *= weight;
+        out[j] = (float)s;
+        if (out64) out64[j] = s;
+    }
+}
+
+}  // namespace
+
+extern "C" int bofi_cider_refs(const int* ref_tok, const int* ref_len, int n_refs, int width, const uint64_t* df_keys, const double* df_vals,
+                               int n_df, double log_ref_len, uint64_t* rec_keys, double* rec_w, int* rec_off, double* rec_meta, int stride,
+                               void* stream) {
+    if (!ref_len || !rec_keys || !rec_w || !rec_off || !rec_meta || n_refs < 0 || width < 0 || width > CIDER_MAX_TOKENS || n_df < 0 ||
+        (n_df > 0 && (!df_keys || !df_vals)) || (width > 0 && !ref_tok) || (stride != 128 && stride != 256) || ngram_count(width) > stride)
+        return BOFI_ERR_ARG;
+    if (n_refs == 0) return BOFI_OK;
+    if (ngram_count(width) <= 128)
+        hipLaunchKernelGGL(cider_refs_kernel<128>, dim3(n_refs), dim3(128), 0, (hipStream_t)stream, ref_tok, ref_len, width, df_keys, df_vals, n_df,
+                           log_ref_len, rec_keys, rec_w, rec_off, rec_meta, stride);
+    else
+        hipLaunchKernelGGL(cider_refs_kernel<256>, dim3(n_refs), dim3(256), 0, (hipStream_t)stream, ref_tok, ref_len, width, df_keys, df_vals, n_df,
+                           log_ref_len, rec_keys, rec_w, rec_off, rec_meta, stride);
+    BOFI_CHECK_LAUNCH();
+    return BOFI_OK;
+}
+
+extern "C" int bofi_cider_score(const int64_t* seq, const int* cand_len, int N, int S, int seq_per_img, const int* ref_start, const uint64_t* df_keys,
+                                const double* df_vals, int n_df, double log_ref_len, double sigma, double weight, const uint64_t* rec_keys,
+                                const double* rec_w, const int* rec_off, const double* rec_meta, int stride, float* out, double* out64,
+                                void* stream) {
+    if (!seq || !ref_start || !rec_keys || !rec_w || !rec_off || !rec_meta || !out || N < 0 || S < 1 || S > CIDER_MAX_TOKENS || seq_per_img < 1 ||
+        N % seq_per_img != 0 || n_df < 0 || (n_df > 0 && (!df_keys || !df_vals)) || (stride != 128 && stride != 256) || !(sigma > 0.0))
+        return BOFI_ERR_ARG;
+    if (N == 0) return BOFI_OK;
+    if (ngram_count(S) <= 128)
+        hipLaunchKernelGGL(cider_score_kernel<128>, dim3(N), dim3(128), 0, (hipStream_t)stream, seq, cand_len, S, seq_per_img, ref_start, df_keys,
+                           df_vals, n_df, log_ref_len, sigma, weight, rec_keys, rec_w, rec_off, rec_meta, stride, out, out64);
+    else
+        hipLaunchKernelGGL(cider_score_kernel<256>, dim3(N), dim3(256), 0, (hipStream_t)stream, seq, cand_len, S, seq_per_img, ref_start, df_keys,
+                           df_vals, n_df, log_ref_len, sigma, weight, rec_keys, rec_w, rec_off, rec_meta, stride, out, out64);
+    BOFI_CHECK_LAUNCH();
+    return BOFI_OK;
+}

@@ -8,8 +8,8 @@ XE branch (struc_flag False): pinned to the reference by tests/golden/tiny_loss_
 around the reference model).  RL branch (struc_flag True): its loss arithmetic is pinned by tests/golden/tiny_rl_loss
 (StructureLosses 'new_self_critical' and the rl_kl term with injected samples and scores) and tests/golden/tiny_structure_losses (the other
 structure_loss_types); the caption scorer itself
-(``get_scores``: CIDEr-D / BLEU of the external ``cider`` and ``coco-caption`` packages, captioning/utils/rewards.py:86-131) is
-not part of this build -- pass ``opt.bofi_score_fn(gts, seq) -> [N] floats`` or install one with ``set_scorer``.
+(``get_scores``, captioning/utils/rewards.py:86-131) is ``opt.bofi_score_fn(gts, seq) -> [N] floats`` or one installed with ``set_scorer`` if
+given, else the device CIDEr-D scorer of ``opt.cached_tokens`` (boficap_amd.cider; the BLEU term is not built).
 
 RL branch, the estimator (round 6): the reference samples with the autograd tape running (and dropout active) and
 differentiates that same pass (loss_wrapper.py:193-209).  In train mode this class does the same by default, as ``XETrainer.rl_step`` does
@@ -22,6 +22,8 @@ coincide (no dropout anywhere) and the fast form runs.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 
 from . import hip, xe
@@ -33,6 +35,25 @@ def set_scorer(fn) -> None:
     """Install the caption scorer of the RL branch: ``fn(data_gts, gen_result int64 [N, S] on the host) -> [N]`` floats
     (the role of get_scores, captioning/utils/rewards.py:86-131)."""
     _SCORER["fn"] = fn
+
+
+_DEVICE_SCORER: dict = {}
+
+
+def device_scorer(opt):
+    """The CIDEr-D scorer of ``opt.cached_tokens`` (boficap_amd.cider.CiderD), built once per df file as init_scorer does (rewards.py:25-31).
+    Raises where the reference's get_scores would need a scorer this build lacks: the BLEU term, or no df file."""
+    from . import cider
+    if float(getattr(opt, "bleu_reward_weight", 0) or 0) > 0:
+        raise NotImplementedError("the BLEU reward term is not built (bleu_reward_weight 0 in the shipped configs)")
+    path = cider.resolve_df(getattr(opt, "cached_tokens", "coco-train-idxs"))
+    if path is None or not float(getattr(opt, "cider_reward_weight", 1)) > 0:
+        raise hip.BofiHipError("no caption scorer: no document-frequency file for opt.cached_tokens (data/<cached_tokens>.p of scripts/prepro_ngrams.py) "
+                               "and no scorer installed; pass opt.bofi_score_fn or call boficap_amd.loss_wrapper.set_scorer")
+    key = (os.path.abspath(path) if path != "corpus" else path, torch.cuda.current_device())
+    if key not in _DEVICE_SCORER:
+        _DEVICE_SCORER[key] = cider.CiderD(df=path)
+    return _DEVICE_SCORER[key]
 
 
 def reference_estimator_pass(model, att_feats, att_masks, sample_n: int, temperature: float, seed: int):
@@ -133,10 +154,10 @@ class StructureLosses(torch.nn.Module):
         n = input.size(0) // len(data_gts)
         assert n == self.opt.train_sample_n, n                   # losses.py:45
         fn = getattr(self.opt, "bofi_score_fn", None) or _SCORER["fn"]
-        if fn is None:
-            raise hip.BofiHipError("no caption scorer: the reference's CIDEr-D scorer is an external package (captioning/utils/rewards.py:163-170); "
-                                   "pass opt.bofi_score_fn or call boficap_amd.loss_wrapper.set_scorer")
-        scores = fn(data_gts, seq.detach().cpu())
+        if fn is None:                                            # get_scores (rewards.py:86-131) on the device: CIDEr-D of the df file opt.cached_tokens
+            scores = device_scorer(self.opt).score(data_gts, seq.detach(), n, weight=float(getattr(self.opt, "cider_reward_weight", 1)))
+        else:
+            scores = fn(data_gts, seq.detach().cpu())
         loss, reward = xe.structure_loss(self.loss_type, input, seq, scores, n, reduction=reduction,
                                          entropy_reward_weight=float(getattr(self.opt, "entropy_reward_weight", 0) or 0))
         return {"loss": loss, "reward": reward}

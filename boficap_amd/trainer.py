@@ -752,7 +752,8 @@ class XETrainer:
     def rl_step(self, att_feats, att_masks, score_fn, *, sample_n: int = 5, temperature: float = 1.0):
         """One self-critical step of a UIC model: sample ``sample_n`` captions per image in SAIC and in NAIC mode on the decode
         engine (no tape), score them with ``score_fn(seq int64 [N, S] on the host) -> [N] floats`` (the external CIDEr-D scorer of
-        captioning/utils/rewards.py in the reference), recompute the samples' log-probs with the tape
+        captioning/utils/rewards.py in the reference) -- or, if ``score_fn.on_device`` (boficap_amd.cider.CiderD.bind), with the device ids
+        and a device tensor back -- recompute the samples' log-probs with the tape
         (``xe.sampled_logprobs``), loss = new_self_critical(SAIC) + new_self_critical(NAIC), backward, all-reduce, Adam.
         Returns (loss, mean SAIC score, mean NAIC score)."""
         from . import xe
@@ -782,23 +783,24 @@ class XETrainer:
         # the scorer and the collate of the sampled layouts run on the host.  The non-autoregressive samples' part of it goes first, on the
         # pinned copies sample_pair left behind an event on its side stream: it runs while the (much longer) semi-autoregressive decode does
         early = getattr(model, "_naic_ready", None) if getattr(model.opt, "bofi_rl_sample_pair", True) and os.environ.get("BOFI_RL_EARLY_NAIC", "1") != "0" else None
+        on_device = getattr(score_fn, "on_device", False)     # a device scorer (boficap_amd.cider) takes the sampled ids where they are
         prep = {}
         if early is not None:
             model._naic_ready = None
             early[0].synchronize()
             naic_host = early[1]
-            seq_n = naic_host["seq"]
+            seq_n = naic["seq"] if on_device else naic_host["seq"]
             s_naic = score_fn(seq_n)
             prep.update(xe.rl_prepare(model.cfg, None, naic_host, sample_n=sample_n, strict_q1=model.strict_reference, device=dev))
         else:
-            seq_n = naic["seq"].cpu()
+            seq_n = naic["seq"] if on_device else naic["seq"].cpu()
             s_naic = score_fn(seq_n)
             prep.update(xe.rl_prepare(model.cfg, None, naic, sample_n=sample_n, strict_q1=model.strict_reference, device=dev))
         if "_capped" in saic or getattr(model.opt, "bofi_rl_sample_pair", True):
             saic = model.saic_finish(saic) if "bound_iters" in saic else saic
         if saic["seq"].is_cuda:                                # the semi-autoregressive samples' collate: one launch on the device, issued before the host waits for the ids
             prep.update(xe.rl_prepare_saic_device(model.cfg, saic["seq"].long(), saic["phrase_length"], saic["phrase_syn"]))
-        seq_s = saic["seq"].cpu()
+        seq_s = saic["seq"] if on_device else saic["seq"].cpu()
         s_saic = score_fn(seq_s)
         if not saic["seq"].is_cuda:
             prep.update(xe.rl_prepare(model.cfg, saic, None, sample_n=sample_n, strict_q1=model.strict_reference, device=dev))
@@ -941,7 +943,10 @@ class XETrainer:
                     if it == 1:
                         draw(lp_n, na_plen, 0, S, seq_n, drawn_n, None)                    # every laid-out position of the non-autoregressive branch
             saic = {"seq": seq_s, "phrase_length": out["phrase_length"], "phrase_syn": out["phrase_syn"]}
-            s_saic, s_naic = score_fn(seq_s.cpu()), score_fn(seq_n.cpu())
+            if getattr(score_fn, "on_device", False):                    # a device scorer (boficap_amd.cider): the ids stay where they were drawn
+                s_saic, s_naic = score_fn(seq_s), score_fn(seq_n)
+            else:
+                s_saic, s_naic = score_fn(seq_s.cpu()), score_fn(seq_n.cpu())
             prep = xe.rl_prepare_saic_device(cfg, seq_s, out["phrase_length"], out["phrase_syn"])
             prep.update(prep_na)
             sc_s = torch.as_tensor(s_saic, dtype=torch.float32).to(dev)

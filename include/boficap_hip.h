@@ -530,6 +530,29 @@ double bofi_gemm_flops(int reset, double* skippable);
 int bofi_engine_fill_naic(bofi_engine_t* e, const int* ext_syn, const int* last, int B, int R, const int* att_len, int flags,
                           int64_t* seq, float* seq_logprob, void* stream);
 
+/* CIDEr-D reward of the self-critical step (get_scores, captioning/utils/rewards.py:86-131, with the CiderD scorer of the
+ * pyciderevalcap package), in fp64.  A row's token list is its ids up to and including the first 0, or the whole row if it has
+ * none (array_to_str, rewards.py:33-39); ids lie in [0, 65534].  An n-gram (n = 1..4) is keyed by its ids packed as (id + 1) into
+ * 16-bit fields of a uint64, first token in the highest used field.  df_keys uint64 [n_df] sorted ascending, unique; df_vals
+ * double [n_df] = L - log(max(1, df)); an n-gram absent from the table takes the value L = log_ref_len.
+ *
+ * bofi_cider_refs: the records of n_refs reference rows.  ref_tok int32 [n_refs, width] (width <= 64), ref_len int32 [n_refs] =
+ * each row's token count (the first-0 rule applied by the caller).  Record of row r: rec_keys [r, stride] its sorted unique
+ * n-grams (unused tail = ~0), rec_w [r, stride] their weights tf * value, rec_off int32 [r, 5] the first n-gram of each order
+ * and the count, rec_meta double [r, 5] the four norms and the length (number of bigrams).  stride 128 or 256, >= the n-grams
+ * of a width-token row.
+ *
+ * bofi_cider_score: out float32 [N] (and out64 double [N] unless NULL) = weight * CIDEr-D of candidate j = row j of seq int64
+ * [N, S] (S <= 64) against the references ref_start[j / seq_per_img] .. ref_start[j / seq_per_img + 1] - 1 (ref_start int32
+ * [N / seq_per_img + 1], every image with at least one reference), the records of bofi_cider_refs on the same stream.
+ * cand_len int32 [N] or NULL: the candidates' token counts instead of the first-0 rule.  A candidate with an id outside
+ * [0, 65534] scores NaN.  Length penalty exp(-(len_h - len_r)^2 / (2 sigma^2)).  Deterministic: a fixed summation order. */
+int bofi_cider_refs(const int* ref_tok, const int* ref_len, int n_refs, int width, const uint64_t* df_keys, const double* df_vals, int n_df,
+                    double log_ref_len, uint64_t* rec_keys, double* rec_w, int* rec_off, double* rec_meta, int stride, void* stream);
+int bofi_cider_score(const int64_t* seq, const int* cand_len, int N, int S, int seq_per_img, const int* ref_start, const uint64_t* df_keys,
+                     const double* df_vals, int n_df, double log_ref_len, double sigma, double weight, const uint64_t* rec_keys,
+                     const double* rec_w, const int* rec_off, const double* rec_meta, int stride, float* out, double* out64, void* stream);
+
 /* Last HIP error string seen by this library on the calling thread (for exceptions in the host). */
 const char* bofi_last_error(void);
 

@@ -13,8 +13,9 @@ build: batches are synthetic captions in the loader's layout (b
 ``--input_label_h5`` -- real captions from the preprocessing's label file (boficap_amd/data.py; region features stay synthetic,
 the feature directories being outside this build).  ``--cfg`` reads the reference's yml files including their ``_BASE_``
 inheritance (captioning/utils/config.py:35-95).  ``--self_critical_after N`` switches to the self-critical step (loss_wrapper.py:181-230,
-``structure_loss_weight: 1``) from iteration N on, scored by ``boficap_amd.loss_wrapper``'s installed scorer or, without one, by
-token overlap with the ground-truth captions (the reference's CIDEr-D scorer is an external package).
+``structure_loss_weight: 1``) from iteration N on, scored by ``boficap_amd.loss_wrapper``'s installed scorer or, without one, by CIDEr-D
+on the device (boficap_amd.cider) with the document frequencies of ``--cached_tokens`` / the cfg's ``cached_tokens`` (data/<name>.p of
+scripts/prepro_ngrams.py, as the reference resolves it); with no such file, by token overlap with the ground-truth captions.
 Checkpoints are the reference's files (captioning/utils/misc.py:87-102): ``model.pth`` (311-entry state_dict), ``optimizer.pth``
 (NoamOpt / torch Adam layout), ``infos_<id>.pkl``, ``histories_<id>.pkl``; ``--start_from`` resumes from either code base's directory.
 """
@@ -49,6 +50,8 @@ def main():
     ap.add_argument("--input_label_h5", default="", help="label file of scripts/prepro_labels_stanford.py (captions and phrase cuts); needs h5py")
     ap.add_argument("--self_critical_after", type=int, default=-1, help="iteration from which the self-critical step replaces the XE step (-1: never)")
     ap.add_argument("--train_sample_n", type=int, default=5)
+    ap.add_argument("--cached_tokens", default=None, help="document-frequency pickle of the CIDEr-D reward (scripts/prepro_ngrams.py): a path, or a name "
+                    "for data/<name>.p (opts.py: coco-train-idxs); without such a file the self-critical step scores with a token-overlap stand-in")
     ap.add_argument("--scheduled_sampling_start", type=int, default=None, help="epoch from which ss_prob rises (opts.py:153-160; -1: never, the shipped configs)")
     ap.add_argument("--drop_worst_after", type=int, default=None, help="epoch from which a step keeps the best (1 - drop_worst_rate) captions (opts.py:165-168, "
                     "tools/train.py:186-189, 216-220; -1: never, the shipped configs)")
@@ -106,6 +109,19 @@ def main():
 
     import numpy as np
     from boficap_amd import loss_wrapper as LW
+    cider = None
+    if args.self_critical_after >= 0:
+        from boficap_amd.cider import CiderD, resolve_df
+        if args.cached_tokens is not None:
+            opt.cached_tokens = args.cached_tokens
+        df = resolve_df(getattr(opt, "cached_tokens", "coco-train-idxs"))
+        if df is not None:
+            if float(getattr(opt, "bleu_reward_weight", 0) or 0) > 0:
+                raise NotImplementedError("the BLEU reward term is not built (bleu_reward_weight 0 in the shipped configs)")
+            cider = CiderD(df=df, device=dev)
+        if rank == 0:
+            print(f"self-critical reward: {'CIDEr-D, document frequencies of ' + df if cider is not None else 'token-overlap stand-in (no cached_tokens file)'}",
+                  flush=True)
     t0, first = time.time(), trainer._step
     for it in range(first, first + args.max_iters):
         # a different shard per rank and step (the loader's role, dataloader.py:550-556)
@@ -137,6 +153,8 @@ def main():
                     toks = set(int(t) for t in s_ if t > 0)
                     out[i] = max((len(toks & set(int(t) for t in r if t > 0)) / max(1, len(toks)) for r in np.asarray(refs[i // n])), default=0.0)
                 return out
+            if LW._SCORER["fn"] is None and cider is not None:   # get_scores (rewards.py:86-131): CIDEr-D of opt.cached_tokens, on the device
+                score = cider.bind(refs, n, weight=float(getattr(opt, "cider_reward_weight", 1)))
             loss, rs, rn = trainer.rl_step(att, None, score, sample_n=n)
             if (it + 1) % args.losses_log_every == 0 or it == first:
                 if rank == 0:
