@@ -108,6 +108,9 @@ SIGNATURES = {
     "bofi_attn_out_ffn_block": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
     "bofi_cider_refs": (_I, [_P, _P, _I, _I, _P, _P, _I, C.c_double, _P, _P, _P, _P, _I, _P]),
     "bofi_cider_score": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "bofi_reward_refs": (_I, [_P, _P, _I, _I, _P, _P, _I, C.c_double, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "bofi_reward_score": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, _I,
+                               _P, _P, _P, _P]),
 }
 
 _lib = None

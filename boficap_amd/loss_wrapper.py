@@ -9,7 +9,8 @@ around the reference model).  RL branch (struc_flag True): its loss arithmetic i
 (StructureLosses 'new_self_critical' and the rl_kl term with injected samples and scores) and tests/golden/tiny_structure_losses (the other
 structure_loss_types); the caption scorer itself
 (``get_scores``, captioning/utils/rewards.py:86-131) is ``opt.bofi_score_fn(gts, seq) -> [N] floats`` or one installed with ``set_scorer`` if
-given, else the device CIDEr-D scorer of ``opt.cached_tokens`` (boficap_amd.cider; the BLEU term is not built).
+given, else the device scorer of ``device_scorer``: CIDEr-D of ``opt.cached_tokens`` (boficap_amd.cider), and with ``opt.bleu_reward_weight`` > 0
+the weighted sum with BLEU-4 (boficap_amd.rewards; the self-CIDEr term is not built).
 
 RL branch, the estimator (round 6): the reference samples with the autograd tape running (and dropout active) and
 differentiates that same pass (loss_wrapper.py:193-209).  In train mode this class does the same by default, as ``XETrainer.rl_step`` does
@@ -26,7 +27,7 @@ import os
 
 import torch
 
-from . import hip, xe
+from . import cider, hip, xe
 
 _SCORER = {"fn": None}
 
@@ -41,13 +42,24 @@ _DEVICE_SCORER: dict = {}
 
 
 def device_scorer(opt):
-    """The CIDEr-D scorer of ``opt.cached_tokens`` (boficap_amd.cider.CiderD), built once per df file as init_scorer does (rewards.py:25-31).
-    Raises where the reference's get_scores would need a scorer this build lacks: the BLEU term, or no df file."""
-    from . import cider
-    if float(getattr(opt, "bleu_reward_weight", 0) or 0) > 0:
-        raise NotImplementedError("the BLEU reward term is not built (bleu_reward_weight 0 in the shipped configs)")
+    """The device scorer of get_scores (rewards.py:86-131) for ``opt``, built once per df file and weights as init_scorer does (rewards.py:25-31):
+    with ``bleu_reward_weight`` 0 the CIDEr-D scorer of ``opt.cached_tokens`` (boficap_amd.cider.CiderD, weighted at the call), else the
+    combined cider_reward_weight * CIDEr-D + bleu_reward_weight * BLEU-4 (boficap_amd.rewards.RewardScorer, weights inside; a df file is
+    needed only if cider_reward_weight > 0).  Raises where no scorer can be built: no df file for a CIDEr-D term, or neither weight > 0."""
+    bw = float(getattr(opt, "bleu_reward_weight", 0) or 0)
+    cw = float(getattr(opt, "cider_reward_weight", 1))
     path = cider.resolve_df(getattr(opt, "cached_tokens", "coco-train-idxs"))
-    if path is None or not float(getattr(opt, "cider_reward_weight", 1)) > 0:
+    if bw > 0:
+        from .rewards import RewardScorer
+        if cw > 0 and path is None:
+            raise hip.BofiHipError("no caption scorer: the CIDEr-D term needs a document-frequency file for opt.cached_tokens (data/<cached_tokens>.p "
+                                   "of scripts/prepro_ngrams.py); pass opt.bofi_score_fn or call boficap_amd.loss_wrapper.set_scorer")
+        path = path if cw > 0 else None
+        key = ("reward", os.path.abspath(path) if path not in (None, "corpus") else path, cw, bw, torch.cuda.current_device())
+        if key not in _DEVICE_SCORER:
+            _DEVICE_SCORER[key] = RewardScorer(df=path, cider_weight=cw, bleu_weight=bw)
+        return _DEVICE_SCORER[key]
+    if path is None or not cw > 0:
         raise hip.BofiHipError("no caption scorer: no document-frequency file for opt.cached_tokens (data/<cached_tokens>.p of scripts/prepro_ngrams.py) "
                                "and no scorer installed; pass opt.bofi_score_fn or call boficap_amd.loss_wrapper.set_scorer")
     key = (os.path.abspath(path) if path != "corpus" else path, torch.cuda.current_device())
@@ -155,7 +167,11 @@ class StructureLosses(torch.nn.Module):
         assert n == self.opt.train_sample_n, n                   # losses.py:45
         fn = getattr(self.opt, "bofi_score_fn", None) or _SCORER["fn"]
         if fn is None:                                            # get_scores (rewards.py:86-131) on the device: CIDEr-D of the df file opt.cached_tokens
-            scores = device_scorer(self.opt).score(data_gts, seq.detach(), n, weight=float(getattr(self.opt, "cider_reward_weight", 1)))
+            sc = device_scorer(self.opt)                          # (+ BLEU-4 with bleu_reward_weight > 0: the weights live in that scorer)
+            if isinstance(sc, cider.CiderD):
+                scores = sc.score(data_gts, seq.detach(), n, weight=float(getattr(self.opt, "cider_reward_weight", 1)))
+            else:
+                scores = sc.score(data_gts, seq.detach(), n)
         else:
             scores = fn(data_gts, seq.detach().cpu())
         loss, reward = xe.structure_loss(self.loss_type, input, seq, scores, n, reduction=reduction,

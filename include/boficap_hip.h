@@ -553,6 +553,28 @@ int bofi_cider_score(const int64_t* seq, const int* cand_len, int N, int S, int 
                      const double* df_vals, int n_df, double log_ref_len, double sigma, double weight, const uint64_t* rec_keys,
                      const double* rec_w, const int* rec_off, const double* rec_meta, int stride, float* out, double* out64, void* stream);
 
+/* The whole reward of get_scores: cider_weight * CIDEr-D + bleu_weight * BLEU-4 (the Bleu(4) scorer of the pycocoevalcap package,
+ * option 'closest'), in fp64, on the token lists, keys and df table of the CIDEr-D pair above.
+ *
+ * bofi_reward_refs: the records of bofi_cider_refs, and with them rec_cnt int32 [n_refs, stride] (each unique n-gram's raw count,
+ * 0 in the unused tail) and rec_len int32 [n_refs] (each row's token count).  rec_cnt and rec_len are both given or both NULL.
+ *
+ * bofi_reward_score: out float32 [N] (and out64 double [N] unless NULL) = cider_weight * CIDEr-D + bleu_weight * BLEU-4 of candidate j
+ * against its image's references (seq, cand_len, ref_start, sigma as for bofi_cider_score), the records of bofi_reward_refs on the same
+ * stream.  BLEU-4 with T candidate tokens: correct[k] = sum over the candidate's unique (k+1)-grams of min(count, max over the references
+ * of their count), guess[k] = max(0, T - k), reflen = the reference length closest to T (a tie goes to the shorter); b = product over
+ * orders <= k of (correct + 1e-15) / (guess + 1e-9), BLEU-(k+1) = b^(1/(k+1)), times exp(1 - 1/ratio) if ratio = (T + 1e-15) / (reflen
+ * + 1e-9) < 1.  comps int32 [N, 10] or NULL: (T, reflen, guess[4], correct[4]) of every candidate, for a corpus score.
+ * cider_weight 0 skips the CIDEr-D work (n_df may be 0); with bleu_weight 0 the value is bofi_cider_score's, bit for bit.  A candidate
+ * with an id outside [0, 65534] scores NaN.  Deterministic: a fixed summation order. */
+int bofi_reward_refs(const int* ref_tok, const int* ref_len, int n_refs, int width, const uint64_t* df_keys, const double* df_vals, int n_df,
+                     double log_ref_len, uint64_t* rec_keys, double* rec_w, int* rec_off, double* rec_meta, int* rec_cnt, int* rec_len, int stride,
+                     void* stream);
+int bofi_reward_score(const int64_t* seq, const int* cand_len, int N, int S, int seq_per_img, const int* ref_start, const uint64_t* df_keys,
+                      const double* df_vals, int n_df, double log_ref_len, double sigma, double cider_weight, double bleu_weight,
+                      const uint64_t* rec_keys, const double* rec_w, const int* rec_off, const double* rec_meta, const int* rec_cnt,
+                      const int* rec_len, int stride, float* out, double* out64, int* comps, void* stream);
+
 /* Last HIP error string seen by this library on the calling thread (for exceptions in the host). */
 const char* bofi_last_error(void);
 

@@ -15,7 +15,8 @@ the feature directories being outside this build).  ``--cfg`` reads the referenc
 inheritance (captioning/utils/config.py:35-95).  ``--self_critical_after N`` switches to the self-critical step (loss_wrapper.py:181-230,
 ``structure_loss_weight: 1``) from iteration N on, scored by ``boficap_amd.loss_wrapper``'s installed scorer or, without one, by CIDEr-D
 on the device (boficap_amd.cider) with the document frequencies of ``--cached_tokens`` / the cfg's ``cached_tokens`` (data/<name>.p of
-scripts/prepro_ngrams.py, as the reference resolves it); with no such file, by token overlap with the ground-truth captions.
+scripts/prepro_ngrams.py, as the reference resolves it), plus BLEU-4 (boficap_amd.rewards) with the cfg's ``bleu_reward_weight`` > 0 (no
+df file needed when ``cider_reward_weight`` is 0); with no such file for a CIDEr-D term, by token overlap with the ground-truth captions.
 Checkpoints are the reference's files (captioning/utils/misc.py:87-102): ``model.pth`` (311-entry state_dict), ``optimizer.pth``
 (NoamOpt / torch Adam layout), ``infos_<id>.pkl``, ``histories_<id>.pkl``; ``--start_from`` resumes from either code base's directory.
 """
@@ -109,19 +110,24 @@ def main():
 
     import numpy as np
     from boficap_amd import loss_wrapper as LW
-    cider = None
+    scorer = None
     if args.self_critical_after >= 0:
         from boficap_amd.cider import CiderD, resolve_df
         if args.cached_tokens is not None:
             opt.cached_tokens = args.cached_tokens
         df = resolve_df(getattr(opt, "cached_tokens", "coco-train-idxs"))
-        if df is not None:
-            if float(getattr(opt, "bleu_reward_weight", 0) or 0) > 0:
-                raise NotImplementedError("the BLEU reward term is not built (bleu_reward_weight 0 in the shipped configs)")
-            cider = CiderD(df=df, device=dev)
+        cw, bw = float(getattr(opt, "cider_reward_weight", 1)), float(getattr(opt, "bleu_reward_weight", 0) or 0)
+        if bw > 0 and (df is not None or not cw > 0):          # get_scores' two terms in one scorer, its weights inside
+            from boficap_amd.rewards import RewardScorer
+            scorer = RewardScorer(df=df if cw > 0 else None, cider_weight=cw, bleu_weight=bw, device=dev)
+            what = f"{cw:g} x CIDEr-D (document frequencies of {df}) + {bw:g} x BLEU-4" if cw > 0 else f"{bw:g} x BLEU-4"
+        elif not bw > 0 and df is not None:
+            scorer = CiderD(df=df, device=dev)
+            what = "CIDEr-D, document frequencies of " + df
+        else:
+            what = "token-overlap stand-in (no cached_tokens file)"
         if rank == 0:
-            print(f"self-critical reward: {'CIDEr-D, document frequencies of ' + df if cider is not None else 'token-overlap stand-in (no cached_tokens file)'}",
-                  flush=True)
+            print(f"self-critical reward: {what}", flush=True)
     t0, first = time.time(), trainer._step
     for it in range(first, first + args.max_iters):
         # a different shard per rank and step (the loader's role, dataloader.py:550-556)
@@ -153,8 +159,8 @@ def main():
                     toks = set(int(t) for t in s_ if t > 0)
                     out[i] = max((len(toks & set(int(t) for t in r if t > 0)) / max(1, len(toks)) for r in np.asarray(refs[i // n])), default=0.0)
                 return out
-            if LW._SCORER["fn"] is None and cider is not None:   # get_scores (rewards.py:86-131): CIDEr-D of opt.cached_tokens, on the device
-                score = cider.bind(refs, n, weight=float(getattr(opt, "cider_reward_weight", 1)))
+            if LW._SCORER["fn"] is None and scorer is not None:  # get_scores (rewards.py:86-131) on the device
+                score = scorer.bind(refs, n, weight=cw) if isinstance(scorer, CiderD) else scorer.bind(refs, n)
             loss, rs, rn = trainer.rl_step(att, None, score, sample_n=n)
             if (it + 1) % args.losses_log_every == 0 or it == first:
                 if rank == 0:
