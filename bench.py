@@ -8,14 +8,19 @@ the reference's ``_sample`` returns them.  One process per GPU; images shard acr
 collective (weak scaling: every rank decodes its own 64-image batch per step).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--dtype bf16|f32]
-                    [--ids-only] [--no-graph] [--no-cpu-baseline] [--dump-outputs DIR]
+                    [--ids-only] [--no-graph] [--dump-outputs DIR] [--full [--no-cpu-baseline] ...]
 
-Prints ONE JSON line on rank 0 (contract in the task brief): metric/value/unit, roofline (MFMA
-bound, algorithmic FLOPs of SURVEY.md §8d over the HIP-event time of the decode launches) and
-cpu_baseline (the CPU oracle timed on this host's cores, bounded sample).  At N = 1 the line also
-carries ``secondary``: short driver-run measurements of the other BASELINE configurations -- XE step
-64 x 5 bf16 (config 3), self-critical step 10 x 5 (config 4), batch 256 with 3 refinement rounds
-(config 5) -- each with a roofline on EXECUTED GEMM FLOPs and a cpu_baseline.
+Prints ONE JSON line on rank 0 (contract in the task brief): metric/value/unit and roofline (MFMA
+bound, algorithmic FLOPs of SURVEY.md §8d over the HIP-event time of the decode launches).  A plain
+run does only that: set up, warm up, time the K steps, write --dump-outputs, print the line.
+
+``--full`` adds every measurement that takes runs of its own, after the timed steps: cpu_baseline
+(the CPU oracle timed on this host's cores, bounded sample), roofline_gemm (per-shape GEMM timings),
+roofline.one_at_a_time, the PCIe-inclusive rate from pinned host memory, the self-critical step's
+fast-estimator leg, and ``secondary``: at N = 1 short measurements of the other BASELINE
+configurations -- XE step 64 x 5 bf16 (config 3), self-critical step 10 x 5 (config 4), batch 256
+with 3 refinement rounds (config 5) -- each with a roofline on EXECUTED GEMM FLOPs and a
+cpu_baseline; at N > 1 the XE step's real gradient exchange.  The ``--no-*`` switches trim --full.
 
 ``--gpus N`` without a torchrun environment starts its own N ranks (children spawned before this
 process touches the GPU) and relays rank 0's line.
@@ -26,6 +31,7 @@ import os
 import sys
 import time
 
+T_START = time.perf_counter()     # (the log lines say how long the process has run: where a run's set-up time goes)
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
@@ -580,25 +586,27 @@ def run_rl(args, ctx, log, cpu=True):
         dumped = dump_outputs(args.dump_outputs, {"loss": loss, "reward_saic": rs, "reward_naic": rn, "parameters_sample": _parameter_sample(model)}, log)
     last_default = dict(tr._last_rl)
     ref_info = {"drawn_rows_vs_gradient_pass_rows_max_abs": last_default.get("reference_gap"), "training_forwards_per_step": last_default.get("training_forwards")}
-    # the fast form of rounds 1-4 beside it (opt.bofi_rl_reference_estimator = False: samples from the dropout-free inference engine, ONE gradient pass with
-    # dropout, replayed as a hipGraph): a few steps
-    try:                                                       # (a failure of this leg must not lose the headline line: it is reported beside it)
-        model.opt.bofi_rl_reference_estimator = False
-        for _ in range(3):
-            tr.rl_step(att, None, score, sample_n=n)
-        torch.cuda.synchronize(dev)
-        t1 = time.perf_counter()
-        for _ in range(10):
-            tr.rl_step(att, None, score, sample_n=n)
-        torch.cuda.synchronize(dev)
-        fast_info = {"ms_per_step": round((time.perf_counter() - t1) / 10 * 1e3, 2),
-                     "what": "samples from the inference engine (no dropout), one gradient pass with dropout as a hipGraph: an importance-weight log-std of ~0.65 per caption "
-                             "against the reference's estimator (dev/exp/rl_dropout_gap.py)"}
-    except Exception as e:
-        log(f"rl: the fast-estimator leg failed: {type(e).__name__}: {e}")
-        fast_info = {"error": f"{type(e).__name__}: {e}"}
-    del model.opt.bofi_rl_reference_estimator
-    tr._last_rl = last_default
+    # --full: the fast form of rounds 1-4 beside it (opt.bofi_rl_reference_estimator = False: samples from the dropout-free inference engine, ONE gradient
+    # pass with dropout, replayed as a hipGraph): a few steps
+    fast_info = None
+    if args.full:
+        try:                                                   # (a failure of this leg must not lose the headline line: it is reported beside it)
+            model.opt.bofi_rl_reference_estimator = False
+            for _ in range(3):
+                tr.rl_step(att, None, score, sample_n=n)
+            torch.cuda.synchronize(dev)
+            t1 = time.perf_counter()
+            for _ in range(10):
+                tr.rl_step(att, None, score, sample_n=n)
+            torch.cuda.synchronize(dev)
+            fast_info = {"ms_per_step": round((time.perf_counter() - t1) / 10 * 1e3, 2),
+                         "what": "samples from the inference engine (no dropout), one gradient pass with dropout as a hipGraph: an importance-weight log-std of ~0.65 per caption "
+                                 "against the reference's estimator (dev/exp/rl_dropout_gap.py)"}
+        except Exception as e:
+            log(f"rl: the fast-estimator leg failed: {type(e).__name__}: {e}")
+            fast_info = {"error": f"{type(e).__name__}: {e}"}
+        del model.opt.bofi_rl_reference_estimator
+        tr._last_rl = last_default
     if rank != 0:
         return None
     ms = elapsed / args.steps * 1e3
@@ -840,9 +848,9 @@ def run_naic(args, ctx, log, cpu=True, gemm_roofline=True):
         dumped["what"] = (f"the last timed launch ({C} batch(es) of {args.batch}; batches in input order)"
                           + ("" if nb > 1 else f"; images of stream {k}, seed {ATT_SEED + 10 * rank + 1000 * k if k else ATT_SEED + 10 * rank}"))
 
-    # for the record: the same K steps strictly one at a time (latency view of the same workload), HIP events on the stream
+    # --full, for the record: the same K steps strictly one at a time (latency view of the same workload), HIP events on the stream
     single_ms = None
-    if len(engines) > 1:
+    if len(engines) > 1 and args.full:
         # (a caller that runs one decode at a time says so: the engine then takes the sublayer kernels' latency forms -- a hint, part of the graph key)
         eng.set_decodes_in_flight(1)
         for i in range(max(warm_launches, 3)):
@@ -953,7 +961,8 @@ def run_naic(args, ctx, log, cpu=True, gemm_roofline=True):
                    "timing": (f"the {args.steps}-step region ({launches} launches) timed {regions} times back to back, each between a barrier + synchronisation; value / "
                               "ms_per_step are the MEDIAN region's" if regions > 1 else f"one region of {args.steps} steps ({launches} launches)"),
                    "images_per_launch": C * args.batch, "refine_rounds": args.refine,
-                   "one_at_a_time_ms_per_step": round(single_ms, 4) if single_ms else round(elapsed / args.steps * 1e3, 4),
+                   # (one launch in flight: the timed region is the one-at-a-time view; several without --full: not measured)
+                   "one_at_a_time_ms_per_step": round(single_ms, 4) if single_ms else round(elapsed / args.steps * 1e3, 4) if len(engines) == 1 else None,
                    "weights": "seeded Xavier init + calibrated bound heads (boficap_amd.weights, seed 0)",
                    "features_from_pinned_host_ms_per_step": round(pcie_ms, 4) if pcie_ms else None, "features_from_pinned_host_how": pcie_note, "att_feats_seed": ATT_SEED, "batches_reordered_for_q1": moved, "nan_in_output": nan, "sharding": "images by rank, no collective"},
         "roofline": roof,
@@ -1067,7 +1076,9 @@ def choose_coalesce(steps: int, inflight: int) -> int:
     return min(cands, key=lambda c: (-(-(steps // c) // n_str)) * c)
 
 
-def main():
+def parse_args(argv=None):
+    """The command line, with the defaults that depend on other flags resolved; ``cpu`` / ``gemm_roofline`` / ``secondary`` say which of the measurements
+    beside the headline run (--full only, each trimmed by its --no-* switch)."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", default="naic", choices=["naic", "xe", "rl"],
                     help="naic: bound+fill decode (headline); xe: XE training step (config 3); rl: self-critical step (config 4)")
@@ -1091,28 +1102,32 @@ def main():
                     "launch; quirk Q1 stays per batch (q1_group), so every step's outputs equal its own separate decode.  K steps = K/C launches.  "
                     "Default for the plain batch-64 decode: 5 or 4 (whichever divides --steps into evenly spread launches), 1 otherwise")
     ap.add_argument("--from-host", action="store_true", default=None, help="also time the launches with the features copied from pinned host memory "
-                    "before each one (PCIe-inclusive rate, reported in config; never the headline value).  Default: on for the plain headline run")
+                    "before each one (PCIe-inclusive rate, reported in config; never the headline value).  Default: on under --full for the headline workload")
     ap.add_argument("--no-from-host", dest="from_host", action="store_false")
     ap.add_argument("--iter-budget", default="auto", choices=["auto", "off"],
                     help="naic: bounding iterations ENQUEUED per decode.  off = all seq_length of them, as round 2 (an iteration past the last live one is five "
                          "launches that return at once).  auto = the largest count of live iterations among the probe decodes + 2; every decode folds its own "
                          "count into a device word (atomic max) that is read after each timed leg: were a decode to need more, the whole measurement is redone "
                          "without the budget.  The reference's loop stops when every image is finished (TransformerModel.py:1869) -- it never runs the idle ones")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-gemm-roofline", action="store_true", help="skip the per-shape GEMM timing (use under rocprofv3 so that the trace holds decodes only)")
-    ap.add_argument("--no-secondary", action="store_true", help="headline measurement only (no XE / RL / refinement lines)")
+    ap.add_argument("--full", action="store_true", help="also every measurement that takes runs of its own: the CPU-oracle baselines, the per-shape GEMM "
+                    "timings, one launch at a time, the pinned-host rate, the self-critical step's fast-estimator leg and the secondary lines (other "
+                    "configurations; with --gpus N > 1 the XE step's gradient exchange).  Off: set-up, warm-up, the timed steps, --dump-outputs, the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU-oracle baselines")
+    ap.add_argument("--no-gemm-roofline", action="store_true", help="--full without the per-shape GEMM timing")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary lines (XE / RL / refinement, the data-parallel exchange)")
     ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU-oracle work per baseline")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the timed path computed in its last step as "
                     "DIR/<name>.npy (float32 / float64, at most 64 MB in all: a fixed, seeded sample of the rows of a larger array); the config says what went where")
-    args = ap.parse_args()
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(self_launch(sys.argv[1:], args.gpus))
+    args = ap.parse_args(argv)
     if args.batch is None:
         args.batch = 10 if args.mode == "rl" else 64
     if args.from_host is None:
-        args.from_host = args.mode == "naic" and args.batch == 64 and not args.refine and args.coalesce is None and not args.no_secondary
-    default_coalesce = args.coalesce is None
-    if default_coalesce:
+        args.from_host = args.full and args.mode == "naic" and args.batch == 64 and not args.refine and args.coalesce is None and not args.no_secondary
+    args.cpu = args.full and not args.no_cpu_baseline
+    args.gemm_roofline = args.full and not args.no_gemm_roofline
+    args.secondary = args.full and not args.no_secondary
+    args.default_coalesce = args.coalesce is None
+    if args.default_coalesce:
         args.coalesce = 1
         if args.mode == "naic" and args.batch == 64 and not args.refine:
             # batches per launch: among 16, 20, 10, 8, 5, 4, 2 the one that divides the timed steps and spreads the launches evenly over the
@@ -1120,14 +1135,21 @@ def main():
             # driver's --steps 20 -> 4 launches of 5 batches, one per stream).  Round 5: the chip wants ~3 000 images in flight -- 254 k img/s at 10 batches
             # per launch, 260 k at 12, 262 k at 16-20 against 239-243 k at 5 (profiles/r05_launch_shape_sweep.txt)
             args.coalesce = choose_coalesce(args.steps, args.inflight)
+    return args
+
+
+def main():
+    args = parse_args()
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        sys.exit(self_launch(sys.argv[1:], args.gpus))
     ctx = dist_setup(args)
     rank, world = ctx[0], ctx[2]
 
     def log(msg):
         if rank == 0:
-            print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
+            print(f"[bench {time.strftime('%H:%M:%S')} +{time.perf_counter() - T_START:.1f}s] {msg}", file=sys.stderr, flush=True)
 
-    cpu = not args.no_cpu_baseline
+    cpu = args.cpu
     if os.environ.get("BOFI_BENCH_REHEARSAL") == "dry":
         res = run_dry(args, ctx, log)
         if rank == 0:
@@ -1142,9 +1164,9 @@ def main():
     elif args.mode == "rl":
         res = run_rl(args, ctx, log, cpu)
     else:
-        res = run_naic(args, ctx, log, cpu, not args.no_gemm_roofline)
-        plain = (args.batch == 64 and not args.refine and default_coalesce and args.dtype == "bf16" and not args.ids_only and not args.no_graph)
-        if world == 1 and plain and not args.no_secondary:
+        res = run_naic(args, ctx, log, cpu, args.gemm_roofline)
+        plain = (args.batch == 64 and not args.refine and args.default_coalesce and args.dtype == "bf16" and not args.ids_only and not args.no_graph)
+        if world == 1 and plain and args.secondary:
             import copy
             raw = {}
             torch.cuda.empty_cache()
@@ -1184,7 +1206,7 @@ def main():
                                      "driver-run lines of BASELINE configs 3, 4, 5 (short runs in the same process, after the headline measurement; every CPU-oracle "
                                      "leg after all of them); config 5's 'autoregressive fallback' has no counterpart: a UIC checkpoint has no AR decode path in the reference "
                                      "(TransformerModel.py:1791-1804 needs EncoderDecoder.decode, :1287-1310)")
-        if world > 1 and plain and not args.no_secondary:
+        if world > 1 and plain and args.secondary:
             # the decode shards with no collective: the scaling run exercises RCCL through this secondary (the XE step's gradient exchange).
             # Never at the cost of the headline line, and never silently: the line says how many ranks the collective backend saw
             # (config.rccl_ranks / dist_backend) and carries config.xe_dp_error when the exchange failed.  A rank that fails INSIDE a step leaves the

@@ -3,7 +3,7 @@
 mkdir -p gpurun_out
 for rep in 1 2 3; do
   for v in 1 0; do
-    BOFI_RB_DEC_FUSE=$v python bench.py --no-cpu-baseline --no-secondary --no-gemm-roofline --steps 400 --warmup 40 2>/dev/null | python -c "
+    BOFI_RB_DEC_FUSE=$v python bench.py --full --no-cpu-baseline --no-secondary --no-gemm-roofline --steps 400 --warmup 40 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -4,7 +4,7 @@
 mkdir -p gpurun_out
 for rep in 1 2 3; do
   for v in "$@"; do
-    env $v python bench.py --no-cpu-baseline --no-secondary --no-gemm-roofline ${BENCH_ARGS:---steps 400 --warmup 40} 2>/dev/null | python -c "
+    env $v python bench.py --full --no-cpu-baseline --no-secondary --no-gemm-roofline ${BENCH_ARGS:---steps 400 --warmup 40} 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

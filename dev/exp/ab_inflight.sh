@@ -3,7 +3,7 @@
 mkdir -p gpurun_out
 for nf in 4 5 6 8; do
   for bl in 1 0; do
-    BOFI_BOUND_LOOP=$bl python bench.py --inflight $nf --no-cpu-baseline --no-secondary --no-gemm-roofline --steps 400 --warmup 40 2>/dev/null | python -c "
+    BOFI_BOUND_LOOP=$bl python bench.py --full --inflight $nf --no-cpu-baseline --no-secondary --no-gemm-roofline --steps 400 --warmup 40 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,5 +1,5 @@
 # CU-partitioned streams (bench.py --cu-partitions P with BOFI_GEMM_PERS_GRID = 256 / P) against the default
-B="python bench.py --no-secondary --no-cpu-baseline --no-gemm-roofline --steps 120 --warmup 20"
+B="python bench.py --full --no-secondary --no-cpu-baseline --no-gemm-roofline --steps 120 --warmup 20"
 p() { python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); print('$1', d['value'], d['ms_per_step'], d['config'].get('one_at_a_time_ms_per_step'))"; }

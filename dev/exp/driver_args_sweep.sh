@@ -1,5 +1,5 @@
 # the driver's arguments (--steps 20 --warmup 5) under different batchings
-B="python bench.py --no-secondary --no-cpu-baseline --no-gemm-roofline --gpus 1 --steps 20 --warmup 5"
+B="python bench.py --full --no-secondary --no-cpu-baseline --no-gemm-roofline --gpus 1 --steps 20 --warmup 5"
 p() { python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); print('$1', d['value'], d['ms_per_step'], d['config'].get('one_at_a_time_ms_per_step'), d['config'].get('nan_in_output'))"; }

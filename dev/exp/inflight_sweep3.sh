@@ -1,5 +1,5 @@
 # batches per launch x launches in flight, final state (steps a multiple of every combination)
-B="python bench.py --no-secondary --no-cpu-baseline --no-gemm-roofline --steps 240 --warmup 40"
+B="python bench.py --full --no-secondary --no-cpu-baseline --no-gemm-roofline --steps 240 --warmup 40"
 p() { python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); print('$1', d['value'], d['ms_per_step'], d['config'].get('one_at_a_time_ms_per_step'))"; }

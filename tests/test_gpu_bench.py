@@ -1,5 +1,6 @@
 """The driver's contract with bench.py: `python bench.py --gpus 1 --steps K --warmup W` prints ONE JSON line last, with the fields the
-driver parses, the roofline and CPU-baseline objects, and a config that names the workload."""
+driver parses, the roofline object and a config that names the workload; `--full` adds the CPU baseline, the per-shape GEMM timings and
+the secondary lines."""
 import json
 import os
 import subprocess
@@ -23,7 +24,7 @@ def _run(*flags, env=None):
 
 
 def test_bench_line_with_the_drivers_arguments():
-    d = _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--no-secondary", "--cpu-budget", "2")
+    d = _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-secondary", "--cpu-budget", "2")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
               "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -54,6 +55,22 @@ def test_bench_line_with_the_drivers_arguments():
     assert d["value"] > 20 * b["value"]
 
 
+def test_bench_plain_run_times_the_headline_only():
+    """Without --full the run sets up, warms up, times the steps and prints the line: no CPU oracle, no per-shape GEMM timings, no one-at-a-time or
+    pinned-host legs, no secondary lines -- and its time outside the warm-up and timed steps stays within 30 s."""
+    import time
+    t0 = time.perf_counter()
+    d = _run("--gpus", "1", "--steps", "20", "--warmup", "5")
+    wall = time.perf_counter() - t0
+    assert d["steps"] == 20 and d["warmup"] == 5 and d["value"] > 0 and abs(d["value"] - 64 * 1e3 / d["ms_per_step"]) <= 0.01 * d["value"]
+    for k in ("cpu_baseline", "roofline_gemm", "secondary", "secondary_note"):
+        assert k not in d, k
+    c = d["config"]
+    assert "one_at_a_time" not in d["roofline"] and c["features_from_pinned_host_ms_per_step"] is None and c["one_at_a_time_ms_per_step"] is None
+    assert c["batches_per_launch"] == 5 and c["timed_regions"] == 5 and not c["nan_in_output"] and "steady_state_img_s" not in c
+    assert wall - 25 * d["ms_per_step"] * 1e-3 <= 30.0, wall
+
+
 def test_bench_odd_step_counts_and_one_batch_per_launch():
     d = _run("--steps", "7", "--warmup", "3", "--no-secondary", "--no-cpu-baseline", "--no-gemm-roofline")
     assert d["steps"] == 7 and d["config"]["batches_per_launch"] == 1 and d["value"] > 0
@@ -66,7 +83,7 @@ def test_bench_two_ranks_walk_the_multi_gpu_path_on_one_device():
     """`python bench.py --gpus 2` as the driver starts it (self-launch through torch.distributed.run, one process per rank), rehearsed on
     the one GPU of the box: both ranks on device 0 over gloo (RCCL refuses two ranks on one device).  Checks what a scaling run needs:
     ONE line from rank 0, n_gpus 2, value = the images of BOTH ranks over the slowest rank's time, and the XE exchange secondary."""
-    d = _run("--gpus", "2", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-gemm-roofline", "--no-from-host",
+    d = _run("--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-gemm-roofline", "--no-from-host",
              env={"BOFI_BENCH_REHEARSAL": "1"})
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and "rehearsal" in d["config"]
     assert abs(d["value"] - 2 * 64 * 1e3 / d["ms_per_step"]) <= 0.01 * d["value"]       # whole-job aggregate: 64 images per rank and step

@@ -266,3 +266,22 @@ def test_bench_batches_per_launch_rule():
     for k in (20, 40, 64, 100, 320, 480):
         c = bench.choose_coalesce(k, 4)
         assert k % c == 0
+
+
+def test_bench_plain_run_leaves_the_extra_measurements_to_full():
+    """bench.py --gpus 1 --steps N --warmup W times the headline only; --full turns on every measurement that takes runs of its own (CPU oracle, per-shape GEMM
+    timings, pinned-host rate, secondary lines), and the --no-* switches trim it."""
+    import importlib, sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    bench = importlib.import_module("bench")
+    a = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not a.full and not a.cpu and not a.gemm_roofline and not a.secondary and not a.from_host
+    assert a.mode == "naic" and a.batch == 64 and a.coalesce == 5 and a.default_coalesce
+    a = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert a.full and a.cpu and a.gemm_roofline and a.secondary and a.from_host and a.coalesce == 5
+    a = bench.parse_args(["--full", "--no-cpu-baseline", "--no-gemm-roofline", "--no-secondary"])
+    assert a.full and not a.cpu and not a.gemm_roofline and not a.secondary and not a.from_host and a.coalesce == 16
+    a = bench.parse_args(["--from-host"])
+    assert a.from_host and not a.full
+    a = bench.parse_args(["--mode", "rl", "--full"])
+    assert a.batch == 10 and a.cpu and not a.from_host and a.coalesce == 1
