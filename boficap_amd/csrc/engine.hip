@@ -50,6 +50,22 @@ struct LinRecipe { Lin* out; std::vector<std::string> prefixes; int n_each, K; s
 
 struct NormRecipe { Norm* out; std::string prefix; int d; };
 
+// A residual stream: the float32 rows, their copy in the compute dtype and the rows' partial sums [rows][groups][2] from which the consuming GEMM
+// applies the pre-norm LayerNorm in its epilogue.  The float32 engine reads the stream itself and keeps no copy.
+struct Stream {
+    float* x = nullptr; void* xb = nullptr; float* st = nullptr;
+    bool f32 = false;
+    int groups = 0;                                                   // partial-sum pairs per row of st (0: d_model / 32)
+    const void* in() const { return f32 ? (const void*)x : xb; }      // what a GEMM of the compute dtype reads
+    void* copy() const { return f32 ? nullptr : xb; }                 // where a producer leaves the copy (none: float32 engine)
+};
+// Which rows of a launch run: all of them, unless an early-out word says the work is over (*skip >= thr: the launch returns at once) or a row list on
+// the device names them (idx[0 .. *m_dev), the SAIC iterations).  Launches that carry either never take the row-block kernels.
+struct Rows {
+    const int* skip = nullptr; int thr = 0;
+    const int* idx = nullptr; const int* m_dev = nullptr;
+};
+
 struct GraphEntry {
     std::vector<uintptr_t> key;
     hipGraph_t graph = nullptr;
@@ -98,19 +114,19 @@ struct bofi_engine {
     float* dbg_part = nullptr;
 
     // workspace
-    float *x_enc = nullptr, *x_fill = nullptr, *logits = nullptr;
+    Stream x_enc, x_fill;                // residual streams of the encoder [Bm*Rm, d] and of the filling pass / decoder rows [Bm*Sq, d]
+    float* logits = nullptr;
     float* logits_pad = nullptr;         // bf16 engine: the generator's output with a pitch of gen.Npad (whole 128-column tiles: the persistent GEMM), read by vocab_finalize
     void *qkv = nullptr, *ctx = nullptr, *hdn = nullptr, *mem = nullptr, *kv = nullptr, *qs = nullptr, *xn = nullptr;
     void* feats_t = nullptr;                                          // bf16 copy of float32 input features
-    void *xb_enc = nullptr, *xb_fill = nullptr, *byb = nullptr;       // compute-dtype copies of the residual streams
-    float *st_enc = nullptr, *st_fill = nullptr, *st_b = nullptr;     // row partial sums [rows][d/32][2]
-    float* st_fill16 = nullptr;                                       // the same for the decoder rows [Bm*Sq][d/16][2] (row-list iterations of the SAIC decode)
+    float* st_fill16 = nullptr;                                       // row partial sums of the decoder rows per 16 columns [Bm*Sq][d/16][2] (row-list iterations of the SAIC decode)
     float* st_b16 = nullptr;                                          // row partial sums per 16 columns [Bm][d/16][2] (bound_ops.hip)
-    float *by1 = nullptr, *by2 = nullptr, *by3 = nullptr;
+    Stream y1, y2;                       // row 0 of a bounding iteration [Bm, d] behind its self-attention / cross-attention sublayer (one copy and one set of statistics serve both)
+    float* by3 = nullptr;                // the feed-forward sublayer's output as up to 4 partial slabs [4][Bm, d]
     void *bctx = nullptr, *bq2 = nullptr, *bctx2 = nullptr, *bh = nullptr;
     bofi::BoundState st{};
     bofi::SaicState sa{};
-    float* xw = nullptr; void* xwb = nullptr; float* st_w = nullptr;   // SAIC bound input rows [B*L, d] (+copy, +stats)
+    Stream xw;                                                          // all L rows of the bound sequence [B*L, d]: SAIC bound input, dense bounding pass
     void* kvs = nullptr;                                                // their K|V [B*L, 2d]
     int64_t* tok64 = nullptr;                                           // greedy ids of one decoder pass [B*S]
     std::vector<void*> qkv_dec;                                         // SAIC: q|k|v of every decoder layer [B*S, 3d] (the K / V cache)
@@ -126,6 +142,7 @@ struct bofi_engine {
     int q1_group = 0;                     // > 0: the call carries several independent batches of this many images (quirk Q1 per batch)
     float sample_temperature = 1.0f;      // BOFI_FLAG_SAMPLE: token draws inside the semi-autoregressive loop
     uint64_t sample_seed = 0;
+    int saic_B = 0;                       // images of the last semi-autoregressive decode (what bofi_engine_saic_put_words may continue)
     int saic_it_begin = 1, saic_it_end = 0;   // iterations the next semi-autoregressive decode enqueues (bofi_engine_set_saic_range; end 0 = seq_length)
     int bound_iter_cap = 0;               // bounding iterations the non-autoregressive decode enqueues (bofi_engine_set_bound_iter_cap; 0 = seq_length)
     int in_flight = 0;                    // decodes the caller keeps in flight (bofi_engine_set_decodes_in_flight; 0 = unknown: throughput forms)
@@ -235,14 +252,12 @@ struct bofi_engine {
         const float* residual = nullptr; int ldr = 0;
         int relu = 0;
         const int* row_len = nullptr; int rpg = 0;
-        bool early = false;
-        bool halt = false;                   // SAIC: early-out on the halt word (counters[2] >= 1)
+        Rows rows;                           // early-out word and / or row list
         int splitk = 1;                      // K split over workgroups, float32 partial slabs out
         const Norm* ln = nullptr;            // explicit LayerNorm kernel on x first (setup-time use only)
         const float* ln_stats = nullptr;     // LayerNorm folded into the GEMM (Lin built with fold_norm)
         float* stats_out = nullptr;          // emit row partial sums of the output
         void* y2 = nullptr;                  // compute-dtype copy of the output
-        const int* row_idx = nullptr; const int* m_dev = nullptr;     // row list (LinearArgs)
         int ln_groups = 0;                   // partial-sum pairs per row of ln_stats (0: K / 32)
     };
     int linear(const void* x, int x_dtype, int ldx, const Lin& l, void* y, int y_dtype, int ldy, int M, const LinOpt& o, hipStream_t s) {
@@ -258,15 +273,39 @@ struct bofi_engine {
         a.residual = o.residual; a.ldr = o.ldr; a.y = y; a.y_dtype = y_dtype; a.ldy = ldy;
         a.M = M; a.N = l.N; a.K = l.K; a.relu = o.relu; a.row_len = o.row_len; a.rows_per_group = o.rpg;
         a.ln_stats = o.ln_stats; a.ln_colsum = o.ln_stats ? l.cs : nullptr; a.ln_groups = o.ln_groups;
-        a.stats_out = o.stats_out; a.y2 = o.y2; a.ldy2 = l.N; a.splitk = o.splitk; a.row_idx = o.row_idx; a.m_dev = o.m_dev;
-        if (o.early) { a.skip_if_ge = st.counters; a.skip_threshold = cur_B; }
-        if (o.halt) { a.skip_if_ge = st.counters + 2; a.skip_threshold = 1; }
+        a.stats_out = o.stats_out; a.y2 = o.y2; a.ldy2 = l.N; a.splitk = o.splitk;
+        a.skip_if_ge = o.rows.skip; a.skip_threshold = o.rows.thr; a.row_idx = o.rows.idx; a.m_dev = o.rows.m_dev;
         return bofi::launch_linear(a, s);
     }
-    // residual stream in the compute dtype: the fp32 engine reads the stream itself
-    const void* stream_t(const float* x32, const void* xt) const { return cfg.dtype == BOFI_DT_F32 ? (const void*)x32 : xt; }
-    void* copy_t(void* xt) const { return cfg.dtype == BOFI_DT_F32 ? nullptr : xt; }
-    int cur_B = 0;
+    // The two GEMMs a pre-norm sublayer is made of, as tiled launches on the rows r.  folded: y = l(LayerNorm(t)), the LayerNorm applied from the
+    // stream's copy and statistics (Lin built with fold_norm).  close_sublayer: t = residual + l(x) -- the stream's float32 rows, its copy and its
+    // statistics are all written here (residual: the stream itself unless the sublayer's input rows live elsewhere, pitch ldr).
+    int folded(const Stream& t, const Lin& l, void* y, int y_dtype, int ldy, int M, const Rows& r, hipStream_t s, int relu = 0) {
+        LinOpt o; o.relu = relu; o.ln_stats = t.st; o.ln_groups = t.groups; o.rows = r;
+        return linear(t.in(), cfg.dtype, cfg.d_model, l, y, y_dtype, ldy, M, o, s);
+    }
+    int close_sublayer(const void* x, const Lin& l, const Stream& t, int M, const Rows& r, hipStream_t s, const float* residual = nullptr, int ldr = 0) {
+        LinOpt o; o.residual = residual ? residual : t.x; o.ldr = residual ? ldr : cfg.d_model; o.stats_out = t.st; o.y2 = t.copy(); o.rows = r;
+        return linear(x, cfg.dtype, l.K, l, t.x, BOFI_DT_F32, cfg.d_model, M, o, s);
+    }
+    // self-attention over a packed q|k|v buffer [B*Lq, 3d] and cross-attention over slot i of the stacked cross K|V `kv` (bound layers, then decoder
+    // layers), context rows into `out`.  Callers add what differs: the key lengths (and quirk Q1's klen_shared_last), the early-out word.
+    const void* kv_slot(int i) const { return (const char*)kv + (size_t)i * 2 * cfg.d_model * tsz; }
+    bofi::AttnArgs attn_args(const void* q, int ldq, const void* k, int ldkv, void* out, int B, int Lq, int Lk, const Rows& r) const {
+        bofi::AttnArgs a{};
+        a.q = q; a.ldq = ldq; a.k = k; a.v = (const char*)k + (size_t)cfg.d_model * tsz; a.ldk = a.ldv = ldkv;
+        a.out = out; a.ldo = cfg.d_model; a.dtype = cfg.dtype; a.B = B; a.H = cfg.heads; a.Lq = Lq; a.Lk = Lk;
+        a.skip_if_ge = r.skip; a.skip_threshold = r.thr;
+        return a;
+    }
+    bofi::AttnArgs self_attn_args(const void* qkv, int B, int Lq, const Rows& r = Rows{}) const {
+        return attn_args(qkv, 3 * cfg.d_model, (const char*)qkv + (size_t)cfg.d_model * tsz, 3 * cfg.d_model, ctx, B, Lq, Lq, r);
+    }
+    bofi::AttnArgs cross_attn_args(const void* q, int i, void* out, int B, int Lq, int R, const int* att_len, const Rows& r = Rows{}) const {
+        bofi::AttnArgs a = attn_args(q, cfg.d_model, kv_slot(i), kv_all.N, out, B, Lq, R, r);
+        a.klen = att_len; a.klen_sb = 1;
+        return a;
+    }
     bool is_fork = false;
     size_t n_weight_allocs = 0;          // allocs[0 .. n) are weights (owned by the parent), the rest workspace
     // bofi_engine_refresh_device: descriptor tables of the batched repack launches (device copy, pinned staging, what was uploaded last)
@@ -279,8 +318,14 @@ struct bofi_engine {
     const int d = c.d_model, dff = c.d_ff;
     const size_t Lm = Sq + 2;
     const size_t rows = Bm * (Rm > Lm ? Rm : Lm);
-    ENG_OK(dalloc(&x_enc, Bm * Rm * d));
-    ENG_OK(dalloc(&x_fill, Bm * Sq * d));
+    auto stream = [&](Stream* t, size_t n) -> int {       // a residual stream of n rows
+        t->f32 = c.dtype == BOFI_DT_F32;
+        ENG_OK(dalloc(&t->x, n * d)); ENG_OK(dalloc((char**)&t->xb, n * d, tsz)); ENG_OK(dalloc(&t->st, n * (d / 32) * 2));
+        return BOFI_OK;
+    };
+    ENG_OK(stream(&x_enc, Bm * Rm)); ENG_OK(stream(&x_fill, Bm * Sq)); ENG_OK(stream(&xw, Bm * L));
+    ENG_OK(stream(&y1, Bm));
+    y2 = y1; ENG_OK(dalloc(&y2.x, Bm * d));
     ENG_OK(dalloc(&logits, Bm * Sq * c.vocab));
     if (c.dtype == BOFI_DT_BF16 && gen.Npad > gen.N) ENG_OK(dalloc(&logits_pad, Bm * Sq * (size_t)gen.Npad));
     ENG_OK(dalloc((char**)&qkv, rows * 3 * d, tsz));
@@ -288,14 +333,11 @@ struct bofi_engine {
     ENG_OK(dalloc((char**)&hdn, rows * dff, tsz));
     ENG_OK(dalloc((char**)&mem, Bm * Rm * d, tsz));
     ENG_OK(dalloc((char**)&kv, Bm * Rm * (size_t)kv_all.N, tsz));
-    ENG_OK(dalloc((char**)&qs, Bm * Sq * d, tsz));
+    ENG_OK(dalloc((char**)&qs, Bm * Lm * d, tsz));                    // (the dense bounding pass projects queries for all L rows of an image)
     ENG_OK(dalloc((char**)&xn, (rows > (size_t)L * 10 ? rows : (size_t)L * 10) * d, tsz));
-    ENG_OK(dalloc((char**)&xb_enc, Bm * Rm * d, tsz)); ENG_OK(dalloc((char**)&xb_fill, Bm * Sq * d, tsz));
-    ENG_OK(dalloc((char**)&byb, Bm * d, tsz));
     if (c.dtype == BOFI_DT_BF16) ENG_OK(dalloc((char**)&feats_t, Bm * Rm * (size_t)c.feat, 2));
-    ENG_OK(dalloc(&st_enc, Bm * Rm * (d / 32) * 2)); ENG_OK(dalloc(&st_fill, Bm * Sq * (d / 32) * 2));
-    ENG_OK(dalloc(&st_b, Bm * (d / 32) * 2)); ENG_OK(dalloc(&st_b16, Bm * (d / 16) * 2));
-    ENG_OK(dalloc(&by1, Bm * d)); ENG_OK(dalloc(&by2, Bm * d)); ENG_OK(dalloc(&by3, 4 * Bm * d));
+    ENG_OK(dalloc(&st_b16, Bm * (d / 16) * 2));
+    ENG_OK(dalloc(&by3, 4 * Bm * d));
     ENG_OK(dalloc((char**)&bctx, Bm * d, tsz)); ENG_OK(dalloc((char**)&bq2, Bm * d, tsz));
     ENG_OK(dalloc((char**)&bctx2, Bm * d, tsz)); ENG_OK(dalloc((char**)&bh, Bm * dff, tsz));
     ENG_OK(dalloc(&st.last, Bm)); ENG_OK(dalloc(&st.finished, Bm)); ENG_OK(dalloc(&st.phrase_num, Bm));
@@ -308,7 +350,6 @@ struct bofi_engine {
     }
     ENG_OK(dalloc(&sa.seq_last, Bm)); ENG_OK(dalloc(&sa.seq, Bm * L)); ENG_OK(dalloc(&sa.ext_len, Bm * L));
     ENG_OK(dalloc(&sa.ext_phrase, Bm * L)); ENG_OK(dalloc(&sa.klen_dec, Bm * L));
-    ENG_OK(dalloc(&xw, Bm * L * d)); ENG_OK(dalloc((char**)&xwb, Bm * L * d, tsz)); ENG_OK(dalloc(&st_w, Bm * L * (d / 32) * 2));
     ENG_OK(dalloc((char**)&kvs, Bm * L * 2 * (size_t)d, tsz)); ENG_OK(dalloc(&tok64, Bm * Sq));
     ENG_OK(dalloc(&sa_rows, Bm * Sq)); ENG_OK(dalloc(&sa_nrows, 4)); ENG_OK(dalloc(&d_seed, 2));
     ENG_OK(dalloc(&st_fill16, Bm * Sq * (d / 16) * 2));
@@ -323,7 +364,7 @@ struct bofi_engine {
         bofi::BoundTailArgs a{};
         a.y = y; a.yparts = yparts; a.y_stride = y_stride; a.w = heads; a.st = st; a.sa = saic ? sa : bofi::SaicState{};
         a.ext_syn_in = ext_syn_in; a.last_in = last_in; a.q0 = b_q0; a.kvtab = b_kvtab; a.votab = b_votab; a.x0b = b_x0b;
-        a.y1 = by1; a.y1t = copy_t(byb); a.stats = st_b;
+        a.y1 = y1.x; a.y1t = y1.copy(); a.stats = y1.st;
         const int tail_dbg = BOFI_ENV_INT("BOFI_TAIL_DBG", 0);     // developer ablations
         a.B = B; a.L = L; a.S = cfg.seq_length; a.d = cfg.d_model; a.hh = cfg.head_hidden; a.H = cfg.heads; a.flags = flags | (tail_dbg << 8); a.iter = iter;
         a.len_logp = len_logp; a.syn_logp = syn_logp;
@@ -411,40 +452,57 @@ struct bofi_engine {
         a.xbuf = bl_xbuf; a.xctl = bl_xctl;                    // (two workgroups per group when the launcher's conditions hold: BOFI_BL_PAIR)
         return bofi::launch_bound_loop(a, s);
     }
-    // y1 (by1 / byb / st_b) -> y3 partial slabs (by3): query projection + cross-attention, Wo_src, FFN, as the direct-operand kernels
-    // of bound_ops.hip.  Returns -1 when the configuration is not theirs (the caller takes the general kernels), else a status;
-    // *parts = number of slabs in by3.  `skip`: early-out word and threshold (NULL: none).
-    int bound_chain_lean(int B, int R, const int* att_len, const int* skip, int skip_thr, hipStream_t s, int* parts) {
+    // y1 -> y3 partial slabs (by3): query projection + cross-attention, Wo_src, FFN, as the direct-operand kernels
+    // of bound_ops.hip.  Returns -1 when the configuration is not theirs (bound_chain then takes the general kernels), else a status;
+    // *parts = number of slabs in by3.
+    int bound_chain_lean(int B, int R, const int* att_len, const Rows& r, hipStream_t s, int* parts) {
         const bool lean_on = BOFI_ENV_INT("BOFI_BOUND_LEAN", 1) != 0;
         const int d = cfg.d_model;
         if (!(lean_on && cfg.dtype == BOFI_DT_BF16 && d == 512 && cfg.heads == 8 && R <= 64 && cfg.d_ff % 512 == 0 && cfg.d_ff / 512 <= 4)) return -1;
         {   bofi::BoundQAttnArgs a{};
-            a.x = (const uint16_t*)byb; a.stats = st_b; a.wq = (const uint16_t*)b_q_src.w; a.bias = b_q_src.b; a.colsum = b_q_src.cs;
+            a.x = (const uint16_t*)y1.xb; a.stats = y1.st; a.wq = (const uint16_t*)b_q_src.w; a.bias = b_q_src.b; a.colsum = b_q_src.cs;
             a.k = (const uint16_t*)kv; a.v = (const uint16_t*)kv + d; a.ldkv = kv_all.N; a.att_len = att_len; a.out = (uint16_t*)bctx2;
-            a.B = B; a.R = R; a.d = d; a.H = cfg.heads; a.skip_if_ge = skip; a.skip_threshold = skip_thr;
+            a.B = B; a.R = R; a.d = d; a.H = cfg.heads; a.skip_if_ge = r.skip; a.skip_threshold = r.thr;
             ENG_OK(bofi::launch_bound_qattn(a, s)); }
         {   bofi::RowGemmArgs a{};                   // y2 = y1 + Wo_src . ctx2 + bo
-            a.x = (const uint16_t*)bctx2; a.ldx = d; a.w = (const uint16_t*)b_o_src.w; a.bias = b_o_src.b; a.residual = by1; a.ldr = d;
-            a.y = by2; a.ldy = d; a.yb = (uint16_t*)byb; a.ldyb = d; a.stats_out = st_b16; a.M = B; a.N = d; a.K = d; a.splitk = 1;
-            a.skip_if_ge = skip; a.skip_threshold = skip_thr;
+            a.x = (const uint16_t*)bctx2; a.ldx = d; a.w = (const uint16_t*)b_o_src.w; a.bias = b_o_src.b; a.residual = y1.x; a.ldr = d;
+            a.y = y2.x; a.ldy = d; a.yb = (uint16_t*)y2.xb; a.ldyb = d; a.stats_out = st_b16; a.M = B; a.N = d; a.K = d; a.splitk = 1;
+            a.skip_if_ge = r.skip; a.skip_threshold = r.thr;
             ENG_OK(bofi::launch_rowgemm(a, s)); }
         {   bofi::RowGemmArgs a{};                   // h = relu(W1 . LN(y2) + b1)
-            a.x = (const uint16_t*)byb; a.ldx = d; a.w = (const uint16_t*)b_w1.w; a.bias = b_w1.b; a.stats = st_b16; a.stats_groups = d / 16;
+            a.x = (const uint16_t*)y2.xb; a.ldx = d; a.w = (const uint16_t*)b_w1.w; a.bias = b_w1.b; a.stats = st_b16; a.stats_groups = d / 16;
             a.colsum = b_w1.cs; a.yb = (uint16_t*)bh; a.ldyb = cfg.d_ff; a.M = B; a.N = cfg.d_ff; a.K = d; a.splitk = 1; a.relu = 1;
-            a.skip_if_ge = skip; a.skip_threshold = skip_thr;
+            a.skip_if_ge = r.skip; a.skip_threshold = r.thr;
             ENG_OK(bofi::launch_rowgemm(a, s)); }
         *parts = cfg.d_ff / 512;
         {   bofi::RowGemmArgs a{};                   // y3 = y2 + W2 . h + b2 as `parts` partial slabs
-            a.x = (const uint16_t*)bh; a.ldx = cfg.d_ff; a.w = (const uint16_t*)b_w2.w; a.bias = b_w2.b; a.residual = by2; a.ldr = d;
+            a.x = (const uint16_t*)bh; a.ldx = cfg.d_ff; a.w = (const uint16_t*)b_w2.w; a.bias = b_w2.b; a.residual = y2.x; a.ldr = d;
             a.y = by3; a.ldy = d; a.M = B; a.N = d; a.K = cfg.d_ff; a.splitk = *parts;
-            a.skip_if_ge = skip; a.skip_threshold = skip_thr;
+            a.skip_if_ge = r.skip; a.skip_threshold = r.thr;
             ENG_OK(bofi::launch_rowgemm(a, s)); }
         return BOFI_OK;
     }
+    // One bounding iteration's row 0 from y1 (left by the previous bound_tail(..., BOUND_ATTN)) to the feed-forward output as *parts partial slabs
+    // in by3: the lean form when it applies, else query projection, cross-attention of the one query row over slot 0, W_o_src, w_1 and w_2 as the
+    // general kernels.  r: the early-out word of the loop this iteration belongs to.
+    int bound_chain(int B, int R, const int* att_len, const Rows& r, hipStream_t s, int* parts) {
+        const int rc = bound_chain_lean(B, R, att_len, r, s, parts);
+        if (rc >= 0) return rc;
+        const int dt = cfg.dtype, d = cfg.d_model;
+        ENG_OK(folded(y1, b_q_src, bq2, dt, d, B, r, s));
+        ENG_OK(bofi::launch_attention(cross_attn_args(bq2, 0, bctx2, B, 1, R, att_len, r), s));
+        ENG_OK(close_sublayer(bctx2, b_o_src, y2, B, r, s, y1.x, d));
+        ENG_OK(folded(y2, b_w1, bh, dt, cfg.d_ff, B, r, s, 1));
+        *parts = (cfg.d_ff % (4 * 128) == 0) ? 4 : 1;     // K = d_ff split 4 ways: 4x the workgroups, a quarter of the K loop
+        LinOpt o; o.residual = y2.x; o.ldr = d; o.rows = r; o.splitk = *parts;
+        return linear(bh, dt, cfg.d_ff, b_w2, by3, BOFI_DT_F32, d, B, o, s);
+    }
     // ---- row-block sublayer kernels (rowblock.hip, bf16 engine at the reference's width): the attention sublayer (attention + output
-    // projection + residual) and the feed-forward sublayer as one launch each.  Return -1 when the configuration or the shape is not
-    // theirs (the caller then runs the separate attention / GEMM launches), else a status.  want_copy: the next consumer is a
-    // LayerNorm-folded GEMM (it reads the compute-dtype copy and the row statistics); a following ffn_sublayer reads the stream itself.
+    // projection + residual) and the feed-forward sublayer as one launch each.  rb_attn / rb_ffn / fold_linear_rb return -1 when the
+    // configuration or the shape is not theirs, else a status; project / attn_sublayer / ffn_sublayer below own the fall-back to the separate
+    // attention / GEMM launches.  want_copy: the next consumer is a tiled LayerNorm-folded GEMM (it reads the compute-dtype copy and the row
+    // statistics); the row-block kernels read the float32 stream itself.  All of these run every row: a launch with an early-out word or a
+    // row list (Rows) goes through folded / close_sublayer / decoder_layer_tiled and never reaches a row-block kernel.
     bool rb_ok() const { return cfg.dtype == BOFI_DT_BF16 && cfg.d_model == 512 && cfg.heads == 8; }
     // the row-block kernels are a fixed latency chain per workgroup (one block of rows, the sublayer's whole weight stream): they pay
     // from a few thousand rows on, where the tiled GEMMs' prologue / epilogue and the hidden tensor's round trip cost more
@@ -472,16 +530,15 @@ struct bofi_engine {
                pj.Npad == 512 && !at.skip_if_ge && at.kdiv <= 1 && !at.q_start && !at.drop_thresh && !at.klen_sq && at.Lq <= 20 && at.Lk <= 32 && M >= rb_min_rows() &&
                !exp_skip("attn") && !exp_skip("qkv");
     }
-    int attn_sublayer(const bofi::AttnArgs& at, const Lin& o, float* x, void* xb, float* stats, bool want_copy, hipStream_t s, const Lin* pj = nullptr, void* pj_y = nullptr,
-                      int pj_ldy = 0) {
+    int rb_attn(const bofi::AttnArgs& at, const Lin& o, const Stream& t, bool want_copy, hipStream_t s, const Lin* pj, void* pj_y, int pj_ldy) {
         const bool on = BOFI_ENV_INT("BOFI_RB_ATTN", 1) != 0;
         if (exp_skip("attn")) return BOFI_OK;
         if (!on || !rb_ok() || !o.wp || at.skip_if_ge || at.kdiv > 1 || at.q_start || at.drop_thresh || at.B * at.Lq < rb_min_rows()) return -1;
         bofi::RbAttnArgs a{};
         a.q = (const uint16_t*)at.q; a.ldq = at.ldq; a.k = (const uint16_t*)at.k; a.ldk = at.ldk; a.v = (const uint16_t*)at.v; a.ldv = at.ldv;
         a.B = at.B; a.Lq = at.Lq; a.Lk = at.Lk; a.klen = at.klen; a.klen_sb = at.klen_sb; a.klen_sq = at.klen_sq; a.klen_bias = at.klen_bias;
-        a.klen_shared_last = at.klen_shared_last; a.wop = (const bofi::u32x4*)o.wp; a.bo = o.b; a.x = x; a.ldx = cfg.d_model; a.y = x; a.ldy = cfg.d_model;
-        a.yb = want_copy ? (uint16_t*)xb : nullptr; a.stats_out = want_copy ? stats : nullptr;
+        a.klen_shared_last = at.klen_shared_last; a.wop = (const bofi::u32x4*)o.wp; a.bo = o.b; a.x = t.x; a.ldx = cfg.d_model; a.y = t.x; a.ldy = cfg.d_model;
+        a.yb = want_copy ? (uint16_t*)t.xb : nullptr; a.stats_out = want_copy ? t.st : nullptr;
         a.alone = in_flight == 1;
         if (pj) { a.pj_wp = (const bofi::u32x4*)pj->wp; a.pj_c = pj->b; a.pj_cs = pj->cs; a.pj_y = (uint16_t*)pj_y; a.pj_ldy = pj_ldy; a.yb = nullptr; a.stats_out = nullptr; }
         return bofi::launch_rb_attn(a, s);
@@ -526,7 +583,9 @@ struct bofi_engine {
     // feed-forward sublayer directly behind the attention sublayer and no consumer of the bf16 copy / statistics.
     // Shapes the fused sublayer kernel does not take (more than 48 keys or 40 queries: real bottom-up features have up to 100 regions) are split at EVERY launch size: the
     // alternative there is the attention core + a tiled GEMM for W_o + the residual stream's round trip (profiles/r06_regions_sweep.txt).
-    bool attn_split_ok(const bofi::AttnArgs& at, const Lin& o, const Lin& w1, const Lin& w2) const {
+    // which: 1 = the encoder's self-attention, 2 = the filling pass's cross-attention (developer knob BOFI_RB_ATTN_SPLIT_WHICH, a mask of these; default both).
+    bool attn_split_ok(const bofi::AttnArgs& at, const Lin& o, const Lin& w1, const Lin& w2, int which) const {
+        if (!(BOFI_ENV_INT("BOFI_RB_ATTN_SPLIT_WHICH", 3) & which)) return false;
         const int v = BOFI_ENV_INT("BOFI_RB_ATTN_SPLIT", 1);
         const int M = at.B * at.Lq;
         const bool beyond = (at.Lq > 40 || at.Lk > 48) && M >= rb_min_rows();
@@ -534,8 +593,8 @@ struct bofi_engine {
                ffn_sublayer_ok(w1, w2, M) && !at.skip_if_ge && at.kdiv <= 1 &&
                !at.q_start && !at.drop_thresh && at.Lq <= 128 && at.Lk <= 128 && !exp_skip("attn") && !exp_skip("ffn");
     }
-    int ffn_sublayer(const Lin& w1, const Lin& w2, float* x, void* xb, float* stats, int M, hipStream_t s, const Lin* pj = nullptr, void* pj_y = nullptr,
-                     int pj_ldy = 0, const Lin* head = nullptr, const void* head_ctx = nullptr) {
+    int rb_ffn(const Lin& w1, const Lin& w2, float* x, void* xb, float* stats, int M, hipStream_t s, const Lin* pj, void* pj_y, int pj_ldy, const Lin* head,
+               const void* head_ctx) {
         if (!ffn_sublayer_ok(w1, w2, M)) return -1;
         if (exp_skip("ffn")) return BOFI_OK;
         bofi::RbFfnArgs a{};
@@ -545,6 +604,54 @@ struct bofi_engine {
         a.y = x; a.ldy = cfg.d_model; a.yb = (uint16_t*)xb; a.stats_out = stats; a.M = M; a.dff = cfg.d_ff;
         a.alone = in_flight == 1;
         return bofi::launch_rb_ffn(a, s);
+    }
+    // ---- one function per sublayer kind on ALL M rows of stream t: the row-block kernel when the shape is its, else the tiled launches
+    // y = l(LayerNorm(t)): y_f32 = float32 out (the generator), else the compute dtype
+    int project(const Stream& t, const Lin& l, void* y, int y_f32, int ldy, int M, hipStream_t s) {
+        const int rc = fold_linear_rb(t.x, l, y, y_f32, ldy, M, s);
+        return rc >= 0 ? rc : folded(t, l, y, y_f32 ? BOFI_DT_F32 : cfg.dtype, ldy, M, Rows{}, s);
+    }
+    // t += W_o . attention(at) + b_o.  split (attn_split_ok; the caller puts the feed-forward sublayer directly behind and hands it `o` as its head):
+    // only the light core runs here.  Else the fused kernel -- with pj, the projection that reads this sublayer's output next, as its tail when
+    // attn_proj_ok: *pj_made -- else attention core + closing GEMM (pj is then the caller's to make).
+    int attn_sublayer(const bofi::AttnArgs& at, const Lin& o, const Stream& t, bool want_copy, bool split, hipStream_t s, const Lin* pj = nullptr,
+                      void* pj_y = nullptr, int pj_ldy = 0, bool* pj_made = nullptr) {
+        if (split) return bofi::launch_attention(at, s);
+        const bool tail = pj && attn_proj_ok(at, o, *pj);
+        const int rc = rb_attn(at, o, t, want_copy, s, tail ? pj : nullptr, pj_y, pj_ldy);
+        if (pj_made) *pj_made = tail && rc == BOFI_OK;
+        if (rc >= 0) return rc;
+        ENG_OK(bofi::launch_attention(at, s));
+        return close_sublayer(at.out, o, t, at.B * at.Lq, Rows{}, s);
+    }
+    // t += w_2 . relu(w_1 . LayerNorm(t)).  head: the W_o of a split attention sublayer whose context rows are in ctx.  pj: the projection that reads
+    // this sublayer's output next; it rides the launch when nothing needs the copy and ffn_proj_ok: *pj_made (else it is the caller's to make).
+    int ffn_sublayer(const Lin& w1, const Lin& w2, const Stream& t, bool want_copy, int M, hipStream_t s, const Lin* head, const Lin* pj, void* pj_y,
+                     int pj_ldy, bool* pj_made) {
+        const bool tail = pj && !want_copy && ffn_proj_ok(w1, w2, *pj, M);
+        *pj_made = tail;
+        const int rc = rb_ffn(w1, w2, t.x, want_copy ? t.xb : nullptr, want_copy ? t.st : nullptr, M, s, tail ? pj : nullptr, tail ? pj_y : nullptr,
+                              tail ? pj_ldy : 0, head, ctx);
+        if (rc >= 0) return rc;
+        ENG_OK(folded(t, w1, hdn, cfg.dtype, cfg.d_ff, M, Rows{}, s, 1));
+        return close_sublayer(hdn, w2, t, M, Rows{}, s);
+    }
+    // One decoder layer as its eight tiled launches (q|k|v, self-attention, W_o, q_src, cross-attention over slot kv_i, o_src, w_1, w_2) on the rows r
+    // of stream t, B images of Lq rows: the dense bounding pass and the SAIC decoder pass, whose launches carry an early-out word / a row list.
+    // self_klen (+ bias): the self-attention's key prefix per (image, row) at pitch L.
+    int decoder_layer_tiled(const DecLayer& l, int kv_i, const Stream& t, void* qkv_buf, int B, int Lq, int R, const int* self_klen, int self_klen_bias,
+                            const int* att_len, const Rows& r, hipStream_t s) {
+        const int d = cfg.d_model, dt = cfg.dtype, M = B * Lq;
+        ENG_OK(folded(t, l.qkv, qkv_buf, dt, 3 * d, M, r, s));
+        bofi::AttnArgs a = self_attn_args(qkv_buf, B, Lq, r);
+        a.klen = self_klen; a.klen_sb = L; a.klen_sq = 1; a.klen_bias = self_klen_bias;
+        ENG_OK(bofi::launch_attention(a, s));
+        ENG_OK(close_sublayer(ctx, l.o, t, M, r, s));
+        ENG_OK(folded(t, l.q_src, qs, dt, d, M, r, s));
+        ENG_OK(bofi::launch_attention(cross_attn_args(qs, kv_i, ctx, B, Lq, R, att_len, r), s));
+        ENG_OK(close_sublayer(ctx, l.o_src, t, M, r, s));
+        ENG_OK(folded(t, l.w1, hdn, dt, cfg.d_ff, M, r, s, 1));
+        return close_sublayer(hdn, l.w2, t, M, r, s);
     }
     int enqueue_encode(const void* feats, int feats_dtype, const int* att_len, int B, int R, float* memory_out, hipStream_t s);
     int enqueue_bound_iter(int B, int R, const int* att_len, const int* ext_syn, const int* last, int update, float* len_logp,
@@ -562,100 +669,52 @@ struct bofi_engine {
 int bofi_engine::enqueue_encode(const void* feats, int feats_dtype, const int* att_len, int B, int R, float* memory_out,
                                 hipStream_t s) {
     const int d = cfg.d_model, dt = cfg.dtype, M = B * R;
-    cur_B = B;
     if (exp_skip("encoder")) return BOFI_OK;           // (experiments build: the whole encoder phase)
     // The residual stream x_enc stays float32; every GEMM that closes a sublayer also writes a copy in
-    // the compute dtype (xb_enc) and per-row partial sums (st_enc), from which the next pre-norm
-    // LayerNorm is applied inside the consuming GEMM's epilogue (no LayerNorm launches).
+    // the compute dtype and per-row partial sums, from which the next pre-norm LayerNorm is applied
+    // inside the consuming GEMM's epilogue (no LayerNorm launches).
     if (feats_dtype != dt) {                         // float32 features into a bf16 engine: one conversion pass
         ENG_OK(bofi::launch_cast_bf16((const float*)feats, feats_t, (size_t)M * cfg.feat, s));
         feats = feats_t; feats_dtype = dt;
     }
     {   // att_embed: Linear + ReLU, rows past an image's region count forced to 0 (AttModel.py:46-51)
-        LinOpt o; o.relu = 1; o.row_len = att_len; o.rpg = R; o.stats_out = st_enc; o.y2 = copy_t(xb_enc);
-        ENG_OK(linear(feats, feats_dtype, cfg.feat, att_embed, x_enc, BOFI_DT_F32, d, M, o, s));
+        LinOpt o; o.relu = 1; o.row_len = att_len; o.rpg = R; o.stats_out = x_enc.st; o.y2 = x_enc.copy();
+        ENG_OK(linear(feats, feats_dtype, cfg.feat, att_embed, x_enc.x, BOFI_DT_F32, d, M, o, s));
     }
-    const void* xa = stream_t(x_enc, xb_enc);
-    const bool memory_out_needs_copy = false;           // (memory_out is a LayerNorm of the float32 stream itself)
-    bool proj_made = false;                              // this layer's q|k|v (after the last layer: the cross K|V) came out of the previous feed-forward launch
+    bool proj_made = false;       // this layer's q|k|v (after the last layer: the cross K|V) came out of the previous feed-forward launch
     for (size_t li = 0; li < enc.size(); ++li) {
         auto& l = enc[li];
-        if (!proj_made) {
-            int rc = fold_linear_rb(x_enc, l.qkv, qkv, 0, 3 * d, M, s);
-            if (rc > 0) return rc;
-            if (rc < 0) { LinOpt o; o.ln_stats = st_enc; ENG_OK(linear(xa, dt, d, l.qkv, qkv, dt, 3 * d, M, o, s)); } }
-        bofi::AttnArgs a{};
-        a.q = qkv; a.k = (char*)qkv + (size_t)d * tsz; a.v = (char*)qkv + (size_t)2 * d * tsz;
-        a.ldq = a.ldk = a.ldv = 3 * d; a.out = ctx; a.ldo = d; a.dtype = dt; a.B = B; a.H = cfg.heads; a.Lq = R; a.Lk = R;
-        a.klen = att_len; a.klen_sb = 1; a.klen_sq = 0;
+        if (!proj_made) ENG_OK(project(x_enc, l.qkv, qkv, 0, 3 * d, M, s));
+        bofi::AttnArgs a = self_attn_args(qkv, B, R);
+        a.klen = att_len; a.klen_sb = 1;
         const bool ffn_rb = ffn_sublayer_ok(l.w1, l.w2, M);
-        const bool need_copy = !(fold_rb_ok(l.qkv, M) && fold_rb_ok(kv_all, M)) || memory_out_needs_copy;      // (consumers of this layer's output that read the copy + statistics: tiled GEMMs)
-        const bool split = ffn_rb && !need_copy && (BOFI_ENV_INT("BOFI_RB_ATTN_SPLIT_WHICH", 3) & 1) && attn_split_ok(a, l.o, l.w1, l.w2);      // attention core now, W_o + residual as the head of the feed-forward launch
-        int rc = split ? bofi::launch_attention(a, s) : attn_sublayer(a, l.o, x_enc, xb_enc, st_enc, !ffn_rb, s);
-        if (rc > 0) return rc;
-        if (rc < 0) {
-            ENG_OK(bofi::launch_attention(a, s));
-            LinOpt o; o.residual = x_enc; o.ldr = d; o.stats_out = st_enc; o.y2 = copy_t(xb_enc);
-            ENG_OK(linear(ctx, dt, d, l.o, x_enc, BOFI_DT_F32, d, M, o, s));
-        }
-        {   // the consumers of this layer's output: the next layer's q|k|v (or the stacked cross K|V): tiled GEMMs read the copy + statistics
-            const bool last = li + 1 == enc.size();
-            const Lin& nxt = last ? kv_all : enc[li + 1].qkv;
-            proj_made = !need_copy && ffn_proj_ok(l.w1, l.w2, nxt, M);
-            const Lin* head = split ? &l.o : nullptr;
-            rc = !ffn_rb ? -1 : proj_made ? ffn_sublayer(l.w1, l.w2, x_enc, nullptr, nullptr, M, s, &nxt, last ? kv : qkv, last ? kv_all.N : 3 * d, head, ctx)
-                                          : ffn_sublayer(l.w1, l.w2, x_enc, need_copy ? xb_enc : nullptr, need_copy ? st_enc : nullptr, M, s, nullptr, nullptr, 0, head, ctx); }
-        if (rc > 0) return rc;
-        if (rc < 0) {
-            { LinOpt o; o.relu = 1; o.ln_stats = st_enc; ENG_OK(linear(xa, dt, d, l.w1, hdn, dt, cfg.d_ff, M, o, s)); }
-            { LinOpt o; o.residual = x_enc; o.ldr = d; o.stats_out = st_enc; o.y2 = copy_t(xb_enc);
-              ENG_OK(linear(hdn, dt, cfg.d_ff, l.w2, x_enc, BOFI_DT_F32, d, M, o, s)); }
-        }
+        // (consumers of this layer's output that read the copy + statistics: tiled GEMMs; memory_out is a LayerNorm of the float32 stream itself)
+        const bool need_copy = !(fold_rb_ok(l.qkv, M) && fold_rb_ok(kv_all, M));
+        // split: the attention core now, W_o + residual as the head of the feed-forward launch
+        const bool split = ffn_rb && !need_copy && attn_split_ok(a, l.o, l.w1, l.w2, 1);
+        ENG_OK(attn_sublayer(a, l.o, x_enc, !ffn_rb, split, s));
+        // the consumer of this layer's output: the next layer's q|k|v, or the stacked cross K|V
+        const bool last = li + 1 == enc.size();
+        const Lin& nxt = last ? kv_all : enc[li + 1].qkv;
+        ENG_OK(ffn_sublayer(l.w1, l.w2, x_enc, need_copy, M, s, split ? &l.o : nullptr, &nxt, last ? kv : qkv, last ? kv_all.N : 3 * d, &proj_made));
     }
-    if (memory_out) ENG_OK(bofi::launch_layernorm(x_enc, enc_norm.g, enc_norm.b, memory_out, BOFI_DT_F32, M, d, s));
+    if (memory_out) ENG_OK(bofi::launch_layernorm(x_enc.x, enc_norm.g, enc_norm.b, memory_out, BOFI_DT_F32, M, d, s));
     // cross-attention K|V of the bound layer and of every decoder layer in one GEMM on memory =
     // encoder.norm(x_enc), the norm folded in
-    if (!proj_made) {
-        int rc = fold_linear_rb(x_enc, kv_all, kv, 0, kv_all.N, M, s);
-        if (rc > 0) return rc;
-        if (rc < 0) { LinOpt o; o.ln_stats = st_enc; ENG_OK(linear(xa, dt, d, kv_all, kv, dt, kv_all.N, M, o, s)); } }
+    if (!proj_made) ENG_OK(project(x_enc, kv_all, kv, 0, kv_all.N, M, s));
     return BOFI_OK;
 }
 
 int bofi_engine::enqueue_bound_iter(int B, int R, const int* att_len, const int* ext_syn, const int* last, int update,
                                     float* len_logp, float* syn_logp, bool early, hipStream_t s) {
-    // One bounding iteration AFTER the row-0 self-attention sublayer output y1 (by1, its copy byb and row statistics st_b)
+    // One bounding iteration AFTER the row-0 self-attention sublayer output y1 (with its copy and row statistics)
     // has been produced by the previous bound_tail(..., BOUND_ATTN).
-    const int d = cfg.d_model, dt = cfg.dtype;
-    cur_B = B;
     if (exp_skip("loop")) return BOFI_OK;
-    {   // bf16 at the reference's width: the four stages as the direct-operand kernels of bound_ops.hip
-        int parts = 0;
-        const int rc = bound_chain_lean(B, R, att_len, early ? st.counters : nullptr, B, s, &parts);
-        if (rc > 0) return rc;
-        if (rc == 0) {
-            const int flags = BOUND_HEADS | (update ? (BOUND_UPDATE | BOUND_ATTN) : 0) | (early ? BOUND_EARLY : 0);
-            return bound_tail(by3, parts, update ? nullptr : ext_syn, update ? nullptr : last, B, flags, len_logp, syn_logp, s);
-        }
-    }
-    { LinOpt o; o.early = early; o.ln_stats = st_b; ENG_OK(linear(stream_t(by1, byb), dt, d, b_q_src, bq2, dt, d, B, o, s)); }
-    {
-    bofi::AttnArgs a{};
-    a.q = bq2; a.ldq = d; a.k = kv; a.v = (char*)kv + (size_t)d * tsz; a.ldk = a.ldv = kv_all.N;
-    a.out = bctx2; a.ldo = d; a.dtype = dt; a.B = B; a.H = cfg.heads; a.Lq = 1; a.Lk = R;
-    a.klen = att_len; a.klen_sb = 1; a.klen_sq = 0;
-    if (early) { a.skip_if_ge = st.counters; a.skip_threshold = B; }
-    ENG_OK(bofi::launch_attention(a, s));
-    }
-    { LinOpt o; o.residual = by1; o.ldr = d; o.early = early; o.stats_out = st_b; o.y2 = copy_t(byb);
-      ENG_OK(linear(bctx2, dt, d, b_o_src, by2, BOFI_DT_F32, d, B, o, s)); }
-    { LinOpt o; o.relu = 1; o.early = early; o.ln_stats = st_b; ENG_OK(linear(stream_t(by2, byb), dt, d, b_w1, bh, dt, cfg.d_ff, B, o, s)); }
-    const int w2parts = (cfg.d_ff % (4 * 128) == 0) ? 4 : 1;     // K = d_ff split 4 ways: 4x the workgroups, a quarter of the K loop
-    { LinOpt o; o.residual = by2; o.ldr = d; o.early = early; o.splitk = w2parts; ENG_OK(linear(bh, dt, cfg.d_ff, b_w2, by3, BOFI_DT_F32, d, B, o, s)); }
+    int parts = 0;
+    ENG_OK(bound_chain(B, R, att_len, early ? Rows{st.counters, B} : Rows{}, s, &parts));
     // heads + bookkeeping, fused with the next iteration's row-0 self-attention
     const int flags = BOUND_HEADS | (update ? (BOUND_UPDATE | BOUND_ATTN) : 0) | (early ? BOUND_EARLY : 0);
-    ENG_OK(bound_tail(by3, w2parts, update ? nullptr : ext_syn, update ? nullptr : last, B, flags, len_logp, syn_logp, s));
-    return BOFI_OK;
+    return bound_tail(by3, parts, update ? nullptr : ext_syn, update ? nullptr : last, B, flags, len_logp, syn_logp, s);
 }
 
 // The bounding loop in its dense form (LengthPredictor_UIC.forward TransformerModel.py:357-383 as the reference runs it): per
@@ -665,36 +724,14 @@ int bofi_engine::enqueue_bound_iter(int B, int R, const int* att_len, const int*
 // Needed for N_len >= 2, where the upper layers read the lower layers' outputs of every visible row; with
 // BOFI_BOUND_DENSE=1 it also serves N_len = 1 as a cross-check of the incremental form.
 int bofi_engine::enqueue_bound_dense(const int* att_len, int B, int R, hipStream_t s) {
-    const int d = cfg.d_model, dt = cfg.dtype, S = cfg.seq_length, M = B * L;
-    cur_B = B;
-    const void* xa = stream_t(xw, xwb);
+    const int d = cfg.d_model, S = cfg.seq_length;
+    const Rows live{st.counters, B};               // every launch returns at once when all B images are finished
     for (int it = 0; it < S; ++it) {
         // input rows: the syntactic table stands where launch_embed_rows takes the word table (no second term)
-        ENG_OK(bofi::launch_embed_rows(lut_syn, nullptr, pe, st.ext_syn, nullptr, L, 0, B, L, d, 0, xw, copy_t(xwb), dt, st_w, nullptr, s));
-        for (size_t li = 0; li < blay.size(); ++li) {
-            auto& l = blay[li];
-            { LinOpt o; o.early = true; o.ln_stats = st_w; ENG_OK(linear(xa, dt, d, l.qkv, qkv, dt, 3 * d, M, o, s)); }
-            bofi::AttnArgs a{};
-            a.q = qkv; a.k = (char*)qkv + (size_t)d * tsz; a.v = (char*)qkv + (size_t)2 * d * tsz;
-            a.ldq = a.ldk = a.ldv = 3 * d; a.out = ctx; a.ldo = d; a.dtype = dt; a.B = B; a.H = cfg.heads; a.Lq = L; a.Lk = L;
-            a.klen = st.klen; a.klen_sb = L; a.klen_sq = 1; a.skip_if_ge = st.counters; a.skip_threshold = B;
-            ENG_OK(bofi::launch_attention(a, s));
-            { LinOpt o; o.early = true; o.residual = xw; o.ldr = d; o.stats_out = st_w; o.y2 = copy_t(xwb);
-              ENG_OK(linear(ctx, dt, d, l.o, xw, BOFI_DT_F32, d, M, o, s)); }
-            { LinOpt o; o.early = true; o.ln_stats = st_w; ENG_OK(linear(xa, dt, d, l.q_src, qs, dt, d, M, o, s)); }
-            bofi::AttnArgs c{};
-            c.q = qs; c.ldq = d;
-            c.k = (char*)kv + (size_t)li * 2 * d * tsz; c.v = (char*)kv + ((size_t)li * 2 * d + d) * tsz;
-            c.ldk = c.ldv = kv_all.N; c.out = ctx; c.ldo = d; c.dtype = dt; c.B = B; c.H = cfg.heads; c.Lq = L; c.Lk = R;
-            c.klen = att_len; c.klen_sb = 1; c.klen_sq = 0; c.skip_if_ge = st.counters; c.skip_threshold = B;
-            ENG_OK(bofi::launch_attention(c, s));
-            { LinOpt o; o.early = true; o.residual = xw; o.ldr = d; o.stats_out = st_w; o.y2 = copy_t(xwb);
-              ENG_OK(linear(ctx, dt, d, l.o_src, xw, BOFI_DT_F32, d, M, o, s)); }
-            { LinOpt o; o.early = true; o.relu = 1; o.ln_stats = st_w; ENG_OK(linear(xa, dt, d, l.w1, hdn, dt, cfg.d_ff, M, o, s)); }
-            { LinOpt o; o.early = true; o.residual = xw; o.ldr = d; o.stats_out = st_w; o.y2 = copy_t(xwb);
-              ENG_OK(linear(hdn, dt, cfg.d_ff, l.w2, xw, BOFI_DT_F32, d, M, o, s)); }
-        }
-        ENG_OK(bound_tail(xw, 1, nullptr, nullptr, B, BOUND_HEADS | BOUND_UPDATE | BOUND_EARLY, nullptr, nullptr, s, false, 0, L * d));
+        ENG_OK(bofi::launch_embed_rows(lut_syn, nullptr, pe, st.ext_syn, nullptr, L, 0, B, L, d, 0, xw.x, xw.copy(), cfg.dtype, xw.st, nullptr, s));
+        for (size_t li = 0; li < blay.size(); ++li)
+            ENG_OK(decoder_layer_tiled(blay[li], (int)li, xw, qkv, B, L, R, st.klen, 0, att_len, live, s));
+        ENG_OK(bound_tail(xw.x, 1, nullptr, nullptr, B, BOUND_HEADS | BOUND_UPDATE | BOUND_EARLY, nullptr, nullptr, s, false, 0, L * d));
     }
     return BOFI_OK;
 }
@@ -706,7 +743,6 @@ int bofi_engine::enqueue_decode(const void* feats, int feats_dtype, const int* a
     // phases (BOFI_FLAG_PHASE_*): none of the bits = the whole decode; else only the named parts (a pipelining caller enqueues them as separate calls)
     const int ph = flags & (BOFI_FLAG_PHASE_ENCODE | BOFI_FLAG_PHASE_BOUND | BOFI_FLAG_PHASE_FILL);
     const bool do_enc = !ph || (ph & BOFI_FLAG_PHASE_ENCODE), do_bound = !ph || (ph & BOFI_FLAG_PHASE_BOUND), do_fill = !ph || (ph & BOFI_FLAG_PHASE_FILL);
-    cur_B = B;
     if (do_enc) ENG_OK(enqueue_encode(feats, feats_dtype, att_len, B, R, memory_out, s));
     // ---- bounding pass (core_NAIC TransformerModel.py:1833-1870)
     if (do_bound) {
@@ -745,75 +781,37 @@ int bofi_engine::enqueue_fill(const int* att_len, int B, int R, int flags, int64
     const int d = cfg.d_model, dt = cfg.dtype, S = cfg.seq_length, M = B * S;
     if (exp_skip("filling")) return BOFI_OK;           // (experiments build: the whole filling pass incl. the vocabulary epilogue)
     const int rounds = 1 + ((flags >> BOFI_FLAG_REFINE_SHIFT) & 15);
-    const void* xa = stream_t(x_fill, xb_fill);
     float* lg = seq_logprob ? seq_logprob : logits;
     const int gen_pad = BOFI_ENV_INT("BOFI_GEN_PAD", 1);      // developer knob: 0 = in place, one-tile kernel
     const bool gen_rb = gen_pad && logits_pad && fold_rb_ok(gen, M);
     for (int round = 0; round < rounds; ++round) {
     // (round 0 under the row-block family: layer 0's q|k|v rows come out of the (label, position) table with the embedding launch -- BOFI_FILL_QKV_TAB=0: the projection)
     const bool qkv_tab = round == 0 && fill_tab_ready && !dec.empty() && fold_rb_ok(dec[0].qkv, M) && BOFI_ENV_INT("BOFI_FILL_QKV_TAB", 1) != 0 && !exp_skip("qkv");
-    ENG_OK(bofi::launch_embed_fill(lut_tok, lut_syn, pe, st.ext_syn, round ? seq : nullptr, B, S, L, d, cfg.bos_idx, x_fill, copy_t(xb_fill), dt,
-                                   st_fill, s, qkv_tab ? f_qkv0 : nullptr, qkv_tab ? qkv : nullptr, 3 * d));
+    ENG_OK(bofi::launch_embed_fill(lut_tok, lut_syn, pe, st.ext_syn, round ? seq : nullptr, B, S, L, d, cfg.bos_idx, x_fill.x, x_fill.copy(), dt,
+                                   x_fill.st, s, qkv_tab ? f_qkv0 : nullptr, qkv_tab ? qkv : nullptr, 3 * d));
     bool proj_made = qkv_tab;                            // this layer's q|k|v came out of the previous layer's feed-forward launch (layer 0: out of the table)
     for (size_t li = 0; li < dec.size(); ++li) {
         auto& l = dec[li];
-        if (!proj_made) {
-            int rc = fold_linear_rb(x_fill, l.qkv, qkv, 0, 3 * d, M, s);
-            if (rc > 0) return rc;
-            if (rc < 0) { LinOpt o; o.ln_stats = st_fill; ENG_OK(linear(xa, dt, d, l.qkv, qkv, dt, 3 * d, M, o, s)); } }
-        bofi::AttnArgs a{};
-        a.q = qkv; a.k = (char*)qkv + (size_t)d * tsz; a.v = (char*)qkv + (size_t)2 * d * tsz;
-        a.ldq = a.ldk = a.ldv = 3 * d; a.out = ctx; a.ldo = d; a.dtype = dt; a.B = B; a.H = cfg.heads; a.Lq = S; a.Lk = S;
+        if (!proj_made) ENG_OK(project(x_fill, l.qkv, qkv, 0, 3 * d, M, s));
+        bofi::AttnArgs a = self_attn_args(qkv, B, S);
         // syn_mask[i, :, :last-1] = True; strict mode reproduces the stale index of :1872-1873 (quirk Q1)
-        a.klen = st.last; a.klen_sb = 1; a.klen_sq = 0; a.klen_bias = -1;
+        a.klen = st.last; a.klen_sb = 1; a.klen_bias = -1;
         a.klen_shared_last = (flags & BOFI_FLAG_STRICT_Q1) ? (q1_group > 0 ? q1_group : B) : 0;
         const bool q_rb = fold_rb_ok(l.q_src, M);
         const bool ffn_rb = ffn_sublayer_ok(l.w1, l.w2, M);
         const bool need_copy_out = !(fold_rb_ok(l.qkv, M) && gen_rb);      // (a consumer of this layer's output reads the bf16 copy + statistics: a tiled GEMM)
-        bool cross_split = false;
         // (round 5's one-launch form of both attention sublayers, rb_dec_attn_kernel, lost 3 % in flight and left the library in round 6: dev/exp/rb_dec_attn_kernel.inc)
-        int rc;
-        {                                                    // attention sublayer (+ folded query projection) + attention sublayer
-        const bool q_tail = attn_proj_ok(a, l.o, l.q_src);      // the cross-attention's query projection rides the self-attention launch
-        rc = q_tail ? attn_sublayer(a, l.o, x_fill, nullptr, nullptr, false, s, &l.q_src, qs, d)
-                    : attn_sublayer(a, l.o, x_fill, xb_fill, st_fill, !q_rb, s);   // (the query projection behind it is a folded GEMM)
-        if (rc > 0) return rc;
-        if (rc < 0) {
-            ENG_OK(bofi::launch_attention(a, s));
-            LinOpt o; o.residual = x_fill; o.ldr = d; o.stats_out = st_fill; o.y2 = copy_t(xb_fill);
-            ENG_OK(linear(ctx, dt, d, l.o, x_fill, BOFI_DT_F32, d, M, o, s));
-        }
-        if (!(q_tail && rc == 0)) {
-        rc = fold_linear_rb(x_fill, l.q_src, qs, 0, d, M, s);
-        if (rc > 0) return rc;
-        if (rc < 0) { LinOpt o; o.ln_stats = st_fill; ENG_OK(linear(xa, dt, d, l.q_src, qs, dt, d, M, o, s)); }
-        }
-        bofi::AttnArgs c{};
-        c.q = qs; c.ldq = d;
-        c.k = (char*)kv + (size_t)(n_len + li) * 2 * d * tsz; c.v = (char*)kv + ((size_t)(n_len + li) * 2 * d + d) * tsz;
-        c.ldk = c.ldv = kv_all.N; c.out = ctx; c.ldo = d; c.dtype = dt; c.B = B; c.H = cfg.heads; c.Lq = S; c.Lk = R;
-        c.klen = att_len; c.klen_sb = 1; c.klen_sq = 0;
-        cross_split = ffn_rb && !need_copy_out && (BOFI_ENV_INT("BOFI_RB_ATTN_SPLIT_WHICH", 3) & 2) && attn_split_ok(c, l.o_src, l.w1, l.w2);      // the cross-attention's core now, its W_o + residual as the head of the feed-forward launch
-        rc = cross_split ? bofi::launch_attention(c, s) : attn_sublayer(c, l.o_src, x_fill, xb_fill, st_fill, !ffn_rb, s);
-        if (rc > 0) return rc;
-        if (rc < 0) {
-            ENG_OK(bofi::launch_attention(c, s));
-            LinOpt o; o.residual = x_fill; o.ldr = d; o.stats_out = st_fill; o.y2 = copy_t(xb_fill);
-            ENG_OK(linear(ctx, dt, d, l.o_src, x_fill, BOFI_DT_F32, d, M, o, s));
-        }
-        }
-        {   // next consumer: the next layer's q|k|v or the generator
-            const bool need_copy = need_copy_out;
-            proj_made = !need_copy && li + 1 < dec.size() && ffn_proj_ok(l.w1, l.w2, dec[li + 1].qkv, M);
-            const Lin* head = cross_split ? &l.o_src : nullptr;
-            rc = !ffn_rb ? -1 : proj_made ? ffn_sublayer(l.w1, l.w2, x_fill, nullptr, nullptr, M, s, &dec[li + 1].qkv, qkv, 3 * d, head, ctx)
-                                          : ffn_sublayer(l.w1, l.w2, x_fill, need_copy ? xb_fill : nullptr, need_copy ? st_fill : nullptr, M, s, nullptr, nullptr, 0, head, ctx); }
-        if (rc > 0) return rc;
-        if (rc < 0) {
-            { LinOpt o; o.relu = 1; o.ln_stats = st_fill; ENG_OK(linear(xa, dt, d, l.w1, hdn, dt, cfg.d_ff, M, o, s)); }
-            { LinOpt o; o.residual = x_fill; o.ldr = d; o.stats_out = st_fill; o.y2 = copy_t(xb_fill);
-              ENG_OK(linear(hdn, dt, cfg.d_ff, l.w2, x_fill, BOFI_DT_F32, d, M, o, s)); }
-        }
+        // self-attention; the cross-attention's query projection rides its launch, or is a folded GEMM behind it
+        bool q_made = false;
+        ENG_OK(attn_sublayer(a, l.o, x_fill, !q_rb, false, s, &l.q_src, qs, d, &q_made));
+        if (!q_made) ENG_OK(project(x_fill, l.q_src, qs, 0, d, M, s));
+        const bofi::AttnArgs c = cross_attn_args(qs, n_len + (int)li, ctx, B, S, R, att_len);
+        // split: the cross-attention's core now, its W_o + residual as the head of the feed-forward launch
+        const bool cross_split = ffn_rb && !need_copy_out && attn_split_ok(c, l.o_src, l.w1, l.w2, 2);
+        ENG_OK(attn_sublayer(c, l.o_src, x_fill, !ffn_rb, cross_split, s));
+        // next consumer: the next layer's q|k|v (it may ride the feed-forward launch) or the generator
+        const Lin* nxt = li + 1 < dec.size() ? &dec[li + 1].qkv : nullptr;
+        ENG_OK(ffn_sublayer(l.w1, l.w2, x_fill, need_copy_out, M, s, cross_split ? &l.o_src : nullptr, nxt, qkv, 3 * d, &proj_made));
     }
     // ---- vocabulary projection (decoder.norm folded in), log-softmax, greedy pick, pad tail
     // generator.  V = 9 491 is not a whole number of 128-column tiles and its rows are not 16-byte aligned: the bf16 engine runs the GEMM
@@ -821,16 +819,11 @@ int bofi_engine::enqueue_fill(const int* att_len, int B, int R, int flags, int64
     // that, writing the log-probs at the caller's pitch V -- the same reads and writes as in place.
     const float* lsrc = nullptr;
     if (gen_pad && logits_pad) {
-        int rc = fold_linear_rb(x_fill, gen, logits_pad, 1, gen.Npad, M, s);
-        if (rc > 0) return rc;
-        if (rc < 0) {
-            Lin gp = gen; gp.N = gen.Npad;
-            LinOpt o; o.ln_stats = st_fill;
-            ENG_OK(linear(xa, dt, d, gp, logits_pad, BOFI_DT_F32, gen.Npad, M, o, s));
-        }
+        Lin gp = gen; gp.N = gen.Npad;                   // (the tiled form computes the zero columns too; the row-block kernel takes Npad anyway)
+        ENG_OK(project(x_fill, gp, logits_pad, 1, gen.Npad, M, s));
         lsrc = logits_pad;
     } else {
-        LinOpt o; o.ln_stats = st_fill; ENG_OK(linear(xa, dt, d, gen, lg, BOFI_DT_F32, cfg.vocab, M, o, s));
+        ENG_OK(folded(x_fill, gen, lg, BOFI_DT_F32, cfg.vocab, M, Rows{}, s));
     }
     // (a round that another one follows: its ids are all the next round reads -- the log-probs it would write are overwritten: not stored)
     const int ids_only_on = BOFI_ENV_INT("BOFI_REFINE_IDS_ONLY", 1);      // developer knob: 0 = every round stores its log-probs
@@ -858,8 +851,7 @@ int bofi_engine::enqueue_decode_saic(const void* feats, int feats_dtype, const i
     ENG_OK(bofi::launch_saic_init(st, sa, B, L, cfg.pad_idx, cfg.bos_idx, cfg.len_idx, s));
     if (seq_logprob) ENG_OK(bofi::launch_zero_f32(seq_logprob, (size_t)M * cfg.vocab, s));   // seq_logprobs = zeros (:1883); not a memset node
     }
-    const void* xwa = stream_t(xw, xwb);
-    const void* xa = stream_t(x_fill, xb_fill);
+    const Rows halted{halt, 1};                    // every launch of an iteration returns at once when the loop has ended
     for (int it = it_first; it <= it_last; ++it) {
         // From the second iteration on only the rows of the phrases placed in this iteration go through the decoder's GEMMs and the
         // vocabulary epilogue (row list; launch_saic_rows): a placed row's input, key set and therefore its K / V in every layer
@@ -869,52 +861,34 @@ int bofi_engine::enqueue_decode_saic(const void* feats, int feats_dtype, const i
         const bool rowlist = saic_cache && it >= 2;
         const int* ri = rowlist ? sa_rows : nullptr;
         const int* rn = rowlist ? sa_nrows : nullptr;
+        const Rows rows{halt, 1, ri, rn};
         // ---- bounding step on the words: K|V of all L rows, row-0 query attends keys < phrase_last
-        ENG_OK(bofi::launch_embed_rows(lut_tok, nullptr, pe, sa.ext_len, nullptr, L, 0, B, L, d, cfg.bos_idx, xw, copy_t(xwb), dt, st_w, halt, s));
-        { LinOpt o; o.halt = true; o.ln_stats = st_w; ENG_OK(linear(xwa, dt, d, b_kv_self, kvs, dt, 2 * d, B * L, o, s)); }
+        ENG_OK(bofi::launch_embed_rows(lut_tok, nullptr, pe, sa.ext_len, nullptr, L, 0, B, L, d, cfg.bos_idx, xw.x, xw.copy(), dt, xw.st, halt, s));
+        ENG_OK(folded(xw, b_kv_self, kvs, dt, 2 * d, B * L, halted, s));
         {
-            bofi::AttnArgs a{};
-            a.q = b_q0_sa; a.ldq = 0; a.k = kvs; a.v = (char*)kvs + (size_t)d * tsz; a.ldk = a.ldv = 2 * d;
-            a.out = bctx; a.ldo = d; a.dtype = dt; a.B = B; a.H = cfg.heads; a.Lq = 1; a.Lk = L;
-            a.klen = st.last; a.klen_sb = 1; a.klen_sq = 0; a.skip_if_ge = halt; a.skip_threshold = 1;
+            bofi::AttnArgs a = attn_args(b_q0_sa, 0, kvs, 2 * d, bctx, B, 1, L, halted);
+            a.klen = st.last; a.klen_sb = 1;
             ENG_OK(bofi::launch_attention(a, s));
         }
-        { LinOpt o; o.residual = b_x0_sa; o.ldr = 0; o.halt = true; o.stats_out = st_b; o.y2 = copy_t(byb);
-          ENG_OK(linear(bctx, dt, d, b_o_self, by1, BOFI_DT_F32, d, B, o, s)); }
+        ENG_OK(close_sublayer(bctx, b_o_self, y1, B, halted, s, b_x0_sa, 0));
         int w2parts = 0;
-        const int lean_rc = bound_chain_lean(B, R, att_len, halt, 1, s, &w2parts);
-        if (lean_rc > 0) return lean_rc;
-        if (lean_rc < 0) {
-            { LinOpt o; o.halt = true; o.ln_stats = st_b; ENG_OK(linear(stream_t(by1, byb), dt, d, b_q_src, bq2, dt, d, B, o, s)); }
-            {
-                bofi::AttnArgs a{};
-                a.q = bq2; a.ldq = d; a.k = kv; a.v = (char*)kv + (size_t)d * tsz; a.ldk = a.ldv = kv_all.N;
-                a.out = bctx2; a.ldo = d; a.dtype = dt; a.B = B; a.H = cfg.heads; a.Lq = 1; a.Lk = R;
-                a.klen = att_len; a.klen_sb = 1; a.klen_sq = 0; a.skip_if_ge = halt; a.skip_threshold = 1;
-                ENG_OK(bofi::launch_attention(a, s));
-            }
-            { LinOpt o; o.residual = by1; o.ldr = d; o.halt = true; o.stats_out = st_b; o.y2 = copy_t(byb);
-              ENG_OK(linear(bctx2, dt, d, b_o_src, by2, BOFI_DT_F32, d, B, o, s)); }
-            { LinOpt o; o.relu = 1; o.halt = true; o.ln_stats = st_b; ENG_OK(linear(stream_t(by2, byb), dt, d, b_w1, bh, dt, cfg.d_ff, B, o, s)); }
-            w2parts = (cfg.d_ff % (4 * 128) == 0) ? 4 : 1;
-            { LinOpt o; o.residual = by2; o.ldr = d; o.halt = true; o.splitk = w2parts; ENG_OK(linear(bh, dt, cfg.d_ff, b_w2, by3, BOFI_DT_F32, d, B, o, s)); }
-        }
+        ENG_OK(bound_chain(B, R, att_len, halted, s, &w2parts));
         ENG_OK(bound_tail(by3, w2parts, nullptr, nullptr, B, BOUND_HEADS | BOUND_UPDATE | BOUND_SAIC | BOUND_EARLY, nullptr, nullptr, s, true, it));
         if (flags & BOFI_FLAG_SAIC_LAYOUT_ONLY) {      // the caller draws this phrase's words itself (bofi_engine_saic_put_words before the next call): layout + positions only
             ENG_OK(bofi::launch_saic_halt(st, sa, B, L, it, s));
             continue;
         }
         // ---- decoder pass over all S positions (decode_SA :520-530) with the phrase-block mask as per-row key prefixes
-        ENG_OK(bofi::launch_embed_rows(lut_tok, lut_syn, pe, sa.ext_phrase, st.ext_syn, L, 1, B, S, d, cfg.bos_idx, x_fill, copy_t(xb_fill), dt,
-                                       st_fill, halt, s));
+        ENG_OK(bofi::launch_embed_rows(lut_tok, lut_syn, pe, sa.ext_phrase, st.ext_syn, L, 1, B, S, d, cfg.bos_idx, x_fill.x, x_fill.copy(), dt,
+                                       x_fill.st, halt, s));
         if (rowlist) ENG_OK(bofi::launch_saic_rows(st, B, L, S, it, sa_rows, sa_nrows, s));
         // the row-list iterations in bf16 at the reference's width: a layer's six GEMMs as direct-operand row GEMMs (bound_ops.hip: no LDS
         // staging, ~5 us per launch whatever the few hundred rows), query projection + cross-attention as one launch; their row
         // statistics come in 16-column groups (st_fill16)
         const bool lean = rowlist && saic_lean && dt == BOFI_DT_BF16 && d == 512 && cfg.heads == 8 && R <= 64 && cfg.d_ff % 512 == 0;
-        const float* fin_stats = st_fill; int fin_groups = 0;
+        Stream fin = x_fill;                                           // what the generator reads: the lean launches leave statistics of their own
         if (lean) {
-            const float* cst = st_fill; int cg = d / 32;               // statistics of the rows' current stream: where, and in how many groups
+            const float* cst = x_fill.st; int cg = d / 32;               // statistics of the rows' current stream: where, and in how many groups
             auto rg = [&](const void* x, int ldx, const Lin& l, const float* stats, int groups, const float* residual, float* y, void* yb,
                           int ldyb, float* stats_out, int relu) {
                 bofi::RowGemmArgs a{};
@@ -927,53 +901,29 @@ int bofi_engine::enqueue_decode_saic(const void* feats, int feats_dtype, const i
             for (size_t li = 0; li < dec.size(); ++li) {
                 auto& l = dec[li];
                 void* qkv = qkv_dec[li];
-                ENG_OK(rg(xb_fill, d, l.qkv, cst, cg, nullptr, nullptr, qkv, 3 * d, nullptr, 0));
-                bofi::AttnArgs a{};
-                a.q = qkv; a.k = (char*)qkv + (size_t)d * tsz; a.v = (char*)qkv + (size_t)2 * d * tsz;
-                a.ldq = a.ldk = a.ldv = 3 * d; a.out = ctx; a.ldo = d; a.dtype = dt; a.B = B; a.H = cfg.heads; a.Lq = S; a.Lk = S;
-                a.klen = sa.klen_dec + 1; a.klen_sb = L; a.klen_sq = 1; a.klen_bias = -1; a.skip_if_ge = halt; a.skip_threshold = 1;
+                ENG_OK(rg(x_fill.xb, d, l.qkv, cst, cg, nullptr, nullptr, qkv, 3 * d, nullptr, 0));
+                bofi::AttnArgs a = self_attn_args(qkv, B, S, halted);
+                a.klen = sa.klen_dec + 1; a.klen_sb = L; a.klen_sq = 1; a.klen_bias = -1;      // (as in the tiled form below)
                 ENG_OK(bofi::launch_attention(a, s));
-                ENG_OK(rg(ctx, d, l.o, nullptr, 0, x_fill, x_fill, xb_fill, d, st_fill16, 0));
+                ENG_OK(rg(ctx, d, l.o, nullptr, 0, x_fill.x, x_fill.x, x_fill.xb, d, st_fill16, 0));
                 cst = st_fill16; cg = d / 16;
                 {   bofi::BoundQAttnArgs q{};
-                    q.x = (const uint16_t*)xb_fill; q.stats = cst; q.stats_groups = cg; q.wq = (const uint16_t*)l.q_src.w; q.bias = l.q_src.b; q.colsum = l.q_src.cs;
-                    q.k = (const uint16_t*)kv + (size_t)(n_len + li) * 2 * d; q.v = q.k + d; q.ldkv = kv_all.N; q.att_len = att_len; q.out = (uint16_t*)ctx;
+                    q.x = (const uint16_t*)x_fill.xb; q.stats = cst; q.stats_groups = cg; q.wq = (const uint16_t*)l.q_src.w; q.bias = l.q_src.b; q.colsum = l.q_src.cs;
+                    q.k = (const uint16_t*)kv_slot(n_len + (int)li); q.v = q.k + d; q.ldkv = kv_all.N; q.att_len = att_len; q.out = (uint16_t*)ctx;
                     q.B = M; q.R = R; q.d = d; q.H = cfg.heads; q.skip_if_ge = halt; q.skip_threshold = 1;
                     q.row_idx = ri; q.n_rows = rn; q.rows_per_image = S;
                     ENG_OK(bofi::launch_bound_qattn(q, s)); }
-                ENG_OK(rg(ctx, d, l.o_src, nullptr, 0, x_fill, x_fill, xb_fill, d, st_fill16, 0));
-                ENG_OK(rg(xb_fill, d, l.w1, cst, cg, nullptr, nullptr, hdn, cfg.d_ff, nullptr, 1));
-                ENG_OK(rg(hdn, cfg.d_ff, l.w2, nullptr, 0, x_fill, x_fill, xb_fill, d, st_fill16, 0));
+                ENG_OK(rg(ctx, d, l.o_src, nullptr, 0, x_fill.x, x_fill.x, x_fill.xb, d, st_fill16, 0));
+                ENG_OK(rg(x_fill.xb, d, l.w1, cst, cg, nullptr, nullptr, hdn, cfg.d_ff, nullptr, 1));
+                ENG_OK(rg(hdn, cfg.d_ff, l.w2, nullptr, 0, x_fill.x, x_fill.x, x_fill.xb, d, st_fill16, 0));
             }
-            fin_stats = st_fill16; fin_groups = d / 16;
-        } else
-        for (size_t li = 0; li < dec.size(); ++li) {
-            auto& l = dec[li];
-            void* qkv = qkv_dec[li];
-            { LinOpt o; o.halt = true; o.ln_stats = st_fill; o.row_idx = ri; o.m_dev = rn; ENG_OK(linear(xa, dt, d, l.qkv, qkv, dt, 3 * d, M, o, s)); }
-            bofi::AttnArgs a{};
-            a.q = qkv; a.k = (char*)qkv + (size_t)d * tsz; a.v = (char*)qkv + (size_t)2 * d * tsz;
-            a.ldq = a.ldk = a.ldv = 3 * d; a.out = ctx; a.ldo = d; a.dtype = dt; a.B = B; a.H = cfg.heads; a.Lq = S; a.Lk = S;
-            // phrase_mask[:, 1:-1, 1:-1]: row t <- row t+1, one key column dropped
-            a.klen = sa.klen_dec + 1; a.klen_sb = L; a.klen_sq = 1; a.klen_bias = -1; a.skip_if_ge = halt; a.skip_threshold = 1;
-            ENG_OK(bofi::launch_attention(a, s));
-            { LinOpt o; o.halt = true; o.residual = x_fill; o.ldr = d; o.stats_out = st_fill; o.y2 = copy_t(xb_fill); o.row_idx = ri; o.m_dev = rn;
-              ENG_OK(linear(ctx, dt, d, l.o, x_fill, BOFI_DT_F32, d, M, o, s)); }
-            { LinOpt o; o.halt = true; o.ln_stats = st_fill; o.row_idx = ri; o.m_dev = rn; ENG_OK(linear(xa, dt, d, l.q_src, qs, dt, d, M, o, s)); }
-            bofi::AttnArgs c{};
-            c.q = qs; c.ldq = d;
-            c.k = (char*)kv + (size_t)(n_len + li) * 2 * d * tsz; c.v = (char*)kv + ((size_t)(n_len + li) * 2 * d + d) * tsz;
-            c.ldk = c.ldv = kv_all.N; c.out = ctx; c.ldo = d; c.dtype = dt; c.B = B; c.H = cfg.heads; c.Lq = S; c.Lk = R;
-            c.klen = att_len; c.klen_sb = 1; c.klen_sq = 0; c.skip_if_ge = halt; c.skip_threshold = 1;
-            ENG_OK(bofi::launch_attention(c, s));
-            { LinOpt o; o.halt = true; o.residual = x_fill; o.ldr = d; o.stats_out = st_fill; o.y2 = copy_t(xb_fill); o.row_idx = ri; o.m_dev = rn;
-              ENG_OK(linear(ctx, dt, d, l.o_src, x_fill, BOFI_DT_F32, d, M, o, s)); }
-            { LinOpt o; o.halt = true; o.relu = 1; o.ln_stats = st_fill; o.row_idx = ri; o.m_dev = rn; ENG_OK(linear(xa, dt, d, l.w1, hdn, dt, cfg.d_ff, M, o, s)); }
-            { LinOpt o; o.halt = true; o.residual = x_fill; o.ldr = d; o.stats_out = st_fill; o.y2 = copy_t(xb_fill); o.row_idx = ri; o.m_dev = rn;
-              ENG_OK(linear(hdn, dt, cfg.d_ff, l.w2, x_fill, BOFI_DT_F32, d, M, o, s)); }
+            fin.st = st_fill16; fin.groups = d / 16;
+        } else {
+            // phrase_mask[:, 1:-1, 1:-1] as key prefixes: row t <- row t+1, one key column dropped
+            for (size_t li = 0; li < dec.size(); ++li)
+                ENG_OK(decoder_layer_tiled(dec[li], n_len + (int)li, x_fill, qkv_dec[li], B, S, R, sa.klen_dec + 1, -1, att_len, rows, s));
         }
-        { LinOpt o; o.halt = true; o.ln_stats = fin_stats; o.ln_groups = fin_groups; o.row_idx = ri; o.m_dev = rn;
-          ENG_OK(linear(xa, dt, d, gen, logits, BOFI_DT_F32, cfg.vocab, M, o, s)); }
+        ENG_OK(folded(fin, gen, logits, BOFI_DT_F32, cfg.vocab, M, rows, s));
         ENG_OK(bofi::launch_vocab_finalize(logits, M, cfg.vocab, S, (flags & BOFI_FLAG_RAW_LOGITS) ? 0 : 1, nullptr, 0, cfg.pad_idx, tok64, s,
                                            st.counters + 3, halt, ri, rn));
         if (flags & BOFI_FLAG_SAMPLE)          // sample_next_word 'sample' (CaptionModel.py:405-425): the drawn ids feed the next bound step
@@ -1218,8 +1168,8 @@ int bofi_engine_refresh_device(bofi_engine_t* e, int n, const char* const* names
 int bofi_engine_debug_copy(bofi_engine_t* e, const char* name, void* dst, int64_t bytes, void* stream) {
     if (!e || !name || !dst) return fail(BOFI_ERR_ARG, "null argument");
     const std::string n = name;
-    const void* src = n == "by1" ? (const void*)e->by1 : n == "byb" ? (const void*)e->byb : n == "st_b" ? (const void*)e->st_b :
-                      n == "bq2" ? (const void*)e->bq2 : n == "bctx2" ? (const void*)e->bctx2 : n == "by2" ? (const void*)e->by2 :
+    const void* src = n == "by1" ? (const void*)e->y1.x : n == "byb" ? (const void*)e->y1.xb : n == "st_b" ? (const void*)e->y1.st :
+                      n == "bq2" ? (const void*)e->bq2 : n == "bctx2" ? (const void*)e->bctx2 : n == "by2" ? (const void*)e->y2.x :
                       n == "bh" ? (const void*)e->bh : n == "by3" ? (const void*)e->by3 : n == "dbg_part" ? (const void*)e->dbg_part :
                       n == "counters" ? (const void*)e->st.counters : nullptr;      // ("counters": int32 [8] of the last decode: [5] = groups whose bounding loop ran as a PAIR of workgroups)
     if (!src) return fail(BOFI_ERR_ARG, "unknown buffer");
@@ -1283,7 +1233,7 @@ int bofi_engine_set_saic_range(bofi_engine_t* e, int it_begin, int it_end) {
 int bofi_engine_saic_put_words(bofi_engine_t* e, const int64_t* seq, int B, void* stream) {
     g_err.clear();
     if (!e || !seq) return fail(BOFI_ERR_ARG, "null argument");
-    if (B < 1 || B > e->cfg.max_batch || B != e->cur_B) return fail(BOFI_ERR_ARG, "saic_put_words: B must be the batch of the decode it continues");
+    if (B < 1 || B > e->cfg.max_batch || B != e->saic_B) return fail(BOFI_ERR_ARG, "saic_put_words: B must be the batch of the decode it continues");
     return bofi::launch_saic_put_words(e->st, e->sa, seq, B, e->L, e->cfg.seq_length, (hipStream_t)stream);
 }
 
@@ -1544,7 +1494,6 @@ int bofi_engine_bound_step(bofi_engine_t* e, const int* ext_syn, const int* last
     ENG_OK(check_call(e, B, R));
     if (!ext_syn || !last || !len_logp || !syn_logp) return fail(BOFI_ERR_ARG, "null argument");
     if (e->bound_dense) return fail(BOFI_ERR_STATE, "bound_step is the incremental (N_len = 1) form's stage; the dense bounding pass runs inside decode_naic");
-    e->cur_B = B;
     if (e->bound_loop_ok(R)) return e->bound_loop(B, R, att_len, ext_syn, last, 0, len_logp, syn_logp, (hipStream_t)stream);
     ENG_OK(e->bound_tail(nullptr, 1, ext_syn, last, B, BOUND_ATTN, nullptr, nullptr, (hipStream_t)stream));
     return e->enqueue_bound_iter(B, R, att_len, ext_syn, last, 0, len_logp, syn_logp, false, (hipStream_t)stream);
@@ -1558,7 +1507,6 @@ int bofi_engine_fill_naic(bofi_engine_t* e, const int* ext_syn, const int* last,
     hipStream_t s = (hipStream_t)stream;
     ENG_HIP(hipMemcpyAsync(e->st.ext_syn, ext_syn, (size_t)B * e->L * sizeof(int), hipMemcpyDeviceToDevice, s));
     ENG_HIP(hipMemcpyAsync(e->st.last, last, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, s));
-    e->cur_B = B;
     return e->enqueue_fill(att_len, B, R, flags & ~BOFI_FLAG_GRAPH, seq, seq_logprob, s);
 }
 
@@ -1571,6 +1519,7 @@ int bofi_engine_decode_saic(bofi_engine_t* e, const void* feats, int feats_dtype
     if (!seq) return fail(BOFI_ERR_ARG, "null seq");
     if (e->n_len != 1) return fail(BOFI_ERR_STATE, "the semi-autoregressive decode is built for a one-layer bounding network (N_len = 1)");
     hipStream_t s = (hipStream_t)stream;
+    e->saic_B = B;
     for (auto& q : e->qkv_dec)                              // the per-layer q|k|v buffers of this mode (never inside a capture)
         if (!q) ENG_OK(e->dalloc((char**)&q, (size_t)e->cfg.max_batch * e->cfg.seq_length * 3 * e->cfg.d_model, e->tsz));
     if (flags & BOFI_FLAG_SAMPLE) ENG_OK(bofi::launch_set_u64(e->d_seed, e->sample_seed, s));     // outside the graph: fresh draws per call

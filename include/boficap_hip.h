@@ -280,7 +280,7 @@ typedef struct bofi_config {
     int dtype;        /* compute dtype: BOFI_DT_F32 (parity) or BOFI_DT_BF16 (throughput) */
     int n_len;        /* layers of the bounding network (LengthPredictor_UIC N_len, TransformerModel.py:357-375): 1 (configs/uic_sd.yml) takes
                          the row-0-only incremental form; >= 2 (configs/uic_sd_N2.yml) the dense form -- all S+2 rows through every layer
-                         per iteration, as the reference computes it (a field since ABI version 2; the library is at version 3: bofi_abi_version) */
+                         per iteration, as the reference computes it (a field since ABI version 2; the library is at version 4: bofi_abi_version) */
 } bofi_config_t;
 
 /* Allocates device weights + workspace for one model replica on the current HIP device. */
