@@ -154,6 +154,22 @@ struct RbGemmArgs {
     int dbg;                                  // developer aid (BOFI_RB_DBG & 16: in-kernel stamps, set by the C entry)
     int alone;                                // 1: nothing runs beside this launch: 64-row blocks (more, shorter workgroups)
 };
+// the generator with the vocabulary epilogue inside (rb_vocab_kernel): ids and row statistics out, no [M, N] tensor
+struct RbVocabArgs {
+    const float* x; int ldx;                  // [M][512] float32 residual stream (decoder.norm folded into wp / c / cs)
+    const rb_u32x4* wp; const float* c; const float* cs;      // the generator's weight fragment-major [N][512] (rows V .. N zero); folded bias, column sums [N]
+    int M, N, V, S;                           // rows, padded and real vocabulary, positions per image
+    const int* ntok; int ntok_bias, pad_idx;  // optional: row (b, t) emits pad_idx when t >= ntok[b] + ntok_bias
+    int64_t* seq;                             // [M] greedy ids
+    float* row_plogp; float* row_chosen;      // optional pair [M]: sum_v p log p, log-prob of the emitted id
+    int* nan_flag;                            // optional: OR-ed with 1 when a row held a NaN
+    float* part; unsigned* ctr;               // workspace of ONE launch in flight: rb_vocab_part_floats(M) floats, rb_vocab_ctr_words(M) words (zero before the first launch)
+    int alone;                                // as RbGemmArgs
+};
+inline size_t rb_vocab_part_floats(size_t M) { return M * 20; }
+inline size_t rb_vocab_ctr_words(size_t M) { return (M + 63) / 64 + 4; }
+int rb_vocab_check(const RbVocabArgs& a);     // the argument checks that need no workspace (BOFI_ERR_ARG)
+int launch_rb_vocab(const RbVocabArgs& a, hipStream_t st);
 int launch_rb_gemm(const RbGemmArgs& a, hipStream_t st);
 int launch_rb_ffn(const RbFfnArgs& a, hipStream_t st);
 int launch_rb_attn(const RbAttnArgs& a, hipStream_t st);           // -1: shape not covered

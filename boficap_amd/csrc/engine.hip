@@ -118,6 +118,8 @@ struct bofi_engine {
     float* logits = nullptr;
     float* logits_pad = nullptr;         // bf16 engine: the generator's output with a pitch of gen.Npad (whole 128-column tiles: the persistent GEMM), read by vocab_finalize
     void *qkv = nullptr, *ctx = nullptr, *hdn = nullptr, *mem = nullptr, *kv = nullptr, *qs = nullptr, *xn = nullptr;
+    bool no_logits = false;              // a fork made with BOFI_FORK_IDS_ONLY: neither of the two buffers above
+    float* vb_part = nullptr; unsigned* vb_ctr = nullptr;             // the fused generator's per-row records and row-block counters (launch_rb_vocab; bf16 engine)
     void* feats_t = nullptr;                                          // bf16 copy of float32 input features
     float* st_fill16 = nullptr;                                       // row partial sums of the decoder rows per 16 columns [Bm*Sq][d/16][2] (row-list iterations of the SAIC decode)
     float* st_b16 = nullptr;                                          // row partial sums per 16 columns [Bm][d/16][2] (bound_ops.hip)
@@ -311,6 +313,8 @@ struct bofi_engine {
     // bofi_engine_refresh_device: descriptor tables of the batched repack launches (device copy, pinned staging, what was uploaded last)
     void* rt_dev = nullptr; void* rt_pin = nullptr; size_t rt_bytes = 0; std::vector<char> rt_cache;
 
+    // the generator runs over zero-padded weight rows into a buffer of its own pitch (logits_pad; enqueue_fill)
+    bool gen_padded() const { return cfg.dtype == BOFI_DT_BF16 && gen.Npad > gen.N; }
     // workspace of one in-flight decode (a forked engine has its own, and shares the weights)
     int alloc_workspace() {
     const bofi_config_t& c = cfg;
@@ -326,8 +330,12 @@ struct bofi_engine {
     ENG_OK(stream(&x_enc, Bm * Rm)); ENG_OK(stream(&x_fill, Bm * Sq)); ENG_OK(stream(&xw, Bm * L));
     ENG_OK(stream(&y1, Bm));
     y2 = y1; ENG_OK(dalloc(&y2.x, Bm * d));
-    ENG_OK(dalloc(&logits, Bm * Sq * c.vocab));
-    if (c.dtype == BOFI_DT_BF16 && gen.Npad > gen.N) ENG_OK(dalloc(&logits_pad, Bm * Sq * (size_t)gen.Npad));
+    logits = logits_pad = nullptr;
+    if (!no_logits) {
+        ENG_OK(dalloc(&logits, Bm * Sq * c.vocab));
+        if (gen_padded()) ENG_OK(dalloc(&logits_pad, Bm * Sq * (size_t)gen.Npad));
+    }
+    if (c.dtype == BOFI_DT_BF16) { ENG_OK(dalloc(&vb_part, bofi::rb_vocab_part_floats(Bm * Sq))); ENG_OK(dalloc(&vb_ctr, bofi::rb_vocab_ctr_words(Bm * Sq))); }
     ENG_OK(dalloc((char**)&qkv, rows * 3 * d, tsz));
     ENG_OK(dalloc((char**)&ctx, rows * d, tsz));
     ENG_OK(dalloc((char**)&hdn, rows * dff, tsz));
@@ -557,6 +565,8 @@ struct bofi_engine {
         a.alone = in_flight == 1;
         return bofi::launch_rb_gemm(a, s);
     }
+    // the generator as the row-block kernel over the padded weight (what enqueue_fill runs from BOFI_RB_MIN_ROWS rows on)
+    bool gen_rb_ok(int M) const { return BOFI_ENV_INT("BOFI_GEN_PAD", 1) != 0 && gen_padded() && fold_rb_ok(gen, M); }
     bool ffn_sublayer_ok(const Lin& w1, const Lin& w2, int M) const {
         const bool on = BOFI_ENV_INT("BOFI_RB_FFN", 1) != 0;
         return on && rb_ok() && w1.wp && w2.wp && w1.cs && cfg.d_ff % 512 == 0 && cfg.d_ff <= 2560 && M >= rb_min_rows();
@@ -783,7 +793,10 @@ int bofi_engine::enqueue_fill(const int* att_len, int B, int R, int flags, int64
     const int rounds = 1 + ((flags >> BOFI_FLAG_REFINE_SHIFT) & 15);
     float* lg = seq_logprob ? seq_logprob : logits;
     const int gen_pad = BOFI_ENV_INT("BOFI_GEN_PAD", 1);      // developer knob: 0 = in place, one-tile kernel
-    const bool gen_rb = gen_pad && logits_pad && fold_rb_ok(gen, M);
+    const bool gen_rb = gen_rb_ok(M);
+    // BOFI_FLAG_IDS_ONLY where the row-block generator would run: generator + epilogue as ONE launch that keeps the distribution on the CU (rb_vocab_kernel)
+    const bool fused = (flags & BOFI_FLAG_IDS_ONLY) && gen_rb;
+    if (no_logits && !fused) return fail(BOFI_ERR_STATE, "this fork has no vocabulary-wide buffers: BOFI_FLAG_IDS_ONLY decodes that take the fused generator only");
     for (int round = 0; round < rounds; ++round) {
     // (round 0 under the row-block family: layer 0's q|k|v rows come out of the (label, position) table with the embedding launch -- BOFI_FILL_QKV_TAB=0: the projection)
     const bool qkv_tab = round == 0 && fill_tab_ready && !dec.empty() && fold_rb_ok(dec[0].qkv, M) && BOFI_ENV_INT("BOFI_FILL_QKV_TAB", 1) != 0 && !exp_skip("qkv");
@@ -817,6 +830,15 @@ int bofi_engine::enqueue_fill(const int* att_len, int B, int R, int flags, int64
     // generator.  V = 9 491 is not a whole number of 128-column tiles and its rows are not 16-byte aligned: the bf16 engine runs the GEMM
     // over the zero-padded weight rows into a buffer of pitch gen.Npad (persistent kernel, vector epilogue) and vocab_finalize reads
     // that, writing the log-probs at the caller's pitch V -- the same reads and writes as in place.
+    if (fused) {
+        if (exp_skip("gen")) continue;
+        bofi::RbVocabArgs v{};
+        v.x = x_fill.x; v.ldx = d; v.wp = (const bofi::u32x4*)gen.wp; v.c = gen.b; v.cs = gen.cs; v.M = M; v.N = gen.Npad; v.V = cfg.vocab; v.S = S;
+        v.ntok = st.last; v.ntok_bias = -1; v.pad_idx = cfg.pad_idx; v.seq = seq; v.row_plogp = row_plogp_out; v.row_chosen = row_chosen_out;
+        v.part = vb_part; v.ctr = vb_ctr; v.alone = in_flight == 1;
+        ENG_OK(bofi::launch_rb_vocab(v, s));
+        continue;
+    }
     const float* lsrc = nullptr;
     if (gen_pad && logits_pad) {
         Lin gp = gen; gp.N = gen.Npad;                   // (the tiled form computes the zero columns too; the row-block kernel takes Npad anyway)
@@ -827,7 +849,7 @@ int bofi_engine::enqueue_fill(const int* att_len, int B, int R, int flags, int64
     }
     // (a round that another one follows: its ids are all the next round reads -- the log-probs it would write are overwritten: not stored)
     const int ids_only_on = BOFI_ENV_INT("BOFI_REFINE_IDS_ONLY", 1);      // developer knob: 0 = every round stores its log-probs
-    const int lsm = (flags & BOFI_FLAG_RAW_LOGITS) ? 0 : ((ids_only_on && round + 1 < rounds && lsrc) ? 2 : 1);
+    const int lsm = (flags & BOFI_FLAG_RAW_LOGITS) ? 0 : ((flags & BOFI_FLAG_IDS_ONLY) || (ids_only_on && round + 1 < rounds && lsrc) ? 2 : 1);
     ENG_OK(bofi::launch_vocab_finalize(lg, M, cfg.vocab, S, lsm, st.last, -1, cfg.pad_idx, seq, s, nullptr, nullptr, nullptr, nullptr,
                                        lsrc, gen.Npad, lsm ? row_plogp_out : nullptr, lsm ? row_chosen_out : nullptr));
     }
@@ -1003,9 +1025,12 @@ void bofi_engine_destroy(bofi_engine_t* e) {
     delete e;
 }
 
-int bofi_engine_fork_sized(bofi_engine_t* parent, int max_batch, bofi_engine_t** out) {
+int bofi_engine_fork_sized(bofi_engine_t* parent, int max_batch, bofi_engine_t** out) { return bofi_engine_fork_ex(parent, max_batch, 0, out); }
+
+int bofi_engine_fork_ex(bofi_engine_t* parent, int max_batch, int fork_flags, bofi_engine_t** out) {
     g_err.clear();
     if (!parent || !out) return fail(BOFI_ERR_ARG, "null argument");
+    if (fork_flags & ~BOFI_FORK_IDS_ONLY) return fail(BOFI_ERR_ARG, "fork: unknown option");
     if (!parent->finalized) return fail(BOFI_ERR_STATE, "fork needs a finalized engine");
     if (max_batch < 0) return fail(BOFI_ERR_ARG, "fork: max_batch >= 0 (0 = the parent's)");
     auto* e = new bofi_engine(*parent);          // copies config and every weight pointer
@@ -1029,6 +1054,7 @@ int bofi_engine_fork_sized(bofi_engine_t* parent, int max_batch, bofi_engine_t**
     e->saic_it_begin = 1;
     e->saic_it_end = 0;
     e->st = bofi::BoundState{};
+    e->no_logits = (fork_flags & BOFI_FORK_IDS_ONLY) != 0;
     if (max_batch > 0) e->cfg.max_batch = max_batch;          // (the weights do not depend on it: only the workspace is sized by it)
     int rc = e->alloc_workspace();
     if (rc == BOFI_OK && hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking) != hipSuccess) rc = fail(BOFI_ERR_HIP, "hipStreamCreate");
@@ -1189,6 +1215,8 @@ int bofi_engine_set_decodes_in_flight(bofi_engine_t* e, int n) {
     e->in_flight = n;
     return BOFI_OK;
 }
+
+int bofi_engine_ids_only_fused(bofi_engine_t* e, int B) { return e && e->finalized && B > 0 && e->gen_rb_ok(B * e->cfg.seq_length) ? 1 : 0; }
 
 int bofi_engine_bound_loop_active(bofi_engine_t* e, int R) { return e && e->finalized && e->bound_loop_ok(R) ? 1 : 0; }
 
@@ -1474,6 +1502,12 @@ static int check_call(bofi_engine_t* e, int B, int R) {
     if (R <= 0 || R > e->cfg.max_regions) return fail(BOFI_ERR_ARG, "regions outside 1..max_regions");
     return BOFI_OK;
 }
+static int check_ids_only(bofi_engine_t* e, int flags, const float* seq_logprob) {
+    if ((flags & BOFI_FLAG_IDS_ONLY) && seq_logprob) return fail(BOFI_ERR_ARG, "BOFI_FLAG_IDS_ONLY: seq_logprob must be NULL");
+    if ((flags & BOFI_FLAG_IDS_ONLY) && (flags & BOFI_FLAG_RAW_LOGITS)) return fail(BOFI_ERR_ARG, "BOFI_FLAG_IDS_ONLY excludes BOFI_FLAG_RAW_LOGITS");
+    if (e->no_logits && !(flags & BOFI_FLAG_IDS_ONLY)) return fail(BOFI_ERR_STATE, "this fork has no vocabulary-wide buffers: decode with BOFI_FLAG_IDS_ONLY");
+    return BOFI_OK;
+}
 static int check_feats(bofi_engine_t* e, const void* feats, int feats_dtype) {
     if (!feats) return fail(BOFI_ERR_ARG, "null att_feats");
     if (feats_dtype != BOFI_DT_F32 && feats_dtype != e->cfg.dtype) return fail(BOFI_ERR_ARG, "att_feats must be float32 or the engine's compute dtype");
@@ -1504,6 +1538,8 @@ int bofi_engine_fill_naic(bofi_engine_t* e, const int* ext_syn, const int* last,
     g_err.clear();
     ENG_OK(check_call(e, B, R));
     if (!ext_syn || !last || !seq) return fail(BOFI_ERR_ARG, "null argument");
+    ENG_OK(check_ids_only(e, flags, seq_logprob));
+    if (e->no_logits && !e->gen_rb_ok(B * e->cfg.seq_length)) return fail(BOFI_ERR_STATE, "this fork has no vocabulary-wide buffers and the launch would not take the fused generator");
     hipStream_t s = (hipStream_t)stream;
     ENG_HIP(hipMemcpyAsync(e->st.ext_syn, ext_syn, (size_t)B * e->L * sizeof(int), hipMemcpyDeviceToDevice, s));
     ENG_HIP(hipMemcpyAsync(e->st.last, last, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, s));
@@ -1518,6 +1554,7 @@ int bofi_engine_decode_saic(bofi_engine_t* e, const void* feats, int feats_dtype
     ENG_OK(check_feats(e, feats, feats_dtype));
     if (!seq) return fail(BOFI_ERR_ARG, "null seq");
     if (e->n_len != 1) return fail(BOFI_ERR_STATE, "the semi-autoregressive decode is built for a one-layer bounding network (N_len = 1)");
+    if (e->no_logits) return fail(BOFI_ERR_STATE, "this fork has no vocabulary-wide buffers: the semi-autoregressive decode needs the distribution");
     hipStream_t s = (hipStream_t)stream;
     e->saic_B = B;
     for (auto& q : e->qkv_dec)                              // the per-layer q|k|v buffers of this mode (never inside a capture)
@@ -1544,6 +1581,9 @@ int bofi_engine_decode_naic(bofi_engine_t* e, const void* feats, int feats_dtype
     ENG_OK(check_call(e, B, R));
     ENG_OK(check_feats(e, feats, feats_dtype));
     if (!seq) return fail(BOFI_ERR_ARG, "null seq");
+    ENG_OK(check_ids_only(e, flags, seq_logprob));
+    // (before anything is enqueued or captured: such a fork's launch must be one the fused generator takes)
+    if (e->no_logits && !e->gen_rb_ok(B * e->cfg.seq_length)) return fail(BOFI_ERR_STATE, "this fork has no vocabulary-wide buffers and the launch would not take the fused generator");
     hipStream_t s = (hipStream_t)stream;
     if (!(flags & BOFI_FLAG_GRAPH))
         return e->enqueue_decode(feats, feats_dtype, att_len, B, R, flags, seq, seq_logprob, phrase_num, phrase_length,

@@ -1448,6 +1448,325 @@ int launch_rb_gemm(const RbGemmArgs& a, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// The generator with the vocabulary epilogue inside (rb_vocab_kernel): rb_gemm_kernel<true, MT> on the generator's weight, but a chunk's logits are
+// never stored -- each wavefront folds them into a running state per block row, and one lane per row writes the greedy id, sum_v p log p and the
+// log-prob of the emitted id (what vocab_finalize_kernel reads the [rows, V] tensor back for).  Every logit is the float32 value rb_gemm_chunks forms
+// for that row: same staging, same rb_segment, same fold expression.
+//   state of a set of columns:  m = max v,  s = sum e^(v - m),  u = sum e^(v - m) (v - m),  bi = lowest column holding m     (sum p log p = u / s - log s)
+// A row's result must not depend on the grid (block size, column split, what else is in the launch), so the REDUCTION TREE is fixed by the columns alone:
+//   * the 64-column chunks form octets (8 chunks, one per wavefront); octet o belongs to column CLASS o % 4;
+//   * a lane folds its 16 columns of every chunk its wavefront owns in a class, in ascending order, into one state (rescaled when the maximum moves);
+//   * per class: the four lane groups of a row (lane, ^16, ^32), then the eight wavefronts in order (LDS);
+//   * the four classes in order, from a per-row record in memory, by the workgroup that arrives last at the row block's counter.
+// gridDim.y = 1, 2 or 4 workgroups share a row block: workgroup y owns the classes y, y + gridDim.y, ... and walks them one after the other -- the same
+// partial states whatever the split.  Columns >= V (the zero rows behind the real weight) enter no field.  A NaN logit poisons its row only.
+struct VbState { float m, s, u; int bi; };
+constexpr int VB_NONE = 0x7fffffff, VB_NAN = -2;      // bi: no column yet / (record in memory only) the workgroup saw a NaN in this row
+constexpr int VB_REC = 20;                            // floats per row record: 4 classes x (m, s, u, bi), the logit at pad_idx, 3 unused
+
+__device__ __forceinline__ VbState vb_merge(const VbState& a, const VbState& b) {      // a: the lower columns' side of the tree (ties between equal maxima go to the lower column anyway)
+#pragma clang fp contract(off)
+    VbState r;
+    r.m = fmaxf(a.m, b.m);
+    r.bi = (b.m > a.m || (b.m == a.m && b.bi < a.bi)) ? b.bi : a.bi;
+    const float da = a.m - r.m, db = b.m - r.m;
+    const float ca = a.s > 0.f ? expf(da) : 0.f, cb = b.s > 0.f ? expf(db) : 0.f;      // (an empty side has m = -inf: no term)
+    const float ua = a.s > 0.f ? ca * (a.u + da * a.s) : 0.f, ub = b.s > 0.f ? cb * (b.u + db * b.s) : 0.f;
+    r.s = a.s * ca + b.s * cb;
+    r.u = ua + ub;
+    return r;
+}
+__device__ __forceinline__ VbState vb_shfl_xor(const VbState& v, int mask) {
+    return VbState{__shfl_xor(v.m, mask, 64), __shfl_xor(v.s, mask, 64), __shfl_xor(v.u, mask, 64), __shfl_xor(v.bi, mask, 64)};
+}
+
+// a chunk's 16 logits per row tile (acc holds the folded values) into the lane's running states; col0: the lane's first column of the chunk.  A NaN logit is never a
+// maximum and turns s into NaN, which nothing below turns back: the row's NaN mark is read off s when the class is closed
+template <int MT, bool FULL>
+__device__ __forceinline__ void vb_fold_chunk(const f32x4 (&acc)[4][MT], int col0, int V, float (&m)[MT], float (&s)[MT], float (&u)[MT], int (&bi)[MT]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        float bm = m[mt];
+        int b = bi[mt];
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float v = acc[nt][mt][j];
+                const int col = col0 + nt * 16 + j;
+                const bool ok = FULL || col < V;
+                if (ok && v > bm) { bm = v; b = col; }            // columns ascend: the first maximum is kept
+            }
+        if (bm > m[mt] && s[mt] > 0.f) {                         // the maximum moved: the sums follow it
+            const float d = m[mt] - bm, c = expf(d);
+            u[mt] = c * (u[mt] + d * s[mt]);
+            s[mt] = s[mt] * c;
+        }
+        m[mt] = bm; bi[mt] = b;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (FULL || col0 + nt * 16 + j < V) {
+                    const float d = acc[nt][mt][j] - bm, e = expf(d);
+                    s[mt] = s[mt] + e;
+                    u[mt] = u[mt] + e * d;
+                }
+            }
+    }
+}
+
+template <int MT>
+struct RbVocabCfg {
+    static constexpr int BR = MT * 16;
+    static constexpr int XT = BR * 1024;
+    static constexpr int WST = XT;                              // per (class, wavefront, row) states: [4][8][BR] float4
+    static constexpr int STAT = WST + 4 * 8 * BR * 16;          // s_mean[BR], s_rstd[BR]
+    static constexpr int CST = STAT + BR * 8;                   // per wavefront [2][64]: c | cs of the current chunk
+    static constexpr int VPAD = CST + 8 * 512;                  // the logit at pad_idx [BR]
+    static constexpr int NANF = VPAD + BR * 4;                  // NaN seen [BR]
+    static constexpr int LAST = NANF + BR * 4;                  // this workgroup arrived last
+    static constexpr int LDS = LAST + 16;
+};
+
+template <int MT>
+__global__ __launch_bounds__(512) void rb_vocab_kernel(RbVocabArgs a) {
+    using Cfg = RbVocabCfg<MT>;
+    constexpr int BR = Cfg::BR;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char* xt = smem;
+    float4* wst = reinterpret_cast<float4*>(smem + Cfg::WST);
+    float* s_mean = reinterpret_cast<float*>(smem + Cfg::STAT);
+    float* s_rstd = s_mean + BR;
+    float* cst = reinterpret_cast<float*>(smem + Cfg::CST);
+    float* s_vpad = reinterpret_cast<float*>(smem + Cfg::VPAD);
+    int* s_nan = reinterpret_cast<int*>(smem + Cfg::NANF);
+    int* s_last = reinterpret_cast<int*>(smem + Cfg::LAST);
+
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l15 = lane & 15, g = lane >> 4;
+    const int m0 = blockIdx.x * BR, nchunks = a.N >> 6, split = gridDim.y, y = blockIdx.y;
+    auto seg = [&](int ch) { return a.wp + (size_t)ch * (16 * 256) + lane; };
+    // this wavefront's walk: class cls (y, y + split, ...), inside it the octets o = cls, cls + 4, ...; chunk wave + 8 o
+    auto settle = [&](int& cls, int& o) { while (cls < 4 && wave + 8 * o >= nchunks) { cls += split; o = cls; } };
+    int cls = y, o = y;
+    settle(cls, o);
+    bf16x8 wb[RB_PF * 4];
+    if (cls < 4) rb_prime<4>(seg(wave + 8 * o), wb);
+    for (int i = tid; i < 4 * 8 * BR; i += 512) wst[i] = make_float4(-INFINITY, 0.f, 0.f, __int_as_float(VB_NONE));      // (a wavefront that owns no chunk of a class: the neutral state)
+    if (tid < BR) { s_vpad[tid] = 0.f; s_nan[tid] = 0; }
+    // ---- the block's staging: rb_gemm_kernel's, statement for statement (the logits are to be the same float32 values)
+    constexpr int RPW = MT * 2;
+#pragma unroll
+    for (int pass = 0; pass < (RPW + 7) / 8; ++pass) {
+        const int lr = pass * 8 + (lane >> 3), r = wave * RPW + lr, sub = lane & 7, m = m0 + r;
+        const bool mine = lr < RPW;
+        float4 v[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            v[j] = (mine && m < a.M) ? *reinterpret_cast<const float4*>(a.x + (size_t)m * a.ldx + j * 32 + sub * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        float sm = 0.f, sq = 0.f;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            sm += (v[j].x + v[j].y) + (v[j].z + v[j].w);
+            sq += (v[j].x * v[j].x + v[j].y * v[j].y) + (v[j].z * v[j].z + v[j].w * v[j].w);
+            if (mine) *reinterpret_cast<uint2*>(xt + rb_off(r, j * 4 + (sub >> 1)) + (sub & 1) * 8) = make_uint2(pack_bf16(v[j].x, v[j].y), pack_bf16(v[j].z, v[j].w));
+        }
+        sm = oct_sum(sm); sq = oct_sum(sq);
+        if (mine && sub == 0) {
+            const float mean = sm * (1.0f / 512.0f);
+            const float var = fmaxf((sq - sm * mean) * (1.0f / 511.0f), 0.f);
+            s_mean[r] = mean;
+            s_rstd[r] = 1.0f / (sqrtf(var) + 1e-6f);
+        }
+    }
+    __syncthreads();
+
+    // ---- the chunk loop
+    constexpr bool STATS_IN_REGS = MT <= 4;                    // (96-row blocks: the registers go to the running states -- the same values, read per chunk from LDS)
+    float mu[STATS_IN_REGS ? MT : 1], rs[STATS_IN_REGS ? MT : 1];
+    if constexpr (STATS_IN_REGS) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) { mu[mt] = s_mean[mt * 16 + l15]; rs[mt] = s_rstd[mt * 16 + l15]; }
+    }
+    const int lbase = rb_lane_base(l15, g);
+    float* mycst = cst + wave * 128;
+    float sm_[MT], ss_[MT], su_[MT];
+    int sb_[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) { sm_[mt] = -INFINITY; ss_[mt] = 0.f; su_[mt] = 0.f; sb_[mt] = VB_NONE; }
+    const int pad_ch = a.pad_idx >> 6;
+#pragma unroll 1
+    while (cls < 4) {
+        const int ch = wave + 8 * o;
+        int ncls = cls, no = o + 4;
+        settle(ncls, no);
+        const float cv = a.c[ch * 64 + lane], csv = a.cs[ch * 64 + lane];
+        f32x4 acc[4][MT];
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) acc[nt][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        rb_segment<MT, 4, RB_PF, (MT > 4 ? MT / 2 : MT)>(seg(ch), seg(ncls < 4 ? wave + 8 * no : ch), wb, xt, lbase, acc);
+        mycst[lane] = cv; mycst[64 + lane] = csv;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            const float4 cc = *reinterpret_cast<const float4*>(mycst + nt * 16 + g * 4);
+            const float4 cs = *reinterpret_cast<const float4*>(mycst + 64 + nt * 16 + g * 4);
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) {
+                const f32x4 t = acc[nt][mt];
+                const float mu_ = STATS_IN_REGS ? mu[STATS_IN_REGS ? mt : 0] : s_mean[mt * 16 + l15], rs_ = STATS_IN_REGS ? rs[STATS_IN_REGS ? mt : 0] : s_rstd[mt * 16 + l15];
+                const float v0 = rs_ * (t[0] - mu_ * cs.x) + cc.x, v1 = rs_ * (t[1] - mu_ * cs.y) + cc.y;      // (rb_gemm_chunks' fold)
+                const float v2 = rs_ * (t[2] - mu_ * cs.z) + cc.z, v3 = rs_ * (t[3] - mu_ * cs.w) + cc.w;
+                acc[nt][mt] = f32x4{v0, v1, v2, v3};
+            }
+        }
+        __builtin_amdgcn_wave_barrier();                         // (the constants are read: the next chunk may park its own)
+        int col0 = ch * 64 + g * 4;
+        asm volatile("" : "+v"(col0));                           // (sixteen column numbers per lane are not to be kept across the MFMA loop)
+        if (ch * 64 + 64 <= a.V) vb_fold_chunk<MT, true>(acc, col0, a.V, sm_, ss_, su_, sb_);
+        else vb_fold_chunk<MT, false>(acc, col0, a.V, sm_, ss_, su_, sb_);
+        if (ch == pad_ch) {                                      // the logit at pad_idx: what a row past its image's token count emits
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (col0 + nt * 16 + j == a.pad_idx) {
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt) s_vpad[mt * 16 + l15] = acc[nt][mt][j];
+                    }
+        }
+        if (ncls != cls) {                                       // the class is through: lane groups in order, then this wavefront's slot
+            const int kc = (cls - y) / split;
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) {
+                VbState st{sm_[mt], ss_[mt], su_[mt], sb_[mt]};
+                if (st.s != st.s) s_nan[mt * 16 + l15] = 1;
+                VbState ot = vb_shfl_xor(st, 16);
+                st = (g & 1) ? vb_merge(ot, st) : vb_merge(st, ot);
+                ot = vb_shfl_xor(st, 32);
+                st = (g & 2) ? vb_merge(ot, st) : vb_merge(st, ot);
+                if (g == 0) wst[(kc * 8 + wave) * BR + mt * 16 + l15] = make_float4(st.m, st.s, st.u, __int_as_float(st.bi));
+                sm_[mt] = -INFINITY; ss_[mt] = 0.f; su_[mt] = 0.f; sb_[mt] = VB_NONE;
+            }
+        }
+        cls = ncls; o = no;
+    }
+    __syncthreads();
+
+    // ---- the eight wavefronts of every (row, class) this workgroup owns, in order -> the row's record
+    const int ncl = (4 - y + split - 1) / split;
+    if (tid < BR * ncl) {
+        const int row = tid % BR, kc = tid / BR, gm = m0 + row;
+        const float4 f0 = wst[(kc * 8) * BR + row];
+        VbState st{f0.x, f0.y, f0.z, __float_as_int(f0.w)};
+#pragma unroll
+        for (int w = 1; w < 8; ++w) {
+            const float4 f = wst[(kc * 8 + w) * BR + row];
+            st = vb_merge(st, VbState{f.x, f.y, f.z, __float_as_int(f.w)});
+        }
+        if (s_nan[row]) st.bi = VB_NAN;
+        if (gm < a.M) {
+            const int kcls = y + kc * split;
+            unsigned long long* rec = reinterpret_cast<unsigned long long*>(a.part + (size_t)gm * VB_REC + kcls * 4);
+            __hip_atomic_store(rec, ((unsigned long long)__float_as_uint(st.s) << 32) | __float_as_uint(st.m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(rec + 1, ((unsigned long long)(unsigned)st.bi << 32) | __float_as_uint(st.u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (kcls == ((pad_ch >> 3) & 3))
+                __hip_atomic_store(reinterpret_cast<unsigned*>(a.part + (size_t)gm * VB_REC + 16), __float_as_uint(s_vpad[row]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    // ---- the row block's counter: agent-scope stores above, drained by every wavefront, released by the arrival; the last workgroup acquires and closes the rows
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __threadfence();
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned old = __hip_atomic_fetch_add(a.ctr + blockIdx.x, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = old + 1u == (unsigned)split;
+        if (last) __hip_atomic_store(a.ctr + blockIdx.x, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (nobody else touches it in this launch: ready for the next)
+        *s_last = last;
+    }
+    __syncthreads();
+    if (!*s_last) return;
+    __threadfence();
+    if (tid < BR && m0 + tid < a.M) {
+#pragma clang fp contract(off)
+        const int gm = m0 + tid;
+        const unsigned long long* rec = reinterpret_cast<const unsigned long long*>(a.part + (size_t)gm * VB_REC);
+        VbState st{-INFINITY, 0.f, 0.f, VB_NONE};
+        bool nan = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned long long q0 = __hip_atomic_load(rec + 2 * k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned long long q1 = __hip_atomic_load(rec + 2 * k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            VbState c{__uint_as_float((unsigned)q0), __uint_as_float((unsigned)(q0 >> 32)), __uint_as_float((unsigned)q1), (int)(unsigned)(q1 >> 32)};
+            if (c.bi == VB_NAN) { nan = true; c.bi = VB_NONE; }
+            st = k ? vb_merge(st, c) : c;
+        }
+        const float vpad = __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned*>(a.part + (size_t)gm * VB_REC + 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        bool padded = false;
+        if (a.ntok) {
+            const int b = gm / a.S, t = gm - b * a.S;
+            padded = t >= a.ntok[b] + a.ntok_bias;
+        }
+        const float lse = logf(st.s);                             // log sum e^v - m
+        int id = (nan || st.bi == VB_NONE) ? 0 : st.bi;           // one NaN poisons the row (vocab_finalize_kernel's log-softmax case); an all -inf row: index 0
+        if (padded) id = a.pad_idx;
+        a.seq[gm] = id;
+        if (a.row_plogp) {
+            const float qn = __builtin_nanf("");
+            a.row_plogp[gm] = nan ? qn : st.u / st.s - lse;
+            a.row_chosen[gm] = nan ? qn : (padded ? (vpad - st.m) - lse : 0.f - lse);
+        }
+        if (nan && a.nan_flag) atomicOr(a.nan_flag, 1);
+    }
+}
+
+template <int MT>
+static int launch_rb_vocab_t(const RbVocabArgs& a, int split, hipStream_t st) {
+    using Cfg = RbVocabCfg<MT>;
+    static_assert(Cfg::LDS <= 160 * 1024, "one workgroup per CU");
+    static bool attr_set = false;
+    if (!attr_set) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&rb_vocab_kernel<MT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return BOFI_ERR_HIP;
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((rb_vocab_kernel<MT>), dim3((a.M + Cfg::BR - 1) / Cfg::BR, split), dim3(512), Cfg::LDS, st, a);
+    return hipGetLastError() == hipSuccess ? BOFI_OK : BOFI_ERR_HIP;
+}
+
+int rb_vocab_check(const RbVocabArgs& a) {
+    if (!a.x || !a.wp || !a.c || !a.cs || !a.seq || a.M < 1 || a.N < 64 || a.N % 64 || a.V < 1 || a.V > a.N || a.S < 1 || a.ldx % 4 || a.ldx < 512 ||
+        (!a.row_plogp != !a.row_chosen) || a.pad_idx < 0 || a.pad_idx >= a.V)
+        return BOFI_ERR_ARG;
+    return BOFI_OK;
+}
+
+int launch_rb_vocab(const RbVocabArgs& a, hipStream_t st) {
+    if (rb_vocab_check(a) != BOFI_OK || !a.part || !a.ctr) return BOFI_ERR_ARG;
+    // developer knobs (read again after bofi_reload_env; the results do not depend on them -- bit for bit): BOFI_VOCAB_MT = 6: 96-row blocks (a third fewer weight
+    // bytes per row, but as compiled the running states push that form 34 registers into scratch; default 4: 64-row blocks, no spill -- `alone` does not choose
+    // between them until the two are timed); BOFI_VOCAB_SPLIT = 1 / 2 / 4 workgroups per row block (default 0: fill the chip when the row blocks alone do not,
+    // as launch_rb_gemm_t)
+    static int env_seen = -1, mt = 4, split_env = 0;
+    if (env_seen != g_env_generation) {
+        const char* e = getenv("BOFI_VOCAB_MT"); mt = e ? atoi(e) : 4;
+        e = getenv("BOFI_VOCAB_SPLIT"); split_env = e ? atoi(e) : 0;
+        env_seen = g_env_generation;
+    }
+    const bool six = mt == 6;
+    const int blocks = (a.M + (six ? 96 : 64) - 1) / (six ? 96 : 64), octets = (a.N / 64 + 7) / 8;
+    int split = 1;
+    if (split_env == 1 || split_env == 2 || split_env == 4) split = split_env;
+    else while (split < 4 && blocks * split * 2 <= 256 && octets >= 6 * split * 2) split *= 2;
+    const int rc = six ? launch_rb_vocab_t<6>(a, split, st) : launch_rb_vocab_t<4>(a, split, st);
+    if (rc == BOFI_OK) g_gemm_flops += 2.0 * a.M * 512.0 * a.N;
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // w [N][K] row-major bf16 -> fragment-major: [N/64 chunks][K/32 steps][4 tiles][64 lanes][8 bf16]; lane (l15, g) of a fragment holds
 // row chunk*64 + tile*16 + l15, k = step*32 + g*8 .. +7
 __global__ __launch_bounds__(256) void rb_pack_frag_kernel(const bf16_t* __restrict__ w, u32x4* __restrict__ out, int N, int K) {
@@ -1510,6 +1829,30 @@ extern "C" int bofi_linear_block(const float* x, int ldx, const void* wp, const 
     a.x = x; a.ldx = ldx; a.wp = (const bofi::u32x4*)wp; a.c = c; a.cs = cs; a.y = y; a.ldy = ldy; a.y_f32 = y_f32; a.M = M; a.N = N; a.relu = relu;
     { const char* e = getenv("BOFI_RB_DBG"); a.dbg = e ? atoi(e) : 0; }
     return bofi::launch_rb_gemm(a, (hipStream_t)stream);
+}
+
+// The operator entry keeps the kernel's small workspace itself (grow-only, one per process): calls on DIFFERENT streams must not overlap, and a call that has to
+// grow it synchronises the device -- not for use inside a stream capture.  The engine hands launch_rb_vocab a workspace of its own per fork.
+extern "C" int bofi_vocab_block(const float* x, int ldx, const void* wp, const float* c, const float* cs, int M, int Npad, int V, int S, const int* ntok,
+                                int ntok_bias, int pad_idx, int64_t* seq, float* row_plogp, float* row_chosen, int* nan_flag, int alone, void* stream) {
+    bofi::RbVocabArgs a{};
+    a.x = x; a.ldx = ldx; a.wp = (const bofi::u32x4*)wp; a.c = c; a.cs = cs; a.M = M; a.N = Npad; a.V = V; a.S = S; a.ntok = ntok; a.ntok_bias = ntok_bias;
+    a.pad_idx = pad_idx; a.seq = seq; a.row_plogp = row_plogp; a.row_chosen = row_chosen; a.nan_flag = nan_flag; a.alone = alone;
+    if (bofi::rb_vocab_check(a) != BOFI_OK) return BOFI_ERR_ARG;
+    static void* ws = nullptr;
+    static size_t ws_rows = 0;
+    if ((size_t)M > ws_rows) {
+        BOFI_HIP(hipDeviceSynchronize());
+        if (ws) (void)hipFree(ws);
+        ws = nullptr; ws_rows = 0;
+        const size_t rows = ((size_t)M + 4095) & ~(size_t)4095, bytes = (bofi::rb_vocab_part_floats(rows) + bofi::rb_vocab_ctr_words(rows)) * 4;
+        BOFI_HIP(hipMalloc(&ws, bytes));
+        BOFI_HIP(hipMemset(ws, 0, bytes));
+        ws_rows = rows;
+    }
+    a.part = (float*)ws;
+    a.ctr = (unsigned*)((float*)ws + bofi::rb_vocab_part_floats(ws_rows));
+    return bofi::launch_rb_vocab(a, (hipStream_t)stream);
 }
 
 extern "C" int bofi_ffn_block(const float* x, int ldx, const void* w1p, const float* c1, const float* cs1, const void* w2p, const float* b2, float* y,

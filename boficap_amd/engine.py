@@ -97,9 +97,11 @@ class BofiEngine:
             hip.check(self._lib.bofi_engine_create(C.byref(c), C.byref(self._h)), "bofi_engine_create")
         self._finalized = False
 
-    def fork(self, max_batch: Optional[int] = None) -> "BofiEngine":
+    def fork(self, max_batch: Optional[int] = None, ids_only: bool = False) -> "BofiEngine":
         """A second engine sharing this one's weights with its own workspace (one per in-flight batch); ``max_batch``: images per call the fork's
-        workspace is sized for (default: this engine's) -- a pipeline that coalesces several loader batches per call forks larger."""
+        workspace is sized for (default: this engine's) -- a pipeline that coalesces several loader batches per call forks larger.
+        ``ids_only``: a workspace without the two vocabulary-wide float32 buffers (most of a fork's memory) -- such a fork serves ``decode_naic(ids_only=True)``
+        launches that take the fused generator and refuses everything else (BOFI_FORK_IDS_ONLY)."""
         if not self._finalized:
             raise hip.BofiHipError("fork() needs loaded weights")
         f = object.__new__(BofiEngine)
@@ -108,7 +110,7 @@ class BofiEngine:
         f._iter_cap, f._q1_group, f._live_word = 0, 0, None           # per-call knobs start from the defaults (bofi_engine_fork resets them too)
         f._h = C.c_void_p()
         with torch.cuda.device(self.device):
-            hip.check(self._lib.bofi_engine_fork_sized(self._h, int(max_batch or 0), C.byref(f._h)), "bofi_engine_fork_sized")
+            hip.check(self._lib.bofi_engine_fork_ex(self._h, int(max_batch or 0), hip.FORK_IDS_ONLY if ids_only else 0, C.byref(f._h)), "bofi_engine_fork_ex")
         return f
 
     def stream(self) -> "torch.cuda.Stream":
@@ -174,7 +176,8 @@ class BofiEngine:
 
     def decode_naic(self, att_feats: torch.Tensor, att_len: Optional[torch.Tensor] = None, *, strict_q1: bool = True,
                     want_logprob: bool = True, want_memory: bool = False, raw_logits: bool = False, graph: bool = False,
-                    refine_rounds: int = 0, out: Optional[dict] = None, q1_group: int = 0, iter_cap: int = 0, phases: str = "", row_stats: bool = False) -> dict:
+                    refine_rounds: int = 0, out: Optional[dict] = None, q1_group: int = 0, iter_cap: int = 0, phases: str = "", row_stats: bool = False,
+                    ids_only: bool = False) -> dict:
         """Greedy NAIC bound+fill decode.  Returns a dict of device tensors: seq [B,S] int64,
         seq_logprob [B,S,V] float32 (or None), phrase_num [B] int32, phrase_length [B,S] int32,
         phrase_syn [B,S] int64, bound_iters [1] int32, memory [B,R,d] float32 (or None).
@@ -188,7 +191,16 @@ class BofiEngine:
         ``phases``: "" = the whole decode; a subset of "ebf" = only the encode / bounding loop / filling pass + export of it (BOFI_FLAG_PHASE_*): a pipelining
         caller enqueues the three on the same engine in that order (its streams / events order them) with the same arguments.
         ``row_stats``: the vocabulary epilogue also leaves, per position, sum_v p log p and the log-prob of the emitted id in ``out['row_plogp']`` / ``out['row_chosen']``
-        (float32 [B, S]; bofi_engine_set_row_stats_out) -- what ``row_stats(out)`` / ``entropy_perplexity(out)`` otherwise read back out of the log-prob tensor."""
+        (float32 [B, S]; bofi_engine_set_row_stats_out) -- what ``row_stats(out)`` / ``entropy_perplexity(out)`` otherwise read back out of the log-prob tensor.
+        ``ids_only`` (BOFI_FLAG_IDS_ONLY; implies ``want_logprob=False``, not with ``raw_logits``): the distribution is not wanted at all -- ids, layout and ``row_stats``
+        only.  Where the row-block generator runs, generator and vocabulary epilogue are then one launch that writes no logits; the ids are the first maxima of the
+        raw logits.  ``row_stats(out)`` / ``sample_tokens(out)`` of such a result need ``row_stats=True`` / are not available: there is no distribution to read."""
+        if ids_only:
+            if raw_logits:
+                raise hip.BofiHipError("ids_only: the raw logits are not produced")
+            if out is not None and out.get("seq_logprob") is not None:
+                raise hip.BofiHipError("ids_only: `out` carries a seq_logprob buffer")
+            want_logprob = False
         self._check_feats(att_feats, att_len)
         B, R, _ = att_feats.shape
         S, V, dev = self.cfg.seq_length, self.cfg.tgt_vocab, att_feats.device
@@ -219,6 +231,7 @@ class BofiEngine:
                       "bofi_engine_set_row_stats_out")
             self._row_stats_ptrs = rs
         out["_row_stats_fused"] = bool(row_stats)
+        out["_ids_only"] = bool(ids_only)
         if q1_group != getattr(self, "_q1_group", 0):
             hip.check(self._lib.bofi_engine_set_q1_group(self._h, int(q1_group)), "bofi_engine_set_q1_group")
             self._q1_group = q1_group
@@ -226,7 +239,7 @@ class BofiEngine:
             hip.check(self._lib.bofi_engine_set_bound_iter_cap(self._h, int(iter_cap)), "bofi_engine_set_bound_iter_cap")
             self._iter_cap = int(iter_cap)
         flags = ((hip.FLAG_STRICT_Q1 if strict_q1 else 0) | (hip.FLAG_RAW_LOGITS if raw_logits else 0) | (hip.FLAG_GRAPH if graph else 0)
-                 | (refine_rounds << hip.FLAG_REFINE_SHIFT))
+                 | (refine_rounds << hip.FLAG_REFINE_SHIFT) | (hip.FLAG_IDS_ONLY if ids_only else 0))
         if phases:
             if set(phases) - set("ebf"):
                 raise hip.BofiHipError("phases: a subset of 'ebf'")
@@ -241,6 +254,10 @@ class BofiEngine:
         """A hint for the kernel choice (bofi_engine_set_decodes_in_flight): 1 = this engine's launches run alone on the device (shorter
         workgroup chains), 0 / > 1 = throughput forms (fewer weight bytes per row).  Part of the graph key: a captured launch is replayed under the hint it was captured with."""
         hip.check(self._lib.bofi_engine_set_decodes_in_flight(self._h, int(n)), "bofi_engine_set_decodes_in_flight")
+
+    def ids_only_fused(self, B: int) -> bool:
+        """Would ``decode_naic(ids_only=True)`` of B images take the fused generator -- what a ``fork(ids_only=True)`` can serve (bofi_engine_ids_only_fused)?"""
+        return bool(self._lib.bofi_engine_ids_only_fused(self._h, int(B)))
 
     def bound_loop_active(self, R: int) -> bool:
         """Does a decode of R regions per image run the bounding loop as the persistent per-16-image kernel (bofi_engine_bound_loop_active)?"""
@@ -302,6 +319,8 @@ class BofiEngine:
         B, S = seq.shape
         if out.get("_row_stats_fused"):                          # the decode's own epilogue left them (decode_naic(row_stats=True))
             return out["row_plogp"], out["row_chosen"]
+        if out.get("_ids_only"):
+            raise hip.BofiHipError("an ids_only decode leaves no distribution: ask it for row_stats=True")
         lp = out.get("seq_logprob")
         src = hip.ptr(lp) if lp is not None else self._lib.bofi_engine_logprob(self._h)
         plogp = torch.empty(B, S, dtype=torch.float32, device=seq.device)
@@ -321,6 +340,8 @@ class BofiEngine:
         int64 [B * n, S], image b's draws in rows b*n .. b*n+n-1."""
         seq = out["seq"]
         B, S = seq.shape
+        if out.get("_ids_only"):
+            raise hip.BofiHipError("an ids_only decode leaves no distribution to sample from")
         lp = out.get("seq_logprob")
         src = hip.ptr(lp) if lp is not None else self._lib.bofi_engine_logprob(self._h)
         ntok = out["phrase_length"].sum(1).to(torch.int32).contiguous()
@@ -429,11 +450,16 @@ class DecodePipeline:
     already in flight."""
 
     def __init__(self, engine: "BofiEngine", *, in_flight: Optional[int] = None, batches_per_launch: int = 16, strict_q1: bool = True, stats: bool = True,
-                 keep_logprob: bool = False, region_buckets=(36, 48, 64, 80, 100, 128)):
+                 keep_logprob: bool = False, region_buckets=(36, 48, 64, 80, 100, 128), fused_vocab: bool = False):
         if in_flight is None:                                    # 3 launch streams + the copy stream = the runtime's default of 4 hardware queues
             in_flight = 3
         if in_flight < 1 or batches_per_launch < 1:
             raise hip.BofiHipError("in_flight and batches_per_launch must be >= 1")
+        if fused_vocab and keep_logprob:
+            raise hip.BofiHipError("fused_vocab leaves no log-probs to keep")
+        # fused_vocab: the forks own no vocabulary-wide buffers and every launch is an ids-only decode (BofiEngine.decode_naic(ids_only=True)): where the launch is
+        # large enough for the row-block kernels, the generator and the vocabulary epilogue are one launch and the distribution never reaches memory
+        self.fused_vocab = bool(fused_vocab)
         self.root, self.nf, self.bpl = engine, int(in_flight), int(batches_per_launch)
         self.strict_q1, self.stats, self.keep_logprob = strict_q1, stats, keep_logprob
         self.dev = engine.device
@@ -451,7 +477,7 @@ class DecodePipeline:
             streams.append(torch.cuda.Stream(self.dev))
         self._slots = []
         for k in range(self.nf):
-            e = self.root.fork(max_batch=rows_max)
+            e = self.root.fork(max_batch=rows_max, ids_only=self.fused_vocab)
             e.set_decodes_in_flight(self.nf)
             self._slots.append(dict(eng=e, stream=streams[k], feats=[{}, {}], lens=[None, None], out=None, host=None, copied=[torch.cuda.Event(), torch.cuda.Event()],
                                     done=torch.cuda.Event()))
@@ -539,8 +565,14 @@ class DecodePipeline:
     def _decode_and_copy_out(self, sl):
         e = sl["eng"]
         feats, lens, b, nb, rows = sl["last"]
+        if self.fused_vocab and not e.ids_only_fused(rows):      # (a launch too small for the fused generator -- a short tail: a plain fork of this slot's, made when first needed)
+            if sl.get("eng_plain") is None:
+                sl["eng_plain"] = self.root.fork(max_batch=self.rows_max)
+                sl["eng_plain"].set_decodes_in_flight(self.nf)
+            e = sl["eng_plain"]
+        sl["ran"] = e
         sl["out"] = e.decode_naic(feats, lens, strict_q1=self.strict_q1, graph=True, out=sl["out"] if sl["out"] is not None and sl["out"]["seq"].shape[0] == rows else None,
-                                  q1_group=b if nb > 1 else 0, row_stats=self.stats, want_logprob=self.keep_logprob)
+                                  q1_group=b if nb > 1 else 0, row_stats=self.stats, want_logprob=self.keep_logprob, ids_only=self.fused_vocab)
         out = sl["out"]
         small = {k2: out[k2] for k2 in ("seq", "phrase_num", "phrase_length", "phrase_syn", "bound_saturated")}
         if self.stats:
@@ -563,7 +595,7 @@ class DecodePipeline:
                     self._decode_and_copy_out(sl)
                     sl["done"].record(sl["stream"])
                 sl["done"].synchronize()
-            sl["eng"]._redo_without_loop_kernel(sat, again)
+            sl["ran"]._redo_without_loop_kernel(sat, again)
         mine = {k2: v.clone() for k2, v in sl["host"].items() if k2 != "bound_saturated"}      # (one private copy per launch: the pinned buffers are the next launch's; batches are views of it)
         o = 0
         for b in sizes:

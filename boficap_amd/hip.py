@@ -17,6 +17,8 @@ FLAG_REFINE_SHIFT = 8
 FLAG_SAMPLE = 16
 FLAG_PHASE_ENCODE, FLAG_PHASE_BOUND, FLAG_PHASE_FILL = 32, 64, 128
 FLAG_SAIC_LAYOUT_ONLY = 4096
+FLAG_IDS_ONLY = 8192
+FORK_IDS_ONLY = 1
 ABI_VERSION = 4
 
 
@@ -88,6 +90,8 @@ SIGNATURES = {
     "bofi_engine_destroy": (None, [_P]),
     "bofi_engine_fork": (_I, [_P, C.POINTER(_P)]),
     "bofi_engine_fork_sized": (_I, [_P, _I, C.POINTER(_P)]),
+    "bofi_engine_fork_ex": (_I, [_P, _I, _I, C.POINTER(_P)]),
+    "bofi_engine_ids_only_fused": (_I, [_P, _I]),
     "bofi_engine_stream": (_P, [_P]),
     "bofi_engine_set_weight": (_I, [_P, C.c_char_p, _P, _I64]),
     "bofi_engine_finalize": (_I, [_P]),
@@ -100,6 +104,7 @@ SIGNATURES = {
     "bofi_pack_frag": (_I, [_P, _P, _I, _I, _P]),
     "bofi_attn_block": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P]),
     "bofi_linear_block": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "bofi_vocab_block": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P]),
     "bofi_engine_set_row_stats_out": (_I, [_P, _P, _P]),
     "bofi_attn_linear_block": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P]),
     "bofi_ffn_block": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _P]),
@@ -172,6 +177,13 @@ def stream_ptr():
         import torch
         _torch = torch
     return _torch._C._cuda_getCurrentRawStream(_torch.cuda.current_device())
+
+
+def vocab_block(x, wp, c, cs, V, S, seq, *, ntok=None, ntok_bias=0, pad_idx=0, row_plogp=None, row_chosen=None, nan_flag=None, alone=False):
+    """``bofi_vocab_block`` on torch tensors: x float32 [M, 512] (row stride x.stride(0)), wp / c / cs the generator's packed weight, folded bias and column sums for
+    ``c.numel()`` (padded) columns of which the first ``V`` count; seq int64 [M] out, row_plogp / row_chosen float32 [M] (both or neither), nan_flag int32 [1]."""
+    check(lib().bofi_vocab_block(ptr(x), x.stride(0), ptr(wp), ptr(c), ptr(cs), x.shape[0], c.numel(), int(V), int(S), ptr(ntok), int(ntok_bias), int(pad_idx),
+                                 ptr(seq), ptr(row_plogp), ptr(row_chosen), ptr(nan_flag), 1 if alone else 0, stream_ptr()), "bofi_vocab_block")
 
 
 def gemm_flops(reset: bool = False):

@@ -304,6 +304,14 @@ int bofi_engine_fork(bofi_engine_t* parent, bofi_engine_t** out);
 /* The same with a workspace for up to max_batch images per call (0 = the parent's): dynamic batching puts several loader batches into one decode call
  * (bofi_engine_set_q1_group), which a model built for one batch per call has no workspace for -- its weights serve either size. */
 int bofi_engine_fork_sized(bofi_engine_t* parent, int max_batch, bofi_engine_t** out);
+/* The same with options.  BOFI_FORK_IDS_ONLY: a workspace WITHOUT the two vocabulary-wide float32 buffers (max_batch * S * (vocab + padded vocab) * 4 bytes: most of a
+ * fork's memory) -- for decodes under BOFI_FLAG_IDS_ONLY that take the fused generator.  On such a fork a decode without that flag, one whose launch would need
+ * the buffers after all (a small launch, the tiled kernel family), and bofi_engine_decode_saic return BOFI_ERR_STATE; bofi_engine_logprob returns NULL. */
+#define BOFI_FORK_IDS_ONLY 1
+int bofi_engine_fork_ex(bofi_engine_t* parent, int max_batch, int fork_flags, bofi_engine_t** out);
+/* 1 when a BOFI_FLAG_IDS_ONLY decode of B images would take the fused generator (bofi_vocab_block's kernel) under the current environment knobs -- what a
+ * BOFI_FORK_IDS_ONLY fork can serve; 0 otherwise. */
+int bofi_engine_ids_only_fused(bofi_engine_t* e, int B);
 
 /* Re-pack the engine's weights from float32 parameters that live on the DEVICE (reference names, as set_weight): the
  * packing of bofi_engine_finalize (q|k|v stacking, LayerNorm folding, compute-dtype cast, bound tables) as kernels on
@@ -400,6 +408,12 @@ void* bofi_engine_stream(bofi_engine_t* e);
                                           no decoder pass, no tokens: the caller draws the phrase's words from its own distribution and hands them back with
                                           bofi_engine_saic_put_words before the next call (the reference-estimator self-critical step) */
 #define BOFI_FLAG_PHASE_FILL 128    /* decode_NA + logit + greedy pick + the slot-state export (:570-587, 1872-1876) on the preceding two */
+#define BOFI_FLAG_IDS_ONLY 8192     /* decode_naic / fill_naic (phased form included): ids, slot layout and the row statistics of bofi_engine_set_row_stats_out only -- the
+                                       vocabulary distribution is not wanted (seq_logprob must be NULL; not with BOFI_FLAG_RAW_LOGITS).  Where the row-block generator would run
+                                       (bf16 engine at the reference's width, launches of BOFI_RB_MIN_ROWS rows or more) every filling round's generator + epilogue is one
+                                       bofi_vocab_block launch: no logits in memory; the pick is the first maximum of the raw logits (it can differ from the log-softmax
+                                       path's only where two log-probs round to one float32).  Elsewhere the flag is honoured by the generator into the workspace and
+                                       the epilogue without its store.  Part of the graph key, as every flag. */
 
 /* model(fc, att, att_masks, opt={'train_mode':'NAIC','sample_method':'greedy'}, mode='sample'):
  * AttModel._sample AttModel.py:307-338,419-429 -> _prepare_feature TransformerModel.py:1674-1690
@@ -476,6 +490,18 @@ int bofi_bound_qattn(const void* x, const float* stats, const void* wq, const fl
  *   and generator projections: TransformerModel.py:1454-1456, AttModel.py:203-210 behind their pre-norms): x float32 [M, 512] -- the
  *   row statistics are computed in the kernel --, wp = bofi_pack_frag of the folded [N, 512] weight (N % 64 == 0), c / cs its folded
  *   bias and column sums, y bf16 or float32 (y_f32) [M, ldy], relu 0 / 1. */
+/* bofi_vocab_block: bofi_linear_block(y_f32 = 1) on the generator's weight + bofi_vocab_finalize's log-softmax case + bofi_vocab_stats as ONE launch that never
+ *   writes the [M, Npad] logits (AttModel.py:203-210, CaptionModel.py:388-390, AttModel.py:422-423, eval_utils.py:463-464): every logit is the float32 value
+ *   bofi_linear_block forms, and each wavefront folds its 64-column chunks into a running (max, sum e, sum e (v - max), first maximal column) per row.
+ *   x float32 [M, ldx]; wp / c / cs as bofi_linear_block's for Npad columns (Npad % 64 == 0) of which the first V are the vocabulary (the rest: zero rows, ignored);
+ *   seq int64 [M] = the first maximum of the row's V logits (0 if the row holds a NaN), or pad_idx where ntok (int32 [M / S], may be NULL) says so:
+ *   position t = row % S of image row / S with t >= ntok[image] + ntok_bias; row_plogp / row_chosen (float32 [M], both or neither): sum_v p log p and the
+ *   log-prob of the emitted id (NaN for a NaN row); nan_flag (int32 [1], may be NULL): OR-ed with 1 when a row held a NaN; 0 <= pad_idx < V; alone: 1 = nothing
+ *   runs beside this launch.  The results depend on the row alone -- not on M, `alone` or the launch's grid, bit for bit: the reduction tree is fixed by the columns.
+ *   The entry keeps a small workspace of its own: calls on different streams must not overlap, and it is not for use inside a stream capture (the engine's
+ *   decodes under BOFI_FLAG_IDS_ONLY use a workspace per engine). */
+int bofi_vocab_block(const float* x, int ldx, const void* wp, const float* c, const float* cs, int M, int Npad, int V, int S, const int* ntok, int ntok_bias,
+                     int pad_idx, int64_t* seq, float* row_plogp, float* row_chosen, int* nan_flag, int alone, void* stream);
 int bofi_pack_frag(const void* w, void* out, int N, int K, void* stream);
 int bofi_linear_block(const float* x, int ldx, const void* wp, const float* c, const float* cs, void* y, int ldy, int y_f32, int M, int N,
                       int relu, void* stream);

@@ -40,6 +40,8 @@ def main():
                     "(eval_utils.py:456-460)")
     ap.add_argument("--batches_per_launch", type=int, default=16)
     ap.add_argument("--in_flight", type=int, default=3, help="launch streams (3 launch streams + the copy stream = the runtime's default of 4 hardware queues)")
+    ap.add_argument("--fused_vocab", action="store_true", help="pipelined NAIC only: ids-only launches -- generator and vocabulary epilogue as one launch that writes no "
+                    "logits, forks without the vocabulary-wide buffers (TransformerModel.decode_many(fused_vocab=True))")
     args = ap.parse_args()
 
     import captioning.models as models
@@ -106,12 +108,12 @@ def main():
                 host = host.to(torch.bfloat16)
             host = host.pin_memory()
             batches = [host[i:i + args.batch_size] for i in range(0, host.size(0), args.batch_size)]
-            for _ in model.decode_many(batches[:2 * args.in_flight * args.batches_per_launch], batches_per_launch=args.batches_per_launch, in_flight=args.in_flight):
+            for _ in model.decode_many(batches[:2 * args.in_flight * args.batches_per_launch], batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab):
                 pass                                             # graph captures and stream choice, outside the clock
             torch.cuda.synchronize()
             import time
             t0, got = time.time(), []
-            for r in model.decode_many(batches, batches_per_launch=args.batches_per_launch, in_flight=args.in_flight):
+            for r in model.decode_many(batches, batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab):
                 got.append(r)                                    # host tensors of one batch: ids, slot layout, entropy, perplexity
             seconds = time.time() - t0
             i = 0
@@ -119,7 +121,7 @@ def main():
                 n = r["seq"].size(0)
                 results.extend(entry_of(i, k, r["seq"], r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"]) for k in range(n))
                 i += n
-            how = f"pipelined: {args.in_flight} launches in flight, {args.batches_per_launch} batches of {args.batch_size} per launch, features from pinned host memory, host results included"
+            how = f"pipelined: {args.in_flight} launches in flight, {args.batches_per_launch} batches of {args.batch_size} per launch, features from pinned host memory, host results included" + (", fused vocabulary epilogue" if args.fused_vocab else "")
         else:
             for i in range(0, len(feats), args.batch_size):
                 att = torch.from_numpy(np.ascontiguousarray(feats[i:i + args.batch_size])).cuda()
