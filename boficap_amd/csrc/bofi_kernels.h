@@ -181,8 +181,7 @@ struct PackLinArgs {
     const float* gain; const float* bln;            // pre-norm LayerNorm to fold in (or null)
     float* bout; float* cs;
 };
-int launch_pack_lin(const PackLinArgs& a, void* wout, int dtype, hipStream_t st);
-// the whole refresh of an engine's Linears as ONE launch each for the packed weights and for their fragment-major copies, and one for the
+// the whole repack of an engine's Linears as ONE launch each for the packed weights and for their fragment-major copies, and one for the
 // small float32 vectors (norm vectors, head layers): descriptor tables in device memory (repack.hip)
 struct PackLinDesc {
     PackLinArgs a; void* wout; void* wp;          // wp: fragment-major copy of wout [Npad][K] bf16 (or null)

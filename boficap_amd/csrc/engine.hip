@@ -33,22 +33,17 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
         if (r__ != BOFI_OK) { if (g_err.empty() || r__ != BOFI_ERR_HIP) g_err = std::string(#call) + " failed"; return r__; } \
     } while (0)
 
-uint16_t host_bf16(float f) {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x0040u);
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
 struct Lin { void* w = nullptr; float* b = nullptr; float* cs = nullptr; int N = 0, K = 0; int Npad = 0; void* wp = nullptr; void* wp16 = nullptr; };   // cs: column sums when a LayerNorm is folded in; Npad > N: rows N .. Npad of w / b / cs exist and are zero; wp: fragment-major copy of w for the row-block kernels (rowblock.hip), bf16 engine only; wp16: fragment-major FP16 copy made from the float32 parameters (bound_loop.hip), the bounding layer's Linears of a bf16 engine only
 struct Norm { float* g = nullptr; float* b = nullptr; };
 struct EncLayer { Lin qkv, o, w1, w2; Norm n0, n1; };
 struct DecLayer { Lin qkv, o, q_src, o_src, w1, w2; Norm n0, n1, n2; };
 
-// how a packed weight was made from the named parameters: replayed on the device by bofi_engine_refresh_device
+// how a packed weight is made from the named parameters: declared by bofi_engine_finalize, carried out on the device by bofi_engine::repack
 struct LinRecipe { Lin* out; std::vector<std::string> prefixes; int n_each, K; std::string fold; };
 
 struct NormRecipe { Norm* out; std::string prefix; int d; };
+// name -> (float32 parameter in device memory, element count): what bofi_engine::repack reads
+using DevParams = std::map<std::string, std::pair<const float*, int64_t>>;
 
 // A residual stream: the float32 rows, their copy in the compute dtype and the rows' partial sums [rows][groups][2] from which the consuming GEMM
 // applies the pre-norm LayerNorm in its epilogue.  The float32 engine reads the stream itself and keeps no copy.
@@ -105,7 +100,7 @@ struct bofi_engine {
     float *b_q0_32 = nullptr, *b_sctab = nullptr, *b_vtab = nullptr;      // [d], [L*10][H], [L*10][d]
     // filling pass, round 0: every word is BOS (decode_NA TransformerModel.py:570-577), so the first decoder layer's input row -- and with it its q|k|v row -- depends on
     // (label, position) only: f_qkv0[(label*S + t)][3d] in the compute dtype, made by the SAME row-block projection kernel a decode would run on those rows (a row's
-    // result does not depend on the launch), gathered by embed_fill instead of a 10-GFLOP projection per 320 images.  Rebuilt by finalize / refresh_device.
+    // result does not depend on the launch), gathered by embed_fill instead of a 10-GFLOP projection per 320 images.  Rebuilt by every repack.
     void* f_qkv0 = nullptr; float* f_x0 = nullptr; int* f_syn = nullptr; bool fill_tab_ready = false;
     // per-call (bofi_engine_set_row_stats_out; part of the graph key): where the filling pass's epilogue leaves, per position, sum_v p log p and the log-prob of the
     // emitted id -- eval's entropy / perplexity (eval_utils.py:463-464) without a second pass over the log-probs
@@ -170,16 +165,6 @@ struct bofi_engine {
         ENG_HIP(hipMemcpy(*p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
         return BOFI_OK;
     }
-    int upload_t(void** p, const std::vector<float>& v) {           // compute dtype
-        if (cfg.dtype == BOFI_DT_F32) return upload_f32((float**)p, v);
-        std::vector<uint16_t> h(v.size());
-        for (size_t i = 0; i < v.size(); ++i) h[i] = host_bf16(v[i]);
-        uint16_t* q = nullptr;
-        ENG_OK(dalloc(&q, h.size()));
-        ENG_HIP(hipMemcpy(q, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-        *p = q;
-        return BOFI_OK;
-    }
     const std::vector<float>* get(const std::string& name, size_t numel) {
         auto it = host.find(name);
         if (it == host.end()) { g_err = "missing weight " + name; return nullptr; }
@@ -189,62 +174,31 @@ struct bofi_engine {
         }
         return &it->second;
     }
-    // stack several [n_i, K] matrices (and their biases) into one Lin.  With fold_norm the pre-norm
-    // LayerNorm that feeds this layer is folded in (gemm_glds.hip): w <- w * a_2 (per input column),
-    // bias <- bias + w . b_2, cs[n] <- sum_k of the ROUNDED scaled weight (so that the mean term of
-    // the epilogue cancels exactly what the MFMA accumulated).
+    // Declare one Lin: several [n_each, K] matrices (and their biases) stacked, with fold_norm the pre-norm LayerNorm that feeds the layer folded
+    // in (gemm_glds.hip).  Shapes and buffers only: the parameters are checked to exist, the outputs are allocated -- zero-filled, which is what rows
+    // N .. Npad stay -- and the recipe is recorded; repack() fills the first N rows (pack_lin_multi_kernel states the arithmetic).
     int make_lin(Lin* out, const std::vector<std::string>& prefixes, int n_each, int K, const std::string& fold_norm = "", int pad_to = 0, bool frag = false) {
-        std::vector<float> w, b;
-        for (const auto& p : prefixes) {
-            const auto* pw = get(p + ".weight", (size_t)n_each * K);
-            const auto* pb = get(p + ".bias", (size_t)n_each);
-            if (!pw || !pb) return BOFI_ERR_STATE;
-            w.insert(w.end(), pw->begin(), pw->end());
-            b.insert(b.end(), pb->begin(), pb->end());
-        }
+        for (const auto& p : prefixes)
+            if (!get(p + ".weight", (size_t)n_each * K) || !get(p + ".bias", (size_t)n_each)) return BOFI_ERR_STATE;
+        if (!fold_norm.empty() && (!get(fold_norm + ".a_2", K) || !get(fold_norm + ".b_2", K))) return BOFI_ERR_STATE;
         out->N = n_each * (int)prefixes.size();
         out->K = K;
-        out->Npad = pad_to > 0 ? ((out->N + pad_to - 1) / pad_to) * pad_to : out->N;      // zero rows behind the N real ones (the repack on the device writes the first N only)
-        if (!fold_norm.empty()) {
-            const auto* g = get(fold_norm + ".a_2", K);
-            const auto* bb = get(fold_norm + ".b_2", K);
-            if (!g || !bb) return BOFI_ERR_STATE;
-            std::vector<float> cs(out->N);
-            for (int n = 0; n < out->N; ++n) {
-                double c = b[n], s = 0.0;
-                float* row = w.data() + (size_t)n * K;
-                for (int k = 0; k < K; ++k) {
-                    c += (double)(*bb)[k] * (double)row[k];
-                    row[k] = row[k] * (*g)[k];
-                    float r = row[k];
-                    if (cfg.dtype == BOFI_DT_BF16) { uint32_t u = (uint32_t)host_bf16(r) << 16; std::memcpy(&r, &u, 4); }
-                    s += (double)r;
-                }
-                b[n] = (float)c;
-                cs[n] = (float)s;
-            }
-            cs.resize(out->Npad, 0.f);
-            ENG_OK(upload_f32(&out->cs, cs));
-        }
-        w.resize((size_t)out->Npad * K, 0.f);
-        b.resize(out->Npad, 0.f);
-        ENG_OK(upload_t(&out->w, w));
-        ENG_OK(upload_f32(&out->b, b));
+        out->Npad = pad_to > 0 ? ((out->N + pad_to - 1) / pad_to) * pad_to : out->N;
+        out->cs = nullptr;
+        if (!fold_norm.empty()) ENG_OK(dalloc(&out->cs, (size_t)out->Npad));
+        ENG_OK(dalloc((char**)&out->w, (size_t)out->Npad * K, tsz));
+        ENG_OK(dalloc(&out->b, (size_t)out->Npad));
         out->wp = nullptr;
         out->wp16 = nullptr;
-        if (frag && cfg.dtype == BOFI_DT_BF16 && out->Npad % 64 == 0 && K % 32 == 0) {      // the layout the row-block kernels stream (zero rows included)
+        if (frag && cfg.dtype == BOFI_DT_BF16 && out->Npad % 64 == 0 && K % 32 == 0)      // the layout the row-block kernels stream (zero rows included)
             ENG_OK(dalloc((char**)&out->wp, (size_t)out->Npad * K, 2));
-            ENG_OK(bofi::launch_rb_pack_frag(out->w, out->wp, out->Npad, K, nullptr));
-        }
         lin_recipes.push_back(LinRecipe{out, prefixes, n_each, K, fold_norm});
         return BOFI_OK;
     }
     int make_norm(Norm* out, const std::string& prefix, int d) {
-        const auto* g = get(prefix + ".a_2", d);
-        const auto* b = get(prefix + ".b_2", d);
-        if (!g || !b) return BOFI_ERR_STATE;
-        ENG_OK(upload_f32(&out->g, *g));
-        ENG_OK(upload_f32(&out->b, *b));
+        if (!get(prefix + ".a_2", d) || !get(prefix + ".b_2", d)) return BOFI_ERR_STATE;
+        ENG_OK(dalloc(&out->g, (size_t)d));
+        ENG_OK(dalloc(&out->b, (size_t)d));
         norm_recipes.push_back(NormRecipe{out, prefix, d});
         return BOFI_OK;
     }
@@ -310,7 +264,7 @@ struct bofi_engine {
     }
     bool is_fork = false;
     size_t n_weight_allocs = 0;          // allocs[0 .. n) are weights (owned by the parent), the rest workspace
-    // bofi_engine_refresh_device: descriptor tables of the batched repack launches (device copy, pinned staging, what was uploaded last)
+    // repack: descriptor tables of its batched launches (device copy, pinned staging, what was uploaded last)
     void* rt_dev = nullptr; void* rt_pin = nullptr; size_t rt_bytes = 0; std::vector<char> rt_cache;
 
     // the generator runs over zero-padded weight rows into a buffer of its own pitch (logits_pad; enqueue_fill)
@@ -381,7 +335,7 @@ struct bofi_engine {
         a.dbg_part = dbg_part;
         return bofi::launch_bound_tail(a, cfg.dtype, s);
     }
-    // tables derived from the bound layer's weights once kvtab exists (finalize and refresh_device)
+    // tables derived from the bound layer's weights once kvtab exists (repack)
     int derive_bound_tables(hipStream_t s) {
         ENG_OK(bofi::launch_pack_w1p(heads.w1t, b_w1p, cfg.dtype, cfg.d_model, 2 * cfg.head_hidden, s));
         ENG_OK(bofi::launch_votab(b_kvtab, b_o_self.w, b_x0, b_o_self.b, b_votab, b_x0b, cfg.dtype, L * 10, cfg.d_model, cfg.heads, s));
@@ -400,7 +354,7 @@ struct bofi_engine {
         return BOFI_OK;
     }
     // ---- the persistent bounding-loop kernel's operands: fp16 fragment-major copies of the bounding layer's Linears and the float32 self-attention
-    // tables, all derived on the device from the float32 parameters (finalize: uploaded temporaries; refresh_device: the caller's tensors)
+    // tables, all derived on the device from the float32 parameters (repack)
     struct BoundSrc {
         const float *wq_self, *bq_self, *wk_self, *bk_self, *wv_self, *bv_self, *n0g, *n0b;
         const float *wo_self, *wq_src, *n1g, *wo_src, *w1, *n2g, *w2, *lw1, *sw1, *hng;
@@ -431,6 +385,123 @@ struct bofi_engine {
         a.q0 = b_q0_32; a.sctab = b_sctab; a.vtab = b_vtab;
         ENG_OK(bofi::launch_bound_tables(a, s));
         loop_ready = true;
+        return BOFI_OK;
+    }
+    // ---- The one implementation of weight packing: every declared Linear and Norm, the embedding tables, the bound heads and the bounding layer's
+    // tables, from float32 parameters in device memory (finalize: a staged copy of the host map, null stream; refresh_device: the caller's tensors
+    // and stream).  Every Linear's repack (stack, fold the pre-norm, cast, column sums), the fragment-major copies and the small float32 vectors are
+    // THREE launches over descriptor tables in device memory (they were ~230 launches and copies: 1.5 ms of a training step that decodes with its
+    // current weights).  The tables hold the source pointers: uploaded again only when one of them changed.
+    int repack(const DevParams& src, hipStream_t s) {
+        const bofi_config_t& c = cfg;
+        const int d = c.d_model, dff = c.d_ff, hh = c.head_hidden;
+        auto param = [&](const std::string& name, int64_t numel) -> const float* {
+            auto it = src.find(name);
+            if (it == src.end() || !it->second.first) { g_err = "missing weight " + name; return nullptr; }
+            if (it->second.second != numel) { g_err = "weight " + name + " has " + std::to_string(it->second.second) + " elements, expected " + std::to_string(numel); return nullptr; }
+            return it->second.first;
+        };
+        std::vector<bofi::PackLinDesc> lin_tab;
+        std::vector<bofi::CopyDesc> copy_tab;
+        int rows = 0, fblocks = 0, cblocks = 0;
+        auto add_copy = [&](const float* src, float* dst, int n) { copy_tab.push_back(bofi::CopyDesc{src, dst, n, cblocks}); cblocks += (n + 255) / 256; };
+        for (const auto& r : lin_recipes) {
+            if (!r.out->w || !r.out->b || (!r.fold.empty() && !r.out->cs)) return fail(BOFI_ERR_STATE, "repack: a packed weight is missing");
+            const int nsrc = (int)r.prefixes.size();
+            for (int i0 = 0; i0 < nsrc; i0 += 16) {       // a table entry stacks up to 16 matrices: a longer stack is several entries, one behind the other
+                bofi::PackLinDesc dsc{};
+                bofi::PackLinArgs& a = dsc.a;
+                a.nsrc = nsrc - i0 < 16 ? nsrc - i0 : 16; a.n_each = r.n_each; a.K = r.K;
+                for (int i = 0; i < a.nsrc; ++i) {
+                    a.w[i] = param(r.prefixes[i0 + i] + ".weight", (int64_t)r.n_each * r.K);
+                    a.b[i] = param(r.prefixes[i0 + i] + ".bias", r.n_each);
+                    if (!a.w[i] || !a.b[i]) return BOFI_ERR_STATE;
+                }
+                if (!r.fold.empty()) {
+                    a.gain = param(r.fold + ".a_2", r.K);
+                    a.bln = param(r.fold + ".b_2", r.K);
+                    if (!a.gain || !a.bln) return BOFI_ERR_STATE;
+                }
+                const size_t at = (size_t)i0 * r.n_each;      // first output row of this entry
+                a.bout = r.out->b + at; a.cs = r.out->cs ? r.out->cs + at : nullptr;
+                dsc.wout = (char*)r.out->w + at * r.K * tsz; dsc.wp = i0 ? nullptr : r.out->wp; dsc.Npad = r.out->Npad;      // (the fragment-major copy: of the whole weight, with its first entry)
+                dsc.row0 = rows; rows += (a.n_each * a.nsrc + 3) / 4 * 4;
+                dsc.blk0 = fblocks; if (dsc.wp) fblocks += (int)(((size_t)dsc.Npad * r.K / 8 + 255) / 256);
+                lin_tab.push_back(dsc);
+            }
+        }
+        for (const auto& r : norm_recipes) {
+            const float *g = param(r.prefix + ".a_2", r.d), *b = param(r.prefix + ".b_2", r.d);
+            if (!g || !b) return BOFI_ERR_STATE;
+            add_copy(g, r.out->g, r.d);
+            add_copy(b, r.out->b, r.d);
+        }
+        const float *ls = param("model.syn_embed.lut.weight", (int64_t)10 * d), *lt_w = param("model.tgt_embed.lut.weight", (int64_t)c.vocab * d);
+        if (!ls || !lt_w) return BOFI_ERR_STATE;
+        add_copy(ls, lut_syn, 10 * d);
+        const std::string lp = "model.length_predictor";
+        const float *lw1 = param(lp + ".Length_classifier1.weight", (int64_t)hh * d), *lb1 = param(lp + ".Length_classifier1.bias", hh);
+        const float *sw1 = param(lp + ".Syntactic_classifier1.weight", (int64_t)hh * d), *sb1 = param(lp + ".Syntactic_classifier1.bias", hh);
+        const float *lw2 = param(lp + ".Length_classifier2.weight", (int64_t)20 * hh), *lb2 = param(lp + ".Length_classifier2.bias", 20);
+        const float *sw2 = param(lp + ".Syntactic_classifier2.weight", (int64_t)10 * hh), *sb2 = param(lp + ".Syntactic_classifier2.bias", 10);
+        if (!lw1 || !lb1 || !sw1 || !sb1 || !lw2 || !lb2 || !sw2 || !sb2) return BOFI_ERR_STATE;
+        add_copy(lw2, const_cast<float*>(heads.len_w2), 20 * hh); add_copy(lb2, const_cast<float*>(heads.len_b2), 20);
+        add_copy(sw2, const_cast<float*>(heads.syn_w2), 10 * hh); add_copy(sb2, const_cast<float*>(heads.syn_b2), 10);
+        {   // [PackLinDesc x n][CopyDesc x m] in one buffer
+            const size_t lb = lin_tab.size() * sizeof(bofi::PackLinDesc), cb = copy_tab.size() * sizeof(bofi::CopyDesc), bytes = lb + cb;
+            std::vector<char> img(bytes);
+            memcpy(img.data(), lin_tab.data(), lb);
+            memcpy(img.data() + lb, copy_tab.data(), cb);
+            if (img != rt_cache) {
+                // (rare path: the pack kernels of a previous repack -- possibly issued on ANOTHER stream -- may still be reading the table, and its upload the
+                // pinned buffer: the whole device is waited out before either is touched)
+                ENG_HIP(hipDeviceSynchronize());
+                if (bytes > rt_bytes) {
+                    if (rt_dev) (void)hipFree(rt_dev);
+                    if (rt_pin) (void)hipHostFree(rt_pin);
+                    rt_dev = rt_pin = nullptr; rt_bytes = 0;
+                    ENG_HIP(hipMalloc(&rt_dev, bytes));
+                    ENG_HIP(hipHostMalloc(&rt_pin, bytes, hipHostMallocDefault));
+                    rt_bytes = bytes;
+                }
+                memcpy(rt_pin, img.data(), bytes);
+                ENG_HIP(hipMemcpyAsync(rt_dev, rt_pin, bytes, hipMemcpyHostToDevice, s));
+                rt_cache.swap(img);
+            }
+            const auto* ltab = static_cast<const bofi::PackLinDesc*>(rt_dev);
+            const auto* ctab = reinterpret_cast<const bofi::CopyDesc*>(static_cast<const char*>(rt_dev) + lb);
+            ENG_OK(bofi::launch_pack_lin_multi(ltab, (int)lin_tab.size(), rows, c.dtype, s));
+            ENG_OK(bofi::launch_pack_frag_multi(ltab, (int)lin_tab.size(), fblocks, s));
+            ENG_OK(bofi::launch_copy_multi(ctab, (int)copy_tab.size(), cblocks, s));
+        }
+        ENG_HIP(hipMemcpyAsync(lut_tok, lt_w, (size_t)c.vocab * d * 4, hipMemcpyDeviceToDevice, s));
+        ENG_OK(bofi::launch_pack_heads(lw1, sw1, lb1, sb1, const_cast<float*>(heads.w1t), const_cast<float*>(heads.b1), d, hh, s));
+        // input-independent tables of the bound layer: its input at (position p, label s) is lut_syn[s]*sqrt(d) + pe[p] (d_xt); K|V of all L*10 rows
+        // and the query of row 0, with [LEN] at position 0 as a label (b_x0) and -- SAIC (TransformerModel.py:1903, 515-518) -- as tgt_embed([LEN]) (b_x0_sa)
+        ENG_OK(bofi::launch_bound_table(lut_syn, lut_tok, pe, d_xt, b_x0, b_x0_sa, L, d, c.len_idx, s));
+        LinOpt o; o.ln = &b_n0;
+        ENG_OK(linear(d_xt, BOFI_DT_F32, d, t_kvself, b_kvtab, c.dtype, 2 * d, L * 10, o, s));
+        ENG_OK(linear(b_x0, BOFI_DT_F32, d, t_qself, b_q0, c.dtype, d, 1, o, s));
+        ENG_OK(linear(b_x0_sa, BOFI_DT_F32, d, t_qself, b_q0_sa, c.dtype, d, 1, o, s));
+        ENG_OK(derive_bound_tables(s));
+        if (loop_config_ok()) {
+            const std::string bl = "model.length_predictor.LengthPredictor.0";
+            BoundSrc b{};
+            b.wq_self = param(bl + ".self_attn.linears.0.weight", (int64_t)d * d); b.bq_self = param(bl + ".self_attn.linears.0.bias", d);
+            b.wk_self = param(bl + ".self_attn.linears.1.weight", (int64_t)d * d); b.bk_self = param(bl + ".self_attn.linears.1.bias", d);
+            b.wv_self = param(bl + ".self_attn.linears.2.weight", (int64_t)d * d); b.bv_self = param(bl + ".self_attn.linears.2.bias", d);
+            b.n0g = param(bl + ".sublayer.0.norm.a_2", d); b.n0b = param(bl + ".sublayer.0.norm.b_2", d);
+            b.wo_self = param(bl + ".self_attn.linears.3.weight", (int64_t)d * d);
+            b.wq_src = param(bl + ".src_attn.linears.0.weight", (int64_t)d * d); b.n1g = param(bl + ".sublayer.1.norm.a_2", d);
+            b.wo_src = param(bl + ".src_attn.linears.3.weight", (int64_t)d * d);
+            b.w1 = param(bl + ".ff.w_1.weight", (int64_t)dff * d); b.n2g = param(bl + ".sublayer.2.norm.a_2", d);
+            b.w2 = param(bl + ".ff.w_2.weight", (int64_t)d * dff);
+            b.lw1 = lw1; b.sw1 = sw1; b.hng = param(lp + ".norm.a_2", d);
+            if (!b.wq_self || !b.bq_self || !b.wk_self || !b.bk_self || !b.wv_self || !b.bv_self || !b.n0g || !b.n0b || !b.wo_self || !b.wq_src || !b.n1g || !b.wo_src ||
+                !b.w1 || !b.n2g || !b.w2 || !b.hng)
+                return BOFI_ERR_STATE;
+            ENG_OK(derive_bound_f16(b, s));
+        }
         return BOFI_OK;
     }
     // BOFI_BOUND_LOOP (re-read after bofi_reload_env): 0 = the five-launch iterations of rounds 2-4 always, 1 (default) = the persistent loop kernel unless the caller
@@ -1070,122 +1141,9 @@ int bofi_engine_refresh_device(bofi_engine_t* e, int n, const char* const* names
     g_err.clear();
     if (e->is_fork) return fail(BOFI_ERR_STATE, "refresh the parent engine (forks share its weights)");
     if (!e->finalized) return fail(BOFI_ERR_STATE, "engine not finalized: the first load goes through set_weight + finalize");
-    hipStream_t s = (hipStream_t)stream;
-    const bofi_config_t& c = e->cfg;
-    const int d = c.d_model, L = e->L, hh = c.head_hidden;
-    std::map<std::string, std::pair<const float*, int64_t>> src;
+    DevParams src;
     for (int i = 0; i < n; ++i) src[names[i]] = {ptrs[i], numels[i]};
-    auto get = [&](const std::string& name, int64_t numel) -> const float* {
-        auto it = src.find(name);
-        if (it == src.end() || !it->second.first) { g_err = "missing weight " + name; return nullptr; }
-        if (it->second.second != numel) { g_err = "weight " + name + " has " + std::to_string(it->second.second) + " elements, expected " + std::to_string(numel); return nullptr; }
-        return it->second.first;
-    };
-    // Every Linear's repack (stack, fold the pre-norm, cast, column sums), the fragment-major copies and the small float32 vectors as THREE launches
-    // over descriptor tables in device memory (they were ~230 launches and copies: 1.5 ms of a training step that decodes with its current weights).
-    // The tables hold the caller's pointers: uploaded again only when one of them changed.
-    std::vector<bofi::PackLinDesc> lt;
-    std::vector<bofi::CopyDesc> ct;
-    int rows = 0, fblocks = 0, cblocks = 0;
-    auto add_copy = [&](const float* src, float* dst, int n) { ct.push_back(bofi::CopyDesc{src, dst, n, cblocks}); cblocks += (n + 255) / 256; };
-    for (const auto& r : e->lin_recipes) {
-        bofi::PackLinDesc dsc{};
-        bofi::PackLinArgs& a = dsc.a;
-        a.nsrc = (int)r.prefixes.size(); a.n_each = r.n_each; a.K = r.K;
-        if (a.nsrc > 16) return fail(BOFI_ERR_STATE, "too many stacked matrices");
-        for (int i = 0; i < a.nsrc; ++i) {
-            a.w[i] = get(r.prefixes[i] + ".weight", (int64_t)r.n_each * r.K);
-            a.b[i] = get(r.prefixes[i] + ".bias", r.n_each);
-            if (!a.w[i] || !a.b[i]) return BOFI_ERR_STATE;
-        }
-        if (!r.fold.empty()) {
-            a.gain = get(r.fold + ".a_2", r.K);
-            a.bln = get(r.fold + ".b_2", r.K);
-            if (!a.gain || !a.bln) return BOFI_ERR_STATE;
-        }
-        a.bout = r.out->b; a.cs = r.out->cs;
-        if (!r.out->w || !a.bout || (a.gain && !a.cs)) return fail(BOFI_ERR_STATE, "refresh: a packed weight is missing");
-        dsc.wout = r.out->w; dsc.wp = r.out->wp; dsc.Npad = r.out->Npad;
-        dsc.row0 = rows; rows += (a.n_each * a.nsrc + 3) / 4 * 4;
-        dsc.blk0 = fblocks; if (dsc.wp) fblocks += (int)(((size_t)dsc.Npad * r.K / 8 + 255) / 256);
-        lt.push_back(dsc);
-    }
-    for (const auto& r : e->norm_recipes) {
-        const float *g = get(r.prefix + ".a_2", r.d), *b = get(r.prefix + ".b_2", r.d);
-        if (!g || !b) return BOFI_ERR_STATE;
-        add_copy(g, r.out->g, r.d);
-        add_copy(b, r.out->b, r.d);
-    }
-    const float *ls = get("model.syn_embed.lut.weight", (int64_t)10 * d), *lt_w = get("model.tgt_embed.lut.weight", (int64_t)c.vocab * d);
-    if (!ls || !lt_w) return BOFI_ERR_STATE;
-    add_copy(ls, e->lut_syn, 10 * d);
-    const float *lw1, *lb1, *sw1, *sb1;
-    {
-        const std::string lp = "model.length_predictor";
-        lw1 = get(lp + ".Length_classifier1.weight", (int64_t)hh * d); lb1 = get(lp + ".Length_classifier1.bias", hh);
-        sw1 = get(lp + ".Syntactic_classifier1.weight", (int64_t)hh * d); sb1 = get(lp + ".Syntactic_classifier1.bias", hh);
-        const float *lw2 = get(lp + ".Length_classifier2.weight", (int64_t)20 * hh), *lb2 = get(lp + ".Length_classifier2.bias", 20);
-        const float *sw2 = get(lp + ".Syntactic_classifier2.weight", (int64_t)10 * hh), *sb2 = get(lp + ".Syntactic_classifier2.bias", 10);
-        if (!lw1 || !lb1 || !sw1 || !sb1 || !lw2 || !lb2 || !sw2 || !sb2) return BOFI_ERR_STATE;
-        auto& h = e->heads;
-        add_copy(lw2, const_cast<float*>(h.len_w2), 20 * hh); add_copy(lb2, const_cast<float*>(h.len_b2), 20);
-        add_copy(sw2, const_cast<float*>(h.syn_w2), 10 * hh); add_copy(sb2, const_cast<float*>(h.syn_b2), 10);
-    }
-    {   // [PackLinDesc x n][CopyDesc x m] in one buffer
-        const size_t lb = lt.size() * sizeof(bofi::PackLinDesc), cb = ct.size() * sizeof(bofi::CopyDesc), bytes = lb + cb;
-        std::vector<char> img(bytes);
-        memcpy(img.data(), lt.data(), lb);
-        memcpy(img.data() + lb, ct.data(), cb);
-        if (img != e->rt_cache) {
-            // (rare path: the pack kernels of a previous refresh -- possibly issued on ANOTHER stream -- may still be reading the table, and its upload the
-            // pinned buffer: the whole device is waited out before either is touched)
-            ENG_HIP(hipDeviceSynchronize());
-            if (bytes > e->rt_bytes) {
-                if (e->rt_dev) (void)hipFree(e->rt_dev);
-                if (e->rt_pin) (void)hipHostFree(e->rt_pin);
-                e->rt_dev = e->rt_pin = nullptr; e->rt_bytes = 0;
-                ENG_HIP(hipMalloc(&e->rt_dev, bytes));
-                ENG_HIP(hipHostMalloc(&e->rt_pin, bytes, hipHostMallocDefault));
-                e->rt_bytes = bytes;
-            }
-            memcpy(e->rt_pin, img.data(), bytes);
-            ENG_HIP(hipMemcpyAsync(e->rt_dev, e->rt_pin, bytes, hipMemcpyHostToDevice, s));
-            e->rt_cache.swap(img);
-        }
-        const auto* ltab = static_cast<const bofi::PackLinDesc*>(e->rt_dev);
-        const auto* ctab = reinterpret_cast<const bofi::CopyDesc*>(static_cast<const char*>(e->rt_dev) + lb);
-        ENG_OK(bofi::launch_pack_lin_multi(ltab, (int)lt.size(), rows, c.dtype, s));
-        ENG_OK(bofi::launch_pack_frag_multi(ltab, (int)lt.size(), fblocks, s));
-        ENG_OK(bofi::launch_copy_multi(ctab, (int)ct.size(), cblocks, s));
-    }
-    ENG_HIP(hipMemcpyAsync(e->lut_tok, lt_w, (size_t)c.vocab * d * 4, hipMemcpyDeviceToDevice, s));
-    ENG_OK(bofi::launch_pack_heads(lw1, sw1, lb1, sb1, const_cast<float*>(e->heads.w1t), const_cast<float*>(e->heads.b1), d, hh, s));
-    // the bound layer's input-independent tables (as at the end of finalize)
-    ENG_OK(bofi::launch_bound_table(e->lut_syn, e->lut_tok, e->pe, e->d_xt, e->b_x0, e->b_x0_sa, L, d, c.len_idx, s));
-    bofi_engine::LinOpt o; o.ln = &e->b_n0;
-    ENG_OK(e->linear(e->d_xt, BOFI_DT_F32, d, e->t_kvself, e->b_kvtab, c.dtype, 2 * d, L * 10, o, s));
-    ENG_OK(e->linear(e->b_x0, BOFI_DT_F32, d, e->t_qself, e->b_q0, c.dtype, d, 1, o, s));
-    ENG_OK(e->linear(e->b_x0_sa, BOFI_DT_F32, d, e->t_qself, e->b_q0_sa, c.dtype, d, 1, o, s));
-    ENG_OK(e->derive_bound_tables(s));
-    if (e->loop_config_ok()) {
-        const std::string bl = "model.length_predictor.LengthPredictor.0", lp = "model.length_predictor";
-        const int dff = c.d_ff;
-        bofi_engine::BoundSrc b{};
-        b.wq_self = get(bl + ".self_attn.linears.0.weight", (int64_t)d * d); b.bq_self = get(bl + ".self_attn.linears.0.bias", d);
-        b.wk_self = get(bl + ".self_attn.linears.1.weight", (int64_t)d * d); b.bk_self = get(bl + ".self_attn.linears.1.bias", d);
-        b.wv_self = get(bl + ".self_attn.linears.2.weight", (int64_t)d * d); b.bv_self = get(bl + ".self_attn.linears.2.bias", d);
-        b.n0g = get(bl + ".sublayer.0.norm.a_2", d); b.n0b = get(bl + ".sublayer.0.norm.b_2", d);
-        b.wo_self = get(bl + ".self_attn.linears.3.weight", (int64_t)d * d);
-        b.wq_src = get(bl + ".src_attn.linears.0.weight", (int64_t)d * d); b.n1g = get(bl + ".sublayer.1.norm.a_2", d);
-        b.wo_src = get(bl + ".src_attn.linears.3.weight", (int64_t)d * d);
-        b.w1 = get(bl + ".ff.w_1.weight", (int64_t)dff * d); b.n2g = get(bl + ".sublayer.2.norm.a_2", d);
-        b.w2 = get(bl + ".ff.w_2.weight", (int64_t)d * dff);
-        b.lw1 = lw1; b.sw1 = sw1; b.hng = get(lp + ".norm.a_2", d);
-        if (!b.wq_self || !b.bq_self || !b.wk_self || !b.bk_self || !b.wv_self || !b.bv_self || !b.n0g || !b.n0b || !b.wo_self || !b.wq_src || !b.n1g || !b.wo_src ||
-            !b.w1 || !b.n2g || !b.w2 || !b.hng)
-            return BOFI_ERR_STATE;
-        ENG_OK(e->derive_bound_f16(b, s));
-    }
+    ENG_OK(e->repack(src, (hipStream_t)stream));
     e->host.clear();                          // the host copies are stale now; a later finalize needs set_weight again
     return BOFI_OK;
 }
@@ -1369,9 +1327,9 @@ int bofi_engine_finalize(bofi_engine_t* e) {
         auto it = e->host.find("model.pos_embed.pe");
         if (!ls || !lt) return BOFI_ERR_STATE;
         if (it == e->host.end() || it->second.size() < (size_t)L * d) return fail(BOFI_ERR_STATE, "missing weight model.pos_embed.pe");
-        ENG_OK(e->upload_f32(&e->lut_syn, *ls));
-        ENG_OK(e->upload_f32(&e->lut_tok, *lt));
-        std::vector<float> pe(it->second.begin(), it->second.begin() + (size_t)L * d);
+        ENG_OK(e->dalloc(&e->lut_syn, ls->size()));
+        ENG_OK(e->dalloc(&e->lut_tok, lt->size()));
+        std::vector<float> pe(it->second.begin(), it->second.begin() + (size_t)L * d);      // a buffer, not a parameter: no repack carries it
         ENG_OK(e->upload_f32(&e->pe, pe));
     }
     // bound layer
@@ -1387,26 +1345,19 @@ int bofi_engine_finalize(bofi_engine_t* e) {
         const std::string lp = "model.length_predictor";
         Norm& nf = e->head_norm;
         ENG_OK(e->make_norm(&nf, lp + ".norm", d));
-        const auto *lw1 = e->get(lp + ".Length_classifier1.weight", (size_t)hh * d), *lb1 = e->get(lp + ".Length_classifier1.bias", hh);
-        const auto *sw1 = e->get(lp + ".Syntactic_classifier1.weight", (size_t)hh * d), *sb1 = e->get(lp + ".Syntactic_classifier1.bias", hh);
-        const auto *lw2 = e->get(lp + ".Length_classifier2.weight", (size_t)20 * hh), *lb2 = e->get(lp + ".Length_classifier2.bias", 20);
-        const auto *sw2 = e->get(lp + ".Syntactic_classifier2.weight", (size_t)10 * hh), *sb2 = e->get(lp + ".Syntactic_classifier2.bias", 10);
-        if (!lw1 || !lb1 || !sw1 || !sb1 || !lw2 || !lb2 || !sw2 || !sb2) return BOFI_ERR_STATE;
-        std::vector<float> w1((size_t)d * 2 * hh), b1(*lb1);          // transposed: [d][2*hh]
-        for (int j = 0; j < hh; ++j)
-            for (int k = 0; k < d; ++k) {
-                w1[(size_t)k * 2 * hh + j] = (*lw1)[(size_t)j * d + k];
-                w1[(size_t)k * 2 * hh + hh + j] = (*sw1)[(size_t)j * d + k];
-            }
-        b1.insert(b1.end(), sb1->begin(), sb1->end());
-        float *p_w1, *p_b1, *p_lw2, *p_lb2, *p_sw2, *p_sb2;
-        ENG_OK(e->upload_f32(&p_w1, w1)); ENG_OK(e->upload_f32(&p_b1, b1));
-        ENG_OK(e->upload_f32(&p_lw2, *lw2)); ENG_OK(e->upload_f32(&p_lb2, *lb2));
-        ENG_OK(e->upload_f32(&p_sw2, *sw2)); ENG_OK(e->upload_f32(&p_sb2, *sb2));
+        if (!e->get(lp + ".Length_classifier1.weight", (size_t)hh * d) || !e->get(lp + ".Length_classifier1.bias", hh) ||
+            !e->get(lp + ".Syntactic_classifier1.weight", (size_t)hh * d) || !e->get(lp + ".Syntactic_classifier1.bias", hh) ||
+            !e->get(lp + ".Length_classifier2.weight", (size_t)20 * hh) || !e->get(lp + ".Length_classifier2.bias", 20) ||
+            !e->get(lp + ".Syntactic_classifier2.weight", (size_t)10 * hh) || !e->get(lp + ".Syntactic_classifier2.bias", 10))
+            return BOFI_ERR_STATE;
+        float *p_w1, *p_b1, *p_lw2, *p_lb2, *p_sw2, *p_sb2;          // first layers of both heads transposed side by side [d][2*hh], their biases concatenated
+        ENG_OK(e->dalloc(&p_w1, (size_t)d * 2 * hh)); ENG_OK(e->dalloc(&p_b1, (size_t)2 * hh));
+        ENG_OK(e->dalloc(&p_lw2, (size_t)20 * hh)); ENG_OK(e->dalloc(&p_lb2, 20));
+        ENG_OK(e->dalloc(&p_sw2, (size_t)10 * hh)); ENG_OK(e->dalloc(&p_sb2, 10));
         ENG_OK(e->dalloc((char**)&e->b_w1p, (size_t)d * 2 * hh, e->tsz));
         e->heads = bofi::BoundHeadWeights{nf.g, nf.b, p_w1, p_b1, p_lw2, p_lb2, p_sw2, p_sb2, e->b_w1p};
         e->loop_ready = false;
-        if (e->loop_config_ok()) {      // the persistent loop kernel's operands (filled by derive_bound_f16 below)
+        if (e->loop_config_ok()) {      // the persistent loop kernel's operands (filled by derive_bound_f16)
             ENG_OK(e->make_lin(&e->b_heads, {lp + ".Length_classifier1", lp + ".Syntactic_classifier1"}, hh, d, lp + ".norm", 256));
             for (Lin* l : {&e->b_o_self, &e->b_q_src, &e->b_o_src, &e->b_w1, &e->b_w2, &e->b_heads}) ENG_OK(e->dalloc((char**)&l->wp16, (size_t)l->Npad * l->K, 2));
             ENG_OK(e->dalloc(&e->b_q0_32, (size_t)d)); ENG_OK(e->dalloc(&e->b_sctab, (size_t)L * 10 * c.heads)); ENG_OK(e->dalloc(&e->b_vtab, (size_t)L * 10 * d));
@@ -1425,69 +1376,40 @@ int bofi_engine_finalize(bofi_engine_t* e) {
     e->n_weight_allocs = e->allocs.size();      // everything allocated so far is weights (shared with forks)
     ENG_OK(e->alloc_workspace());
 
-    // input-independent tables of the bound layer: layer input at (position p, label s) is
-    // lut_syn[s]*sqrt(d) + pe[p]; K|V of all L*10 rows and the query of row 0 ([LEN] at position 0)
-    {
-        const auto& ls = e->host["model.syn_embed.lut.weight"];
-        const auto& pe = e->host["model.pos_embed.pe"];
-        const float sq = (float)std::sqrt((double)d);
-        std::vector<float> xt((size_t)L * 10 * d);
-        for (int p = 0; p < L; ++p)
-            for (int s = 0; s < 10; ++s)
-                for (int k = 0; k < d; ++k) xt[((size_t)p * 10 + s) * d + k] = ls[(size_t)s * d + k] * sq + pe[(size_t)p * d + k];
-        std::vector<float> x0(xt.begin() + (size_t)c.len_idx * d, xt.begin() + (size_t)(c.len_idx + 1) * d);
-        float*& d_xt = e->d_xt;
-        Lin &kvself = e->t_kvself, &qself = e->t_qself;
-        ENG_OK(e->upload_f32(&d_xt, xt));
-        ENG_OK(e->upload_f32(&e->b_x0, x0));
-        ENG_OK(e->make_lin(&kvself, {bl + ".self_attn.linears.1", bl + ".self_attn.linears.2"}, d, d));
-        ENG_OK(e->make_lin(&qself, {bl + ".self_attn.linears.0"}, d, d));
-        ENG_OK(e->dalloc((char**)&e->b_kvtab, (size_t)L * 10 * 2 * d, e->tsz));
-        ENG_OK(e->dalloc((char**)&e->b_q0, (size_t)d, e->tsz));
-        bofi_engine::LinOpt o; o.ln = &e->b_n0;
-        ENG_OK(e->linear(d_xt, BOFI_DT_F32, d, kvself, e->b_kvtab, c.dtype, 2 * d, L * 10, o, nullptr));
-        ENG_OK(e->linear(e->b_x0, BOFI_DT_F32, d, qself, e->b_q0, c.dtype, d, 1, o, nullptr));
-        // SAIC: position 0 of the bound input is tgt_embed([LEN]) (TransformerModel.py:1903, 515-518)
-        const auto& lt = e->host["model.tgt_embed.lut.weight"];
-        std::vector<float> x0s(d);
-        for (int k = 0; k < d; ++k) x0s[k] = lt[(size_t)c.len_idx * d + k] * sq + pe[k];
-        ENG_OK(e->upload_f32(&e->b_x0_sa, x0s));
-        ENG_OK(e->dalloc((char**)&e->b_q0_sa, (size_t)d, e->tsz));
-        ENG_OK(e->linear(e->b_x0_sa, BOFI_DT_F32, d, qself, e->b_q0_sa, c.dtype, d, 1, o, nullptr));
-        ENG_OK(e->make_lin(&e->b_kv_self, {bl + ".self_attn.linears.1", bl + ".self_attn.linears.2"}, d, d, bl + ".sublayer.0.norm"));
-        ENG_OK(e->dalloc((char**)&e->b_votab, (size_t)L * 10 * c.heads * d, e->tsz));
-        ENG_OK(e->dalloc(&e->b_x0b, (size_t)d));
-        ENG_OK(e->derive_bound_tables(nullptr));
-        ENG_HIP(hipDeviceSynchronize());
+    // operands and outputs of the bound layer's input-independent tables (repack)
+    ENG_OK(e->dalloc(&e->d_xt, (size_t)L * 10 * d));
+    ENG_OK(e->dalloc(&e->b_x0, (size_t)d));
+    ENG_OK(e->make_lin(&e->t_kvself, {bl + ".self_attn.linears.1", bl + ".self_attn.linears.2"}, d, d));
+    ENG_OK(e->make_lin(&e->t_qself, {bl + ".self_attn.linears.0"}, d, d));
+    ENG_OK(e->dalloc((char**)&e->b_kvtab, (size_t)L * 10 * 2 * d, e->tsz));
+    ENG_OK(e->dalloc((char**)&e->b_q0, (size_t)d, e->tsz));
+    ENG_OK(e->dalloc(&e->b_x0_sa, (size_t)d));
+    ENG_OK(e->dalloc((char**)&e->b_q0_sa, (size_t)d, e->tsz));
+    ENG_OK(e->make_lin(&e->b_kv_self, {bl + ".self_attn.linears.1", bl + ".self_attn.linears.2"}, d, d, bl + ".sublayer.0.norm"));
+    ENG_OK(e->dalloc((char**)&e->b_votab, (size_t)L * 10 * c.heads * d, e->tsz));
+    ENG_OK(e->dalloc(&e->b_x0b, (size_t)d));
+
+    // Stage the float32 parameters of the host map in one temporary arena on the device (never in e->allocs) and pack from there: the same
+    // kernels on the same values as a refresh_device with these weights
+    DevParams src;
+    size_t bytes = 256;
+    for (const auto& kv : e->host) bytes += (kv.second.size() * 4 + 255) & ~(size_t)255;
+    char* arena = nullptr;
+    ENG_HIP(hipMalloc((void**)&arena, bytes));
+    int rc = BOFI_OK;
+    size_t off = 0;
+    for (const auto& kv : e->host) {
+        const size_t nb = kv.second.size() * 4;
+        if (rc == BOFI_OK && nb && hipMemcpy(arena + off, kv.second.data(), nb, hipMemcpyHostToDevice) != hipSuccess) rc = fail(BOFI_ERR_HIP, "hipMemcpy: staging " + kv.first);
+        src[kv.first] = {(const float*)(arena + off), (int64_t)kv.second.size()};
+        off += (nb + 255) & ~(size_t)255;
     }
-    if (e->loop_config_ok()) {      // fp16 copies and float32 tables of the bounding layer from the float32 parameters (temporaries on the device)
-        std::vector<void*> tmp;
-        auto up = [&](const std::string& name, const float** out) -> int {
-            auto it = e->host.find(name);
-            if (it == e->host.end()) return fail(BOFI_ERR_STATE, "missing weight " + name);
-            void* q = nullptr;
-            ENG_HIP(hipMalloc(&q, it->second.size() * 4));
-            tmp.push_back(q);
-            ENG_HIP(hipMemcpy(q, it->second.data(), it->second.size() * 4, hipMemcpyHostToDevice));
-            *out = (const float*)q;
-            return BOFI_OK;
-        };
-        bofi_engine::BoundSrc b{};
-        const std::string lp = "model.length_predictor";
-        int rc = BOFI_OK;
-        const std::pair<std::string, const float**> items[] = {
-            {bl + ".self_attn.linears.0.weight", &b.wq_self}, {bl + ".self_attn.linears.0.bias", &b.bq_self}, {bl + ".self_attn.linears.1.weight", &b.wk_self},
-            {bl + ".self_attn.linears.1.bias", &b.bk_self}, {bl + ".self_attn.linears.2.weight", &b.wv_self}, {bl + ".self_attn.linears.2.bias", &b.bv_self},
-            {bl + ".sublayer.0.norm.a_2", &b.n0g}, {bl + ".sublayer.0.norm.b_2", &b.n0b}, {bl + ".self_attn.linears.3.weight", &b.wo_self},
-            {bl + ".src_attn.linears.0.weight", &b.wq_src}, {bl + ".sublayer.1.norm.a_2", &b.n1g}, {bl + ".src_attn.linears.3.weight", &b.wo_src},
-            {bl + ".ff.w_1.weight", &b.w1}, {bl + ".sublayer.2.norm.a_2", &b.n2g}, {bl + ".ff.w_2.weight", &b.w2},
-            {lp + ".Length_classifier1.weight", &b.lw1}, {lp + ".Syntactic_classifier1.weight", &b.sw1}, {lp + ".norm.a_2", &b.hng}};
-        for (const auto& it : items) if (rc == BOFI_OK) rc = up(it.first, it.second);
-        if (rc == BOFI_OK) rc = e->derive_bound_f16(b, nullptr);
-        (void)hipDeviceSynchronize();
-        for (void* q : tmp) (void)hipFree(q);
-        if (rc != BOFI_OK) return rc;
-    }
+    if (rc == BOFI_OK) rc = e->repack(src, nullptr);
+    const hipError_t done = hipDeviceSynchronize();
+    (void)hipFree(arena);
+    e->rt_cache.clear();        // the descriptor table names the arena: no later refresh_device may take it for its own
+    if (rc != BOFI_OK) return rc;
+    if (done != hipSuccess) return fail(BOFI_ERR_HIP, std::string("hipDeviceSynchronize: ") + hipGetErrorString(done));
     // NB: hardware-queue assignment follows stream creation order; the capture stream is created here (and in
     // fork) because that order measured best with 4 decodes in flight on torch's pooled streams
     if (!e->cap_stream) ENG_HIP(hipStreamCreateWithFlags(&e->cap_stream, hipStreamNonBlocking));

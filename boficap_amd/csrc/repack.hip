@@ -1,8 +1,8 @@
-// Device-side refresh of the decode engine's packed weights from float32 parameters that already live in HBM (the
-// trainer's flat bucket): what bofi_engine_finalize does on the host -- stack q|k|v, fold the pre-norm LayerNorm into the
-// consumer GEMM (w' = w * gain, c[n] = bias[n] + sum_k b_ln[k] w[n][k], colsum[n] = sum_k round(w'[n][k])), cast to the
-// compute dtype, transpose the bound heads' first layers, rebuild the bound layer's input table -- as a handful of
-// kernels, so that a training loop can decode with its current weights without a host round trip.
+// The decode engine's weight packing, from float32 parameters in HBM (bofi_engine::repack in engine.hip; bofi_engine_finalize runs it on a staged
+// copy of the host tensors, bofi_engine_refresh_device on the trainer's flat bucket): stack q|k|v, fold the pre-norm LayerNorm into the consumer
+// GEMM (w' = w * gain, c[n] = bias[n] + sum_k b_ln[k] w[n][k], colsum[n] = sum_k round(w'[n][k]): of the ROUNDED weight, so that the mean term of
+// the GEMM's epilogue cancels exactly what the MFMA accumulated), cast to the compute dtype, transpose the bound heads' first layers, build the
+// bound layer's input table -- as a handful of kernels, so that a training loop can decode with its current weights without a host round trip.
 #include "bofi_common.h"
 #include "bofi_kernels.h"
 #include "bofi_naic.h"
@@ -15,34 +15,8 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void pack_lin_kernel(PackLinArgs a, T* __restrict__ wout) {
-    const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (n >= a.n_each * a.nsrc) return;
-    const int src = n / a.n_each, r = n - src * a.n_each;
-    const float* row = a.w[src] + (size_t)r * a.K;
-    T* out = wout + (size_t)n * a.K;
-    double c = 0.0, s = 0.0;
-    for (int k = lane; k < a.K; k += 64) {
-        float wv = row[k];
-        if (a.gain) {
-            c += (double)a.bln[k] * (double)wv;
-            wv = wv * a.gain[k];
-        }
-        ElemOps<T>::store(out + k, wv);
-        float rv = wv;
-        if constexpr (sizeof(T) == 2) rv = bf16_to_f32(f32_to_bf16(wv));
-        s += (double)rv;
-    }
-    if (a.gain) { c = wave_sum_f64(c); s = wave_sum_f64(s); }
-    if (lane == 0) {
-        a.bout[n] = (float)((double)a.b[src][r] + c);
-        if (a.gain) a.cs[n] = (float)s;
-    }
-}
-
-// ---- the batched forms (bofi_engine_refresh_device: ~230 launches and copies of a refresh as three): a workgroup finds its entry by bisection
-// over the table's first rows / blocks
+// ---- the batched forms (~230 launches and copies of a repack as three): a workgroup finds its entry by bisection over the table's first
+// rows / blocks
 template <typename F>
 __device__ __forceinline__ int find_entry(int n_ent, int x, F first) {      // largest e with first(e) <= x
     int lo = 0, hi = n_ent - 1;
@@ -61,7 +35,7 @@ __global__ __launch_bounds__(256) void pack_lin_multi_kernel(const PackLinDesc* 
     const float* row = a.w[src] + (size_t)r * a.K;
     T* out = static_cast<T*>(tab[e].wout) + (size_t)n * a.K;
     double c = 0.0, s = 0.0;
-    for (int k = lane; k < a.K; k += 64) {            // (the same sums in the same order as pack_lin_kernel)
+    for (int k = lane; k < a.K; k += 64) {            // c, s: 64 strided partial sums in double, reduced across the wave, rounded to float32 once
         float wv = row[k];
         if (a.gain) {
             c += (double)a.bln[k] * (double)wv;
@@ -122,15 +96,6 @@ int launch_copy_multi(const CopyDesc* tab_dev, int n_ent, int total_blocks, hipS
     return BOFI_OK;
 }
 
-int launch_pack_lin(const PackLinArgs& a, void* wout, int dtype, hipStream_t st) {
-    const int N = a.n_each * a.nsrc;
-    if (N <= 0 || a.K <= 0 || a.nsrc > 16 || !wout || !a.bout || (a.gain && (!a.bln || !a.cs))) return BOFI_ERR_ARG;
-    if (dtype == BOFI_DT_F32) hipLaunchKernelGGL((pack_lin_kernel<float>), dim3((N + 3) / 4), dim3(256), 0, st, a, (float*)wout);
-    else hipLaunchKernelGGL((pack_lin_kernel<bf16_t>), dim3((N + 3) / 4), dim3(256), 0, st, a, (bf16_t*)wout);
-    BOFI_CHECK_LAUNCH();
-    return BOFI_OK;
-}
-
 // bound heads: first layers of both heads transposed side by side [d][2*hh], biases concatenated
 __global__ void pack_heads_kernel(const float* __restrict__ lw1, const float* __restrict__ sw1, const float* __restrict__ lb1,
                                   const float* __restrict__ sb1, float* __restrict__ w1t, float* __restrict__ b1, int d, int hh) {
@@ -149,9 +114,11 @@ int launch_pack_heads(const float* lw1, const float* sw1, const float* lb1, cons
     return BOFI_OK;
 }
 
-// bound-layer input table: xt[(p*10 + s)*d + k] = lut_syn[s][k]*sqrt(d) + pe[p][k]; x0 = row (0, len_idx); x0_sa from the word table
+// bound-layer input table: xt[(p*10 + s)*d + k] = lut_syn[s][k]*sqrt(d) + pe[p][k]; x0 = row (0, len_idx); x0_sa from the word table.  The product
+// is rounded before the sum, as the reference's two operations are (and as the host loops this kernel replaced did): contraction into a fused multiply-add is switched off in the kernel's body.
 __global__ void bound_table_kernel(const float* __restrict__ lut_syn, const float* __restrict__ lut_tok, const float* __restrict__ pe,
                                    float* __restrict__ xt, float* __restrict__ x0, float* __restrict__ x0_sa, int L, int d, int len_idx, float sq) {
+#pragma clang fp contract(off)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < L * 10 * d) {
         const int k = i % d, ps = i / d, s = ps % 10, p = ps / 10;

@@ -507,8 +507,11 @@ def test_dynamic_batching_keeps_per_batch_results(dtype, weight_cache, manifest)
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_device_side_weight_refresh_equals_a_fresh_load(dtype, weight_cache, manifest):
-    """bofi_engine_refresh_device (re-pack from float32 parameters in HBM: stacking, LayerNorm folding, cast, bound tables,
-    all as kernels) against an engine loaded through the host path with the same weights; captured graphs stay valid."""
+    """bofi_engine_refresh_device (the engine's one re-pack, from the caller's float32 parameters in HBM: stacking, LayerNorm
+    folding, cast, bound tables, all as kernels) against an engine whose load_state_dict ran the same re-pack on a staged copy
+    of the same weights: a graph captured before the refresh stays valid and replays with the new weights, a refresh back
+    restores the first ids, an incomplete parameter set is refused.  (Exact equality of the two entries, eagerly:
+    test_refresh_and_load_pack_the_same_bits.)"""
     from boficap_amd.engine import BofiEngine
     m = manifest["tiny_mix"]
     cfg, sd_a = weight_cache(m["config"], m["seed"], m["gen_scale"], m["digest"])
@@ -537,6 +540,71 @@ def test_device_side_weight_refresh_equals_a_fresh_load(dtype, weight_cache, man
     assert torch.equal(back["seq"], first["seq"])
     with pytest.raises(Exception):
         eng.refresh_from_device({k: v for k, v in dev_b.items() if "generator" not in k})
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_refresh_and_load_pack_the_same_bits(dtype, weight_cache, manifest):
+    """One packing implementation behind both entries: an engine that loaded weight set b directly and one that loaded set a and
+    was then refreshed with b from device memory decode -- eagerly, no graph -- to identical tensors, log-probs included
+    (NaN positions equal, every other value bit-equal).  The guard that finalize and refresh_device cannot drift apart."""
+    from boficap_amd.engine import BofiEngine
+    m = manifest["tiny_mix"]
+    cfg, sd_a = weight_cache(m["config"], m["seed"], m["gen_scale"], m["digest"])
+    _, sd_b = weight_cache("TINY", 0, 1.0)
+    att = torch.from_numpy(load_golden("tiny_mix")["att_feats"])[:8].cuda().to(dtype).contiguous()
+    assert att.shape[:2] == (8, 36)
+    direct = BofiEngine(cfg, dtype, max_batch=8, max_regions=36)
+    direct.load_state_dict(sd_b)
+    refreshed = BofiEngine(cfg, dtype, max_batch=8, max_regions=36)
+    refreshed.load_state_dict(sd_a)
+    dev_b = {k: torch.from_numpy(v).cuda().contiguous() for k, v in sd_b.items()}
+    refreshed.refresh_from_device(dev_b)
+    for decode in ("decode_naic", "decode_saic"):
+        want, got = getattr(direct, decode)(att), getattr(refreshed, decode)(att)
+        torch.cuda.synchronize()
+        tensors = sorted(k for k, v in want.items() if torch.is_tensor(v))
+        assert "seq" in tensors and "seq_logprob" in tensors and tensors == sorted(k for k, v in got.items() if torch.is_tensor(v))
+        for k in tensors:
+            a, b = got[k], want[k]
+            assert a.shape == b.shape and a.dtype == b.dtype, (decode, k)
+            if a.is_floating_point():
+                assert torch.equal(a.isnan(), b.isnan()) and torch.equal(a.nan_to_num(), b.nan_to_num()), (decode, k)
+            else:
+                assert torch.equal(a, b), (decode, k)
+
+
+def test_cross_kv_stack_of_more_than_16_matrices():
+    """Eight decoder layers and the bound layer: 18 cross-attention K / V matrices stacked into one Linear, more than one entry of
+    the repack's descriptor table holds (16), so the stack is packed as two entries.  The float32 decode against the oracle --
+    slot layout equal, log-probs within smoke()'s bar for this comparison at this width (1e-3; a misplaced row block is an error
+    of order 1), ids equal wherever the oracle's top-2 gap exceeds it -- and a refresh_device with the same weights changes nothing."""
+    import dataclasses
+    from boficap_amd import weights as W
+    from boficap_amd.config import TINY
+    from boficap_amd.engine import BofiEngine
+    cfg = dataclasses.replace(TINY, N_dec=8)
+    sd = dict(W.make_state_dict(TINY, seed=0, gen_scale=6.0))            # tiny_mix's encoder and bounding network (its layouts: phrases in six of eight images) ...
+    sd.update({k: v for k, v in W.make_state_dict(cfg, seed=0, gen_scale=6.0).items() if k not in sd})      # ... and decoder layers 2 .. 7 behind its two
+    att = torch.from_numpy(load_golden("tiny_mix")["att_feats"])
+    oseq, olp, opn, opl, ops, _ = O.sample_naic(O.as_torch(sd), cfg, att)
+    assert int(opn.sum()) > 0
+    eng = BofiEngine(cfg, torch.float32, max_batch=8, max_regions=36)
+    eng.load_state_dict(sd)
+    r = {k: v.clone() for k, v in eng.decode_naic(att.cuda()).items() if torch.is_tensor(v)}
+    assert torch.equal(r["phrase_num"].cpu(), opn) and torch.equal(r["phrase_length"].cpu(), opl) and torch.equal(r["phrase_syn"].cpu(), ops)
+    lp = r["seq_logprob"].cpu()
+    assert torch.equal(lp.isnan(), olp.isnan())
+    err = float((lp - olp).nan_to_num().abs().max())
+    print(f"max |dlogp| against the oracle: {err:.3e}")
+    assert err < 1e-3, err
+    top = torch.topk(olp.nan_to_num(-1e30), 2, dim=2)[0]
+    safe = (top[..., 0] - top[..., 1]) > 1e-3
+    assert torch.equal(r["seq"].cpu()[safe], oseq[safe])
+    dev = {k: torch.from_numpy(v).cuda().contiguous() for k, v in sd.items()}
+    eng.refresh_from_device(dev)
+    again = eng.decode_naic(att.cuda())
+    assert torch.equal(again["seq"], r["seq"]) and torch.equal(again["phrase_length"], r["phrase_length"])
+    assert torch.equal(again["seq_logprob"].isnan(), r["seq_logprob"].isnan()) and torch.equal(again["seq_logprob"].nan_to_num(), r["seq_logprob"].nan_to_num())
 
 
 def test_dynamic_batching_with_refinement_rounds(weight_cache, manifest):
