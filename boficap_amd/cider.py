@@ -241,22 +241,29 @@ class CiderD:
         """The scorer of one batch as a ``score_fn(seq)`` for XETrainer.rl_step."""
         return _Bound(self, data_gts, seq_per_img, weight=weight)
 
-    def _launch(self, refs, seq, cand_len, seq_per_img, weight, want64):
-        N, S = seq.shape
-        pk = pack_references(refs, N, S, seq_per_img, self.device, self.df)
+    def records(self, pk):
+        """The records of uploaded references ``pk`` (``upload``) by bofi_cider_refs, enqueued on the current stream: ``(pk, tensors)`` for
+        ``_launch(records=...)`` -- a caller that scores many candidate sets against the same references builds them once."""
         R, stride = pk.R, pk.stride
         rec_keys = torch.empty(R, stride, dtype=torch.int64, device=self.device)
         rec_w = torch.empty(R, stride, dtype=torch.float64, device=self.device)
         rec_off = torch.empty(R, ORDERS + 1, dtype=torch.int32, device=self.device)
         rec_meta = torch.empty(R, ORDERS + 1, dtype=torch.float64, device=self.device)
+        hip.check(hip.lib().bofi_cider_refs(hip.ptr(pk.tok), hip.ptr(pk.lens), R, pk.width, hip.ptr(pk.df_keys), hip.ptr(pk.df_vals), pk.n_df, pk.L,
+                                            hip.ptr(rec_keys), hip.ptr(rec_w), hip.ptr(rec_off), hip.ptr(rec_meta), stride, hip.stream_ptr()),
+                  "bofi_cider_refs")
+        return pk, (rec_keys, rec_w, rec_off, rec_meta)
+
+    def _launch(self, refs, seq, cand_len, seq_per_img, weight, want64, records=None):
+        """``records``: what ``records()`` returned for these references -- no packing and no refs kernel then (``refs`` is not read)."""
+        N, S = seq.shape
+        pk, (rec_keys, rec_w, rec_off, rec_meta) = records if records is not None else self.records(
+            pack_references(refs, N, S, seq_per_img, self.device, self.df))
         out = torch.empty(N, dtype=torch.float32, device=self.device)
         out64 = torch.empty(N, dtype=torch.float64, device=self.device) if want64 else None
-        lib, st = hip.lib(), hip.stream_ptr()
-        hip.check(lib.bofi_cider_refs(hip.ptr(pk.tok), hip.ptr(pk.lens), R, pk.width, hip.ptr(pk.df_keys), hip.ptr(pk.df_vals), pk.n_df, pk.L,
-                                      hip.ptr(rec_keys), hip.ptr(rec_w), hip.ptr(rec_off), hip.ptr(rec_meta), stride, st), "bofi_cider_refs")
-        hip.check(lib.bofi_cider_score(hip.ptr(seq), hip.ptr(cand_len), N, S, seq_per_img, hip.ptr(pk.start), hip.ptr(pk.df_keys), hip.ptr(pk.df_vals),
-                                       pk.n_df, pk.L, self.sigma, float(weight), hip.ptr(rec_keys), hip.ptr(rec_w), hip.ptr(rec_off), hip.ptr(rec_meta),
-                                       stride, hip.ptr(out), hip.ptr(out64), st), "bofi_cider_score")
+        hip.check(hip.lib().bofi_cider_score(hip.ptr(seq), hip.ptr(cand_len), N, S, seq_per_img, hip.ptr(pk.start), hip.ptr(pk.df_keys), hip.ptr(pk.df_vals),
+                                             pk.n_df, pk.L, self.sigma, float(weight), hip.ptr(rec_keys), hip.ptr(rec_w), hip.ptr(rec_off), hip.ptr(rec_meta),
+                                             pk.stride, hip.ptr(out), hip.ptr(out64), hip.stream_ptr()), "bofi_cider_score")
         return out, out64
 
     def score(self, data_gts, seq, seq_per_img: int, weight: float = 1.0, out64: bool = False):

@@ -1,0 +1,142 @@
+"""The evaluation of a split as the reference's ``eval_split`` runs it for a UIC model (captioning/utils/eval_utils.py:425-520): the validation
+loss, one greedy caption per image, and the language scores that need no Java (boficap_amd.lang_eval).
+
+    val_loss, predictions, lang_stats = eval_split(model, feats, store_or_gts, eval_kwargs)
+
+``feats``: region features [N, R, F] (array or tensor on the host).  ``store_or_gts``: a label source with ``batch(image_ixs, seq_per_img, rng)``
+and ``gts(ix)`` (``data.LabelStore``, ``SyntheticLabels``) -- the loss is computed and the references come from it --, or the per-image
+references alone (integer rows or id strings; no loss then), or None.  ``eval_kwargs``:
+
+    inference_mode   'NAIC' (default; the batches go through ``model.decode_many``) or 'SAIC' (one ``mode='sample'`` call per batch)
+    batch_size       images per batch (default 64);  seq_per_img  captions per image of the loss pass (default 5)
+    language_eval    1: ``lang_stats`` from ``eval_kwargs['lang_eval']``, a ``LanguageEval`` of these images' references that the CALLER keeps
+                     from one validation to the next (built here, and stored under that key, if absent)
+    image_ixs        the label source's image of every row of ``feats`` (default 0 .. N - 1)
+    verbose_loss     0: no loss pass;  vocab  {str(id): word} for the entries' 'caption'
+    batches_per_launch, in_flight, fused_vocab     ``decode_many``'s knobs
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import weights as W
+from .collate import synthetic_training_batch
+
+LANG_KEYS = ("Bleu_1", "Bleu_2", "Bleu_3", "Bleu_4", "ROUGE_L", "CIDEr", "entropy", "perplexity")
+
+
+def entry_of(i, k, seq, pn, pl, ent, ppl, vocab=None):
+    """The prediction entry of row ``k`` of a decoded batch whose first image is ``i``."""
+    ids = [int(v) for v in seq[k].tolist() if v > 0]
+    entry = {"image_id": i + k, "seq": ids, "phrase_num": int(pn[k]), "phrase_length": [int(v) for v in pl[k].tolist() if v > 0],
+             "entropy": float(ent[k]), "perplexity": float(ppl[k])}
+    if vocab:
+        entry["caption"] = " ".join(vocab.get(str(v), "UNK") for v in ids if v > 6)
+    return entry
+
+
+def validation_loss(model, feats, store, batch_size: int, seq_per_img: int, image_ixs=None):
+    """The loss of eval_split (verbose_loss, eval_utils.py:440-453) as a pass of its own: (sum of the batches' LanguageModelCriterion_UIC losses,
+    number of batches).  Image i of ``feats`` is image ``image_ixs[i]`` (default i) of ``store``."""
+    from .loss_wrapper import LanguageModelCriterion_UIC
+    crit, rng, loss_sum, loss_evals = LanguageModelCriterion_UIC(), np.random.default_rng(0), 0.0, 0
+    with torch.no_grad():
+        for i in range(0, len(feats), batch_size):
+            att = torch.from_numpy(np.ascontiguousarray(feats[i:i + batch_size])).cuda()
+            fc = torch.zeros(att.size(0), 0, device="cuda")
+            ixs = range(i, i + att.size(0)) if image_ixs is None else [int(x) for x in image_ixs[i:i + att.size(0)]]
+            hb = store.batch(ixs, seq_per_img, rng)
+            hb.pop("gts", None)
+            b = {k: torch.from_numpy(v).cuda() for k, v in hb.items()}
+            outs = model(fc, att.float(), b["labels"], None, b["phrase_num"], b["phrase_length"], b["phrase_syn"],
+                         b["extend_phrase_syn_seq"], b["extend_phrase_seq"], b["extend_phrase_seq_mask"])
+            loss_sum += float(crit(*outs, b["phrase_num"], b["phrase_length"], b["phrase_syn"], b["labels"])[0])
+            loss_evals += 1
+    return loss_sum, loss_evals
+
+
+class SyntheticLabels:
+    """A label source for the synthetic stream: ``n_img`` images of ``seq_per_img`` synthetic captions each from a fixed seed, and the region
+    features that go with them; the captions are the images' references."""
+
+    def __init__(self, cfg, n_img: int, seq_per_img: int, seed: int = 0, regions: int = 36):
+        self.num_images, self.seq_per_img = int(n_img), int(seq_per_img)
+        self.host = synthetic_training_batch(cfg, self.num_images, self.seq_per_img, seed=seed)
+        self.feats = W.synthetic_att_feats(self.num_images, regions, cfg.att_feat_size, seed=seed)
+
+    def batch(self, image_ixs, seq_per_img: int, rng=None):
+        if int(seq_per_img) != self.seq_per_img:
+            raise ValueError(f"the synthetic labels hold {self.seq_per_img} captions per image, not {seq_per_img}")
+        ixs = np.asarray(list(image_ixs), dtype=np.int64)
+        return {k: np.ascontiguousarray(v[ixs]) for k, v in self.host.items()}
+
+    def gts(self, ix: int):
+        return self.host["labels"][int(ix), :, 1:-1]
+
+
+def _torch_feats(feats):
+    return feats if torch.is_tensor(feats) else torch.from_numpy(np.ascontiguousarray(feats))
+
+
+def eval_split(model, feats, store_or_gts, eval_kwargs):
+    """(val_loss, predictions, lang_stats) of ``feats``' images: see the module's head.  The model is put in eval() and restored."""
+    kw = eval_kwargs
+    mode = kw.get("inference_mode", "NAIC")
+    if mode not in ("NAIC", "SAIC"):
+        raise NotImplementedError(f"inference mode {mode!r}: a UIC model decodes in 'NAIC' or 'SAIC' mode")
+    batch_size, seq_per_img = int(kw.get("batch_size", 64)), int(kw.get("seq_per_img", 5))
+    N = len(feats)
+    ixs = kw.get("image_ixs")
+    store = store_or_gts if hasattr(store_or_gts, "batch") and hasattr(store_or_gts, "gts") else None
+    was_training = model.training
+    model.eval()
+    try:
+        model.engine()                                           # the engine's packed weights follow the parameters (re-packed on the device if they moved)
+        torch.cuda.synchronize()                                 # ... before any fork's stream reads them
+        val_loss = 0.0
+        if store is not None and kw.get("verbose_loss", 1):
+            loss_sum, loss_evals = validation_loss(model, feats, store, batch_size, seq_per_img, ixs)
+            val_loss = loss_sum / max(1, loss_evals)
+        predictions, seqs, ents, ppls = [], [], [], []
+        vocab = kw.get("vocab")
+        host = _torch_feats(feats)
+        with torch.no_grad():
+            if mode == "NAIC":
+                if host.dtype != torch.float32 and host.dtype != model.compute_dtype:
+                    host = host.float()
+                if model.compute_dtype == torch.bfloat16:     # (as a loader of half-precision feature files hands them over)
+                    host = host.to(torch.bfloat16)
+                if not host.is_cuda:
+                    host = host.pin_memory()
+                batches = [host[i:i + batch_size] for i in range(0, N, batch_size)]
+                i = 0
+                for r in model.decode_many(batches, batches_per_launch=int(kw.get("batches_per_launch", 16)), in_flight=kw.get("in_flight"),
+                                           fused_vocab=bool(kw.get("fused_vocab", False))):
+                    n = r["seq"].size(0)
+                    predictions.extend(entry_of(i, k, r["seq"], r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"], vocab) for k in range(n))
+                    seqs.append(r["seq"]); ents.append(r["entropy"]); ppls.append(r["perplexity"])
+                    i += n
+            else:
+                for i in range(0, N, batch_size):
+                    att = host[i:i + batch_size].cuda()
+                    fc = torch.zeros(att.size(0), 0, device="cuda")
+                    seq, lp, pn, pl, ps, _ = model(fc, att, None, opt={"train_mode": "SAIC", "sample_method": "greedy", "sample_n": 1}, mode="sample")
+                    # per-image entropy / perplexity as eval_utils.py:463-464, from the fused row reductions (bofi_vocab_stats)
+                    ent, ppl = model.engine().entropy_perplexity({"seq": seq, "seq_logprob": lp})
+                    seq, pn, pl, ent, ppl = seq.cpu(), pn.cpu(), pl.cpu(), ent.cpu(), ppl.cpu()
+                    predictions.extend(entry_of(i, k, seq, pn, pl, ent, ppl, vocab) for k in range(att.size(0)))
+                    seqs.append(seq); ents.append(ent); ppls.append(ppl)
+        lang_stats = None
+        if int(kw.get("language_eval", 0)) == 1:
+            ev = kw.get("lang_eval")
+            if ev is None:
+                if store_or_gts is None:
+                    raise ValueError("language_eval needs the images' references (a label source, or the references themselves)")
+                gts = [store.gts(int(ixs[i]) if ixs is not None else i) for i in range(N)] if store is not None else list(store_or_gts)
+                from .lang_eval import LanguageEval
+                ev = kw["lang_eval"] = LanguageEval(gts, next(model.parameters()).device)
+            lang_stats = ev.evaluate(torch.cat(seqs), torch.cat(ents), torch.cat(ppls))
+    finally:
+        model.train(was_training)
+    return val_loss, predictions, lang_stats

@@ -116,6 +116,7 @@ SIGNATURES = {
     "bofi_reward_refs": (_I, [_P, _P, _I, _I, _P, _P, _I, C.c_double, _P, _P, _P, _P, _P, _P, _I, _P]),
     "bofi_reward_score": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, _I,
                                _P, _P, _P, _P]),
+    "bofi_rouge_score": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, C.c_double, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -38,9 +38,9 @@ class RewardScorer:
         """The scorer of one batch as a ``score_fn(seq)`` for XETrainer.rl_step."""
         return _Bound(self, data_gts, seq_per_img)
 
-    def _launch(self, refs, seq, cand_len, seq_per_img, want64, want_comps):
-        N, S = seq.shape
-        pk = pack_references(refs, N, S, seq_per_img, self.device, self.df)
+    def records(self, pk):
+        """The records of uploaded references ``pk`` (cider.upload) by bofi_reward_refs, enqueued on the current stream: ``(pk, tensors)`` for
+        ``_launch(records=...)`` -- a caller that scores many candidate sets against the same references builds them once."""
         R, stride, dev = pk.R, pk.stride, self.device
         rec_keys = torch.empty(R, stride, dtype=torch.int64, device=dev)
         rec_w = torch.empty(R, stride, dtype=torch.float64, device=dev)
@@ -48,17 +48,24 @@ class RewardScorer:
         rec_meta = torch.empty(R, ORDERS + 1, dtype=torch.float64, device=dev)
         rec_cnt = torch.empty(R, stride, dtype=torch.int32, device=dev)
         rec_len = torch.empty(R, dtype=torch.int32, device=dev)
+        hip.check(hip.lib().bofi_reward_refs(hip.ptr(pk.tok), hip.ptr(pk.lens), R, pk.width, hip.ptr(pk.df_keys), hip.ptr(pk.df_vals), pk.n_df, pk.L,
+                                             hip.ptr(rec_keys), hip.ptr(rec_w), hip.ptr(rec_off), hip.ptr(rec_meta), hip.ptr(rec_cnt), hip.ptr(rec_len),
+                                             stride, hip.stream_ptr()), "bofi_reward_refs")
+        return pk, (rec_keys, rec_w, rec_off, rec_meta, rec_cnt, rec_len)
+
+    def _launch(self, refs, seq, cand_len, seq_per_img, want64, want_comps, records=None):
+        """``records``: what ``records()`` returned for these references -- no packing and no refs kernel then (``refs`` is not read)."""
+        N, S = seq.shape
+        pk, (rec_keys, rec_w, rec_off, rec_meta, rec_cnt, rec_len) = records if records is not None else self.records(
+            pack_references(refs, N, S, seq_per_img, self.device, self.df))
+        stride, dev = pk.stride, self.device
         out = torch.empty(N, dtype=torch.float32, device=dev)
         out64 = torch.empty(N, dtype=torch.float64, device=dev) if want64 else None
         comps = torch.empty(N, COMPS, dtype=torch.int32, device=dev) if want_comps else None
-        lib, st = hip.lib(), hip.stream_ptr()
-        hip.check(lib.bofi_reward_refs(hip.ptr(pk.tok), hip.ptr(pk.lens), R, pk.width, hip.ptr(pk.df_keys), hip.ptr(pk.df_vals), pk.n_df, pk.L,
-                                       hip.ptr(rec_keys), hip.ptr(rec_w), hip.ptr(rec_off), hip.ptr(rec_meta), hip.ptr(rec_cnt), hip.ptr(rec_len),
-                                       stride, st), "bofi_reward_refs")
-        hip.check(lib.bofi_reward_score(hip.ptr(seq), hip.ptr(cand_len), N, S, seq_per_img, hip.ptr(pk.start), hip.ptr(pk.df_keys),
-                                        hip.ptr(pk.df_vals), pk.n_df, pk.L, self.sigma, self.cider_weight, self.bleu_weight, hip.ptr(rec_keys),
-                                        hip.ptr(rec_w), hip.ptr(rec_off), hip.ptr(rec_meta), hip.ptr(rec_cnt), hip.ptr(rec_len), stride,
-                                        hip.ptr(out), hip.ptr(out64), hip.ptr(comps), st), "bofi_reward_score")
+        hip.check(hip.lib().bofi_reward_score(hip.ptr(seq), hip.ptr(cand_len), N, S, seq_per_img, hip.ptr(pk.start), hip.ptr(pk.df_keys),
+                                              hip.ptr(pk.df_vals), pk.n_df, pk.L, self.sigma, self.cider_weight, self.bleu_weight, hip.ptr(rec_keys),
+                                              hip.ptr(rec_w), hip.ptr(rec_off), hip.ptr(rec_meta), hip.ptr(rec_cnt), hip.ptr(rec_len), stride,
+                                              hip.ptr(out), hip.ptr(out64), hip.ptr(comps), hip.stream_ptr()), "bofi_reward_score")
         return out, out64, comps
 
     def score(self, data_gts, seq, seq_per_img: int, out64: bool = False, comps: bool = False):

@@ -601,6 +601,18 @@ int bofi_reward_score(const int64_t* seq, const int* cand_len, int N, int S, int
                       const uint64_t* rec_keys, const double* rec_w, const int* rec_off, const double* rec_meta, const int* rec_cnt,
                       const int* rec_len, int stride, float* out, double* out64, int* comps, void* stream);
 
+/* ROUGE-L of the validation pass (the Rouge scorer of the pycocoevalcap package, beta = 1.2) on id token lists, in fp64.  For candidate j =
+ * row j of seq int64 [N, S] (S <= 64) and the references i of its image (ref_start as for bofi_cider_score; ref_tok int32 [n_refs, width],
+ * ref_len int32 [n_refs] as for bofi_cider_refs, width <= 64): lcs_i = the longest common subsequence of the two token lists,
+ * p = max_i lcs_i / |c|, r = max_i lcs_i / |r_i|, out64[j] = (1 + beta^2) p r / (r + beta^2 p) if p and r are non-zero, else 0; an empty
+ * candidate or reference gives its pair p = r = 0.  The candidate's token list: cand_len[j] ids, or (cand_len NULL) the ids up to and
+ * including the first 0 (eval_rule 0, array_to_str) or before the first id <= 0 (eval_rule 1, decode_sequence), else the whole row.
+ * lcs int32 [seq_per_img * n_refs] or NULL: lcs_i of every pair, candidate j's at ref_start[img] * seq_per_img + (j % seq_per_img) * (the
+ * image's references) + i.  best int32 [N, 2] or NULL: the reference (index within the image) that gives p and the one that gives r, the
+ * lowest index on ties.  All counts are integers; deterministic. */
+int bofi_rouge_score(const int64_t* seq, const int* cand_len, int N, int S, int seq_per_img, const int* ref_start, const int* ref_tok,
+                     const int* ref_len, int width, int eval_rule, double beta, double* out64, int* lcs, int* best, void* stream);
+
 /* Last HIP error string seen by this library on the calling thread (for exceptions in the host). */
 const char* bofi_last_error(void);
 

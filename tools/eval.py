@@ -6,8 +6,9 @@ path this repository implements: greedy NAIC bound+fill decoding of precomputed 
         [--input_att_npy feats.npy | --synthetic 64] [--batch_size 64] [--dtype bf16|f32] [--dump_json out.json]
 
 `--model` is a state_dict written by the reference (311 entries) or by this repository.  Data loading
-(lmdb/h5), language evaluation (coco-caption) and beam search are outside the scope of this build
-(SURVEY.md §2): features come from a .npy of shape [N, R, 2048] or are synthetic.
+(lmdb/h5) and beam search are outside the scope of this build: features come from a .npy of shape [N, R, 2048] or are
+synthetic.  ``--language_eval 1`` (with ``--input_label_npz``: the references) adds the language scores that need no Java -- BLEU-1..4,
+ROUGE-L, CIDEr on the device (boficap_amd.lang_eval) -- as a printed line and, in ``--dump_json``, under a top-level key.
 """
 import argparse
 import json
@@ -42,10 +43,14 @@ def main():
     ap.add_argument("--in_flight", type=int, default=3, help="launch streams (3 launch streams + the copy stream = the runtime's default of 4 hardware queues)")
     ap.add_argument("--fused_vocab", action="store_true", help="pipelined NAIC only: ids-only launches -- generator and vocabulary epilogue as one launch that writes no "
                     "logits, forks without the vocabulary-wide buffers (TransformerModel.decode_many(fused_vocab=True))")
+    ap.add_argument("--language_eval", type=int, default=0, choices=[0, 1], help="1: BLEU-1..4, ROUGE-L and CIDEr of the captions against the references of "
+                    "--input_label_npz; --dump_json then holds {'predictions': [...], 'lang_stats': {...}} instead of the list")
     args = ap.parse_args()
+    if args.language_eval and not args.input_label_npz:
+        ap.error("--language_eval 1 needs the references: --input_label_npz")
 
     import captioning.models as models
-    from boficap_amd import weights as W
+    from boficap_amd import eval_utils, weights as W
     from boficap_amd.config import FULL
 
     vocab = None
@@ -73,33 +78,19 @@ def main():
     store = None
     if args.input_label_npz:
         from boficap_amd.data import LabelStore
-        from boficap_amd.loss_wrapper import LanguageModelCriterion_UIC
         c = model.cfg
         src = args.input_label_npz if args.input_label_npz.endswith((".h5", ".hdf5")) else dict(np.load(args.input_label_npz))
         store = LabelStore(src, pad_idx=c.pad_idx, bos_idx=c.bos_idx, eos_idx=c.eos_idx, len_idx=c.len_idx)
-        crit, rng, loss_sum, loss_evals = LanguageModelCriterion_UIC(), np.random.default_rng(0), 0.0, 0
-    results, seconds = [], 0.0
+    results, seconds, rows, stats = [], 0.0, [], ([], [])
 
     def entry_of(i, k, seq, pn, pl, ent, ppl):
-        ids = [int(v) for v in seq[k].tolist() if v > 0]
-        entry = {"image_id": i + k, "seq": ids, "phrase_num": int(pn[k]), "phrase_length": [int(v) for v in pl[k].tolist() if v > 0],
-                 "entropy": float(ent[k]), "perplexity": float(ppl[k])}
-        if vocab:
-            entry["caption"] = " ".join(vocab.get(str(v), "UNK") for v in ids if v > 6)
-        return entry
+        if args.language_eval and k == 0:                        # (the batch's raw rows, for the language scores)
+            rows.append(seq.cpu()); stats[0].append(ent.cpu()); stats[1].append(ppl.cpu())
+        return eval_utils.entry_of(i, k, seq, pn, pl, ent, ppl, vocab)
 
     with torch.no_grad():
         if store is not None:                                    # the loss of eval_split (verbose_loss), eval_utils.py:440-453: a pass of its own
-            for i in range(0, len(feats), args.batch_size):
-                att = torch.from_numpy(np.ascontiguousarray(feats[i:i + args.batch_size])).cuda()
-                fc = torch.zeros(att.size(0), 0, device="cuda")
-                hb = store.batch(range(i, i + att.size(0)), args.seq_per_img, rng)
-                hb.pop("gts", None)
-                b = {k: torch.from_numpy(v).cuda() for k, v in hb.items()}
-                outs = model(fc, att.float(), b["labels"], None, b["phrase_num"], b["phrase_length"], b["phrase_syn"],
-                             b["extend_phrase_syn_seq"], b["extend_phrase_seq"], b["extend_phrase_seq_mask"])
-                loss_sum += float(crit(*outs, b["phrase_num"], b["phrase_length"], b["phrase_syn"], b["labels"])[0])
-                loss_evals += 1
+            loss_sum, loss_evals = eval_utils.validation_loss(model, feats, store, args.batch_size, args.seq_per_img)
         if args.pipeline and args.inference_mode == "NAIC":
             # the features as a loader of half-precision feature files hands them over: compute dtype, pinned host memory (staged once, outside the clock --
             # float32 features would cross PCIe at twice the bytes: ~190 k images/s at 55 GB/s)
@@ -135,9 +126,14 @@ def main():
     print(f"decoded {len(results)} images in {seconds:.4f} s ({len(results) / max(seconds, 1e-9):.1f} images/s; {how})")
     if store is not None:
         print(f"validation loss {loss_sum / max(1, loss_evals):.4f} over {loss_evals} batches (LanguageModelCriterion_UIC)")
+    lang_stats = None
+    if args.language_eval:
+        from boficap_amd.lang_eval import LanguageEval
+        lang_stats = LanguageEval([store.gts(i) for i in range(len(results))], "cuda").evaluate(torch.cat(rows), torch.cat(stats[0]), torch.cat(stats[1]))
+        print("language scores " + " ".join(f"{k} {v:.6f}" for k, v in lang_stats.items()))
     if args.dump_json:
         with open(args.dump_json, "w") as f:
-            json.dump(results, f)
+            json.dump({"predictions": results, "lang_stats": lang_stats} if args.language_eval else results, f)
 
 
 if __name__ == "__main__":

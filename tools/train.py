@@ -8,8 +8,7 @@
 
 One process per GPU (RANK / LOCAL_RANK / WORLD_SIZE from the environment) instead of ``nn.DataParallel``: every rank
 steps on its own shard of images and the gradients meet in one RCCL all-reduce over the flat gradient bucket
-(boficap_amd/trainer.py).  Data loading (lmdb / h5), language evaluation and the self-critical phase are outside this
-build: batches are synthetic captions in the loader's layout (boficap_amd/collate.py), or -- with
+(boficap_amd/trainer.py).  Data loading (lmdb / h5) is outside this build: batches are synthetic captions in the loader's layout (boficap_amd/collate.py), or -- with
 ``--input_label_h5`` -- real captions from the preprocessing's label file (boficap_amd/data.py; region features stay synthetic,
 the feature directories being outside this build).  ``--cfg`` reads the reference's yml files including their ``_BASE_``
 inheritance (captioning/utils/config.py:35-95).  ``--self_critical_after N`` switches to the self-critical step (loss_wrapper.py:181-230,
@@ -17,7 +16,9 @@ inheritance (captioning/utils/config.py:35-95).  ``--self_critical_after N`` swi
 on the device (boficap_amd.cider) with the document frequencies of ``--cached_tokens`` / the cfg's ``cached_tokens`` (data/<name>.p of
 scripts/prepro_ngrams.py, as the reference resolves it), plus BLEU-4 (boficap_amd.rewards) with the cfg's ``bleu_reward_weight`` > 0 (no
 df file needed when ``cider_reward_weight`` is 0); with no such file for a CIDEr-D term, by token overlap with the ground-truth captions.
-Checkpoints are the reference's files (captioning/utils/misc.py:87-102): ``model.pth`` (311-entry state_dict), ``optimizer.pth``
+Checkpoints are the reference's files (captioning/utils/misc.py:87-102; with ``--val_images_use N`` every ``save_checkpoint_every`` iterations follow a validation pass as the
+reference's loop runs it, :296-363 -- loss, SAIC and NAIC captions, with ``--language_eval 1`` BLEU / ROUGE-L / CIDEr on the device -- into
+``histories['val_result_history']`` and ``infos['best_val_score']``, and the best one is kept as ``model-best.pth``): ``model.pth`` (311-entry state_dict), ``optimizer.pth``
 (NoamOpt / torch Adam layout), ``infos_<id>.pkl``, ``histories_<id>.pkl``; ``--start_from`` resumes from either code base's directory.
 """
 import argparse
@@ -57,6 +58,11 @@ def main():
     ap.add_argument("--drop_worst_after", type=int, default=None, help="epoch from which a step keeps the best (1 - drop_worst_rate) captions (opts.py:165-168, "
                     "tools/train.py:186-189, 216-220; -1: never, the shipped configs)")
     ap.add_argument("--iters_per_epoch", type=int, default=1000, help="the synthetic stream has no epochs of its own: iterations that count as one")
+    ap.add_argument("--val_images_use", type=int, default=0, help="images of the validation pass at every save_checkpoint_every iterations (tools/train.py:296-363): the last "
+                    "N images of --input_label_h5, kept out of the training draws, or N synthetic images from fixed seeds; 0: no validation")
+    ap.add_argument("--language_eval", type=int, default=0, choices=[0, 1], help="1: BLEU-1..4, ROUGE-L and CIDEr of the validation captions on the device "
+                    "(boficap_amd.lang_eval); the best checkpoint is then chosen by CIDEr instead of the validation loss")
+    ap.add_argument("--save_history_ckpt", action="store_true", help="also keep every validated checkpoint as model-<iteration>.pth")
     args = ap.parse_args()
 
     import captioning.models as models
@@ -104,6 +110,50 @@ def main():
     if args.input_label_h5:
         from boficap_amd.data import LabelStore
         store = LabelStore(args.input_label_h5, pad_idx=cfg.pad_idx, bos_idx=cfg.bos_idx, eos_idx=cfg.eos_idx, len_idx=cfg.len_idx)
+    n_val, val = max(0, args.val_images_use), None
+    if store is not None and n_val >= store.num_images:
+        raise SystemExit(f"--val_images_use {n_val} leaves no training image of the label file's {store.num_images}")
+    if n_val and rank == 0:                                      # the validation set, fixed for the run; its references are packed on first use and kept
+        from boficap_amd import eval_utils
+        if store is not None:
+            val = {"labels": store, "ixs": list(range(store.num_images - n_val, store.num_images)),
+                   "feats": W.synthetic_att_feats(n_val, 36, cfg.att_feat_size, seed=args.seed + 977)}
+        else:
+            labels = eval_utils.SyntheticLabels(cfg, n_val, opt.seq_per_img, seed=args.seed + 977)
+            val = {"labels": labels, "ixs": None, "feats": labels.feats}
+        val["kwargs"] = {"batch_size": min(n_val, model.max_batch), "seq_per_img": opt.seq_per_img, "language_eval": args.language_eval,
+                         "image_ixs": val["ixs"], "vocab": opt.vocab, "lang_eval": None}
+
+    def validate_and_save(iteration):
+        """tools/train.py:296-363: the validation pass on rank 0 (the other ranks wait), its history entry, the checkpoint and the best one."""
+        if n_val and rank == 0:
+            from boficap_amd import eval_utils
+            kw = val["kwargs"]
+            sa_kw = dict(kw, inference_mode="SAIC", verbose_loss=0)
+            _, _, sa_stats = eval_utils.eval_split(model, val["feats"], val["labels"], sa_kw)
+            kw["lang_eval"] = sa_kw["lang_eval"]                # the references' records: built by the run's first pass, kept from then on
+            val_loss, pred, stats = eval_utils.eval_split(model, val["feats"], val["labels"], dict(kw, inference_mode="NAIC"))
+            line = " ".join(f"{k} {v:.4f}" for k, v in (stats or {}).items())
+            line += "".join(f" SA_{k} {v:.4f}" for k, v in (sa_stats or {}).items())
+            print(f"iter {iteration} validation loss {val_loss:.4f} {line}".rstrip(), flush=True)
+            histories["val_result_history"][iteration] = {"loss": val_loss, "lang_stats": stats, "predictions": pred}
+            current = stats["CIDEr"] if args.language_eval == 1 else -val_loss
+            best = infos.get("best_val_score")
+            best_flag = best is None or current > best
+            infos["best_val_score"] = current if best_flag else best
+            if args.checkpoint_path:
+                infos["opt"] = ck.resume_opt(opt)
+                ck.save_checkpoint(opt, model, infos, trainer, histories)
+                if args.save_history_ckpt:
+                    ck.save_checkpoint(opt, model, infos, trainer, append=str(iteration))
+                if best_flag:
+                    ck.save_checkpoint(opt, model, infos, trainer, append="best")
+        elif args.checkpoint_path and rank == 0:
+            infos["opt"] = ck.resume_opt(opt)
+            ck.save_checkpoint(opt, model, infos, trainer, histories)
+        if n_val and world > 1:
+            torch.distributed.barrier()
+
     if rank == 0:
         print(f"{type(model).__name__}: {trainer.bucket.numel} parameters in one bucket, {world} rank(s), "
               f"{opt.batch_size} images x {opt.seq_per_img} captions per rank and step, GEMM operands {args.dtype}", flush=True)
@@ -137,7 +187,7 @@ def main():
             host_batch = synthetic_training_batch(cfg, opt.batch_size, opt.seq_per_img, seed=seed)
         else:
             rng = np.random.default_rng(seed)
-            host_batch = store.batch(rng.integers(0, store.num_images, opt.batch_size), opt.seq_per_img, rng)
+            host_batch = store.batch(rng.integers(0, store.num_images - n_val, opt.batch_size), opt.seq_per_img, rng)
             gts = host_batch.pop("gts")
         ss_start = args.scheduled_sampling_start if args.scheduled_sampling_start is not None else getattr(opt, "scheduled_sampling_start", -1)
         epoch = it // max(1, args.iters_per_epoch)
@@ -168,6 +218,8 @@ def main():
                           f"{(time.time() - t0) / (it + 1 - first):.3f} s/it", flush=True)
                 histories["loss_history"][it + 1] = float(loss)
             infos["iter"] = it + 1
+            if n_val and args.save_checkpoint_every and (it + 1) % args.save_checkpoint_every == 0:
+                validate_and_save(it + 1)
             continue
         batch = {k: torch.from_numpy(v).to(dev) for k, v in host_batch.items()}
         batch["max_phrase_num"] = int(host_batch["phrase_num"].max())
@@ -198,9 +250,8 @@ def main():
             histories["lr_history"][it + 1] = trainer.rate()
             histories["ss_prob_history"][it + 1] = model.ss_prob
         infos["iter"] = it + 1                                   # tools/train.py:292-294
-        if args.checkpoint_path and args.save_checkpoint_every and (it + 1) % args.save_checkpoint_every == 0 and rank == 0:
-            infos["opt"] = ck.resume_opt(opt)
-            ck.save_checkpoint(opt, model, infos, trainer, histories)
+        if args.save_checkpoint_every and (it + 1) % args.save_checkpoint_every == 0 and (args.checkpoint_path or n_val):
+            validate_and_save(it + 1)
     if args.checkpoint_path and rank == 0:
         infos["opt"] = ck.resume_opt(opt)                     # plain values, every option of the reference's resume check present
         ck.save_checkpoint(opt, model, infos, trainer, histories)
