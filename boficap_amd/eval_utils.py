@@ -2,6 +2,7 @@
 loss, one greedy caption per image, and the language scores that need no Java (boficap_amd.lang_eval).
 
     val_loss, predictions, lang_stats = eval_split(model, feats, store_or_gts, eval_kwargs)
+    val_loss, predictions, lang_stats = eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=5)       # + eval_kwargs['preds_n']
 
 ``feats``: region features [N, R, F] (array or tensor on the host).  ``store_or_gts``: a label source with ``batch(image_ixs, seq_per_img, rng)``
 and ``gts(ix)`` (``data.LabelStore``, ``SyntheticLabels``) -- the loss is computed and the references come from it --, or the per-image
@@ -14,6 +15,11 @@ references alone (integer rows or id strings; no loss then), or None.  ``eval_kw
     image_ixs        the label source's image of every row of ``feats`` (default 0 .. N - 1)
     verbose_loss     0: no loss pass;  vocab  {str(id): word} for the entries' 'caption'
     batches_per_launch, in_flight, fused_vocab     ``decode_many``'s knobs
+    sample_n         N > 1 (or the ``sample_n`` argument): after the greedy pass, N captions per image are drawn through ``mode='sample'`` with
+                     ``sample_method='sample'`` (eval_split_n, eval_utils.py:670-700, ``sample_n_method='sample'``); their entries are stored under
+                     ``eval_kwargs['preds_n']``, and ``lang_stats`` gains the diversity statistics of boficap_amd.diversity ('Div-1', 'Div-2',
+                     'mBLEU_1'..'mBLEU_4', 'self_cider'; per image under ``eval_kwargs['diversity_per_image']``) on the document frequencies of
+    cached_tokens    a df pickle of scripts/prepro_ngrams.py: a path, or a name resolved as data/<name>.p (default 'coco-train-idxs')
 """
 from __future__ import annotations
 
@@ -75,13 +81,50 @@ class SyntheticLabels:
         return self.host["labels"][int(ix), :, 1:-1]
 
 
+def sample_n_predictions(model, feats, sample_n: int, mode: str = "NAIC", batch_size: int = 64, vocab=None):
+    """eval_split_n (eval_utils.py:670-700) for ``sample_n_method='sample'``: ``sample_n`` captions per image of ``feats`` drawn through
+    ``mode='sample'``.  Returns (entries {'image_id', 'seq'[, 'caption']} in row order, the sampled ids [N * sample_n, S] on the device); an
+    entry's 'seq' holds the ids before the first id <= 0 (decode_sequence)."""
+    n, host = int(sample_n), _torch_feats(feats)
+    step = batch_size if mode == "NAIC" else max(1, min(batch_size, model.max_batch // n))       # the SAIC sampler decodes images x n rows
+    rows = []
+    with torch.no_grad():
+        for i in range(0, len(host), step):
+            att = host[i:i + step].cuda()
+            if att.dtype != torch.float32 and att.dtype != model.compute_dtype:
+                att = att.float()
+            fc = torch.zeros(att.size(0), 0, device="cuda")
+            rows.append(model(fc, att, None, opt={"train_mode": mode, "sample_method": "sample", "sample_n": n}, mode="sample")[0])
+    seq = torch.cat(rows)
+    entries = []
+    for j, row in enumerate(seq.cpu().tolist()):
+        stop = next((q for q, v in enumerate(row) if v <= 0), len(row))
+        entry = {"image_id": j // n, "seq": [int(v) for v in row[:stop]]}
+        if vocab:
+            entry["caption"] = " ".join(vocab.get(str(v), "UNK") for v in entry["seq"] if v > 6)
+        entries.append(entry)
+    return entries, seq
+
+
+def diversity_stats(seq, sample_n: int, eval_kwargs):
+    """The diversity statistics of sampled ids ``seq`` [N * sample_n, S] on the df file of ``eval_kwargs['cached_tokens']``; the
+    ``DiversityEval`` is kept under ``eval_kwargs['diversity_eval']`` from one evaluation to the next.  Returns ({key: float}, per-image arrays)."""
+    from .diversity import KEYS, DiversityEval
+    ev = eval_kwargs.get("diversity_eval")
+    if ev is None:
+        ev = eval_kwargs["diversity_eval"] = DiversityEval(eval_kwargs.get("cached_tokens", "coco-train-idxs"), seq.device)
+    out = ev.evaluate(seq, int(sample_n))
+    return {k: out[k] for k in KEYS}, out["per_image"]
+
+
 def _torch_feats(feats):
     return feats if torch.is_tensor(feats) else torch.from_numpy(np.ascontiguousarray(feats))
 
 
-def eval_split(model, feats, store_or_gts, eval_kwargs):
+def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
     """(val_loss, predictions, lang_stats) of ``feats``' images: see the module's head.  The model is put in eval() and restored."""
     kw = eval_kwargs
+    sample_n = int(kw.get("sample_n", 1) if sample_n is None else sample_n)
     mode = kw.get("inference_mode", "NAIC")
     if mode not in ("NAIC", "SAIC"):
         raise NotImplementedError(f"inference mode {mode!r}: a UIC model decodes in 'NAIC' or 'SAIC' mode")
@@ -137,6 +180,10 @@ def eval_split(model, feats, store_or_gts, eval_kwargs):
                 from .lang_eval import LanguageEval
                 ev = kw["lang_eval"] = LanguageEval(gts, next(model.parameters()).device)
             lang_stats = ev.evaluate(torch.cat(seqs), torch.cat(ents), torch.cat(ppls))
+        if sample_n > 1:                                         # eval_split_n + the div_stats / self_cider of language_eval (eval_utils.py:105-120)
+            kw["preds_n"], sampled = sample_n_predictions(model, feats, sample_n, mode, batch_size, vocab)
+            div, kw["diversity_per_image"] = diversity_stats(sampled, sample_n, kw)
+            lang_stats = dict(lang_stats or {}, **div)
     finally:
         model.train(was_training)
     return val_loss, predictions, lang_stats

@@ -10,7 +10,8 @@ around the reference model).  RL branch (struc_flag True): its loss arithmetic i
 structure_loss_types); the caption scorer itself
 (``get_scores``, captioning/utils/rewards.py:86-131) is ``opt.bofi_score_fn(gts, seq) -> [N] floats`` or one installed with ``set_scorer`` if
 given, else the device scorer of ``device_scorer``: CIDEr-D of ``opt.cached_tokens`` (boficap_amd.cider), and with ``opt.bleu_reward_weight`` > 0
-the weighted sum with BLEU-4 (boficap_amd.rewards; the self-CIDEr term is not built).
+the weighted sum with BLEU-4 (boficap_amd.rewards).  With ``opt.self_cider_reward_weight`` > 0 and 'new_self_critical' the self-CIDEr diversity
+of every image's samples (boficap_amd.diversity, the df file of ``opt.cached_tokens``) is added to the advantage, whichever scorer gave the reward.
 
 RL branch, the estimator (round 6): the reference samples with the autograd tape running (and dropout active) and
 differentiates that same pass (loss_wrapper.py:193-209).  In train mode this class does the same by default, as ``XETrainer.rl_step`` does
@@ -153,16 +154,27 @@ class LanguageModelCriterion_UIC(torch.nn.Module):
 
 class StructureLosses(torch.nn.Module):
     """captioning/modules/losses.py:29-179: every ``structure_loss_type`` (configs/uic_sd_kd100_sd_nscl.yml uses 'new_self_critical'),
-    the entropy reward and reduction 'none' (xe.structure_loss).  Not built: the self-CIDEr reward term (:167-171, another external scorer)."""
+    the entropy reward, reduction 'none' (xe.structure_loss) and the self-CIDEr reward term of 'new_self_critical' (:167-171): weight x the
+    self-CIDEr diversity of the image's samples (``self_cider_term``), added to every sample's advantage after the baseline subtraction."""
 
     def __init__(self, opt):
         super().__init__()
         self.opt = opt
         self.loss_type = getattr(opt, "structure_loss_type", "seqnll")
 
+    def self_cider_term(self, input, seq, n):
+        """losses.py:167-171: ``self_cider_reward_weight`` x get_self_cider_scores as [B, 1] in ``input``'s dtype, on the device (no host
+        copy, no sync); None unless the weight is above 0 and the type is 'new_self_critical' (the other types ignore the weight).  An image
+        whose samples hold no n-gram of non-zero weight (e.g. every sample the id 0 alone, with (0) in every document of the df file) scores
+        NaN, as the reference's formula does, and so do the advantage and the batch's loss."""
+        w = float(getattr(self.opt, "self_cider_reward_weight", 0) or 0)
+        if not w > 0 or self.loss_type != "new_self_critical":
+            return None
+        from .diversity import self_cider_scorer
+        score = self_cider_scorer(self.opt, seq.device if seq.is_cuda else None).score(seq.detach().to(input.device), n)
+        return w * score.to(input.dtype).view(-1, 1)              # (the reference casts the scores first, then weighs them)
+
     def forward(self, input, seq, data_gts, reduction="mean"):
-        if getattr(self.opt, "self_cider_reward_weight", 0) > 0:
-            raise NotImplementedError("the self-CIDEr reward term is not built (0 in the shipped configs)")
         n = input.size(0) // len(data_gts)
         assert n == self.opt.train_sample_n, n                   # losses.py:45
         fn = getattr(self.opt, "bofi_score_fn", None) or _SCORER["fn"]
@@ -175,7 +187,8 @@ class StructureLosses(torch.nn.Module):
         else:
             scores = fn(data_gts, seq.detach().cpu())
         loss, reward = xe.structure_loss(self.loss_type, input, seq, scores, n, reduction=reduction,
-                                         entropy_reward_weight=float(getattr(self.opt, "entropy_reward_weight", 0) or 0))
+                                         entropy_reward_weight=float(getattr(self.opt, "entropy_reward_weight", 0) or 0),
+                                         extra_advantage=self.self_cider_term(input, seq, n))
         return {"loss": loss, "reward": reward}
 
 

@@ -1872,14 +1872,17 @@ def new_self_critical(logprobs, seq, scores, sample_n: int):
 STRUCTURE_LOSS_TYPES = ("seqnll", "risk", "max_margin", "multi_margin", "softmax_margin", "real_softmax_margin", "new_self_critical")
 
 
-def structure_loss(loss_type: str, logprobs, seq, scores, sample_n: int, reduction: str = "mean", entropy_reward_weight: float = 0.0):
+def structure_loss(loss_type: str, logprobs, seq, scores, sample_n: int, reduction: str = "mean", entropy_reward_weight: float = 0.0,
+                   extra_advantage=None):
     """StructureLosses.forward for every ``structure_loss_type`` of the reference (captioning/modules/losses.py:38-179): the sequence-level
     losses of Edunov et al. over the ``sample_n`` sampled captions of an image -- 'seqnll' (:72-79), 'risk' (:81-87), 'max_margin' (:96-106),
     'multi_margin' (:118-128), 'softmax_margin' (:136-144), 'real_softmax_margin' (:146-155), 'new_self_critical' (:157-176) -- with the
     entropy reward (:53-57) and reduction 'none' where the reference has it.  ``logprobs`` [N, S, V] (what the type takes: log-softmax or
     logits), ``scores`` [N] from the caption scorer.  The reference AS SHIPPED raises a NameError for every type but 'new_self_critical'
     (its losses.py never imports ``F``); the formulas are pinned by tests/golden/tiny_structure_losses, recorded from the reference's code
-    with that import supplied.  Index bookkeeping on [N, S] tensors; returns (loss, reward [B, n] = the raw scores)."""
+    with that import supplied.  ``extra_advantage`` [B, n] (or None): added to the 'new_self_critical' advantage after the baseline is
+    subtracted (the self-CIDEr reward term, :167-171); the other types do not read it, as in the reference.  Index bookkeeping on [N, S]
+    tensors; returns (loss, reward [B, n] = the raw scores)."""
     if loss_type not in STRUCTURE_LOSS_TYPES:
         raise ValueError(f"structure_loss_type {loss_type!r}: one of {STRUCTURE_LOSS_TYPES}")
     if reduction not in ("mean", "none") or (reduction == "none" and loss_type in ("risk", "max_margin", "multi_margin")):
@@ -1904,7 +1907,9 @@ def structure_loss(loss_type: str, logprobs, seq, scores, sample_n: int, reducti
     picked = logprobs.gather(2, seq.unsqueeze(2)).squeeze(2)
     if loss_type == "new_self_critical":
         adv = sc - (sc.sum(1, keepdim=True) - sc) / (sample_n - 1)
-        out = -picked * mask * adv.view(-1, 1)
+        if extra_advantage is not None:
+            adv = adv + torch.as_tensor(extra_advantage, dtype=adv.dtype, device=adv.device).expand_as(adv)
+        out = -picked * mask * adv.reshape(-1, 1)
         return (out.sum(1) / mask.sum(1) if reduction == "none" else out.sum() / mask.sum()), reward
     picked = picked * mask
     if loss_type == "risk":

@@ -613,6 +613,26 @@ int bofi_reward_score(const int64_t* seq, const int* cand_len, int N, int S, int
 int bofi_rouge_score(const int64_t* seq, const int* cand_len, int N, int S, int seq_per_img, const int* ref_start, const int* ref_tok,
                      const int* ref_len, int width, int eval_rule, double beta, double* out64, int* lcs, int* best, void* stream);
 
+/* Diversity of the n sampled captions of every image (n consecutive rows of seq int64 [images * n, S], 2 <= n <= 16, S <= 64), in fp64 on the
+ * records, keys and df table of the CIDEr-D pair above.  Token list of a row: eval_rule 0 = the ids up to and including the first 0
+ * (array_to_str), eval_rule 1 = the ids before the first id <= 0 (decode_sequence, possibly none), else the whole row.
+ *   mat double [images, n, n] or NULL: M[i][j] = 1/4 sum over the orders k of cos_k(i, j), cos_k = sum over the shared k-grams of w_i w_j /
+ *     (norm_k(i) norm_k(j)), 0 if either norm is 0 -- plain CIDEr between two samples, no clipping, no length penalty; exactly symmetric.
+ *   score double [images]: -log(sqrt(l_max) / sum sqrt(l)) / log n over the eigenvalues l of M clipped below at 0 (get_self_cider_scores,
+ *     captioning/utils/rewards.py:119-139), by a cyclic Jacobi iteration with a fixed rotation order and a fixed cap of sweeps; NaN where every
+ *     eigenvalue clips to 0, i.e. M = 0: all samples empty (eval_rule 1), or no sample with an n-gram of non-zero weight (e.g. rows of
+ *     the id 0 alone under eval_rule 0 when the df table gives the n-gram (0) a document frequency of ref_len); NaN too where a sample holds
+ *     an id above 65534 (or, eval_rule 0, below 0).
+ *   div int32 [images, 3]: distinct unigrams, distinct bigrams and tokens over the image's samples (Div-n = distinct n-grams / tokens).
+ *   comps int32 [images * n, 10] or NULL: (T, reflen, guess[4], correct[4]) of sample i as BLEU candidate against the image's other n - 1
+ *     samples, the layout and rules of bofi_reward_score (mBLEU).
+ * workspace: bofi_diversity_workspace(images, n, S) bytes (-1 for sizes the kernel refuses), 8-byte aligned, the records' scratch.
+ * Deterministic: fixed summation and rotation orders. */
+int64_t bofi_diversity_workspace(int images, int n, int S);
+int bofi_diversity_score(const int64_t* seq, int images, int n, int S, int eval_rule, const uint64_t* df_keys, const double* df_vals, int n_df,
+                         double log_ref_len, void* workspace, int64_t workspace_bytes, double* score, double* mat, int* div, int* comps,
+                         void* stream);
+
 /* Last HIP error string seen by this library on the calling thread (for exceptions in the host). */
 const char* bofi_last_error(void);
 

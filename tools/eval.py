@@ -9,6 +9,9 @@ path this repository implements: greedy NAIC bound+fill decoding of precomputed 
 (lmdb/h5) and beam search are outside the scope of this build: features come from a .npy of shape [N, R, 2048] or are
 synthetic.  ``--language_eval 1`` (with ``--input_label_npz``: the references) adds the language scores that need no Java -- BLEU-1..4,
 ROUGE-L, CIDEr on the device (boficap_amd.lang_eval) -- as a printed line and, in ``--dump_json``, under a top-level key.
+``--sample_n N`` (N > 1, with ``--cached_tokens``: the document frequencies) draws N captions per image after the greedy pass and adds their
+diversity statistics -- Div-1, Div-2, mBLEU-1..4, self-CIDEr on the device (boficap_amd.diversity) -- the same way, with the sampled captions under
+``preds_n``.
 """
 import argparse
 import json
@@ -45,6 +48,10 @@ def main():
                     "logits, forks without the vocabulary-wide buffers (TransformerModel.decode_many(fused_vocab=True))")
     ap.add_argument("--language_eval", type=int, default=0, choices=[0, 1], help="1: BLEU-1..4, ROUGE-L and CIDEr of the captions against the references of "
                     "--input_label_npz; --dump_json then holds {'predictions': [...], 'lang_stats': {...}} instead of the list")
+    ap.add_argument("--sample_n", type=int, default=1, help="N > 1: after the greedy pass draw N captions per image (sample_method 'sample') and report Div-1, Div-2, "
+                    "mBLEU-1..4 and self-CIDEr over them; --dump_json then holds {'predictions', 'preds_n', 'lang_stats'}")
+    ap.add_argument("--cached_tokens", default="coco-train-idxs", help="document-frequency pickle of the self-CIDEr score (scripts/prepro_ngrams.py): a path, or a "
+                    "name resolved as data/<name>.p")
     args = ap.parse_args()
     if args.language_eval and not args.input_label_npz:
         ap.error("--language_eval 1 needs the references: --input_label_npz")
@@ -131,9 +138,18 @@ def main():
         from boficap_amd.lang_eval import LanguageEval
         lang_stats = LanguageEval([store.gts(i) for i in range(len(results))], "cuda").evaluate(torch.cat(rows), torch.cat(stats[0]), torch.cat(stats[1]))
         print("language scores " + " ".join(f"{k} {v:.6f}" for k, v in lang_stats.items()))
+    preds_n = None
+    if args.sample_n > 1:
+        preds_n, sampled = eval_utils.sample_n_predictions(model, feats, args.sample_n, args.inference_mode, args.batch_size, vocab)
+        div, _ = eval_utils.diversity_stats(sampled, args.sample_n, {"cached_tokens": args.cached_tokens})
+        lang_stats = dict(lang_stats or {}, **div)
+        print("diversity scores " + " ".join(f"{k} {v:.6f}" for k, v in div.items()))
     if args.dump_json:
         with open(args.dump_json, "w") as f:
-            json.dump({"predictions": results, "lang_stats": lang_stats} if args.language_eval else results, f)
+            if preds_n is not None:
+                json.dump({"predictions": results, "preds_n": preds_n, "lang_stats": lang_stats}, f)
+            else:
+                json.dump({"predictions": results, "lang_stats": lang_stats} if args.language_eval else results, f)
 
 
 if __name__ == "__main__":

@@ -167,6 +167,11 @@ def main():
             opt.cached_tokens = args.cached_tokens
         df = resolve_df(getattr(opt, "cached_tokens", "coco-train-idxs"))
         cw, bw = float(getattr(opt, "cider_reward_weight", 1)), float(getattr(opt, "bleu_reward_weight", 0) or 0)
+        if float(getattr(opt, "self_cider_reward_weight", 0) or 0) > 0:
+            # the self-CIDEr term (boficap_amd.diversity) enters the advantage in LossWrapper's StructureLosses; XETrainer.rl_step's captured
+            # gradient pass has no input for it, and training on without the term would be a different objective
+            raise SystemExit("self_cider_reward_weight > 0: XETrainer.rl_step does not take the self-CIDEr reward term; "
+                             "boficap_amd.loss_wrapper.LossWrapper (StructureLosses) does, with the df file of cached_tokens")
         if bw > 0 and (df is not None or not cw > 0):          # get_scores' two terms in one scorer, its weights inside
             from boficap_amd.rewards import RewardScorer
             scorer = RewardScorer(df=df if cw > 0 else None, cider_weight=cw, bleu_weight=bw, device=dev)
