@@ -6,6 +6,7 @@
 // loop lives on the device and finished batches make the remaining bound kernels return at once.
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <string>
@@ -1148,15 +1149,63 @@ int bofi_engine_refresh_device(bofi_engine_t* e, int n, const char* const* names
     return BOFI_OK;
 }
 
-// Developer aid: copy a workspace buffer of the bounding iteration into user memory (device to device, on `stream`).
+// Developer aid: copy a workspace buffer of the bounding iteration, or a packed operand left by repack(), into user memory (device to device, on `stream`).
+// The packed operands carry their size: *cap is set to it (left at -1 for the workspace buffers, whose extent depends on the last call).
+static const void* debug_buffer(bofi_engine_t* e, const std::string& n, int64_t* cap) {
+    const bofi_config_t& c = e->cfg;
+    const int64_t d = c.d_model, hh = c.head_hidden, rows = (int64_t)e->L * 10, tsz = (int64_t)e->tsz;
+    *cap = -1;
+    const size_t at = n.find('@');
+    if (at != std::string::npos) {          // "<field>@<first prefix of the recipe>[#k]": k-th (from 0) declared Linear / Norm that starts with this prefix
+        const std::string field = n.substr(0, at);
+        std::string prefix = n.substr(at + 1);
+        int nth = 0;
+        const size_t hash = prefix.rfind('#');
+        if (hash != std::string::npos) {
+            if (hash + 1 >= prefix.size() || prefix.find_first_not_of("0123456789", hash + 1) != std::string::npos || prefix.size() - hash > 6) return nullptr;
+            nth = std::atoi(prefix.c_str() + hash + 1);
+            prefix.resize(hash);
+        }
+        if (field == "g" || field == "nb") {
+            for (const auto& r : e->norm_recipes)
+                if (r.prefix == prefix && nth-- == 0) { *cap = (int64_t)r.d * 4; return field == "g" ? r.out->g : r.out->b; }
+            return nullptr;
+        }
+        for (const auto& r : e->lin_recipes) {
+            if (r.prefixes.empty() || r.prefixes[0] != prefix || nth-- != 0) continue;
+            const Lin& l = *r.out;
+            const int64_t np = l.Npad;
+            if (field == "w") { *cap = np * l.K * tsz; return l.w; }
+            if (field == "b") { *cap = np * 4; return l.b; }
+            if (field == "cs") { *cap = np * 4; return l.cs; }
+            if (field == "wp") { *cap = np * l.K * 2; return l.wp; }
+            if (field == "wp16") { *cap = np * l.K * 2; return l.wp16; }
+            return nullptr;
+        }
+        return nullptr;
+    }
+    struct Tab { const char* name; const void* p; int64_t bytes; };
+    const Tab tabs[] = {
+        {"xt", e->d_xt, rows * d * 4}, {"x0", e->b_x0, d * 4}, {"x0_sa", e->b_x0_sa, d * 4}, {"x0b", e->b_x0b, d * 4},
+        {"kvtab", e->b_kvtab, rows * 2 * d * tsz}, {"q0", e->b_q0, d * tsz}, {"q0_sa", e->b_q0_sa, d * tsz},
+        {"votab", e->b_votab, rows * c.heads * d * tsz}, {"w1p", e->b_w1p, d * 2 * hh * tsz}, {"w1t", e->heads.w1t, d * 2 * hh * 4}, {"b1", e->heads.b1, 2 * hh * 4},
+        {"q0_32", e->b_q0_32, d * 4}, {"sctab", e->b_sctab, rows * c.heads * 4}, {"vtab", e->b_vtab, rows * d * 4}, {"wsat", e->b_wsat, 4},
+        {"len_w2", e->heads.len_w2, 20 * hh * 4}, {"len_b2", e->heads.len_b2, 20 * 4}, {"syn_w2", e->heads.syn_w2, 10 * hh * 4}, {"syn_b2", e->heads.syn_b2, 10 * 4},
+    };
+    for (const Tab& t : tabs)
+        if (n == t.name) { *cap = t.bytes; return t.p; }
+    return n == "by1" ? (const void*)e->y1.x : n == "byb" ? (const void*)e->y1.xb : n == "st_b" ? (const void*)e->y1.st :
+           n == "bq2" ? (const void*)e->bq2 : n == "bctx2" ? (const void*)e->bctx2 : n == "by2" ? (const void*)e->y2.x :
+           n == "bh" ? (const void*)e->bh : n == "by3" ? (const void*)e->by3 : n == "dbg_part" ? (const void*)e->dbg_part :
+           n == "counters" ? (const void*)e->st.counters : nullptr;      // ("counters": int32 [8] of the last decode: [5] = groups whose bounding loop ran as a PAIR of workgroups)
+}
+
 int bofi_engine_debug_copy(bofi_engine_t* e, const char* name, void* dst, int64_t bytes, void* stream) {
     if (!e || !name || !dst) return fail(BOFI_ERR_ARG, "null argument");
-    const std::string n = name;
-    const void* src = n == "by1" ? (const void*)e->y1.x : n == "byb" ? (const void*)e->y1.xb : n == "st_b" ? (const void*)e->y1.st :
-                      n == "bq2" ? (const void*)e->bq2 : n == "bctx2" ? (const void*)e->bctx2 : n == "by2" ? (const void*)e->y2.x :
-                      n == "bh" ? (const void*)e->bh : n == "by3" ? (const void*)e->by3 : n == "dbg_part" ? (const void*)e->dbg_part :
-                      n == "counters" ? (const void*)e->st.counters : nullptr;      // ("counters": int32 [8] of the last decode: [5] = groups whose bounding loop ran as a PAIR of workgroups)
-    if (!src) return fail(BOFI_ERR_ARG, "unknown buffer");
+    int64_t cap = -1;
+    const void* src = debug_buffer(e, name, &cap);
+    if (!src) return fail(BOFI_ERR_ARG, "unknown buffer");      // (also: a field this Linear does not have, a table this configuration does not build)
+    if (cap >= 0 && (bytes < 0 || bytes > cap)) return fail(BOFI_ERR_ARG, std::string(name) + " holds " + std::to_string(cap) + " bytes");
     ENG_HIP(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return BOFI_OK;
 }

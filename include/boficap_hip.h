@@ -537,8 +537,21 @@ int bofi_attn_out_ffn_block(const float* x, int ldx, const void* ctx, int ldc, c
                             const float* cs1, const void* w2p, const float* b2, float* y, int ldy, int M, int dff, const void* pj_wp, const float* pj_c,
                             const float* pj_cs, void* pj_y, int pj_ldy, int pj_N, void* stream);
 
-/* Developer aid: copy one of the bounding iteration's workspace buffers ("by1", "byb", "st_b", "bq2", "bctx2", "by2", "bh", "by3")
- * into user memory (device to device, on `stream`). */
+/* Developer aid: copy one of the engine's buffers into user memory (device to device, on `stream`).  `name` is
+ *   - a workspace buffer of the bounding iteration: "by1", "byb", "st_b", "bq2", "bctx2", "by2", "bh", "by3", "dbg_part", "counters" (the caller knows the extent);
+ *   - a packed operand, as the last bofi_engine_finalize / bofi_engine_refresh_device left it.  The engine knows these buffers' sizes: asking for more bytes than one
+ *     holds is BOFI_ERR_ARG, and so is a field or table that this engine does not have.
+ *       "<field>@<prefix>[#k]": field "w" (compute dtype [Npad][K]), "b" (float32 [Npad]: the bias, with a folded LayerNorm's offset), "cs" (float32 [Npad]: column sums,
+ *         Linears with a folded LayerNorm only), "wp" (bf16 fragment-major copy of w, bofi_pack_frag's layout; bf16 engine, where kept) or "wp16" (fp16 fragment-major copy
+ *         from the float32 parameters: the persistent bounding-loop kernel's operands) of the packed Linear whose FIRST stacked parameter prefix is <prefix>, e.g.
+ *         "w@model.encoder.layers.0.self_attn.linears.0" is the encoder's first q|k|v.  Rows N .. Npad are zero padding.  Where several packed Linears start with the same
+ *         prefix (the bound layer's self-attention K|V is packed plain for the setup-time tables and once more with sublayer.0.norm folded in), "#k" picks the k-th of them
+ *         in the order they were declared, from 0; no suffix is "#0".
+ *       "g@<prefix>" / "nb@<prefix>": gain and offset (float32 [d_model]) of the LayerNorm <prefix> (".a_2" / ".b_2").
+ *       the bound layer's tables, L = seq_length + 2: "xt" (float32 [L*10][d]), "x0", "x0_sa", "x0b" (float32 [d]), "kvtab" (compute dtype [L*10][2d]), "q0", "q0_sa"
+ *         (compute dtype [d]), "votab" (compute dtype [L*10][heads][d]), "w1t" (float32 [d][2*head_hidden]), "w1p" (compute dtype, w1t permuted), "b1" (float32
+ *         [2*head_hidden]), "len_w2" / "len_b2" / "syn_w2" / "syn_b2" (float32), and -- where the persistent bounding-loop kernel's operands exist -- "q0_32" (float32 [d]),
+ *         "sctab" (float32 [L*10][heads]), "vtab" (float32 [L*10][d]), "wsat" (int32 [1]: an fp16 weight copy was clamped). */
 int bofi_engine_debug_copy(bofi_engine_t* e, const char* name, void* dst, int64_t bytes, void* stream);
 
 /* Measurement aid: GEMM FLOPs (2 M N K per launch of bofi_linear* / the weight-gradient GEMMs, engine calls included) enqueued
