@@ -17,7 +17,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(ROOT, "build", "obj")
 LIB = os.path.join(HERE, "libboficap_hip.so")
-SOURCES = ["ln.hip", "gemm.hip", "gemm_glds.hip", "gemm_pers.hip", "attn.hip", "attn_bf16.hip", "naic.hip", "train_ops.hip", "gemm_tn.hip", "attn_bwd_mfma.hip", "repack.hip", "bound_ops.hip", "bound_loop.hip", "rowblock.hip", "engine.hip", "cider.hip", "rouge.hip", "diversity.hip"]
+SOURCES = ["ln.hip", "gemm.hip", "gemm_glds.hip", "gemm_pers.hip", "attn.hip", "attn_bf16.hip", "naic.hip", "train_ops.hip", "gemm_tn.hip", "attn_bwd_mfma.hip", "repack.hip", "bound_ops.hip", "bound_loop.hip", "rowblock.hip", "engine.hip", "cider.hip", "rouge.hip", "diversity.hip", "knobs.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fno-slp-vectorize -fno-vectorize: no v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32.  Measured on MI355X (round 2, dev/exp/dbg_step*.py): a wavefront
 # whose float32 FMA chains were packed by the SLP vectoriser (v_pk_fma_f32 with op_sel operands) computed wrong sums in lanes 48-63
@@ -26,7 +26,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # packed forms buy nothing here anyway: the VALU work of these kernels sits beside MFMA or memory latency.)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-fno-vectorize", "-Wall", "-Wno-unused-function",
          f"-I{os.path.join(ROOT, 'include')}", f"-I{CSRC}"]
-if os.environ.get("BOFI_EXPERIMENTS") == "1":       # developer build: the timing-only ablation switches of engine.hip (BOFI_EXP_SKIP / BOFI_EXP_ITERS); use with --force
+if os.environ.get("BOFI_EXPERIMENTS") == "1":       # developer build: the timing-only ablation switches of engine.hip (BOFI_EXP_SKIP / BOFI_EXP_ITERS) and the sweep-only tiles of gemm_glds.hip (BOFI_GEMM_TILE); use with --force
     FLAGS.append("-DBOFI_EXPERIMENTS")
 
 
@@ -52,7 +52,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
             subprocess.run(cmd, check=True)
         return o
 
-    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1)) as ex:
+    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1, 16)) as ex:      # (one hipcc per thread: at most 16 at once)
         objs = list(ex.map(compile_one, SOURCES))
     if force or not _newer(LIB, objs):
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, *objs]

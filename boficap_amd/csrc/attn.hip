@@ -205,7 +205,7 @@ int launch_attention(const AttnArgs& a, hipStream_t st) {
     if (a.dtype != BOFI_DT_F32 && a.dtype != BOFI_DT_BF16) return BOFI_ERR_ARG;
     if ((a.ldq * el) % 16 || (a.ldk * el) % 16 || (a.ldv * el) % 16) return BOFI_ERR_ARG;
     if (((uintptr_t)a.q % 16) || ((uintptr_t)a.k % 16) || ((uintptr_t)a.v % 16)) return BOFI_ERR_ARG;
-    if (!getenv("BOFI_ATTN_GENERIC")) {                 // bf16, <= 64 keys: the register-resident kernel
+    if (!knob_set(BOFI_ATTN_GENERIC)) {                 // bf16, <= 64 keys: the register-resident kernel
         const int rc = launch_attention_bf16(a, st);
         if (rc >= 0) return rc;
     }

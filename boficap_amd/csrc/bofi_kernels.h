@@ -146,6 +146,9 @@ struct RbAttnArgs {
     // [512][512] projection of the sublayer's OUTPUT (the decoder layer's cross-attention queries), computed from each block while it sits in LDS
     const rb_u32x4* pj_wp; const float* pj_c; const float* pj_cs; uint16_t* pj_y; int pj_ldy;
 };
+// shapes launch_rb_attn takes (beyond: -1), stated once for the launcher and for the engine's gates that predict it
+constexpr int RB_ATTN_MAX_LQ = 40, RB_ATTN_MAX_LK = 48;              // the fused sublayer kernel
+constexpr int RB_ATTN_PJ_MAX_LQ = 20, RB_ATTN_PJ_MAX_LK = 32;        // ... with the projection tail
 struct RbGemmArgs {
     const float* x; int ldx;                  // [M][512] float32 residual stream (the LayerNorm is folded into w / c / cs)
     const rb_u32x4* wp; const float* c; const float* cs;      // fragment-major [N][512]; folded bias, column sums [N]

@@ -32,7 +32,6 @@
 
 namespace bofi {
 
-extern int g_env_generation;                   // bumped by bofi_reload_env (gemm_glds.hip)
 
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
@@ -729,7 +728,7 @@ int launch_bound_loop(const BoundLoopArgs& a, hipStream_t s) {
         if (!scratch && hipGetSymbolAddress(reinterpret_cast<void**>(&scratch), HIP_SYMBOL(g_bl_sat_scratch)) != hipSuccess) return BOFI_ERR_HIP;
         v.sat = scratch;
     }
-    v.dbg = BOFI_ENV_INT("BOFI_BL_DBG", 0);
+    v.dbg = knob(BOFI_BL_DBG);
     const int groups = (a.B + BL_G - 1) / BL_G;
     // two workgroups per group (BOFI_BL_PAIR, re-read after bofi_reload_env: 0 = never, 1 (default) = launches of at most BOFI_BL_PAIR_MAX_B = 384 images, 2 = always): the
     // whole loop only (the stage API evaluates one iteration), hidden units in two halves of whole 512-unit segments (dff 1 024 or 2 048), and the caller's exchange
@@ -737,8 +736,8 @@ int launch_bound_loop(const BoundLoopArgs& a, hipStream_t s) {
     // exchange) at the price of twice the CUs and of the iteration's other stages run twice: +2.1 % on the 20-step region (4 launches of 320 images, where the four loops
     // coincide and most of the chip waits for them), -1.2 % at 640 and -2.5 % at 1 024 images per launch, where the loops hide under other launches' work
     // (profiles/r06_bound_loop_pair_ab.txt).  Results are bit-identical either way.
-    const int pair_knob = BOFI_ENV_INT("BOFI_BL_PAIR", 1);
-    v.pair = (a.update && a.xbuf && a.xctl && !((a.dff >> 9) & 1) && pair_knob != 0 && (pair_knob == 2 || a.B <= BOFI_ENV_INT("BOFI_BL_PAIR_MAX_B", 384))) ? 1 : 0;
+    const int pair_knob = knob(BOFI_BL_PAIR);
+    v.pair = (a.update && a.xbuf && a.xctl && !((a.dff >> 9) & 1) && pair_knob != 0 && (pair_knob == 2 || a.B <= knob(BOFI_BL_PAIR_MAX_B))) ? 1 : 0;
     if (v.pair && a.st.pair_ctl != a.xctl)                  // (the engine's launch_bound_init zeroes the control words with the slot state: no launch of its own)
         hipLaunchKernelGGL(bl_zero_words_kernel, dim3((groups * 4 + 255) / 256), dim3(256), 0, s, reinterpret_cast<int*>(a.xctl), groups * 4);
     const int grid = v.pair ? 2 * groups : groups;

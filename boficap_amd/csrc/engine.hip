@@ -328,10 +328,10 @@ struct bofi_engine {
         a.y = y; a.yparts = yparts; a.y_stride = y_stride; a.w = heads; a.st = st; a.sa = saic ? sa : bofi::SaicState{};
         a.ext_syn_in = ext_syn_in; a.last_in = last_in; a.q0 = b_q0; a.kvtab = b_kvtab; a.votab = b_votab; a.x0b = b_x0b;
         a.y1 = y1.x; a.y1t = y1.copy(); a.stats = y1.st;
-        const int tail_dbg = BOFI_ENV_INT("BOFI_TAIL_DBG", 0);     // developer ablations
+        const int tail_dbg = bofi::knob(BOFI_TAIL_DBG);     // developer ablations
         a.B = B; a.L = L; a.S = cfg.seq_length; a.d = cfg.d_model; a.hh = cfg.head_hidden; a.H = cfg.heads; a.flags = flags | (tail_dbg << 8); a.iter = iter;
         a.len_logp = len_logp; a.syn_logp = syn_logp;
-        const bool want_dbg = BOFI_ENV_INT("BOFI_DBG_PART", 0) != 0;
+        const bool want_dbg = bofi::knob(BOFI_DBG_PART) != 0;
         if (want_dbg && !dbg_part) ENG_OK(dalloc(&dbg_part, (size_t)cfg.max_batch * (16 * cfg.head_hidden + cfg.d_model)));
         a.dbg_part = dbg_part;
         return bofi::launch_bound_tail(a, cfg.dtype, s);
@@ -508,7 +508,7 @@ struct bofi_engine {
     // BOFI_BOUND_LOOP (re-read after bofi_reload_env): 0 = the five-launch iterations of rounds 2-4 always, 1 (default) = the persistent loop kernel unless the caller
     // said its decodes run alone (bofi_engine_set_decodes_in_flight(1): the five launches are the shorter chain there -- 0.65 against 0.95 ms per 320 images),
     // 2 = the loop kernel whatever the hint
-    static int bound_loop_knob() { return BOFI_ENV_INT("BOFI_BOUND_LOOP", 1); }
+    static int bound_loop_knob() { return bofi::knob(BOFI_BOUND_LOOP); }
     bool bound_loop_ok(int R) const {
         const int k = loop_mode >= 0 ? loop_mode : bound_loop_knob();
         return loop_ready && loop_config_ok() && R <= 128 && k != 0 && (k == 2 || in_flight != 1);
@@ -536,7 +536,7 @@ struct bofi_engine {
     // of bound_ops.hip.  Returns -1 when the configuration is not theirs (bound_chain then takes the general kernels), else a status;
     // *parts = number of slabs in by3.
     int bound_chain_lean(int B, int R, const int* att_len, const Rows& r, hipStream_t s, int* parts) {
-        const bool lean_on = BOFI_ENV_INT("BOFI_BOUND_LEAN", 1) != 0;
+        const bool lean_on = bofi::knob(BOFI_BOUND_LEAN) != 0;
         const int d = cfg.d_model;
         if (!(lean_on && cfg.dtype == BOFI_DT_BF16 && d == 512 && cfg.heads == 8 && R <= 64 && cfg.d_ff % 512 == 0 && cfg.d_ff / 512 <= 4)) return -1;
         {   bofi::BoundQAttnArgs a{};
@@ -589,12 +589,14 @@ struct bofi_engine {
     // (BOFI_RB_MIN_ROWS: 0 = always, a huge value = never; re-read after bofi_reload_env.  Kernel family and launch size are then
     // decoupled: under ONE family a row's result does not depend on what else is in the launch -- bit for bit)
     static int rb_min_rows() {
-        return BOFI_ENV_INT("BOFI_RB_MIN_ROWS", 4096);
+        return bofi::knob(BOFI_RB_MIN_ROWS);
     }
     // timing-only ablation switches (results INVALID): compiled in only by `BOFI_EXPERIMENTS=1 python -m boficap_amd.build --force`
 #ifdef BOFI_EXPERIMENTS
     static bool exp_skip(const char* what) {
-        static const char* v = [] { const char* e = getenv("BOFI_EXP_SKIP"); if (e) fprintf(stderr, "[boficap_hip] BOFI_EXP_SKIP=%s: kernels skipped, RESULTS INVALID\n", e); return e; }();
+        const char* v = bofi::knob_str(BOFI_EXP_SKIP);
+        static bool told = false;
+        if (v && !told) { told = true; fprintf(stderr, "[boficap_hip] BOFI_EXP_SKIP=%s: kernels skipped, RESULTS INVALID\n", v); }
         return v && strstr(v, what);
     }
 #else
@@ -604,14 +606,14 @@ struct bofi_engine {
     // launch from each block while it sits in LDS (pj_y bf16, pitch pj_ldy); attn_proj_ok says when the attention kernel takes it (BOFI_RB_ATTN_PROJ, re-read after
     // bofi_reload_env: 0 = never, 1 (default) = when launches overlap, 2 = always)
     bool attn_proj_ok(const bofi::AttnArgs& at, const Lin& o, const Lin& pj) const {
-        const int v = BOFI_ENV_INT("BOFI_RB_ATTN_PROJ", 1);
+        const int v = bofi::knob(BOFI_RB_ATTN_PROJ);
         const int M = at.B * at.Lq;
-        return v && (v == 2 || in_flight != 1) && BOFI_ENV_INT("BOFI_RB_ATTN", 1) != 0 && BOFI_ENV_INT("BOFI_RB_ATTN_W", 0) == 0 && rb_ok() && o.wp && fold_rb_ok(pj, M) &&
-               pj.Npad == 512 && !at.skip_if_ge && at.kdiv <= 1 && !at.q_start && !at.drop_thresh && !at.klen_sq && at.Lq <= 20 && at.Lk <= 32 && M >= rb_min_rows() &&
+        return v && (v == 2 || in_flight != 1) && bofi::knob(BOFI_RB_ATTN) != 0 && bofi::knob(BOFI_RB_ATTN_W) == 0 && rb_ok() && o.wp && fold_rb_ok(pj, M) &&
+               pj.Npad == 512 && !at.skip_if_ge && at.kdiv <= 1 && !at.q_start && !at.drop_thresh && !at.klen_sq && at.Lq <= bofi::RB_ATTN_PJ_MAX_LQ && at.Lk <= bofi::RB_ATTN_PJ_MAX_LK && M >= rb_min_rows() &&
                !exp_skip("attn") && !exp_skip("qkv");
     }
     int rb_attn(const bofi::AttnArgs& at, const Lin& o, const Stream& t, bool want_copy, hipStream_t s, const Lin* pj, void* pj_y, int pj_ldy) {
-        const bool on = BOFI_ENV_INT("BOFI_RB_ATTN", 1) != 0;
+        const bool on = bofi::knob(BOFI_RB_ATTN) != 0;
         if (exp_skip("attn")) return BOFI_OK;
         if (!on || !rb_ok() || !o.wp || at.skip_if_ge || at.kdiv > 1 || at.q_start || at.drop_thresh || at.B * at.Lq < rb_min_rows()) return -1;
         bofi::RbAttnArgs a{};
@@ -626,7 +628,7 @@ struct bofi_engine {
     // a LayerNorm-folded projection (K = d_model) of the residual stream x32 as a row-block kernel: it reads the float32 stream itself
     // (no compute-dtype copy, no row statistics from the producer).  -1: not its configuration.
     bool fold_rb_ok(const Lin& l, int M) const {
-        const bool on = BOFI_ENV_INT("BOFI_RB_GEMM", 1) != 0;
+        const bool on = bofi::knob(BOFI_RB_GEMM) != 0;
         return on && rb_ok() && l.wp && l.cs && l.K == 512 && M >= rb_min_rows();
     }
     int fold_linear_rb(const float* x32, const Lin& l, void* y, int y_f32, int ldy, int M, hipStream_t s) {
@@ -638,19 +640,19 @@ struct bofi_engine {
         return bofi::launch_rb_gemm(a, s);
     }
     // the generator as the row-block kernel over the padded weight (what enqueue_fill runs from BOFI_RB_MIN_ROWS rows on)
-    bool gen_rb_ok(int M) const { return BOFI_ENV_INT("BOFI_GEN_PAD", 1) != 0 && gen_padded() && fold_rb_ok(gen, M); }
+    bool gen_rb_ok(int M) const { return bofi::knob(BOFI_GEN_PAD) != 0 && gen_padded() && fold_rb_ok(gen, M); }
     bool ffn_sublayer_ok(const Lin& w1, const Lin& w2, int M) const {
-        const bool on = BOFI_ENV_INT("BOFI_RB_FFN", 1) != 0;
+        const bool on = bofi::knob(BOFI_RB_FFN) != 0;
         return on && rb_ok() && w1.wp && w2.wp && w1.cs && cfg.d_ff % 512 == 0 && cfg.d_ff <= 2560 && M >= rb_min_rows();
     }
     // pj (optional): the LayerNorm-folded projection that reads this sublayer's output next (the next layer's q|k|v, the stacked cross K|V), computed by
     // the SAME launch from each closed block while it sits in LDS (pj_y, pitch pj_ldy); ffn_proj_ok says when the feed-forward kernel takes it
     // (BOFI_RB_FFN_PROJ, re-read after bofi_reload_env: 0 = never, 1 (default) = when launches overlap, 2 = always)
     bool ffn_proj_ok(const Lin& w1, const Lin& w2, const Lin& pj, int M) const {
-        const int v = BOFI_ENV_INT("BOFI_RB_FFN_PROJ", 1);
+        const int v = bofi::knob(BOFI_RB_FFN_PROJ);
         // (a decode running alone keeps the separate launches of 64-row blocks: measured 0.515 against 0.523 ms per batch with the narrow projections fused,
         // 0.536 with all of them)
-        const int maxn = BOFI_ENV_INT("BOFI_RB_FFN_PROJ_MAXN", 0);          // developer knob: projections wider than this stay launches of their own (0: no limit)
+        const int maxn = bofi::knob(BOFI_RB_FFN_PROJ_MAXN);          // developer knob: projections wider than this stay launches of their own (0: no limit)
         return v && (v == 2 || in_flight != 1) && ffn_sublayer_ok(w1, w2, M) && fold_rb_ok(pj, M) && pj.Npad >= 512 && (!maxn || pj.Npad <= maxn) && !exp_skip("ffn") &&
                !exp_skip("qkv") && !exp_skip("kv");
     }
@@ -667,11 +669,11 @@ struct bofi_engine {
     // alternative there is the attention core + a tiled GEMM for W_o + the residual stream's round trip (profiles/r06_regions_sweep.txt).
     // which: 1 = the encoder's self-attention, 2 = the filling pass's cross-attention (developer knob BOFI_RB_ATTN_SPLIT_WHICH, a mask of these; default both).
     bool attn_split_ok(const bofi::AttnArgs& at, const Lin& o, const Lin& w1, const Lin& w2, int which) const {
-        if (!(BOFI_ENV_INT("BOFI_RB_ATTN_SPLIT_WHICH", 3) & which)) return false;
-        const int v = BOFI_ENV_INT("BOFI_RB_ATTN_SPLIT", 1);
+        if (!(bofi::knob(BOFI_RB_ATTN_SPLIT_WHICH) & which)) return false;
+        const int v = bofi::knob(BOFI_RB_ATTN_SPLIT);
         const int M = at.B * at.Lq;
-        const bool beyond = (at.Lq > 40 || at.Lk > 48) && M >= rb_min_rows();
-        return v && (v == 2 || beyond || (in_flight != 1 && at.B >= BOFI_ENV_INT("BOFI_RB_ATTN_SPLIT_MIN_B", 512))) && BOFI_ENV_INT("BOFI_RB_ATTN", 1) != 0 && rb_ok() && o.wp &&
+        const bool beyond = (at.Lq > bofi::RB_ATTN_MAX_LQ || at.Lk > bofi::RB_ATTN_MAX_LK) && M >= rb_min_rows();
+        return v && (v == 2 || beyond || (in_flight != 1 && at.B >= bofi::knob(BOFI_RB_ATTN_SPLIT_MIN_B))) && bofi::knob(BOFI_RB_ATTN) != 0 && rb_ok() && o.wp &&
                ffn_sublayer_ok(w1, w2, M) && !at.skip_if_ge && at.kdiv <= 1 &&
                !at.q_start && !at.drop_thresh && at.Lq <= 128 && at.Lk <= 128 && !exp_skip("attn") && !exp_skip("ffn");
     }
@@ -837,7 +839,9 @@ int bofi_engine::enqueue_decode(const void* feats, int feats_dtype, const int* a
     } else {
         ENG_OK(bound_tail(nullptr, 1, nullptr, nullptr, B, BOUND_ATTN, nullptr, nullptr, s));
 #ifdef BOFI_EXPERIMENTS
-        static const int exp_iters = [] { const char* v = getenv("BOFI_EXP_ITERS"); if (v) fprintf(stderr, "[boficap_hip] BOFI_EXP_ITERS=%s: bounding loop truncated, RESULTS INVALID\n", v); return v ? atoi(v) : 0; }();
+        const int exp_iters = bofi::knob(BOFI_EXP_ITERS);
+        static bool told = false;
+        if (bofi::knob_set(BOFI_EXP_ITERS) && !told) { told = true; fprintf(stderr, "[boficap_hip] BOFI_EXP_ITERS=%d: bounding loop truncated, RESULTS INVALID\n", exp_iters); }
 #else
         constexpr int exp_iters = 0;                 // (timing experiment, experiments build only)
 #endif
@@ -864,14 +868,14 @@ int bofi_engine::enqueue_fill(const int* att_len, int B, int R, int flags, int64
     if (exp_skip("filling")) return BOFI_OK;           // (experiments build: the whole filling pass incl. the vocabulary epilogue)
     const int rounds = 1 + ((flags >> BOFI_FLAG_REFINE_SHIFT) & 15);
     float* lg = seq_logprob ? seq_logprob : logits;
-    const int gen_pad = BOFI_ENV_INT("BOFI_GEN_PAD", 1);      // developer knob: 0 = in place, one-tile kernel
+    const int gen_pad = bofi::knob(BOFI_GEN_PAD);      // developer knob: 0 = in place, one-tile kernel
     const bool gen_rb = gen_rb_ok(M);
     // BOFI_FLAG_IDS_ONLY where the row-block generator would run: generator + epilogue as ONE launch that keeps the distribution on the CU (rb_vocab_kernel)
     const bool fused = (flags & BOFI_FLAG_IDS_ONLY) && gen_rb;
     if (no_logits && !fused) return fail(BOFI_ERR_STATE, "this fork has no vocabulary-wide buffers: BOFI_FLAG_IDS_ONLY decodes that take the fused generator only");
     for (int round = 0; round < rounds; ++round) {
     // (round 0 under the row-block family: layer 0's q|k|v rows come out of the (label, position) table with the embedding launch -- BOFI_FILL_QKV_TAB=0: the projection)
-    const bool qkv_tab = round == 0 && fill_tab_ready && !dec.empty() && fold_rb_ok(dec[0].qkv, M) && BOFI_ENV_INT("BOFI_FILL_QKV_TAB", 1) != 0 && !exp_skip("qkv");
+    const bool qkv_tab = round == 0 && fill_tab_ready && !dec.empty() && fold_rb_ok(dec[0].qkv, M) && bofi::knob(BOFI_FILL_QKV_TAB) != 0 && !exp_skip("qkv");
     ENG_OK(bofi::launch_embed_fill(lut_tok, lut_syn, pe, st.ext_syn, round ? seq : nullptr, B, S, L, d, cfg.bos_idx, x_fill.x, x_fill.copy(), dt,
                                    x_fill.st, s, qkv_tab ? f_qkv0 : nullptr, qkv_tab ? qkv : nullptr, 3 * d));
     bool proj_made = qkv_tab;                            // this layer's q|k|v came out of the previous layer's feed-forward launch (layer 0: out of the table)
@@ -920,7 +924,7 @@ int bofi_engine::enqueue_fill(const int* att_len, int B, int R, int flags, int64
         ENG_OK(folded(x_fill, gen, lg, BOFI_DT_F32, cfg.vocab, M, Rows{}, s));
     }
     // (a round that another one follows: its ids are all the next round reads -- the log-probs it would write are overwritten: not stored)
-    const int ids_only_on = BOFI_ENV_INT("BOFI_REFINE_IDS_ONLY", 1);      // developer knob: 0 = every round stores its log-probs
+    const int ids_only_on = bofi::knob(BOFI_REFINE_IDS_ONLY);      // developer knob: 0 = every round stores its log-probs
     const int lsm = (flags & BOFI_FLAG_RAW_LOGITS) ? 0 : ((flags & BOFI_FLAG_IDS_ONLY) || (ids_only_on && round + 1 < rounds && lsrc) ? 2 : 1);
     ENG_OK(bofi::launch_vocab_finalize(lg, M, cfg.vocab, S, lsm, st.last, -1, cfg.pad_idx, seq, s, nullptr, nullptr, nullptr, nullptr,
                                        lsrc, gen.Npad, lsm ? row_plogp_out : nullptr, lsm ? row_chosen_out : nullptr));
@@ -1075,9 +1079,10 @@ int bofi_engine_create(const bofi_config_t* c, bofi_engine_t** out) {
     auto* e = new bofi_engine();
     e->cfg = *c;
     e->n_len = c->n_len;
-    { const char* v = getenv("BOFI_BOUND_DENSE"); e->bound_dense = c->n_len > 1 || (v && atoi(v) != 0); }
-    { const char* v = getenv("BOFI_SAIC_CACHE"); e->saic_cache = !v || atoi(v) != 0; }     // 0: every row through the decoder in every iteration
-    { const char* v = getenv("BOFI_SAIC_LEAN"); e->saic_lean = !v || atoi(v) != 0; }       // 0: the row-list iterations on the general GEMM / attention kernels
+    // the per-engine knobs: from the live environment, now (no reload needed), kept for the engine's life
+    e->bound_dense = c->n_len > 1 || bofi::knob_live(BOFI_BOUND_DENSE).i != 0;
+    { const bofi::KnobValue v = bofi::knob_live(BOFI_SAIC_CACHE); e->saic_cache = !v.set || v.i != 0; }     // 0: every row through the decoder in every iteration
+    { const bofi::KnobValue v = bofi::knob_live(BOFI_SAIC_LEAN); e->saic_lean = !v.set || v.i != 0; }       // 0: the row-list iterations on the general GEMM / attention kernels
     e->L = c->seq_length + 2;
     e->tsz = c->dtype == BOFI_DT_F32 ? 4 : 2;
     *out = e;

@@ -23,8 +23,6 @@
 
 namespace bofi {
 
-int g_env_generation = 0;      // bumped by bofi_reload_env(): cached developer knobs are read again
-
 // counted wait that leaves `younger` slabs (LPS LDS-DMA instructions each) in flight, younger in [0, MAXY] (wave-uniform)
 template <int MAXY, int LPS> __device__ __forceinline__ void wait_slabs(int younger) {
     if constexpr (MAXY <= 0) {
@@ -348,51 +346,85 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_glds_kernel(Gemm2Params p) 
     }
 }
 
-template <typename T, int BM, int BN, int NS, int WM = 2, int WN = 2, int FEAT = FEAT_ALL>
+template <typename T, int BM, int BN, int NS, int WM, int WN, int FEAT>
 static void launch_one(const Gemm2Params& p, hipStream_t st) {
     hipLaunchKernelGGL((gemm_glds_kernel<T, BM, BN, NS, WM, WN, FEAT>), dim3(((p.N + BN - 1) / BN) * ((p.M + BM - 1) / BM), p.splitk), dim3(64 * WM * WN), 0, st, p);
 }
 
-// the three tile shapes the heuristic picks, specialised for the feature sets the decode and training paths actually use
+// The tile table: (BM, BN, NS, waves = WM x WN) -> instantiation, one row per tile, with the (dtype, feature set) pairs the build holds of it.
+// FEAT_ALL is the generic kernel: it serves every feature set that has no specialisation of the tile.
+//
+// What the default build holds is exactly what launch_glds_t's heuristic can return without BOFI_GEMM_TILE (whatever the other knobs say):
+//   M <= 64           -> 64x32x4 (4 waves); bf16 with K / splitk <= 512 and BOFI_GEMM_DEEP: 64x32x9 (4), or 64x16x9 (2) for consumers without row statistics
+//   M > 64, t >= thr  -> 128x64x2 (8)
+//   M > 64, else      -> 64x64x2 (8); bf16 with K >= 1024, splitk == 1, feat in {0, 1, 2, 6, 18, 82} and BOFI_GEMM_HEUR2: 64x64x4 (8)
+// and the dispatch below sends a feature set of GLDS_FEATS to its specialisation where the tile has one, every other to FEAT_ALL.  Hence:
+//   128x64x2, 64x64x2, 64x32x4: float32 and bf16, each feature set of GLDS_FEATS (their callers are not enumerable here: the C entry takes any) + FEAT_ALL;
+//   64x64x4: bf16 only; of its six feature sets 0, 1, 2, 18, 82 are specialised and 6 goes to FEAT_ALL;
+//   64x32x9, 64x16x9: bf16 only, the feature sets of GLDS_FEATS; any other feature set is BOFI_ERR_ARG (there has never been a generic 9-deep kernel).
+// The experiments build (BOFI_EXPERIMENTS) adds the tiles only BOFI_GEMM_TILE reaches: the sweeps of dev/mb_tiles*.py.
+#ifdef BOFI_EXPERIMENTS
+constexpr bool GLDS_SWEEP = true;
+#else
+constexpr bool GLDS_SWEEP = false;
+#endif
+//  X(BM, BN, NS, WM, WN, held)   held: a condition on bf16 / spec (a feature set of its own, not FEAT_ALL) / FEAT
+#define GLDS_TILES(X)                                                                                                         \
+    X(128, 64, 2, 4, 2, true)                                                                                                 \
+    X(64, 64, 2, 4, 2, true)                                                                                                  \
+    X(64, 32, 4, 2, 2, true)                                                                                                  \
+    X(64, 64, 4, 4, 2, (bf16 && (FEAT < 3 || FEAT == 18 || FEAT == 82 || !spec)) || (GLDS_SWEEP && !spec))                    \
+    X(64, 32, 9, 2, 2, bf16 && spec)         /* M <= 64, K <= 512 per slice: all 8 slabs of the K extent in flight (108 KB of LDS) */ \
+    X(64, 16, 9, 2, 1, bf16 && spec)         /* (90 KB) */                                                                    \
+    /* sweep only: deeper rings / larger tiles for the encoder and fill GEMMs (one workgroup per CU) */                       \
+    X(64, 64, 3, 4, 2, GLDS_SWEEP && ((bf16 && FEAT < 3) || !spec))                                                           \
+    X(64, 64, 6, 4, 2, GLDS_SWEEP && bf16 && FEAT < 3)                                                                        \
+    X(64, 64, 9, 4, 2, GLDS_SWEEP && bf16 && FEAT < 3)                                                                        \
+    X(128, 64, 3, 4, 2, GLDS_SWEEP && ((bf16 && FEAT < 3) || !spec))                                                          \
+    X(128, 64, 4, 4, 2, GLDS_SWEEP && bf16 && FEAT < 3)                                                                       \
+    X(128, 64, 6, 4, 2, GLDS_SWEEP && bf16 && FEAT < 3)                                                                       \
+    X(128, 128, 3, 4, 2, GLDS_SWEEP && ((bf16 && FEAT < 3) || !spec))                                                         \
+    X(128, 128, 4, 4, 2, GLDS_SWEEP && bf16 && FEAT < 3)                                                                      \
+    X(64, 128, 4, 2, 4, GLDS_SWEEP && bf16 && FEAT < 3)                                                                       \
+    X(64, 128, 6, 2, 4, GLDS_SWEEP && bf16 && FEAT < 3)                                                                       \
+    X(256, 128, 3, 4, 2, GLDS_SWEEP && bf16 && FEAT < 3)                                                                      \
+    /* sweep only: generic kernel */                                                                                          \
+    X(128, 128, 2, 4, 4, GLDS_SWEEP && !spec)                                                                                 \
+    X(128, 128, 2, 4, 2, GLDS_SWEEP && !spec)                                                                                 \
+    X(256, 128, 2, 4, 2, GLDS_SWEEP && !spec)                                                                                 \
+    X(128, 256, 2, 2, 4, GLDS_SWEEP && !spec)                                                                                 \
+    X(128, 128, 2, 2, 2, GLDS_SWEEP && !spec)                                                                                 \
+    X(128, 128, 3, 2, 2, GLDS_SWEEP && !spec)                                                                                 \
+    X(128, 128, 4, 2, 2, GLDS_SWEEP && !spec)                                                                                 \
+    X(128, 64, 2, 2, 2, GLDS_SWEEP && !spec)                                                                                  \
+    X(128, 64, 3, 2, 2, GLDS_SWEEP && !spec)                                                                                  \
+    X(64, 64, 2, 2, 2, GLDS_SWEEP && !spec)                                                                                   \
+    X(64, 64, 3, 2, 2, GLDS_SWEEP && !spec)                                                                                   \
+    X(64, 64, 4, 2, 2, GLDS_SWEEP && !spec)                                                                                   \
+    X(64, 32, 2, 2, 2, GLDS_SWEEP && !spec)
+// the feature sets with specialisations: plain (bias / ReLU / residual), consumer of a folded LayerNorm, producer of a residual stream; the same three
+// inside the bound loop (16 ..); training: dropout (+ compute-dtype copy), dX through relu; the SAIC decoder pass over a row list (+ halt word)
+#define GLDS_FEATS(X) X(0) X(1) X(2) X(16) X(17) X(18) X(8) X(10) X(32) X(81) X(82)
+
+// launches tile (bm, bn, ns, nw waves) as FEAT's instantiation if the build holds one
 template <typename T, int FEAT>
-static bool launch_specialised(const Gemm2Params& p, int bm, int bn, int ns, int nw, hipStream_t st) {
-    if (bm == 128 && bn == 64 && ns == 2 && nw == 8) { launch_one<T, 128, 64, 2, 4, 2, FEAT>(p, st); return true; }
-    if (bm == 64 && bn == 64 && ns == 2 && nw == 8) { launch_one<T, 64, 64, 2, 4, 2, FEAT>(p, st); return true; }
-    if (bm == 64 && bn == 32 && ns == 4 && nw == 4) { launch_one<T, 64, 32, 4, 2, 2, FEAT>(p, st); return true; }
-    if constexpr (sizeof(T) == 2 && (FEAT == 18 || FEAT == 82)) {     // the K >= 1024 rule inside the bounding / semi-autoregressive loops
-        if (nw == 8 && bm == 64 && bn == 64 && ns == 4) { launch_one<T, 64, 64, 4, 4, 2, FEAT>(p, st); return true; }
-    }
-    if constexpr (sizeof(T) == 2 && FEAT < 3) {      // deeper rings / larger tiles for the encoder and fill GEMMs (one workgroup per CU)
-        if (nw == 8) {
-            if (bm == 64 && bn == 64 && ns == 4) { launch_one<T, 64, 64, 4, 4, 2, FEAT>(p, st); return true; }
-            if (bm == 64 && bn == 64 && ns == 6) { launch_one<T, 64, 64, 6, 4, 2, FEAT>(p, st); return true; }
-            if (bm == 64 && bn == 64 && ns == 9) { launch_one<T, 64, 64, 9, 4, 2, FEAT>(p, st); return true; }
-            if (bm == 128 && bn == 64 && ns == 3) { launch_one<T, 128, 64, 3, 4, 2, FEAT>(p, st); return true; }
-            if (bm == 64 && bn == 64 && ns == 3) { launch_one<T, 64, 64, 3, 4, 2, FEAT>(p, st); return true; }
-            if (bm == 128 && bn == 64 && ns == 4) { launch_one<T, 128, 64, 4, 4, 2, FEAT>(p, st); return true; }
-            if (bm == 128 && bn == 64 && ns == 6) { launch_one<T, 128, 64, 6, 4, 2, FEAT>(p, st); return true; }
-            if (bm == 128 && bn == 128 && ns == 3) { launch_one<T, 128, 128, 3, 4, 2, FEAT>(p, st); return true; }
-            if (bm == 128 && bn == 128 && ns == 4) { launch_one<T, 128, 128, 4, 4, 2, FEAT>(p, st); return true; }
-            if (bm == 64 && bn == 128 && ns == 4) { launch_one<T, 64, 128, 4, 2, 4, FEAT>(p, st); return true; }
-            if (bm == 64 && bn == 128 && ns == 6) { launch_one<T, 64, 128, 6, 2, 4, FEAT>(p, st); return true; }
-            if (bm == 256 && bn == 128 && ns == 3) { launch_one<T, 256, 128, 3, 4, 2, FEAT>(p, st); return true; }
-        }
-    }
-    if constexpr (sizeof(T) == 2) {      // M <= 64, K <= 512 per slice: all 8 slabs of the K extent in flight at once (108 / 90 KB of LDS)
-        if (bm == 64 && bn == 32 && ns == 9 && nw == 4) { launch_one<T, 64, 32, 9, 2, 2, FEAT>(p, st); return true; }
-        if (bm == 64 && bn == 16 && ns == 9 && nw == 2) { launch_one<T, 64, 16, 9, 2, 1, FEAT>(p, st); return true; }
-    }
+static bool launch_tile(const Gemm2Params& p, int bm, int bn, int ns, int nw, hipStream_t st) {
+    [[maybe_unused]] constexpr bool bf16 = sizeof(T) == 2, spec = FEAT != FEAT_ALL;
+#define GLDS_TILE_CASE(BM, BN, NS, WM, WN, HELD)                                                                               \
+    if constexpr (HELD) { if (bm == BM && bn == BN && ns == NS && nw == WM * WN) { launch_one<T, BM, BN, NS, WM, WN, FEAT>(p, st); return true; } }
+    GLDS_TILES(GLDS_TILE_CASE)
+#undef GLDS_TILE_CASE
     return false;
 }
 
 template <typename T>
 static int launch_glds_t(const Gemm2Params& p, hipStream_t st) {
-    // developer override: BOFI_GEMM_TILE=<BM>x<BN>x<NS>
+    // developer override: BOFI_GEMM_TILE=<BM>x<BN>x<NS>[x<waves>] (waves: 4 unless given)
     int bm = 0, bn = 0, ns = 0;
     int nw = 4;
     const int feat = (p.ln_stats ? 1 : 0) | ((p.stats_out || p.y2) ? 2 : 0) | (p.row_len ? 4 : 0) | (p.drop_thresh ? 8 : 0) |
                      ((p.skip_if_ge || p.dbg) ? 16 : 0) | (p.mask_scale != 0.f ? 32 : 0) | (p.row_idx ? 64 : 0);
-    if (const char* t = getenv("BOFI_GEMM_TILE")) { if (p.M > 64) sscanf(t, "%dx%dx%dx%d", &bm, &bn, &ns, &nw); }
+    if (const char* t = knob_str(BOFI_GEMM_TILE)) { if (p.M > 64) sscanf(t, "%dx%dx%dx%d", &bm, &bn, &ns, &nw); }
     if constexpr (sizeof(T) == 2) {
         // GEMMs of >= 90 tiles of 256 x 128 (N % 128 == 0): persistent workgroups with loader wavefronts (gemm_pers.hip; same bits).
         // Alone such a launch is about as fast as this kernel (1.0-1.2x at >= 700 tiles, 0.8-0.95x below); with several decodes in
@@ -400,15 +432,8 @@ static int launch_glds_t(const Gemm2Params& p, hipStream_t st) {
         // default bench (tools/exp/ab_bench2.sh, thresholds 1000 / 500 / 250 / 150 / 90: +3 / +8 / +9 / +14 / +17 %).
         // BOFI_GEMM_PERS=0 turns it off, BOFI_GEMM_PERS_MIN=<tiles> moves the threshold (developer knobs)
         if (!bm && (feat & ~16) <= 3 && !p.skip_if_ge) {       // (feature bit 4 alone = developer ablations)
-            static int env_seen = -1, pers_on = 1;            // the two knobs are read once, and again after bofi_reload_env() (tests flip them)
-            static long pers_min = 90;
-            if (env_seen != g_env_generation) {
-                const char* e = getenv("BOFI_GEMM_PERS");
-                const char* m = getenv("BOFI_GEMM_PERS_MIN");
-                pers_on = !e || atoi(e); pers_min = m ? atol(m) : 90; env_seen = g_env_generation;
-            }
             const long t256 = (long)((p.M + 255) / 256) * (p.N / 128);
-            if (pers_on && t256 >= pers_min) {
+            if (knob(BOFI_GEMM_PERS) && t256 >= knob(BOFI_GEMM_PERS_MIN)) {
                 const int r = launch_gemm_pers(p, feat & 3, st);
                 if (r != -1) return r;
             }
@@ -418,7 +443,7 @@ static int launch_glds_t(const Gemm2Params& p, hipStream_t st) {
         // measured on MI355X (tools/microbench_ops.py, round 1): occupancy beats ring depth at K = 512;
         // 2 stages keep 3-5 workgroups per CU so that one's prologue/epilogue hides under another's loop
         const long t = (long)((p.M + 127) / 128) * ((p.N + 63) / 64);
-        const int heur2 = BOFI_ENV_INT("BOFI_GEMM_HEUR2", 1);
+        const int heur2 = knob(BOFI_GEMM_HEUR2);
         // 128-row tiles from 200 tiles on (round 2: the fill pass's qkv and w_1 at M = 1280 gain 15-25 % with four decodes in flight)
         const long thr = heur2 ? 200 : 400;
         if (p.M <= 64) {
@@ -426,7 +451,7 @@ static int launch_glds_t(const Gemm2Params& p, hipStream_t st) {
             // the bounding loop's GEMMs (64 rows, K = 512 per slice) are latency chains: one L2 round trip per slab with a 4-deep
             // ring.  With the whole K extent (<= 8 slabs) issued up front the chain is one round trip; consumers that emit no row
             // statistics take 16-column tiles (twice the workgroups, half the weight bytes per workgroup)
-            const int deep = BOFI_ENV_INT("BOFI_GEMM_DEEP", 1);
+            const int deep = knob(BOFI_GEMM_DEEP);
             if (deep && sizeof(T) == 2 && p.K / p.splitk <= 8 * 64) {
                 ns = 9;
                 if (!(p.stats_out || p.y2) && p.vec_ok && p.N % 16 == 0) { bn = 16; nw = 2; }
@@ -439,48 +464,14 @@ static int launch_glds_t(const Gemm2Params& p, hipStream_t st) {
         // four in flight at M = 1280; 18.3 -> 15.2 us alone at M = 2304)
         if (heur2 && sizeof(T) == 2 && bm == 64 && bn == 64 && p.M > 64 && p.splitk == 1 && p.K >= 1024 && (feat < 3 || feat == 6 || feat == 18 || feat == 82)) ns = 4;
     }
-    {
-        bool done = false;
-        switch (feat) {
-            case 0: done = launch_specialised<T, 0>(p, bm, bn, ns, nw, st); break;          // plain: bias / ReLU / residual
-            case 1: done = launch_specialised<T, 1>(p, bm, bn, ns, nw, st); break;          // consumer of a folded LayerNorm
-            case 2: done = launch_specialised<T, 2>(p, bm, bn, ns, nw, st); break;          // producer of a residual stream
-            case 16: done = launch_specialised<T, 16>(p, bm, bn, ns, nw, st); break;        // the same three inside the bound loop
-            case 17: done = launch_specialised<T, 17>(p, bm, bn, ns, nw, st); break;
-            case 18: done = launch_specialised<T, 18>(p, bm, bn, ns, nw, st); break;
-            case 8: done = launch_specialised<T, 8>(p, bm, bn, ns, nw, st); break;          // training: dropout (+ compute-dtype copy)
-            case 10: done = launch_specialised<T, 10>(p, bm, bn, ns, nw, st); break;
-            case 32: done = launch_specialised<T, 32>(p, bm, bn, ns, nw, st); break;        // training: dX through relu (+ dropout)
-            case 81: done = launch_specialised<T, 81>(p, bm, bn, ns, nw, st); break;        // SAIC decoder pass over a row list (+ halt word)
-            case 82: done = launch_specialised<T, 82>(p, bm, bn, ns, nw, st); break;
-            default: break;
-        }
-        if (done) { BOFI_CHECK_LAUNCH(); return BOFI_OK; }
+    bool done = false;
+    switch (feat) {
+#define GLDS_FEAT_CASE(F) case F: done = launch_tile<T, F>(p, bm, bn, ns, nw, st); break;
+        GLDS_FEATS(GLDS_FEAT_CASE)
+#undef GLDS_FEAT_CASE
+        default: break;
     }
-    const int key = bm * 10000 + bn * 10 + ns + (nw == 8 ? 100000000 : nw == 16 ? 200000000 : 0);
-    switch (key) {
-        case 100640642: launch_one<T, 64, 64, 2, 4, 2>(p, st); break;
-        case 100640643: launch_one<T, 64, 64, 3, 4, 2>(p, st); break;
-        case 100640644: launch_one<T, 64, 64, 4, 4, 2>(p, st); break;
-        case 101280643: launch_one<T, 128, 64, 3, 4, 2>(p, st); break;
-        case 201281282: launch_one<T, 128, 128, 2, 4, 4>(p, st); break;    // 16 waves
-        case 101281282: launch_one<T, 128, 128, 2, 4, 2>(p, st); break;     // 8 waves
-        case 101281283: launch_one<T, 128, 128, 3, 4, 2>(p, st); break;
-        case 102561282: launch_one<T, 256, 128, 2, 4, 2>(p, st); break;
-        case 101282562: launch_one<T, 128, 256, 2, 2, 4>(p, st); break;
-        case 101280642: launch_one<T, 128, 64, 2, 4, 2>(p, st); break;
-        case 1281282: launch_one<T, 128, 128, 2>(p, st); break;
-        case 1281283: launch_one<T, 128, 128, 3>(p, st); break;
-        case 1281284: launch_one<T, 128, 128, 4>(p, st); break;
-        case 1280642: launch_one<T, 128, 64, 2>(p, st); break;
-        case 1280643: launch_one<T, 128, 64, 3>(p, st); break;
-        case 640642: launch_one<T, 64, 64, 2>(p, st); break;
-        case 640643: launch_one<T, 64, 64, 3>(p, st); break;
-        case 640644: launch_one<T, 64, 64, 4>(p, st); break;
-        case 640322: launch_one<T, 64, 32, 2>(p, st); break;
-        case 640324: launch_one<T, 64, 32, 4>(p, st); break;
-        default: return BOFI_ERR_ARG;
-    }
+    if (!done && !launch_tile<T, FEAT_ALL>(p, bm, bn, ns, nw, st)) return BOFI_ERR_ARG;      // a tile this build does not hold
     BOFI_CHECK_LAUNCH();
     return BOFI_OK;
 }
@@ -508,9 +499,9 @@ int launch_linear_glds(const LinearArgs& a, hipStream_t st) {
     if (p.mask_scale != 0.f && (!a.residual || a.splitk > 1 || a.stats_out || a.ln_stats)) return BOFI_ERR_ARG;
     if (p.splitk > 1 && (a.y_dtype != BOFI_DT_F32 || a.relu || a.ln_stats || a.stats_out || a.y2 || a.row_len || (a.K / p.splitk) % bk || a.K % p.splitk))
         return BOFI_ERR_ARG;
-    { const char* dv = getenv("BOFI_GEMM_DBG"); p.dbg = dv ? atoi(dv) : 0; }
+    p.dbg = knob(BOFI_GEMM_DBG);
     {   // bytes an XCD layout makes the eight L2s fetch: rb * W + (8 / rb) * A
-        const int forced = BOFI_ENV_INT("BOFI_GEMM_BANDS", 0);
+        const int forced = knob(BOFI_GEMM_BANDS);
         const double wb = (double)a.N * a.K, ab = (double)a.M * a.K;
         int best = 8; double cost = 8 * wb + ab;
         for (int rb : {4, 2, 1}) { const double c = rb * wb + (8 / rb) * ab; if (c < 0.9 * cost) { best = rb; cost = c; } }

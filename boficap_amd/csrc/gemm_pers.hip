@@ -345,27 +345,27 @@ __global__ __launch_bounds__(64 * (PCONS + PLOAD)) void gemm_pers_kernel(Gemm2Pa
 
 int launch_gemm_pers(const Gemm2Params& p_in, int feat, hipStream_t st) {
     Gemm2Params p = p_in;
-    if (p.dbg & 64) { const char* b = getenv("BOFI_GEMM_DBG_BUF"); p.skip_if_ge = b ? reinterpret_cast<const int*>(strtoull(b, nullptr, 0)) : nullptr; if (!p.skip_if_ge) p.dbg &= ~64; }
+    if (p.dbg & 64) { const char* b = knob_str(BOFI_GEMM_DBG_BUF); p.skip_if_ge = b ? reinterpret_cast<const int*>(strtoull(b, nullptr, 0)) : nullptr; if (!p.skip_if_ge) p.dbg &= ~64; }
     if (feat > 3 || p.splitk != 1 || !p.vec_ok || p.N % PBN || p.K % PBK || p.K < 3 * PBK || p.row_len || p.row_idx || p.drop_thresh || p.mask_scale != 0.f ||
         (p.skip_if_ge && !(p.dbg & 64)))
         return -1;
     if (p.ln_stats) { const int g = p.ln_groups > 0 ? p.ln_groups : p.K >> 5; if (g != 16) return -1; }      // (other group counts: gemm_glds.hip)
     // 128-row tiles where 256-row tiles would leave half of the chip idle (at most 128 of them: the fill pass's N = 512 GEMMs are 92)
-    const int bm128_max = BOFI_ENV_INT("BOFI_GEMM_PERS_BM128", 128);      // developer knob: 0 = 256-row tiles only
+    const int bm128_max = knob(BOFI_GEMM_PERS_BM128);      // developer knob: 0 = 256-row tiles only
     const int t256 = (p.N / PBN) * ((p.M + 255) / 256);
     const int bm = t256 <= bm128_max ? 128 : 256;
     const int ntiles = (p.N / PBN) * ((p.M + bm - 1) / bm);
-    const int cus = BOFI_ENV_INT("BOFI_GEMM_PERS_GRID", 256);
+    const int cus = knob(BOFI_GEMM_PERS_GRID);
     // every workgroup walks `rounds` tiles: the grid is the smallest multiple of 8 (tile v stays on XCD v % 8) that covers the tiles in
     // as many rounds as all CUs would need -- 540 tiles run on 184 CUs in 3 rounds, not on 256 in 3, and the rest stay free for the
     // other decodes in flight
-    const int min_rounds = BOFI_ENV_INT("BOFI_GEMM_PERS_ROUNDS", 1);      // developer knob: tiles per workgroup at least
+    const int min_rounds = knob(BOFI_GEMM_PERS_ROUNDS);      // developer knob: tiles per workgroup at least
     int rounds = (ntiles + cus - 1) / cus;
     if (rounds < min_rounds) rounds = min_rounds;
     int grid = ntiles;
     if (ntiles > cus || rounds > 1) { grid = (((ntiles + rounds - 1) / rounds + 7) / 8) * 8; if (grid > cus) grid = cus; if (grid > ntiles) grid = ntiles; }
     const dim3 g(grid), b(64 * (PCONS + PLOAD));
-    const int fast_ok = BOFI_ENV_INT("BOFI_GEMM_PERS_FAST", 1);      // developer knob: 0 = staged epilogue everywhere
+    const int fast_ok = knob(BOFI_GEMM_PERS_FAST);      // developer knob: 0 = staged epilogue everywhere
     const bool fast = fast_ok && !(feat & 2) && !p.residual && !p.y_is_f32 && p.ldy % 8 == 0 && (uintptr_t)p.y % 16 == 0;
 #define PERS_LAUNCH(F, R, Q)                                                                       \
     { if (bm == 128) hipLaunchKernelGGL((gemm_pers_kernel<F, R, Q, 128>), g, b, 0, st, p);          \

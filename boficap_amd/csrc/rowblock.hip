@@ -32,8 +32,6 @@
 
 namespace bofi {
 
-extern int g_env_generation;                   // bumped by bofi_reload_env (gemm_glds.hip)
-
 // developer aid (BOFI_RB_DBG & 16): s_memtime stamps of workgroup 0, [wave][slot], read back by bofi_rb_stamps
 __device__ unsigned long long g_rb_stamps[16 * 16];
 #define RB_STAMP(dbg, wave, lane, slot) do { if (((dbg) & 16) && blockIdx.x == 0 && (lane) == 0) g_rb_stamps[(wave) * 16 + (slot)] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -929,16 +927,10 @@ int launch_rb_ffn(const RbFfnArgs& a, hipStream_t st) {
     // knobs (read again after bofi_reload_env): BOFI_RB_FFN_V = 5 (default): 80-row blocks -- +3 % on the decode with launches in flight; 2: one
     // 64-row block per workgroup (round 3's kernel) -- 6-12 us faster per launch when ONE decode runs alone (62 against 68 us at 11 520 rows);
     // BOFI_RB_FFN_BPW = row blocks a workgroup of the 80-row kernel walks (default 1; grid = blocks / that)
-    static int env_seen = -1, version = 5, bpw = 1, v5_rows = 0, forced = 0, one_on = 1;
-    if (env_seen != g_env_generation) {
-        const char* e = getenv("BOFI_RB_FFN_V"); version = e ? atoi(e) : 5; forced = e != nullptr;
-        e = getenv("BOFI_RB_FFN_BPW"); bpw = e ? max(1, atoi(e)) : 1;
-        e = getenv("BOFI_RB_FFN_ONE"); one_on = e ? atoi(e) : 1;           // 0: the block-walking build of the kernel also at one block per workgroup
-        e = getenv("BOFI_RB_FFN_V5_ROWS"); v5_rows = e ? atoi(e) : 0;      // rows from which the 80-row kernel runs (below: the 64-row kernel)
-        env_seen = g_env_generation;
-    }
+    const int version = knob(BOFI_RB_FFN_V), bpw = max(1, knob(BOFI_RB_FFN_BPW)), one_on = knob(BOFI_RB_FFN_ONE), v5_rows = knob(BOFI_RB_FFN_V5_ROWS);
+    const bool forced = knob_set(BOFI_RB_FFN_V);
     RbFfnArgs b = a;
-    { const char* e = getenv("BOFI_RB_DBG"); b.dbg = e ? atoi(e) : 0; }
+    b.dbg = knob(BOFI_RB_DBG);
     if (a.pj_wp && (!a.pj_c || !a.pj_cs || !a.pj_y || a.pj_N < 512 || a.pj_N % 64 || a.pj_ldy % 8 || a.yb || a.stats_out)) return BOFI_ERR_ARG;
     if (a.head_wop) {                                         // with the attention sublayer's W_o + residual in front (and, optionally, the projection tail behind): one block per workgroup
         if (!a.head_ctx || !a.head_bo || a.head_ldc % 8 || a.yb || a.stats_out) return BOFI_ERR_ARG;
@@ -1317,19 +1309,18 @@ static int launch_rb_attn_t(const RbAttnArgs& a, hipStream_t st) {
 int launch_rb_attn(const RbAttnArgs& a, hipStream_t st) {
     if (!a.q || !a.k || !a.v || !a.wop || !a.bo || !a.x || !a.y || a.B < 1 || a.Lq < 1 || a.Lk < 1 || a.ldq % 8 || a.ldk % 8 || a.ldv % 8 || a.ldx % 4 || a.ldy % 4)
         return BOFI_ERR_ARG;
-    if (a.Lq > 40 || a.Lk > 48) return -1;
+    if (a.Lq > RB_ATTN_MAX_LQ || a.Lk > RB_ATTN_MAX_LK) return -1;
     // BOFI_RB_ATTN_W (developer knob, read again after bofi_reload_env) = 16: one 16-wavefront workgroup per CU (round 3), 8: 8-wavefront workgroups of
     // half the images, two per CU; default (0): 8 for query blocks of <= 20 rows (the filling pass: 25.9 -> 20.3 / 31.9 -> 24.7 us per launch at 320
     // images), 16 for the encoder's 36 (28.1 against 29.6 us; with four launches in flight the 8-wavefront form there costs 1-2 %)
-    static int env_seen = -1, wenv = 0;
-    if (env_seen != g_env_generation) { const char* e = getenv("BOFI_RB_ATTN_W"); wenv = e ? atoi(e) : 0; env_seen = g_env_generation; }
+    const int wenv = knob(BOFI_RB_ATTN_W);
     // (round 5: with launches in flight what counts is the weight bytes a launch pulls through L2, not its latency: 16 wavefronts -- four images per W_o stream -- for
     // the filling pass too, +1.3 % on the headline, profiles/r05_weight_bytes_ab.txt; a launch that runs alone keeps the 8-wavefront form)
     const int w = wenv ? wenv : (a.Lq <= 20 && a.alone ? 8 : 16);
     int rc;
     if (a.pj_wp) {                                              // with the projection tail: the 16-wavefront form of the filling pass's self-attention only
         if (!a.pj_c || !a.pj_cs || !a.pj_y || a.pj_ldy % 4 || a.yb || a.stats_out) return BOFI_ERR_ARG;
-        if (a.Lq > 20 || a.Lk > 32) return -1;
+        if (a.Lq > RB_ATTN_PJ_MAX_LQ || a.Lk > RB_ATTN_PJ_MAX_LK) return -1;
         rc = launch_rb_attn_t<2, 2, 2, 16, true>(a, st);
         if (rc == BOFI_OK) g_gemm_flops += 2 * 2.0 * a.B * a.Lq * 512.0 * 512.0;
         return rc;
@@ -1431,14 +1422,9 @@ int launch_rb_gemm(const RbGemmArgs& a, hipStream_t st) {
     if (a.M < 1 || a.N < 64 || a.N % 64 || !a.x || !a.wp || !a.c || !a.cs || !a.y || a.ldx % 4 || a.ldy % 8) return BOFI_ERR_ARG;
     // developer knob (read again after bofi_reload_env): BOFI_RB_GEMM_MT = 4: 64-row blocks everywhere; 6 (default): 96-row blocks for bf16
     // outputs from BOFI_RB_GEMM_MT8_ROWS rows on (below that the 64-row blocks' larger number of workgroups wins; round 4's 128-row form, <false, 8>, spilled 46 registers, never won and left in round 6)
-    static int env_seen = -1, mt = 6, mt8_rows = 4096, mt_min_n = 0, gen6 = -1;
-    if (env_seen != g_env_generation) {
-        const char* e = getenv("BOFI_RB_GEMM_MT"); mt = e ? atoi(e) : 6;
-        e = getenv("BOFI_RB_GEMM_MT8_ROWS"); mt8_rows = e ? atoi(e) : 4096;
-        e = getenv("BOFI_RB_GEMM_MT_MIN_N"); mt_min_n = e ? atoi(e) : 0;   // output columns from which the larger blocks run
-        e = getenv("BOFI_RB_GEN_MT6"); gen6 = e ? atoi(e) : -1;            // float32 outputs (the generator) on 96-row blocks too: 1 always, 0 never, default: with launches in flight (a third fewer weight bytes: +0.7 %)
-        env_seen = g_env_generation;
-    }
+    // BOFI_RB_GEN_MT6: float32 outputs (the generator) on 96-row blocks too: 1 always, 0 never, unset: with launches in flight (a third fewer weight bytes: +0.7 %)
+    const int mt = knob(BOFI_RB_GEMM_MT), mt8_rows = knob(BOFI_RB_GEMM_MT8_ROWS), mt_min_n = knob(BOFI_RB_GEMM_MT_MIN_N);
+    const int gen6 = knob(BOFI_RB_GEN_MT6);
     int rc;
     if (a.y_f32) rc = (mt == 6 && (gen6 > 0 || (gen6 < 0 && !a.alone)) && a.M >= mt8_rows) ? launch_rb_gemm_t<true, 6>(a, st) : launch_rb_gemm_t<true, 4>(a, st);
     else if (mt == 6 && a.M >= mt8_rows && a.N >= mt_min_n && !(a.alone && a.N < 2048)) rc = launch_rb_gemm_t<false, 6>(a, st);      // (alone: 96-row blocks only where they win alone)
@@ -1750,12 +1736,7 @@ int launch_rb_vocab(const RbVocabArgs& a, hipStream_t st) {
     // bytes per row, but as compiled the running states push that form 34 registers into scratch; default 4: 64-row blocks, no spill -- `alone` does not choose
     // between them until the two are timed); BOFI_VOCAB_SPLIT = 1 / 2 / 4 workgroups per row block (default 0: fill the chip when the row blocks alone do not,
     // as launch_rb_gemm_t)
-    static int env_seen = -1, mt = 4, split_env = 0;
-    if (env_seen != g_env_generation) {
-        const char* e = getenv("BOFI_VOCAB_MT"); mt = e ? atoi(e) : 4;
-        e = getenv("BOFI_VOCAB_SPLIT"); split_env = e ? atoi(e) : 0;
-        env_seen = g_env_generation;
-    }
+    const int mt = knob(BOFI_VOCAB_MT), split_env = knob(BOFI_VOCAB_SPLIT);
     const bool six = mt == 6;
     const int blocks = (a.M + (six ? 96 : 64) - 1) / (six ? 96 : 64), octets = (a.N / 64 + 7) / 8;
     int split = 1;
@@ -1803,7 +1784,7 @@ extern "C" int bofi_attn_block(const void* q, int ldq, const void* k, int ldk, c
     a.q = (const bofi::bf16_t*)q; a.ldq = ldq; a.k = (const bofi::bf16_t*)k; a.ldk = ldk; a.v = (const bofi::bf16_t*)v; a.ldv = ldv;
     a.B = B; a.Lq = Lq; a.Lk = Lk; a.klen = klen; a.klen_sb = klen_sb; a.klen_sq = klen_sq; a.klen_bias = klen_bias; a.klen_shared_last = klen_shared_last;
     a.wop = (const bofi::u32x4*)wop; a.bo = bo; a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy; a.yb = (bofi::bf16_t*)yb; a.stats_out = stats_out;
-    { const char* e = getenv("BOFI_RB_DBG"); a.dbg = e ? atoi(e) : 0; }
+    a.dbg = bofi::knob(BOFI_RB_DBG);
     a.alone = 1;                                               // (the direct entry: a launch of its own; BOFI_RB_ATTN_W picks the other form)
     const int rc = bofi::launch_rb_attn(a, (hipStream_t)stream);
     return rc < 0 ? BOFI_ERR_ARG : rc;
@@ -1818,7 +1799,7 @@ extern "C" int bofi_attn_linear_block(const void* q, int ldq, const void* k, int
     a.B = B; a.Lq = Lq; a.Lk = Lk; a.klen = klen; a.klen_sb = klen_sb; a.klen_sq = 0; a.klen_bias = klen_bias; a.klen_shared_last = klen_shared_last;
     a.wop = (const bofi::u32x4*)wop; a.bo = bo; a.x = x; a.ldx = ldx; a.y = x; a.ldy = ldx;
     a.pj_wp = (const bofi::u32x4*)pj_wp; a.pj_c = pj_c; a.pj_cs = pj_cs; a.pj_y = (bofi::bf16_t*)pj_y; a.pj_ldy = pj_ldy;
-    { const char* e = getenv("BOFI_RB_DBG"); a.dbg = e ? atoi(e) : 0; }
+    a.dbg = bofi::knob(BOFI_RB_DBG);
     const int rc = bofi::launch_rb_attn(a, (hipStream_t)stream);
     return rc < 0 ? BOFI_ERR_ARG : rc;
 }
@@ -1827,7 +1808,7 @@ extern "C" int bofi_linear_block(const float* x, int ldx, const void* wp, const 
                                  int relu, void* stream) {
     bofi::RbGemmArgs a{};
     a.x = x; a.ldx = ldx; a.wp = (const bofi::u32x4*)wp; a.c = c; a.cs = cs; a.y = y; a.ldy = ldy; a.y_f32 = y_f32; a.M = M; a.N = N; a.relu = relu;
-    { const char* e = getenv("BOFI_RB_DBG"); a.dbg = e ? atoi(e) : 0; }
+    a.dbg = bofi::knob(BOFI_RB_DBG);
     return bofi::launch_rb_gemm(a, (hipStream_t)stream);
 }
 

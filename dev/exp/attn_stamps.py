@@ -37,7 +37,7 @@ for what, Lq, Lk, W in (("encoder self-attention", 36, 36, 16), ("filling self-a
         run()
     e1.record(); torch.cuda.synchronize()
     us = e0.elapsed_time(e1) / 50 * 1e3
-    os.environ["BOFI_RB_DBG"] = "16"
+    os.environ["BOFI_RB_DBG"] = "16"; L.bofi_reload_env()
     run(); torch.cuda.synchronize()
     buf = (C.c_ulonglong * 256)()
     H.check(L.bofi_rb_stamps(buf))

@@ -45,7 +45,7 @@ def timed(fn, n=50):
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / n * 1e3
 print(f"{B} images x {S} rows, {R} regions: one launch {timed(fused):.1f} us, three launches {timed(three):.1f} us (back to back on one stream, eager)")
-os.environ["BOFI_RB_DBG"] = "16"
+os.environ["BOFI_RB_DBG"] = "16"; L.bofi_reload_env()
 x = x0.clone(); fused(x); torch.cuda.synchronize()
 buf = (C.c_ulonglong * 256)()
 H.check(L.bofi_rb_stamps(buf))

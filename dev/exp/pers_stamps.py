@@ -8,7 +8,7 @@ M, N, K = (int(v) for v in (sys.argv[1] if len(sys.argv) > 1 else "11520x2048x51
 dbg = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 plain = len(sys.argv) > 3 and sys.argv[3] == "plain"          # no folded LayerNorm (no statistics loads in the loaders)
 buf = torch.zeros(8 * 2 * 256, dtype=torch.int64, device="cuda")
-os.environ["BOFI_GEMM_DBG"] = str(64 | dbg); os.environ["BOFI_GEMM_DBG_BUF"] = str(buf.data_ptr()); os.environ["BOFI_GEMM_PERS_MIN"] = "1"
+os.environ["BOFI_GEMM_DBG"] = str(64 | dbg); os.environ["BOFI_GEMM_DBG_BUF"] = str(buf.data_ptr()); os.environ["BOFI_GEMM_PERS_MIN"] = "1"; lib.bofi_reload_env()
 x = torch.randn(M, K, device="cuda").to(torch.bfloat16); w = (torch.randn(N, K, device="cuda") / K ** 0.5).to(torch.bfloat16)
 bias = torch.randn(N, device="cuda"); st = torch.rand(M, K // 32, 2, device="cuda") + 1.0; cs = w.float().sum(1)
 y = torch.empty(M, N, dtype=torch.bfloat16, device="cuda")

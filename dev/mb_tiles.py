@@ -23,6 +23,7 @@ for M, N, K in SHAPES:
             os.environ.pop("BOFI_GEMM_TILE", None)
         else:
             os.environ["BOFI_GEMM_TILE"] = cfg
+        lib.bofi_reload_env()          # (the library reads its knobs at the reload, not at the launch)
         run = lambda: lib.bofi_linear(H.ptr(x), H.DT_BF16, K, H.ptr(w), H.DT_BF16, H.ptr(b), None, N, H.ptr(y), H.DT_F32, N, M, N, K, 0, None, 0, H.stream_ptr())
         if run() != 0:
             continue

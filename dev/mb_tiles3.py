@@ -36,6 +36,7 @@ for sh in SHAPES:
             os.environ.pop("BOFI_GEMM_TILE", None)
         else:
             os.environ["BOFI_GEMM_TILE"] = cfg
+        lib.bofi_reload_env()          # (the library reads its knobs at the reload, not at the launch)
         graphs, ok = [], True
         for si, st in enumerate(streams):
             with torch.cuda.stream(st):

@@ -221,8 +221,9 @@ int bofi_linear_fused(const void* x, int ldx, const void* w, const float* bias, 
                       void* y2, int ldy2, const float* ln_stats, const float* ln_colsum, int ln_groups, float* stats_out, int M, int N, int K,
                       int relu, void* stream);
 
-/* Developer knobs read from the environment (BOFI_GEMM_PERS, BOFI_GEMM_PERS_MIN) are cached at first use: after changing them in a
- * running process call this to have them read again. */
+/* The BOFI_* knobs of the library (the table in csrc/bofi_knobs.h) are read from the environment at first use, all of them: after changing
+ * one in a running process call this to have them all read again (it also starts a new generation of the engines' graph keys).  Not to be
+ * called while another thread launches. */
 void bofi_reload_env(void);
 
 /* y = mask > 0 ? (x w^T) * scale : 0 (no bias): the input gradient of a linear whose INPUT came out of relu (+ dropout with
