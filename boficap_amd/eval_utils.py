@@ -20,6 +20,9 @@ references alone (integer rows or id strings; no loss then), or None.  ``eval_kw
                      ``eval_kwargs['preds_n']``, and ``lang_stats`` gains the diversity statistics of boficap_amd.diversity ('Div-1', 'Div-2',
                      'mBLEU_1'..'mBLEU_4', 'self_cider'; per image under ``eval_kwargs['diversity_per_image']``) on the document frequencies of
     cached_tokens    a df pickle of scripts/prepro_ngrams.py: a path, or a name resolved as data/<name>.p (default 'coco-train-idxs')
+    eval_oracle      1, with ``language_eval`` 1 and ``sample_n`` > 1 (nothing changes otherwise): every sampled caption is scored against its image's
+                     references and ``lang_stats`` gains 'oracle_<M>' (the best of an image's N, averaged over the images) and 'avg_<M>' (their mean)
+                     for M = Bleu_1..Bleu_4, ROUGE_L, CIDEr (``LanguageEval.evaluate_n``); per image under ``eval_kwargs['oracle_per_image']``
 """
 from __future__ import annotations
 
@@ -170,7 +173,7 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
                     seq, pn, pl, ent, ppl = seq.cpu(), pn.cpu(), pl.cpu(), ent.cpu(), ppl.cpu()
                     predictions.extend(entry_of(i, k, seq, pn, pl, ent, ppl, vocab) for k in range(att.size(0)))
                     seqs.append(seq); ents.append(ent); ppls.append(ppl)
-        lang_stats = None
+        lang_stats, ev = None, None
         if int(kw.get("language_eval", 0)) == 1:
             ev = kw.get("lang_eval")
             if ev is None:
@@ -184,6 +187,10 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
             kw["preds_n"], sampled = sample_n_predictions(model, feats, sample_n, mode, batch_size, vocab)
             div, kw["diversity_per_image"] = diversity_stats(sampled, sample_n, kw)
             lang_stats = dict(lang_stats or {}, **div)
+            if ev is not None and int(kw.get("eval_oracle", 0)) == 1:      # the oracle of language_eval (eval_utils.py:112-114): inside it, and only with a preds_n
+                oracle = ev.evaluate_n(sampled, sample_n)
+                kw["oracle_per_image"] = oracle.pop("per_image")
+                lang_stats.update(oracle)
     finally:
         model.train(was_training)
     return val_loss, predictions, lang_stats

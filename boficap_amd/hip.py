@@ -119,6 +119,7 @@ SIGNATURES = {
     "bofi_rouge_score": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, C.c_double, _P, _P, _P, _P]),
     "bofi_diversity_workspace": (_I64, [_I, _I, _I]),
     "bofi_diversity_score": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, C.c_double, _P, _I64, _P, _P, _P, _P, _P]),
+    "bofi_oracle_stats": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -647,6 +647,18 @@ int bofi_diversity_score(const int64_t* seq, int images, int n, int S, int eval_
                          double log_ref_len, void* workspace, int64_t workspace_bytes, double* score, double* mat, int* div, int* comps,
                          void* stream);
 
+/* Oracle and average language scores of every image's n sampled captions (the reference's --eval_oracle 1), in fp64, from the per-candidate
+ * outputs of bofi_reward_score and bofi_rouge_score at seq_per_img = n: row m * n + i is sample i of image m, 1 <= n <= 64.
+ *   comps int32 [images * n, 10]: bofi_reward_score's counts (testlen, reflen, guess[4], correct[4]); cider, rouge double [images * n].
+ *   sent double [images * n, 6] or NULL: the sentence-level Bleu_1, Bleu_2, Bleu_3, Bleu_4 (bleu_scorer.py's compute_score on the row's
+ *     counts, option 'closest': the arithmetic of bofi_reward_score's BLEU-4, every order kept), ROUGE_L, CIDEr.
+ *   stats double [images, 6, 2]: per metric (oracle, avg) = (the maximum over the n samples, their sum in index order / n).
+ *   pick int32 [images, 6]: the lowest sample index that attains the oracle.
+ * A NaN among an image's n values of a metric (a CIDEr of a row with an id above 65534) makes that oracle and avg NaN and the pick -1.
+ * images = 0 is BOFI_OK without a launch.  Maximum and index are exact, the sum has a fixed order: deterministic. */
+int bofi_oracle_stats(const int* comps, const double* cider, const double* rouge, int images, int n, double* sent, double* stats, int* pick,
+                      void* stream);
+
 /* Last HIP error string seen by this library on the calling thread (for exceptions in the host). */
 const char* bofi_last_error(void);
 

@@ -11,7 +11,8 @@ synthetic.  ``--language_eval 1`` (with ``--input_label_npz``: the references) a
 ROUGE-L, CIDEr on the device (boficap_amd.lang_eval) -- as a printed line and, in ``--dump_json``, under a top-level key.
 ``--sample_n N`` (N > 1, with ``--cached_tokens``: the document frequencies) draws N captions per image after the greedy pass and adds their
 diversity statistics -- Div-1, Div-2, mBLEU-1..4, self-CIDEr on the device (boficap_amd.diversity) -- the same way, with the sampled captions under
-``preds_n``.
+``preds_n``.  ``--eval_oracle 1`` (with ``--language_eval 1 --sample_n N``) scores every sampled caption against its image's references and adds
+the best of an image's N and their mean per metric (``oracle_<M>``, ``avg_<M>``: boficap_amd.lang_eval.LanguageEval.evaluate_n) as one more line.
 """
 import argparse
 import json
@@ -52,9 +53,13 @@ def main():
                     "mBLEU-1..4 and self-CIDEr over them; --dump_json then holds {'predictions', 'preds_n', 'lang_stats'}")
     ap.add_argument("--cached_tokens", default="coco-train-idxs", help="document-frequency pickle of the self-CIDEr score (scripts/prepro_ngrams.py): a path, or a "
                     "name resolved as data/<name>.p")
+    ap.add_argument("--eval_oracle", type=int, default=0, choices=[0, 1], help="1 (with --language_eval 1 --sample_n N): oracle_<M> and avg_<M>, the best and the "
+                    "mean of an image's N sampled captions, for BLEU-1..4, ROUGE-L and CIDEr against the references")
     args = ap.parse_args()
     if args.language_eval and not args.input_label_npz:
         ap.error("--language_eval 1 needs the references: --input_label_npz")
+    if args.eval_oracle and not (args.language_eval and args.sample_n > 1):
+        ap.error("--eval_oracle 1 scores the sampled captions against the references: it needs --language_eval 1 and --sample_n N (N > 1)")
 
     import captioning.models as models
     from boficap_amd import eval_utils, weights as W
@@ -136,7 +141,8 @@ def main():
     lang_stats = None
     if args.language_eval:
         from boficap_amd.lang_eval import LanguageEval
-        lang_stats = LanguageEval([store.gts(i) for i in range(len(results))], "cuda").evaluate(torch.cat(rows), torch.cat(stats[0]), torch.cat(stats[1]))
+        lang_ev = LanguageEval([store.gts(i) for i in range(len(results))], "cuda")
+        lang_stats = lang_ev.evaluate(torch.cat(rows), torch.cat(stats[0]), torch.cat(stats[1]))
         print("language scores " + " ".join(f"{k} {v:.6f}" for k, v in lang_stats.items()))
     preds_n = None
     if args.sample_n > 1:
@@ -144,6 +150,11 @@ def main():
         div, _ = eval_utils.diversity_stats(sampled, args.sample_n, {"cached_tokens": args.cached_tokens})
         lang_stats = dict(lang_stats or {}, **div)
         print("diversity scores " + " ".join(f"{k} {v:.6f}" for k, v in div.items()))
+        if args.eval_oracle:
+            oracle = lang_ev.evaluate_n(sampled, args.sample_n)
+            oracle.pop("per_image")
+            lang_stats.update(oracle)
+            print("oracle scores " + " ".join(f"{k} {v:.6f}" for k, v in oracle.items()))
     if args.dump_json:
         with open(args.dump_json, "w") as f:
             if preds_n is not None:
