@@ -10,6 +10,7 @@
 
 #define BOFI_DT_F32 0
 #define BOFI_DT_BF16 1
+#define BOFI_DT_F16 2      // bofi_pack_regions' input only
 
 namespace bofi {
 
@@ -124,6 +125,10 @@ __device__ __forceinline__ uint32_t drop_hash(uint64_t seed, uint64_t i) {
 
 // host-side: the BOFI_* environment knobs (one table, one reader; re-read by bofi_reload_env)
 #include "bofi_knobs.h"
+
+// host-side: records `msg` for bofi_last_error() on the calling thread and returns `code` (engine.hip owns the string)
+#include <string>
+namespace bofi { int fail(int code, const std::string& msg); }
 
 // host-side launch check: kernels are enqueued on a stream, so this only catches launch errors
 #define BOFI_CHECK_LAUNCH()                                   \

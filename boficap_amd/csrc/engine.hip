@@ -70,6 +70,8 @@ struct GraphEntry {
 
 }  // namespace
 
+int bofi::fail(int code, const std::string& msg) { g_err = msg; return code; }      // the other translation units' way to bofi_last_error()
+
 struct bofi_engine {
     bofi_config_t cfg{};
     std::map<std::string, std::vector<float>> host;

@@ -10,7 +10,7 @@
 ``LabelStore`` reads those arrays (from an open h5py file, a path when h5py is installed, or any mapping of arrays with those
 names) and restates the loader's caption sampling (captioning/data/dataloader.py:186-229) and the label framing of its collate
 (:295-300); the phrase-aware part of the collate is ``boficap_amd.collate.phrase_collate`` (vectorised restatement of :343-428).
-Region features come from elsewhere (lmdb / npz directories in the reference): this class handles the label side only.
+Region features (npz / npy directories, .pth dictionaries) are the other half of the loader: ``boficap_amd.features``.
 """
 from __future__ import annotations
 

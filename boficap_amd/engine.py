@@ -495,7 +495,10 @@ class DecodePipeline:
 
     def run(self, batches):
         """``batches``: iterable of ``att_feats`` or ``(att_feats, att_len)``: [b, R, F] tensors / arrays in the engine's compute dtype or float32, on
-        the host (pinned: the copy is asynchronous) or the device; ``att_len`` int32 [b] region counts or None (every image has R regions)."""
+        the host (pinned: the copy is asynchronous) or the device; ``att_len`` int32 [b] region counts or None (every image has R regions).  An item may
+        also be a ``features.RaggedBatch``: its real rows alone are copied, in the files' dtype, and ``bofi_pack_regions`` pads them to the region bucket
+        in the compute dtype on the device (a batch whose images all have the bucket's count is decoded without counts, as the loader hands it over)."""
+        from .features import RaggedBatch
         pending = []                                             # launches in flight: (slot, [batch sizes])
         group, gkey = [], None
         j = 0
@@ -508,11 +511,19 @@ class DecodePipeline:
             if j >= self.nf:
                 yield from self._finish(pending.pop(0))
             self._launch(k, p, group, gkey)
-            pending.append((k, [g[0].shape[0] for g in group]))
+            pending.append((k, [g[0].B if isinstance(g[0], RaggedBatch) else g[0].shape[0] for g in group]))
             j += 1
             group = []
 
         for item in batches:
+            if isinstance(item, RaggedBatch):
+                r = self._bucket(item.max_len)
+                key = (item.B, r, item.F, self.root.dtype, item.equal_lengths and item.max_len == r)
+                if group and (key != gkey or len(group) >= self.bpl):
+                    yield from flush()
+                group.append((item, None))
+                gkey = key
+                continue
             att, lens = item if isinstance(item, (tuple, list)) else (item, None)
             att = self._as_host_or_device(att)
             lens = None if lens is None else self._as_host_or_device(lens).to(torch.int32)
@@ -547,7 +558,14 @@ class DecodePipeline:
                 sl["lens"][p] = torch.zeros(self.rows_max, dtype=torch.int32, device=self.dev)
             feats, lens = buf[:rows], (sl["lens"][p][:rows] if has_len else None)
             cs.wait_event(sl["done"])                            # the launch that last read this slot's buffers is through (it was finished before this one is issued)
+            staged = self._stage_ragged(sl, p, group)
             for i, (att, ln) in enumerate(group):
+                if i in staged:                                  # a RaggedBatch: its rows and offsets to the slot's staging buffer, the padding made on the device
+                    srows, soffs = staged[i]
+                    srows.copy_(att.rows, non_blocking=True)
+                    soffs.copy_(att.offsets, non_blocking=True)
+                    hip.pack_regions(srows, soffs, att.offsets, feats[i * b:(i + 1) * b], norm=att.norm, att_len=lens[i * b:(i + 1) * b] if has_len else None)
+                    continue
                 for src in (att, ln):                            # a DEVICE batch was produced on its caller's stream: the copy waits for that stream, and the caching
                     if src is not None and src.is_cuda:          # allocator must not hand the batch's memory out again while the copy is pending
                         cs.wait_stream(caller)
@@ -561,6 +579,28 @@ class DecodePipeline:
             st.wait_event(sl["copied"][p])
             self._decode_and_copy_out(sl)
             sl["done"].record(st)
+
+    def _stage_ragged(self, sl, p, group):
+        """Device views {item index: (rows, offsets)} for the RaggedBatch items of ``group``, carved out of slot ``sl``'s staging buffers of parity ``p`` (grown,
+        never shrunk; created and reused on the copy stream alone, so the stream orders every use)."""
+        from .features import RaggedBatch
+        items = [(i, g[0]) for i, g in enumerate(group) if isinstance(g[0], RaggedBatch)]
+        if not items:
+            return {}
+        need = sum(it.rows.numel() * it.rows.element_size() for _, it in items)      # (every item's bytes are a multiple of 16: F % 8 == 0 is checked by the kernel's wrapper)
+        need_off = sum(it.B + 1 for _, it in items)
+        stage = sl.setdefault("stage", [None, None])
+        if stage[p] is None or stage[p][0].numel() < need or stage[p][1].numel() < need_off:
+            old = stage[p]
+            stage[p] = (torch.empty(max(need, old[0].numel() if old else 0), dtype=torch.uint8, device=self.dev),
+                        torch.empty(max(need_off, old[1].numel() if old else 0), dtype=torch.int32, device=self.dev))
+        raw, offs = stage[p]
+        views, o, q = {}, 0, 0
+        for i, it in items:
+            n = it.rows.numel() * it.rows.element_size()
+            views[i] = (raw[o:o + n].view(it.rows.dtype).view(it.rows.shape), offs[q:q + it.B + 1])
+            o, q = o + n, q + it.B + 1
+        return views
 
     def _decode_and_copy_out(self, sl):
         e = sl["eng"]

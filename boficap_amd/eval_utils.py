@@ -4,7 +4,9 @@ loss, one greedy caption per image, and the language scores that need no Java (b
     val_loss, predictions, lang_stats = eval_split(model, feats, store_or_gts, eval_kwargs)
     val_loss, predictions, lang_stats = eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=5)       # + eval_kwargs['preds_n']
 
-``feats``: region features [N, R, F] (array or tensor on the host).  ``store_or_gts``: a label source with ``batch(image_ixs, seq_per_img, rng)``
+``feats``: region features [N, R, F] (array or tensor on the host), or a REGION SOURCE -- an object with ``__len__`` and ``ragged(i0, i1)`` -> a
+``features.RaggedBatch`` of images i0 .. i1 - 1 (``features.RegionSource``: per-image feature files of 10..100 regions): every batch is then staged ragged
+and padded to its longest image on the device, with the loader's mask (None when the batch's images have equal counts).  ``store_or_gts``: a label source with ``batch(image_ixs, seq_per_img, rng)``
 and ``gts(ix)`` (``data.LabelStore``, ``SyntheticLabels``) -- the loss is computed and the references come from it --, or the per-image
 references alone (integer rows or id strings; no loss then), or None.  ``eval_kwargs``:
 
@@ -45,6 +47,18 @@ def entry_of(i, k, seq, pn, pl, ent, ppl, vocab=None):
     return entry
 
 
+def is_region_source(feats) -> bool:
+    return hasattr(feats, "ragged") and hasattr(feats, "__len__")
+
+
+def device_batch(source, i0: int, i1: int, dtype=torch.float32):
+    """Images i0 .. i1 - 1 of a region source on the device as the loader's collate hands them over: (att_feats [b, longest, F] in ``dtype``, att_masks
+    float32 [b, longest] or None)."""
+    from .features import att_masks_of
+    att, att_len = source.ragged(i0, min(i1, len(source))).to_device(out_dtype=dtype)
+    return att, att_masks_of(att_len, att.size(1))
+
+
 def validation_loss(model, feats, store, batch_size: int, seq_per_img: int, image_ixs=None):
     """The loss of eval_split (verbose_loss, eval_utils.py:440-453) as a pass of its own: (sum of the batches' LanguageModelCriterion_UIC losses,
     number of batches).  Image i of ``feats`` is image ``image_ixs[i]`` (default i) of ``store``."""
@@ -52,13 +66,16 @@ def validation_loss(model, feats, store, batch_size: int, seq_per_img: int, imag
     crit, rng, loss_sum, loss_evals = LanguageModelCriterion_UIC(), np.random.default_rng(0), 0.0, 0
     with torch.no_grad():
         for i in range(0, len(feats), batch_size):
-            att = torch.from_numpy(np.ascontiguousarray(feats[i:i + batch_size])).cuda()
+            if is_region_source(feats):
+                att, masks = device_batch(feats, i, i + batch_size)
+            else:
+                att, masks = torch.from_numpy(np.ascontiguousarray(feats[i:i + batch_size])).cuda(), None
             fc = torch.zeros(att.size(0), 0, device="cuda")
             ixs = range(i, i + att.size(0)) if image_ixs is None else [int(x) for x in image_ixs[i:i + att.size(0)]]
             hb = store.batch(ixs, seq_per_img, rng)
             hb.pop("gts", None)
             b = {k: torch.from_numpy(v).cuda() for k, v in hb.items()}
-            outs = model(fc, att.float(), b["labels"], None, b["phrase_num"], b["phrase_length"], b["phrase_syn"],
+            outs = model(fc, att.float(), b["labels"], masks, b["phrase_num"], b["phrase_length"], b["phrase_syn"],
                          b["extend_phrase_syn_seq"], b["extend_phrase_seq"], b["extend_phrase_seq_mask"])
             loss_sum += float(crit(*outs, b["phrase_num"], b["phrase_length"], b["phrase_syn"], b["labels"])[0])
             loss_evals += 1
@@ -88,16 +105,20 @@ def sample_n_predictions(model, feats, sample_n: int, mode: str = "NAIC", batch_
     """eval_split_n (eval_utils.py:670-700) for ``sample_n_method='sample'``: ``sample_n`` captions per image of ``feats`` drawn through
     ``mode='sample'``.  Returns (entries {'image_id', 'seq'[, 'caption']} in row order, the sampled ids [N * sample_n, S] on the device); an
     entry's 'seq' holds the ids before the first id <= 0 (decode_sequence)."""
-    n, host = int(sample_n), _torch_feats(feats)
+    n, ragged = int(sample_n), is_region_source(feats)
+    host = feats if ragged else _torch_feats(feats)
     step = batch_size if mode == "NAIC" else max(1, min(batch_size, model.max_batch // n))       # the SAIC sampler decodes images x n rows
     rows = []
     with torch.no_grad():
         for i in range(0, len(host), step):
-            att = host[i:i + step].cuda()
+            if ragged:
+                att, masks = device_batch(host, i, i + step)
+            else:
+                att, masks = host[i:i + step].cuda(), None
             if att.dtype != torch.float32 and att.dtype != model.compute_dtype:
                 att = att.float()
             fc = torch.zeros(att.size(0), 0, device="cuda")
-            rows.append(model(fc, att, None, opt={"train_mode": mode, "sample_method": "sample", "sample_n": n}, mode="sample")[0])
+            rows.append(model(fc, att, masks, opt={"train_mode": mode, "sample_method": "sample", "sample_n": n}, mode="sample")[0])
     seq = torch.cat(rows)
     entries = []
     for j, row in enumerate(seq.cpu().tolist()):
@@ -146,9 +167,18 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
             val_loss = loss_sum / max(1, loss_evals)
         predictions, seqs, ents, ppls = [], [], [], []
         vocab = kw.get("vocab")
-        host = _torch_feats(feats)
+        ragged = is_region_source(feats)
+        host = feats if ragged else _torch_feats(feats)
         with torch.no_grad():
-            if mode == "NAIC":
+            if mode == "NAIC" and ragged:                       # staged ragged batch by batch, ahead of the launches that consume them
+                i = 0
+                for r in model.decode_many((feats.ragged(j, min(j + batch_size, N)) for j in range(0, N, batch_size)), batches_per_launch=int(kw.get("batches_per_launch", 16)),
+                                           in_flight=kw.get("in_flight"), fused_vocab=bool(kw.get("fused_vocab", False))):
+                    n = r["seq"].size(0)
+                    predictions.extend(entry_of(i, k, r["seq"], r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"], vocab) for k in range(n))
+                    seqs.append(r["seq"]); ents.append(r["entropy"]); ppls.append(r["perplexity"])
+                    i += n
+            elif mode == "NAIC":
                 if host.dtype != torch.float32 and host.dtype != model.compute_dtype:
                     host = host.float()
                 if model.compute_dtype == torch.bfloat16:     # (as a loader of half-precision feature files hands them over)
@@ -165,9 +195,12 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
                     i += n
             else:
                 for i in range(0, N, batch_size):
-                    att = host[i:i + batch_size].cuda()
+                    if ragged:
+                        att, masks = device_batch(host, i, i + batch_size)
+                    else:
+                        att, masks = host[i:i + batch_size].cuda(), None
                     fc = torch.zeros(att.size(0), 0, device="cuda")
-                    seq, lp, pn, pl, ps, _ = model(fc, att, None, opt={"train_mode": "SAIC", "sample_method": "greedy", "sample_n": 1}, mode="sample")
+                    seq, lp, pn, pl, ps, _ = model(fc, att, masks, opt={"train_mode": "SAIC", "sample_method": "greedy", "sample_n": 1}, mode="sample")
                     # per-image entropy / perplexity as eval_utils.py:463-464, from the fused row reductions (bofi_vocab_stats)
                     ent, ppl = model.engine().entropy_perplexity({"seq": seq, "seq_logprob": lp})
                     seq, pn, pl, ent, ppl = seq.cpu(), pn.cpu(), pl.cpu(), ent.cpu(), ppl.cpu()

@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BOFI_LIB_PATH") or os.path.join(HERE, "libboficap_hip.so")     # (the override is a developer knob for A/B runs)
 
 DT_F32, DT_BF16 = 0, 1
+DT_F16 = 2                          # bofi_pack_regions' input only
 FLAG_STRICT_Q1, FLAG_RAW_LOGITS, FLAG_GRAPH = 1, 2, 4
 FLAG_REFINE_SHIFT = 8
 FLAG_SAMPLE = 16
@@ -120,6 +121,7 @@ SIGNATURES = {
     "bofi_diversity_workspace": (_I64, [_I, _I, _I]),
     "bofi_diversity_score": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, C.c_double, _P, _I64, _P, _P, _P, _P, _P]),
     "bofi_oracle_stats": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "bofi_pack_regions": (_I, [_P, _I, _P, _P, _I, _I, _P, _I, _I, _I, _P, _P]),
 }
 
 _lib = None
@@ -188,6 +190,29 @@ def vocab_block(x, wp, c, cs, V, S, seq, *, ntok=None, ntok_bias=0, pad_idx=0, r
     ``c.numel()`` (padded) columns of which the first ``V`` count; seq int64 [M] out, row_plogp / row_chosen float32 [M] (both or neither), nan_flag int32 [1]."""
     check(lib().bofi_vocab_block(ptr(x), x.stride(0), ptr(wp), ptr(c), ptr(cs), x.shape[0], c.numel(), int(V), int(S), ptr(ntok), int(ntok_bias), int(pad_idx),
                                  ptr(seq), ptr(row_plogp), ptr(row_chosen), ptr(nan_flag), 1 if alone else 0, stream_ptr()), "bofi_vocab_block")
+
+
+def pack_regions(rows, offsets, offsets_host, out, *, norm=False, att_len=None):
+    """``bofi_pack_regions`` on torch tensors: rows [sum len, F] float32 / float16 / bfloat16 and offsets int32 [B + 1] on the device, offsets_host the host's
+    int32 copy of the offsets (checked before the launch) or None, out [B, out_R, F] float32 / bfloat16 contiguous, att_len int32 [B] or None.  One launch on
+    the current stream, no synchronisation."""
+    import torch
+    codes = {torch.float32: DT_F32, torch.bfloat16: DT_BF16, torch.float16: DT_F16}
+    if rows.dtype not in codes or out.dtype not in (torch.float32, torch.bfloat16):
+        raise BofiHipError(f"pack_regions: rows {rows.dtype} -> out {out.dtype} is not a supported pair")
+    if rows.dim() != 2 or out.dim() != 3 or rows.size(1) != out.size(2) or not rows.is_contiguous() or not out.is_contiguous() or not rows.is_cuda or not out.is_cuda:
+        raise BofiHipError("pack_regions: contiguous device tensors rows [n, F] and out [B, out_R, F] expected")
+    B = out.size(0)
+    if offsets.dtype != torch.int32 or offsets.numel() != B + 1 or not offsets.is_cuda or not offsets.is_contiguous():
+        raise BofiHipError("pack_regions: offsets must be int32 [B + 1] on the device")
+    if offsets_host is not None and (offsets_host.dtype != torch.int32 or offsets_host.numel() != B + 1 or offsets_host.is_cuda or not offsets_host.is_contiguous()):
+        raise BofiHipError("pack_regions: offsets_host must be int32 [B + 1] on the host")
+    if offsets_host is not None and int(offsets_host[B]) > rows.size(0):
+        raise BofiHipError(f"pack_regions: the offsets name {int(offsets_host[B])} rows, rows holds {rows.size(0)}")
+    if att_len is not None and (att_len.dtype != torch.int32 or att_len.numel() != B or not att_len.is_cuda or not att_len.is_contiguous()):
+        raise BofiHipError("pack_regions: att_len must be int32 [B] on the device")
+    check(lib().bofi_pack_regions(ptr(rows), codes[rows.dtype], ptr(offsets), ptr(offsets_host), B, rows.size(1), ptr(out), dtype_code(out), out.size(1),
+                                  1 if norm else 0, ptr(att_len), stream_ptr()), "bofi_pack_regions")
 
 
 def gemm_flops(reset: bool = False):

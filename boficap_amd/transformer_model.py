@@ -247,7 +247,8 @@ class TransformerModel(nn.Module):
         host memory on a copy stream ahead of the launches (``boficap_amd.engine.DecodePipeline``).
 
         ``batches``: iterable of ``att_feats`` or ``(att_feats, att_masks)`` -- [b, R, F] float32 / compute-dtype tensors or arrays on the host or the device,
-        masks [b, R] as the loader builds them (prefix-structured, clipped to the batch's longest image by the caller as AttModel.clip_att does).
+        masks [b, R] as the loader builds them (prefix-structured, clipped to the batch's longest image by the caller as AttModel.clip_att does) -- or of
+        ``features.RaggedBatch``es (real rows only, in the files' dtype: padding, cast and norm_att_feat happen on the device).
         Yields one dict per batch, in order: seq [b, S] int64, phrase_num [b] int32, phrase_length [b, S] int32, phrase_syn [b, S] int64 (+ entropy,
         perplexity [b] as eval_utils.py:463-464 with ``stats``; + seq_logprob [b, S, V] on the device with ``keep_logprob``), host tensors.
         ``fused_vocab``: ids-only launches on forks without the vocabulary-wide buffers (``DecodePipeline(fused_vocab=True)``; not with ``keep_logprob``)."""
@@ -260,7 +261,11 @@ class TransformerModel(nn.Module):
                                                                        stats=stats, keep_logprob=keep_logprob, fused_vocab=fused_vocab))
 
         def items():
+            from .features import RaggedBatch
             for it in batches:
+                if isinstance(it, RaggedBatch):                 # staged ragged: padded, cast (and normalised) on the device by the pipeline
+                    yield it
+                    continue
                 att, masks = it if isinstance(it, (tuple, list)) else (it, None)
                 att = torch.from_numpy(att) if not torch.is_tensor(att) else att
                 if att.dtype not in (torch.float32, self.compute_dtype):

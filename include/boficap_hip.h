@@ -31,6 +31,7 @@ extern "C" {
 
 #define BOFI_DT_F32 0
 #define BOFI_DT_BF16 1
+#define BOFI_DT_F16 2   /* float16 (raw 16-bit): the input of bofi_pack_regions only */
 
 /* version of this ABI; bumped on any signature change */
 int bofi_abi_version(void);
@@ -658,6 +659,21 @@ int bofi_diversity_score(const int64_t* seq, int images, int n, int S, int eval_
  * images = 0 is BOFI_OK without a launch.  Maximum and index are exact, the sum has a fixed order: deterministic. */
 int bofi_oracle_stats(const int* comps, const double* cider, const double* rouge, int images, int n, double* sent, double* stats, int* pick,
                       void* stream);
+
+/* The region side of the loader's collate (captioning/data/dataloader.py:326-338: zero-padded features + region counts) and its optional
+ * norm_att_feat (:475-476: x / ||x||_2 per region), from a batch staged ragged.
+ *   rows: rows_dtype [offsets[B], F], the images' real region rows back to back; rows_dtype BOFI_DT_F32, BOFI_DT_BF16 or BOFI_DT_F16
+ *   offsets: int32 [B + 1], non-decreasing, offsets[0] = 0; offsets_host: the host's copy of the same array or NULL
+ *   out: out_dtype [B, out_R, F] contiguous (BOFI_DT_F32 or BOFI_DT_BF16); rows and out 16-byte aligned, F % 8 == 0
+ *   att_len: int32 [B] or NULL: len_b = offsets[b + 1] - offsets[b]
+ * Row r < len_b of image b is the image's row (divided by its norm when norm = 1) in out_dtype, rows len_b <= r < out_R are +0.0: EVERY
+ * element of out is written.  f16 -> f32 is exact, -> bf16 rounds the float32 value to nearest even.  norm: squares summed in float32 in a
+ * fixed order (no atomics: bit-identical run to run), sqrtf, one division per element; a row of zeros is NaN in every element (0 / 0, as
+ * numpy).  B < 1, F % 8 != 0, an unknown dtype, and -- checked on offsets_host, when given -- offsets[0] != 0, decreasing offsets or
+ * len_b > out_R are BOFI_ERR_ARG with a message and NOTHING is launched.  The kernel clamps len_b to [0, out_R] whatever the device array
+ * holds, so it never writes outside out.  One launch, no synchronisation. */
+int bofi_pack_regions(const void* rows, int rows_dtype, const int* offsets, const int* offsets_host, int B, int F, void* out, int out_dtype,
+                      int out_R, int norm, int* att_len, void* stream);
 
 /* Last HIP error string seen by this library on the calling thread (for exceptions in the host). */
 const char* bofi_last_error(void);

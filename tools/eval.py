@@ -3,11 +3,14 @@
 path this repository implements: greedy NAIC bound+fill decoding of precomputed region features.
 
     python tools/eval.py --model model.pth [--infos_path infos.pkl] --inference_mode NAIC \\
-        [--input_att_npy feats.npy | --synthetic 64] [--batch_size 64] [--dtype bf16|f32] [--dump_json out.json]
+        [--input_att_npy feats.npy | --input_att_dir DIR --input_json J [--split val] | --synthetic 64] [--batch_size 64] [--dtype bf16|f32] [--dump_json out.json]
 
-`--model` is a state_dict written by the reference (311 entries) or by this repository.  Data loading
-(lmdb/h5) and beam search are outside the scope of this build: features come from a .npy of shape [N, R, 2048] or are
-synthetic.  ``--language_eval 1`` (with ``--input_label_npz``: the references) adds the language scores that need no Java -- BLEU-1..4,
+`--model` is a state_dict written by the reference (311 entries) or by this repository.  Beam search is outside the scope of this build
+(SURVEY.md §2).  Features come from a .npy of shape [N, R, 2048], are synthetic, or -- ``--input_att_dir D --input_json J [--split val|test|train]
+[--num_images N] [--norm_att_feat 1]`` -- are the reference's per-image feature files (``<id>.npz`` / ``<id>.npy`` of 10..100 regions each, a ``.pth``
+dictionary; boficap_amd.features): the images and their ids are the json's split, every batch is staged ragged by ``--feeder_workers`` reader threads and
+padded on the device, ``image_id`` in the predictions is the json's id, and image i of the split uses image ``split_ix[i]`` of ``--input_label_npz``.
+Box features (``--use_box 1``) are refused: they make F = 2053 and the engine needs F % 64 == 0.  ``--language_eval 1`` (with ``--input_label_npz``: the references) adds the language scores that need no Java -- BLEU-1..4,
 ROUGE-L, CIDEr on the device (boficap_amd.lang_eval) -- as a printed line and, in ``--dump_json``, under a top-level key.
 ``--sample_n N`` (N > 1, with ``--cached_tokens``: the document frequencies) draws N captions per image after the greedy pass and adds their
 diversity statistics -- Div-1, Div-2, mBLEU-1..4, self-CIDEr on the device (boficap_amd.diversity) -- the same way, with the sampled captions under
@@ -33,6 +36,16 @@ def main():
     ap.add_argument("--infos_path", default="", help="infos_*.pkl of the reference (opt namespace + vocab)")
     ap.add_argument("--inference_mode", default="NAIC", choices=["NAIC", "SAIC"])
     ap.add_argument("--input_att_npy", default="")
+    ap.add_argument("--input_att_dir", default="", help="the reference's input_att_dir: a directory of <id>.npz (key 'feat', else 'z') or <id>.npy, or a .pth key -> array "
+                    "dictionary (.h5 / .lmdb with h5py / lmdbdict); needs --input_json")
+    ap.add_argument("--input_att_ext", default=".npz", choices=[".npz", ".npy"], help="file type of a feature directory")
+    ap.add_argument("--input_json", default="", help="the preprocessing's json: images[*]['id'] and ['split']")
+    ap.add_argument("--split", default="val", choices=["val", "test", "train"])
+    ap.add_argument("--num_images", type=int, default=-1, help="the first N images of the split (-1: all)")
+    ap.add_argument("--norm_att_feat", type=int, default=0, choices=[0, 1], help="1: every region divided by its L2 norm (dataloader.py:475-476), on the device")
+    ap.add_argument("--use_box", type=int, default=0, choices=[0, 1], help="refused: box features make F = 2053 and the engine needs F %% 64 == 0")
+    ap.add_argument("--in_memory", type=int, default=0, choices=[0, 1], help="1: every feature file is read once before the decode and served from memory")
+    ap.add_argument("--feeder_workers", type=int, default=4, help="reader threads of the feature files (at most 16)")
     ap.add_argument("--synthetic", type=int, default=64)
     ap.add_argument("--batch_size", type=int, default=64)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
@@ -58,6 +71,12 @@ def main():
     args = ap.parse_args()
     if args.language_eval and not args.input_label_npz:
         ap.error("--language_eval 1 needs the references: --input_label_npz")
+    if args.use_box:
+        ap.error("--use_box 1 is not supported: box features make F = 2053 and the engine needs F % 64 == 0")
+    if args.input_att_dir and not args.input_json:
+        ap.error("--input_att_dir needs the images' ids and splits: --input_json")
+    if args.input_att_dir and args.input_att_npy:
+        ap.error("--input_att_dir and --input_att_npy are two sources of the same features: give one")
     if args.eval_oracle and not (args.language_eval and args.sample_n > 1):
         ap.error("--eval_oracle 1 scores the sampled captions against the references: it needs --language_eval 1 and --sample_n N (N > 1)")
 
@@ -82,7 +101,20 @@ def main():
         model.load_state_dict({k: torch.from_numpy(v) for k, v in W.make_state_dict(model.cfg, 0).items()}, strict=True)
     model.cuda().eval()
 
-    if args.input_att_npy:
+    image_ixs, image_ids, att_store = None, None, None
+    if args.input_att_dir:
+        from boficap_amd.features import ImageIndex, RegionFeeder, RegionSource, RegionStore
+        index = ImageIndex(args.input_json)
+        image_ixs = index.split_ix[args.split][:args.num_images if args.num_images >= 0 else None]
+        if not image_ixs:
+            raise SystemExit(f"{args.input_json} assigns no image to split {args.split!r}")
+        image_ids = [index.ids[i] for i in image_ixs]
+        att_store = RegionStore(args.input_att_dir, args.input_att_ext, in_memory=bool(args.in_memory))
+        feats = RegionSource(att_store, image_ids, bool(args.norm_att_feat))
+        if args.in_memory:
+            for k in feats.keys:
+                att_store.get(k)
+    elif args.input_att_npy:
         feats = np.load(args.input_att_npy)
     else:                                                        # (2 048 distinct synthetic images, repeated: the generator is a CPU loop)
         uniq = W.synthetic_att_feats(min(args.synthetic, 2048), 36, model.cfg.att_feat_size, seed=1235)
@@ -102,8 +134,29 @@ def main():
 
     with torch.no_grad():
         if store is not None:                                    # the loss of eval_split (verbose_loss), eval_utils.py:440-453: a pass of its own
-            loss_sum, loss_evals = eval_utils.validation_loss(model, feats, store, args.batch_size, args.seq_per_img)
-        if args.pipeline and args.inference_mode == "NAIC":
+            loss_sum, loss_evals = eval_utils.validation_loss(model, feats, store, args.batch_size, args.seq_per_img, image_ixs)
+        if args.pipeline and args.inference_mode == "NAIC" and att_store is not None:
+            # the feature files are read and staged ragged by the feeder's threads INSIDE the clock, ahead of the launches; padding and cast happen on the device
+            key_batches = [feats.keys[i:i + args.batch_size] for i in range(0, len(feats), args.batch_size)]
+
+            def feeder(kb):
+                return RegionFeeder(att_store, kb, workers=args.feeder_workers, norm_att_feat=bool(args.norm_att_feat))
+            for _ in model.decode_many(feeder(key_batches[:2 * args.in_flight * args.batches_per_launch]), batches_per_launch=args.batches_per_launch, in_flight=args.in_flight,
+                                       fused_vocab=args.fused_vocab):
+                pass                                             # graph captures and stream choice, outside the clock
+            torch.cuda.synchronize()
+            import time
+            t0 = time.time()
+            got = list(model.decode_many(feeder(key_batches), batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab))
+            seconds = time.time() - t0
+            i = 0
+            for r in got:
+                n = r["seq"].size(0)
+                results.extend(entry_of(i, k, r["seq"], r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"]) for k in range(n))
+                i += n
+            how = (f"pipelined: {args.in_flight} launches in flight, {args.batches_per_launch} batches of {args.batch_size} per launch, feature files read by {args.feeder_workers} "
+                   f"threads and staged ragged, file reads and host results included" + (", fused vocabulary epilogue" if args.fused_vocab else ""))
+        elif args.pipeline and args.inference_mode == "NAIC":
             # the features as a loader of half-precision feature files hands them over: compute dtype, pinned host memory (staged once, outside the clock --
             # float32 features would cross PCIe at twice the bytes: ~190 k images/s at 55 GB/s)
             host = torch.from_numpy(np.ascontiguousarray(feats))
@@ -127,26 +180,35 @@ def main():
             how = f"pipelined: {args.in_flight} launches in flight, {args.batches_per_launch} batches of {args.batch_size} per launch, features from pinned host memory, host results included" + (", fused vocabulary epilogue" if args.fused_vocab else "")
         else:
             for i in range(0, len(feats), args.batch_size):
-                att = torch.from_numpy(np.ascontiguousarray(feats[i:i + args.batch_size])).cuda()
+                if att_store is not None:
+                    att, masks = eval_utils.device_batch(feats, i, i + args.batch_size)
+                else:
+                    att, masks = torch.from_numpy(np.ascontiguousarray(feats[i:i + args.batch_size])).cuda(), None
                 fc = torch.zeros(att.size(0), 0, device="cuda")
-                seq, lp, pn, pl, ps, t = model(fc, att, None, opt={"train_mode": args.inference_mode, "sample_method": "greedy", "sample_n": 1}, mode="sample")
+                seq, lp, pn, pl, ps, t = model(fc, att, masks, opt={"train_mode": args.inference_mode, "sample_method": "greedy", "sample_n": 1}, mode="sample")
                 seconds += t
                 # per-image entropy / perplexity as eval_utils.py:463-464, from the fused row reductions (bofi_vocab_stats)
                 ent, ppl = model.engine().entropy_perplexity({"seq": seq, "seq_logprob": lp})
                 results.extend(entry_of(i, k, seq, pn, pl, ent, ppl) for k in range(att.size(0)))
             how = "one synchronised mode='sample' call per batch (the reference's eval loop), decode time only"
+    if image_ids is not None:                                    # the json's ids, in the split's order
+        for e, iid in zip(results, image_ids):
+            e["image_id"] = iid
     print(f"decoded {len(results)} images in {seconds:.4f} s ({len(results) / max(seconds, 1e-9):.1f} images/s; {how})")
     if store is not None:
         print(f"validation loss {loss_sum / max(1, loss_evals):.4f} over {loss_evals} batches (LanguageModelCriterion_UIC)")
     lang_stats = None
     if args.language_eval:
         from boficap_amd.lang_eval import LanguageEval
-        lang_ev = LanguageEval([store.gts(i) for i in range(len(results))], "cuda")
+        lang_ev = LanguageEval([store.gts(image_ixs[i] if image_ixs is not None else i) for i in range(len(results))], "cuda")
         lang_stats = lang_ev.evaluate(torch.cat(rows), torch.cat(stats[0]), torch.cat(stats[1]))
         print("language scores " + " ".join(f"{k} {v:.6f}" for k, v in lang_stats.items()))
     preds_n = None
     if args.sample_n > 1:
         preds_n, sampled = eval_utils.sample_n_predictions(model, feats, args.sample_n, args.inference_mode, args.batch_size, vocab)
+        if image_ids is not None:
+            for e in preds_n:
+                e["image_id"] = image_ids[e["image_id"]]
         div, _ = eval_utils.diversity_stats(sampled, args.sample_n, {"cached_tokens": args.cached_tokens})
         lang_stats = dict(lang_stats or {}, **div)
         print("diversity scores " + " ".join(f"{k} {v:.6f}" for k, v in div.items()))

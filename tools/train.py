@@ -8,9 +8,12 @@
 
 One process per GPU (RANK / LOCAL_RANK / WORLD_SIZE from the environment) instead of ``nn.DataParallel``: every rank
 steps on its own shard of images and the gradients meet in one RCCL all-reduce over the flat gradient bucket
-(boficap_amd/trainer.py).  Data loading (lmdb / h5) is outside this build: batches are synthetic captions in the loader's layout (boficap_amd/collate.py), or -- with
-``--input_label_h5`` -- real captions from the preprocessing's label file (boficap_amd/data.py; region features stay synthetic,
-the feature directories being outside this build).  ``--cfg`` reads the reference's yml files including their ``_BASE_``
+(boficap_amd/trainer.py).  Batches are synthetic captions in the loader's layout (boficap_amd/collate.py), or -- with
+``--input_label_h5`` (the label file, or an .npz of the same arrays) -- real captions from the preprocessing's label file (boficap_amd/data.py), on synthetic
+region features unless ``--input_att_dir D --input_json J [--norm_att_feat 1] [--train_only 0|1] [--feeder_workers 4]`` names the reference's per-image feature
+files (boficap_amd/features.py; XE phase only: ``--self_critical_after`` is refused with them): the training images are then drawn from the json's train split, their features are read by a feeder's threads a few steps
+ahead, staged ragged and padded on the device (``att_masks`` from the region counts, None when a batch's counts are equal), and the validation set is the
+first ``--val_images_use`` images of the val split.  ``--cfg`` reads the reference's yml files including their ``_BASE_``
 inheritance (captioning/utils/config.py:35-95).  ``--self_critical_after N`` switches to the self-critical step (loss_wrapper.py:181-230,
 ``structure_loss_weight: 1``) from iteration N on, scored by ``boficap_amd.loss_wrapper``'s installed scorer or, without one, by CIDEr-D
 on the device (boficap_amd.cider) with the document frequencies of ``--cached_tokens`` / the cfg's ``cached_tokens`` (data/<name>.p of
@@ -49,7 +52,15 @@ def main():
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--tiny", action="store_true", help="the small test configuration instead of the 512-d model")
     ap.add_argument("--no_graph", action="store_true", help="run the step eagerly instead of replaying one hipGraph per batch signature")
-    ap.add_argument("--input_label_h5", default="", help="label file of scripts/prepro_labels_stanford.py (captions and phrase cuts); needs h5py")
+    ap.add_argument("--input_label_h5", default="", help="label file of scripts/prepro_labels_stanford.py (captions and phrase cuts; .h5 / .hdf5 needs h5py), or an .npz of "
+                    "the same arrays")
+    ap.add_argument("--input_att_dir", default="", help="the reference's input_att_dir: a directory of <id>.npz (key 'feat', else 'z') or <id>.npy, or a .pth key -> array "
+                    "dictionary (.h5 / .lmdb with h5py / lmdbdict); needs --input_json and --input_label_h5")
+    ap.add_argument("--input_att_ext", default=".npz", choices=[".npz", ".npy"], help="file type of a feature directory")
+    ap.add_argument("--input_json", default="", help="the preprocessing's json: images[*]['id'] and ['split']; image i = image i of the label file")
+    ap.add_argument("--norm_att_feat", type=int, default=0, choices=[0, 1], help="1: every region divided by its L2 norm (dataloader.py:475-476), on the device")
+    ap.add_argument("--train_only", type=int, default=0, choices=[0, 1], help="1: 'restval' images stay out of the train split (dataloader.py:177)")
+    ap.add_argument("--feeder_workers", type=int, default=4, help="reader threads of the feature files (at most 16)")
     ap.add_argument("--self_critical_after", type=int, default=-1, help="iteration from which the self-critical step replaces the XE step (-1: never)")
     ap.add_argument("--train_sample_n", type=int, default=5)
     ap.add_argument("--cached_tokens", default=None, help="document-frequency pickle of the CIDEr-D reward (scripts/prepro_ngrams.py): a path, or a name "
@@ -64,6 +75,15 @@ def main():
                     "(boficap_amd.lang_eval); the best checkpoint is then chosen by CIDEr instead of the validation loss")
     ap.add_argument("--save_history_ckpt", action="store_true", help="also keep every validated checkpoint as model-<iteration>.pth")
     args = ap.parse_args()
+    if bool(args.input_att_dir) != bool(args.input_json):
+        ap.error("--input_att_dir and --input_json go together: the feature files are keyed by the json's image ids")
+    if args.input_att_dir and args.self_critical_after >= 0:
+        ap.error("--self_critical_after is not supported with --input_att_dir: the self-critical step has not been validated on feature files "
+                 "(ragged, masked batches); train the XE phase on them, or the self-critical phase on synthetic features")
+    if args.input_att_dir and not args.input_label_h5:
+        ap.error("--input_att_dir needs the captions of its images: --input_label_h5")
+
+    import numpy as np
 
     import captioning.models as models
     from boficap_amd import checkpoint as ck, dp, weights as W
@@ -109,13 +129,26 @@ def main():
     store = None
     if args.input_label_h5:
         from boficap_amd.data import LabelStore
-        store = LabelStore(args.input_label_h5, pad_idx=cfg.pad_idx, bos_idx=cfg.bos_idx, eos_idx=cfg.eos_idx, len_idx=cfg.len_idx)
+        src = args.input_label_h5 if args.input_label_h5.endswith((".h5", ".hdf5")) else dict(np.load(args.input_label_h5))
+        store = LabelStore(src, pad_idx=cfg.pad_idx, bos_idx=cfg.bos_idx, eos_idx=cfg.eos_idx, len_idx=cfg.len_idx)
     n_val, val = max(0, args.val_images_use), None
-    if store is not None and n_val >= store.num_images:
+    att_store, train_ix, val_ix = None, None, None
+    if args.input_att_dir:
+        from boficap_amd.features import ImageIndex, RegionFeeder, RegionSource, RegionStore, att_masks_of
+        index = ImageIndex(args.input_json, args.train_only)
+        if len(index) != store.num_images:
+            raise SystemExit(f"{args.input_json} lists {len(index)} images, the label file {store.num_images}")
+        train_ix, val_ix = index.split_ix["train"], index.split_ix["val"][:n_val]
+        if not train_ix or len(val_ix) < n_val:
+            raise SystemExit(f"{args.input_json}: {len(train_ix)} training images, {len(index.split_ix['val'])} validation images (--val_images_use {n_val})")
+        att_store = RegionStore(args.input_att_dir, args.input_att_ext)
+    elif store is not None and n_val >= store.num_images:
         raise SystemExit(f"--val_images_use {n_val} leaves no training image of the label file's {store.num_images}")
     if n_val and rank == 0:                                      # the validation set, fixed for the run; its references are packed on first use and kept
         from boficap_amd import eval_utils
-        if store is not None:
+        if att_store is not None:
+            val = {"labels": store, "ixs": list(val_ix), "feats": RegionSource(att_store, index.keys(val_ix), bool(args.norm_att_feat))}
+        elif store is not None:
             val = {"labels": store, "ixs": list(range(store.num_images - n_val, store.num_images)),
                    "feats": W.synthetic_att_feats(n_val, 36, cfg.att_feat_size, seed=args.seed + 977)}
         else:
@@ -158,7 +191,6 @@ def main():
         print(f"{type(model).__name__}: {trainer.bucket.numel} parameters in one bucket, {world} rank(s), "
               f"{opt.batch_size} images x {opt.seq_per_img} captions per rank and step, GEMM operands {args.dtype}", flush=True)
 
-    import numpy as np
     from boficap_amd import loss_wrapper as LW
     scorer = None
     if args.self_critical_after >= 0:
@@ -184,15 +216,37 @@ def main():
         if rank == 0:
             print(f"self-critical reward: {what}", flush=True)
     t0, first = time.time(), trainer._step
+
+    def step_seed(it):                                           # a different shard per rank and step (the loader's role, dataloader.py:550-556)
+        return (it * world + rank) * 7919 + args.seed
+
+    def step_images(it):
+        """The label-file images of step ``it`` and the generator that goes on to draw their captions: a pure function of the iteration number."""
+        rng = np.random.default_rng(step_seed(it))
+        if train_ix is None:
+            return rng.integers(0, store.num_images - n_val, opt.batch_size), rng
+        return [train_ix[int(d)] for d in rng.integers(0, len(train_ix), opt.batch_size)], rng
+
+    feed = None
+    if att_store is not None:                                    # the steps' features, read and staged ragged by threads that run a few steps ahead
+        feed = iter(RegionFeeder(att_store, (index.keys(step_images(it)[0]) for it in range(first, first + args.max_iters)), workers=args.feeder_workers,
+                                 norm_att_feat=bool(args.norm_att_feat)))
+
+    def step_features(seed):
+        """(att_feats float32 [B, R, F], att_masks [B, R] or None) of this step on the device."""
+        if feed is None:
+            return torch.from_numpy(W.synthetic_att_feats(opt.batch_size, 36, cfg.att_feat_size, seed=seed)).to(dev), None
+        att, att_len = next(feed).to_device(out_dtype=torch.float32)
+        return att, att_masks_of(att_len, att.size(1))
+
     for it in range(first, first + args.max_iters):
-        # a different shard per rank and step (the loader's role, dataloader.py:550-556)
-        seed = (it * world + rank) * 7919 + args.seed
+        seed = step_seed(it)
         gts = None
         if store is None:
             host_batch = synthetic_training_batch(cfg, opt.batch_size, opt.seq_per_img, seed=seed)
         else:
-            rng = np.random.default_rng(seed)
-            host_batch = store.batch(rng.integers(0, store.num_images - n_val, opt.batch_size), opt.seq_per_img, rng)
+            ixs, rng = step_images(it)
+            host_batch = store.batch(ixs, opt.seq_per_img, rng)
             gts = host_batch.pop("gts")
         ss_start = args.scheduled_sampling_start if args.scheduled_sampling_start is not None else getattr(opt, "scheduled_sampling_start", -1)
         epoch = it // max(1, args.iters_per_epoch)
@@ -202,7 +256,7 @@ def main():
             opt.ss_prob = min(getattr(opt, "scheduled_sampling_increase_prob", 0.05) * frac, getattr(opt, "scheduled_sampling_max_prob", 0.25))
             model.ss_prob = opt.ss_prob
         if 0 <= args.self_critical_after <= it:                 # struc_flag (tools/train.py:181-185)
-            att = torch.from_numpy(W.synthetic_att_feats(opt.batch_size, 36, cfg.att_feat_size, seed=seed)).to(dev)
+            att, _ = step_features(seed)                         # (synthetic features: feature files are refused with --self_critical_after)
             refs = gts if gts is not None else [host_batch["labels"][b, :, 1:-1] for b in range(opt.batch_size)]
             n = args.train_sample_n
 
@@ -229,7 +283,9 @@ def main():
         batch = {k: torch.from_numpy(v).to(dev) for k, v in host_batch.items()}
         batch["max_phrase_num"] = int(host_batch["phrase_num"].max())
         batch["max_tokens"] = int((host_batch["phrase_length"].sum(-1) - 1).max())
-        batch["att_feats"] = torch.from_numpy(W.synthetic_att_feats(opt.batch_size, 36, cfg.att_feat_size, seed=seed)).to(dev)
+        batch["att_feats"], att_masks = step_features(seed)
+        if att_masks is not None:
+            batch["att_masks"] = att_masks
         batch = trainer.add_token_rows(batch, host_batch)
         glat_p = args.unmasked_rate_start if args.glancing_token else -1.0          # train.py:165-170
         dw_after = args.drop_worst_after if args.drop_worst_after is not None else getattr(opt, "drop_worst_after", -1)
@@ -257,6 +313,8 @@ def main():
         infos["iter"] = it + 1                                   # tools/train.py:292-294
         if args.save_checkpoint_every and (it + 1) % args.save_checkpoint_every == 0 and (args.checkpoint_path or n_val):
             validate_and_save(it + 1)
+    if feed is not None:
+        feed.close()                                             # (ends the feeder's threads)
     if args.checkpoint_path and rank == 0:
         infos["opt"] = ck.resume_opt(opt)                     # plain values, every option of the reference's resume check present
         ck.save_checkpoint(opt, model, infos, trainer, histories)
