@@ -7,6 +7,7 @@ flat gradient bucket and the optimiser is a single HBM-bound kernel (``bofi_adam
 """
 from __future__ import annotations
 
+import contextlib
 import re
 from typing import Dict, Optional
 
@@ -260,6 +261,36 @@ def noam_rate(step: int, d_model: int, factor: float = 1.0, warmup: int = 2000) 
     return factor * (d_model ** -0.5 * min(step ** -0.5, step * warmup ** -1.5))
 
 
+def step_plan(batch, seq_length: int, *, glat_p: float = -1.0, dense=None, scheduled_sampling: bool = False, streams=None, stage2=None):
+    """Which form of the step a batch (the collate's dict) takes, as the xe.StepPlan the forward reads: dense, compact, unpadded or paired.
+    ``dense``: None / "plain" / "drop_worst"; ``streams``: side streams an unpadded step may use, or None; ``stage2``: a two-stage backward's
+    dict.  A function of its arguments alone: it needs no device."""
+    from . import xe
+    has = lambda k: batch.get(k) is not None
+    plan = xe.StepPlan(split_memory=stage2, criterion="drop_worst" if dense == "drop_worst" else "dense")
+    if scheduled_sampling or dense:                            # scheduled sampling: the SA branch follows the model's own layout, not the loader's --
+        return plan                                            # no bounds, no row lists, the reference's dense criterion (as self_dis / drop_worst)
+    if has("max_phrase_num"):                                  # known on the host since the collate: spares the forward a device read
+        plan.max_phrase_num = XETrainer._bucket(batch["max_phrase_num"], seq_length + 1)
+    if has("max_tokens"):                                      # dynamic padding: decoder positions past the longest caption are skipped
+        plan.max_tokens = XETrainer._bucket(batch["max_tokens"], seq_length)
+    if not (has("token_rows") and has("max_tokens")):
+        return plan
+    plan.token_rows, plan.criterion = batch["token_rows"], "compact"      # project only the real tokens' rows onto the vocabulary
+    if not has("row_cap"):
+        return plan
+    # ... and run the decoder on those rows only.  add_token_rows pads the list to a multiple of 256: fewer than 256 rows at its end belong to no caption
+    plan.unpadded = (batch["row_start"], batch["row_count"], batch["row_cap"], batch["row_pos"], 256)
+    if not has("pair_src"):
+        plan.streams = streams
+        return plan
+    plan.paired = (batch["pair_start"], batch["pair_count"], batch["pair_src"], batch["pair_na"], 256)
+    plan.pick_labels, plan.criterion = batch["pair_labels"], "paired"     # the criterion's token labels: picked inside the forward
+    if has("prep_tok2") and not has("att_masks") and glat_p < 0:
+        plan.paired_inputs = {k[5:]: batch[k] for k in XETrainer._OPT_KEYS if k.startswith("prep_")}
+    return plan
+
+
 class XETrainer:
     """One XE optimisation step of the UIC model per ``step()`` call.
 
@@ -422,25 +453,13 @@ class XETrainer:
             g2.replay()
         return loss, parts
 
-    def _backward_stage2(self, stage2) -> None:
-        """The encoder's part of the backward (see xe.forward_uic, split_memory) and its weight gradients."""
+    def _backward_stage2(self, stage2, end: bool = False) -> None:
+        """The encoder's part of the backward (see xe.forward_uic, split_memory) and its weight gradients.  ``end``: it closes an eager step."""
         from . import xe
-        armed = self.ops is not None and self.model.train_dtype == torch.bfloat16
-        if armed:
-            xe._WEIGHTS["provider"] = self.ops
-        if self.grouped_dw:
-            xe._DEFER["list"] = []
-        try:
-            self._arm_dw_stream()
+        with self._armed(prepare=False, end=end):
             torch.autograd.backward(stage2["memory"], stage2["memory_detached"].grad)
             xe.flush_weight_grads_aside(final=True)
             xe.join_weight_grads()
-        finally:
-            xe._DEFER["list"] = None
-            xe._DEFER["side"] = None
-            xe._DEFER["held"] = []
-            if armed:
-                xe._WEIGHTS["provider"] = None
         stage2.clear()
 
     def _forward_backward_eager(self, batch: Dict[str, torch.Tensor], glat_p: float = -1.0, dense=None, between=None):
@@ -448,90 +467,67 @@ class XETrainer:
         are final (eager mode); a dict = stage 1 only, the split tensors are left in it (the captured form: _replay runs stage 2)."""
         from . import xe
         self.bucket.zero_grad()
-        armed = self.ops is not None and self.model.train_dtype == torch.bfloat16
-        if armed:
-            if not self._capturing():
-                self.ops.refresh_if_stale()
-            self.ops.launch_transposes()
-            xe._WEIGHTS["provider"] = self.ops
-        if self.grouped_dw:
-            xe._DEFER["list"] = []                             # weight gradients: grouped launches beside / after backward
-            self._arm_dw_stream()
-        try:
-            stage2 = between if isinstance(between, dict) else ({} if between is not None and dense is None else None)
+        stage2 = between if isinstance(between, dict) else ({} if between is not None and dense is None else None)
+        two_stage = stage2 is not None and not isinstance(between, dict)      # (eager: stage 2 runs here, and ends the step)
+        with self._armed(end=not two_stage):
             out = self._forward_backward_armed(batch, glat_p, dense, stage2)
             xe.flush_weight_grads_aside(final=True)
             xe.join_weight_grads()
-            if stage2 is not None and not isinstance(between, dict):
-                between()
-                if armed:
-                    xe._WEIGHTS["provider"] = None
-                xe._DEFER["list"] = None
-                self._backward_stage2(stage2)
-            elif between is not None and not isinstance(between, dict):
-                between()                                      # (a dense step has no split: the whole gradient is final here)
-            return out
-        finally:
-            xe._DEFER["list"] = None
-            xe._DEFER["side"] = None
-            xe._DEFER["held"] = []
-            if armed:
-                xe._WEIGHTS["provider"] = None
-                self.ops.end_step()
+        if two_stage:
+            between()
+            self._backward_stage2(stage2, end=True)
+        elif between is not None and not isinstance(between, dict):
+            between()                                          # (a dense step has no split: the whole gradient is final here)
+        return out
 
-    def _arm_dw_stream(self) -> None:
-        """Weight-gradient launches go beside the backward on a stream of their own, `dw_every` problems at a time (xe._DEFER).  Eager steps
-        only: a captured step keeps them on the capture stream (see the forward's side streams in _forward_backward_armed)."""
+    @contextlib.contextmanager
+    def _armed(self, prepare: bool = True, end: bool = True, dw_aside: bool = True):
+        """The one place that arms a forward + backward and disarms it however it ends (xe.step_state).  bf16 mode: ``prepare`` brings the
+        weights' bf16 operands up to date and transposes them in one launch first, ``end`` lets matrices asked for the first time join that
+        launch afterwards (a two-stage backward prepares in stage 1 and ends in stage 2).  ``dw_aside``: with `dw_every` > 0 the weight-gradient
+        launches go beside the backward on a stream of their own, `dw_every` problems at a time -- eager steps only: a captured step keeps
+        them on the capture stream (see the forward's side streams in _forward_backward_armed)."""
         from . import xe
-        if self.dw_every > 0 and self.grouped_dw and not self._capturing():
+        ops = self.ops if self.ops is not None and self.model.train_dtype == torch.bfloat16 else None
+        if ops is not None and prepare:
+            if not self._capturing():
+                ops.refresh_if_stale()
+            ops.launch_transposes()
+        side = None
+        if dw_aside and self.dw_every > 0 and self.grouped_dw and not self._capturing():
             if self._dw_stream is None:
                 self._dw_stream = torch.cuda.Stream()
-            xe._DEFER["side"], xe._DEFER["every"], xe._DEFER["held"] = self._dw_stream, self.dw_every, []
+            side = self._dw_stream
+        try:
+            with xe.step_state(weights=ops, defer=self.grouped_dw, side=side, every=self.dw_every):
+                yield
+        finally:
+            if ops is not None and end:
+                ops.end_step()
 
     def _forward_backward_armed(self, batch, glat_p, dense=None, stage2=None):
         from . import xe
-        if stage2 is not None:
-            xe.HINTS["split_memory"] = stage2
         fc = batch.get("fc_feats")
         if fc is None:
             fc = torch.zeros(batch["att_feats"].shape[0], 0, device=batch["att_feats"].device)
-        if batch.get("max_phrase_num") is not None:            # known on the host since the collate: spares the forward a device read
-            xe.HINTS["max_phrase_num"] = self._bucket(batch["max_phrase_num"], self.model.cfg.seq_length + 1)
-        if batch.get("max_tokens") is not None:                # dynamic padding: decoder positions past the longest caption are skipped
-            xe.HINTS["max_tokens"] = self._bucket(batch["max_tokens"], self.model.cfg.seq_length)
-        compact = batch.get("token_rows") is not None and batch.get("max_tokens") is not None
-        if getattr(self.model, "ss_prob", 0.0) > 0 or dense:   # scheduled sampling: the SA branch follows the model's own layout, not the
-            compact = False                                    # loader's -- no row lists, the reference's dense criterion (as self_dis / drop_worst)
-            xe.HINTS.pop("max_phrase_num", None); xe.HINTS.pop("max_tokens", None)
-        if compact:                                            # project only the real tokens' rows onto the vocabulary
-            xe.HINTS["token_rows"] = batch["token_rows"]
-            if batch.get("row_cap") is not None:               # ... and run the decoder on those rows only
-                # add_token_rows pads the list to a multiple of 256: fewer than 256 rows at its end belong to no caption
-                xe.HINTS["unpadded"] = (batch["row_start"], batch["row_count"], batch["row_cap"], batch["row_pos"], 256)
-                # (eager steps only: replaying a step captured with branches on side streams -- these, or the weight-gradient stream of
-                # _arm_dw_stream -- crashed the HIP runtime with a host-side segmentation fault inside the graph launch, though every dependency
-                # was recorded inside the capture; a captured step keeps its work on the capture stream: same results, no overlap)
-                xe.HINTS.pop("streams", None)
-                if self._side is not None and xe._WEIGHTS["provider"] is not None and self.ops._tables and not self.ops._pending and not self._capturing():
-                    xe.HINTS["streams"] = self._side
-        paired = compact and batch.get("row_cap") is not None and batch.get("pair_src") is not None
-        if paired:
-            xe.HINTS["paired"] = (batch["pair_start"], batch["pair_count"], batch["pair_src"], batch["pair_na"], 256)
-            xe.HINTS["pick_labels"] = batch["pair_labels"]      # the criterion's token labels: picked inside the forward
-            if batch.get("prep_tok2") is not None and batch.get("att_masks") is None and glat_p < 0:
-                xe.HINTS["paired_inputs"] = {k[5:]: batch[k] for k in self._OPT_KEYS if k.startswith("prep_")}
-            xe.HINTS.pop("streams", None)
-        forked = xe.HINTS.get("streams") is not None
+        # (side streams for eager steps only: replaying a step captured with branches on side streams -- these, or the weight-gradient stream
+        # of _armed -- crashed the HIP runtime with a host-side segmentation fault inside the graph launch, though every dependency
+        # was recorded inside the capture; a captured step keeps its work on the capture stream: same results, no overlap)
+        streams = None
+        if self._side is not None and xe._WEIGHTS["provider"] is not None and self.ops._tables and not self.ops._pending and not self._capturing():
+            streams = self._side
+        plan = step_plan(batch, self.model.cfg.seq_length, glat_p=glat_p, dense=dense, scheduled_sampling=getattr(self.model, "ss_prob", 0.0) > 0,
+                         streams=streams, stage2=stage2)
         outs = self.model(fc, batch["att_feats"], batch["labels"], batch.get("att_masks"), batch["phrase_num"], batch["phrase_length"],
                           batch["phrase_syn"], batch["extend_phrase_syn_seq"], batch["extend_phrase_seq"], batch["extend_phrase_seq_mask"],
-                          glat_p)
-        if paired:
+                          glat_p, plan=plan)
+        if plan.criterion == "paired":
             loss, parts = xe.criterion_uic_compact(outs, batch["phrase_num"], batch["phrase_length"], batch["phrase_syn"],
                                                    batch["pair_labels"], (batch["pair_w_sa"], batch["pair_w_na"]))
-        elif compact:
+        elif plan.criterion == "compact":
             loss, parts = xe.criterion_uic_compact(outs, batch["phrase_num"], batch["phrase_length"], batch["phrase_syn"],
                                                    batch["token_labels"], batch["token_weight"])
-        elif dense == "drop_worst":
+        elif plan.criterion == "drop_worst":
             per_cap, _ = xe.criterion_uic(outs, batch["phrase_num"], batch["phrase_length"], batch["phrase_syn"], batch["labels"], reduction="none",
                                           self_dis=self.self_dis)
             import torch.distributed as dist
@@ -553,7 +549,7 @@ class XETrainer:
             loss, parts = xe.criterion_uic(outs, batch["phrase_num"], batch["phrase_length"], batch["phrase_syn"], batch["labels"],
                                            self_dis=self.self_dis)
         loss.backward()
-        if forked:
+        if plan.streams is not None:
             # the kernels accumulate parameter gradients themselves, so autograd sees no leaf on the side streams and does not
             # join them at the end of backward(): do it here (the optimiser, or the end of a graph capture, comes next)
             main = torch.cuda.current_stream()
@@ -562,7 +558,7 @@ class XETrainer:
         return loss.detach(), [p.detach() for p in parts]
 
     def add_token_rows(self, batch: Dict[str, torch.Tensor], host_batch) -> Dict[str, torch.Tensor]:
-        """Adds ``token_rows`` / ``token_labels`` / ``token_weight`` (see xe.HINTS) to a device batch from the host copy the
+        """Adds ``token_rows`` / ``token_labels`` / ``token_weight`` (see xe.StepPlan) to a device batch from the host copy the
         collate produced: the flat (caption, position) indices of the real tokens under THIS trainer's bucketing of
         ``max_tokens``, zero-padded to a multiple of 256 so that a handful of lengths covers a data stream."""
         import numpy as np
@@ -863,16 +859,8 @@ class XETrainer:
             step_word.fill_(self._fwd_calls)
         base = int(getattr(model.opt, "seed", 0)) << 32
         seed = base if step_word is not None else base + self._fwd_calls
-        armed = self.ops is not None and model.train_dtype == torch.bfloat16
         self.bucket.zero_grad()
-        if armed:
-            self.ops.refresh_if_stale()
-            self.ops.launch_transposes()
-            xe._WEIGHTS["provider"] = self.ops
-        if self.grouped_dw:
-            xe._DEFER["list"] = []
         P = xe.Params(model)
-        pos = torch.arange(S, device=dev)[None]
 
         shared: dict = {}                                       # the encoder's memory and the cross K|V of the tape-free per-phrase forwards (same in each of them)
 
@@ -880,12 +868,7 @@ class XETrainer:
             return xe.sampled_logprobs_prepared(P, cfg, att_feats if feats is None else feats, att_masks, prep, sample_n=sample_n, training=model.training, seed=seed,
                                                 compute_dtype=model.train_dtype, step_word=step_word, reuse=reuse)
 
-        # The tape-free per-phrase forwards as TWO captured graphs per input signature (graph-mode trainers: the dropout step lives in a device word, so a replay
-        # draws this step's masks): A = encoder + decoder (the step's first forward: fills the memory / cross K|V the others share), B = decoder only.  ~250
-        # launches per forward become one replay: 1.6 -> ~0.7 ms each, twelve to fourteen times per step.
-        fwd_graphs = None
-        if self.graph and att_masks is None and step_word is not None and not self._capturing() and getattr(model.opt, "bofi_rl_graph_forwards", True):
-            fwd_graphs = self._rl_forward_graphs(rows_of, att_feats, N, S, dev, sample_n)
+        fwd_graphs = None                                       # (set below, once the step is armed)
 
         def rows_graphed(seq, out, prep_na, first):
             # (the graphs read the words so far and the engine's layout from static buffers and collate them on the device: no host round trip per phrase)
@@ -913,7 +896,13 @@ class XETrainer:
             hip.check(hip.lib().bofi_rl_take_draws(hip.ptr(lpf), hip.ptr(tok), hip.ptr(plen), n_, s_, V, int(p0), int(p1), hip.ptr(seq), hip.ptr(drawn), hip.ptr(mask),
                                                    hip.stream_ptr()), "bofi_rl_take_draws")
 
-        try:
+        with self._armed(dw_aside=False):                         # (from the first tape-free forward to the gradient pass's weight gradients)
+            pos = torch.arange(S, device=dev)[None]
+            # The tape-free per-phrase forwards as TWO captured graphs per input signature (graph-mode trainers: the dropout step lives in a device word, so a replay
+            # draws this step's masks): A = encoder + decoder (the step's first forward: fills the memory / cross K|V the others share), B = decoder only.  ~250
+            # launches per forward become one replay: 1.6 -> ~0.7 ms each, twelve to fourteen times per step.
+            if self.graph and att_masks is None and step_word is not None and not self._capturing() and getattr(model.opt, "bofi_rl_graph_forwards", True):
+                fwd_graphs = self._rl_forward_graphs(rows_of, att_feats, N, S, dev, sample_n)
             prep_na = xe.rl_prepare_naic_device(cfg, na["phrase_length"], na["phrase_syn"], strict_q1=model.strict_reference)
             seq_s = torch.zeros(N, S, dtype=torch.int64, device=dev)
             seq_n = torch.zeros(N, S, dtype=torch.int64, device=dev)
@@ -966,11 +955,6 @@ class XETrainer:
                 loss.backward()
                 xe.flush_weight_grads()
                 loss, m1, m2 = loss.detach(), r1.mean(), r2.mean()
-        finally:
-            xe._DEFER["list"] = None
-            if armed:
-                xe._WEIGHTS["provider"] = None
-                self.ops.end_step()
         if replayed:
             # the gradient pass as the captured graph of the fast form (the same forward under the same seed and dropout masks + new_self_critical + backward):
             # its log-probs at the drawn tokens come back in the graph's "picked" buffers
@@ -1035,15 +1019,7 @@ class XETrainer:
         self.bucket.zero_grad()
         step_word = getattr(self, "_step_word", None)
         base = int(getattr(model.opt, "seed", 0)) << 32
-        armed = self.ops is not None and model.train_dtype == torch.bfloat16
-        if armed:
-            if not self._capturing():
-                self.ops.refresh_if_stale()
-            self.ops.launch_transposes()
-            xe._WEIGHTS["provider"] = self.ops
-        if self.grouped_dw:
-            xe._DEFER["list"] = []
-        try:
+        with self._armed(dw_aside=False):
             lp_saic, lp_naic = xe.sampled_logprobs_prepared(xe.Params(model), model.cfg, b["att_feats"], att_masks, b, sample_n=sample_n,
                                                             training=model.training,
                                                             seed=base if step_word is not None else base + self._fwd_calls,
@@ -1059,11 +1035,6 @@ class XETrainer:
                 loss = loss + xe.rl_kl_term(lp_naic, lp_saic, b["seq_saic"])
             loss.backward()
             xe.flush_weight_grads()
-        finally:
-            xe._DEFER["list"] = None
-            if armed:
-                xe._WEIGHTS["provider"] = None
-                self.ops.end_step()
         return loss.detach(), r1.mean(), r2.mean()
 
     def _rl_replay(self, b, sample_n):

@@ -354,9 +354,10 @@ class TransformerModel(nn.Module):
         return (*outs, end - start)
 
     def _forward(self, fc_feats, att_feats, seq, att_masks=None, phrase_num=None, phrase_length=None, phrase_syn=None,
-                 extend_phrase_syn_seq=None, extend_phrase_seq=None, extend_phrase_seq_mask=None, glat_p=-1.0):
+                 extend_phrase_syn_seq=None, extend_phrase_seq=None, extend_phrase_seq_mask=None, glat_p=-1.0, *, plan=None):
         """TransformerModel.py:1713-1724,1759-1775 (train_mode 'UIC'; ss_prob > 0: the scheduled-sampling form): the six log-prob tensors, with the
-        autograd tape running over the HIP kernels (boficap_amd/xe.py).  float32."""
+        autograd tape running over the HIP kernels (boficap_amd/xe.py).  float32.  ``plan``: an xe.StepPlan (a trainer's; the scheduled-sampling
+        form follows the model's own layout and takes none)."""
         from . import xe
         if phrase_num is None:
             raise hip.BofiHipError("the UIC forward needs the phrase tensors of the loader (dataloader.py:343-428)")
@@ -372,7 +373,7 @@ class TransformerModel(nn.Module):
                                      training=self.training, seed=seed, compute_dtype=self.train_dtype, step_word=step_word)
         return xe.forward_uic(xe.Params(self), self.cfg, att_feats, seq, att_masks, phrase_num, phrase_length, phrase_syn,
                               extend_phrase_syn_seq, extend_phrase_seq, extend_phrase_seq_mask, glat_p=float(glat_p),
-                              training=self.training, seed=seed, compute_dtype=self.train_dtype, step_word=step_word)
+                              training=self.training, seed=seed, compute_dtype=self.train_dtype, step_word=step_word, plan=plan)
 
 
 def setup(opt):

@@ -11,8 +11,11 @@ the buffers, the tape and the parameter tensors.  Differences in STRUCTURE from 
     grown per caption) run as ONE batched pass over N x Pmax virtual [LEN] queries with per-query key counts,
     because only row 0 of each pass is ever read (:375);
   * every mask on this path is a key prefix per query row, so masks travel as int32 key counts;
-  * with the collate's row lists (HINTS) the decoder runs over the captions' real positions only and the SA and NA branch
+  * with the collate's row lists (StepPlan) the decoder runs over the captions' real positions only and the SA and NA branch
     share one bound pass and one decoder pass (_fill_unpadded, _forward_paired).
+
+What a caller knows about the batch is an argument (``forward_uic(..., plan=StepPlan(...))``; no plan: the reference's dense forward);
+what lasts for one forward + backward is set by ``step_state`` and put back when it ends.
 
 float32 is the parity mode.  In bf16 mode (GEMM operands bf16, everything else float32) the module keeps a few per-step
 side tables, all cleared by the next forward:
@@ -27,12 +30,14 @@ side tables, all cleared by the next forward:
                  reader of a placeholder raises (_real, _operand); placeholders are only created where the tensor has one
                  consumer, and the entries keep them alive so that a pointer names one tensor for the whole step;
   _WEIGHTS       the trainer's per-step bf16 weight operands (trainer.WeightOperands);
-  _DEFER         weight-gradient GEMMs put off to one grouped launch after backward (flush_weight_grads).
+  _DEFER         weight-gradient GEMMs put off to grouped launches (flush_weight_grads).
+_WEIGHTS and _DEFER are the storage behind step_state, which alone arms and restores them.  HINTS holds two test hooks only.
 """
 from __future__ import annotations
 
 import ctypes as C
 import contextlib
+from dataclasses import dataclass
 from typing import Optional
 
 import torch
@@ -41,16 +46,6 @@ from torch.autograd import Function
 from . import hip
 
 F32 = hip.DT_F32
-
-
-_LIB = None
-
-
-def _lib():
-    global _LIB
-    if _LIB is None:
-        _LIB = hip.lib()
-    return _LIB
 
 
 def _chk(rc, what):
@@ -101,6 +96,20 @@ _WEIGHTS = {"provider": None}
 _DEFER = {"list": None, "side": None, "every": 0, "held": []}
 
 
+@contextlib.contextmanager
+def step_state(weights=None, defer: bool = False, side=None, every: int = 0):
+    """The state of one forward + backward: ``weights`` the trainer's bf16 operands (_WEIGHTS); ``defer``: weight-gradient GEMMs collected for
+    grouped launches, with ``side`` on that stream every ``every`` problems (_DEFER).  What it found comes back however the step ends."""
+    found = _WEIGHTS["provider"], dict(_DEFER)
+    _WEIGHTS["provider"] = weights
+    _DEFER.update(list=[] if defer else None, side=side, every=every, held=[])
+    try:
+        yield
+    finally:
+        _WEIGHTS["provider"] = found[0]
+        _DEFER.update(found[1])
+
+
 def flush_weight_grads():
     """Run the deferred weight-gradient GEMMs (bofi_gemm_tn_grouped) on the current stream and forget them."""
     todo = _DEFER["list"]
@@ -109,7 +118,7 @@ def flush_weight_grads():
     n = len(todo)
     vp, ci = C.c_void_p * n, C.c_int * n
     col = lambda k: [t[k] for t in todo]
-    rc = _lib().bofi_gemm_tn_grouped(
+    rc = hip.lib().bofi_gemm_tn_grouped(
         n, vp(*[hip.ptr(t) for t in col(0)]), ci(*col(1)), ci(*col(1)), vp(*[hip.ptr(t) for t in col(2)]), ci(*col(3)), ci(*col(3)),
         vp(*[hip.ptr(t) for t in col(4)]), ci(*col(5)), ci(*col(6)), ci(*col(7)), ci(*col(8)),
         vp(*[hip.ptr(t) for t in col(9)]), hip.stream_ptr())
@@ -164,11 +173,11 @@ def _gemm(x, ldx, w, bias, residual, y, M, N, K, relu=0, row_len=None, rpg=0, dr
     if drop is not None or y2 is not None:
         if drop is not None and row_len is not None:
             raise hip.BofiHipError("dropout in the epilogue is not combined with row_len")
-        _chk(_lib().bofi_linear_ex(hip.ptr(x), code, ldx, hip.ptr(w), code, hip.ptr(bias), hip.ptr(residual), N if residual is not None else 0,
+        _chk(hip.lib().bofi_linear_ex(hip.ptr(x), code, ldx, hip.ptr(w), code, hip.ptr(bias), hip.ptr(residual), N if residual is not None else 0,
                                    hip.ptr(y), F32, N, M, N, K, relu, hip.ptr(row_len), rpg, drop[0] if drop else 0.0, drop[1] if drop else 0,
                                    hip.ptr(drop[2]) if drop else None, hip.ptr(y2), N, hip.stream_ptr()), "bofi_linear_ex")
         return
-    _chk(_lib().bofi_linear(hip.ptr(x), code, ldx, hip.ptr(w), code, hip.ptr(bias), hip.ptr(residual), N if residual is not None else 0,
+    _chk(hip.lib().bofi_linear(hip.ptr(x), code, ldx, hip.ptr(w), code, hip.ptr(bias), hip.ptr(residual), N if residual is not None else 0,
                             hip.ptr(y), F32, N, M, N, K, relu, hip.ptr(row_len), rpg, hip.stream_ptr()), "bofi_linear")
 
 
@@ -208,7 +217,7 @@ def _operand(x, M, N, dt, cache=True, colsum=None, relu_y=None, drop=None):
         y[:, :N] = x
     else:
         y = torch.empty(M, Np, dtype=torch.bfloat16, device=x.device)
-        _chk(_lib().bofi_cast_bf16(hip.ptr(x), N, hip.ptr(y), Np, M, N, hip.ptr(colsum), hip.ptr(relu_y),
+        _chk(hip.lib().bofi_cast_bf16(hip.ptr(x), N, hip.ptr(y), Np, M, N, hip.ptr(colsum), hip.ptr(relu_y),
                                    drop[0] if drop else 0.0, drop[1] if drop else 0, hip.ptr(drop[2]) if drop else None, hip.stream_ptr()),
              "bofi_cast_bf16")
     if cache and colsum is None:
@@ -229,7 +238,7 @@ def _transposed(x, M, N, dt, colsum=None, cache=True):
         if xt is not None:
             return xt, Mp
     xt = torch.empty(N, Mp, dtype=dt, device=x.device)
-    _chk(_lib().bofi_transpose_pad(hip.ptr(x), N, hip.ptr(xt), F32 if dt == torch.float32 else hip.DT_BF16, M, N, Mp, hip.ptr(colsum),
+    _chk(hip.lib().bofi_transpose_pad(hip.ptr(x), N, hip.ptr(xt), F32 if dt == torch.float32 else hip.DT_BF16, M, N, Mp, hip.ptr(colsum),
                                    hip.stream_ptr()), "bofi_transpose_pad")
     if cache and colsum is None:
         _STEP_CACHE[key] = (x, xt)
@@ -292,7 +301,7 @@ class LinearFn(Function):
         N = w.shape[0]
         dt = ctx.dt
         dy = _need(dy, "linear dy")
-        L, st = _lib(), hip.stream_ptr()
+        L, st = hip.lib(), hip.stream_ptr()
         dz = dy
         if ctx.relu and dt != torch.bfloat16:          # zeroed rows (row_len) have y == 0 and drop out here too
             dz = torch.empty_like(dy)
@@ -387,10 +396,10 @@ class LayerNormFn(Function):
         if gemm_only and _COMPUTE["dtype"] == torch.bfloat16 and d % 64 == 0:
             # every consumer is a GEMM: write the normalised rows as bf16 only; y stays an unfilled placeholder
             yb = torch.empty(rows, d, dtype=torch.bfloat16, device=x.device)
-            _chk(_lib().bofi_layernorm(hip.ptr(x), hip.ptr(gain), hip.ptr(bias), hip.ptr(yb), hip.DT_BF16, rows, d, hip.stream_ptr()), "bofi_layernorm")
+            _chk(hip.lib().bofi_layernorm(hip.ptr(x), hip.ptr(gain), hip.ptr(bias), hip.ptr(yb), hip.DT_BF16, rows, d, hip.stream_ptr()), "bofi_layernorm")
             _register_shadow(y, yb, only=True)
         else:
-            _chk(_lib().bofi_layernorm(hip.ptr(x), hip.ptr(gain), hip.ptr(bias), hip.ptr(y), F32, rows, d, hip.stream_ptr()), "bofi_layernorm")
+            _chk(hip.lib().bofi_layernorm(hip.ptr(x), hip.ptr(gain), hip.ptr(bias), hip.ptr(y), F32, rows, d, hip.stream_ptr()), "bofi_layernorm")
         ctx.gg, ctx.gb = gg, gb
         prod = _STEP_CACHE.get(("prod", x.data_ptr()))
         ctx.prod_drop = prod[1] if (prod is not None and prod[0] is x and _COMPUTE["dtype"] == torch.bfloat16 and d in (512, 128)) else None
@@ -413,11 +422,11 @@ class LayerNormFn(Function):
         if pd is not None:
             # x came out of a linear with epilogue dropout: also write that linear's dz (mask applied, bf16)
             dz = torch.empty(rows, d, dtype=torch.bfloat16, device=x.device)
-            _chk(_lib().bofi_layernorm_bwd_ex(hip.ptr(x), hip.ptr(gain), hip.ptr(dy), hip.ptr(add), hip.ptr(dx), hip.ptr(dg), hip.ptr(db), rows, d,
+            _chk(hip.lib().bofi_layernorm_bwd_ex(hip.ptr(x), hip.ptr(gain), hip.ptr(dy), hip.ptr(add), hip.ptr(dx), hip.ptr(dg), hip.ptr(db), rows, d,
                                               hip.ptr(dz), pd[0], pd[1], hip.ptr(pd[2]), hip.stream_ptr()), "bofi_layernorm_bwd_ex")
             _STEP_CACHE[("gop", dx.data_ptr())] = (dx, dz, pd)
         else:
-            _chk(_lib().bofi_layernorm_bwd(hip.ptr(x), hip.ptr(gain), hip.ptr(dy), hip.ptr(add), hip.ptr(dx), hip.ptr(dg), hip.ptr(db), rows, d,
+            _chk(hip.lib().bofi_layernorm_bwd(hip.ptr(x), hip.ptr(gain), hip.ptr(dy), hip.ptr(add), hip.ptr(dx), hip.ptr(dg), hip.ptr(db), rows, d,
                                            hip.stream_ptr()), "bofi_layernorm_bwd")
         return (dx, None, None, None, None, None) if direct else (dx, dg, db, None, None, None)
 
@@ -478,7 +487,7 @@ class AttentionFn(Function):
             # ``out`` stays an unfilled placeholder
             out = _empty(qbuf, qbuf.shape[0], d)              # placeholder: consumers read the bf16 copy
             ob = torch.empty(qbuf.shape[0], d, dtype=torch.bfloat16, device=qbuf.device)      # (unpadded rows: the kernel clears the trailing rows)
-            _chk(_lib().bofi_attention_ex(_off(qs, qoff), ldq, _off(kvs, koff), ldk, _off(kvs, voff), ldk, hip.ptr(ob), d, hip.DT_BF16, B, H,
+            _chk(hip.lib().bofi_attention_ex(_off(qs, qoff), ldq, _off(kvs, koff), ldk, _off(kvs, voff), ldk, hip.ptr(ob), d, hip.DT_BF16, B, H,
                                           Lq, Lk, kdiv, hip.ptr(klen), klen_sb, klen_sq, klen_bias, drop[0] if drop else 0.0,
                                           drop[1] if drop else 0, hip.ptr(drop[2]) if drop else None, sp[0], sp[1], sp[2],
                                           qbuf.shape[0] if seg is not None else 0, hip.stream_ptr()),
@@ -489,7 +498,7 @@ class AttentionFn(Function):
             _real(qbuf, "attention q"), _real(kvbuf, "attention kv")
             out = _rows_alloc((qbuf.shape[0], d), torch.float32, qbuf.device, seg is not None, tail)
             drop = None                                        # dropout(p_attn) is built into the bf16 kernels only
-            _chk(_lib().bofi_attention_ex(_off(qbuf, qoff), ldq, _off(kvbuf, koff), ldk, _off(kvbuf, voff), ldk, hip.ptr(out), d, F32, B, H,
+            _chk(hip.lib().bofi_attention_ex(_off(qbuf, qoff), ldq, _off(kvbuf, koff), ldk, _off(kvbuf, voff), ldk, hip.ptr(out), d, F32, B, H,
                                           Lq, Lk, kdiv, hip.ptr(klen), klen_sb, klen_sq, klen_bias, 0.0, 0, None, sp[0], sp[1], sp[2], 0,
                                           hip.stream_ptr()), "bofi_attention_ex")
             ctx.save_for_backward(qbuf, kvbuf)
@@ -534,14 +543,14 @@ class AttentionFn(Function):
         if ctx.mfma:
             F32c, B16c = F32, hip.DT_BF16
             kv_out = dq_out if ctx.same else dkv
-            _chk(_lib().bofi_attention_bwd_mfma(_off(qbuf, qoff), ldq, _off(kvbuf, koff), ldk, _off(kvbuf, voff), ldk, hip.dtype_code(qbuf),
+            _chk(hip.lib().bofi_attention_bwd_mfma(_off(qbuf, qoff), ldq, _off(kvbuf, koff), ldk, _off(kvbuf, voff), ldk, hip.dtype_code(qbuf),
                                                 hip.ptr(dout), H * 64, _off(dq_out, qoff), ldq, _off(kv_out, koff), _off(kv_out, voff), ldk,
                                                 B16c if qb16 else F32c, B16c if (qb16 and ctx.same) else F32c, B, H, Lq, Lk,
                                                 kdiv, hip.ptr(ctx.klen), sb, sq, bias, ctx.drop[0] if ctx.drop else 0.0,
                                                 ctx.drop[1] if ctx.drop else 0, hip.ptr(ctx.drop[2]) if ctx.drop else None, sp[0], sp[1], sp[2],
                                                 qbuf.shape[0] if (ctx.seg is not None and fits) else 0, hip.stream_ptr()), "bofi_attention_bwd_mfma")
             return (dq, None if ctx.same else dkv) + (None,) * 15
-        _chk(_lib().bofi_attention_bwd(_off(qbuf, qoff), ldq, _off(kvbuf, koff), ldk, _off(kvbuf, voff), ldk, hip.ptr(dout), H * 64,
+        _chk(hip.lib().bofi_attention_bwd(_off(qbuf, qoff), ldq, _off(kvbuf, koff), ldk, _off(kvbuf, voff), ldk, hip.ptr(dout), H * 64,
                                        _off(dq, qoff), _off(dkv, koff), _off(dkv, voff), B, H, Lq, Lk, kdiv, hip.ptr(ctx.klen), sb, sq, bias,
                                        sp[0], sp[1], sp[2], hip.stream_ptr()), "bofi_attention_bwd")
         return (dq, None if ctx.same else dkv) + (None,) * 15
@@ -568,7 +577,7 @@ class EmbedFn(Function):
             if t is not None and (t.dtype != torch.int64 or not t.is_contiguous() or lut is None):
                 raise hip.BofiHipError("embedding ids must be contiguous int64 with their table")
         x = _empty(ref, rows, d)
-        _chk(_lib().bofi_embed_rows(hip.ptr(lut_tok if tok is not None else None), hip.ptr(lut_syn if syn is not None else None), hip.ptr(pe),
+        _chk(hip.lib().bofi_embed_rows(hip.ptr(lut_tok if tok is not None else None), hip.ptr(lut_syn if syn is not None else None), hip.ptr(pe),
                                     hip.ptr(tok), hip.ptr(syn), hip.ptr(pos), rows, L, d, hip.ptr(x), hip.stream_ptr()), "bofi_embed_rows")
         ctx.tok, ctx.syn, ctx.g = tok, syn, (g_tok, g_syn)
         ctx.shapes = (None if lut_tok is None else lut_tok.shape, None if lut_syn is None else lut_syn.shape)
@@ -584,7 +593,7 @@ class EmbedFn(Function):
                 out.append(None)
                 continue
             g = direct if direct is not None else _zeros(dx, *shape)
-            _chk(_lib().bofi_embed_bwd(hip.ptr(dx), hip.ptr(ids), hip.ptr(g), rows, d, float(d) ** 0.5, hip.stream_ptr()), "bofi_embed_bwd")
+            _chk(hip.lib().bofi_embed_bwd(hip.ptr(dx), hip.ptr(ids), hip.ptr(g), rows, d, float(d) ** 0.5, hip.stream_ptr()), "bofi_embed_bwd")
             out.append(None if direct is not None else g)
         return out[0], out[1], None, None, None, None, None, None, None
 
@@ -603,7 +612,7 @@ class LogSoftmaxFn(Function):
         rows, V = logits.shape
         ids = torch.empty(rows, dtype=torch.int64, device=logits.device)
         if rows:
-            _chk(_lib().bofi_vocab_finalize(hip.ptr(logits), rows, V, 1, 1, None, 0, hip.ptr(ids), hip.stream_ptr()), "bofi_vocab_finalize")
+            _chk(hip.lib().bofi_vocab_finalize(hip.ptr(logits), rows, V, 1, 1, None, 0, hip.ptr(ids), hip.stream_ptr()), "bofi_vocab_finalize")
         ctx.mark_dirty(logits)
         ctx.save_for_backward(logits)
         return logits
@@ -613,7 +622,7 @@ class LogSoftmaxFn(Function):
         (y,) = ctx.saved_tensors
         dy = _need(dy, "log_softmax dy")
         dx = torch.empty_like(y)
-        _chk(_lib().bofi_logsoftmax_bwd(hip.ptr(y), hip.ptr(dy), hip.ptr(dx), y.shape[0], y.shape[1], hip.stream_ptr()), "bofi_logsoftmax_bwd")
+        _chk(hip.lib().bofi_logsoftmax_bwd(hip.ptr(y), hip.ptr(dy), hip.ptr(dx), y.shape[0], y.shape[1], hip.stream_ptr()), "bofi_logsoftmax_bwd")
         return dx
 
 
@@ -634,7 +643,7 @@ class PickLogSoftmaxFn(Function):
         labels = labels.to(torch.int64).contiguous()
         ids = torch.empty(rows, dtype=torch.int64, device=logits.device)
         if rows:
-            _chk(_lib().bofi_vocab_finalize(hip.ptr(logits), rows, V, 1, 1, None, 0, hip.ptr(ids), hip.stream_ptr()), "bofi_vocab_finalize")
+            _chk(hip.lib().bofi_vocab_finalize(hip.ptr(logits), rows, V, 1, 1, None, 0, hip.ptr(ids), hip.stream_ptr()), "bofi_vocab_finalize")
         picked = logits.gather(1, labels.unsqueeze(1)).squeeze(1)
         ctx.mark_dirty(logits)
         ctx.set_materialize_grads(False)
@@ -654,18 +663,18 @@ class PickLogSoftmaxFn(Function):
                 # dx stays an unfilled placeholder
                 Vp = (y.shape[1] + 63) // 64 * 64
                 dzb = torch.empty(y.shape[0], Vp, dtype=torch.bfloat16, device=y.device)
-                _chk(_lib().bofi_nll_bwd(hip.ptr(y), hip.ptr(labels), hip.ptr(gp), hip.ptr(dzb), hip.DT_BF16, Vp, y.shape[0], y.shape[1],
+                _chk(hip.lib().bofi_nll_bwd(hip.ptr(y), hip.ptr(labels), hip.ptr(gp), hip.ptr(dzb), hip.DT_BF16, Vp, y.shape[0], y.shape[1],
                                          hip.stream_ptr()), "bofi_nll_bwd")
                 _register_shadow(dx, dzb, only=True)
                 return dx, None, None
-            _chk(_lib().bofi_nll_bwd(hip.ptr(y), hip.ptr(labels), hip.ptr(gp), hip.ptr(dx), F32, y.shape[1], y.shape[0], y.shape[1],
+            _chk(hip.lib().bofi_nll_bwd(hip.ptr(y), hip.ptr(labels), hip.ptr(gp), hip.ptr(dx), F32, y.shape[1], y.shape[0], y.shape[1],
                                      hip.stream_ptr()), "bofi_nll_bwd")
             return dx, None, None
         dy = _need(g_logp, "log_softmax dy")
         if g_picked is not None:                               # both outputs used: fold the picked gradient into the dense one
             dy = dy.clone()
             dy.scatter_add_(1, labels.unsqueeze(1), g_picked.unsqueeze(1))
-        _chk(_lib().bofi_logsoftmax_bwd(hip.ptr(y), hip.ptr(dy), hip.ptr(dx), y.shape[0], y.shape[1], hip.stream_ptr()), "bofi_logsoftmax_bwd")
+        _chk(hip.lib().bofi_logsoftmax_bwd(hip.ptr(y), hip.ptr(dy), hip.ptr(dx), y.shape[0], y.shape[1], hip.stream_ptr()), "bofi_logsoftmax_bwd")
         return dx, None, None
 
 
@@ -684,7 +693,7 @@ class UicCriterionFn(Function):
             raise hip.BofiHipError("criterion: inconsistent shapes")
         ints = [t.to(torch.int64).contiguous() for t in (phrase_num, phrase_length, phrase_syn)]
         out = torch.empty(8, dtype=torch.float32, device=ts[0].device)
-        _chk(_lib().bofi_uic_criterion(hip.ptr(ts[0]), hip.ptr(ts[1]), hip.ptr(ts[2]), hip.ptr(ts[3]), N, Pm, c_len, c_syn, hip.ptr(ints[0]),
+        _chk(hip.lib().bofi_uic_criterion(hip.ptr(ts[0]), hip.ptr(ts[1]), hip.ptr(ts[2]), hip.ptr(ts[3]), N, Pm, c_len, c_syn, hip.ptr(ints[0]),
                                        hip.ptr(ints[1]), hip.ptr(ints[2]), L, hip.ptr(ts[4]), hip.ptr(ts[5]), hip.ptr(ts[6]), T, hip.ptr(out),
                                        hip.stream_ptr()), "bofi_uic_criterion")
         ctx.save_for_backward(*ts, *ints, out)
@@ -699,7 +708,7 @@ class UicCriterionFn(Function):
         N, Pm, c_len, c_syn, L, T = ctx.dims
         g = _need(g_loss, "criterion gradient")
         d = [torch.empty_like(t) for t in (sa_len, sa_syn, na_len, na_syn, picked)]
-        _chk(_lib().bofi_uic_criterion_bwd(hip.ptr(sa_len), hip.ptr(sa_syn), hip.ptr(na_len), hip.ptr(na_syn), N, Pm, c_len, c_syn, hip.ptr(pnum),
+        _chk(hip.lib().bofi_uic_criterion_bwd(hip.ptr(sa_len), hip.ptr(sa_syn), hip.ptr(na_len), hip.ptr(na_syn), N, Pm, c_len, c_syn, hip.ptr(pnum),
                                            hip.ptr(plen), hip.ptr(psyn), L, hip.ptr(picked), hip.ptr(w_sa), hip.ptr(w_na), T, hip.ptr(g), hip.ptr(out),
                                            hip.ptr(d[0]), hip.ptr(d[1]), hip.ptr(d[2]), hip.ptr(d[3]), hip.ptr(d[4]), hip.stream_ptr()),
              "bofi_uic_criterion_bwd")
@@ -716,7 +725,7 @@ def greedy_ids(logits):
     """argmax over the last dim (first maximal index), no tape; the logits are consumed."""
     rows, V = logits.shape
     ids = torch.empty(rows, dtype=torch.int64, device=logits.device)
-    _chk(_lib().bofi_vocab_finalize(hip.ptr(logits), rows, V, 1, 0, None, 0, hip.ptr(ids), hip.stream_ptr()), "bofi_vocab_finalize")
+    _chk(hip.lib().bofi_vocab_finalize(hip.ptr(logits), rows, V, 1, 0, None, 0, hip.ptr(ids), hip.stream_ptr()), "bofi_vocab_finalize")
     return ids
 
 
@@ -727,7 +736,7 @@ class DropoutFn(Function):
     def forward(ctx, x, residual, p, seed, step_word=None):
         x = _real(_need(x, "dropout x"), "dropout x")
         y = torch.empty_like(x)
-        _chk(_lib().bofi_dropout(hip.ptr(x), hip.ptr(residual), hip.ptr(y), x.numel(), p, seed, hip.ptr(step_word), hip.stream_ptr()), "bofi_dropout")
+        _chk(hip.lib().bofi_dropout(hip.ptr(x), hip.ptr(residual), hip.ptr(y), x.numel(), p, seed, hip.ptr(step_word), hip.stream_ptr()), "bofi_dropout")
         ctx.p, ctx.seed, ctx.has_r, ctx.step_word = p, seed, residual is not None, step_word
         return y
 
@@ -735,7 +744,7 @@ class DropoutFn(Function):
     def backward(ctx, dy):
         dy = _need(dy, "dropout dy")
         dx = torch.empty_like(dy)
-        _chk(_lib().bofi_dropout(hip.ptr(dy), None, hip.ptr(dx), dy.numel(), ctx.p, ctx.seed, hip.ptr(ctx.step_word), hip.stream_ptr()), "bofi_dropout")
+        _chk(hip.lib().bofi_dropout(hip.ptr(dy), None, hip.ptr(dx), dy.numel(), ctx.p, ctx.seed, hip.ptr(ctx.step_word), hip.stream_ptr()), "bofi_dropout")
         return dx, (dy if ctx.has_r else None), None, None, None
 
 
@@ -1006,14 +1015,33 @@ def bound_teacher_forced_dense(P, cfg, drop, x_in, memory, kv_cache, N, L, R, sp
     return len_lp.view(N, Pm, -1), syn_lp.view(N, Pm, -1)
 
 
-# Host-side facts about the batch the caller already knows (set by the trainer from the collate's output) so that the
-# forward pass needs no device->host read: {"max_phrase_num": int, "max_tokens": int}.  Consumed (cleared) by the next
-# forward_uic.  "max_tokens" (the longest caption of the batch) additionally lets the two decoder passes and the vocabulary
-# projection run over that many positions instead of seq_length: positions past a caption's last token are neither attended
-# by earlier ones nor counted by the criterion, so the loss and every gradient are unchanged (dynamic padding); the two token
-# tensors then come back as [N, max_tokens, V].  "token_rows" (int64 device tensor of flat indices n * max_tokens + t of the
-# real caption tokens, zero-padded to a fixed length) goes one step further for the vocabulary projection: only those rows are
-# projected, the two token tensors come back as [len(token_rows), V] (criterion_uic_compact is their criterion).
+@dataclass
+class StepPlan:
+    """What forward_uic's caller knows about the batch (trainer.step_plan, from the collate's output); all None: the reference's dense forward.
+    ``max_phrase_num`` / ``max_tokens``: host-side upper bounds, so that the forward needs no device->host read.  ``max_tokens`` (the longest
+    caption of the batch) additionally lets the two decoder passes and the vocabulary projection run over that many positions instead of
+    seq_length: positions past a caption's last token are neither attended by earlier ones nor counted by the criterion, so the loss and every
+    gradient are unchanged (dynamic padding); the two token tensors then come back as [N, max_tokens, V].  ``token_rows`` (int64 device tensor
+    of flat indices n * max_tokens + t of the real caption tokens, zero-padded to a fixed length): only those rows are projected, the two token
+    tensors come back as [len(token_rows), V] (criterion_uic_compact is their criterion).  ``unpadded`` (row_start, row_count, row_cap, row_pos,
+    granule): the decoder itself runs on those rows only (_fill_unpadded), with ``streams`` its branches on side streams.  ``paired``
+    (pair_start, pair_count, pair_src, pair_na, granule): both branches as one batch (_forward_paired), with ``pick_labels`` the criterion's
+    labels picked inside it and ``paired_inputs`` its index tensors made on the host.  ``split_memory``: the dict of a two-stage backward.
+    ``criterion``: the criterion that follows -- "paired", "compact", "dense" or "drop_worst"."""
+    max_phrase_num: Optional[int] = None
+    max_tokens: Optional[int] = None
+    token_rows: Optional[torch.Tensor] = None
+    unpadded: Optional[tuple] = None
+    streams: Optional[list] = None
+    paired: Optional[tuple] = None
+    pick_labels: Optional[torch.Tensor] = None
+    paired_inputs: Optional[dict] = None
+    split_memory: Optional[dict] = None
+    criterion: Optional[str] = None
+
+
+# Two test hooks only: "glat_uniform" -- the glancing pass's uniform draws, injected by parity tests and consumed by the next _glance_draws;
+# "ss_trace" -- what forward_uic_ss's sampling loop decided, left behind for the tests to read.
 HINTS: dict = {}
 
 
@@ -1046,9 +1074,10 @@ def bound_pass_klen(phrase_num: torch.Tensor, phrase_length: torch.Tensor, max_p
 @_scoped_compute_dtype
 def forward_uic(P, cfg, att_feats, labels, att_masks, phrase_num, phrase_length, phrase_syn, extend_phrase_syn_seq, extend_phrase_seq,
                 extend_phrase_seq_mask, *, glat_p: float = -1.0, training: bool = False, seed: Optional[int] = None,
-                compute_dtype: torch.dtype = torch.float32, step_word: Optional[torch.Tensor] = None):
+                compute_dtype: torch.dtype = torch.float32, step_word: Optional[torch.Tensor] = None, plan: Optional[StepPlan] = None):
     """The six log-prob tensors of EncoderDecoder_UIC.forward (TransformerModel.py:413-468):
-    (sa_len [N,S+1,20], sa_syn [N,S+1,10], sa_tok [N,S,V], na_len, na_syn, na_tok).  ``P``: a ``Params``."""
+    (sa_len [N,S+1,20], sa_syn [N,S+1,10], sa_tok [N,S,V], na_len, na_syn, na_tok).  ``P``: a ``Params``.  ``plan``: see StepPlan."""
+    plan = plan if plan is not None else StepPlan()
     dev = att_feats.device
     S, L, d = cfg.seq_length, cfg.seq_length + 2, cfg.d_model
     dense_bound = cfg.N_len != 1         # a deeper bounding network: whole-sequence passes (bound_teacher_forced_dense), the plain form of the step
@@ -1077,7 +1106,7 @@ def forward_uic(P, cfg, att_feats, labels, att_masks, phrase_num, phrase_length,
     spi = N // B
     drop = _Drop(cfg.dropout, cfg.drop_prob_lm, seed if training else None, step_word)
     memory = encode_memory(P, cfg, att_feats, att_len, drop)
-    split = HINTS.pop("split_memory", None)
+    split = plan.split_memory
     if split is not None:
         # two-stage backward (XETrainer, data-parallel): everything behind the encoder hangs off a DETACHED copy of its output, so that
         # loss.backward() stops there with every decoder-side gradient final -- their exchange starts while the encoder's backward
@@ -1094,21 +1123,15 @@ def forward_uic(P, cfg, att_feats, labels, att_masks, phrase_num, phrase_length,
     labels, phrase_num, phrase_length = labels.to(dev).long(), phrase_num.to(dev).long(), phrase_length.to(dev).long()
     ext_syn = extend_phrase_syn_seq.to(dev).long().contiguous()
     ext_seq = extend_phrase_seq.to(dev).long().contiguous()
-    prepared = HINTS.pop("paired_inputs", None)                # the paired step's index tensors, made by the collate on the host
-    if prepared is not None and (glat_p >= 0 or att_len is not None or HINTS.get("paired") is None):
+    prepared = plan.paired_inputs                              # the paired step's index tensors, made by the collate on the host
+    if prepared is not None and (glat_p >= 0 or att_len is not None or plan.paired is None):
         prepared = None                                        # (the glancing pass and ragged region masks take the device-side prep)
     if prepared is None:
-        klen_pass, last, Pm = bound_pass_klen(phrase_num, phrase_length, HINTS.pop("max_phrase_num", None))
+        klen_pass, last, Pm = bound_pass_klen(phrase_num, phrase_length, plan.max_phrase_num)
     else:
-        HINTS.pop("max_phrase_num", None)
         klen_pass, last, Pm = None, None, int(prepared["klen_b"].shape[1])
-    Sd = HINTS.pop("max_tokens", None)
-    Sd = S if not Sd else max(1, min(S, int(Sd)))               # decoder positions actually computed
-    token_rows = HINTS.pop("token_rows", None)
-    unpadded = HINTS.pop("unpadded", None)
-    streams = HINTS.pop("streams", None)
-    paired = HINTS.pop("paired", None)
-    pick_labels = HINTS.pop("pick_labels", None)
+    Sd = S if not plan.max_tokens else max(1, min(S, int(plan.max_tokens)))    # decoder positions actually computed
+    token_rows, unpadded, streams, paired, pick_labels = plan.token_rows, plan.unpadded, plan.streams, plan.paired, plan.pick_labels
     bound_fn = bound_teacher_forced
     if dense_bound:
         if prepared is not None:
@@ -1203,8 +1226,6 @@ def forward_uic_ss(P, cfg, att_feats, labels, att_masks, phrase_num, phrase_leng
     if cfg.N_len != 1:
         raise NotImplementedError("training with N_len >= 2 (see forward_uic)")
     draw = draw if draw is not None else _random.random
-    for k in ("max_phrase_num", "max_tokens", "token_rows", "unpadded", "streams", "paired", "pick_labels", "paired_inputs"):
-        HINTS.pop(k, None)                                     # the row-list fast paths describe the ground-truth layout: not this pass
     _COMPUTE["dtype"] = compute_dtype
     _STEP_CACHE.clear()
     _SHADOW_ONLY.clear()
@@ -1597,7 +1618,7 @@ def _fill_unpadded(P, cfg, drop, emb, vocab, unpadded, labels, phrase_length, ex
 
 @_scoped_compute_dtype
 def criterion_uic_compact(outs, phrase_num, phrase_length, phrase_syn, token_labels, token_weight):
-    """criterion_uic for token tensors that hold the real tokens' rows only (HINTS["token_rows"]): ``token_labels`` int64 and
+    """criterion_uic for token tensors that hold the real tokens' rows only (StepPlan.token_rows): ``token_labels`` int64 and
     ``token_weight`` float32 [len(token_rows)] are the labels of those rows and 1 / 0 for real / padding entries.  Same value and
     gradients as criterion_uic on the full tensors (the rows left out carry zero weight there)."""
     sa_len, sa_syn, sa_tok, na_len, na_syn, na_tok = outs
@@ -1611,7 +1632,7 @@ def criterion_uic_compact(outs, phrase_num, phrase_length, phrase_syn, token_lab
     if pair:
         if sa_tok is not na_tok:
             raise hip.BofiHipError("a pair of token weights goes with the paired log-probs of _forward_paired")
-        made = getattr(sa_tok, "_bofi_picked", None)              # picked inside the forward (HINTS["pick_labels"]): fused backward
+        made = getattr(sa_tok, "_bofi_picked", None)              # picked inside the forward (StepPlan.pick_labels): fused backward
         if made is not None and made[1] is token_labels and sa_len.dim() == 3 and sa_len.shape[1] + 1 <= phrase_length.shape[1]:
             # everything the criterion needs is at hand as small tensors: one launch (and one in the backward); the slot masks and the
             # token count of the general form below are not even made
@@ -1958,7 +1979,7 @@ def criterion_uic(outs, phrase_num, phrase_length, phrase_syn, labels, reduction
         labels = labels.reshape(-1, labels.shape[2])
     phrase_num, phrase_length = phrase_num.to(dev).long(), phrase_length.to(dev).long()
     phrase_syn, labels = phrase_syn.to(dev).long(), labels.to(dev).long()
-    real = labels[:, 1:-1][:, :sa_tok.shape[1]]                # the token tensors may cover max_tokens positions only (HINTS)
+    real = labels[:, 1:-1][:, :sa_tok.shape[1]]                # the token tensors may cover max_tokens positions only (StepPlan)
     pos = torch.arange(real.shape[1], device=dev).unsqueeze(0)
     tok_mask = pos < (phrase_length.sum(1, keepdim=True) - 1)
     slot = torch.arange(phrase_length.shape[1] - 1, device=dev).unsqueeze(0)

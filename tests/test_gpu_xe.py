@@ -540,11 +540,9 @@ def test_grouped_weight_gradient_gemms(n):
         rc += ab[:M, :NI].float().cpu().double().t() @ bb[:M, :NJ].float().cpu().double()
         if with_cs:
             rcs += ab[:M, :NI].float().cpu().double().sum(0)
-    xe._DEFER["list"] = todo
-    try:
+    with xe.step_state(defer=True):
+        xe._DEFER["list"].extend(todo)
         assert xe.flush_weight_grads() == n and xe._DEFER["list"] == []
-    finally:
-        xe._DEFER["list"] = None
     for c, cs, rc, rcs in targets.values():
         assert _maxdiff(c, rc) < 2e-3 * max(1.0, float(rc.abs().max()))
         assert _maxdiff(cs, rcs) < 2e-3 * max(1.0, float(rcs.abs().max()))
@@ -677,10 +675,42 @@ def test_dynamic_padding_leaves_loss_and_gradients_unchanged(weight_cache, manif
     assert _maxdiff(tb.bucket.grad, ta.bucket.grad) <= 1e-4 * max(1e-3, float(ta.bucket.grad.abs().max()))
     fc = torch.zeros(n_img, 0, device="cuda")
     from boficap_amd import xe
-    xe.HINTS["max_tokens"] = mt
     outs = short(fc, batch["att_feats"], batch["labels"], None, batch["phrase_num"], batch["phrase_length"], batch["phrase_syn"],
-                 batch["extend_phrase_syn_seq"], batch["extend_phrase_seq"], batch["extend_phrase_seq_mask"], -1.0)
+                 batch["extend_phrase_syn_seq"], batch["extend_phrase_seq"], batch["extend_phrase_seq_mask"], -1.0, plan=xe.StepPlan(max_tokens=mt))
     assert outs[2].shape[1] == mt and outs[5].shape[1] == mt and outs[0].shape[1] == cfg.seq_length + 1
+
+
+def test_failed_step_leaves_nothing_for_the_next_forward(weight_cache, manifest):
+    """What a trainer knows about one batch reaches that batch's forward only: after a paired step, and a step that fails on the host
+    before its forward has read anything, a plain model(...) call is the dense forward, and no per-step state is left armed."""
+    from boficap_amd import hip, xe
+    from boficap_amd.collate import max_tokens, synthetic_training_batch
+    from boficap_amd.trainer import XETrainer
+    from boficap_amd.weights import synthetic_att_feats
+    cfg, model = _model(weight_cache, manifest, "tiny_train_xe")
+    model.eval()
+    model.train_dtype = torch.bfloat16                             # (the trainer's weight operands are armed in this mode)
+    n_img, spi = 3, 3
+    hb = synthetic_training_batch(cfg, n_img, spi, seed=12)
+    assert max_tokens(hb) < cfg.seq_length
+    batch = {k: torch.from_numpy(v).cuda() for k, v in hb.items()}
+    batch["att_feats"] = torch.from_numpy(synthetic_att_feats(n_img, 36, cfg.att_feat_size, seed=3)).cuda()
+    batch["max_phrase_num"] = int(hb["phrase_num"].max())
+    tr = XETrainer(model)
+    bb = tr.add_token_rows(batch, hb)
+    assert "pair_src" in bb and "prep_tok2" in bb
+    loss, _ = tr.forward_backward(bb)
+    assert torch.isfinite(loss)
+    flat = bb["labels"].reshape(n_img * spi, -1)
+    with pytest.raises(hip.BofiHipError, match="captions for"):
+        tr.forward_backward(dict(bb, labels=torch.cat([flat, flat[:1]])))     # one caption too many: N % B, checked on the host
+    fc = torch.zeros(n_img, 0, device="cuda")
+    outs = model(fc, batch["att_feats"], batch["labels"], None, batch["phrase_num"], batch["phrase_length"], batch["phrase_syn"],
+                 batch["extend_phrase_syn_seq"], batch["extend_phrase_seq"], batch["extend_phrase_seq_mask"], -1.0)
+    N, S = n_img * spi, cfg.seq_length
+    assert outs[2].shape[:2] == (N, S) and outs[5].shape[:2] == (N, S)
+    assert all(outs[i].shape[:2] == (N, S + 1) for i in (0, 1, 3, 4))
+    assert xe._WEIGHTS["provider"] is None and xe._DEFER["list"] is None and xe._DEFER["side"] is None
 
 
 def test_compact_vocabulary_rows_leave_loss_and_gradients_unchanged(weight_cache, manifest):
