@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bofi_kernels.h"      // RbGemmArgs (the projection beside the bounding loop)
+
 namespace bofi {
 
 // Per-image state of core_NAIC (reference TransformerModel.py:1825-1831), all int32 on the device.
@@ -87,8 +89,17 @@ struct BoundLoopArgs {
     // formed), [1] / [2] iteration counters of role 0 / 1.  `xbuf` [groups][2 parities][2 roles][16][512] float32.  NULL / NULL: one workgroup per group.
     float* xbuf; unsigned* xctl;
     int pair;                                             // set by the launcher: the grid holds two workgroups per group
+    // the decoder layers' cross K|V beside the loop (round 7; the pair form at <= 36 regions only, else BOFI_ERR_ARG): kv_pj.wp != NULL asks for extra workgroups BEHIND the loop's
+    // in the same launch that run the LayerNorm-folded row-block projection kv_pj (launch_rb_gemm's arguments: the float32 encoder output, the stacked kv_all weight, y = the
+    // K|V buffer the loop reads) on 96-row blocks over the columns [kv_col0, kv_pj.N) only -- the columns the loop itself does not read.  They wait for nothing and nobody waits
+    // for them: the launch ends when both kinds of workgroup have ended.  rb_gemm_kernel<false, 6>'s code (bofi_rowblock.h) with the row sums in the order of the feed-forward kernel's projection tail: the bits are the TAIL's.
+    RbGemmArgs kv_pj; int kv_col0;
+    int kv_in_flight;                                     // launches the caller keeps in flight (0: unknown), which sizes the projection's share of the chip
+    int kv_wg0, kv_split, kv_blocks, kv_slots;            // set by the launcher: the first projection workgroup (= the loop's workgroups), workgroups per row block, row blocks, and
+                                                          // the row blocks walked at a time (workgroup (slot, part) takes the blocks slot, slot + kv_slots, ...)
 };
 int launch_bound_loop(const BoundLoopArgs& a, hipStream_t s);
+bool bound_loop_pairs(int B, int dff, int update, bool have_exchange);      // will launch_bound_loop run two workgroups per group (BOFI_BL_PAIR and the launch's size)?
 struct Pack16Entry { const float* w[2]; const float* gain; void* out; int n_each, nsrc, K, Npad, blk0; };      // blk0: set by the launcher
 struct Pack16Table { Pack16Entry e[8]; int n; int* sat; };      // sat (may be NULL): set to 1 when a weight (times its folded gain) left the fp16 range and was clamped; the launcher zeroes it first
 int launch_pack_frag16(const Pack16Table& t, hipStream_t s);

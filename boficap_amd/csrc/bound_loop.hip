@@ -27,6 +27,7 @@
 #include "bofi_common.h"
 #include "bofi_kernels.h"
 #include "bofi_naic.h"
+#include "bofi_rowblock.h"
 
 #include <cstdlib>
 
@@ -55,6 +56,8 @@ constexpr int BL_OFF_SCT = BL_OFF_BIG + 65536;           // float32 [L*10][8] se
 constexpr int BL_OFF_ST = BL_OFF_SCT + BL_LMAX * 10 * 8 * 4;       // int32 slot state: last, finished, phrase_num, att_len [16]; ext_syn, phrase_length, phrase_syn [16][24]; picks [16][2]
 constexpr int BL_ST_INTS = 4 * BL_G + 3 * BL_G * BL_LMAX + 2 * BL_G + BL_G + 16;      // (... + s_act[16 + 1] + the pair's role word s_act[BL_G + 1])
 constexpr int BL_SMEM = BL_OFF_ST + BL_ST_INTS * 4;
+constexpr int BL_SMEM_KV = BL_SMEM > RbGemmCfg<false, 6>::LDS ? BL_SMEM : RbGemmCfg<false, 6>::LDS;      // <5, true>: the larger of the two roles' needs
+static_assert(BL_SMEM_KV <= 160 * 1024, "one workgroup per CU");
 
 __device__ __forceinline__ float bl_clamp16(float v) { return v > 65504.f ? 65504.f : (v < -65504.f ? -65504.f : v); }      // (a NaN fails both tests and passes)
 __device__ __forceinline__ uint32_t bl_pack(float lo, float hi) {
@@ -102,9 +105,33 @@ __device__ __forceinline__ unsigned bl_cas(unsigned* p, unsigned expect, unsigne
     return expect;                                     // the value found
 }
 
-template <int NTT>      // the cross-attention's form: 5 = at most 36 regions (every BASELINE config), 8 = at most 64 (scores of an image in registers), 0 = any count (online softmax)
+// The PROJECTION role of bound_loop_kernel<5, true> (round 7): workgroup j behind the loop's -- (slot, part) = (j / kv_split, j % kv_split): row blocks slot, slot + kv_slots, ...,
+// chunk octets part, part + kv_split, ... of the columns [kv_col0, N) -- runs rb_gemm_kernel<false, 6>'s body (bofi_rowblock.h) per row block on the encoder's float32 output,
+// with the row sums taken in the order of the feed-forward kernel's projection tail (TAIL_SUMS): the bits of the chain that projects these columns in that tail:
+// the decoder layers' cross K|V, which nothing reads before the filling pass, on CUs that have nothing to run while the loops of the launches in flight coincide.  No flag,
+// no counter, no partner: it ends when its chunks are stored.
+__device__ __forceinline__ void bl_kv_project(const BoundLoopArgs& a, unsigned char* smem) {
+    const int j = (int)blockIdx.x - a.kv_wg0, slot = j / a.kv_split, part = j - slot * a.kv_split;
+#pragma unroll 1
+    for (int blk = slot; blk < a.kv_blocks; blk += a.kv_slots) {
+        // (everything lane-derived is derived again per block from a value the optimiser cannot see through: as invariants of this loop the block's addresses are hoisted
+        // above it and spilled -- the cure of the loop role's iteration loop)
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+        rb_gemm_block<false, 6, true>(a.kv_pj, smem, blk * RbGemmCfg<false, 6>::BR, wave, lane, (a.kv_col0 >> 6) + wave + 8 * part, 8 * a.kv_split);
+        __syncthreads();                                      // (the next block is staged over this one)
+    }
+}
+
+template <int NTT, bool KV = false>      // the cross-attention's form: 5 = at most 36 regions (every BASELINE config), 8 = at most 64 (scores of an image in registers), 0 = any count (online softmax)
+                                         // KV: workgroups from a.kv_wg0 on run the projection role (the pair form at <= 36 regions: <5, true>)
 __global__ __launch_bounds__(512) void bound_loop_kernel(BoundLoopArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
+    if constexpr (KV) {
+        // (each role runs to the end of its own branch: the projection returns here, the loop below never meets it behind a join -- see rb_ffn5_proj_tail's comment in rowblock.hip)
+        if ((int)blockIdx.x >= a.kv_wg0) { bl_kv_project(a, sm); return; }
+    }
     float* Y = reinterpret_cast<float*>(sm + BL_OFF_Y);
     unsigned char* X16 = sm + BL_OFF_X;
     unsigned char* BIG = sm + BL_OFF_BIG;
@@ -705,6 +732,11 @@ __global__ __launch_bounds__(512) void bound_loop_kernel(BoundLoopArgs a) {
 
 __global__ void bl_zero_words_kernel(int* w, int n) { const int i = blockIdx.x * 256 + threadIdx.x; if (i < n) w[i] = 0; }
 
+bool bound_loop_pairs(int B, int dff, int update, bool have_exchange) {
+    const int pair_knob = knob(BOFI_BL_PAIR);
+    return update && have_exchange && !((dff >> 9) & 1) && pair_knob != 0 && (pair_knob == 2 || B <= knob(BOFI_BL_PAIR_MAX_B));
+}
+
 int launch_bound_loop(const BoundLoopArgs& a, hipStream_t s) {
     if (a.B < 1 || a.R < 1 || a.R > 128 || a.L < 3 || a.L > BL_LMAX || a.S != a.L - 2 || a.hh < 1 || a.hh > 128 || 2 * a.hh > 256 || a.dff < 512 || a.dff > 2048 ||
         a.dff % 512 || a.ldkv % 8 || a.max_iters < 1)
@@ -716,7 +748,8 @@ int launch_bound_loop(const BoundLoopArgs& a, hipStream_t s) {
     if (!a.update && (!a.ext_syn_in || !a.last_in)) return BOFI_ERR_ARG;
     static bool attr_set = false;
     if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(bound_loop_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, BL_SMEM) != hipSuccess ||
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(bound_loop_kernel<5, true>), hipFuncAttributeMaxDynamicSharedMemorySize, BL_SMEM_KV) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void*>(bound_loop_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, BL_SMEM) != hipSuccess ||
             hipFuncSetAttribute(reinterpret_cast<const void*>(bound_loop_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, BL_SMEM) != hipSuccess ||
             hipFuncSetAttribute(reinterpret_cast<const void*>(bound_loop_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, BL_SMEM) != hipSuccess)
             return BOFI_ERR_HIP;
@@ -736,11 +769,38 @@ int launch_bound_loop(const BoundLoopArgs& a, hipStream_t s) {
     // exchange) at the price of twice the CUs and of the iteration's other stages run twice: +2.1 % on the 20-step region (4 launches of 320 images, where the four loops
     // coincide and most of the chip waits for them), -1.2 % at 640 and -2.5 % at 1 024 images per launch, where the loops hide under other launches' work
     // (profiles/r06_bound_loop_pair_ab.txt).  Results are bit-identical either way.
-    const int pair_knob = knob(BOFI_BL_PAIR);
-    v.pair = (a.update && a.xbuf && a.xctl && !((a.dff >> 9) & 1) && pair_knob != 0 && (pair_knob == 2 || a.B <= knob(BOFI_BL_PAIR_MAX_B))) ? 1 : 0;
+    v.pair = bound_loop_pairs(a.B, a.dff, a.update, a.xbuf && a.xctl) ? 1 : 0;
     if (v.pair && a.st.pair_ctl != a.xctl)                  // (the engine's launch_bound_init zeroes the control words with the slot state: no launch of its own)
         hipLaunchKernelGGL(bl_zero_words_kernel, dim3((groups * 4 + 255) / 256), dim3(256), 0, s, reinterpret_cast<int*>(a.xctl), groups * 4);
     const int grid = v.pair ? 2 * groups : groups;
+    if (a.kv_pj.wp) {
+        // the projection role: 96-row blocks, the chunk octets of [kv_col0, N) over 1-4 workgroups per row block -- launch_rb_gemm_t's rule, on the CUs the loop leaves (256 - grid).
+        // The caller counted on this form when it left these columns out of the encoder's last launch: where it cannot run, that is an error, not another form.
+        const RbGemmArgs& p = a.kv_pj;
+        if (!v.pair || a.R > 36 || p.M < 1 || !p.x || !p.c || !p.cs || !p.y || p.y_f32 || p.relu || p.ldx % 4 || p.ldy % 8 || p.N % 64 || a.kv_col0 % 512 || a.kv_col0 < 0 ||
+            a.kv_col0 >= p.N || p.ldy < p.N)
+            return BOFI_ERR_ARG;
+        const int blocks = (p.M + RbGemmCfg<false, 6>::BR - 1) / RbGemmCfg<false, 6>::BR, octets = ((p.N - a.kv_col0) / 64 + 7) / 8;
+        // How many projection workgroups: the CUs that the loops of the launches in flight leave, per launch (a.kv_in_flight launches, 4 when the caller gave no hint: the
+        // throughput forms' assumption everywhere).  Where that share covers the row blocks, one workgroup per row block, 2-4 where the chip has room (launch_rb_gemm_t's
+        // rule).  Where it does not -- 320 images, four in flight: 40 loop workgroups and a share of 24 for 120 row blocks -- a workgroup WALKS row blocks slot, slot + slots, ...:
+        // one workgroup per row block (120 a launch, 125 us each) took the CUs the OTHER launches' loop workgroups were about to get, and the loops it was meant to hide under
+        // started late: -1.1 % on the 20-step region, against +4.9 % with 24 walking workgroups (16: +2.6, 20: +4.0, 30: +1.4, 40: +3.0 %; profiles/r07_kv_beside_loop_ab.txt).
+        // At most KV_WALK blocks per workgroup:
+        // five blocks of 96 rows x 6 144 columns take about as long as a loop of ten iterations; beyond that the launch would end with the projection, not with the loop.
+        constexpr int KV_WALK = 5;
+        const int n = a.kv_in_flight > 1 ? a.kv_in_flight : 4;
+        const int share = (256 - n * grid > 0 ? 256 - n * grid : 0) / n;
+        int split = 1, slots = blocks;
+        if (share >= blocks) while (split < 4 && grid + blocks * (split + 1) <= 256 && octets >= 6 * (split + 1)) ++split;
+        else slots = share > (blocks + KV_WALK - 1) / KV_WALK ? share : (blocks + KV_WALK - 1) / KV_WALK;
+        v.kv_wg0 = grid; v.kv_split = split; v.kv_pj.dbg = 0; v.kv_blocks = blocks; v.kv_slots = slots;
+        hipLaunchKernelGGL((bound_loop_kernel<5, true>), dim3(grid + slots * split), dim3(512), BL_SMEM_KV, s, v);
+        BOFI_CHECK_LAUNCH();
+        g_gemm_flops += 2.0 * p.M * 512.0 * (p.N - a.kv_col0);
+        g_gemm_flops_skippable += (double)a.max_iters * a.B * (2.0 * 3 * 512 * 512 + 4.0 * 512 * a.dff);
+        return BOFI_OK;
+    }
     if (a.R <= 36) hipLaunchKernelGGL(bound_loop_kernel<5>, dim3(grid), dim3(512), BL_SMEM, s, v);
     else if (a.R <= 64) hipLaunchKernelGGL(bound_loop_kernel<8>, dim3(grid), dim3(512), BL_SMEM, s, v);
     else hipLaunchKernelGGL(bound_loop_kernel<0>, dim3(grid), dim3(512), BL_SMEM, s, v);

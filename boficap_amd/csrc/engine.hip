@@ -149,6 +149,7 @@ struct bofi_engine {
     int* live_max = nullptr;              // optional device word: max over decodes of their live-iteration counts (bofi_engine_set_live_iterations_max)
     int* sat_out = nullptr;               // optional device word: fp16 saturation status of the following NAIC decodes' bounding loop (bofi_engine_set_saturation_out)
     int loop_mode = -1;                   // bofi_engine_set_bound_loop: -1 = BOFI_BOUND_LOOP / hint decide, 0 = five-launch iterations, 2 = the persistent loop kernel
+    int kv_beside = 1;                    // bofi_engine_set_bound_kv_beside: 0 = never, 1 = the decoder layers' cross K|V are projected beside the bounding loop where bound_kv_beside_ok says so
     float* bl_xbuf = nullptr; unsigned* bl_xctl = nullptr;      // the loop kernel's pair exchange: partial sums and control words (workspace: one set per engine / fork)
     int* b_wsat = nullptr;                // [1] set by pack_frag16 when an fp16 weight copy was clamped (shared with forks, like the weights)
     hipStream_t run_stream = nullptr;     // a stream of the engine's own, offered to callers that keep several decodes in flight
@@ -516,8 +517,15 @@ struct bofi_engine {
         return loop_ready && loop_config_ok() && R <= 128 && k != 0 && (k == 2 || in_flight != 1);
     }
     // update != 0: the whole loop on the engine's slot state (after launch_bound_init); update == 0: one iteration on a given layout, log-probabilities out
-    int bound_loop(int B, int R, const int* att_len, const int* ext_syn_in, const int* last_in, int update, float* len_logp, float* syn_logp, hipStream_t s) {
+    // kv_beside: the launch also projects the columns behind the bounding layers' of kv_all (the decoder layers' cross K|V) from the encoder's output, in extra workgroups
+    int bound_loop(int B, int R, const int* att_len, const int* ext_syn_in, const int* last_in, int update, float* len_logp, float* syn_logp, hipStream_t s,
+                   bool kv_beside_now = false) {
         bofi::BoundLoopArgs a{};
+        if (kv_beside_now) {
+            bofi::RbGemmArgs& p = a.kv_pj;
+            p.x = x_enc.x; p.ldx = cfg.d_model; p.wp = (const bofi::u32x4*)kv_all.wp; p.c = kv_all.b; p.cs = kv_all.cs; p.y = kv; p.ldy = kv_all.N; p.M = B * R; p.N = kv_all.Npad;
+            a.kv_col0 = n_len * 2 * cfg.d_model; a.kv_in_flight = in_flight;
+        }
         a.wo_self = (const bofi::bl_u32x4*)b_o_self.wp16; a.x0b = b_x0b;
         a.wq_src = (const bofi::bl_u32x4*)b_q_src.wp16; a.cq = b_q_src.b;
         a.wo_src = (const bofi::bl_u32x4*)b_o_src.wp16; a.bo_src = b_o_src.b;
@@ -537,6 +545,22 @@ struct bofi_engine {
     // y1 -> y3 partial slabs (by3): query projection + cross-attention, Wo_src, FFN, as the direct-operand kernels
     // of bound_ops.hip.  Returns -1 when the configuration is not theirs (bound_chain then takes the general kernels), else a status;
     // *parts = number of slabs in by3.
+    // The decoder layers' cross K|V BESIDE the bounding loop (round 7): with several launches in flight their loops coincide -- 40 workgroups each -- and most of the chip has
+    // nothing to run meanwhile, while the projection of all of kv_all sits in front of the loop as the tail of the encoder's last feed-forward launch.  The loop reads the
+    // bounding layer's columns only; nothing reads the others before the filling pass.  In this form the tail carries the first n_len * 2 * d columns and the loop launch
+    // projects the rest in workgroups of its own (bound_loop_kernel<5, true>): one kernel node, one stream, no fork / join.  On exactly where the loops are exposed and
+    // today's chain has the tail: the pair form of the loop kernel by the library's own rule (BOFI_BL_PAIR = 1, <= BOFI_BL_PAIR_MAX_B images), not a decode running alone (the
+    // decodes-in-flight hint also sizes the projection's share of the chip), <= 36 regions, the whole decode in one call (a phased call's ENCODE promises the whole stacked
+    // K|V), the row-block encoder with the projection tail.  Else today's chain, unchanged.
+    bool bound_kv_beside_ok(int B, int R, int phases) const {
+        if (!kv_beside || phases || enc.empty() || in_flight == 1 || R > 36 || !bound_loop_ok(R) || exp_skip("loop") || exp_skip("encoder")) return false;
+        // (the pair as the library's own choice: BOFI_BL_PAIR = 2 forces pairs at any size for the tests of the pair itself -- they compare its bits with one workgroup per
+        // group's -- and moves nothing else in the chain)
+        if (bofi::knob(BOFI_BL_PAIR) != 1 || !bofi::bound_loop_pairs(B, cfg.d_ff, 1, bl_xbuf && bl_xctl)) return false;
+        const int M = B * R, col0 = n_len * 2 * cfg.d_model;
+        const EncLayer& l = enc.back();
+        return kv_all.Npad == kv_all.N && col0 >= 512 && col0 < kv_all.N && fold_rb_ok(l.qkv, M) && fold_rb_ok(kv_all, M) && ffn_proj_ok(l.w1, l.w2, kv_all, M);
+    }
     int bound_chain_lean(int B, int R, const int* att_len, const Rows& r, hipStream_t s, int* parts) {
         const bool lean_on = bofi::knob(BOFI_BOUND_LEAN) != 0;
         const int d = cfg.d_model;
@@ -739,7 +763,7 @@ struct bofi_engine {
         ENG_OK(folded(t, l.w1, hdn, dt, cfg.d_ff, M, r, s, 1));
         return close_sublayer(hdn, l.w2, t, M, r, s);
     }
-    int enqueue_encode(const void* feats, int feats_dtype, const int* att_len, int B, int R, float* memory_out, hipStream_t s);
+    int enqueue_encode(const void* feats, int feats_dtype, const int* att_len, int B, int R, float* memory_out, hipStream_t s, bool kv_bound_only = false);
     int enqueue_bound_iter(int B, int R, const int* att_len, const int* ext_syn, const int* last, int update, float* len_logp,
                            float* syn_logp, bool early, hipStream_t s);
     int enqueue_fill(const int* att_len, int B, int R, int flags, int64_t* seq, float* seq_logprob, hipStream_t s);
@@ -752,8 +776,10 @@ struct bofi_engine {
 };
 
 // ================================================================================================
+// kv_bound_only (bound_kv_beside_ok): the last feed-forward launch's tail projects the bounding layers' columns of kv_all only -- a column's value does not depend on how
+// many are projected -- and the caller's loop launch makes the rest
 int bofi_engine::enqueue_encode(const void* feats, int feats_dtype, const int* att_len, int B, int R, float* memory_out,
-                                hipStream_t s) {
+                                hipStream_t s, bool kv_bound_only) {
     const int d = cfg.d_model, dt = cfg.dtype, M = B * R;
     if (exp_skip("encoder")) return BOFI_OK;           // (experiments build: the whole encoder phase)
     // The residual stream x_enc stays float32; every GEMM that closes a sublayer also writes a copy in
@@ -781,8 +807,11 @@ int bofi_engine::enqueue_encode(const void* feats, int feats_dtype, const int* a
         ENG_OK(attn_sublayer(a, l.o, x_enc, !ffn_rb, split, s));
         // the consumer of this layer's output: the next layer's q|k|v, or the stacked cross K|V
         const bool last = li + 1 == enc.size();
-        const Lin& nxt = last ? kv_all : enc[li + 1].qkv;
+        Lin kv_bound = kv_all;                                           // (the same operands, the first columns: the bounding layers' K|V)
+        if (kv_bound_only) kv_bound.N = kv_bound.Npad = n_len * 2 * d;
+        const Lin& nxt = last ? (kv_bound_only ? kv_bound : kv_all) : enc[li + 1].qkv;
         ENG_OK(ffn_sublayer(l.w1, l.w2, x_enc, need_copy, M, s, split ? &l.o : nullptr, &nxt, last ? kv : qkv, last ? kv_all.N : 3 * d, &proj_made));
+        if (last && kv_bound_only && !proj_made) return BOFI_ERR_STATE;  // (bound_kv_beside_ok saw this tail)
     }
     if (memory_out) ENG_OK(bofi::launch_layernorm(x_enc.x, enc_norm.g, enc_norm.b, memory_out, BOFI_DT_F32, M, d, s));
     // cross-attention K|V of the bound layer and of every decoder layer in one GEMM on memory =
@@ -829,7 +858,8 @@ int bofi_engine::enqueue_decode(const void* feats, int feats_dtype, const int* a
     // phases (BOFI_FLAG_PHASE_*): none of the bits = the whole decode; else only the named parts (a pipelining caller enqueues them as separate calls)
     const int ph = flags & (BOFI_FLAG_PHASE_ENCODE | BOFI_FLAG_PHASE_BOUND | BOFI_FLAG_PHASE_FILL);
     const bool do_enc = !ph || (ph & BOFI_FLAG_PHASE_ENCODE), do_bound = !ph || (ph & BOFI_FLAG_PHASE_BOUND), do_fill = !ph || (ph & BOFI_FLAG_PHASE_FILL);
-    if (do_enc) ENG_OK(enqueue_encode(feats, feats_dtype, att_len, B, R, memory_out, s));
+    const bool kv_beside_now = bound_kv_beside_ok(B, R, ph);
+    if (do_enc) ENG_OK(enqueue_encode(feats, feats_dtype, att_len, B, R, memory_out, s, kv_beside_now));
     // ---- bounding pass (core_NAIC TransformerModel.py:1833-1870)
     if (do_bound) {
     ENG_OK(bofi::launch_bound_init(st, B, L, cfg.pad_idx, cfg.len_idx, s));
@@ -837,7 +867,7 @@ int bofi_engine::enqueue_decode(const void* feats, int feats_dtype, const int* a
         ENG_OK(enqueue_bound_dense(att_len, B, R, s));
     } else if (bound_loop_ok(R) && !exp_skip("loop")) {
         // one launch: a workgroup per 16 images runs every iteration and leaves when its images are finished (no iteration budget to enqueue)
-        ENG_OK(bound_loop(B, R, att_len, nullptr, nullptr, 1, nullptr, nullptr, s));
+        ENG_OK(bound_loop(B, R, att_len, nullptr, nullptr, 1, nullptr, nullptr, s, kv_beside_now));
     } else {
         ENG_OK(bound_tail(nullptr, 1, nullptr, nullptr, B, BOUND_ATTN, nullptr, nullptr, s));
 #ifdef BOFI_EXPERIMENTS
@@ -1130,6 +1160,7 @@ int bofi_engine_fork_ex(bofi_engine_t* parent, int max_batch, int fork_flags, bo
     e->live_max = nullptr;                       // (a raw device pointer the fork's handle does not keep alive)
     e->sat_out = nullptr;
     e->loop_mode = -1;
+    // (kv_beside -- a form switch for A/B runs, not a per-call knob -- stays the parent's)
     e->saic_it_begin = 1;
     e->saic_it_end = 0;
     e->st = bofi::BoundState{};
@@ -1204,7 +1235,8 @@ static const void* debug_buffer(bofi_engine_t* e, const std::string& n, int64_t*
     return n == "by1" ? (const void*)e->y1.x : n == "byb" ? (const void*)e->y1.xb : n == "st_b" ? (const void*)e->y1.st :
            n == "bq2" ? (const void*)e->bq2 : n == "bctx2" ? (const void*)e->bctx2 : n == "by2" ? (const void*)e->y2.x :
            n == "bh" ? (const void*)e->bh : n == "by3" ? (const void*)e->by3 : n == "dbg_part" ? (const void*)e->dbg_part :
-           n == "counters" ? (const void*)e->st.counters : nullptr;      // ("counters": int32 [8] of the last decode: [5] = groups whose bounding loop ran as a PAIR of workgroups)
+           n == "counters" ? (const void*)e->st.counters :                // ("counters": int32 [8] of the last decode: [5] = groups whose bounding loop ran as a PAIR of workgroups)
+           n == "kv" ? (const void*)e->kv : n == "x_enc" ? (const void*)e->x_enc.x : nullptr;      // ("kv": the stacked cross K|V rows [B*R][kv_all.N] of the last encode, compute dtype; "x_enc": the encoder's float32 output rows [B*R][d] they were projected from)
 }
 
 int bofi_engine_debug_copy(bofi_engine_t* e, const char* name, void* dst, int64_t bytes, void* stream) {
@@ -1261,6 +1293,17 @@ int bofi_engine_set_bound_loop(bofi_engine_t* e, int mode) {
     if (!e || (mode != -1 && mode != 0 && mode != 2)) return fail(BOFI_ERR_ARG, "bound loop mode: -1 (environment / hint), 0 (five-launch iterations) or 2 (persistent loop kernel)");
     e->loop_mode = mode;
     return BOFI_OK;
+}
+
+int bofi_engine_set_bound_kv_beside(bofi_engine_t* e, int mode) {
+    g_err.clear();
+    if (!e || (mode != 0 && mode != 1)) return fail(BOFI_ERR_ARG, "cross K|V beside the bounding loop: 0 (never) or 1 (where the loops are exposed)");
+    e->kv_beside = mode;
+    return BOFI_OK;
+}
+
+int bofi_engine_bound_kv_beside_active(bofi_engine_t* e, int B, int R, int flags) {
+    return e && e->finalized && B > 0 && R > 0 && e->bound_kv_beside_ok(B, R, flags & (BOFI_FLAG_PHASE_ENCODE | BOFI_FLAG_PHASE_BOUND | BOFI_FLAG_PHASE_FILL)) ? 1 : 0;
 }
 
 int bofi_engine_set_saic_range(bofi_engine_t* e, int it_begin, int it_end) {
@@ -1572,7 +1615,7 @@ int bofi_engine_decode_naic(bofi_engine_t* e, const void* feats, int feats_dtype
                                   (uintptr_t)phrase_length, (uintptr_t)phrase_syn, (uintptr_t)memory_out, (uintptr_t)bound_iters,
                                   (uintptr_t)e->q1_group, (uintptr_t)e->bound_iter_cap, (uintptr_t)e->live_max, (uintptr_t)e->in_flight,
                                   (uintptr_t)bofi::g_env_generation, (uintptr_t)e->row_plogp_out, (uintptr_t)e->row_chosen_out,
-                                  (uintptr_t)e->sat_out, (uintptr_t)(e->loop_mode + 1)};
+                                  (uintptr_t)e->sat_out, (uintptr_t)(e->loop_mode + 1), (uintptr_t)e->kv_beside};
     return run_graphed(e, key, s, [&](hipStream_t cs) {
         return e->enqueue_decode(feats, feats_dtype, att_len, B, R, flags, seq, seq_logprob, phrase_num, phrase_length,
                                  phrase_syn, memory_out, bound_iters, cs);

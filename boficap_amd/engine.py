@@ -108,6 +108,7 @@ class BofiEngine:
         f.cfg, f.dtype, f.device, f.max_batch, f.max_regions = self.cfg, self.dtype, self.device, int(max_batch or self.max_batch), self.max_regions
         f._lib, f._finalized, f._parent = self._lib, True, getattr(self, "_parent", self)        # keeps the weights' owner alive
         f._iter_cap, f._q1_group, f._live_word = 0, 0, None           # per-call knobs start from the defaults (bofi_engine_fork resets them too)
+        f._kv_beside = getattr(self, "_kv_beside", 1)                 # (the form switch of set_bound_kv_beside is inherited: bofi_engine_fork copies it)
         f._h = C.c_void_p()
         with torch.cuda.device(self.device):
             hip.check(self._lib.bofi_engine_fork_ex(self._h, int(max_batch or 0), hip.FORK_IDS_ONLY if ids_only else 0, C.byref(f._h)), "bofi_engine_fork_ex")
@@ -268,6 +269,17 @@ class BofiEngine:
         0 = the five-launch bf16 iterations, 2 = the persistent fp16 loop kernel whatever the hint."""
         hip.check(self._lib.bofi_engine_set_bound_loop(self._h, int(mode)), "bofi_engine_set_bound_loop")
         self._loop_mode = int(mode)
+
+    def set_bound_kv_beside(self, mode: int) -> None:
+        """Where the decoder layers' cross K|V are projected (bofi_engine_set_bound_kv_beside): 1 (default) = beside the bounding loop, in extra workgroups of the loop
+        kernel's launch, wherever ``bound_kv_beside_active`` says so; 0 = never (all of the stacked K|V in front of the loop).  Part of the graph key; forks made afterwards inherit it."""
+        hip.check(self._lib.bofi_engine_set_bound_kv_beside(self._h, int(mode)), "bofi_engine_set_bound_kv_beside")
+        self._kv_beside = int(mode)
+
+    def bound_kv_beside_active(self, B: int, R: int, phases: str = "") -> bool:
+        """Would a ``decode_naic`` of B images of R regions (``phases`` as there) project the decoder layers' cross K|V beside the bounding loop (bofi_engine_bound_kv_beside_active)?"""
+        flags = (hip.FLAG_PHASE_ENCODE if "e" in phases else 0) | (hip.FLAG_PHASE_BOUND if "b" in phases else 0) | (hip.FLAG_PHASE_FILL if "f" in phases else 0)
+        return bool(self._lib.bofi_engine_bound_kv_beside_active(self._h, int(B), int(R), flags))
 
     def saturated(self, out: dict) -> int:
         """fp16 saturation status of the decode that produced ``out`` (a device -> host read: call it where the caller synchronises anyway): 0 = clean; bit 0 = the

@@ -87,6 +87,8 @@ SIGNATURES = {
     "bofi_engine_set_live_iterations_max": (_I, [_P, _P]),
     "bofi_engine_set_saturation_out": (_I, [_P, _P]),
     "bofi_engine_set_bound_loop": (_I, [_P, _I]),
+    "bofi_engine_set_bound_kv_beside": (_I, [_P, _I]),
+    "bofi_engine_bound_kv_beside_active": (_I, [_P, _I, _I, _I]),
     "bofi_engine_create": (_I, [C.POINTER(BofiConfigC), C.POINTER(_P)]),
     "bofi_engine_destroy": (None, [_P]),
     "bofi_engine_fork": (_I, [_P, C.POINTER(_P)]),

@@ -378,6 +378,16 @@ int bofi_engine_set_saturation_out(bofi_engine_t* e, int* word);
 /* Per-engine choice of the bounding loop's form for the following decodes: -1 (default, also of a fork) = BOFI_BOUND_LOOP and the decodes-in-flight hint decide
  * (bofi_engine_bound_loop_active), 0 = the five-launch bf16 iterations, 2 = the persistent fp16 loop kernel whatever the hint.  Part of the graph key. */
 int bofi_engine_set_bound_loop(bofi_engine_t* e, int mode);
+/* Where the decoder layers' cross K|V -- the columns of the stacked K|V behind the bounding layer's -- are projected (round 7): 1 (default) = BESIDE the bounding loop, in extra
+ * workgroups of the loop kernel's own launch, wherever that pays: the loop kernel runs two workgroups per group by the library's own rule (BOFI_BL_PAIR = 1: launches of at most
+ * BOFI_BL_PAIR_MAX_B images; not a decode running alone -- the decodes-in-flight hint also sizes the projection's share of the chip, 4 when there is none), at most 36 regions, the row-block encoder with the projection tail, and the decode is one call (a call with BOFI_FLAG_PHASE_* keeps the other
+ * form: its ENCODE phase promises the whole stacked K|V).  The encoder's last feed-forward launch then projects the bounding layer's columns only.  0 = never: all columns
+ * in front of the loop, as everywhere else.  Every result is the same bits either way: the projection beside the loop takes the LayerNorm row sums in the feed-forward tail's
+ * order, so the decoder layers' K|V -- and with them the captions and their log-probabilities -- are the tail's.  A switch for A/B runs and tests, not a knob: per-engine state,
+ * part of the graph key, inherited by a fork. */
+int bofi_engine_set_bound_kv_beside(bofi_engine_t* e, int mode);
+/* 1 when a bofi_engine_decode_naic of B images of R regions called with `flags` would take that form under the engine's current settings; 0 otherwise. */
+int bofi_engine_bound_kv_beside_active(bofi_engine_t* e, int B, int R, int flags);
 
 /* Device pointer of the engine's own [max_batch * S, V] float32 log-prob workspace: where a decode called WITHOUT a
  * seq_logprob buffer leaves the distribution (valid until the next decode on this engine) -- input of
