@@ -203,6 +203,19 @@ int launch_bound_table(const float* lut_syn, const float* lut_tok, const float* 
 int launch_vocab_sample(const float* logp, int rows, int V, int S, int n, float temperature, uint64_t seed, const int* ntok, int pad_idx,
                         int64_t* out, hipStream_t st, const int* halt = nullptr, const int* row_idx = nullptr, const int* n_rows = nullptr,
                         const uint64_t* seed_dev = nullptr);      // seed_dev: device word added to `seed` (so that a captured launch can draw anew)
+// ---- mask-predict refinement (refine.hip): the per-image step behind pass t of T + 1 filling passes, all buffers [B, S]
+struct MaskPredictArgs {
+    int64_t* ids; float* chosen; float* plogp; int* round;                              // the state (y, c, e, emitted_round): read and written
+    const int64_t* fresh_ids; const float* fresh_chosen; const float* fresh_plogp;      // what pass t's vocabulary epilogue left
+    int* mask;                        // in: the mask of pass t (t >= 1); out (t < T): the mask of pass t + 1
+    int64_t* next_ids;                // out (t < T): the input ids of pass t + 1
+    const int* last;                  // [B] 1 + tokens laid out
+    int B, S, t, T, bos_idx, pad_idx;
+    int64_t* seq_out; float* plogp_out; float* chosen_out; int* round_out;              // out (t == T): the state; the statistics pair and round_out are optional
+};
+int mask_predict_check(const MaskPredictArgs& a);     // BOFI_ERR_ARG: B >= 1, 1 <= S <= 64, 0 <= t <= T <= 15, non-null pointers
+int launch_mask_predict_step(const MaskPredictArgs& a, hipStream_t st);
+
 int launch_set_u64(uint64_t* p, uint64_t v, hipStream_t s);
 int launch_zero_f32(float* p, size_t n, hipStream_t s);
 

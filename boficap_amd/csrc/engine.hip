@@ -108,6 +108,8 @@ struct bofi_engine {
     // per-call (bofi_engine_set_row_stats_out; part of the graph key): where the filling pass's epilogue leaves, per position, sum_v p log p and the log-prob of the
     // emitted id -- eval's entropy / perplexity (eval_utils.py:463-464) without a second pass over the log-probs
     float *row_plogp_out = nullptr, *row_chosen_out = nullptr;
+    // per-call (bofi_engine_set_refine_out; part of the graph key): where a decode under BOFI_FLAG_MASK_PREDICT leaves the pass that emitted each position's token
+    int* refine_round_out = nullptr;
     bool loop_ready = false;
     float* dbg_part = nullptr;
 
@@ -129,6 +131,10 @@ struct bofi_engine {
     Stream xw;                                                          // all L rows of the bound sequence [B*L, d]: SAIC bound input, dense bounding pass
     void* kvs = nullptr;                                                // their K|V [B*L, 2d]
     int64_t* tok64 = nullptr;                                           // greedy ids of one decoder pass [B*S]
+    // mask-predict refinement (refine.hip), [Bm*Sq] each: the state (id, its log-prob, sum_v p log p, emitting pass), what a pass's epilogue left, the next pass's mask and input ids
+    int64_t *mp_ids = nullptr, *mp_fresh_ids = nullptr, *mp_next_ids = nullptr;
+    float *mp_chosen = nullptr, *mp_plogp = nullptr, *mp_fresh_chosen = nullptr, *mp_fresh_plogp = nullptr;
+    int *mp_round = nullptr, *mp_mask = nullptr;
     std::vector<void*> qkv_dec;                                         // SAIC: q|k|v of every decoder layer [B*S, 3d] (the K / V cache)
     int *sa_rows = nullptr, *sa_nrows = nullptr;                        // decoder rows of the iteration's new phrases, their count
     uint64_t* d_seed = nullptr;                                         // per-call sampling seed (read by the captured sampling kernels)
@@ -319,6 +325,9 @@ struct bofi_engine {
     ENG_OK(dalloc((char**)&kvs, Bm * L * 2 * (size_t)d, tsz)); ENG_OK(dalloc(&tok64, Bm * Sq));
     ENG_OK(dalloc(&sa_rows, Bm * Sq)); ENG_OK(dalloc(&sa_nrows, 4)); ENG_OK(dalloc(&d_seed, 2));
     ENG_OK(dalloc(&st_fill16, Bm * Sq * (d / 16) * 2));
+    ENG_OK(dalloc(&mp_ids, Bm * Sq)); ENG_OK(dalloc(&mp_fresh_ids, Bm * Sq)); ENG_OK(dalloc(&mp_next_ids, Bm * Sq));
+    ENG_OK(dalloc(&mp_chosen, Bm * Sq)); ENG_OK(dalloc(&mp_plogp, Bm * Sq)); ENG_OK(dalloc(&mp_fresh_chosen, Bm * Sq)); ENG_OK(dalloc(&mp_fresh_plogp, Bm * Sq));
+    ENG_OK(dalloc(&mp_round, Bm * Sq)); ENG_OK(dalloc(&mp_mask, Bm * Sq));
     qkv_dec.assign(c.n_dec, nullptr);                  // allocated by the first semi-autoregressive decode
 
         return BOFI_OK;
@@ -894,7 +903,9 @@ int bofi_engine::enqueue_decode(const void* feats, int feats_dtype, const int* a
 
 // ---- filling pass (decode_NA :570-587) on the slot layout in st.ext_syn / st.last and the cross K|V of the preceding
 // encode; with refinement the pass is repeated with the previous round's ids as decoder input tokens (the glat_input hook
-// of decode_NA :570-574 -- the reference has no refinement loop itself)
+// of decode_NA :570-574 -- the reference has no refinement loop itself).  Under BOFI_FLAG_MASK_PREDICT the extra passes are mask-predict rounds: every pass's
+// epilogue writes ids and row statistics into the engine's scratch, mask_predict_step (refine.hip) merges them into the state and makes the next pass's
+// input ids (BOS at the least confident positions), and the last step writes the caller's seq, row statistics and emitted rounds.
 int bofi_engine::enqueue_fill(const int* att_len, int B, int R, int flags, int64_t* seq, float* seq_logprob, hipStream_t s) {
     const int d = cfg.d_model, dt = cfg.dtype, S = cfg.seq_length, M = B * S;
     if (exp_skip("filling")) return BOFI_OK;           // (experiments build: the whole filling pass incl. the vocabulary epilogue)
@@ -905,10 +916,25 @@ int bofi_engine::enqueue_fill(const int* att_len, int B, int R, int flags, int64
     // BOFI_FLAG_IDS_ONLY where the row-block generator would run: generator + epilogue as ONE launch that keeps the distribution on the CU (rb_vocab_kernel)
     const bool fused = (flags & BOFI_FLAG_IDS_ONLY) && gen_rb;
     if (no_logits && !fused) return fail(BOFI_ERR_STATE, "this fork has no vocabulary-wide buffers: BOFI_FLAG_IDS_ONLY decodes that take the fused generator only");
+    const bool mp = (flags & BOFI_FLAG_MASK_PREDICT) != 0;
+    // where a pass's epilogue leaves its ids and row statistics, and what the next pass's embedding reads
+    int64_t* const ep_seq = mp ? mp_fresh_ids : seq;
+    float* const ep_plogp = mp ? mp_fresh_plogp : row_plogp_out;
+    float* const ep_chosen = mp ? mp_fresh_chosen : row_chosen_out;
+    const int64_t* const fed = mp ? mp_next_ids : seq;
+    auto refine_step = [&](int round) -> int {
+        if (!mp) return BOFI_OK;
+        bofi::MaskPredictArgs m{};
+        m.ids = mp_ids; m.chosen = mp_chosen; m.plogp = mp_plogp; m.round = mp_round;
+        m.fresh_ids = mp_fresh_ids; m.fresh_chosen = mp_fresh_chosen; m.fresh_plogp = mp_fresh_plogp; m.mask = mp_mask; m.next_ids = mp_next_ids;
+        m.last = st.last; m.B = B; m.S = S; m.t = round; m.T = rounds - 1; m.bos_idx = cfg.bos_idx; m.pad_idx = cfg.pad_idx;
+        m.seq_out = seq; m.plogp_out = row_plogp_out; m.chosen_out = row_chosen_out; m.round_out = refine_round_out;
+        return bofi::launch_mask_predict_step(m, s);
+    };
     for (int round = 0; round < rounds; ++round) {
     // (round 0 under the row-block family: layer 0's q|k|v rows come out of the (label, position) table with the embedding launch -- BOFI_FILL_QKV_TAB=0: the projection)
     const bool qkv_tab = round == 0 && fill_tab_ready && !dec.empty() && fold_rb_ok(dec[0].qkv, M) && bofi::knob(BOFI_FILL_QKV_TAB) != 0 && !exp_skip("qkv");
-    ENG_OK(bofi::launch_embed_fill(lut_tok, lut_syn, pe, st.ext_syn, round ? seq : nullptr, B, S, L, d, cfg.bos_idx, x_fill.x, x_fill.copy(), dt,
+    ENG_OK(bofi::launch_embed_fill(lut_tok, lut_syn, pe, st.ext_syn, round ? fed : nullptr, B, S, L, d, cfg.bos_idx, x_fill.x, x_fill.copy(), dt,
                                    x_fill.st, s, qkv_tab ? f_qkv0 : nullptr, qkv_tab ? qkv : nullptr, 3 * d));
     bool proj_made = qkv_tab;                            // this layer's q|k|v came out of the previous layer's feed-forward launch (layer 0: out of the table)
     for (size_t li = 0; li < dec.size(); ++li) {
@@ -942,9 +968,10 @@ int bofi_engine::enqueue_fill(const int* att_len, int B, int R, int flags, int64
         if (exp_skip("gen")) continue;
         bofi::RbVocabArgs v{};
         v.x = x_fill.x; v.ldx = d; v.wp = (const bofi::u32x4*)gen.wp; v.c = gen.b; v.cs = gen.cs; v.M = M; v.N = gen.Npad; v.V = cfg.vocab; v.S = S;
-        v.ntok = st.last; v.ntok_bias = -1; v.pad_idx = cfg.pad_idx; v.seq = seq; v.row_plogp = row_plogp_out; v.row_chosen = row_chosen_out;
+        v.ntok = st.last; v.ntok_bias = -1; v.pad_idx = cfg.pad_idx; v.seq = ep_seq; v.row_plogp = ep_plogp; v.row_chosen = ep_chosen;
         v.part = vb_part; v.ctr = vb_ctr; v.alone = in_flight == 1;
         ENG_OK(bofi::launch_rb_vocab(v, s));
+        ENG_OK(refine_step(round));
         continue;
     }
     const float* lsrc = nullptr;
@@ -958,8 +985,9 @@ int bofi_engine::enqueue_fill(const int* att_len, int B, int R, int flags, int64
     // (a round that another one follows: its ids are all the next round reads -- the log-probs it would write are overwritten: not stored)
     const int ids_only_on = bofi::knob(BOFI_REFINE_IDS_ONLY);      // developer knob: 0 = every round stores its log-probs
     const int lsm = (flags & BOFI_FLAG_RAW_LOGITS) ? 0 : ((flags & BOFI_FLAG_IDS_ONLY) || (ids_only_on && round + 1 < rounds && lsrc) ? 2 : 1);
-    ENG_OK(bofi::launch_vocab_finalize(lg, M, cfg.vocab, S, lsm, st.last, -1, cfg.pad_idx, seq, s, nullptr, nullptr, nullptr, nullptr,
-                                       lsrc, gen.Npad, lsm ? row_plogp_out : nullptr, lsm ? row_chosen_out : nullptr));
+    ENG_OK(bofi::launch_vocab_finalize(lg, M, cfg.vocab, S, lsm, st.last, -1, cfg.pad_idx, ep_seq, s, nullptr, nullptr, nullptr, nullptr,
+                                       lsrc, gen.Npad, lsm ? ep_plogp : nullptr, lsm ? ep_chosen : nullptr));
+    ENG_OK(refine_step(round));
     }
     return BOFI_OK;
 }
@@ -1156,6 +1184,7 @@ int bofi_engine_fork_ex(bofi_engine_t* parent, int max_batch, int fork_flags, bo
     e->sample_seed = 0;
     e->bound_iter_cap = 0;                       // (a capped parent must not truncate the fork's bounding loop)
     e->row_plogp_out = nullptr; e->row_chosen_out = nullptr;
+    e->refine_round_out = nullptr;
     e->in_flight = 0;
     e->live_max = nullptr;                       // (a raw device pointer the fork's handle does not keep alive)
     e->sat_out = nullptr;
@@ -1333,6 +1362,13 @@ int bofi_engine_set_row_stats_out(bofi_engine_t* e, float* row_plogp, float* row
     if (!e || (!row_plogp != !row_chosen)) return fail(BOFI_ERR_ARG, "row statistics: both buffers or none");
     e->row_plogp_out = row_plogp;
     e->row_chosen_out = row_chosen;
+    return BOFI_OK;
+}
+
+int bofi_engine_set_refine_out(bofi_engine_t* e, int* emitted_round) {
+    g_err.clear();
+    if (!e) return fail(BOFI_ERR_ARG, "null engine");
+    e->refine_round_out = emitted_round;
     return BOFI_OK;
 }
 
@@ -1529,6 +1565,15 @@ static int check_ids_only(bofi_engine_t* e, int flags, const float* seq_logprob)
     if (e->no_logits && !(flags & BOFI_FLAG_IDS_ONLY)) return fail(BOFI_ERR_STATE, "this fork has no vocabulary-wide buffers: decode with BOFI_FLAG_IDS_ONLY");
     return BOFI_OK;
 }
+// BOFI_FLAG_MASK_PREDICT: what the flag goes with, checked before anything is enqueued or captured
+static int check_mask_predict(bofi_engine_t* e, int flags) {
+    if (!(flags & BOFI_FLAG_MASK_PREDICT)) return BOFI_OK;
+    if (((flags >> BOFI_FLAG_REFINE_SHIFT) & 15) == 0) return fail(BOFI_ERR_ARG, "BOFI_FLAG_MASK_PREDICT needs a refinement count >= 1 in bits 8..11");
+    if (flags & BOFI_FLAG_RAW_LOGITS) return fail(BOFI_ERR_ARG, "BOFI_FLAG_MASK_PREDICT ranks log-probs: not with BOFI_FLAG_RAW_LOGITS");
+    if (flags & BOFI_FLAG_SAMPLE) return fail(BOFI_ERR_ARG, "BOFI_FLAG_MASK_PREDICT refines greedy picks: not with BOFI_FLAG_SAMPLE");
+    if (e->cfg.seq_length > 64) return fail(BOFI_ERR_ARG, "BOFI_FLAG_MASK_PREDICT: seq_length above 64 (one wavefront holds an image's positions)");
+    return BOFI_OK;
+}
 static int check_feats(bofi_engine_t* e, const void* feats, int feats_dtype) {
     if (!feats) return fail(BOFI_ERR_ARG, "null att_feats");
     if (feats_dtype != BOFI_DT_F32 && feats_dtype != e->cfg.dtype) return fail(BOFI_ERR_ARG, "att_feats must be float32 or the engine's compute dtype");
@@ -1560,6 +1605,7 @@ int bofi_engine_fill_naic(bofi_engine_t* e, const int* ext_syn, const int* last,
     ENG_OK(check_call(e, B, R));
     if (!ext_syn || !last || !seq) return fail(BOFI_ERR_ARG, "null argument");
     ENG_OK(check_ids_only(e, flags, seq_logprob));
+    if (const int rc = check_mask_predict(e, flags)) return rc;      // (its message stays: ENG_OK would put the call's text in its place)
     if (e->no_logits && !e->gen_rb_ok(B * e->cfg.seq_length)) return fail(BOFI_ERR_STATE, "this fork has no vocabulary-wide buffers and the launch would not take the fused generator");
     hipStream_t s = (hipStream_t)stream;
     ENG_HIP(hipMemcpyAsync(e->st.ext_syn, ext_syn, (size_t)B * e->L * sizeof(int), hipMemcpyDeviceToDevice, s));
@@ -1574,6 +1620,7 @@ int bofi_engine_decode_saic(bofi_engine_t* e, const void* feats, int feats_dtype
     ENG_OK(check_call(e, B, R));
     ENG_OK(check_feats(e, feats, feats_dtype));
     if (!seq) return fail(BOFI_ERR_ARG, "null seq");
+    if (flags & BOFI_FLAG_MASK_PREDICT) return fail(BOFI_ERR_ARG, "BOFI_FLAG_MASK_PREDICT refines the non-autoregressive filling pass: not with the semi-autoregressive decode");
     if (e->n_len != 1) return fail(BOFI_ERR_STATE, "the semi-autoregressive decode is built for a one-layer bounding network (N_len = 1)");
     if (e->no_logits) return fail(BOFI_ERR_STATE, "this fork has no vocabulary-wide buffers: the semi-autoregressive decode needs the distribution");
     hipStream_t s = (hipStream_t)stream;
@@ -1603,6 +1650,7 @@ int bofi_engine_decode_naic(bofi_engine_t* e, const void* feats, int feats_dtype
     ENG_OK(check_feats(e, feats, feats_dtype));
     if (!seq) return fail(BOFI_ERR_ARG, "null seq");
     ENG_OK(check_ids_only(e, flags, seq_logprob));
+    if (const int rc = check_mask_predict(e, flags)) return rc;      // (its message stays: ENG_OK would put the call's text in its place)
     // (before anything is enqueued or captured: such a fork's launch must be one the fused generator takes)
     if (e->no_logits && !e->gen_rb_ok(B * e->cfg.seq_length)) return fail(BOFI_ERR_STATE, "this fork has no vocabulary-wide buffers and the launch would not take the fused generator");
     hipStream_t s = (hipStream_t)stream;
@@ -1615,7 +1663,7 @@ int bofi_engine_decode_naic(bofi_engine_t* e, const void* feats, int feats_dtype
                                   (uintptr_t)phrase_length, (uintptr_t)phrase_syn, (uintptr_t)memory_out, (uintptr_t)bound_iters,
                                   (uintptr_t)e->q1_group, (uintptr_t)e->bound_iter_cap, (uintptr_t)e->live_max, (uintptr_t)e->in_flight,
                                   (uintptr_t)bofi::g_env_generation, (uintptr_t)e->row_plogp_out, (uintptr_t)e->row_chosen_out,
-                                  (uintptr_t)e->sat_out, (uintptr_t)(e->loop_mode + 1), (uintptr_t)e->kv_beside};
+                                  (uintptr_t)e->sat_out, (uintptr_t)(e->loop_mode + 1), (uintptr_t)e->kv_beside, (uintptr_t)e->refine_round_out};
     return run_graphed(e, key, s, [&](hipStream_t cs) {
         return e->enqueue_decode(feats, feats_dtype, att_len, B, R, flags, seq, seq_logprob, phrase_num, phrase_length,
                                  phrase_syn, memory_out, bound_iters, cs);

@@ -178,7 +178,7 @@ class BofiEngine:
     def decode_naic(self, att_feats: torch.Tensor, att_len: Optional[torch.Tensor] = None, *, strict_q1: bool = True,
                     want_logprob: bool = True, want_memory: bool = False, raw_logits: bool = False, graph: bool = False,
                     refine_rounds: int = 0, out: Optional[dict] = None, q1_group: int = 0, iter_cap: int = 0, phases: str = "", row_stats: bool = False,
-                    ids_only: bool = False) -> dict:
+                    ids_only: bool = False, refine_method: str = "feed_back") -> dict:
         """Greedy NAIC bound+fill decode.  Returns a dict of device tensors: seq [B,S] int64,
         seq_logprob [B,S,V] float32 (or None), phrase_num [B] int32, phrase_length [B,S] int32,
         phrase_syn [B,S] int64, bound_iters [1] int32, memory [B,R,d] float32 (or None).
@@ -195,7 +195,12 @@ class BofiEngine:
         (float32 [B, S]; bofi_engine_set_row_stats_out) -- what ``row_stats(out)`` / ``entropy_perplexity(out)`` otherwise read back out of the log-prob tensor.
         ``ids_only`` (BOFI_FLAG_IDS_ONLY; implies ``want_logprob=False``, not with ``raw_logits``): the distribution is not wanted at all -- ids, layout and ``row_stats``
         only.  Where the row-block generator runs, generator and vocabulary epilogue are then one launch that writes no logits; the ids are the first maxima of the
-        raw logits.  ``row_stats(out)`` / ``sample_tokens(out)`` of such a result need ``row_stats=True`` / are not available: there is no distribution to read."""
+        raw logits.  ``row_stats(out)`` / ``sample_tokens(out)`` of such a result need ``row_stats=True`` / are not available: there is no distribution to read.
+        ``refine_method``: what the ``refine_rounds`` extra passes are.  'feed_back' (default): all of the previous ids as decoder input.  'mask_predict'
+        (BOFI_FLAG_MASK_PREDICT; ``refine_rounds`` >= 1, not with ``raw_logits``): pass t re-predicts the n (T + 1 - t) / (T + 1) least confident of an image's n
+        positions from BOS and keeps the rest; ``out['refine_round']`` (int32 [B, S]) names the pass that emitted each token, ``row_stats`` are those of the
+        emitting pass, and ``seq_logprob`` is the LAST pass's tensor (kept positions' rows are its re-prediction, not the distribution that emitted the token)."""
+        mp = self._refine_flag(refine_method, refine_rounds, raw_logits)
         if ids_only:
             if raw_logits:
                 raise hip.BofiHipError("ids_only: the raw logits are not produced")
@@ -233,6 +238,12 @@ class BofiEngine:
             self._row_stats_ptrs = rs
         out["_row_stats_fused"] = bool(row_stats)
         out["_ids_only"] = bool(ids_only)
+        if mp and out.get("refine_round") is None:
+            out["refine_round"] = torch.empty(B, S, dtype=torch.int32, device=dev)
+        rr = out["refine_round"].data_ptr() if mp else 0
+        if rr != getattr(self, "_refine_ptr", 0):
+            hip.check(self._lib.bofi_engine_set_refine_out(self._h, hip.ptr(out["refine_round"]) if mp else None), "bofi_engine_set_refine_out")
+            self._refine_ptr = rr
         if q1_group != getattr(self, "_q1_group", 0):
             hip.check(self._lib.bofi_engine_set_q1_group(self._h, int(q1_group)), "bofi_engine_set_q1_group")
             self._q1_group = q1_group
@@ -240,7 +251,7 @@ class BofiEngine:
             hip.check(self._lib.bofi_engine_set_bound_iter_cap(self._h, int(iter_cap)), "bofi_engine_set_bound_iter_cap")
             self._iter_cap = int(iter_cap)
         flags = ((hip.FLAG_STRICT_Q1 if strict_q1 else 0) | (hip.FLAG_RAW_LOGITS if raw_logits else 0) | (hip.FLAG_GRAPH if graph else 0)
-                 | (refine_rounds << hip.FLAG_REFINE_SHIFT) | (hip.FLAG_IDS_ONLY if ids_only else 0))
+                 | (refine_rounds << hip.FLAG_REFINE_SHIFT) | (hip.FLAG_IDS_ONLY if ids_only else 0) | mp)
         if phases:
             if set(phases) - set("ebf"):
                 raise hip.BofiHipError("phases: a subset of 'ebf'")
@@ -250,6 +261,19 @@ class BofiEngine:
             hip.ptr(out["seq_logprob"]), hip.ptr(out["phrase_num"]), hip.ptr(out["phrase_length"]), hip.ptr(out["phrase_syn"]),
             hip.ptr(out["memory"]), hip.ptr(out["bound_iters"]), hip.stream_ptr()), "bofi_engine_decode_naic")
         return out
+
+    @staticmethod
+    def _refine_flag(refine_method: str, refine_rounds: int, raw_logits: bool) -> int:
+        """BOFI_FLAG_MASK_PREDICT or 0 for a ``refine_method``; what the library would refuse is refused here, with the Python names."""
+        if refine_method not in ("feed_back", "mask_predict"):
+            raise hip.BofiHipError(f"refine_method {refine_method!r}: 'feed_back' or 'mask_predict'")
+        if refine_method == "feed_back":
+            return 0
+        if not 1 <= refine_rounds <= 15:
+            raise hip.BofiHipError("refine_method='mask_predict' needs refine_rounds in 1..15")
+        if raw_logits:
+            raise hip.BofiHipError("refine_method='mask_predict' ranks log-probs: not with raw logits (output_logsoftmax=0)")
+        return hip.FLAG_MASK_PREDICT
 
     def set_decodes_in_flight(self, n: int) -> None:
         """A hint for the kernel choice (bofi_engine_set_decodes_in_flight): 1 = this engine's launches run alone on the device (shorter
@@ -429,19 +453,25 @@ class BofiEngine:
         return llp, slp
 
     def fill_naic(self, ext_syn: torch.Tensor, last: torch.Tensor, R: int, att_len: Optional[torch.Tensor] = None, *, strict_q1: bool = True,
-                  raw_logits: bool = False, refine_rounds: int = 0):
+                  raw_logits: bool = False, refine_rounds: int = 0, refine_method: str = "feed_back"):
         """The filling pass alone on a given slot layout (``ext_syn`` int32 [B, S+2], ``last`` int32 [B]) and the memory of the
-        preceding ``encode``: (seq int64 [B, S], seq_logprob float32 [B, S, V])."""
+        preceding ``encode``: (seq int64 [B, S], seq_logprob float32 [B, S, V]); with ``refine_method='mask_predict'`` (as ``decode_naic``) a third
+        element, refine_round int32 [B, S]."""
+        mp = self._refine_flag(refine_method, refine_rounds, raw_logits)
         B = ext_syn.size(0)
         if ext_syn.dtype != torch.int32 or last.dtype != torch.int32 or ext_syn.size(1) != self.cfg.bound_len or last.numel() != B:
             raise hip.BofiHipError("ext_syn must be int32 [B, S+2] and last int32 [B]")
         S, V, dev = self.cfg.seq_length, self.cfg.tgt_vocab, ext_syn.device
         seq = torch.empty(B, S, dtype=torch.int64, device=dev)
         lp = torch.empty(B, S, V, dtype=torch.float32, device=dev)
-        flags = (hip.FLAG_STRICT_Q1 if strict_q1 else 0) | (hip.FLAG_RAW_LOGITS if raw_logits else 0) | (refine_rounds << hip.FLAG_REFINE_SHIFT)
+        flags = (hip.FLAG_STRICT_Q1 if strict_q1 else 0) | (hip.FLAG_RAW_LOGITS if raw_logits else 0) | (refine_rounds << hip.FLAG_REFINE_SHIFT) | mp
+        rnd = torch.empty(B, S, dtype=torch.int32, device=dev) if mp else None
+        if (rnd.data_ptr() if mp else 0) != getattr(self, "_refine_ptr", 0):
+            hip.check(self._lib.bofi_engine_set_refine_out(self._h, hip.ptr(rnd)), "bofi_engine_set_refine_out")
+            self._refine_ptr = rnd.data_ptr() if mp else 0
         hip.check(self._lib.bofi_engine_fill_naic(self._h, hip.ptr(ext_syn.contiguous()), hip.ptr(last.contiguous()), B, R, hip.ptr(att_len), flags,
                                                   hip.ptr(seq), hip.ptr(lp), hip.stream_ptr()), "bofi_engine_fill_naic")
-        return seq, lp
+        return (seq, lp, rnd) if mp else (seq, lp)
 
 
 class DecodePipeline:
@@ -462,7 +492,11 @@ class DecodePipeline:
     already in flight."""
 
     def __init__(self, engine: "BofiEngine", *, in_flight: Optional[int] = None, batches_per_launch: int = 16, strict_q1: bool = True, stats: bool = True,
-                 keep_logprob: bool = False, region_buckets=(36, 48, 64, 80, 100, 128), fused_vocab: bool = False):
+                 keep_logprob: bool = False, region_buckets=(36, 48, 64, 80, 100, 128), fused_vocab: bool = False,
+                 refine_rounds: int = 0, refine_method: str = "feed_back"):
+        BofiEngine._refine_flag(refine_method, refine_rounds, False)
+        # refine_rounds / refine_method: as BofiEngine.decode_naic; with 'mask_predict' every yielded dict also carries refine_round [b, S]
+        self.refine_rounds, self.refine_method = int(refine_rounds), refine_method
         if in_flight is None:                                    # 3 launch streams + the copy stream = the runtime's default of 4 hardware queues
             in_flight = 3
         if in_flight < 1 or batches_per_launch < 1:
@@ -624,9 +658,12 @@ class DecodePipeline:
             e = sl["eng_plain"]
         sl["ran"] = e
         sl["out"] = e.decode_naic(feats, lens, strict_q1=self.strict_q1, graph=True, out=sl["out"] if sl["out"] is not None and sl["out"]["seq"].shape[0] == rows else None,
-                                  q1_group=b if nb > 1 else 0, row_stats=self.stats, want_logprob=self.keep_logprob, ids_only=self.fused_vocab)
+                                  q1_group=b if nb > 1 else 0, row_stats=self.stats, want_logprob=self.keep_logprob, ids_only=self.fused_vocab,
+                                  refine_rounds=self.refine_rounds, refine_method=self.refine_method)
         out = sl["out"]
         small = {k2: out[k2] for k2 in ("seq", "phrase_num", "phrase_length", "phrase_syn", "bound_saturated")}
+        if self.refine_method == "mask_predict":
+            small["refine_round"] = out["refine_round"]
         if self.stats:
             small["entropy"], small["perplexity"] = e.entropy_perplexity(out)
         if sl["host"] is None or sl["host"]["seq"].shape[0] != rows:

@@ -17,6 +17,9 @@ references alone (integer rows or id strings; no loss then), or None.  ``eval_kw
     image_ixs        the label source's image of every row of ``feats`` (default 0 .. N - 1)
     verbose_loss     0: no loss pass;  vocab  {str(id): word} for the entries' 'caption'
     batches_per_launch, in_flight, fused_vocab     ``decode_many``'s knobs
+    refine_rounds, refine_method     NAIC only: extra filling passes as ``decode_many`` takes them ('feed_back', the default, or 'mask_predict'); with
+                     'mask_predict' the pass that emitted each token is stored under ``eval_kwargs['refine_round']`` (int32 [N, S]), and entropy /
+                     perplexity come from the emitting passes' statistics
     sample_n         N > 1 (or the ``sample_n`` argument): after the greedy pass, N captions per image are drawn through ``mode='sample'`` with
                      ``sample_method='sample'`` (eval_split_n, eval_utils.py:670-700, ``sample_n_method='sample'``); their entries are stored under
                      ``eval_kwargs['preds_n']``, and ``lang_stats`` gains the diversity statistics of boficap_amd.diversity ('Div-1', 'Div-2',
@@ -153,6 +156,10 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
     if mode not in ("NAIC", "SAIC"):
         raise NotImplementedError(f"inference mode {mode!r}: a UIC model decodes in 'NAIC' or 'SAIC' mode")
     batch_size, seq_per_img = int(kw.get("batch_size", 64)), int(kw.get("seq_per_img", 5))
+    refine = {"refine_rounds": int(kw.get("refine_rounds", 0)), "refine_method": kw.get("refine_method", "feed_back")}
+    if mode != "NAIC" and (refine["refine_rounds"] or refine["refine_method"] != "feed_back"):
+        raise ValueError("refine_rounds / refine_method refine the non-autoregressive filling pass: inference_mode 'NAIC' only")
+    rounds = []
     N = len(feats)
     ixs = kw.get("image_ixs")
     store = store_or_gts if hasattr(store_or_gts, "batch") and hasattr(store_or_gts, "gts") else None
@@ -173,8 +180,9 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
             if mode == "NAIC" and ragged:                       # staged ragged batch by batch, ahead of the launches that consume them
                 i = 0
                 for r in model.decode_many((feats.ragged(j, min(j + batch_size, N)) for j in range(0, N, batch_size)), batches_per_launch=int(kw.get("batches_per_launch", 16)),
-                                           in_flight=kw.get("in_flight"), fused_vocab=bool(kw.get("fused_vocab", False))):
+                                           in_flight=kw.get("in_flight"), fused_vocab=bool(kw.get("fused_vocab", False)), **refine):
                     n = r["seq"].size(0)
+                    rounds.append(r.get("refine_round"))
                     predictions.extend(entry_of(i, k, r["seq"], r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"], vocab) for k in range(n))
                     seqs.append(r["seq"]); ents.append(r["entropy"]); ppls.append(r["perplexity"])
                     i += n
@@ -188,8 +196,9 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
                 batches = [host[i:i + batch_size] for i in range(0, N, batch_size)]
                 i = 0
                 for r in model.decode_many(batches, batches_per_launch=int(kw.get("batches_per_launch", 16)), in_flight=kw.get("in_flight"),
-                                           fused_vocab=bool(kw.get("fused_vocab", False))):
+                                           fused_vocab=bool(kw.get("fused_vocab", False)), **refine):
                     n = r["seq"].size(0)
+                    rounds.append(r.get("refine_round"))
                     predictions.extend(entry_of(i, k, r["seq"], r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"], vocab) for k in range(n))
                     seqs.append(r["seq"]); ents.append(r["entropy"]); ppls.append(r["perplexity"])
                     i += n
@@ -206,6 +215,8 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
                     seq, pn, pl, ent, ppl = seq.cpu(), pn.cpu(), pl.cpu(), ent.cpu(), ppl.cpu()
                     predictions.extend(entry_of(i, k, seq, pn, pl, ent, ppl, vocab) for k in range(att.size(0)))
                     seqs.append(seq); ents.append(ent); ppls.append(ppl)
+        if refine["refine_method"] == "mask_predict":
+            kw["refine_round"] = torch.cat(rounds)
         lang_stats, ev = None, None
         if int(kw.get("language_eval", 0)) == 1:
             ev = kw.get("lang_eval")

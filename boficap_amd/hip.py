@@ -19,6 +19,7 @@ FLAG_SAMPLE = 16
 FLAG_PHASE_ENCODE, FLAG_PHASE_BOUND, FLAG_PHASE_FILL = 32, 64, 128
 FLAG_SAIC_LAYOUT_ONLY = 4096
 FLAG_IDS_ONLY = 8192
+FLAG_MASK_PREDICT = 16384
 FORK_IDS_ONLY = 1
 ABI_VERSION = 4
 
@@ -124,6 +125,8 @@ SIGNATURES = {
     "bofi_diversity_score": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, C.c_double, _P, _I64, _P, _P, _P, _P, _P]),
     "bofi_oracle_stats": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "bofi_pack_regions": (_I, [_P, _I, _P, _P, _I, _I, _P, _I, _I, _I, _P, _P]),
+    "bofi_engine_set_refine_out": (_I, [_P, _P]),
+    "bofi_mask_predict_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

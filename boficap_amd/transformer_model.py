@@ -240,7 +240,7 @@ class TransformerModel(nn.Module):
         return saic, naic
 
     def decode_many(self, batches, *, batches_per_launch: int = 16, in_flight: Optional[int] = None, stats: bool = True, keep_logprob: bool = False,
-                    fused_vocab: bool = False):
+                    fused_vocab: bool = False, refine_rounds: int = 0, refine_method: str = "feed_back"):
         """Greedy NAIC decode of MANY loader batches at the engine's throughput -- the eval loop of the reference (eval_utils.py:456-460: one synchronised
         ``model(..., mode='sample')`` per batch, which is what ``_sample`` reproduces) as a pipeline: ``in_flight`` engine forks on overlapping streams,
         ``batches_per_launch`` consecutive batches per launch (quirk Q1 per batch: every batch's result is its own decode's), features copied from (pinned)
@@ -251,14 +251,17 @@ class TransformerModel(nn.Module):
         ``features.RaggedBatch``es (real rows only, in the files' dtype: padding, cast and norm_att_feat happen on the device).
         Yields one dict per batch, in order: seq [b, S] int64, phrase_num [b] int32, phrase_length [b, S] int32, phrase_syn [b, S] int64 (+ entropy,
         perplexity [b] as eval_utils.py:463-464 with ``stats``; + seq_logprob [b, S, V] on the device with ``keep_logprob``), host tensors.
-        ``fused_vocab``: ids-only launches on forks without the vocabulary-wide buffers (``DecodePipeline(fused_vocab=True)``; not with ``keep_logprob``)."""
+        ``fused_vocab``: ids-only launches on forks without the vocabulary-wide buffers (``DecodePipeline(fused_vocab=True)``; not with ``keep_logprob``).
+        ``refine_rounds`` / ``refine_method``: extra filling passes as ``BofiEngine.decode_naic`` takes them; with 'mask_predict' every dict also carries
+        refine_round [b, S] int32, the pass that emitted each token."""
         from .engine import DecodePipeline
         eng = self.engine()
-        key = (id(eng), batches_per_launch, in_flight, stats, keep_logprob, self.strict_reference, fused_vocab)
+        key = (id(eng), batches_per_launch, in_flight, stats, keep_logprob, self.strict_reference, fused_vocab, int(refine_rounds), refine_method)
         cached = self.__dict__.get("_pipeline")
         if cached is None or cached[0] != key:
             cached = self.__dict__["_pipeline"] = (key, DecodePipeline(eng, in_flight=in_flight, batches_per_launch=batches_per_launch, strict_q1=self.strict_reference,
-                                                                       stats=stats, keep_logprob=keep_logprob, fused_vocab=fused_vocab))
+                                                                       stats=stats, keep_logprob=keep_logprob, fused_vocab=fused_vocab,
+                                                                       refine_rounds=refine_rounds, refine_method=refine_method))
 
         def items():
             from .features import RaggedBatch
@@ -293,6 +296,20 @@ class TransformerModel(nn.Module):
         if sample_method not in ("greedy", "sample"):
             raise NotImplementedError(f"sample_method {sample_method!r}: greedy and 'sample' (Categorical) are built; "
                                       "gumbel / top-k / top-p are autoregressive-path options")
+        # opt['refine_rounds'] / opt['refine_method']: extra filling passes of the NAIC decode (BofiEngine.decode_naic); the 6-tuple stays, and a
+        # mask-predict decode leaves the pass that emitted each token in self.last_refine_round and the emitting passes' (sum_v p log p, log-prob of the id)
+        # in self.last_refine_row_stats (None otherwise)
+        refine_rounds, refine_method = int(opt.get("refine_rounds", 0)), opt.get("refine_method", "feed_back")
+        if refine_method not in ("feed_back", "mask_predict"):
+            raise hip.BofiHipError(f"refine_method {refine_method!r}: 'feed_back' or 'mask_predict'")
+        if (refine_rounds or refine_method != "feed_back") and train_mode != "NAIC":
+            raise hip.BofiHipError("refine_rounds / refine_method refine the non-autoregressive filling pass: train_mode 'NAIC' only")
+        if refine_method == "mask_predict" and sample_method == "sample":
+            raise hip.BofiHipError("refine_method='mask_predict' refines greedy picks: not with sample_method='sample'")
+        if refine_method == "mask_predict" and not output_logsoftmax:
+            raise hip.BofiHipError("refine_method='mask_predict' ranks log-probs: not with raw logits (output_logsoftmax=0)")
+        rkw = dict(refine_rounds=refine_rounds, refine_method=refine_method, row_stats=refine_method == "mask_predict")
+        self.last_refine_round = self.last_refine_row_stats = None
         eng = self.engine()
         torch.cuda.synchronize()                                  # the reference does (AttModel.py:337)
         start = time.time()
@@ -309,17 +326,19 @@ class TransformerModel(nn.Module):
             feats_in, lens_in = self._as_input(att_feats), self._att_len(att_masks)
             if cap and eng.bound_loop_active(feats_in.size(1)):  # the persistent loop kernel ends by itself and ignores the budget: the first decode IS complete
                 cap = 0                                          # (a repeat on live >= cap would be a redundant second decode)
-            r = eng.decode_naic(feats_in, lens_in, strict_q1=self.strict_reference, raw_logits=not output_logsoftmax, iter_cap=cap)
+            r = eng.decode_naic(feats_in, lens_in, strict_q1=self.strict_reference, raw_logits=not output_logsoftmax, iter_cap=cap, **rkw)
             live = int(r["bound_iters"])                          # (a device -> host read: the reference synchronises here too, AttModel.py:337)
             sat = eng.saturated(r)                                # fp16 saturation word of the loop kernel (0 for every model seen so far): fall back to the bf16 iterations
             if sat:
-                r = eng._redo_without_loop_kernel(sat, lambda: eng.decode_naic(feats_in, lens_in, strict_q1=self.strict_reference, raw_logits=not output_logsoftmax, out=r, iter_cap=0))
+                r = eng._redo_without_loop_kernel(sat, lambda: eng.decode_naic(feats_in, lens_in, strict_q1=self.strict_reference, raw_logits=not output_logsoftmax, out=r, iter_cap=0, **rkw))
                 live = int(r["bound_iters"])
             if cap and live >= cap:
-                r = eng.decode_naic(feats_in, lens_in, strict_q1=self.strict_reference, raw_logits=not output_logsoftmax, out=r, iter_cap=0)
+                r = eng.decode_naic(feats_in, lens_in, strict_q1=self.strict_reference, raw_logits=not output_logsoftmax, out=r, iter_cap=0, **rkw)
                 live = int(r["bound_iters"])
             recent.append(live)
             del recent[:-8]
+            if refine_method == "mask_predict":                 # (the log-prob tensor is the last pass's: the emitting passes' row statistics are kept beside the rounds)
+                self.last_refine_round, self.last_refine_row_stats = r["refine_round"], (r["row_plogp"], r["row_chosen"])
         elif sample_method == "greedy":                           # core_SAIC, AttModel.py:430-437
             # (the loop is enqueued for the iterations recent decodes needed, the rest only if this one needs them: saic_cap / saic_finish)
             adaptive = getattr(self.opt, "bofi_saic_iter_budget", True)

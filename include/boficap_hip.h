@@ -397,6 +397,9 @@ const float* bofi_engine_logprob(bofi_engine_t* e);
  * that every following bofi_engine_decode_naic of this engine fills (greedy decodes with log-softmax; NULL, NULL: off -- the default, also of a fork).  Per-call state,
  * part of the graph key.  sum_v p log p is formed as sum_v e_v (x_v - max) / sum_v e_v - lse in the pass that sums the exponentials. */
 int bofi_engine_set_row_stats_out(bofi_engine_t* e, float* row_plogp, float* row_chosen);
+/* Optional output of decodes under BOFI_FLAG_MASK_PREDICT: int32 [B * S] device buffer that receives, per position, the pass (0 .. T) that emitted the
+ * token standing there (0 on the pad tail); NULL: off -- the default, also of a fork.  Per-call state, part of the graph key. */
+int bofi_engine_set_refine_out(bofi_engine_t* e, int* emitted_round);
 
 /* A HIP stream owned by the engine (hipStream_t as void*), for callers that keep one decode per engine in
  * flight and want each on its own hardware queue. */
@@ -426,6 +429,17 @@ void* bofi_engine_stream(bofi_engine_t* e);
                                        bofi_vocab_block launch: no logits in memory; the pick is the first maximum of the raw logits (it can differ from the log-softmax
                                        path's only where two log-probs round to one float32).  Elsewhere the flag is honoured by the generator into the workspace and
                                        the epilogue without its store.  Part of the graph key, as every flag. */
+#define BOFI_FLAG_MASK_PREDICT 16384 /* decode_naic / fill_naic (phased form included), only with T = bits 8..11 >= 1: the T extra filling passes are MASK-PREDICT rounds instead
+                                       of feed-back rounds.  n_b = last[b] - 1 tokens are laid out for image b.  The state (y, c, e, emitted_round) [B, S] holds per position the
+                                       id, the log-prob of that id, sum_v p log p of the row that emitted it, and the pass that did.  Pass 0 is today's (BOS everywhere) and fills
+                                       the state.  Pass t = 1 .. T: k = n_b (T + 1 - t) / (T + 1) (integer division); its mask is the k positions s < n_b with the lowest c[s] -- ties go
+                                       to the lower position, a NaN ranks below every number, NaNs among themselves by position; its input ids are BOS under the mask and y[s] elsewhere
+                                       (s >= n_b: pad, as feed-back); positions in the mask take the pass's id and statistics and emitted_round = t, the others keep the state; s >= n_b
+                                       always takes the fresh pass's values (pad, emitted_round 0).  Outputs: seq = y after pass T; the buffers of bofi_engine_set_row_stats_out
+                                       receive c and e of the STATE (each position's figures come from the pass that emitted its token); seq_logprob, when wanted, is the LAST pass's
+                                       tensor -- the rows of kept positions are that pass's re-prediction, not the distribution that emitted the token; emitted_round goes to the buffer
+                                       of bofi_engine_set_refine_out.  Costs T + 1 launches of bofi_mask_predict_step's kernel per decode over feed-back.  BOFI_ERR_ARG before any
+                                       launch: T = 0, BOFI_FLAG_RAW_LOGITS, BOFI_FLAG_SAMPLE, bofi_engine_decode_saic, seq_length > 64. */
 
 /* model(fc, att, att_masks, opt={'train_mode':'NAIC','sample_method':'greedy'}, mode='sample'):
  * AttModel._sample AttModel.py:307-338,419-429 -> _prepare_feature TransformerModel.py:1674-1690
@@ -684,6 +698,19 @@ int bofi_oracle_stats(const int* comps, const double* cider, const double* rouge
  * holds, so it never writes outside out.  One launch, no synchronisation. */
 int bofi_pack_regions(const void* rows, int rows_dtype, const int* offsets, const int* offsets_host, int B, int F, void* out, int out_dtype,
                       int out_R, int norm, int* att_len, void* stream);
+
+/* The step between two passes of a mask-predict refinement (BOFI_FLAG_MASK_PREDICT states the rules), on given arrays; all buffers [B, S], S <= 64.
+ *   ids int64, chosen / plogp float32, round int32: the state (y, c, e, emitted_round), read and written.
+ *   fresh_ids / fresh_chosen / fresh_plogp: what pass t left (ids after the pad-tail rule, the log-prob of each id, sum_v p log p).
+ *   mask int32: in, the mask of pass t (not read at t = 0: every position is taken); out when t < T, the mask of pass t + 1 (1 = re-predict).
+ *   next_ids int64: out when t < T, the input ids of pass t + 1 (bos_idx under the mask, the state's id elsewhere).
+ *   last int32 [B]: 1 + tokens laid out (n_b = last[b] - 1, clamped to 0 .. S).
+ *   seq_out int64, plogp_out / chosen_out float32 (both or NULL), round_out int32 (or NULL): written when t = T only, the state after the merge.
+ * B < 1, S outside 1..64, not 0 <= t <= T <= 15, a NULL among state / fresh / mask / next_ids / last, a NULL seq_out at t = T: BOFI_ERR_ARG, nothing is launched.
+ * One launch, one wavefront per image, comparisons only: deterministic. */
+int bofi_mask_predict_step(int64_t* ids, float* chosen, float* plogp, int* round, const int64_t* fresh_ids, const float* fresh_chosen,
+                           const float* fresh_plogp, int* mask, int64_t* next_ids, const int* last, int B, int S, int t, int T, int bos_idx,
+                           int pad_idx, int64_t* seq_out, float* plogp_out, float* chosen_out, int* round_out, void* stream);
 
 /* Last HIP error string seen by this library on the calling thread (for exceptions in the host). */
 const char* bofi_last_error(void);

@@ -12,6 +12,8 @@ dictionary; boficap_amd.features): the images and their ids are the json's split
 padded on the device, ``image_id`` in the predictions is the json's id, and image i of the split uses image ``split_ix[i]`` of ``--input_label_npz``.
 Box features (``--use_box 1``) are refused: they make F = 2053 and the engine needs F % 64 == 0.  ``--language_eval 1`` (with ``--input_label_npz``: the references) adds the language scores that need no Java -- BLEU-1..4,
 ROUGE-L, CIDEr on the device (boficap_amd.lang_eval) -- as a printed line and, in ``--dump_json``, under a top-level key.
+``--refine_rounds N [--refine_method feed_back|mask_predict]`` (NAIC) adds N filling passes: on all of the previous ids, or -- mask-predict -- on the least
+confident positions only.
 ``--sample_n N`` (N > 1, with ``--cached_tokens``: the document frequencies) draws N captions per image after the greedy pass and adds their
 diversity statistics -- Div-1, Div-2, mBLEU-1..4, self-CIDEr on the device (boficap_amd.diversity) -- the same way, with the sampled captions under
 ``preds_n``.  ``--eval_oracle 1`` (with ``--language_eval 1 --sample_n N``) scores every sampled caption against its image's references and adds
@@ -68,7 +70,15 @@ def main():
                     "name resolved as data/<name>.p")
     ap.add_argument("--eval_oracle", type=int, default=0, choices=[0, 1], help="1 (with --language_eval 1 --sample_n N): oracle_<M> and avg_<M>, the best and the "
                     "mean of an image's N sampled captions, for BLEU-1..4, ROUGE-L and CIDEr against the references")
+    ap.add_argument("--refine_rounds", type=int, default=0, help="NAIC only: N extra filling passes (0..15) after the first")
+    ap.add_argument("--refine_method", default="feed_back", choices=["feed_back", "mask_predict"], help="what the extra passes are: 'feed_back' decodes again on all of the "
+                    "previous ids; 'mask_predict' (needs --refine_rounds >= 1) re-predicts only each caption's least confident positions, fewer every pass, and keeps the rest")
     args = ap.parse_args()
+    if (args.refine_rounds or args.refine_method != "feed_back") and args.inference_mode != "NAIC":
+        ap.error("--refine_rounds / --refine_method refine the non-autoregressive filling pass: they need --inference_mode NAIC")
+    if not 0 <= args.refine_rounds <= 15 or (args.refine_method == "mask_predict" and args.refine_rounds < 1):
+        ap.error("--refine_rounds must be in 0..15, and --refine_method mask_predict needs at least 1")
+    refine = {"refine_rounds": args.refine_rounds, "refine_method": args.refine_method}
     if args.language_eval and not args.input_label_npz:
         ap.error("--language_eval 1 needs the references: --input_label_npz")
     if args.use_box:
@@ -142,12 +152,12 @@ def main():
             def feeder(kb):
                 return RegionFeeder(att_store, kb, workers=args.feeder_workers, norm_att_feat=bool(args.norm_att_feat))
             for _ in model.decode_many(feeder(key_batches[:2 * args.in_flight * args.batches_per_launch]), batches_per_launch=args.batches_per_launch, in_flight=args.in_flight,
-                                       fused_vocab=args.fused_vocab):
+                                       fused_vocab=args.fused_vocab, **refine):
                 pass                                             # graph captures and stream choice, outside the clock
             torch.cuda.synchronize()
             import time
             t0 = time.time()
-            got = list(model.decode_many(feeder(key_batches), batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab))
+            got = list(model.decode_many(feeder(key_batches), batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab, **refine))
             seconds = time.time() - t0
             i = 0
             for r in got:
@@ -164,12 +174,12 @@ def main():
                 host = host.to(torch.bfloat16)
             host = host.pin_memory()
             batches = [host[i:i + args.batch_size] for i in range(0, host.size(0), args.batch_size)]
-            for _ in model.decode_many(batches[:2 * args.in_flight * args.batches_per_launch], batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab):
+            for _ in model.decode_many(batches[:2 * args.in_flight * args.batches_per_launch], batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab, **refine):
                 pass                                             # graph captures and stream choice, outside the clock
             torch.cuda.synchronize()
             import time
             t0, got = time.time(), []
-            for r in model.decode_many(batches, batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab):
+            for r in model.decode_many(batches, batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab, **refine):
                 got.append(r)                                    # host tensors of one batch: ids, slot layout, entropy, perplexity
             seconds = time.time() - t0
             i = 0
@@ -185,10 +195,15 @@ def main():
                 else:
                     att, masks = torch.from_numpy(np.ascontiguousarray(feats[i:i + args.batch_size])).cuda(), None
                 fc = torch.zeros(att.size(0), 0, device="cuda")
-                seq, lp, pn, pl, ps, t = model(fc, att, masks, opt={"train_mode": args.inference_mode, "sample_method": "greedy", "sample_n": 1}, mode="sample")
+                seq, lp, pn, pl, ps, t = model(fc, att, masks, opt=dict({"train_mode": args.inference_mode, "sample_method": "greedy", "sample_n": 1},
+                                                                                   **(refine if args.inference_mode == "NAIC" else {})), mode="sample")
                 seconds += t
-                # per-image entropy / perplexity as eval_utils.py:463-464, from the fused row reductions (bofi_vocab_stats)
-                ent, ppl = model.engine().entropy_perplexity({"seq": seq, "seq_logprob": lp})
+                # per-image entropy / perplexity as eval_utils.py:463-464, from the fused row reductions (bofi_vocab_stats); under mask-predict from the statistics of
+                # the pass that emitted each token (the log-prob tensor is the last pass's)
+                if args.refine_method == "mask_predict":
+                    ent, ppl = model.engine().entropy_perplexity({"seq": seq, "_row_stats_fused": True, "row_plogp": model.last_refine_row_stats[0], "row_chosen": model.last_refine_row_stats[1]})
+                else:
+                    ent, ppl = model.engine().entropy_perplexity({"seq": seq, "seq_logprob": lp})
                 results.extend(entry_of(i, k, seq, pn, pl, ent, ppl) for k in range(att.size(0)))
             how = "one synchronised mode='sample' call per batch (the reference's eval loop), decode time only"
     if image_ids is not None:                                    # the json's ids, in the split's order
