@@ -605,7 +605,7 @@ class XETrainer:
                 pair_w_sa=t(w2 * ~na), pair_w_na=t(w2 * na))
             if all(k in host_batch for k in ("phrase_num", "extend_phrase_syn_seq", "extend_phrase_seq", "extend_phrase_seq_mask")) \
                     and batch.get("max_phrase_num") is not None:
-                # ... and every index tensor the paired forward would otherwise derive on the device (xe._forward_paired): the bound
+                # ... and every index tensor the paired forward would otherwise derive on the device (xe._paired_bound_inputs, xe._paired_fill_inputs): the bound
                 # passes' inputs and key counts, the decoder rows' token / label ids, positions and key counts
                 cfg = self.model.cfg
                 L = S + 2

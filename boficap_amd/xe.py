@@ -15,7 +15,8 @@ the buffers, the tape and the parameter tensors.  Differences in STRUCTURE from 
     share one bound pass and one decoder pass (_fill_unpadded, _forward_paired).
 
 What a caller knows about the batch is an argument (``forward_uic(..., plan=StepPlan(...))``; no plan: the reference's dense forward);
-what lasts for one forward + backward is set by ``step_state`` and put back when it ends.
+what lasts for one forward + backward is set by ``step_state`` and put back when it ends; what one forward's stages share -- weights,
+dropout sites, memory, cross K|V, batch sizes -- travels as one ``_Fwd`` (made by ``_begin_forward``, the preamble of every forward here).
 
 float32 is the parity mode.  In bf16 mode (GEMM operands bf16, everything else float32) the module keeps a few per-step
 side tables, all cleared by the next forward:
@@ -37,7 +38,8 @@ from __future__ import annotations
 
 import ctypes as C
 import contextlib
-from dataclasses import dataclass
+from collections import namedtuple
+from dataclasses import dataclass, field, replace
 from typing import Optional
 
 import torch
@@ -68,12 +70,12 @@ def _need(t: torch.Tensor, what: str) -> torch.Tensor:
 
 
 # GEMM compute dtype of the training path: float32 (parity) or bfloat16 operands with float32 accumulation, outputs,
-# master weights and gradients (BASELINE config 3).  Set per forward pass by forward_uic.
+# master weights and gradients (BASELINE config 3).  Set per forward pass by _begin_forward.
 _COMPUTE = {"dtype": torch.float32}
 
 # GEMM operands made during the current step: (kind, data_ptr, shape, dtype) -> (source kept alive, operand).  A weight
 # that serves two passes (the decoder runs for the SA and the NA branch) and the image memory that feeds every cross
-# K/V projection are cast / transposed once per step instead of once per use.  Cleared by forward_uic.
+# K/V projection are cast / transposed once per step instead of once per use.  Cleared by _begin_forward.
 _STEP_CACHE: dict = {}
 
 # bf16 mode keeps activations that only ever feed a GEMM / attention kernel as bf16 "shadows" made by their producer
@@ -846,78 +848,174 @@ def _ffn(P, pre, drop, n, x):
     return _sublayer_linear(P, drop, h, pre + ".w_2", x)
 
 
-def encode_memory(P, cfg, att_feats, att_len, drop):
+_TOK, _SYN = "model.tgt_embed.lut.weight", "model.syn_embed.lut.weight"
+
+
+@dataclass
+class _Fwd:
+    """One forward pass over one batch (_begin_forward): the weights, the dropout sites, the images and their encoded memory, the cross
+    K|V made from it so far, and the sizes every stage below reads -- B images of R regions, N captions (spi per image), S decoder
+    positions, L = seq_length + 2 bound positions.  ``att_len_cap`` int32 [N]: regions of each caption's image (None: all R)."""
+    P: Params
+    cfg: object
+    drop: _Drop
+    att_feats: torch.Tensor
+    att_len: Optional[torch.Tensor]
+    att_len_cap: Optional[torch.Tensor]
+    B: int
+    R: int
+    N: int
+    spi: int
+    S: int
+    L: int
+    memory: Optional[torch.Tensor] = None
+    kv_cache: dict = field(default_factory=dict)
+
+    @property
+    def dev(self):
+        return self.att_feats.device
+
+    def view(self, **changes) -> "_Fwd":
+        """The same pass with some fields replaced (the paired batch: N and spi doubled); the dropout sites and the cache stay the one object."""
+        return replace(self, **changes)
+
+    def emb(self, tok, syn, Lp, pos=None):
+        P, drop = self.P, self.drop
+        x = embed(P[_TOK] if tok is not None else None, P[_SYN] if syn is not None else None, P["model.pos_embed.pe"], tok, syn, Lp,
+                  P.g(_TOK) if tok is not None else None, P.g(_SYN) if syn is not None else None, pos)
+        return drop(x) if drop.on and drop.p > 0.0 else x
+
+    def vocab(self, x):
+        return self.P.lin(x, "model.generator.proj")
+
+    def pad_slots(self, t, Pm):
+        """[N, Pm, .] of Pm bound passes -> [N, L - 1, .]: pass i lands in slot i of the returned [:, 1:] view."""
+        out = t.new_zeros(self.N, self.L - 1, t.shape[2])
+        out[:, :Pm] = t
+        return out
+
+    def cross_kv(self, pre):
+        """K|V of the memory for the cross-attention ``pre``: they depend on the memory and the layer only, so every pass over it shares them."""
+        if pre not in self.kv_cache:
+            self.kv_cache[pre] = self.P.lin_packed(self.memory, pre, (1, 2))
+        return self.kv_cache[pre]
+
+    def prefill_cross_kv(self, with_bound=False):
+        """Every decoder layer's cross K|V (and the bound layer's) now, with the tape: ahead of a tape-free glancing pass, or of streams that part."""
+        for l in range(self.cfg.N_dec):
+            self.cross_kv(f"model.decoder.layers.{l}.src_attn")
+        if with_bound:
+            self.cross_kv("model.length_predictor.LengthPredictor.0.src_attn")
+
+
+def _begin_forward(P, cfg, att_feats, att_masks, *, N=None, spi=None, S=None, training=False, seed=None, compute_dtype=torch.float32,
+                   step_word=None) -> _Fwd:
+    """The preamble of every training forward: sets the compute dtype and clears the per-step tables, clips the regions to the batch's
+    longest image (clip_att, AttModel.py:113-120), and sizes the batch from ``N`` captions or ``spi`` captions per image.  The memory is
+    the caller's next step (encode_memory, or a kept one)."""
+    if compute_dtype not in (torch.float32, torch.bfloat16):
+        raise hip.BofiHipError(f"training compute dtype {compute_dtype}: float32 or bfloat16")
+    _COMPUTE["dtype"] = compute_dtype
+    _STEP_CACHE.clear()
+    _SHADOW_ONLY.clear()
+    att_len = None
+    if att_masks is not None:
+        max_len = int(att_masks.long().sum(1).max())
+        att_feats, att_masks = att_feats[:, :max_len].contiguous(), att_masks[:, :max_len]
+        att_len = att_masks.long().sum(1).to(torch.int32).contiguous()
+    att_feats = _need(att_feats.float() if att_feats.dtype != torch.float32 else att_feats, "att_feats")
+    B, R, _ = att_feats.shape
+    N = B * spi if N is None else N
+    if N % B:
+        raise hip.BofiHipError(f"{N} captions for {B} images")
+    spi = N // B
+    att_len_cap = None if att_len is None else att_len.repeat_interleave(spi).contiguous()
+    drop = _Drop(cfg.dropout, cfg.drop_prob_lm, seed if training else None, step_word)
+    return _Fwd(P, cfg, drop, att_feats, att_len, att_len_cap, B, R, N, spi, cfg.seq_length if S is None else S, cfg.seq_length + 2)
+
+
+def _flat_captions(labels, *more):
+    """The loader's [images, seq_per_img, ...] caption tensors as [N, ...]."""
+    return tuple(t.reshape(-1, *t.shape[2:]) if labels.dim() == 3 else t for t in (labels,) + more)
+
+
+def encode_memory(fwd):
     """att_embed (TransformerModel.py:1642-1645 + pack_wrapper AttModel.py:36-44) and the encoder stack
     (:1366-1383): returns memory [B*R, d]."""
-    B, R, Fdim = att_feats.shape
+    P, cfg, drop, att_len = fwd.P, fwd.cfg, fwd.drop, fwd.att_len
+    B, R, Fdim = fwd.att_feats.shape
     d = cfg.d_model
-    x = P.lin(att_feats.reshape(B * R, Fdim), "att_embed.0", relu=True, row_len=att_len, rpg=R)
+    x = P.lin(fwd.att_feats.reshape(B * R, Fdim), "att_embed.0", relu=True, row_len=att_len, rpg=R)
     if drop.on:
-        x = drop(x, None, drop.p_att)
+        x = drop(x, p=drop.p_att)
     sb = 1 if att_len is not None else 0
     for l in range(cfg.N_enc):
         p = f"model.encoder.layers.{l}"
         xr, n = P.ln_res(x, p + ".sublayer.0.norm")
         qkv = P.lin_packed(n, p + ".self_attn", (0, 1, 2))
-        ctx = attention(qkv, qkv, 0, d, 2 * d, B, cfg.h, R, R, 1, att_len, sb, 0, 0, drop.attn(), None, True)
+        ctx = attention(qkv, qkv, 0, d, 2 * d, B, cfg.h, R, R, kdiv=1, klen=att_len, klen_sb=sb, klen_sq=0, klen_bias=0, drop=drop.attn(),
+                        grad_bf16=True)
         x = _sublayer_linear(P, drop, ctx, p + ".self_attn.linears.3", xr)
         xr, n = P.ln_res(x, p + ".sublayer.1.norm")
         x = _ffn(P, p + ".feed_forward", drop, n, xr)
     return P.ln(x, "model.encoder.norm")
 
 
-def _cross(P, pre, cfg, drop, n, x, memory, kv_cache, B, Lq, R, spi, att_len_cap, seg=None, seg_img=None, grad_bf16=True):
-    """x + src_attn(n, memory, memory): the image's keys are shared by its captions (kdiv) and, because they depend
-    on the memory and the layer only, by the SA and the NA pass of the same layer (kv_cache).  ``seg``: unpadded query rows
-    (then ``att_len_cap`` holds one key count per ROW)."""
+def _cross(fwd, pre, n, x, Lq, cap, seg=None, seg_img=None):
+    """x + src_attn(n, memory, memory) for fwd.N query sequences of Lq rows: the image's keys are shared by its captions (kdiv) and by
+    every pass over the same layer (_Fwd.cross_kv).  ``cap``: int32 key count per sequence, or None.  ``seg``: unpadded query rows (then
+    ``cap`` holds one key count per ROW)."""
+    P, cfg, drop = fwd.P, fwd.cfg, fwd.drop
     d = cfg.d_model
     q = P.lin(n, pre + ".linears.0", shadow=True)
-    if pre not in kv_cache:
-        kv_cache[pre] = P.lin_packed(memory, pre, (1, 2))
+    kv = fwd.cross_kv(pre)
     if seg is not None and seg_img is not None and _COMPUTE["dtype"] == torch.bfloat16:
         # unpadded rows, bf16 kernels: one item per IMAGE (its captions' rows are one contiguous run) instead of one per caption --
         # fuller 16-row tiles in the forward, and the MFMA backward walks runs in chunks anyway
-        ctx = attention(q, kv_cache[pre], 0, 0, d, B // spi, cfg.h, seg_img[2], R, 1, att_len_cap, 0, 1, 0, drop.attn(),
-                        (seg_img[0], seg_img[1], False) + tuple(seg[2:3]), True)
+        ctx = attention(q, kv, 0, 0, d, fwd.N // fwd.spi, cfg.h, seg_img[2], fwd.R, kdiv=1, klen=cap, klen_sb=0, klen_sq=1, klen_bias=0,
+                        drop=drop.attn(), seg=(seg_img[0], seg_img[1], False) + tuple(seg[2:3]), grad_bf16=True)
         return _sublayer_linear(P, drop, ctx, pre + ".linears.3", x)
-    sb = 0 if seg is not None else (1 if att_len_cap is not None else 0)
-    ctx = attention(q, kv_cache[pre], 0, 0, d, B, cfg.h, Lq, R, spi, att_len_cap, sb, (1 if seg is not None else 0), 0, drop.attn(),
-                    None if seg is None else (seg[0], seg[1], False) + tuple(seg[2:3]), grad_bf16)
+    sb = 0 if seg is not None else (1 if cap is not None else 0)
+    ctx = attention(q, kv, 0, 0, d, fwd.N, cfg.h, Lq, fwd.R, kdiv=fwd.spi, klen=cap, klen_sb=sb, klen_sq=1 if seg is not None else 0, klen_bias=0,
+                    drop=drop.attn(), seg=None if seg is None else (seg[0], seg[1], False) + tuple(seg[2:3]), grad_bf16=True)
     return _sublayer_linear(P, drop, ctx, pre + ".linears.3", x)
 
 
-def decode_rows(P, cfg, drop, x, memory, kv_cache, N, S, R, spi, klen_self, att_len_cap, out_gemm_only=True, seg=None, seg_img=None):
-    """Decoder stack + final norm (TransformerModel.py:1386-1413) over N captions x S positions; self-attention
+def decode_rows(fwd, x, klen_self, *, out_gemm_only=True, seg=None, seg_img=None, cross_len=None):
+    """Decoder stack + final norm (TransformerModel.py:1386-1413) over fwd.N captions x fwd.S positions; self-attention
     row (n, i) sees keys < klen_self[n, i].  ``out_gemm_only`` False: the output is also read outside a GEMM (row gather).
 
     ``seg`` = (row_start int32 [N], row_count int32 [N]): ``x`` holds the captions' REAL positions only, caption n in rows
-    row_start[n] .. +row_count[n] (rows past the last caption are padding nobody attends to); klen_self / att_len_cap are then
-    per row.  Every other op of the stack is row-wise, so only the two attentions know about the layout.
+    row_start[n] .. +row_count[n] (rows past the last caption are padding nobody attends to); klen_self and the regions per image
+    (``cross_len`` instead of fwd.att_len_cap) are then per row.  Every other op of the stack is row-wise, so only the two attentions
+    know about the layout.
     ``seg_img`` = (row_start int32 [images], row_count int32 [images], max rows of an image): the same rows grouped per image,
     for the cross-attention (see _cross)."""
+    P, cfg, drop, N, S = fwd.P, fwd.cfg, fwd.drop, fwd.N, fwd.S
     d = cfg.d_model
+    cap = fwd.att_len_cap if seg is None else cross_len
+    seg_self = None if seg is None else (seg[0], seg[1], True) + tuple(seg[2:3])
     for l in range(cfg.N_dec):
         p = f"model.decoder.layers.{l}"
         xr, n_ = P.ln_res(x, p + ".sublayer.0.norm")
         qkv = P.lin_packed(n_, p + ".self_attn", (0, 1, 2))
-        if seg is None:
-            ctx = attention(qkv, qkv, 0, d, 2 * d, N, cfg.h, S, S, 1, klen_self, S, 1, 0, drop.attn(), None, True)
-        else:
-            ctx = attention(qkv, qkv, 0, d, 2 * d, N, cfg.h, S, S, 1, klen_self, 0, 1, 0, drop.attn(), (seg[0], seg[1], True) + tuple(seg[2:3]), True)
+        ctx = attention(qkv, qkv, 0, d, 2 * d, N, cfg.h, S, S, kdiv=1, klen=klen_self, klen_sb=S if seg is None else 0, klen_sq=1, klen_bias=0,
+                        drop=drop.attn(), seg=seg_self, grad_bf16=True)
         x = _sublayer_linear(P, drop, ctx, p + ".self_attn.linears.3", xr)
         xr, n_ = P.ln_res(x, p + ".sublayer.1.norm")
-        x = _cross(P, p + ".src_attn", cfg, drop, n_, xr, memory, kv_cache, N, S, R, spi, att_len_cap, seg, seg_img)
+        x = _cross(fwd, p + ".src_attn", n_, xr, S, cap, seg=seg, seg_img=seg_img)
         xr, n_ = P.ln_res(x, p + ".sublayer.2.norm")
         x = _ffn(P, p + ".feed_forward", drop, n_, xr)
     return P.ln(x, "model.decoder.norm", gemm_only=out_gemm_only)
 
 
-def bound_teacher_forced(P, cfg, drop, x_in, memory, kv_cache, N, L, R, spi, klen_pass, att_len_cap):
+def bound_teacher_forced(fwd, x_in, klen_pass):
     """The teacher-forced bound passes of one branch as one batch.
 
     x_in [N*L, d] is the embedded bound input; klen_pass int32 [N, Pmax] the number of keys the [LEN] row of
     caption n sees in pass i.  Returns (len_logp [N, Pmax, 20], syn_logp [N, Pmax, 10]).  Follows
     LengthPredictorLayer (TransformerModel.py:1025-1029) + LengthPredictor_UIC.forward (:367-383), row 0 only."""
+    P, cfg, drop, N, L = fwd.P, fwd.cfg, fwd.drop, fwd.N, fwd.L
     d, H = cfg.d_model, cfg.h
     Pm = klen_pass.shape[1]
     lp = "model.length_predictor"
@@ -931,10 +1029,10 @@ def bound_teacher_forced(P, cfg, drop, x_in, memory, kv_cache, N, L, R, spi, kle
     if _shadow(q0) is not None:                                 # bf16 mode: the virtual queries' bf16 copy, so that the bf16 / MFMA attention kernels run
         _register_shadow(qv, _shadow(q0).unsqueeze(1).expand(N, Pm, d).reshape(N * Pm, d))
     xv = x0.unsqueeze(1).expand(N, Pm, d).reshape(N * Pm, d).contiguous()     # (one pass: reshape alone would hand out the strided row-0 view)
-    ctx = attention(qv, kv, 0, 0, d, N, H, Pm, L, 1, klen_pass, Pm, 1, 0, drop.attn())
+    ctx = attention(qv, kv, 0, 0, d, N, H, Pm, L, kdiv=1, klen=klen_pass, klen_sb=Pm, klen_sq=1, klen_bias=0, drop=drop.attn())
     x = _sublayer_linear(P, drop, ctx, p + ".self_attn.linears.3", xv)
     xr, n_ = P.ln_res(x, p + ".sublayer.1.norm")
-    x = _cross(P, p + ".src_attn", cfg, drop, n_, xr, memory, kv_cache, N, Pm, R, spi, att_len_cap)
+    x = _cross(fwd, p + ".src_attn", n_, xr, Pm, fwd.att_len_cap)
     xr, n_ = P.ln_res(x, p + ".sublayer.2.norm")
     x = _ffn(P, p + ".ff", drop, n_, xr)
     o = P.ln(x, lp + ".norm")
@@ -977,7 +1075,7 @@ def _bound_heads(P, drop, o):
     return len_lp, syn_lp
 
 
-def bound_teacher_forced_dense(P, cfg, drop, x_in, memory, kv_cache, N, L, R, spi, klen_pass, att_len_cap):
+def bound_teacher_forced_dense(fwd, x_in, klen_pass):
     """The teacher-forced bound passes for a bounding network of N_len >= 2 layers (configs/uic_sd_N2.yml): the upper layers read the
     lower layers' outputs of EVERY visible row, so a pass is the whole L-row sequence through every layer under that pass's tgt_mask
     (LengthPredictor_UIC.forward TransformerModel.py:367-375 as called from :476-513 / :532-565), not a row-0 query.  The Pmax passes
@@ -985,6 +1083,7 @@ def bound_teacher_forced_dense(P, cfg, drop, x_in, memory, kv_cache, N, L, R, sp
 
     tgt_mask of pass i (:478-506) as key-prefix counts: row 0 sees keys < cum[i]; row r >= 1 sees through the end of the laid-out block
     it starts in or before -- cum[min(i, j(r))], j(r) = #{k : cum[k] <= r} -- and at least key 0 (:486)."""
+    P, cfg, drop, N, L = fwd.P, fwd.cfg, fwd.drop, fwd.N, fwd.L
     d, H = cfg.d_model, cfg.h
     Pm = klen_pass.shape[1]
     dev = x_in.device
@@ -997,16 +1096,17 @@ def bound_teacher_forced_dense(P, cfg, drop, x_in, memory, kv_cache, N, L, R, sp
     klen = klen.clamp(max=L).to(torch.int32).reshape(N * Pm, L).contiguous()
     M = N * Pm
     x = x_in.view(N, 1, L, d).expand(N, Pm, L, d).reshape(M * L, d).contiguous()
-    cap = None if att_len_cap is None else att_len_cap.repeat_interleave(Pm).contiguous()
+    cap = None if fwd.att_len_cap is None else fwd.att_len_cap.repeat_interleave(Pm).contiguous()
+    seqs = fwd.view(N=M, spi=fwd.spi * Pm)                     # every pass a sequence of its own: Pmax times as many share an image's keys
     lp = "model.length_predictor"
     for l in range(cfg.N_len):
         p = f"{lp}.LengthPredictor.{l}"
         xr, n_ = P.ln_res(x, p + ".sublayer.0.norm")
         qkv = P.lin_packed(n_, p + ".self_attn", (0, 1, 2))
-        ctx = attention(qkv, qkv, 0, d, 2 * d, M, H, L, L, 1, klen, L, 1, 0, drop.attn(), None, True)
+        ctx = attention(qkv, qkv, 0, d, 2 * d, M, H, L, L, kdiv=1, klen=klen, klen_sb=L, klen_sq=1, klen_bias=0, drop=drop.attn(), grad_bf16=True)
         x = _sublayer_linear(P, drop, ctx, p + ".self_attn.linears.3", xr)
         xr, n_ = P.ln_res(x, p + ".sublayer.1.norm")
-        x = _cross(P, p + ".src_attn", cfg, drop, n_, xr, memory, kv_cache, M, L, R, spi * Pm, cap)
+        x = _cross(seqs, p + ".src_attn", n_, xr, L, cap)
         xr, n_ = P.ln_res(x, p + ".sublayer.2.norm")
         x = _ffn(P, p + ".ff", drop, n_, xr)
     o_all = P.ln(x, lp + ".norm", gemm_only=False)
@@ -1024,7 +1124,7 @@ class StepPlan:
     gradient are unchanged (dynamic padding); the two token tensors then come back as [N, max_tokens, V].  ``token_rows`` (int64 device tensor
     of flat indices n * max_tokens + t of the real caption tokens, zero-padded to a fixed length): only those rows are projected, the two token
     tensors come back as [len(token_rows), V] (criterion_uic_compact is their criterion).  ``unpadded`` (row_start, row_count, row_cap, row_pos,
-    granule): the decoder itself runs on those rows only (_fill_unpadded), with ``streams`` its branches on side streams.  ``paired``
+    granule): the decoder itself runs on those rows only (_fill_unpadded, _derive_rows), with ``streams`` its branches on side streams.  ``paired``
     (pair_start, pair_count, pair_src, pair_na, granule): both branches as one batch (_forward_paired), with ``pick_labels`` the criterion's
     labels picked inside it and ``paired_inputs`` its index tensors made on the host.  ``split_memory``: the dict of a two-stage backward.
     ``criterion``: the criterion that follows -- "paired", "compact", "dense" or "drop_worst"."""
@@ -1038,6 +1138,20 @@ class StepPlan:
     paired_inputs: Optional[dict] = None
     split_memory: Optional[dict] = None
     criterion: Optional[str] = None
+
+
+@dataclass
+class _Captions:
+    """The loader's caption tensors [N, ...] on the device, as the stages of a forward read them; what a path does not read stays None.
+    ``word_seq``: the labels with [LEN] in front (the SA bound input); ``klen_pass`` / ``last``: bound_pass_klen's."""
+    labels: torch.Tensor
+    phrase_length: torch.Tensor
+    ext_syn: torch.Tensor
+    ext_seq: Optional[torch.Tensor] = None
+    ext_mask: Optional[torch.Tensor] = None
+    word_seq: Optional[torch.Tensor] = None
+    klen_pass: Optional[torch.Tensor] = None
+    last: Optional[torch.Tensor] = None
 
 
 # Two test hooks only: "glat_uniform" -- the glancing pass's uniform draws, injected by parity tests and consumed by the next _glance_draws;
@@ -1078,129 +1192,96 @@ def forward_uic(P, cfg, att_feats, labels, att_masks, phrase_num, phrase_length,
     """The six log-prob tensors of EncoderDecoder_UIC.forward (TransformerModel.py:413-468):
     (sa_len [N,S+1,20], sa_syn [N,S+1,10], sa_tok [N,S,V], na_len, na_syn, na_tok).  ``P``: a ``Params``.  ``plan``: see StepPlan."""
     plan = plan if plan is not None else StepPlan()
-    dev = att_feats.device
-    S, L, d = cfg.seq_length, cfg.seq_length + 2, cfg.d_model
+    S, L = cfg.seq_length, cfg.seq_length + 2
     dense_bound = cfg.N_len != 1         # a deeper bounding network: whole-sequence passes (bound_teacher_forced_dense), the plain form of the step
-    if compute_dtype not in (torch.float32, torch.bfloat16):
-        raise hip.BofiHipError(f"training compute dtype {compute_dtype}: float32 or bfloat16")
-    _COMPUTE["dtype"] = compute_dtype
-    _STEP_CACHE.clear()
-    _SHADOW_ONLY.clear()
-    if labels.dim() == 3:
-        labels = labels.reshape(-1, labels.shape[2])
-        phrase_num = phrase_num.reshape(-1)
-        phrase_length = phrase_length.reshape(-1, phrase_length.shape[2])
-        extend_phrase_syn_seq = extend_phrase_syn_seq.reshape(-1, extend_phrase_syn_seq.shape[2])
-        extend_phrase_seq = extend_phrase_seq.reshape(-1, extend_phrase_seq.shape[2])
-        extend_phrase_seq_mask = extend_phrase_seq_mask.reshape(-1, extend_phrase_seq.shape[1], extend_phrase_seq.shape[1])
-    att_len = None
-    if att_masks is not None:                                  # clip_att, AttModel.py:113-120
-        max_len = int(att_masks.long().sum(1).max())
-        att_feats, att_masks = att_feats[:, :max_len].contiguous(), att_masks[:, :max_len]
-        att_len = att_masks.long().sum(1).to(torch.int32).contiguous()
-    att_feats = _need(att_feats.float() if att_feats.dtype != torch.float32 else att_feats, "att_feats")
-    B, R, _ = att_feats.shape
-    N = labels.shape[0]
-    if N % B:
-        raise hip.BofiHipError(f"{N} captions for {B} images")
-    spi = N // B
-    drop = _Drop(cfg.dropout, cfg.drop_prob_lm, seed if training else None, step_word)
-    memory = encode_memory(P, cfg, att_feats, att_len, drop)
+    if labels.dim() == 3:                # (the loader hands the [S', S'] masks over flattened or not: TransformerModel.py:1722)
+        extend_phrase_seq_mask = extend_phrase_seq_mask.reshape(-1, extend_phrase_seq.shape[2], extend_phrase_seq.shape[2])
+    labels, phrase_num, phrase_length, extend_phrase_syn_seq, extend_phrase_seq = _flat_captions(
+        labels, phrase_num, phrase_length, extend_phrase_syn_seq, extend_phrase_seq)
+    Sd = S if not plan.max_tokens else max(1, min(S, int(plan.max_tokens)))    # decoder positions actually computed
+    fwd = _begin_forward(P, cfg, att_feats, att_masks, N=labels.shape[0], S=Sd, training=training, seed=seed, compute_dtype=compute_dtype,
+                         step_word=step_word)
+    dev = fwd.dev
+    fwd.memory = encode_memory(fwd)
     split = plan.split_memory
     if split is not None:
         # two-stage backward (XETrainer, data-parallel): everything behind the encoder hangs off a DETACHED copy of its output, so that
         # loss.backward() stops there with every decoder-side gradient final -- their exchange starts while the encoder's backward
         # (memory.backward(memory_detached.grad)) still runs
-        sh = _shadow(memory)
-        split["memory"] = memory
-        memory = memory.detach().requires_grad_(True)
+        sh = _shadow(fwd.memory)
+        split["memory"] = fwd.memory
+        fwd.memory = fwd.memory.detach().requires_grad_(True)
         if sh is not None:
-            _register_shadow(memory, sh)
-        split["memory_detached"] = memory
-    att_len_cap = None if att_len is None else att_len.repeat_interleave(spi).contiguous()
-    kv_cache: dict = {}
+            _register_shadow(fwd.memory, sh)
+        split["memory_detached"] = fwd.memory
 
     labels, phrase_num, phrase_length = labels.to(dev).long(), phrase_num.to(dev).long(), phrase_length.to(dev).long()
-    ext_syn = extend_phrase_syn_seq.to(dev).long().contiguous()
-    ext_seq = extend_phrase_seq.to(dev).long().contiguous()
+    cap = _Captions(labels, phrase_length, extend_phrase_syn_seq.to(dev).long().contiguous(), extend_phrase_seq.to(dev).long().contiguous())
     prepared = plan.paired_inputs                              # the paired step's index tensors, made by the collate on the host
-    if prepared is not None and (glat_p >= 0 or att_len is not None or plan.paired is None):
+    if prepared is not None and (glat_p >= 0 or fwd.att_len is not None or plan.paired is None):
         prepared = None                                        # (the glancing pass and ragged region masks take the device-side prep)
-    if prepared is None:
-        klen_pass, last, Pm = bound_pass_klen(phrase_num, phrase_length, plan.max_phrase_num)
-    else:
-        klen_pass, last, Pm = None, None, int(prepared["klen_b"].shape[1])
-    Sd = S if not plan.max_tokens else max(1, min(S, int(plan.max_tokens)))    # decoder positions actually computed
+    Pm = plan.max_phrase_num if prepared is None else int(prepared["klen_b"].shape[1])
     token_rows, unpadded, streams, paired, pick_labels = plan.token_rows, plan.unpadded, plan.streams, plan.paired, plan.pick_labels
-    bound_fn = bound_teacher_forced
+    bound = bound_teacher_forced
     if dense_bound:
-        if prepared is not None:
-            klen_pass, last, Pm = bound_pass_klen(phrase_num, phrase_length, Pm)
         prepared = token_rows = unpadded = streams = paired = pick_labels = None
-        bound_fn = bound_teacher_forced_dense
-    tname, sname = "model.tgt_embed.lut.weight", "model.syn_embed.lut.weight"
-    pe = P["model.pos_embed.pe"]
-
-    def emb(tok, syn, Lp, pos=None):
-        x = embed(P[tname] if tok is not None else None, P[sname] if syn is not None else None, pe, tok, syn, Lp,
-                  P.g(tname) if tok is not None else None, P.g(sname) if syn is not None else None, pos)
-        return drop(x) if drop.on and drop.p > 0.0 else x
-
-    def pad_slots(t):                                          # pass i lands in slot i of the returned [:, 1:] view
-        out = t.new_zeros(N, L - 1, t.shape[2])
-        out[:, :Pm] = t
-        return out
-
-    def vocab(x):
-        return P.lin(x, "model.generator.proj")
+        bound = bound_teacher_forced_dense
+    if prepared is not None:
+        return _forward_paired(fwd, cap, unpadded, paired, pick_labels=pick_labels, prepared=prepared)
+    cap.klen_pass, cap.last, Pm = bound_pass_klen(phrase_num, phrase_length, Pm)
+    # --- semi-autoregressive branch (TransformerModel.py:476-530)
+    cap.word_seq = labels.clone()
+    cap.word_seq[:, 0] = cfg.len_idx
+    cap.ext_mask = extend_phrase_seq_mask.to(dev)
+    if unpadded is not None and paired is not None:
+        return _forward_paired(fwd, cap, unpadded, paired, glat_p=glat_p, pick_labels=pick_labels)
+    if unpadded is not None:
+        return _fill_unpadded(fwd, cap, unpadded, Pm, glat_p=glat_p, streams=streams)
 
     def token_logprobs(x):
         if token_rows is None:
-            return log_softmax(vocab(x)).view(N, Sd, -1)
-        return log_softmax(vocab(x.index_select(0, token_rows)))          # [len(token_rows), V]: the real tokens' rows only
+            return log_softmax(fwd.vocab(x)).view(fwd.N, Sd, -1)
+        return log_softmax(fwd.vocab(x.index_select(0, token_rows)))      # [len(token_rows), V]: the real tokens' rows only
 
-    if prepared is not None:
-        return _forward_paired(P, cfg, drop, emb, vocab, pad_slots, unpadded, paired, labels, None, phrase_length,
-                               ext_syn, ext_seq, None, None, memory, kv_cache, N, L, Sd, R, spi, None, None, glat_p, pick_labels, prepared)
-    # --- semi-autoregressive branch (TransformerModel.py:476-530)
-    word_seq = labels.clone()
-    word_seq[:, 0] = cfg.len_idx
-    sa_bound = lambda: bound_fn(P, cfg, drop, emb(word_seq.contiguous(), None, L), memory, kv_cache, N, L, R, spi, klen_pass, att_len_cap)
-    if unpadded is not None and paired is not None:
-        return _forward_paired(P, cfg, drop, emb, vocab, pad_slots, unpadded, paired, labels, word_seq, phrase_length, ext_syn, ext_seq,
-                               extend_phrase_seq_mask.to(dev), last, memory, kv_cache, N, L, Sd, R, spi, att_len_cap, klen_pass, glat_p,
-                               pick_labels)
-    if unpadded is not None:
-        na_bound = lambda: bound_teacher_forced(P, cfg, drop, emb(None, ext_syn, L), memory, kv_cache, N, L, R, spi, klen_pass, att_len_cap)
-        (sa_len, sa_syn), sa_tok, (na_len, na_syn), na_tok = _fill_unpadded(
-            P, cfg, drop, emb, vocab, unpadded, labels, phrase_length, ext_syn, ext_seq, extend_phrase_seq_mask.to(dev), last, memory,
-            kv_cache, N, Sd, R, spi, att_len_cap, glat_p, sa_bound, na_bound, streams)
-        return pad_slots(sa_len), pad_slots(sa_syn), sa_tok, pad_slots(na_len), pad_slots(na_syn), na_tok
-    sa_len, sa_syn = sa_bound()
-    syn_mid = ext_syn[:, 1:1 + Sd].contiguous()
-    ext_seq = ext_seq[:, :Sd].contiguous()
-    klen_sa = extend_phrase_seq_mask.to(dev).long().sum(-1)[:, :Sd].to(torch.int32).contiguous()  # prefix masks (dataloader.py:414)
-    x = decode_rows(P, cfg, drop, emb(ext_seq, syn_mid, Sd), memory, kv_cache, N, Sd, R, spi, klen_sa, att_len_cap, token_rows is None)
+    sa_len, sa_syn = bound(fwd, fwd.emb(tok=cap.word_seq.contiguous(), syn=None, Lp=L), cap.klen_pass)
+    syn_mid = cap.ext_syn[:, 1:1 + Sd].contiguous()
+    klen_sa = cap.ext_mask.long().sum(-1)[:, :Sd].to(torch.int32).contiguous()    # prefix masks (dataloader.py:414)
+    x = decode_rows(fwd, fwd.emb(cap.ext_seq[:, :Sd].contiguous(), syn_mid, Sd), klen_sa, out_gemm_only=token_rows is None)
     sa_tok = token_logprobs(x)
-
     # --- non-autoregressive branch (:532-587)
-    na_len, na_syn = bound_fn(P, cfg, drop, emb(None, ext_syn, L), memory, kv_cache, N, L, R, spi, klen_pass, att_len_cap)
-    klen_na = (last - 1).unsqueeze(1).expand(N, Sd).contiguous()
-    fill_in = torch.full((N, Sd), cfg.bos_idx, dtype=torch.int64, device=dev)
+    na_len, na_syn, x = _na_padded(fwd, cap, syn_mid, bound, glat_p=glat_p, out_gemm_only=token_rows is None)
+    na_tok = token_logprobs(x)
+    return fwd.pad_slots(sa_len, Pm), fwd.pad_slots(sa_syn, Pm), sa_tok, fwd.pad_slots(na_len, Pm), fwd.pad_slots(na_syn, Pm), na_tok
+
+
+def _glance_share(ntok, same, glat_p):
+    """The share of a caption's true tokens the glancing pass reveals (TransformerModel.py:449-453): its wrong predictions' share times glat_p."""
+    return (ntok - same) / ntok * glat_p
+
+
+def _na_padded(fwd, cap, syn_mid, bound, *, glat_p=-1.0, out_gemm_only=True):
+    """The teacher-forced non-autoregressive branch on the padded [N, S] batch (TransformerModel.py:532-587): NA bound pass, the
+    glancing pass if ``glat_p`` >= 0, decode_NA.  Returns (na_len, na_syn, the decoder's output rows).  The glancing pass keeps a
+    form of its own here -- it counts per caption with .sum(1) where the row lists (_glance_rows) scatter-add, and reads the draws as
+    [:, :S] -- and shares the reveal share with them (_glance_share)."""
+    N, S, dev = fwd.N, fwd.S, fwd.dev
+    na_len, na_syn = bound(fwd, fwd.emb(tok=None, syn=cap.ext_syn, Lp=fwd.L), cap.klen_pass)
+    klen_na = (cap.last - 1).unsqueeze(1).expand(N, S).contiguous()
+    fill_in = torch.full((N, S), fwd.cfg.bos_idx, dtype=torch.int64, device=dev)
     if glat_p >= 0:                                            # glancing input (:437-463): reveal a share of the true tokens
         with torch.no_grad():
-            x = decode_rows(P, cfg, drop, emb(fill_in, syn_mid, Sd), memory, dict(kv_cache), N, Sd, R, spi, klen_na, att_len_cap)
-            pred = greedy_ids(vocab(x)).view(N, Sd)
-            real = labels[:, 1:1 + Sd]
-            ntok = phrase_length.sum(1) - 1
-            tok_mask = torch.arange(Sd, device=dev).unsqueeze(0) < ntok.unsqueeze(1)
+            # (a copy of the cache: this tape-free pass must not leave no-grad K|V behind for the passes with the tape)
+            x = decode_rows(fwd.view(kv_cache=dict(fwd.kv_cache)), fwd.emb(fill_in, syn_mid, S), klen_na)
+            pred = greedy_ids(fwd.vocab(x)).view(N, S)
+            real = cap.labels[:, 1:1 + S]
+            ntok = cap.phrase_length.sum(1) - 1
+            tok_mask = torch.arange(S, device=dev).unsqueeze(0) < ntok.unsqueeze(1)
             same = ((pred == real) & tok_mask).sum(1)
-            keep_prob = ((ntok - same) / ntok * glat_p).unsqueeze(-1) * tok_mask.float()
-            keep = _glance_draws(N, cfg.seq_length, dev)[:, :Sd] < keep_prob
+            keep_prob = _glance_share(ntok, same, glat_p).unsqueeze(-1) * tok_mask.float()
+            keep = _glance_draws(N, fwd.cfg.seq_length, dev)[:, :S] < keep_prob
             fill_in = torch.where(keep, real, fill_in).contiguous()
-    x = decode_rows(P, cfg, drop, emb(fill_in, syn_mid, Sd), memory, kv_cache, N, Sd, R, spi, klen_na, att_len_cap, token_rows is None)
-    na_tok = token_logprobs(x)
-    return pad_slots(sa_len), pad_slots(sa_syn), sa_tok, pad_slots(na_len), pad_slots(na_syn), na_tok
+    x = decode_rows(fwd, fwd.emb(fill_in, syn_mid, S), klen_na, out_gemm_only=out_gemm_only)
+    return na_len, na_syn, x
 
 
 @_scoped_compute_dtype
@@ -1221,42 +1302,18 @@ def forward_uic_ss(P, cfg, att_feats, labels, att_masks, phrase_num, phrase_leng
     and the differentiated pass applies it (the reference does both in one stochastic pass)."""
     import random as _random
     import numpy as np
-    dev = att_feats.device
-    S, L, d = cfg.seq_length, cfg.seq_length + 2, cfg.d_model
+    S, L = cfg.seq_length, cfg.seq_length + 2
     if cfg.N_len != 1:
         raise NotImplementedError("training with N_len >= 2 (see forward_uic)")
     draw = draw if draw is not None else _random.random
-    _COMPUTE["dtype"] = compute_dtype
-    _STEP_CACHE.clear()
-    _SHADOW_ONLY.clear()
-    if labels.dim() == 3:
-        labels = labels.reshape(-1, labels.shape[2])
-        phrase_num = phrase_num.reshape(-1)
-        phrase_length = phrase_length.reshape(-1, phrase_length.shape[2])
-        phrase_syn = phrase_syn.reshape(-1, phrase_syn.shape[2])
-        extend_phrase_syn_seq = extend_phrase_syn_seq.reshape(-1, extend_phrase_syn_seq.shape[2])
-    att_len = None
-    if att_masks is not None:
-        max_len = int(att_masks.long().sum(1).max())
-        att_feats, att_masks = att_feats[:, :max_len].contiguous(), att_masks[:, :max_len]
-        att_len = att_masks.long().sum(1).to(torch.int32).contiguous()
-    att_feats = _need(att_feats.float() if att_feats.dtype != torch.float32 else att_feats, "att_feats")
-    B, R, _ = att_feats.shape
-    N = labels.shape[0]
-    spi = N // B
-    att_len_cap = None if att_len is None else att_len.repeat_interleave(spi).contiguous()
-    tname, sname = "model.tgt_embed.lut.weight", "model.syn_embed.lut.weight"
-    pe = P["model.pos_embed.pe"]
+    labels, phrase_num, phrase_length, phrase_syn, extend_phrase_syn_seq = _flat_captions(labels, phrase_num, phrase_length, phrase_syn,
+                                                                                           extend_phrase_syn_seq)
+    fwd = _begin_forward(P, cfg, att_feats, att_masks, N=labels.shape[0], training=training, seed=seed, compute_dtype=compute_dtype,
+                         step_word=step_word)
+    dev, N = fwd.dev, fwd.N
     lab_h = labels.cpu().numpy().astype(np.int64)
     plen_h = phrase_length.cpu().numpy().astype(np.int64)
     psyn_h = phrase_syn.cpu().numpy().astype(np.int64)
-
-    def make_emb(dr):
-        def emb(tok, syn, Lp):
-            x = embed(P[tname] if tok is not None else None, P[sname] if syn is not None else None, pe, tok, syn, Lp,
-                      P.g(tname) if tok is not None else None, P.g(sname) if syn is not None else None, None)
-            return dr(x) if dr.on and dr.p > 0.0 else x
-        return emb
 
     t = lambda a, dt=torch.int64: torch.from_numpy(np.ascontiguousarray(a)).to(dev).to(dt)
 
@@ -1282,15 +1339,12 @@ def forward_uic_ss(P, cfg, att_feats, labels, att_masks, phrase_num, phrase_leng
                 dst[pl + copied: pl + copied + n] = src[s0 + k]
                 copied += n
 
-    off = _Drop(cfg.dropout, cfg.drop_prob_lm, None, None)
-    emb0 = make_emb(off)
+    f0 = fwd.view(drop=_Drop(cfg.dropout, cfg.drop_prob_lm, seed=None), kv_cache={})      # the same batch without dropout: a memory and K|V of its own
     with torch.no_grad():
-        memory0 = encode_memory(P, cfg, att_feats, att_len, off)
-        kv0: dict = {}
+        f0.memory = encode_memory(f0)
         for i in range(1, L):
             klen_iters.append(phrase_last.copy())
-            len_lp, syn_lp = bound_teacher_forced(P, cfg, off, emb0(t(ext_len), None, L), memory0, kv0, N, L, R, spi,
-                                                  t(phrase_last.reshape(N, 1), torch.int32), att_len_cap)
+            len_lp, syn_lp = bound_teacher_forced(f0, f0.emb(tok=t(ext_len), syn=None, Lp=L), t(phrase_last.reshape(N, 1), torch.int32))
             len_n = len_lp.view(N, -1).cpu().numpy().argmax(1)           # first maximal index, as torch.max on the CPU
             syn_n = syn_lp.view(N, -1).cpu().numpy().argmax(1)
             for j in range(N):
@@ -1325,9 +1379,8 @@ def forward_uic_ss(P, cfg, att_feats, labels, att_masks, phrase_num, phrase_leng
             if (klen_dec == 0).any():
                 raise FloatingPointError("ss_SAIC: a caption without any key -- NaN log-probs; the reference returns a malformed tuple here "
                                          "(TransformerModel.py:2103-2105)")
-            x = decode_rows(P, cfg, off, emb0(t(ext_phrase[:, 1:-1]), t(ext_syn[:, 1:-1]), S), memory0, kv0, N, S, R, spi,
-                            t(klen_dec, torch.int32), att_len_cap)
-            tok = greedy_ids(P.lin(x, "model.generator.proj")).view(N, S).cpu().numpy()
+            x = decode_rows(f0, f0.emb(t(ext_phrase[:, 1:-1]), t(ext_syn[:, 1:-1]), S), t(klen_dec, torch.int32))
+            tok = greedy_ids(f0.vocab(x)).view(N, S).cpu().numpy()
             for j in range(N):
                 cur = int(ppl[j, i])
                 if cur == 0:
@@ -1347,34 +1400,22 @@ def forward_uic_ss(P, cfg, att_feats, labels, att_masks, phrase_num, phrase_leng
     _STEP_CACHE.clear()
     _SHADOW_ONLY.clear()
     P._packed.clear()                                          # (stacked q|k|v operands made without the tape above carry no gradient)
-    drop = _Drop(cfg.dropout, cfg.drop_prob_lm, seed if training else None, step_word)
-    emb = make_emb(drop)
-    memory = encode_memory(P, cfg, att_feats, att_len, drop)
-    kv_cache: dict = {}
-
-    def pad_slots(x, Pm):
-        out = x.new_zeros(N, L - 1, x.shape[2])
-        out[:, :Pm] = x
-        return out
-
+    fwd.memory = encode_memory(fwd)
     klen_pass = t(np.stack(klen_iters, 1), torch.int32)                     # [N, iterations]: keys of the [LEN] row per iteration
-    sa_len, sa_syn = bound_teacher_forced(P, cfg, drop, emb(t(ext_len), None, L), memory, kv_cache, N, L, R, spi, klen_pass, att_len_cap)
+    sa_len, sa_syn = bound_teacher_forced(fwd, fwd.emb(tok=t(ext_len), syn=None, Lp=L), klen_pass)
     klen_dec = t(np.maximum(row_end[:, 1:1 + S] - 1, 0), torch.int32)
-    x = decode_rows(P, cfg, drop, emb(t(ext_phrase[:, 1:-1]), t(ext_syn[:, 1:-1]), S), memory, kv_cache, N, S, R, spi, klen_dec, att_len_cap)
-    sa_tok = log_softmax(P.lin(x, "model.generator.proj")).view(N, S, -1)
+    x = decode_rows(fwd, fwd.emb(t(ext_phrase[:, 1:-1]), t(ext_syn[:, 1:-1]), S), klen_dec)
+    sa_tok = log_softmax(fwd.vocab(x)).view(N, S, -1)
     sa_tok = torch.where(t(written[:, 1:1 + S], torch.bool).unsqueeze(-1), sa_tok, torch.zeros_like(sa_tok))
 
-    # ---- non-autoregressive branch, teacher-forced (:1764-1766)
+    # ---- non-autoregressive branch, teacher-forced, no glancing pass (:1764-1766)
     labels_d, phrase_num_d, phrase_length_d = labels.to(dev).long(), phrase_num.to(dev).long(), phrase_length.to(dev).long()
-    ext_syn_gt = extend_phrase_syn_seq.to(dev).long().contiguous()
-    klen_gt, last, Pm = bound_pass_klen(phrase_num_d, phrase_length_d)
-    na_len, na_syn = bound_teacher_forced(P, cfg, drop, emb(None, ext_syn_gt, L), memory, kv_cache, N, L, R, spi, klen_gt, att_len_cap)
-    klen_na = (last - 1).unsqueeze(1).expand(N, S).contiguous()
-    fill_in = torch.full((N, S), cfg.bos_idx, dtype=torch.int64, device=dev)
-    x = decode_rows(P, cfg, drop, emb(fill_in, ext_syn_gt[:, 1:1 + S].contiguous(), S), memory, kv_cache, N, S, R, spi, klen_na, att_len_cap)
-    na_tok = log_softmax(P.lin(x, "model.generator.proj")).view(N, S, -1)
+    cap = _Captions(labels_d, phrase_length_d, extend_phrase_syn_seq.to(dev).long().contiguous())
+    cap.klen_pass, cap.last, Pm = bound_pass_klen(phrase_num_d, phrase_length_d)
+    na_len, na_syn, x = _na_padded(fwd, cap, cap.ext_syn[:, 1:1 + S].contiguous(), bound_teacher_forced)
+    na_tok = log_softmax(fwd.vocab(x)).view(N, S, -1)
     HINTS["ss_trace"] = dict(iters=n_it, emitted=seq[:, 1:-1].copy(), predict_phrase_length=ppl.copy())
-    return pad_slots(sa_len, n_it), pad_slots(sa_syn, n_it), sa_tok, pad_slots(na_len, Pm), pad_slots(na_syn, Pm), na_tok
+    return fwd.pad_slots(sa_len, n_it), fwd.pad_slots(sa_syn, n_it), sa_tok, fwd.pad_slots(na_len, Pm), fwd.pad_slots(na_syn, Pm), na_tok
 
 
 def _glance_draws(N: int, S: int, dev) -> torch.Tensor:
@@ -1409,8 +1450,78 @@ def _paired_order(N, spi, dev):
     return hit
 
 
-def _forward_paired(P, cfg, drop, emb, vocab, pad_slots, unpadded, paired, labels, word_seq, phrase_length, ext_syn, ext_seq, ext_mask,
-                    last, memory, kv_cache, N, L, Sd, R, spi, att_len_cap, klen_pass, glat_p, pick_labels=None, prepared=None):
+# The single-branch row list of a batch (``unpadded``) with the loader's tensors gathered per row: row r is position row_pos[r] of caption
+# row_cap[r].  ``seg``: (row_start, row_count [, tail]) for the attentions; T rows, padding included.  ``syn_c`` / ``seq_c``: the row's
+# syntactic label and SA input token; ``klen_sa`` / ``klen_na``: its self-attention key count in either branch; ``cross_len``: the regions
+# of its image (None: all).  For the glancing pass only: ``real`` the true token, ``ntok`` [N] tokens per caption, ``in_cap`` whether the
+# row belongs to a caption.
+_Rows = namedtuple("_Rows", "row_cap row_pos seg T syn_c seq_c klen_sa klen_na cross_len real ntok in_cap")
+
+
+def _derive_rows(fwd, cap, unpadded, glance=True) -> _Rows:
+    """``unpadded`` = (row_start int32 [N], row_count int32 [N], row_cap int64 [T], row_pos int64 [T] [, tail]) + the loader's tensors ->
+    _Rows.  ``glance`` False leaves out what only the glancing pass reads."""
+    row_start, row_count, row_cap, row_pos = unpadded[:4]
+    seg = (row_start, row_count) + tuple(unpadded[4:5])        # (+ the host's bound on the number of padding rows, if given)
+    T = row_cap.numel()
+    with torch.no_grad():
+        at = row_cap * fwd.L + row_pos                            # (caption, position) in the [N, L] loader arrays
+        klen_full = cap.ext_mask.long().sum(-1)                   # [N, S'] prefix masks (dataloader.py:414)
+        return _Rows(row_cap, row_pos, seg, T,
+                     syn_c=cap.ext_syn.reshape(-1)[at + 1],
+                     seq_c=cap.ext_seq.reshape(-1)[row_cap * cap.ext_seq.shape[1] + row_pos],
+                     klen_sa=klen_full.reshape(-1)[row_cap * klen_full.shape[1] + row_pos].to(torch.int32),
+                     klen_na=(cap.last - 1)[row_cap].to(torch.int32),
+                     cross_len=None if fwd.att_len_cap is None else fwd.att_len_cap[row_cap],
+                     real=cap.labels.reshape(-1)[at + 1] if glance else None,
+                     ntok=cap.phrase_length.sum(1) - 1 if glance else None,
+                     in_cap=torch.arange(T, device=fwd.dev) < (row_start[-1] + row_count[-1]) if glance else None)
+
+
+def _glance_rows(fwd, rows, glat_p, fill_in):
+    """The glancing pass (TransformerModel.py:437-463) on a row list: a tape-free decode_NA of ``fill_in`` [T], then a share of each
+    caption's true tokens -- as large as its share of wrong predictions, times glat_p -- revealed in it.  The padded form is in _na_padded."""
+    with torch.no_grad():
+        # (a copy of the cache: this tape-free pass must not leave no-grad K|V behind for the passes with the tape)
+        x = decode_rows(fwd.view(kv_cache=dict(fwd.kv_cache)), fwd.emb(fill_in, rows.syn_c, fwd.S, rows.row_pos), rows.klen_na, seg=rows.seg,
+                        cross_len=rows.cross_len)
+        pred = greedy_ids(fwd.vocab(x)).view(rows.T)
+        same = torch.zeros(fwd.N, dtype=torch.int64, device=fwd.dev).index_add_(0, rows.row_cap, ((pred == rows.real) & rows.in_cap).long())
+        keep_prob = _glance_share(rows.ntok, same, glat_p)[rows.row_cap] * rows.in_cap.float()
+        keep = _glance_draws(fwd.N, fwd.cfg.seq_length, fwd.dev)[rows.row_cap, rows.row_pos] < keep_prob
+        return torch.where(keep, rows.real, fill_in)
+
+
+def _paired_bound_inputs(fwd, cap):
+    """The paired bound pass's inputs, derived on the device -- what the collate makes on the host as ``paired_inputs``' tok_b / syn_b /
+    klen_b (+ att_b: the regions per paired caption, ragged region masks only)."""
+    with torch.no_grad():
+        cap_n, cap_na = _paired_order(fwd.N, fwd.spi, fwd.dev)[:2]    # captions in paired order (constants of the batch shape)
+        tok_b, syn_b = cap.word_seq[cap_n], cap.ext_syn[cap_n]
+        none = torch.full_like(tok_b, -1)                         # the SA bound input has no syntactic term, the NA one no token term
+        return dict(tok_b=torch.where(cap_na, none, tok_b).contiguous(), syn_b=torch.where(cap_na, syn_b, none).contiguous(),
+                    klen_b=cap.klen_pass[cap_n].contiguous(), att_b=None if fwd.att_len_cap is None else fwd.att_len_cap[cap_n].contiguous())
+
+
+def _paired_fill_inputs(fwd, cap, unpadded, paired, glat_p):
+    """The paired decoder pass's inputs, derived on the device (the host's: tok2 / syn2 / pos2 / klen2 / img_start / img_count; + cross2):
+    the single row list's tensors -- its NA rows after the glancing pass, which runs on that list -- gathered into paired order."""
+    pair_start, pair_count, pair_src, pair_na = paired[:4]
+    rows = _derive_rows(fwd, cap, unpadded, glance=glat_p >= 0)
+    fill_in = torch.full((rows.T,), fwd.cfg.bos_idx, dtype=torch.int64, device=fwd.dev)
+    if glat_p >= 0:                                               # NA rows only
+        fill_in = _glance_rows(fwd, rows, glat_p, fill_in)
+    with torch.no_grad():
+        per_img = 2 * fwd.spi                                     # the same rows per image: its 2 spi captions are adjacent
+        return dict(tok2=torch.where(pair_na, fill_in[pair_src], rows.seq_c[pair_src]).contiguous(), syn2=rows.syn_c[pair_src].contiguous(),
+                    pos2=rows.row_pos[pair_src].contiguous(),
+                    klen2=torch.where(pair_na, rows.klen_na[pair_src], rows.klen_sa[pair_src]).contiguous(),
+                    cross2=None if rows.cross_len is None else rows.cross_len[pair_src].contiguous(),
+                    img_start=pair_start.view(-1, per_img)[:, 0].contiguous(),
+                    img_count=pair_count.view(-1, per_img).sum(1).to(torch.int32).contiguous())
+
+
+def _forward_paired(fwd, cap, unpadded, paired, *, glat_p=-1.0, pick_labels=None, prepared=None):
     """forward_uic with the SA and the NA branch as ONE batch: one bound pass over 2N captions and one decoder pass over both
     branches' rows, instead of two of each.
 
@@ -1420,89 +1531,32 @@ def _forward_paired(P, cfg, drop, emb, vocab, pad_slots, unpadded, paired, label
     decoder and bound stacks, forward and backward.  Captions are ordered image-major -- image i's ``spi`` SA copies, then its
     ``spi`` NA copies -- so that the 2*spi captions sharing an image's cross-attention keys stay adjacent (kdiv = 2 spi).
 
-    ``unpadded`` as in _fill_unpadded (the single-branch row list: the glancing pass runs on it); ``paired`` =
+    ``unpadded`` as in _derive_rows (the single-branch row list: the glancing pass runs on it); ``paired`` =
     (pair_start int32 [2N], pair_count int32 [2N], pair_src int64 [T2], pair_na bool [T2] [, tail]): row r of the paired list is
-    row pair_src[r] of the single list, in the NA branch iff pair_na[r]; T2 padded like T.  Returns the six tensors of
-    forward_uic with BOTH token entries being the paired log-probs [T2, V] (criterion_uic_compact with a pair of weights) and the
-    four bound outputs as [N, Pm, .] -- Pm passes, not padded out to seq_length + 1 slots."""
-    dev = labels.device
-    row_start, row_count, row_cap, row_pos = unpadded[:4]
-    pair_start, pair_count, pair_src, pair_na = paired[:4]
-    if prepared is not None:
-        # every index tensor comes from the collate (XETrainer.add_token_rows, numpy): nothing to derive on the device
-        cap_n, cap_na, at_sa, at_na = _paired_order(N, spi, dev)
-        for pre in [f"model.decoder.layers.{l}.src_attn" for l in range(cfg.N_dec)]:
-            if pre not in kv_cache:
-                kv_cache[pre] = P.lin_packed(memory, pre, (1, 2))
-        len_lp, syn_lp = bound_teacher_forced(P, cfg, drop, emb(prepared["tok_b"], prepared["syn_b"], L), memory, kv_cache, 2 * N, L, R, 2 * spi,
-                                              prepared["klen_b"], None)
-        sa_len, sa_syn = len_lp.index_select(0, at_sa), syn_lp.index_select(0, at_sa)
-        na_len, na_syn = len_lp.index_select(0, at_na), syn_lp.index_select(0, at_na)
-        seg2 = (pair_start, pair_count) + tuple(paired[4:5])
-        img = (prepared["img_start"], prepared["img_count"], 2 * spi * Sd)
-        x = decode_rows(P, cfg, drop, emb(prepared["tok2"], prepared["syn2"], Sd, prepared["pos2"]), memory, kv_cache, 2 * N, Sd, R, 2 * spi,
-                        prepared["klen2"], None, True, seg2, img)
-        if pick_labels is not None:
-            tok_all, picked = log_softmax_pick(vocab(x), pick_labels, True)
-            tok_all._bofi_picked = (picked, pick_labels)
-        else:
-            tok_all = log_softmax(vocab(x))
-        return sa_len, sa_syn, tok_all, na_len, na_syn, tok_all
-    with torch.no_grad():
-        at = row_cap * L + row_pos
-        syn_c = ext_syn.reshape(-1)[at + 1]
-        seq_c = ext_seq.reshape(-1)[row_cap * ext_seq.shape[1] + row_pos]
-        klen_full = ext_mask.long().sum(-1)
-        klen_sa = klen_full.reshape(-1)[row_cap * klen_full.shape[1] + row_pos].to(torch.int32)
-        klen_na = (last - 1)[row_cap].to(torch.int32)
-        cross_len = None if att_len_cap is None else att_len_cap[row_cap]
-        T = row_cap.numel()
-        cap_n, cap_na, at_sa, at_na = _paired_order(N, spi, dev)  # captions in paired order (constants of the batch shape)
-        tok_b, syn_b = word_seq[cap_n], ext_syn[cap_n]
-        none = torch.full_like(tok_b, -1)                         # the SA bound input has no syntactic term, the NA one no token term
-        tok_b = torch.where(cap_na, none, tok_b).contiguous()
-        syn_b = torch.where(cap_na, syn_b, none).contiguous()
-        klen_b = klen_pass[cap_n].contiguous()
-        att_b = None if att_len_cap is None else att_len_cap[cap_n].contiguous()
-    # the image's cross-attention K/V of every layer that reads it, once, with the tape (the glancing pass below has none)
-    for pre in [f"model.decoder.layers.{l}.src_attn" for l in range(cfg.N_dec)]:
-        if pre not in kv_cache:
-            kv_cache[pre] = P.lin_packed(memory, pre, (1, 2))
-    len_lp, syn_lp = bound_teacher_forced(P, cfg, drop, emb(tok_b, syn_b, L), memory, kv_cache, 2 * N, L, R, 2 * spi, klen_b, att_b)
+    row pair_src[r] of the single list, in the NA branch iff pair_na[r]; T2 padded like T.  ``prepared``: every index tensor comes from
+    the collate (XETrainer.add_token_rows, numpy); None: each pass's are derived on the device right before it (_paired_bound_inputs,
+    _paired_fill_inputs).  Returns the six tensors of forward_uic with BOTH token entries being the paired log-probs [T2, V]
+    (criterion_uic_compact with a pair of weights) and the four bound outputs as [N, Pm, .] -- Pm passes (Pm >= the batch's largest
+    phrase count: the slots past it carry no loss weight; criterion_uic_compact reads as many label slots as there are outputs), not
+    padded out to seq_length + 1 slots."""
+    at_sa, at_na = _paired_order(fwd.N, fwd.spi, fwd.dev)[2:]
+    ix = prepared if prepared is not None else _paired_bound_inputs(fwd, cap)
+    # the image's cross-attention K/V of every layer that reads it, once, with the tape (a glancing pass below has none)
+    fwd.prefill_cross_kv()
+    both = fwd.view(N=2 * fwd.N, spi=2 * fwd.spi, att_len_cap=ix.get("att_b"))
+    len_lp, syn_lp = bound_teacher_forced(both, both.emb(ix["tok_b"], ix["syn_b"], fwd.L), ix["klen_b"])
     sa_len, sa_syn = len_lp.index_select(0, at_sa), syn_lp.index_select(0, at_sa)
     na_len, na_syn = len_lp.index_select(0, at_na), syn_lp.index_select(0, at_na)
-
-    fill_in = torch.full((T,), cfg.bos_idx, dtype=torch.int64, device=dev)
-    if glat_p >= 0:                                               # glancing input (TransformerModel.py:437-463), NA rows only
-        with torch.no_grad():
-            seg1 = (row_start, row_count) + tuple(unpadded[4:5])
-            x = decode_rows(P, cfg, drop, emb(fill_in, syn_c.contiguous(), Sd, row_pos), memory, dict(kv_cache), N, Sd, R, spi,
-                            klen_na.contiguous(), None if cross_len is None else cross_len.contiguous(), True, seg1)
-            pred = greedy_ids(vocab(x)).view(T)
-            real = labels.reshape(-1)[at + 1]
-            ntok = phrase_length.sum(1) - 1
-            in_cap = torch.arange(T, device=dev) < (row_start[-1] + row_count[-1])
-            same = torch.zeros(N, dtype=torch.int64, device=dev).index_add_(0, row_cap, ((pred == real) & in_cap).long())
-            keep_prob = ((ntok - same) / ntok * glat_p)[row_cap] * in_cap.float()
-            keep = _glance_draws(N, cfg.seq_length, dev)[row_cap, row_pos] < keep_prob
-            fill_in = torch.where(keep, real, fill_in)
-    with torch.no_grad():
-        tok2 = torch.where(pair_na, fill_in[pair_src], seq_c[pair_src]).contiguous()
-        syn2 = syn_c[pair_src].contiguous()
-        pos2 = row_pos[pair_src].contiguous()
-        klen2 = torch.where(pair_na, klen_na[pair_src], klen_sa[pair_src]).contiguous()
-        cross2 = None if cross_len is None else cross_len[pair_src].contiguous()
-    seg2 = (pair_start, pair_count) + tuple(paired[4:5])
-    with torch.no_grad():                                         # the same rows per image: its 2 spi captions are adjacent
-        img = (pair_start.view(-1, 2 * spi)[:, 0].contiguous(), pair_count.view(-1, 2 * spi).sum(1).to(torch.int32).contiguous(), 2 * spi * Sd)
-    x = decode_rows(P, cfg, drop, emb(tok2, syn2, Sd, pos2), memory, kv_cache, 2 * N, Sd, R, 2 * spi, klen2, cross2, True, seg2, img)
+    if prepared is None:
+        ix = _paired_fill_inputs(fwd, cap, unpadded, paired, glat_p)
+    seg2 = tuple(paired[:2]) + tuple(paired[4:5])
+    img = (ix["img_start"], ix["img_count"], both.spi * fwd.S)
+    x = decode_rows(both, both.emb(ix["tok2"], ix["syn2"], fwd.S, ix["pos2"]), ix["klen2"], seg=seg2, seg_img=img, cross_len=ix.get("cross2"))
     if pick_labels is not None:                                   # the criterion's token labels are known: pick while the row is at hand
-        tok_all, picked = log_softmax_pick(vocab(x), pick_labels, True)
+        tok_all, picked = log_softmax_pick(fwd.vocab(x), pick_labels, True)
         tok_all._bofi_picked = (picked, pick_labels)
     else:
-        tok_all = log_softmax(vocab(x))
-    # the four bound outputs stay [N, Pm, .] (Pm >= the batch's largest phrase count: the slots past it carry no loss weight;
-    # criterion_uic_compact reads as many label slots as there are outputs)
+        tok_all = log_softmax(fwd.vocab(x))
     return sa_len, sa_syn, tok_all, na_len, na_syn, tok_all
 
 
@@ -1554,34 +1608,17 @@ class _NoFork:
     def join(self, outs): pass
 
 
-def _fill_unpadded(P, cfg, drop, emb, vocab, unpadded, labels, phrase_length, ext_syn, ext_seq, ext_mask, last, memory, kv_cache, N, Sd, R,
-                   spi, att_len_cap, glat_p, sa_bound, na_bound, streams=None):
-    """The two bound passes and decode_SA / decode_NA (+ the glancing pass) of forward_uic, the decoder over the captions' real
-    positions only.
+def _fill_unpadded(fwd, cap, unpadded, Pm, *, glat_p=-1.0, streams=None):
+    """forward_uic with the decoder over the captions' real positions only: the two bound passes and decode_SA / decode_NA (+ the
+    glancing pass) on the row list ``unpadded`` (_derive_rows; T is padded, to a multiple the caller chooses, with rows that belong
+    to no caption).
 
-    ``unpadded`` = (row_start int32 [N], row_count int32 [N], row_cap int64 [T], row_pos int64 [T] [, tail]): row r of the decoder
-    batch is position row_pos[r] of caption row_cap[r]; T is padded (to a multiple the caller chooses) with rows that belong
-    to no caption.  A padded [N, Sd] batch spends most of its rows on positions past the captions' ends (synthetic
-    COCO-like captions: ~45% real); their outputs carry zero loss weight and nothing attends to them, so leaving them out
-    changes neither the loss nor any gradient.  Returns (sa_bound(), sa_tok [T, V], na_bound(), na_tok [T, V]); the op order
-    (SA bound, SA fill, NA bound, glancing, NA fill) is the padded path's, so the dropout streams agree with it site by site.
+    A padded [N, Sd] batch spends most of its rows on positions past the captions' ends (synthetic COCO-like captions: ~45% real);
+    their outputs carry zero loss weight and nothing attends to them, so leaving them out changes neither the loss nor any gradient.
+    Returns forward_uic's six tensors with the token entries as [T, V]; the op order (SA bound, SA fill, NA bound, glancing, NA fill)
+    is the padded path's, so the dropout streams agree with it site by site.
     ``streams``: three side streams -> the branches run concurrently (see _Fork)."""
-    dev = labels.device
-    row_start, row_count, row_cap, row_pos = unpadded[:4]
-    seg = (row_start, row_count) + tuple(unpadded[4:5])        # (+ the host's bound on the number of padding rows, if given)
-    L = labels.shape[1]
-    with torch.no_grad():
-        at = row_cap * L + row_pos                                # (caption, position) in the [N, L] loader arrays
-        syn_c = ext_syn.reshape(-1)[at + 1].contiguous()
-        seq_c = ext_seq.reshape(-1)[row_cap * ext_seq.shape[1] + row_pos].contiguous()
-        klen_full = ext_mask.long().sum(-1)                       # [N, S'] prefix masks (dataloader.py:414)
-        klen_sa = klen_full.reshape(-1)[row_cap * klen_full.shape[1] + row_pos].to(torch.int32).contiguous()
-        klen_na = (last - 1)[row_cap].to(torch.int32).contiguous()
-        cross_len = None if att_len_cap is None else att_len_cap[row_cap].contiguous()
-        real = labels.reshape(-1)[at + 1]
-        ntok = phrase_length.sum(1) - 1
-        T = row_cap.numel()
-        in_cap = torch.arange(T, device=dev) < (row_start[-1] + row_count[-1])
+    rows = _derive_rows(fwd, cap, unpadded)
     fork = _NoFork()
     if streams:
         if len(streams) < 3:
@@ -1589,31 +1626,24 @@ def _fill_unpadded(P, cfg, drop, emb, vocab, unpadded, labels, phrase_length, ex
         fork = _Fork(streams)
         # what every branch reads is made here, on the main stream, before the streams part: the image's cross-attention K/V of
         # the decoder layers and of the bound layer
-        for pre in [f"model.decoder.layers.{l}.src_attn" for l in range(cfg.N_dec)] + ["model.length_predictor.LengthPredictor.0.src_attn"]:
-            if pre not in kv_cache:
-                kv_cache[pre] = P.lin_packed(memory, pre, (1, 2))
-        fork.share([memory, syn_c, seq_c, klen_sa, klen_na, cross_len, real, ntok, in_cap] + list(kv_cache.values()))
+        fwd.prefill_cross_kv(with_bound=True)
+        fork.share([fwd.memory, rows.syn_c, rows.seq_c, rows.klen_sa, rows.klen_na, rows.cross_len, rows.real, rows.ntok, rows.in_cap]
+                   + list(fwd.kv_cache.values()))
         fork.begin()
-    bound_sa = sa_bound()
+    sa_len, sa_syn = bound_teacher_forced(fwd, fwd.emb(tok=cap.word_seq.contiguous(), syn=None, Lp=fwd.L), cap.klen_pass)
     with fork.on(0):
-        x = decode_rows(P, cfg, drop, emb(seq_c, syn_c, Sd, row_pos), memory, kv_cache, N, Sd, R, spi, klen_sa, cross_len, True, seg)
-        sa_tok = log_softmax(vocab(x))
+        x = decode_rows(fwd, fwd.emb(rows.seq_c, rows.syn_c, fwd.S, rows.row_pos), rows.klen_sa, seg=rows.seg, cross_len=rows.cross_len)
+        sa_tok = log_softmax(fwd.vocab(x))
     with fork.on(1):
-        bound_na = na_bound()
+        na_len, na_syn = bound_teacher_forced(fwd, fwd.emb(tok=None, syn=cap.ext_syn, Lp=fwd.L), cap.klen_pass)
     with fork.on(2):
-        fill_in = torch.full((T,), cfg.bos_idx, dtype=torch.int64, device=dev)
-        if glat_p >= 0:                                           # glancing input (TransformerModel.py:437-463)
-            with torch.no_grad():
-                x = decode_rows(P, cfg, drop, emb(fill_in, syn_c, Sd, row_pos), memory, dict(kv_cache), N, Sd, R, spi, klen_na, cross_len, True, seg)
-                pred = greedy_ids(vocab(x)).view(T)
-                same = torch.zeros(N, dtype=torch.int64, device=dev).index_add_(0, row_cap, ((pred == real) & in_cap).long())
-                keep_prob = ((ntok - same) / ntok * glat_p)[row_cap] * in_cap.float()
-                keep = _glance_draws(N, cfg.seq_length, dev)[row_cap, row_pos] < keep_prob
-                fill_in = torch.where(keep, real, fill_in).contiguous()
-        x = decode_rows(P, cfg, drop, emb(fill_in, syn_c, Sd, row_pos), memory, kv_cache, N, Sd, R, spi, klen_na, cross_len, True, seg)
-        na_tok = log_softmax(vocab(x))
-    fork.join([sa_tok, na_tok, bound_na[0], bound_na[1]])
-    return bound_sa, sa_tok, bound_na, na_tok
+        fill_in = torch.full((rows.T,), fwd.cfg.bos_idx, dtype=torch.int64, device=fwd.dev)
+        if glat_p >= 0:
+            fill_in = _glance_rows(fwd, rows, glat_p, fill_in)
+        x = decode_rows(fwd, fwd.emb(fill_in, rows.syn_c, fwd.S, rows.row_pos), rows.klen_na, seg=rows.seg, cross_len=rows.cross_len)
+        na_tok = log_softmax(fwd.vocab(x))
+    fork.join([sa_tok, na_tok, na_len, na_syn])
+    return fwd.pad_slots(sa_len, Pm), fwd.pad_slots(sa_syn, Pm), sa_tok, fwd.pad_slots(na_len, Pm), fwd.pad_slots(na_syn, Pm), na_tok
 
 
 @_scoped_compute_dtype
@@ -1765,57 +1795,27 @@ def rl_prepare_saic_device(cfg, seq: torch.Tensor, phrase_length: torch.Tensor, 
 @_scoped_compute_dtype
 def sampled_logprobs_prepared(P, cfg, att_feats, att_masks, prep, *, sample_n: int = 1, training: bool = False, seed: Optional[int] = None,
                               compute_dtype: torch.dtype = torch.float32, step_word: Optional[torch.Tensor] = None, reuse: Optional[dict] = None):
-    out = _sampled_logprobs_prepared(P, cfg, att_feats, att_masks, prep, sample_n=sample_n, training=training, seed=seed, compute_dtype=compute_dtype,
-                                     step_word=step_word, reuse=reuse)
-    if reuse is not None and "shadows" not in reuse:            # the bf16 operands the cross K|V were made as (kept by their producers in the step cache, which
-        reuse["shadows"] = [(t, _shadow(t), t.data_ptr() in _SHADOW_ONLY) for t in reuse["kv_cache"].values()]      # every call clears): registered again by the next calls
-    return out
-
-
-def _sampled_logprobs_prepared(P, cfg, att_feats, att_masks, prep, *, sample_n: int = 1, training: bool = False, seed: Optional[int] = None,
-                               compute_dtype: torch.dtype = torch.float32, step_word: Optional[torch.Tensor] = None, reuse: Optional[dict] = None):
     """Device half of ``sampled_logprobs``: tensors in, log-probs out, no host work (``att_masks`` None) -- what a captured
     self-critical step replays.  ``prep``: rl_prepare's dict.  ``reuse`` (tape-free callers only: a dict kept across calls on the SAME inputs, weights and
     seed): the encoder's memory and the decoder layers' cross K|V do not depend on the captions -- under the counter-based dropout masks they are the same
     tensors in every call -- so the per-phrase forwards of the reference-estimator step compute them once."""
-    dev = att_feats.device
-    S, d = cfg.seq_length, cfg.d_model
-    if compute_dtype not in (torch.float32, torch.bfloat16):
-        raise hip.BofiHipError(f"training compute dtype {compute_dtype}: float32 or bfloat16")
-    _COMPUTE["dtype"] = compute_dtype
-    _STEP_CACHE.clear()
-    _SHADOW_ONLY.clear()
-    att_len = None
-    if att_masks is not None:
-        max_len = int(att_masks.long().sum(1).max())
-        att_feats, att_masks = att_feats[:, :max_len].contiguous(), att_masks[:, :max_len]
-        att_len = att_masks.long().sum(1).to(torch.int32).contiguous()
-    att_feats = _need(att_feats.float() if att_feats.dtype != torch.float32 else att_feats, "att_feats")
-    B, R, _ = att_feats.shape
-    N = B * sample_n
-    drop = _Drop(cfg.dropout, cfg.drop_prob_lm, seed if training else None, step_word)
     if reuse is not None and torch.is_grad_enabled():
         raise hip.BofiHipError("reuse: tape-free calls only (the gradient pass needs its own graph through the encoder)")
+    fwd = _begin_forward(P, cfg, att_feats, att_masks, spi=sample_n, training=training, seed=seed, compute_dtype=compute_dtype, step_word=step_word)
+    B, N, S, dev = fwd.B, fwd.N, fwd.S, fwd.dev
     if reuse is not None and "memory" in reuse:
-        memory, kv_cache = reuse["memory"], reuse["kv_cache"]
-        drop.k = reuse["drop_sites"]                          # (the decoder's dropout sites keep the numbers they have behind the encoder's: the same masks)
+        fwd.memory, fwd.kv_cache = reuse["memory"], reuse["kv_cache"]
+        fwd.drop.k = reuse["drop_sites"]                      # (the decoder's dropout sites keep the numbers they have behind the encoder's: the same masks)
         for t, sh, only in reuse.get("shadows", ()):
             if sh is not None:
                 _register_shadow(t, sh, only)
     else:
-        memory = encode_memory(P, cfg, att_feats, att_len, drop)
-        kv_cache = {}
+        fwd.memory = encode_memory(fwd)
         if reuse is not None:
-            reuse["memory"], reuse["kv_cache"], reuse["drop_sites"] = memory, kv_cache, drop.k
-    att_len_cap = None if att_len is None else att_len.repeat_interleave(sample_n).contiguous()
-    tname, sname, pe = "model.tgt_embed.lut.weight", "model.syn_embed.lut.weight", P["model.pos_embed.pe"]
+            reuse["memory"], reuse["kv_cache"], reuse["drop_sites"] = fwd.memory, fwd.kv_cache, fwd.drop.k
 
-    def emb(tok, syn):
-        x = embed(P[tname], P[sname], pe, tok, syn, S, P.g(tname), P.g(sname))
-        return drop(x) if drop.on and drop.p > 0.0 else x
-
-    def tokens(x):
-        return log_softmax(P.lin(x, "model.generator.proj")).view(N, S, -1)
+    def tokens(f, x):
+        return log_softmax(f.vocab(x)).view(f.N, S, -1)
 
     def check(t, dtype):
         if t.shape != (N, S) or t.dtype != dtype:
@@ -1837,19 +1837,18 @@ def _sampled_logprobs_prepared(P, cfg, att_feats, att_masks, prep, *, sample_n: 
             tok2 = torch.where(is_na, torch.full_like(prep["sa_seq"][cap], cfg.bos_idx), check(prep["sa_seq"], torch.int64)[cap]).contiguous()
             syn2 = torch.where(is_na, check(prep["na_syn"], torch.int64)[cap], check(prep["sa_syn"], torch.int64)[cap]).contiguous()
             klen2 = torch.where(is_na, check(prep["na_klen"], torch.int32)[cap], check(prep["sa_klen"], torch.int32)[cap]).contiguous()
-            len2 = None if att_len_cap is None else att_len_cap[cap].contiguous()
-        x = embed(P[tname], P[sname], pe, tok2, syn2, S, P.g(tname), P.g(sname))
-        x = drop(x) if drop.on and drop.p > 0.0 else x
-        x = decode_rows(P, cfg, drop, x, memory, kv_cache, 2 * N, S, R, 2 * sample_n, klen2, len2)
-        lp = log_softmax(P.lin(x, "model.generator.proj")).view(2 * N, S, -1)
-        return lp.index_select(0, at_sa), lp.index_select(0, at_sa + sample_n)
-    if "sa_seq" in prep:
-        out[0] = tokens(decode_rows(P, cfg, drop, emb(check(prep["sa_seq"], torch.int64), check(prep["sa_syn"], torch.int64)), memory, kv_cache,
-                                    N, S, R, sample_n, check(prep["sa_klen"], torch.int32), att_len_cap))
-    if "na_syn" in prep:
+            len2 = None if fwd.att_len_cap is None else fwd.att_len_cap[cap].contiguous()
+        both = fwd.view(N=2 * N, spi=2 * sample_n, att_len_cap=len2)
+        lp = tokens(both, decode_rows(both, both.emb(tok2, syn2, S), klen2))
+        out = [lp.index_select(0, at_sa), lp.index_select(0, at_sa + sample_n)]
+    elif "sa_seq" in prep:
+        out[0] = tokens(fwd, decode_rows(fwd, fwd.emb(check(prep["sa_seq"], torch.int64), check(prep["sa_syn"], torch.int64), S),
+                                         check(prep["sa_klen"], torch.int32)))
+    elif "na_syn" in prep:
         bos = torch.full((N, S), cfg.bos_idx, dtype=torch.int64, device=dev)
-        out[1] = tokens(decode_rows(P, cfg, drop, emb(bos, check(prep["na_syn"], torch.int64)), memory, kv_cache, N, S, R, sample_n,
-                                    check(prep["na_klen"], torch.int32), att_len_cap))
+        out[1] = tokens(fwd, decode_rows(fwd, fwd.emb(bos, check(prep["na_syn"], torch.int64), S), check(prep["na_klen"], torch.int32)))
+    if reuse is not None and "shadows" not in reuse:            # the bf16 operands the cross K|V were made as (kept by their producers in the step cache, which
+        reuse["shadows"] = [(t, _shadow(t), t.data_ptr() in _SHADOW_ONLY) for t in reuse["kv_cache"].values()]      # every call clears): registered again by the next calls
     return out[0], out[1]
 
 
