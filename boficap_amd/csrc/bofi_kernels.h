@@ -216,6 +216,19 @@ struct MaskPredictArgs {
 int mask_predict_check(const MaskPredictArgs& a);     // BOFI_ERR_ARG: B >= 1, 1 <= S <= 64, 0 <= t <= T <= 15, non-null pointers
 int launch_mask_predict_step(const MaskPredictArgs& a, hipStream_t st);
 
+// ---- word-to-region attention maps (attn_maps.hip): softmax(q . k * scale) per head from queries [B*Lq, ldq] and keys [B*Lk, ldk] of the compute dtype (d_k = 64)
+struct AttnMapsArgs {
+    const void* q; int ldq; const void* k; int ldk; int dtype;
+    int B, H, Lq, Lk; float scale;
+    const int* klen;                  // [B] keys per image or NULL (Lk)
+    const int* qlen; int qlen_bias;   // [B] (+ bias) query rows whose top-K is wanted, or NULL (Lq)
+    float* mean;                      // [B, Lq, Lk] the heads' mean, optional
+    float* heads;                     // [B, H, Lq, Lk] optional
+    int K; int* top_idx; float* top_w;      // [B, Lq, K] both or neither
+};
+const char* attn_maps_check(const AttnMapsArgs& a);     // NULL, or what is wrong with the arguments (BOFI_ERR_ARG)
+int launch_attn_maps(const AttnMapsArgs& a, hipStream_t st);
+
 int launch_set_u64(uint64_t* p, uint64_t v, hipStream_t s);
 int launch_zero_f32(float* p, size_t n, hipStream_t s);
 

@@ -110,6 +110,11 @@ struct bofi_engine {
     float *row_plogp_out = nullptr, *row_chosen_out = nullptr;
     // per-call (bofi_engine_set_refine_out; part of the graph key): where a decode under BOFI_FLAG_MASK_PREDICT leaves the pass that emitted each position's token
     int* refine_round_out = nullptr;
+    // per-call (bofi_engine_set_attn_out; part of the graph key): where the filling pass leaves decoder layer attn_layer's (-1: the last) cross-attention maps (attn_maps.hip)
+    float *attn_mean_out = nullptr, *attn_heads_out = nullptr, *attn_top_w_out = nullptr;
+    int* attn_top_idx_out = nullptr;
+    int attn_layer = -1, attn_topk = 0;
+    bool attn_out_set() const { return attn_mean_out || attn_heads_out || attn_top_idx_out; }
     bool loop_ready = false;
     float* dbg_part = nullptr;
 
@@ -956,6 +961,15 @@ int bofi_engine::enqueue_fill(const int* att_len, int B, int R, int flags, int64
         // split: the cross-attention's core now, its W_o + residual as the head of the feed-forward launch
         const bool cross_split = ffn_rb && !need_copy_out && attn_split_ok(c, l.o_src, l.w1, l.w2, 2);
         ENG_OK(attn_sublayer(c, l.o_src, x_fill, !ffn_rb, cross_split, s));
+        // the word-to-region maps of this layer (bofi_engine_set_attn_out), last pass only: from the queries and keys the sublayer above read, whatever its form --
+        // qs stands until the next layer's query projection, and the kernels apply 1 / sqrt(d_k) themselves
+        if (attn_out_set() && round + 1 == rounds && (int)li == (attn_layer < 0 ? (int)dec.size() - 1 : attn_layer)) {
+            bofi::AttnMapsArgs m{};
+            m.q = qs; m.ldq = d; m.k = kv_slot(n_len + (int)li); m.ldk = kv_all.N; m.dtype = dt; m.B = B; m.H = cfg.heads; m.Lq = S; m.Lk = R; m.scale = 0.125f;
+            m.klen = att_len; m.qlen = st.last; m.qlen_bias = -1;
+            m.mean = attn_mean_out; m.heads = attn_heads_out; m.K = attn_topk; m.top_idx = attn_top_idx_out; m.top_w = attn_top_w_out;
+            ENG_OK(bofi::launch_attn_maps(m, s));
+        }
         // next consumer: the next layer's q|k|v (it may ride the feed-forward launch) or the generator
         const Lin* nxt = li + 1 < dec.size() ? &dec[li + 1].qkv : nullptr;
         ENG_OK(ffn_sublayer(l.w1, l.w2, x_fill, need_copy_out, M, s, cross_split ? &l.o_src : nullptr, nxt, qkv, 3 * d, &proj_made));
@@ -1185,6 +1199,7 @@ int bofi_engine_fork_ex(bofi_engine_t* parent, int max_batch, int fork_flags, bo
     e->bound_iter_cap = 0;                       // (a capped parent must not truncate the fork's bounding loop)
     e->row_plogp_out = nullptr; e->row_chosen_out = nullptr;
     e->refine_round_out = nullptr;
+    e->attn_mean_out = e->attn_heads_out = e->attn_top_w_out = nullptr; e->attn_top_idx_out = nullptr; e->attn_layer = -1; e->attn_topk = 0;
     e->in_flight = 0;
     e->live_max = nullptr;                       // (a raw device pointer the fork's handle does not keep alive)
     e->sat_out = nullptr;
@@ -1369,6 +1384,21 @@ int bofi_engine_set_refine_out(bofi_engine_t* e, int* emitted_round) {
     g_err.clear();
     if (!e) return fail(BOFI_ERR_ARG, "null engine");
     e->refine_round_out = emitted_round;
+    return BOFI_OK;
+}
+
+int bofi_engine_set_attn_out(bofi_engine_t* e, int layer, float* mean, float* heads, int K, int* top_idx, float* top_w) {
+    g_err.clear();
+    if (!e) return fail(BOFI_ERR_ARG, "null engine");
+    if (!mean && !heads && !top_idx && !top_w) {                 // off
+        e->attn_mean_out = e->attn_heads_out = e->attn_top_w_out = nullptr; e->attn_top_idx_out = nullptr; e->attn_layer = -1; e->attn_topk = 0;
+        return BOFI_OK;
+    }
+    if (layer < -1 || layer >= e->cfg.n_dec) return fail(BOFI_ERR_ARG, "attention output: layer in 0 .. N_dec - 1, or -1 for the last");
+    if (K < 0 || K > 8) return fail(BOFI_ERR_ARG, "attention output: K in 0..8");
+    if (!top_idx != !top_w) return fail(BOFI_ERR_ARG, "attention output: top_idx and top_w, both or neither");
+    if ((K > 0) != (top_idx != nullptr)) return fail(BOFI_ERR_ARG, "attention output: K > 0 goes with top_idx and top_w, K = 0 with neither");
+    e->attn_layer = layer; e->attn_mean_out = mean; e->attn_heads_out = heads; e->attn_topk = K; e->attn_top_idx_out = top_idx; e->attn_top_w_out = top_w;
     return BOFI_OK;
 }
 
@@ -1574,6 +1604,13 @@ static int check_mask_predict(bofi_engine_t* e, int flags) {
     if (e->cfg.seq_length > 64) return fail(BOFI_ERR_ARG, "BOFI_FLAG_MASK_PREDICT: seq_length above 64 (one wavefront holds an image's positions)");
     return BOFI_OK;
 }
+// bofi_engine_set_attn_out: the map kernel's limits, checked before anything is enqueued or captured
+static int check_attn_out(bofi_engine_t* e, int R) {
+    if (!e->attn_out_set()) return BOFI_OK;
+    if (e->cfg.seq_length > 64 || R > 128) return fail(BOFI_ERR_ARG, "attention output: seq_length <= 64 and at most 128 regions (bofi_attn_maps)");
+    if (e->cfg.d_model != e->cfg.heads * 64) return fail(BOFI_ERR_ARG, "attention output: head dim 64");
+    return BOFI_OK;
+}
 static int check_feats(bofi_engine_t* e, const void* feats, int feats_dtype) {
     if (!feats) return fail(BOFI_ERR_ARG, "null att_feats");
     if (feats_dtype != BOFI_DT_F32 && feats_dtype != e->cfg.dtype) return fail(BOFI_ERR_ARG, "att_feats must be float32 or the engine's compute dtype");
@@ -1606,6 +1643,7 @@ int bofi_engine_fill_naic(bofi_engine_t* e, const int* ext_syn, const int* last,
     if (!ext_syn || !last || !seq) return fail(BOFI_ERR_ARG, "null argument");
     ENG_OK(check_ids_only(e, flags, seq_logprob));
     if (const int rc = check_mask_predict(e, flags)) return rc;      // (its message stays: ENG_OK would put the call's text in its place)
+    if (const int rc = check_attn_out(e, R)) return rc;
     if (e->no_logits && !e->gen_rb_ok(B * e->cfg.seq_length)) return fail(BOFI_ERR_STATE, "this fork has no vocabulary-wide buffers and the launch would not take the fused generator");
     hipStream_t s = (hipStream_t)stream;
     ENG_HIP(hipMemcpyAsync(e->st.ext_syn, ext_syn, (size_t)B * e->L * sizeof(int), hipMemcpyDeviceToDevice, s));
@@ -1621,6 +1659,7 @@ int bofi_engine_decode_saic(bofi_engine_t* e, const void* feats, int feats_dtype
     ENG_OK(check_feats(e, feats, feats_dtype));
     if (!seq) return fail(BOFI_ERR_ARG, "null seq");
     if (flags & BOFI_FLAG_MASK_PREDICT) return fail(BOFI_ERR_ARG, "BOFI_FLAG_MASK_PREDICT refines the non-autoregressive filling pass: not with the semi-autoregressive decode");
+    if (e->attn_out_set()) return fail(BOFI_ERR_STATE, "an attention output is set (bofi_engine_set_attn_out): the maps come out of the non-autoregressive filling pass only, not the semi-autoregressive decode");
     if (e->n_len != 1) return fail(BOFI_ERR_STATE, "the semi-autoregressive decode is built for a one-layer bounding network (N_len = 1)");
     if (e->no_logits) return fail(BOFI_ERR_STATE, "this fork has no vocabulary-wide buffers: the semi-autoregressive decode needs the distribution");
     hipStream_t s = (hipStream_t)stream;
@@ -1651,6 +1690,7 @@ int bofi_engine_decode_naic(bofi_engine_t* e, const void* feats, int feats_dtype
     if (!seq) return fail(BOFI_ERR_ARG, "null seq");
     ENG_OK(check_ids_only(e, flags, seq_logprob));
     if (const int rc = check_mask_predict(e, flags)) return rc;      // (its message stays: ENG_OK would put the call's text in its place)
+    if (const int rc = check_attn_out(e, R)) return rc;
     // (before anything is enqueued or captured: such a fork's launch must be one the fused generator takes)
     if (e->no_logits && !e->gen_rb_ok(B * e->cfg.seq_length)) return fail(BOFI_ERR_STATE, "this fork has no vocabulary-wide buffers and the launch would not take the fused generator");
     hipStream_t s = (hipStream_t)stream;
@@ -1663,7 +1703,9 @@ int bofi_engine_decode_naic(bofi_engine_t* e, const void* feats, int feats_dtype
                                   (uintptr_t)phrase_length, (uintptr_t)phrase_syn, (uintptr_t)memory_out, (uintptr_t)bound_iters,
                                   (uintptr_t)e->q1_group, (uintptr_t)e->bound_iter_cap, (uintptr_t)e->live_max, (uintptr_t)e->in_flight,
                                   (uintptr_t)bofi::g_env_generation, (uintptr_t)e->row_plogp_out, (uintptr_t)e->row_chosen_out,
-                                  (uintptr_t)e->sat_out, (uintptr_t)(e->loop_mode + 1), (uintptr_t)e->kv_beside, (uintptr_t)e->refine_round_out};
+                                  (uintptr_t)e->sat_out, (uintptr_t)(e->loop_mode + 1), (uintptr_t)e->kv_beside, (uintptr_t)e->refine_round_out,
+                                  (uintptr_t)e->attn_mean_out, (uintptr_t)e->attn_heads_out, (uintptr_t)e->attn_top_idx_out, (uintptr_t)e->attn_top_w_out,
+                                  (uintptr_t)(e->attn_layer + 1), (uintptr_t)e->attn_topk};
     return run_graphed(e, key, s, [&](hipStream_t cs) {
         return e->enqueue_decode(feats, feats_dtype, att_len, B, R, flags, seq, seq_logprob, phrase_num, phrase_length,
                                  phrase_syn, memory_out, bound_iters, cs);

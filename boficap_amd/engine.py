@@ -178,7 +178,8 @@ class BofiEngine:
     def decode_naic(self, att_feats: torch.Tensor, att_len: Optional[torch.Tensor] = None, *, strict_q1: bool = True,
                     want_logprob: bool = True, want_memory: bool = False, raw_logits: bool = False, graph: bool = False,
                     refine_rounds: int = 0, out: Optional[dict] = None, q1_group: int = 0, iter_cap: int = 0, phases: str = "", row_stats: bool = False,
-                    ids_only: bool = False, refine_method: str = "feed_back") -> dict:
+                    ids_only: bool = False, refine_method: str = "feed_back", attn_topk: int = 0, attn_maps: bool = False, attn_heads: bool = False,
+                    attn_layer: int = -1) -> dict:
         """Greedy NAIC bound+fill decode.  Returns a dict of device tensors: seq [B,S] int64,
         seq_logprob [B,S,V] float32 (or None), phrase_num [B] int32, phrase_length [B,S] int32,
         phrase_syn [B,S] int64, bound_iters [1] int32, memory [B,R,d] float32 (or None).
@@ -199,7 +200,12 @@ class BofiEngine:
         ``refine_method``: what the ``refine_rounds`` extra passes are.  'feed_back' (default): all of the previous ids as decoder input.  'mask_predict'
         (BOFI_FLAG_MASK_PREDICT; ``refine_rounds`` >= 1, not with ``raw_logits``): pass t re-predicts the n (T + 1 - t) / (T + 1) least confident of an image's n
         positions from BOS and keeps the rest; ``out['refine_round']`` (int32 [B, S]) names the pass that emitted each token, ``row_stats`` are those of the
-        emitting pass, and ``seq_logprob`` is the LAST pass's tensor (kept positions' rows are its re-prediction, not the distribution that emitted the token)."""
+        emitting pass, and ``seq_logprob`` is the LAST pass's tensor (kept positions' rows are its re-prediction, not the distribution that emitted the token).
+        ``attn_topk`` / ``attn_maps`` / ``attn_heads`` / ``attn_layer`` (bofi_engine_set_attn_out; one extra launch in the filling pass): the word-to-region attention of
+        decoder layer ``attn_layer`` (-1: the last) -- ``out['attn']`` float32 [B, S, R], the heads' mean cross-attention probabilities per position (what the reference
+        keeps as ``decoder.layers[-1].src_attn.attn``, averaged over heads); ``out['attn_heads']`` [B, H, S, R]; ``out['attn_top']`` int32 / ``out['attn_top_w']``
+        float32 [B, S, K]: each position's K heaviest regions in descending order (-1 / 0 past an image's region count and on positions that carry no word).  With
+        refinement rounds the maps are the LAST pass's (under 'mask_predict' a kept position's row is that pass's re-prediction, as ``seq_logprob``)."""
         mp = self._refine_flag(refine_method, refine_rounds, raw_logits)
         if ids_only:
             if raw_logits:
@@ -244,6 +250,7 @@ class BofiEngine:
         if rr != getattr(self, "_refine_ptr", 0):
             hip.check(self._lib.bofi_engine_set_refine_out(self._h, hip.ptr(out["refine_round"]) if mp else None), "bofi_engine_set_refine_out")
             self._refine_ptr = rr
+        self._set_attn_out(out, B, R, dev, attn_topk, attn_maps, attn_heads, attn_layer)
         if q1_group != getattr(self, "_q1_group", 0):
             hip.check(self._lib.bofi_engine_set_q1_group(self._h, int(q1_group)), "bofi_engine_set_q1_group")
             self._q1_group = q1_group
@@ -261,6 +268,29 @@ class BofiEngine:
             hip.ptr(out["seq_logprob"]), hip.ptr(out["phrase_num"]), hip.ptr(out["phrase_length"]), hip.ptr(out["phrase_syn"]),
             hip.ptr(out["memory"]), hip.ptr(out["bound_iters"]), hip.stream_ptr()), "bofi_engine_decode_naic")
         return out
+
+    def _set_attn_out(self, out: dict, B: int, R: int, dev, attn_topk: int, attn_maps: bool, attn_heads: bool, attn_layer: int) -> None:
+        """The attention outputs of the next decode (bofi_engine_set_attn_out): buffers in ``out`` (made when missing or of another shape), the setter called only when
+        a pointer, K or the layer changed; everything off clears it."""
+        if not (attn_topk or attn_maps or attn_heads) and getattr(self, "_attn_state", None) is None:
+            return                                               # (off and nothing to clear: the usual call)
+        K = int(attn_topk)
+        if not 0 <= K <= 8:
+            raise hip.BofiHipError("attn_topk must be in 0..8")
+        if not -1 <= int(attn_layer) < self.cfg.N_dec:
+            raise hip.BofiHipError(f"attn_layer must be in 0..{self.cfg.N_dec - 1}, or -1 for the last decoder layer")
+        S, H = self.cfg.seq_length, self.cfg.h
+        ptrs = []
+        for key, on, shape, dt in (("attn", attn_maps, (B, S, R), torch.float32), ("attn_heads", attn_heads, (B, H, S, R), torch.float32),
+                                   ("attn_top", K > 0, (B, S, K), torch.int32), ("attn_top_w", K > 0, (B, S, K), torch.float32)):
+            if on and (out.get(key) is None or tuple(out[key].shape) != shape):
+                out[key] = torch.empty(shape, dtype=dt, device=dev)
+            ptrs.append(out[key].data_ptr() if on else 0)
+        state = (tuple(ptrs), K, int(attn_layer)) if any(ptrs) else None
+        if state != getattr(self, "_attn_state", None):
+            p = [C.c_void_p(v) if v else None for v in ptrs]
+            hip.check(self._lib.bofi_engine_set_attn_out(self._h, int(attn_layer), p[0], p[1], K, p[2], p[3]), "bofi_engine_set_attn_out")
+            self._attn_state = state
 
     @staticmethod
     def _refine_flag(refine_method: str, refine_rounds: int, raw_logits: bool) -> int:
@@ -453,10 +483,12 @@ class BofiEngine:
         return llp, slp
 
     def fill_naic(self, ext_syn: torch.Tensor, last: torch.Tensor, R: int, att_len: Optional[torch.Tensor] = None, *, strict_q1: bool = True,
-                  raw_logits: bool = False, refine_rounds: int = 0, refine_method: str = "feed_back"):
+                  raw_logits: bool = False, refine_rounds: int = 0, refine_method: str = "feed_back", attn_topk: int = 0, attn_maps: bool = False,
+                  attn_heads: bool = False, attn_layer: int = -1):
         """The filling pass alone on a given slot layout (``ext_syn`` int32 [B, S+2], ``last`` int32 [B]) and the memory of the
         preceding ``encode``: (seq int64 [B, S], seq_logprob float32 [B, S, V]); with ``refine_method='mask_predict'`` (as ``decode_naic``) a third
-        element, refine_round int32 [B, S]."""
+        element, refine_round int32 [B, S].  With ``attn_topk`` / ``attn_maps`` / ``attn_heads`` (as ``decode_naic``) a last element, a dict of the attention tensors
+        ('attn', 'attn_heads', 'attn_top', 'attn_top_w': those asked for)."""
         mp = self._refine_flag(refine_method, refine_rounds, raw_logits)
         B = ext_syn.size(0)
         if ext_syn.dtype != torch.int32 or last.dtype != torch.int32 or ext_syn.size(1) != self.cfg.bound_len or last.numel() != B:
@@ -469,9 +501,12 @@ class BofiEngine:
         if (rnd.data_ptr() if mp else 0) != getattr(self, "_refine_ptr", 0):
             hip.check(self._lib.bofi_engine_set_refine_out(self._h, hip.ptr(rnd)), "bofi_engine_set_refine_out")
             self._refine_ptr = rnd.data_ptr() if mp else 0
+        attn = {}
+        self._set_attn_out(attn, B, int(R), dev, attn_topk, attn_maps, attn_heads, attn_layer)
         hip.check(self._lib.bofi_engine_fill_naic(self._h, hip.ptr(ext_syn.contiguous()), hip.ptr(last.contiguous()), B, R, hip.ptr(att_len), flags,
                                                   hip.ptr(seq), hip.ptr(lp), hip.stream_ptr()), "bofi_engine_fill_naic")
-        return (seq, lp, rnd) if mp else (seq, lp)
+        res = (seq, lp, rnd) if mp else (seq, lp)
+        return res + (attn,) if attn else res
 
 
 class DecodePipeline:
@@ -493,8 +528,13 @@ class DecodePipeline:
 
     def __init__(self, engine: "BofiEngine", *, in_flight: Optional[int] = None, batches_per_launch: int = 16, strict_q1: bool = True, stats: bool = True,
                  keep_logprob: bool = False, region_buckets=(36, 48, 64, 80, 100, 128), fused_vocab: bool = False,
-                 refine_rounds: int = 0, refine_method: str = "feed_back"):
+                 refine_rounds: int = 0, refine_method: str = "feed_back", attn_topk: int = 0, keep_attn: bool = False):
         BofiEngine._refine_flag(refine_method, refine_rounds, False)
+        # attn_topk = K > 0: every yielded dict carries attn_top int32 / attn_top_w float32 [b, S, K] -- each position's K heaviest regions (BofiEngine.decode_naic) -- on the
+        # host, through the pinned buffers (rows x S x K x 8 bytes per launch); keep_attn: also attn [b, S, R of the launch's region bucket] on the device, as keep_logprob
+        if not 0 <= int(attn_topk) <= 8:
+            raise hip.BofiHipError("attn_topk must be in 0..8")
+        self.attn_topk, self.keep_attn = int(attn_topk), bool(keep_attn)
         # refine_rounds / refine_method: as BofiEngine.decode_naic; with 'mask_predict' every yielded dict also carries refine_round [b, S]
         self.refine_rounds, self.refine_method = int(refine_rounds), refine_method
         if in_flight is None:                                    # 3 launch streams + the copy stream = the runtime's default of 4 hardware queues
@@ -659,11 +699,13 @@ class DecodePipeline:
         sl["ran"] = e
         sl["out"] = e.decode_naic(feats, lens, strict_q1=self.strict_q1, graph=True, out=sl["out"] if sl["out"] is not None and sl["out"]["seq"].shape[0] == rows else None,
                                   q1_group=b if nb > 1 else 0, row_stats=self.stats, want_logprob=self.keep_logprob, ids_only=self.fused_vocab,
-                                  refine_rounds=self.refine_rounds, refine_method=self.refine_method)
+                                  refine_rounds=self.refine_rounds, refine_method=self.refine_method, attn_topk=self.attn_topk, attn_maps=self.keep_attn)
         out = sl["out"]
         small = {k2: out[k2] for k2 in ("seq", "phrase_num", "phrase_length", "phrase_syn", "bound_saturated")}
         if self.refine_method == "mask_predict":
             small["refine_round"] = out["refine_round"]
+        if self.attn_topk:
+            small["attn_top"], small["attn_top_w"] = out["attn_top"], out["attn_top_w"]
         if self.stats:
             small["entropy"], small["perplexity"] = e.entropy_perplexity(out)
         if sl["host"] is None or sl["host"]["seq"].shape[0] != rows:
@@ -671,6 +713,7 @@ class DecodePipeline:
         for k2, v in small.items():
             sl["host"][k2].copy_(v, non_blocking=True)
         sl["lp"] = out["seq_logprob"].clone() if self.keep_logprob else None
+        sl["attn"] = out["attn"].clone() if self.keep_attn else None
 
     def _finish(self, launch):
         k, sizes = launch
@@ -691,5 +734,7 @@ class DecodePipeline:
             res = {k2: v[o:o + b] for k2, v in mine.items()}
             if sl["lp"] is not None:
                 res["seq_logprob"] = sl["lp"][o:o + b]
+            if sl["attn"] is not None:
+                res["attn"] = sl["attn"][o:o + b]
             o += b
             yield res

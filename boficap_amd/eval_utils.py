@@ -20,6 +20,8 @@ references alone (integer rows or id strings; no loss then), or None.  ``eval_kw
     refine_rounds, refine_method     NAIC only: extra filling passes as ``decode_many`` takes them ('feed_back', the default, or 'mask_predict'); with
                      'mask_predict' the pass that emitted each token is stored under ``eval_kwargs['refine_round']`` (int32 [N, S]), and entropy /
                      perplexity come from the emitting passes' statistics
+    attn_topk        K in 1..8, NAIC only: every entry gains 'regions', one list per id of its 'seq': the [region, weight] pairs of the K image regions the word's
+                     position attended to most (mean over heads of the last decoder layer's cross-attention in the filling pass), heaviest first
     sample_n         N > 1 (or the ``sample_n`` argument): after the greedy pass, N captions per image are drawn through ``mode='sample'`` with
                      ``sample_method='sample'`` (eval_split_n, eval_utils.py:670-700, ``sample_n_method='sample'``); their entries are stored under
                      ``eval_kwargs['preds_n']``, and ``lang_stats`` gains the diversity statistics of boficap_amd.diversity ('Div-1', 'Div-2',
@@ -47,6 +49,19 @@ def entry_of(i, k, seq, pn, pl, ent, ppl, vocab=None):
              "entropy": float(ent[k]), "perplexity": float(ppl[k])}
     if vocab:
         entry["caption"] = " ".join(vocab.get(str(v), "UNK") for v in ids if v > 6)
+    return entry
+
+
+def regions_of(seq_row, top_row, top_w_row):
+    """The 'regions' field of a prediction entry: for every emitted word -- every position of ``seq_row`` [S] whose id is > 0, the ids of the entry's 'seq' -- the
+    [region, weight] pairs of ``top_row`` / ``top_w_row`` [S, K] (``decode_many(attn_topk=K)``), heaviest first; index -1 marks an empty slot and is skipped."""
+    return [[[int(r), float(w)] for r, w in zip(top_row[t].tolist(), top_w_row[t].tolist()) if r >= 0] for t, v in enumerate(seq_row.tolist()) if v > 0]
+
+
+def with_regions(entry, r, k):
+    """``entry`` with the 'regions' of row ``k`` of a decoded batch ``r`` that carries attn_top / attn_top_w (unchanged otherwise)."""
+    if "attn_top" in r:
+        entry["regions"] = regions_of(r["seq"][k], r["attn_top"][k], r["attn_top_w"][k])
     return entry
 
 
@@ -159,6 +174,11 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
     refine = {"refine_rounds": int(kw.get("refine_rounds", 0)), "refine_method": kw.get("refine_method", "feed_back")}
     if mode != "NAIC" and (refine["refine_rounds"] or refine["refine_method"] != "feed_back"):
         raise ValueError("refine_rounds / refine_method refine the non-autoregressive filling pass: inference_mode 'NAIC' only")
+    attn_topk = int(kw.get("attn_topk", 0))
+    if attn_topk and mode != "NAIC":
+        raise ValueError("attn_topk reads the non-autoregressive filling pass's cross-attention: inference_mode 'NAIC' only")
+    if attn_topk:
+        refine["attn_topk"] = attn_topk
     rounds = []
     N = len(feats)
     ixs = kw.get("image_ixs")
@@ -183,7 +203,7 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
                                            in_flight=kw.get("in_flight"), fused_vocab=bool(kw.get("fused_vocab", False)), **refine):
                     n = r["seq"].size(0)
                     rounds.append(r.get("refine_round"))
-                    predictions.extend(entry_of(i, k, r["seq"], r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"], vocab) for k in range(n))
+                    predictions.extend(with_regions(entry_of(i, k, r["seq"], r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"], vocab), r, k) for k in range(n))
                     seqs.append(r["seq"]); ents.append(r["entropy"]); ppls.append(r["perplexity"])
                     i += n
             elif mode == "NAIC":
@@ -199,7 +219,7 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
                                            fused_vocab=bool(kw.get("fused_vocab", False)), **refine):
                     n = r["seq"].size(0)
                     rounds.append(r.get("refine_round"))
-                    predictions.extend(entry_of(i, k, r["seq"], r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"], vocab) for k in range(n))
+                    predictions.extend(with_regions(entry_of(i, k, r["seq"], r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"], vocab), r, k) for k in range(n))
                     seqs.append(r["seq"]); ents.append(r["entropy"]); ppls.append(r["perplexity"])
                     i += n
             else:

@@ -127,6 +127,8 @@ SIGNATURES = {
     "bofi_pack_regions": (_I, [_P, _I, _P, _P, _I, _I, _P, _I, _I, _I, _P, _P]),
     "bofi_engine_set_refine_out": (_I, [_P, _P]),
     "bofi_mask_predict_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "bofi_attn_maps": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_float, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
+    "bofi_engine_set_attn_out": (_I, [_P, _I, _P, _P, _I, _P, _P]),
 }
 
 _lib = None
@@ -218,6 +220,23 @@ def pack_regions(rows, offsets, offsets_host, out, *, norm=False, att_len=None):
         raise BofiHipError("pack_regions: att_len must be int32 [B] on the device")
     check(lib().bofi_pack_regions(ptr(rows), codes[rows.dtype], ptr(offsets), ptr(offsets_host), B, rows.size(1), ptr(out), dtype_code(out), out.size(1),
                                   1 if norm else 0, ptr(att_len), stream_ptr()), "bofi_pack_regions")
+
+
+def attn_maps(q, k, B, H, Lq, Lk, *, scale=0.125, klen=None, qlen=None, qlen_bias=0, mean=None, heads=None, K=0, top_idx=None, top_w=None):
+    """``bofi_attn_maps`` on torch tensors: q [B * Lq, >= 64 H] and k [B * Lk, >= 64 H] float32 / bfloat16 device tensors whose row strides are the pitches; klen / qlen
+    int32 [B] or None; mean float32 [B, Lq, Lk], heads float32 [B, H, Lq, Lk], top_idx int32 / top_w float32 [B, Lq, K] -- contiguous, each optional.  One launch on the
+    current stream, no synchronisation."""
+    import torch
+    if q.dtype != k.dtype or q.dim() != 2 or k.dim() != 2 or q.stride(1) != 1 or k.stride(1) != 1 or not q.is_cuda or not k.is_cuda:
+        raise BofiHipError("attn_maps: q and k must be 2-d device tensors of one dtype with unit column stride")
+    if q.size(0) < B * Lq or k.size(0) < B * Lk or q.size(1) < 64 * H or k.size(1) < 64 * H:
+        raise BofiHipError("attn_maps: q needs B * Lq rows, k B * Lk rows, both 64 * H columns")
+    for name, t, dt, shape in (("klen", klen, torch.int32, (B,)), ("qlen", qlen, torch.int32, (B,)), ("mean", mean, torch.float32, (B, Lq, Lk)),
+                               ("heads", heads, torch.float32, (B, H, Lq, Lk)), ("top_idx", top_idx, torch.int32, (B, Lq, K)), ("top_w", top_w, torch.float32, (B, Lq, K))):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_cuda or not t.is_contiguous()):
+            raise BofiHipError(f"attn_maps: {name} must be a contiguous {dt} device tensor of shape {shape}")
+    check(lib().bofi_attn_maps(ptr(q), q.stride(0), ptr(k), k.stride(0), dtype_code(q), int(B), int(H), int(Lq), int(Lk), float(scale), ptr(klen), ptr(qlen), int(qlen_bias),
+                               ptr(mean), ptr(heads), int(K), ptr(top_idx), ptr(top_w), stream_ptr()), "bofi_attn_maps")
 
 
 def gemm_flops(reset: bool = False):

@@ -240,7 +240,7 @@ class TransformerModel(nn.Module):
         return saic, naic
 
     def decode_many(self, batches, *, batches_per_launch: int = 16, in_flight: Optional[int] = None, stats: bool = True, keep_logprob: bool = False,
-                    fused_vocab: bool = False, refine_rounds: int = 0, refine_method: str = "feed_back"):
+                    fused_vocab: bool = False, refine_rounds: int = 0, refine_method: str = "feed_back", attn_topk: int = 0, keep_attn: bool = False):
         """Greedy NAIC decode of MANY loader batches at the engine's throughput -- the eval loop of the reference (eval_utils.py:456-460: one synchronised
         ``model(..., mode='sample')`` per batch, which is what ``_sample`` reproduces) as a pipeline: ``in_flight`` engine forks on overlapping streams,
         ``batches_per_launch`` consecutive batches per launch (quirk Q1 per batch: every batch's result is its own decode's), features copied from (pinned)
@@ -253,15 +253,18 @@ class TransformerModel(nn.Module):
         perplexity [b] as eval_utils.py:463-464 with ``stats``; + seq_logprob [b, S, V] on the device with ``keep_logprob``), host tensors.
         ``fused_vocab``: ids-only launches on forks without the vocabulary-wide buffers (``DecodePipeline(fused_vocab=True)``; not with ``keep_logprob``).
         ``refine_rounds`` / ``refine_method``: extra filling passes as ``BofiEngine.decode_naic`` takes them; with 'mask_predict' every dict also carries
-        refine_round [b, S] int32, the pass that emitted each token."""
+        refine_round [b, S] int32, the pass that emitted each token.
+        ``attn_topk`` = K > 0: every dict also carries attn_top int32 / attn_top_w float32 [b, S, K], each position's K heaviest image regions under the last decoder
+        layer's mean cross-attention, in descending order (-1 / 0 past an image's region count and where no word stands); ``keep_attn``: also the whole map attn
+        [b, S, R] on the device (R: the launch's region bucket, the padding columns zero)."""
         from .engine import DecodePipeline
         eng = self.engine()
-        key = (id(eng), batches_per_launch, in_flight, stats, keep_logprob, self.strict_reference, fused_vocab, int(refine_rounds), refine_method)
+        key = (id(eng), batches_per_launch, in_flight, stats, keep_logprob, self.strict_reference, fused_vocab, int(refine_rounds), refine_method, int(attn_topk), bool(keep_attn))
         cached = self.__dict__.get("_pipeline")
         if cached is None or cached[0] != key:
             cached = self.__dict__["_pipeline"] = (key, DecodePipeline(eng, in_flight=in_flight, batches_per_launch=batches_per_launch, strict_q1=self.strict_reference,
                                                                        stats=stats, keep_logprob=keep_logprob, fused_vocab=fused_vocab,
-                                                                       refine_rounds=refine_rounds, refine_method=refine_method))
+                                                                       refine_rounds=refine_rounds, refine_method=refine_method, attn_topk=attn_topk, keep_attn=keep_attn))
 
         def items():
             from .features import RaggedBatch
@@ -310,6 +313,14 @@ class TransformerModel(nn.Module):
             raise hip.BofiHipError("refine_method='mask_predict' ranks log-probs: not with raw logits (output_logsoftmax=0)")
         rkw = dict(refine_rounds=refine_rounds, refine_method=refine_method, row_stats=refine_method == "mask_predict")
         self.last_refine_round = self.last_refine_row_stats = None
+        # opt['attn_topk'] / opt['attn_maps'] / opt['attn_layer']: the word-to-region attention of the NAIC filling pass (BofiEngine.decode_naic); the 6-tuple stays and the
+        # tensors ('attn' [B, S, R]; 'attn_top' / 'attn_top_w' [B, S, K]) land in self.last_attn (None otherwise), repeated like the layout under sample_n > 1
+        attn_topk, attn_maps, attn_layer = int(opt.get("attn_topk", 0)), bool(opt.get("attn_maps", False)), int(opt.get("attn_layer", -1))
+        if (attn_topk or attn_maps) and train_mode != "NAIC":
+            raise hip.BofiHipError("attn_topk / attn_maps read the non-autoregressive filling pass's cross-attention: train_mode 'NAIC' only")
+        if attn_topk or attn_maps:
+            rkw.update(attn_topk=attn_topk, attn_maps=attn_maps, attn_layer=attn_layer)
+        self.last_attn = None
         eng = self.engine()
         torch.cuda.synchronize()                                  # the reference does (AttModel.py:337)
         start = time.time()
@@ -339,6 +350,9 @@ class TransformerModel(nn.Module):
             del recent[:-8]
             if refine_method == "mask_predict":                 # (the log-prob tensor is the last pass's: the emitting passes' row statistics are kept beside the rounds)
                 self.last_refine_round, self.last_refine_row_stats = r["refine_round"], (r["row_plogp"], r["row_chosen"])
+            if attn_topk or attn_maps:
+                keys = (("attn",) if attn_maps else ()) + (("attn_top", "attn_top_w") if attn_topk else ())
+                self.last_attn = {k: (r[k].repeat_interleave(sample_n, dim=0) if sample_n > 1 else r[k]) for k in keys}
         elif sample_method == "greedy":                           # core_SAIC, AttModel.py:430-437
             # (the loop is enqueued for the iterations recent decodes needed, the rest only if this one needs them: saic_cap / saic_finish)
             adaptive = getattr(self.opt, "bofi_saic_iter_budget", True)

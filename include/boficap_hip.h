@@ -712,6 +712,33 @@ int bofi_mask_predict_step(int64_t* ids, float* chosen, float* plogp, int* round
                            const float* fresh_plogp, int* mask, int64_t* next_ids, const int* last, int B, int S, int t, int T, int bos_idx,
                            int pad_idx, int64_t* seq_out, float* plogp_out, float* chosen_out, int* round_out, void* stream);
 
+/* Word-to-region attention maps: the cross-attention probabilities the fused attention sublayers never leave in memory (the reference keeps them as
+ * MultiHeadedAttention.attn, TransformerModel.py:1459), from the queries and keys such a sublayer reads.  d_k = 64.
+ *   q [B * Lq rows, pitch ldq elements], k [B * Lk rows, pitch ldk]: `dtype` BOFI_DT_F32 or BOFI_DT_BF16; head h is columns 64 h .. 64 h + 63 (ldq, ldk >= 64 H).
+ *   klen int32 [B] or NULL: keys per image (clamped to 0 .. Lk; NULL: Lk).  qlen int32 [B] or NULL, qlen_bias: query rows that carry a word, qlen[b] + qlen_bias (NULL: Lq).
+ *   A[b,h,t,r] = softmax over r < len_b of (q[b,t,h,:] . k[b,r,h,:] * scale); +0.0 for len_b <= r < Lk.  A row whose scores hold a NaN (or +infinity) is NaN in ALL
+ *                its Lk entries, as the reference's softmax over the masked scores leaves it.  The engine's attention kernels apply scale = 1 / sqrt(64) themselves
+ *                (it is not folded into the query projection), so that is what the engine passes.
+ *   mean  float32 [B, Lq, Lk] or NULL:  M = (A[b,0] + A[b,1] + ... in head order) / H.
+ *   heads float32 [B, H, Lq, Lk] or NULL:  A.
+ *   top_idx int32 / top_w float32 [B, Lq, K], both or NULL, 0 <= K <= 8: the K largest entries of M[b,t,:len_b] in descending order, equal weights by lower region
+ *                index, top_w = M's own floats bit for bit; slots j >= len_b: (-1, 0); a row of M with a NaN: (-1, NaN) in every slot; rows t >= qlen[b] + qlen_bias:
+ *                (-1, 0) -- M and A are written for those rows all the same.
+ * Every element of every given buffer is written.  float32 throughout from the inputs as stored, max-subtracted exp, fixed summation orders, no atomics: deterministic.
+ * BOFI_ERR_ARG with a message and no launch: B < 1, H < 1, Lq outside 1..64, Lk outside 1..128, K outside 0..8, an unknown dtype, NULL q or k, a pitch below 64 H,
+ * no output buffer, one of top_idx / top_w without the other, K > 0 without them, H so large that one query row's share of LDS exceeds 144 KB.
+ * One launch: a workgroup per image, a wavefront per head. */
+int bofi_attn_maps(const void* q, int ldq, const void* k, int ldk, int dtype, int B, int H, int Lq, int Lk, float scale, const int* klen,
+                   const int* qlen, int qlen_bias, float* mean, float* heads, int K, int* top_idx, float* top_w, void* stream);
+/* Optional outputs of the following bofi_engine_decode_naic / bofi_engine_fill_naic calls of this engine: the maps above for decoder layer `layer` (0 .. N_dec - 1, or -1 =
+ * the last) of the filling pass -- Lq = seq_length, Lk = R, klen = att_len, qlen = tokens laid out -- device buffers mean [B, S, R], heads [B, H, S, R], top_idx / top_w
+ * [B, S, K] as for bofi_attn_maps (any of the three groups may be NULL; all NULL: off -- the default, also of a fork).  One extra launch per decode, right behind the layer's
+ * cross-attention sublayer, from the queries and keys that sublayer read; it belongs to BOFI_FLAG_PHASE_FILL.  With refinement rounds only the LAST pass launches it:
+ * under feed-back that is the final ids' own pass; under BOFI_FLAG_MASK_PREDICT the rows of kept positions are that pass's re-prediction, not the pass that emitted the
+ * token (as seq_logprob).  Needs seq_length <= 64 and R <= 128 (BOFI_ERR_ARG at the decode otherwise); bofi_engine_decode_saic with an output set is BOFI_ERR_STATE.
+ * Per-call state, part of the graph key. */
+int bofi_engine_set_attn_out(bofi_engine_t* e, int layer, float* mean, float* heads, int K, int* top_idx, float* top_w);
+
 /* Last HIP error string seen by this library on the calling thread (for exceptions in the host). */
 const char* bofi_last_error(void);
 

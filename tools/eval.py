@@ -12,6 +12,7 @@ dictionary; boficap_amd.features): the images and their ids are the json's split
 padded on the device, ``image_id`` in the predictions is the json's id, and image i of the split uses image ``split_ix[i]`` of ``--input_label_npz``.
 Box features (``--use_box 1``) are refused: they make F = 2053 and the engine needs F % 64 == 0.  ``--language_eval 1`` (with ``--input_label_npz``: the references) adds the language scores that need no Java -- BLEU-1..4,
 ROUGE-L, CIDEr on the device (boficap_amd.lang_eval) -- as a printed line and, in ``--dump_json``, under a top-level key.
+``--attn_topk K`` (NAIC) adds 'regions' to every prediction: per emitted word the K image regions its position attended to most, as [region, weight] pairs.
 ``--refine_rounds N [--refine_method feed_back|mask_predict]`` (NAIC) adds N filling passes: on all of the previous ids, or -- mask-predict -- on the least
 confident positions only.
 ``--sample_n N`` (N > 1, with ``--cached_tokens``: the document frequencies) draws N captions per image after the greedy pass and adds their
@@ -73,12 +74,20 @@ def main():
     ap.add_argument("--refine_rounds", type=int, default=0, help="NAIC only: N extra filling passes (0..15) after the first")
     ap.add_argument("--refine_method", default="feed_back", choices=["feed_back", "mask_predict"], help="what the extra passes are: 'feed_back' decodes again on all of the "
                     "previous ids; 'mask_predict' (needs --refine_rounds >= 1) re-predicts only each caption's least confident positions, fewer every pass, and keeps the rest")
+    ap.add_argument("--attn_topk", type=int, default=0, help="NAIC only: K in 1..8 -- every prediction gains 'regions', per emitted word the [region, weight] pairs of the K "
+                    "image regions its position attended to most (mean over heads of the last decoder layer's cross-attention), heaviest first")
     args = ap.parse_args()
+    if args.attn_topk and args.inference_mode != "NAIC":
+        ap.error("--attn_topk reads the non-autoregressive filling pass's cross-attention: it needs --inference_mode NAIC")
+    if not 0 <= args.attn_topk <= 8:
+        ap.error("--attn_topk must be in 0..8")
     if (args.refine_rounds or args.refine_method != "feed_back") and args.inference_mode != "NAIC":
         ap.error("--refine_rounds / --refine_method refine the non-autoregressive filling pass: they need --inference_mode NAIC")
     if not 0 <= args.refine_rounds <= 15 or (args.refine_method == "mask_predict" and args.refine_rounds < 1):
         ap.error("--refine_rounds must be in 0..15, and --refine_method mask_predict needs at least 1")
     refine = {"refine_rounds": args.refine_rounds, "refine_method": args.refine_method}
+    if args.attn_topk:                                           # (rides with the refinement options: decode_many and mode='sample' take it the same way)
+        refine["attn_topk"] = args.attn_topk
     if args.language_eval and not args.input_label_npz:
         ap.error("--language_eval 1 needs the references: --input_label_npz")
     if args.use_box:
@@ -162,7 +171,7 @@ def main():
             i = 0
             for r in got:
                 n = r["seq"].size(0)
-                results.extend(entry_of(i, k, r["seq"], r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"]) for k in range(n))
+                results.extend(eval_utils.with_regions(entry_of(i, k, r["seq"], r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"]), r, k) for k in range(n))
                 i += n
             how = (f"pipelined: {args.in_flight} launches in flight, {args.batches_per_launch} batches of {args.batch_size} per launch, feature files read by {args.feeder_workers} "
                    f"threads and staged ragged, file reads and host results included" + (", fused vocabulary epilogue" if args.fused_vocab else ""))
@@ -185,7 +194,7 @@ def main():
             i = 0
             for r in got:                                        # (the JSON entries are built outside the clock: ~20 us of Python per image)
                 n = r["seq"].size(0)
-                results.extend(entry_of(i, k, r["seq"], r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"]) for k in range(n))
+                results.extend(eval_utils.with_regions(entry_of(i, k, r["seq"], r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"]), r, k) for k in range(n))
                 i += n
             how = f"pipelined: {args.in_flight} launches in flight, {args.batches_per_launch} batches of {args.batch_size} per launch, features from pinned host memory, host results included" + (", fused vocabulary epilogue" if args.fused_vocab else "")
         else:
@@ -204,7 +213,8 @@ def main():
                     ent, ppl = model.engine().entropy_perplexity({"seq": seq, "_row_stats_fused": True, "row_plogp": model.last_refine_row_stats[0], "row_chosen": model.last_refine_row_stats[1]})
                 else:
                     ent, ppl = model.engine().entropy_perplexity({"seq": seq, "seq_logprob": lp})
-                results.extend(entry_of(i, k, seq, pn, pl, ent, ppl) for k in range(att.size(0)))
+                r = {"seq": seq.cpu(), **({k2: model.last_attn[k2].cpu() for k2 in ("attn_top", "attn_top_w")} if args.attn_topk else {})}
+                results.extend(eval_utils.with_regions(entry_of(i, k, seq, pn, pl, ent, ppl), r, k) for k in range(att.size(0)))
             how = "one synchronised mode='sample' call per batch (the reference's eval loop), decode time only"
     if image_ids is not None:                                    # the json's ids, in the split's order
         for e, iid in zip(results, image_ids):
