@@ -30,6 +30,14 @@ references alone (integer rows or id strings; no loss then), or None.  ``eval_kw
     eval_oracle      1, with ``language_eval`` 1 and ``sample_n`` > 1 (nothing changes otherwise): every sampled caption is scored against its image's
                      references and ``lang_stats`` gains 'oracle_<M>' (the best of an image's N, averaged over the images) and 'avg_<M>' (their mean)
                      for M = Bleu_1..Bleu_4, ROUGE_L, CIDEr (``LanguageEval.evaluate_n``); per image under ``eval_kwargs['oracle_per_image']``
+    remove_bad_endings   1: every caption loses its trailing function words (decode_sequence under REMOVE_BAD_ENDINGS, boficap_amd.surface) before the entries are
+                     built and before any scorer reads it -- the greedy ids before ``LanguageEval.evaluate``, the sampled ids before ``preds_n``, the diversity
+                     statistics and the oracle scores: 'seq', 'caption' and 'regions' cover the kept ids only.  'phrase_num', 'phrase_length', entropy, perplexity
+                     and ``eval_kwargs['refine_round']`` describe the decode and stay.  ``model(..., mode='sample')`` itself returns untrimmed ids
+    surface_stats    1: with ``language_eval`` 1 ``lang_stats`` gains 'bad_count_rate' (the share of captions that end in a word of surface.COUNT_WORDS), and with
+                     ``sample_n`` > 1 'novel_sentences' and 'vocab_size' of the sampled captions against ``eval_kwargs['train_sentences']``, a
+                     ``surface.TrainSentences`` (required then); the new keys follow every other key, in the order novel_sentences, vocab_size, bad_count_rate
+    caption_surface  the ``surface.CaptionSurface`` both options use, kept by the caller; built from ``vocab`` (and stored under this key) if absent
 """
 from __future__ import annotations
 
@@ -119,10 +127,11 @@ class SyntheticLabels:
         return self.host["labels"][int(ix), :, 1:-1]
 
 
-def sample_n_predictions(model, feats, sample_n: int, mode: str = "NAIC", batch_size: int = 64, vocab=None):
+def sample_n_predictions(model, feats, sample_n: int, mode: str = "NAIC", batch_size: int = 64, vocab=None, surface=None):
     """eval_split_n (eval_utils.py:670-700) for ``sample_n_method='sample'``: ``sample_n`` captions per image of ``feats`` drawn through
     ``mode='sample'``.  Returns (entries {'image_id', 'seq'[, 'caption']} in row order, the sampled ids [N * sample_n, S] on the device); an
-    entry's 'seq' holds the ids before the first id <= 0 (decode_sequence)."""
+    entry's 'seq' holds the ids before the first id <= 0 (decode_sequence).  ``surface``: a ``CaptionSurface`` -- the ids are trimmed of their bad endings on
+    the device first, and both results are the trimmed ones."""
     n, ragged = int(sample_n), is_region_source(feats)
     host = feats if ragged else _torch_feats(feats)
     step = batch_size if mode == "NAIC" else max(1, min(batch_size, model.max_batch // n))       # the SAIC sampler decodes images x n rows
@@ -138,6 +147,8 @@ def sample_n_predictions(model, feats, sample_n: int, mode: str = "NAIC", batch_
             fc = torch.zeros(att.size(0), 0, device="cuda")
             rows.append(model(fc, att, masks, opt={"train_mode": mode, "sample_method": "sample", "sample_n": n}, mode="sample")[0])
     seq = torch.cat(rows)
+    if surface is not None:
+        seq = surface.trim(seq)[0]
     entries = []
     for j, row in enumerate(seq.cpu().tolist()):
         stop = next((q for q, v in enumerate(row) if v <= 0), len(row))
@@ -163,6 +174,21 @@ def _torch_feats(feats):
     return feats if torch.is_tensor(feats) else torch.from_numpy(np.ascontiguousarray(feats))
 
 
+def caption_surface(model, eval_kwargs):
+    """The ``CaptionSurface`` of ``remove_bad_endings`` / ``surface_stats``: ``eval_kwargs['caption_surface']``, else one built from
+    ``eval_kwargs['vocab']`` and kept under that key from one evaluation to the next."""
+    surface = eval_kwargs.get("caption_surface")
+    if surface is None:
+        vocab = eval_kwargs.get("vocab")
+        if not vocab:
+            raise ValueError("remove_bad_endings / surface_stats need the ids of the bad-ending words: eval_kwargs['caption_surface'] (a "
+                             "surface.CaptionSurface) or eval_kwargs['vocab'] ({str(id): word})")
+        from .surface import CaptionSurface
+        V = max(int(model.cfg.tgt_vocab), 1 + max(int(k) for k in vocab))
+        surface = eval_kwargs["caption_surface"] = CaptionSurface.from_vocab(vocab, V, next(model.parameters()).device)
+    return surface
+
+
 def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
     """(val_loss, predictions, lang_stats) of ``feats``' images: see the module's head.  The model is put in eval() and restored."""
     kw = eval_kwargs
@@ -179,6 +205,11 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
         raise ValueError("attn_topk reads the non-autoregressive filling pass's cross-attention: inference_mode 'NAIC' only")
     if attn_topk:
         refine["attn_topk"] = attn_topk
+    remove, surface_stats = int(kw.get("remove_bad_endings", 0)) == 1, int(kw.get("surface_stats", 0)) == 1
+    if surface_stats and sample_n > 1 and kw.get("train_sentences") is None:
+        raise ValueError("surface_stats with sample_n > 1 looks the sampled captions up among the training sentences: eval_kwargs['train_sentences'] "
+                         "(a surface.TrainSentences) is missing")
+    surface = caption_surface(model, kw) if remove or surface_stats else None
     rounds = []
     N = len(feats)
     ixs = kw.get("image_ixs")
@@ -192,20 +223,16 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
         if store is not None and kw.get("verbose_loss", 1):
             loss_sum, loss_evals = validation_loss(model, feats, store, batch_size, seq_per_img, ixs)
             val_loss = loss_sum / max(1, loss_evals)
-        predictions, seqs, ents, ppls = [], [], [], []
+        predictions, got = [], []
         vocab = kw.get("vocab")
         ragged = is_region_source(feats)
         host = feats if ragged else _torch_feats(feats)
         with torch.no_grad():
             if mode == "NAIC" and ragged:                       # staged ragged batch by batch, ahead of the launches that consume them
-                i = 0
                 for r in model.decode_many((feats.ragged(j, min(j + batch_size, N)) for j in range(0, N, batch_size)), batches_per_launch=int(kw.get("batches_per_launch", 16)),
                                            in_flight=kw.get("in_flight"), fused_vocab=bool(kw.get("fused_vocab", False)), **refine):
-                    n = r["seq"].size(0)
                     rounds.append(r.get("refine_round"))
-                    predictions.extend(with_regions(entry_of(i, k, r["seq"], r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"], vocab), r, k) for k in range(n))
-                    seqs.append(r["seq"]); ents.append(r["entropy"]); ppls.append(r["perplexity"])
-                    i += n
+                    got.append(r)
             elif mode == "NAIC":
                 if host.dtype != torch.float32 and host.dtype != model.compute_dtype:
                     host = host.float()
@@ -214,14 +241,10 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
                 if not host.is_cuda:
                     host = host.pin_memory()
                 batches = [host[i:i + batch_size] for i in range(0, N, batch_size)]
-                i = 0
                 for r in model.decode_many(batches, batches_per_launch=int(kw.get("batches_per_launch", 16)), in_flight=kw.get("in_flight"),
                                            fused_vocab=bool(kw.get("fused_vocab", False)), **refine):
-                    n = r["seq"].size(0)
                     rounds.append(r.get("refine_round"))
-                    predictions.extend(with_regions(entry_of(i, k, r["seq"], r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"], vocab), r, k) for k in range(n))
-                    seqs.append(r["seq"]); ents.append(r["entropy"]); ppls.append(r["perplexity"])
-                    i += n
+                    got.append(r)
             else:
                 for i in range(0, N, batch_size):
                     if ragged:
@@ -232,9 +255,19 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
                     seq, lp, pn, pl, ps, _ = model(fc, att, masks, opt={"train_mode": "SAIC", "sample_method": "greedy", "sample_n": 1}, mode="sample")
                     # per-image entropy / perplexity as eval_utils.py:463-464, from the fused row reductions (bofi_vocab_stats)
                     ent, ppl = model.engine().entropy_perplexity({"seq": seq, "seq_logprob": lp})
-                    seq, pn, pl, ent, ppl = seq.cpu(), pn.cpu(), pl.cpu(), ent.cpu(), ppl.cpu()
-                    predictions.extend(entry_of(i, k, seq, pn, pl, ent, ppl, vocab) for k in range(att.size(0)))
-                    seqs.append(seq); ents.append(ent); ppls.append(ppl)
+                    got.append({"seq": seq.cpu(), "phrase_num": pn.cpu(), "phrase_length": pl.cpu(), "entropy": ent.cpu(), "perplexity": ppl.cpu()})
+            # the batches' results are host tensors: with a surface option, ONE trim launch over the split's ids, before the entries and the scorers
+            seqs, ents, ppls = [r["seq"] for r in got], [r["entropy"] for r in got], [r["perplexity"] for r in got]
+            scored, bad = None, None
+            if got and (remove or (surface_stats and int(kw.get("language_eval", 0)) == 1)):
+                scored, _, bad = surface.trim(torch.cat(seqs), remove=remove)
+                if remove:
+                    seqs = list(torch.split(scored.cpu(), [s.size(0) for s in seqs]))
+            i = 0
+            for r, seq in zip(got, seqs):
+                r = dict(r, seq=seq)
+                predictions.extend(with_regions(entry_of(i, k, seq, r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"], vocab), r, k) for k in range(seq.size(0)))
+                i += seq.size(0)
         if refine["refine_method"] == "mask_predict":
             kw["refine_round"] = torch.cat(rounds)
         lang_stats, ev = None, None
@@ -246,15 +279,21 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
                 gts = [store.gts(int(ixs[i]) if ixs is not None else i) for i in range(N)] if store is not None else list(store_or_gts)
                 from .lang_eval import LanguageEval
                 ev = kw["lang_eval"] = LanguageEval(gts, next(model.parameters()).device)
-            lang_stats = ev.evaluate(torch.cat(seqs), torch.cat(ents), torch.cat(ppls))
+            lang_stats = ev.evaluate(scored if remove else torch.cat(seqs), torch.cat(ents), torch.cat(ppls))
         if sample_n > 1:                                         # eval_split_n + the div_stats / self_cider of language_eval (eval_utils.py:105-120)
-            kw["preds_n"], sampled = sample_n_predictions(model, feats, sample_n, mode, batch_size, vocab)
+            kw["preds_n"], sampled = sample_n_predictions(model, feats, sample_n, mode, batch_size, vocab, surface if remove else None)
             div, kw["diversity_per_image"] = diversity_stats(sampled, sample_n, kw)
             lang_stats = dict(lang_stats or {}, **div)
             if ev is not None and int(kw.get("eval_oracle", 0)) == 1:      # the oracle of language_eval (eval_utils.py:112-114): inside it, and only with a preds_n
                 oracle = ev.evaluate_n(sampled, sample_n)
                 kw["oracle_per_image"] = oracle.pop("per_image")
                 lang_stats.update(oracle)
+            if surface_stats:                                    # novel_sentences / vocab_size of language_eval (eval_utils.py:55-69), on the ids
+                from .surface import sentence_stats
+                canon, kept, _ = surface.trim(sampled, remove=False)      # (the canonical form of the -- already trimmed -- rows, and their lengths)
+                lang_stats.update(sentence_stats(canon, kept, kw["train_sentences"], surface.V))
+        if surface_stats and bad is not None and ev is not None:      # bad_count_rate (eval_utils.py:122): inside language_eval, of the scored captions
+            lang_stats["bad_count_rate"] = surface.bad_count_rate(bad)
     finally:
         model.train(was_training)
     return val_loss, predictions, lang_stats

@@ -129,6 +129,8 @@ SIGNATURES = {
     "bofi_mask_predict_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "bofi_attn_maps": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_float, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
     "bofi_engine_set_attn_out": (_I, [_P, _I, _P, _P, _I, _P, _P]),
+    "bofi_caption_trim": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "bofi_sentence_lookup": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
 }
 
 _lib = None

@@ -739,6 +739,30 @@ int bofi_attn_maps(const void* q, int ldq, const void* k, int ldk, int dtype, in
  * Per-call state, part of the graph key. */
 int bofi_engine_set_attn_out(bofi_engine_t* e, int layer, float* mean, float* heads, int K, int* top_idx, float* top_w);
 
+/* The bad-ending trim of the reference's decode_sequence (captioning/utils/misc.py:75-82, REMOVE_BAD_ENDINGS) and the flag of its count_bad
+ * (captioning/utils/eval_utils.py:32-37), on id rows.  seq int64 [rows, S], 1 <= S <= 64.  The caption of a row is its ids before the first id <= limit
+ * (the whole row without one; 'eval' rule: limit = 0), L of them.  trim_bits / count_bits: uint32 [ceil(V / 32)] each, bit (id % 32) of word id / 32 set for
+ * the ids of a word set; either may be NULL (the empty set).  An id < 0 or >= V is in neither set and is not looked up.
+ *   k = the length of the run of trim_bits members that ends at position L - 1; k = L (every word a member, or L = 0) counts as k = 0: nothing is removed.
+ *   out_seq int64 [rows, S]: the L - k kept ids, then `pad` to the end of the row; it may be seq itself.  out_len int32 [rows]: L - k.
+ *   out_bad int32 [rows]: 1 when L - k > 0 and the last kept id is a count_bits member, else 0.
+ * rows = 0 is BOFI_OK without a launch; rows < 0, S outside 1..64, V < 1, a NULL seq or output: BOFI_ERR_ARG with a message, nothing is launched.
+ * One launch, one wavefront per row, comparisons only: deterministic. */
+int bofi_caption_trim(const int64_t* seq, int rows, int S, int limit, const uint32_t* trim_bits, const uint32_t* count_bits, int V, int pad,
+                      int64_t* out_seq, int* out_len, int* out_bad, void* stream);
+
+/* Generated sentences among the training sentences, and the words they use (novel_sentences / vocab_size of the reference's language_eval,
+ * eval_utils.py:61-69), on id rows in the canonical form bofi_caption_trim writes with pad = 0: len[r] kept ids (clamped to 0..S), then zeros.
+ *   seq int64 [rows, S], len int32 [rows], 1 <= S <= 64.  train int32 [M, St]: the training sentences in the same form, distinct, sorted lexicographically
+ *   by row (signed comparison, column 0 first); M >= 0 (train may be NULL when M = 0), 1 <= St <= 64.
+ *   novel int32 [rows]: 0 when the row, zero-extended, equals a training row, zero-extended; else 1.  So a row with a non-zero id at a position >= St is novel, a
+ *     strict prefix of a training row is novel, and the empty row is a sentence like any other.
+ *   seen int32 [V], zeroed by the caller: seen[id] = 1 for every kept id in [0, V) of every row (plain stores of the same value); other ids are skipped.
+ * rows = 0 is BOFI_OK without a launch; bad sizes or a NULL among seq / len / novel / seen: BOFI_ERR_ARG with a message, nothing is launched.
+ * One launch, one wavefront per row: a binary search of at most ceil(log2(M + 1)) probes, each one row of train.  Deterministic. */
+int bofi_sentence_lookup(const int64_t* seq, const int* len, int rows, int S, const int* train, int M, int St, int V, int* novel, int* seen,
+                         void* stream);
+
 /* Last HIP error string seen by this library on the calling thread (for exceptions in the host). */
 const char* bofi_last_error(void);
 

@@ -19,6 +19,10 @@ confident positions only.
 diversity statistics -- Div-1, Div-2, mBLEU-1..4, self-CIDEr on the device (boficap_amd.diversity) -- the same way, with the sampled captions under
 ``preds_n``.  ``--eval_oracle 1`` (with ``--language_eval 1 --sample_n N``) scores every sampled caption against its image's references and adds
 the best of an image's N and their mean per metric (``oracle_<M>``, ``avg_<M>``: boficap_amd.lang_eval.LanguageEval.evaluate_n) as one more line.
+``--remove_bad_endings 1`` strips every caption's trailing function words on the device (the reference's REMOVE_BAD_ENDINGS; boficap_amd.surface) before it is
+scored and dumped; ``--surface_stats 1`` adds ``bad_count_rate`` (with ``--language_eval 1``) and, with ``--sample_n N``, ``novel_sentences`` and ``vocab_size``
+of the sampled captions against the training sentences: the captions in ``--input_label_npz`` of every image of ``--input_json`` whose split is neither val nor
+test.  Both need the words' ids: ``--infos_path`` (a vocabulary), or ``--bad_endings W1,W2,...``, which overrides the trimmed word set for other vocabularies.
 """
 import argparse
 import json
@@ -76,7 +80,16 @@ def main():
                     "previous ids; 'mask_predict' (needs --refine_rounds >= 1) re-predicts only each caption's least confident positions, fewer every pass, and keeps the rest")
     ap.add_argument("--attn_topk", type=int, default=0, help="NAIC only: K in 1..8 -- every prediction gains 'regions', per emitted word the [region, weight] pairs of the K "
                     "image regions its position attended to most (mean over heads of the last decoder layer's cross-attention), heaviest first")
+    ap.add_argument("--remove_bad_endings", type=int, default=0, choices=[0, 1], help="1: every caption (greedy and sampled) loses its trailing run of bad-ending "
+                    "words before it is scored and dumped; a caption of such words alone is left as it is")
+    ap.add_argument("--surface_stats", type=int, default=0, choices=[0, 1], help="1: bad_count_rate (with --language_eval 1) and, with --sample_n N, novel_sentences "
+                    "and vocab_size of the sampled captions (these need --input_label_npz and --input_json: the training sentences)")
+    ap.add_argument("--bad_endings", default="", help="W1,W2,...: the words --remove_bad_endings strips, instead of the reference's list")
     args = ap.parse_args()
+    if (args.remove_bad_endings or args.surface_stats) and not (args.infos_path or args.bad_endings):
+        ap.error("--remove_bad_endings / --surface_stats need the ids of the bad-ending words: --infos_path (a vocabulary) or --bad_endings W1,W2,...")
+    if args.surface_stats and args.sample_n > 1 and not (args.input_label_npz and args.input_json):
+        ap.error("--surface_stats 1 with --sample_n N looks the sampled captions up among the training sentences: it needs --input_label_npz and --input_json")
     if args.attn_topk and args.inference_mode != "NAIC":
         ap.error("--attn_topk reads the non-autoregressive filling pass's cross-attention: it needs --inference_mode NAIC")
     if not 0 <= args.attn_topk <= 8:
@@ -145,6 +158,22 @@ def main():
         src = args.input_label_npz if args.input_label_npz.endswith((".h5", ".hdf5")) else dict(np.load(args.input_label_npz))
         store = LabelStore(src, pad_idx=c.pad_idx, bos_idx=c.bos_idx, eos_idx=c.eos_idx, len_idx=c.len_idx)
     results, seconds, rows, stats = [], 0.0, [], ([], [])
+    surface, bad_flags = None, []
+    if args.remove_bad_endings or args.surface_stats:
+        from boficap_amd.surface import CaptionSurface, TrainSentences, sentence_stats
+        words = vocab or opt.vocab
+        surface = CaptionSurface.from_vocab(words, max(int(model.cfg.tgt_vocab), 1 + max(int(k) for k in words)), "cuda",
+                                            trim_words=[w for w in args.bad_endings.split(",") if w] if args.bad_endings else None)
+
+    def surfaced(batches):
+        """The decoded batches with their ids trimmed (--remove_bad_endings): one launch over all of them; their bad-ending flags are kept."""
+        if surface is None or not batches:
+            return batches
+        out, _, bad = surface.trim(torch.cat([r["seq"] for r in batches]), remove=bool(args.remove_bad_endings))
+        bad_flags.append(bad)
+        if not args.remove_bad_endings:
+            return batches
+        return [dict(r, seq=seq) for r, seq in zip(batches, torch.split(out.cpu(), [r["seq"].size(0) for r in batches]))]
 
     def entry_of(i, k, seq, pn, pl, ent, ppl):
         if args.language_eval and k == 0:                        # (the batch's raw rows, for the language scores)
@@ -169,7 +198,7 @@ def main():
             got = list(model.decode_many(feeder(key_batches), batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab, **refine))
             seconds = time.time() - t0
             i = 0
-            for r in got:
+            for r in surfaced(got):
                 n = r["seq"].size(0)
                 results.extend(eval_utils.with_regions(entry_of(i, k, r["seq"], r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"]), r, k) for k in range(n))
                 i += n
@@ -192,7 +221,7 @@ def main():
                 got.append(r)                                    # host tensors of one batch: ids, slot layout, entropy, perplexity
             seconds = time.time() - t0
             i = 0
-            for r in got:                                        # (the JSON entries are built outside the clock: ~20 us of Python per image)
+            for r in surfaced(got):                              # (the JSON entries are built outside the clock: ~20 us of Python per image)
                 n = r["seq"].size(0)
                 results.extend(eval_utils.with_regions(entry_of(i, k, r["seq"], r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"]), r, k) for k in range(n))
                 i += n
@@ -213,8 +242,8 @@ def main():
                     ent, ppl = model.engine().entropy_perplexity({"seq": seq, "_row_stats_fused": True, "row_plogp": model.last_refine_row_stats[0], "row_chosen": model.last_refine_row_stats[1]})
                 else:
                     ent, ppl = model.engine().entropy_perplexity({"seq": seq, "seq_logprob": lp})
-                r = {"seq": seq.cpu(), **({k2: model.last_attn[k2].cpu() for k2 in ("attn_top", "attn_top_w")} if args.attn_topk else {})}
-                results.extend(eval_utils.with_regions(entry_of(i, k, seq, pn, pl, ent, ppl), r, k) for k in range(att.size(0)))
+                r = surfaced([{"seq": seq.cpu(), **({k2: model.last_attn[k2].cpu() for k2 in ("attn_top", "attn_top_w")} if args.attn_topk else {})}])[0]
+                results.extend(eval_utils.with_regions(entry_of(i, k, r["seq"], pn, pl, ent, ppl), r, k) for k in range(att.size(0)))
             how = "one synchronised mode='sample' call per batch (the reference's eval loop), decode time only"
     if image_ids is not None:                                    # the json's ids, in the split's order
         for e, iid in zip(results, image_ids):
@@ -230,7 +259,8 @@ def main():
         print("language scores " + " ".join(f"{k} {v:.6f}" for k, v in lang_stats.items()))
     preds_n = None
     if args.sample_n > 1:
-        preds_n, sampled = eval_utils.sample_n_predictions(model, feats, args.sample_n, args.inference_mode, args.batch_size, vocab)
+        preds_n, sampled = eval_utils.sample_n_predictions(model, feats, args.sample_n, args.inference_mode, args.batch_size, vocab,
+                                                           surface if args.remove_bad_endings else None)
         if image_ids is not None:
             for e in preds_n:
                 e["image_id"] = image_ids[e["image_id"]]
@@ -242,6 +272,18 @@ def main():
             oracle.pop("per_image")
             lang_stats.update(oracle)
             print("oracle scores " + " ".join(f"{k} {v:.6f}" for k, v in oracle.items()))
+    if args.surface_stats:
+        surf = {}
+        if args.sample_n > 1:                                    # the training sentences: every image of the json that is neither val nor test
+            from boficap_amd.features import ImageIndex
+            train_ixs = [ix for ix, img in enumerate(ImageIndex(args.input_json).images) if img.get("split") not in ("val", "test")]
+            canon, kept, _ = surface.trim(sampled, remove=False)
+            surf.update(sentence_stats(canon, kept, TrainSentences.from_store(store, train_ixs, "cuda"), surface.V))
+        if args.language_eval:
+            surf["bad_count_rate"] = surface.bad_count_rate(torch.cat(bad_flags))
+        if surf:
+            lang_stats = dict(lang_stats or {}, **surf)
+            print("surface statistics " + " ".join(f"{k} {v:.6f}" for k, v in surf.items()))
     if args.dump_json:
         with open(args.dump_json, "w") as f:
             if preds_n is not None:
