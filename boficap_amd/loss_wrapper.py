@@ -28,7 +28,7 @@ import os
 
 import torch
 
-from . import cider, hip, xe
+from . import cider, hip, rl_draws, xe
 
 _SCORER = {"fn": None}
 
@@ -70,76 +70,24 @@ def device_scorer(opt):
 
 
 def reference_estimator_pass(model, att_feats, att_masks, sample_n: int, temperature: float, seed: int):
-    """loss_wrapper.py:193-209 (``model(..., mode='sample')`` twice in train mode with the tape, then the loss on THOSE log-probs) on this build's training forward
-    -- the eager form of ``XETrainer._rl_reference_step`` (boficap_amd/trainer.py), without a trainer: the caller owns backward and the optimiser.
-
-      * non-autoregressive branch: the engine's bounding loop lays the slots out (greedy heads: one layout per image, no gradient reaches it in the reference either);
-        the words of every slot are drawn from the training forward's fill rows;
-      * semi-autoregressive branch: the engine's loop runs one iteration per call (bofi_engine_set_saic_range, layout only): its bounding step lays the next phrase
-        out on the words so far (TransformerModel.py:1903-1948), a tape-free training forward under ``seed`` gives that phrase's rows, its words are drawn from them
-        (Categorical(logits / temperature), CaptionModel.py:405-425) and handed back (bofi_engine_saic_put_words);
-      * then the same forward once more WITH the tape: counter-based dropout masks (seed, site, element) make it the same rows bit for bit.
+    """loss_wrapper.py:193-209 (``model(..., mode='sample')`` twice in train mode with the tape, then the loss on THOSE log-probs) on this build's training
+    forward, without a trainer (the caller owns backward and the optimiser): ``rl_draws.draw_pass`` -- the one draw pass, ``XETrainer._rl_reference_step``'s
+    too -- draws every token of both branches from eager tape-free training forwards under ``seed``, then the same forward once more WITH the tape:
+    counter-based dropout masks (seed, site, element) make it the same rows bit for bit.
     Returns (saic log-probs [N, S, V] with grad, naic log-probs, saic dict, naic dict, gap) -- ``gap``: max |tape row - drawn row| at the drawn tokens (0.0)."""
-    cfg = model.cfg
-    S, dev = cfg.seq_length, att_feats.device
-    eng = model.engine()
-    feats_in, lens_in = model._as_input(att_feats), model._att_len(att_masks)
-    N = feats_in.size(0) * sample_n
-    if N > model.max_batch:
-        raise hip.BofiHipError(f"{N} sampled rows exceed bofi_max_batch={model.max_batch}")
-    P = xe.Params(model)
+    cfg, P = model.cfg, xe.Params(model)
+    shared: dict = {}                                             # the encoder's memory and the cross K|V: the same tensors in every tape-free forward of this step
 
     def rows_of(prep, reuse=None):
         return xe.sampled_logprobs_prepared(P, cfg, att_feats, att_masks, prep, sample_n=sample_n, training=True, seed=seed, compute_dtype=model.train_dtype, reuse=reuse)
 
-    draws = [0]
-
-    def draw(lp, plen, p0, p1, seq, drawn, mask):
-        lpf = lp if lp.dtype == torch.float32 and lp.is_contiguous() else lp.float().contiguous()
-        n_, s_, V = lpf.shape
-        tok = torch.empty(n_, s_, dtype=torch.int64, device=dev)
-        draws[0] += 1
-        sseed = (seed + 0x5EED0000 + draws[0]) & 0xFFFFFFFFFFFFFFFF
-        hip.check(hip.lib().bofi_vocab_sample(hip.ptr(lpf), n_ * s_, V, s_, 1, float(temperature), sseed, None, cfg.pad_idx, hip.ptr(tok), hip.stream_ptr()), "bofi_vocab_sample")
-        hip.check(hip.lib().bofi_rl_take_draws(hip.ptr(lpf), hip.ptr(tok), hip.ptr(plen), n_, s_, V, int(p0), int(p1), hip.ptr(seq), hip.ptr(drawn), hip.ptr(mask),
-                                               hip.stream_ptr()), "bofi_rl_take_draws")
-
+    d = rl_draws.draw_pass(model, rl_draws.naic_layout(model, att_feats, att_masks, sample_n), temperature,
+                           lambda layout, first: rows_of(rl_draws.prepared(cfg, layout), shared), draw_base=seed + 0x5EED0000)
+    lp_saic, lp_naic = rows_of(d.prep)                            # the gradient pass: the same rows, with the tape
     with torch.no_grad():
-        r = eng.decode_naic(feats_in, lens_in, strict_q1=model.strict_reference)
-        na = {k: r[k].repeat_interleave(sample_n, dim=0).contiguous() for k in ("phrase_num", "phrase_length", "phrase_syn")}
-        feats_rep = feats_in.repeat_interleave(sample_n, dim=0).contiguous()
-        lens_rep = None if lens_in is None else lens_in.repeat_interleave(sample_n).contiguous()
-        prep_na = xe.rl_prepare_naic_device(cfg, na["phrase_length"], na["phrase_syn"], strict_q1=model.strict_reference)
-        seq_s = torch.zeros(N, S, dtype=torch.int64, device=dev)
-        seq_n = torch.zeros(N, S, dtype=torch.int64, device=dev)
-        drawn_s, drawn_n = torch.zeros(N, S, device=dev), torch.zeros(N, S, device=dev)
-        mask_s = torch.zeros(N, S, dtype=torch.bool, device=dev)
-        mask_n = torch.arange(S, device=dev)[None] < na["phrase_length"].long().sum(1)[:, None]
-        na_plen = na["phrase_length"].to(torch.int32).contiguous()
-        shared: dict = {}                                         # the encoder's memory and the cross K|V: the same tensors in every tape-free forward of this step
-        out, passes = None, 0
-        for it in range(1, S + 1):
-            out = eng.decode_saic(feats_rep, lens_rep, it_range=(it, it), out=out, want_logprob=False, layout_only=True)
-            if int(out["bound_iters"]) < it:                      # no caption was open in this iteration: the loop is through
-                break
-            prep = xe.rl_prepare_saic_device(cfg, seq_s, out["phrase_length"], out["phrase_syn"])
-            prep.update(prep_na)
-            lp_s, lp_n = rows_of(prep, shared)
-            passes += 1
-            draw(lp_s, out["phrase_length"], it - 1, it, seq_s, drawn_s, mask_s)
-            eng.saic_put_words(seq_s)
-            if it == 1:
-                draw(lp_n, na_plen, 0, S, seq_n, drawn_n, None)
-        prep = xe.rl_prepare_saic_device(cfg, seq_s, out["phrase_length"], out["phrase_syn"])
-        prep.update(prep_na)
-    lp_saic, lp_naic = rows_of(prep)                              # the gradient pass: the same rows, with the tape
-    with torch.no_grad():
-        g_s = (lp_saic.detach().float().gather(2, seq_s[..., None]).squeeze(2) - drawn_s)[mask_s]
-        g_n = (lp_naic.detach().float().gather(2, seq_n[..., None]).squeeze(2) - drawn_n)[mask_n]
-        gap = max(float(g_s.abs().max()) if g_s.numel() else 0.0, float(g_n.abs().max()) if g_n.numel() else 0.0)
-    saic = {"seq": seq_s, "phrase_num": out["phrase_num"], "phrase_length": out["phrase_length"], "phrase_syn": out["phrase_syn"]}
-    naic = {"seq": seq_n, "phrase_num": na["phrase_num"], "phrase_length": na["phrase_length"], "phrase_syn": na["phrase_syn"]}
-    return lp_saic, lp_naic, saic, naic, {"reference_gap": gap, "training_forwards": passes + 1}
+        gap = rl_draws.drawn_gap(rl_draws.picked(lp_saic, d.seq_s), rl_draws.picked(lp_naic, d.seq_n), d)
+    saic = {"seq": d.seq_s, "phrase_num": d.out["phrase_num"], "phrase_length": d.out["phrase_length"], "phrase_syn": d.out["phrase_syn"]}
+    return lp_saic, lp_naic, saic, d.naic, {"reference_gap": gap, "training_forwards": d.passes + 1}
 
 
 class LanguageModelCriterion_UIC(torch.nn.Module):

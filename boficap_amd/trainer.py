@@ -380,12 +380,10 @@ class XETrainer:
             # these need the dense [N, S, V] log-probs of the two branches side by side (or, for a bounding network of N_len >= 2 layers,
             # whole-sequence bound passes): the reference's own form of the step, run eagerly
             if self.graph and not self._capturing():
-                self._fwd_calls += 1
-                self._step_word.fill_(self._fwd_calls)
+                self._next_step()
             return self._forward_backward_eager(batch, glat_p, dense="drop_worst" if drop_worst else "plain")
         if self.graph and not self._capturing():
-            self._fwd_calls += 1
-            self._step_word.fill_(self._fwd_calls)             # outside any graph: every step draws new dropout masks
+            self._next_step()                                  # outside any graph: every step draws new dropout masks
             # (scheduled sampling decides on the host between its iterations: it cannot live in a captured graph)
             if batch.get("att_masks") is None and batch.get("max_phrase_num") is not None and not getattr(self.model, "ss_prob", 0.0) > 0:
                 return self._replay(batch, glat_p, between)
@@ -400,6 +398,19 @@ class XETrainer:
     @staticmethod
     def _capturing() -> bool:
         return torch.cuda.is_current_stream_capturing()
+
+    def _next_step(self):
+        """Count a step's forward: its number picks the dropout masks, on the host or -- graph mode -- in the device word the kernels read."""
+        self._fwd_calls += 1
+        step_word = getattr(self, "_step_word", None)
+        if step_word is not None:
+            step_word.fill_(self._fwd_calls)
+
+    def _dropout_seed(self):
+        """(seed, step word) of this step's training forwards: with a device step word the seed stays put and the kernels add the word."""
+        step_word = getattr(self, "_step_word", None)
+        base = int(getattr(self.model.opt, "seed", 0)) << 32
+        return (base if step_word is not None else base + self._fwd_calls), step_word
 
     def _replay(self, batch, glat_p, between=None):
         S = self.model.cfg.seq_length
@@ -807,10 +818,7 @@ class XETrainer:
         b = {"att_feats": att_feats, "seq_saic": saic["seq"].to(dev).long(), "seq_naic": naic["seq"].to(dev).long(),
              "sc_saic": torch.as_tensor(s_saic, dtype=torch.float32).to(dev), "sc_naic": torch.as_tensor(s_naic, dtype=torch.float32).to(dev)}
         b.update(prep)
-        self._fwd_calls += 1
-        step_word = getattr(self, "_step_word", None)
-        if step_word is not None:
-            step_word.fill_(self._fwd_calls)
+        self._next_step()
         if self.ops is not None and model.train_dtype == torch.bfloat16:
             self.ops.refresh_if_stale()
         if self.graph and att_masks is None and not self._capturing():
@@ -827,41 +835,20 @@ class XETrainer:
         engine's dropout-free one.
 
         The masks are counter-based (seed, site, element), so the training forward run twice on the same inputs gives the same rows bit for bit,
-        and a row of phrase i depends only on the layout and the words up to phrase i - 1 (key-prefix masks, row-wise sublayers).  So:
-          * non-autoregressive branch: the engine's bounding loop gives the layout (greedy heads: one per image, no gradient reaches it in the
-            reference either); one tape-free training forward gives the fill rows; the words are drawn from them;
-          * semi-autoregressive branch: the engine's loop runs ONE iteration per call (bofi_engine_set_saic_range): its bounding step lays the next
-            phrase out on the words so far; a tape-free training forward (same seed) gives that phrase's rows; its words are drawn from them and
-            handed back to the engine (bofi_engine_saic_put_words), whose next bounding step reads them -- core_SAIC's own process
-            (TransformerModel.py:1903-1984) with the fill distribution of the training pass;
-          * then the gradient pass: the same forward once more WITH the tape -- its rows at the drawn tokens are the rows they were drawn from
-            (``last_rl["reference_gap"]``, 0) --, new_self_critical on both branches, backward, all-reduce, Adam.
-        What stays different from the reference: the bound heads decide on the engine (no dropout in the bounding steps); they are argmax decisions
-        without gradient.  Cost: one training forward per phrase (no graph replay: the host scorer and the draws sit between the passes)."""
-        from . import xe
+        and a row of phrase i depends only on the layout and the words up to phrase i - 1 (key-prefix masks, row-wise sublayers).  So
+        ``rl_draws.naic_layout`` + ``draw_pass`` (the one draw pass, LossWrapper's too) lay out and draw both branches phrase by phrase from tape-free training forwards
+        under this step's seed -- eager, or the two captured graphs of _rl_forward_graphs --; then the gradient pass: the same forward once more WITH
+        the tape -- its rows at the drawn tokens are the rows they were drawn from (``last_rl["reference_gap"]``, 0) --, new_self_critical on both
+        branches, backward, all-reduce, Adam.  Cost: one training forward per phrase (the host scorer and the draws sit between the passes)."""
+        from . import rl_draws, xe
         model, cfg = self.model, self.model.cfg
         S, dev = cfg.seq_length, att_feats.device
-        eng = model.engine()
-        feats_in, lens_in = model._as_input(att_feats), model._att_len(att_masks)
-        B = feats_in.size(0)
-        N = B * sample_n
-        if N > model.max_batch:
-            raise hip.BofiHipError(f"{N} sampled rows exceed bofi_max_batch={model.max_batch}")
-        with torch.no_grad():
-            r = eng.decode_naic(feats_in, lens_in, strict_q1=model.strict_reference)
-            na = {k: r[k].repeat_interleave(sample_n, dim=0).contiguous() for k in ("phrase_length", "phrase_syn")}
-            na["seq"] = torch.zeros(N, S, dtype=torch.int64, device=dev)
-            feats_rep = feats_in.repeat_interleave(sample_n, dim=0).contiguous()
-            lens_rep = None if lens_in is None else lens_in.repeat_interleave(sample_n).contiguous()
-        self._fwd_calls += 1
-        step_word = getattr(self, "_step_word", None)
-        if step_word is not None:
-            step_word.fill_(self._fwd_calls)
-        base = int(getattr(model.opt, "seed", 0)) << 32
-        seed = base if step_word is not None else base + self._fwd_calls
+        N = att_feats.size(0) * sample_n
+        laid = rl_draws.naic_layout(model, att_feats, att_masks, sample_n)      # (ahead of this step's own first launches: see there)
+        self._next_step()
+        seed, step_word = self._dropout_seed()
         self.bucket.zero_grad()
         P = xe.Params(model)
-
         shared: dict = {}                                       # the encoder's memory and the cross K|V of the tape-free per-phrase forwards (same in each of them)
 
         def rows_of(prep, reuse=None, feats=None):
@@ -870,106 +857,47 @@ class XETrainer:
 
         fwd_graphs = None                                       # (set below, once the step is armed)
 
-        def rows_graphed(seq, out, prep_na, first):
+        def rows_graphed(layout, first):
             # (the graphs read the words so far and the engine's layout from static buffers and collate them on the device: no host round trip per phrase)
             g_a, g_b, st_in, st_feats, out_a, out_b = fwd_graphs
             if first:
                 st_feats.copy_(att_feats)
-                st_in["na_syn"].copy_(prep_na["na_syn"]); st_in["na_klen"].copy_(prep_na["na_klen"])
-            torch._foreach_copy_([st_in["seq"], st_in["pl"], st_in["psyn"]], [seq, out["phrase_length"], out["phrase_syn"]], non_blocking=True)
+                st_in["na_syn"].copy_(layout["na_syn"]); st_in["na_klen"].copy_(layout["na_klen"])
+            torch._foreach_copy_([st_in["seq"], st_in["pl"], st_in["psyn"]], [layout["seq"], layout["phrase_length"], layout["phrase_syn"]], non_blocking=True)
             (g_a if first else g_b).replay()
             return out_a if first else out_b
 
-        draws = [0]
-
-        def draw(lp, plen, p0, p1, seq, drawn, mask):
-            # one draw per slot from Categorical(logits = row / temperature) by the library's one-pass Gumbel-max sampler (bofi_vocab_sample: counter-hash uniforms, a NaN
-            # log-prob counts as -10 as in CaptionModel.py:419-425), kept at the positions of phrases [p0, p1) (bofi_rl_take_draws: ids, their log-probs under the rows they
-            # were drawn from, the sampled mask): no index list, no host synchronisation, two launches per phrase
-            lpf = lp if lp.dtype == torch.float32 and lp.is_contiguous() else lp.float().contiguous()
-            n_, s_, V = lpf.shape
-            tok = torch.empty(n_, s_, dtype=torch.int64, device=dev)
-            draws[0] += 1
-            sseed = (base + 0x5EED0000 + (self._fwd_calls << 8) + draws[0]) & 0xFFFFFFFFFFFFFFFF
-            hip.check(hip.lib().bofi_vocab_sample(hip.ptr(lpf), n_ * s_, V, s_, 1, float(temperature), sseed, None, cfg.pad_idx, hip.ptr(tok), hip.stream_ptr()),
-                      "bofi_vocab_sample")
-            hip.check(hip.lib().bofi_rl_take_draws(hip.ptr(lpf), hip.ptr(tok), hip.ptr(plen), n_, s_, V, int(p0), int(p1), hip.ptr(seq), hip.ptr(drawn), hip.ptr(mask),
-                                                   hip.stream_ptr()), "bofi_rl_take_draws")
-
         with self._armed(dw_aside=False):                         # (from the first tape-free forward to the gradient pass's weight gradients)
-            pos = torch.arange(S, device=dev)[None]
             # The tape-free per-phrase forwards as TWO captured graphs per input signature (graph-mode trainers: the dropout step lives in a device word, so a replay
             # draws this step's masks): A = encoder + decoder (the step's first forward: fills the memory / cross K|V the others share), B = decoder only.  ~250
             # launches per forward become one replay: 1.6 -> ~0.7 ms each, twelve to fourteen times per step.
             if self.graph and att_masks is None and step_word is not None and not self._capturing() and getattr(model.opt, "bofi_rl_graph_forwards", True):
                 fwd_graphs = self._rl_forward_graphs(rows_of, att_feats, N, S, dev, sample_n)
-            prep_na = xe.rl_prepare_naic_device(cfg, na["phrase_length"], na["phrase_syn"], strict_q1=model.strict_reference)
-            seq_s = torch.zeros(N, S, dtype=torch.int64, device=dev)
-            seq_n = torch.zeros(N, S, dtype=torch.int64, device=dev)
-            drawn_s = torch.zeros(N, S, device=dev)
-            drawn_n = torch.zeros(N, S, device=dev)
-            mask_s = torch.zeros(N, S, dtype=torch.bool, device=dev)
-            mask_n = pos < na["phrase_length"].long().sum(1)[:, None]
-            na_plen = na["phrase_length"].to(torch.int32).contiguous()
-            out = None
-            self._sample_calls_ref = getattr(self, "_sample_calls_ref", 0) + 1
-            passes = 0
-            for it in range(1, S + 1):
-                with torch.no_grad():
-                    # (the engine lays the next phrase out on the words so far and stops: this step draws the words itself, from the training forward's rows)
-                    out = eng.decode_saic(feats_rep, lens_rep, it_range=(it, it), out=out, want_logprob=False, layout_only=True)
-                    if int(out["bound_iters"]) < it:                     # no caption was open in this iteration: the loop is through
-                        break
-                    if fwd_graphs is not None:
-                        lp_s, lp_n = rows_graphed(seq_s, out, prep_na, passes == 0)
-                    else:
-                        prep = xe.rl_prepare_saic_device(cfg, seq_s, out["phrase_length"], out["phrase_syn"])
-                        prep.update(prep_na)
-                        lp_s, lp_n = rows_of(prep, shared)
-                    passes += 1
-                    draw(lp_s, out["phrase_length"], it - 1, it, seq_s, drawn_s, mask_s)       # phrase `it`'s positions
-                    eng.saic_put_words(seq_s)
-                    if it == 1:
-                        draw(lp_n, na_plen, 0, S, seq_n, drawn_n, None)                    # every laid-out position of the non-autoregressive branch
-            saic = {"seq": seq_s, "phrase_length": out["phrase_length"], "phrase_syn": out["phrase_syn"]}
+            rows = rows_graphed if fwd_graphs is not None else lambda layout, first: rows_of(rl_draws.prepared(cfg, layout), shared)
+            d = rl_draws.draw_pass(model, laid, temperature, rows,
+                                   draw_base=(int(getattr(model.opt, "seed", 0)) << 32) + 0x5EED0000 + (self._fwd_calls << 8))
+            seq_s, seq_n = d.seq_s, d.seq_n
             if getattr(score_fn, "on_device", False):                    # a device scorer (boficap_amd.cider): the ids stay where they were drawn
                 s_saic, s_naic = score_fn(seq_s), score_fn(seq_n)
             else:
                 s_saic, s_naic = score_fn(seq_s.cpu()), score_fn(seq_n.cpu())
-            prep = xe.rl_prepare_saic_device(cfg, seq_s, out["phrase_length"], out["phrase_syn"])
-            prep.update(prep_na)
-            sc_s = torch.as_tensor(s_saic, dtype=torch.float32).to(dev)
-            sc_n = torch.as_tensor(s_naic, dtype=torch.float32).to(dev)
-            replayed = self.graph and att_masks is None and not self._capturing()
-            if not replayed:
-                lp_saic, lp_naic = rows_of(prep)                          # the gradient pass: the same rows, with the tape
-                with torch.no_grad():
-                    g_s = (lp_saic.detach().float().gather(2, seq_s[..., None]).squeeze(2) - drawn_s)[mask_s]
-                    g_n = (lp_naic.detach().float().gather(2, seq_n[..., None]).squeeze(2) - drawn_n)[mask_n]
-                    gap = max(float(g_s.abs().max()) if g_s.numel() else 0.0, float(g_n.abs().max()) if g_n.numel() else 0.0)
-                l1, r1 = xe.new_self_critical(lp_saic, seq_s, sc_s, sample_n)
-                l2, r2 = xe.new_self_critical(lp_naic, seq_n, sc_n, sample_n)
-                loss = l1 + l2
-                if self.rl_kl:
-                    loss = loss + xe.rl_kl_term(lp_naic, lp_saic, seq_s)
-                loss.backward()
-                xe.flush_weight_grads()
-                loss, m1, m2 = loss.detach(), r1.mean(), r2.mean()
-        if replayed:
-            # the gradient pass as the captured graph of the fast form (the same forward under the same seed and dropout masks + new_self_critical + backward):
-            # its log-probs at the drawn tokens come back in the graph's "picked" buffers
-            b = {"att_feats": att_feats, "seq_saic": seq_s, "seq_naic": seq_n, "sc_saic": sc_s, "sc_naic": sc_n,
+            # the gradient pass reads tensors only; its log-probs at the drawn tokens come back in the "picked" buffers
+            b = {"att_feats": att_feats, "seq_saic": seq_s, "seq_naic": seq_n,
+                 "sc_saic": torch.as_tensor(s_saic, dtype=torch.float32).to(dev), "sc_naic": torch.as_tensor(s_naic, dtype=torch.float32).to(dev),
                  "picked_saic": torch.zeros(N, S, device=dev), "picked_naic": torch.zeros(N, S, device=dev)}
-            b.update(prep)
-            loss, m1, m2 = self._rl_replay(b, sample_n)
-            st = self._rl_static
-            with torch.no_grad():
-                g_s, g_n = (st["picked_saic"] - drawn_s)[mask_s], (st["picked_naic"] - drawn_n)[mask_n]
-                gap = max(float(g_s.abs().max()) if g_s.numel() else 0.0, float(g_n.abs().max()) if g_n.numel() else 0.0)
+            b.update(d.prep)
+            replayed = self.graph and att_masks is None and not self._capturing()
+            if not replayed:                                             # the same rows, with the tape, inside this scope
+                (loss, m1, m2), st = self._rl_gradient_pass(b, att_masks, sample_n), b
+        if replayed:
+            # ... as the captured graph of the fast form (the same forward under the same seed and dropout masks + new_self_critical + backward)
+            (loss, m1, m2), st = self._rl_replay(b, sample_n), self._rl_static
+        with torch.no_grad():
+            gap = rl_draws.drawn_gap(st["picked_saic"], st["picked_naic"], d)
         self._last_rl = {"saic_tokens": (seq_s > 0).float().sum(1).mean(), "naic_tokens": (seq_n > 0).float().sum(1).mean(),
-                         "active_share": min(S, int(out["phrase_num"].max()) + 1) / S, "reference_gap": gap, "training_forwards": passes + 1,
+                         "active_share": min(S, int(d.out["phrase_num"].max()) + 1) / S, "reference_gap": gap, "training_forwards": d.passes + 1,
                          "gradient_pass_replayed": bool(replayed),
-                         "seq_saic": seq_s, "seq_naic": seq_n, "phrase_length_saic": out["phrase_length"], "phrase_syn_saic": out["phrase_syn"]}
+                         "seq_saic": seq_s, "seq_naic": seq_n, "phrase_length_saic": d.out["phrase_length"], "phrase_syn_saic": d.out["phrase_syn"]}
         self.reduce_and_step()
         return loss, m1, m2
 
@@ -1014,27 +942,28 @@ class XETrainer:
     def _rl_forward_backward(self, b, att_masks, sample_n):
         """zero-grad, differentiable re-forward of the sampled captions, new_self_critical for both modes, backward (tensors in,
         device scalars out: what a captured self-critical step replays)."""
-        from . import xe
-        model = self.model
         self.bucket.zero_grad()
-        step_word = getattr(self, "_step_word", None)
-        base = int(getattr(model.opt, "seed", 0)) << 32
         with self._armed(dw_aside=False):
-            lp_saic, lp_naic = xe.sampled_logprobs_prepared(xe.Params(model), model.cfg, b["att_feats"], att_masks, b, sample_n=sample_n,
-                                                            training=model.training,
-                                                            seed=base if step_word is not None else base + self._fwd_calls,
-                                                            compute_dtype=model.train_dtype, step_word=step_word)
-            if "picked_saic" in b:                             # (the reference-estimator step checks the drawn rows against these: the gradient pass's own log-probs at the drawn tokens)
-                with torch.no_grad():
-                    b["picked_saic"].copy_(lp_saic.detach().float().gather(2, b["seq_saic"][..., None]).squeeze(2))
-                    b["picked_naic"].copy_(lp_naic.detach().float().gather(2, b["seq_naic"][..., None]).squeeze(2))
-            l1, r1 = xe.new_self_critical(lp_saic, b["seq_saic"], b["sc_saic"], sample_n)
-            l2, r2 = xe.new_self_critical(lp_naic, b["seq_naic"], b["sc_naic"], sample_n)
-            loss = l1 + l2
-            if self.rl_kl:
-                loss = loss + xe.rl_kl_term(lp_naic, lp_saic, b["seq_saic"])
-            loss.backward()
-            xe.flush_weight_grads()
+            return self._rl_gradient_pass(b, att_masks, sample_n)
+
+    def _rl_gradient_pass(self, b, att_masks, sample_n):
+        """The body of _rl_forward_backward, for a caller that has zeroed the gradients and holds the _armed scope."""
+        from . import rl_draws, xe
+        model = self.model
+        seed, step_word = self._dropout_seed()
+        lp_saic, lp_naic = xe.sampled_logprobs_prepared(xe.Params(model), model.cfg, b["att_feats"], att_masks, b, sample_n=sample_n,
+                                                        training=model.training, seed=seed, compute_dtype=model.train_dtype, step_word=step_word)
+        if "picked_saic" in b:                                 # (the reference-estimator step checks the drawn rows against these: the gradient pass's own log-probs at the drawn tokens)
+            with torch.no_grad():
+                b["picked_saic"].copy_(rl_draws.picked(lp_saic, b["seq_saic"]))
+                b["picked_naic"].copy_(rl_draws.picked(lp_naic, b["seq_naic"]))
+        l1, r1 = xe.new_self_critical(lp_saic, b["seq_saic"], b["sc_saic"], sample_n)
+        l2, r2 = xe.new_self_critical(lp_naic, b["seq_naic"], b["sc_naic"], sample_n)
+        loss = l1 + l2
+        if self.rl_kl:
+            loss = loss + xe.rl_kl_term(lp_naic, lp_saic, b["seq_saic"])
+        loss.backward()
+        xe.flush_weight_grads()
         return loss.detach(), r1.mean(), r2.mean()
 
     def _rl_replay(self, b, sample_n):

@@ -7,8 +7,9 @@
 
 ``run`` (one process per tree; needs the GPU): TINY weights from a seed, fixed synthetic batches, model.train() under a fixed opt.seed -- the
 dropout masks are counter-based by (seed, site, element), so a changed launch order changes the loss.  Per case a few forward + backward
-calls on unchanged weights (XE: forward_backward; self-critical: rl_step at learning rate 0), the losses and loss parts of every call as hex
-floats (cases.json) and the gradient bucket after the last call (<case>.pt).  ``compare``: losses must be bit-equal; gradients go through
+calls on unchanged weights (XE: forward_backward; self-critical: rl_step at learning rate 0, and LossWrapper's struc_flag branch + backward),
+the losses and loss parts of every call as hex floats -- for the reference-estimator forms also a sha256 of the call's drawn ids and layouts, compared
+like a loss -- (cases.json) and the gradient bucket (LossWrapper: the parameters' gradients) after the last call (<case>.pt).  ``compare``: losses must be bit-equal; gradients go through
 float atomics, so the parent against itself gives the noise (max and mean |dgrad| per case) and the branch against the parent may show at
 most twice that.  Exit status 1 if a case misses either."""
 import argparse
@@ -40,7 +41,21 @@ def cases():
     for ref in (True, False):
         for dt, graph in (("f32", False), ("bf16", False), ("bf16", True)):
             out.append((f"rl {'reference' if ref else 'fast'}-estimator {dt} {'graph' if graph else 'eager'}", dict(rl=ref, dtype=dt, graph=graph)))
+    out.append(("rl reference-estimator f32 eager ragged", dict(rl=True, dtype="f32", graph=False, ragged=True)))
+    for dt in ("f32", "bf16"):                                 # LossWrapper's struc_flag branch in train mode: the same draw pass without a trainer
+        out.append((f"lw rl reference {dt}", dict(lw=True, dtype=dt, graph=False, opt=dict(
+            structure_loss_type="new_self_critical", train_sample_n=3, structure_loss_weight=1, train_sample_method="sample", train_beam_size=1))))
     return out
+
+
+def _digest(*tensors):
+    """sha256 over the tensors' bytes (drawn ids, slot layouts): equal hashes = the same draws."""
+    import hashlib
+    import torch
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(t.detach().to(torch.int64).cpu().contiguous().numpy().tobytes())
+    return h.hexdigest()
 
 
 def run(tree, out_dir):
@@ -58,7 +73,7 @@ def run(tree, out_dir):
     for name, c in cases():
         cfg = TINY_N2 if c.get("n_len") == 2 else TINY
         sd = W.make_state_dict(cfg, seed=0)
-        if "rl" in c or c.get("ss_prob"):
+        if "rl" in c or "lw" in c or c.get("ss_prob"):
             sd = W.with_len_row_shared(sd, cfg)                # (the semi-autoregressive mode lays out several phrases with these)
         opt = cfg.to_opt()
         opt.seed, opt.noamopt, opt.learning_rate = 7, False, 0.0
@@ -72,15 +87,39 @@ def run(tree, out_dir):
         # (scheduled sampling: a caption whose first sampled slot is empty is left without keys and raises -- images and a batch that have none)
         spi, bseed, aseed = (2, 3, 4) if c.get("ss_prob") else (3, 12, 3)
         att = torch.from_numpy(W.synthetic_att_feats(n_img, 36, cfg.att_feat_size, seed=aseed)).cuda()
-        losses = []
-        if "rl" in c:
+        losses, tr = [], None
+        if "rl" in c or "lw" in c:
             # (the images of the fixture these weights lay several phrases out on: an image whose samples are all empty gives a NaN loss)
             att = torch.from_numpy(np.load(os.path.join(ROOT, "tests", "golden", "tiny_saic_multi.npz"))["att_feats"]).cuda()
+            masks = None
+            if c.get("ragged"):
+                masks = torch.ones(att.shape[:2], device="cuda"); masks[0, 20:] = 0
+        if "lw" in c:
+            from boficap_amd.loss_wrapper import LossWrapper
+            seen = []                                          # what the scorer hook is handed: the drawn ids of the two branches
+
+            def scorer(gts, seq):
+                seen.append(seq)
+                return (seq % 7 == 0).float().mean(1)
+            model.opt.bofi_score_fn = scorer
+            lw = LossWrapper(model, model.opt)
+            fc, gts = torch.zeros(att.size(0), 0, device="cuda"), [[np.zeros(3, np.int64)] for _ in range(att.size(0))]
+            for _ in range(calls):
+                model.zero_grad()
+                del seen[:]
+                out = lw(fc, att, None, None, masks, gts, torch.arange(att.size(0)), False, True, False)
+                out["loss"].backward()
+                losses.append([float(out["loss"]).hex()] + [float(x).hex() for x in out["reward"].flatten()] + [_digest(*seen)])
+            grad = torch.cat([(torch.zeros_like(p) if p.grad is None else p.grad).detach().flatten().cpu() for p in model.parameters()])
+        elif "rl" in c:
             model.opt.bofi_rl_reference_estimator = c["rl"]
             tr = XETrainer(model, opt, graph=c["graph"])
             for _ in range(calls):
-                r = tr.rl_step(att, None, lambda seq: (seq % 7 == 0).float().mean(1), sample_n=3, temperature=1.0)
+                r = tr.rl_step(att, masks, lambda seq: (seq % 7 == 0).float().mean(1), sample_n=3, temperature=1.0)
                 losses.append([float(x).hex() for x in r])
+                if c["rl"]:                                    # the draws themselves: ids of both branches and the semi-autoregressive layout
+                    last = tr._last_rl
+                    losses[-1].append(_digest(last["seq_saic"], last["seq_naic"], last["phrase_length_saic"], last["phrase_syn_saic"]))
         else:
             form = c["form"]
             tr = XETrainer(model, opt, graph=c["graph"], unpadded=form != "compact", paired=form == "paired", streams=bool(c.get("streams")))
@@ -101,7 +140,9 @@ def run(tree, out_dir):
                 losses.append([float(x).hex() for x in [loss] + list(parts)])
             xe.HINTS.pop("glat_uniform", None)
         torch.cuda.synchronize()                               # (a case that raises ends the run: every case runs on the parent)
-        torch.save(tr.bucket.grad.detach().cpu(), os.path.join(out_dir, name.replace(" ", "_") + ".pt"))
+        if tr is not None:
+            grad = tr.bucket.grad.detach().cpu()
+        torch.save(grad, os.path.join(out_dir, name.replace(" ", "_") + ".pt"))
         record[name] = losses
         print(f"{name}: {losses[-1][0]}", flush=True)
         del tr, model

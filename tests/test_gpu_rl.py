@@ -437,6 +437,48 @@ def test_reference_estimator_cold_and_without_dropout_is_the_greedy_decode(weigh
     assert last["reference_gap"] == 0.0
 
 
+def test_draw_pass_is_one_reproducible_process_for_both_callers(weight_cache, manifest):
+    """rl_draws.draw_pass (the reference-estimator step's draws, shared by XETrainer._rl_reference_step and loss_wrapper.reference_estimator_pass) with eager
+    tape-free training forwards as its rows: the same dropout seed and draw_base give the same ids, layouts and drawn log-probs; several phrases are laid out
+    (more than one forward); a tape forward on the result has the drawn rows (gap exactly 0.0); another draw_base draws other words; and
+    reference_estimator_pass is that pass under draw_base = seed + 0x5EED0000."""
+    from boficap_amd import rl_draws, xe
+    from boficap_amd.loss_wrapper import reference_estimator_pass
+    cfg, sd, model = _model(weight_cache, manifest)
+    model.train()
+    assert cfg.dropout > 0
+    att = _images().cuda()
+    n, seed = 2, (7 << 32) + 1
+    P = xe.Params(model)
+
+    def forward(prep, reuse=None):
+        return xe.sampled_logprobs_prepared(P, cfg, att, None, prep, sample_n=n, training=True, seed=seed, compute_dtype=model.train_dtype, reuse=reuse)
+
+    def run(draw_base):
+        shared = {}
+        d = rl_draws.draw_pass(model, rl_draws.naic_layout(model, att, None, n), 1.0, lambda layout, first: forward(rl_draws.prepared(cfg, layout), shared),
+                               draw_base=draw_base)
+        layouts = [v[k].clone() for v in (d.out, d.naic) for k in ("phrase_num", "phrase_length", "phrase_syn")]      # (the engine may hand its own buffers out)
+        return d, layouts
+
+    a, a_layouts = run(seed + 0x5EED0000)
+    b, b_layouts = run(seed + 0x5EED0000)
+    for k in ("seq_s", "seq_n", "drawn_s", "drawn_n", "mask_s", "mask_n"):
+        assert torch.equal(getattr(a, k), getattr(b, k)), k
+    assert all(torch.equal(x, y) for x, y in zip(a_layouts, b_layouts))
+    assert a.passes >= 2 and a.passes == b.passes
+    assert int(a.mask_s.sum()) > att.size(0) and int(a.mask_n.sum()) > 0
+    lp_s, lp_n = forward(a.prep)                                                # the gradient pass's forward: with the tape
+    assert lp_s.requires_grad and lp_n.requires_grad
+    with torch.no_grad():
+        assert rl_draws.drawn_gap(rl_draws.picked(lp_s, a.seq_s), rl_draws.picked(lp_n, a.seq_n), a) == 0.0
+    c, _ = run(seed + 0x5EED0000 + 1000)
+    assert not torch.equal(c.seq_s, a.seq_s)
+    _, _, saic, naic, info = reference_estimator_pass(model, att, None, n, 1.0, seed)
+    assert torch.equal(saic["seq"], a.seq_s) and torch.equal(naic["seq"], a.seq_n)
+    assert torch.equal(naic["phrase_num"], a_layouts[3]) and info["reference_gap"] == 0.0 and info["training_forwards"] == a.passes + 1
+
+
 def test_device_side_layout_collate_equals_the_host_collate():
     """xe.rl_prepare_saic_device (tensor operations on the device, usable inside a captured graph) against xe.rl_prepare (the host collate through
     boficap_amd.collate.phrase_collate, itself pinned to the reference's collate_func): random layouts with squeezes, stretches, empty captions."""
