@@ -105,16 +105,10 @@ struct bofi_engine {
     // (label, position) only: f_qkv0[(label*S + t)][3d] in the compute dtype, made by the SAME row-block projection kernel a decode would run on those rows (a row's
     // result does not depend on the launch), gathered by embed_fill instead of a 10-GFLOP projection per 320 images.  Rebuilt by every repack.
     void* f_qkv0 = nullptr; float* f_x0 = nullptr; int* f_syn = nullptr; bool fill_tab_ready = false;
-    // per-call (bofi_engine_set_row_stats_out; part of the graph key): where the filling pass's epilogue leaves, per position, sum_v p log p and the log-prob of the
-    // emitted id -- eval's entropy / perplexity (eval_utils.py:463-464) without a second pass over the log-probs
-    float *row_plogp_out = nullptr, *row_chosen_out = nullptr;
-    // per-call (bofi_engine_set_refine_out; part of the graph key): where a decode under BOFI_FLAG_MASK_PREDICT leaves the pass that emitted each position's token
-    int* refine_round_out = nullptr;
-    // per-call (bofi_engine_set_attn_out; part of the graph key): where the filling pass leaves decoder layer attn_layer's (-1: the last) cross-attention maps (attn_maps.hip)
-    float *attn_mean_out = nullptr, *attn_heads_out = nullptr, *attn_top_w_out = nullptr;
-    int* attn_top_idx_out = nullptr;
-    int attn_layer = -1, attn_topk = 0;
-    bool attn_out_set() const { return attn_mean_out || attn_heads_out || attn_top_idx_out; }
+    // the options of the entry-point call that is running (bofi_call_opts_t states each field): every entry point overwrites them -- with the caller's record, or
+    // with the defaults -- before it enqueues anything, so nothing of one call reaches the next; key_call() puts them into the graph key
+    bofi_call_opts_t opt{};
+    bool attn_out_set() const { return opt.attn_mean || opt.attn_heads || opt.attn_top_idx; }
     bool loop_ready = false;
     float* dbg_part = nullptr;
 
@@ -150,17 +144,14 @@ struct bofi_engine {
     void* b_q0_sa = nullptr; float* b_x0_sa = nullptr;                  // row-0 constants when position 0 holds tgt_embed([LEN])
 
     hipStream_t cap_stream = nullptr;
-    int q1_group = 0;                     // > 0: the call carries several independent batches of this many images (quirk Q1 per batch)
-    float sample_temperature = 1.0f;      // BOFI_FLAG_SAMPLE: token draws inside the semi-autoregressive loop
-    uint64_t sample_seed = 0;
     int saic_B = 0;                       // images of the last semi-autoregressive decode (what bofi_engine_saic_put_words may continue)
-    int saic_it_begin = 1, saic_it_end = 0;   // iterations the next semi-autoregressive decode enqueues (bofi_engine_set_saic_range; end 0 = seq_length)
-    int bound_iter_cap = 0;               // bounding iterations the non-autoregressive decode enqueues (bofi_engine_set_bound_iter_cap; 0 = seq_length)
-    int in_flight = 0;                    // decodes the caller keeps in flight (bofi_engine_set_decodes_in_flight; 0 = unknown: throughput forms)
-    int* live_max = nullptr;              // optional device word: max over decodes of their live-iteration counts (bofi_engine_set_live_iterations_max)
-    int* sat_out = nullptr;               // optional device word: fp16 saturation status of the following NAIC decodes' bounding loop (bofi_engine_set_saturation_out)
-    int loop_mode = -1;                   // bofi_engine_set_bound_loop: -1 = BOFI_BOUND_LOOP / hint decide, 0 = five-launch iterations, 2 = the persistent loop kernel
-    int kv_beside = 1;                    // bofi_engine_set_bound_kv_beside: 0 = never, 1 = the decoder layers' cross K|V are projected beside the bounding loop where bound_kv_beside_ok says so
+    // what describes the engine, not one call (their setters; part of the graph key).  A fork inherits kv_beside -- a form switch for A/B runs -- and starts from the defaults otherwise
+    struct Settings {
+        int in_flight = 0;                // decodes the caller keeps in flight (bofi_engine_set_decodes_in_flight; 0 = unknown: throughput forms)
+        int loop_mode = -1;               // bofi_engine_set_bound_loop: -1 = BOFI_BOUND_LOOP / hint decide, 0 = five-launch iterations, 2 = the persistent loop kernel
+        int kv_beside = 1;                // bofi_engine_set_bound_kv_beside: 0 = never, 1 = the decoder layers' cross K|V are projected beside the bounding loop where bound_kv_beside_ok says so
+        Settings forked() const { Settings s; s.kv_beside = kv_beside; return s; }
+    } settings;
     float* bl_xbuf = nullptr; unsigned* bl_xctl = nullptr;      // the loop kernel's pair exchange: partial sums and control words (workspace: one set per engine / fork)
     int* b_wsat = nullptr;                // [1] set by pack_frag16 when an fp16 weight copy was clamped (shared with forks, like the weights)
     hipStream_t run_stream = nullptr;     // a stream of the engine's own, offered to callers that keep several decodes in flight
@@ -527,8 +518,8 @@ struct bofi_engine {
     // 2 = the loop kernel whatever the hint
     static int bound_loop_knob() { return bofi::knob(BOFI_BOUND_LOOP); }
     bool bound_loop_ok(int R) const {
-        const int k = loop_mode >= 0 ? loop_mode : bound_loop_knob();
-        return loop_ready && loop_config_ok() && R <= 128 && k != 0 && (k == 2 || in_flight != 1);
+        const int k = settings.loop_mode >= 0 ? settings.loop_mode : bound_loop_knob();
+        return loop_ready && loop_config_ok() && R <= 128 && k != 0 && (k == 2 || settings.in_flight != 1);
     }
     // update != 0: the whole loop on the engine's slot state (after launch_bound_init); update == 0: one iteration on a given layout, log-probabilities out
     // kv_beside: the launch also projects the columns behind the bounding layers' of kv_all (the decoder layers' cross K|V) from the encoder's output, in extra workgroups
@@ -538,7 +529,7 @@ struct bofi_engine {
         if (kv_beside_now) {
             bofi::RbGemmArgs& p = a.kv_pj;
             p.x = x_enc.x; p.ldx = cfg.d_model; p.wp = (const bofi::u32x4*)kv_all.wp; p.c = kv_all.b; p.cs = kv_all.cs; p.y = kv; p.ldy = kv_all.N; p.M = B * R; p.N = kv_all.Npad;
-            a.kv_col0 = n_len * 2 * cfg.d_model; a.kv_in_flight = in_flight;
+            a.kv_col0 = n_len * 2 * cfg.d_model; a.kv_in_flight = settings.in_flight;
         }
         a.wo_self = (const bofi::bl_u32x4*)b_o_self.wp16; a.x0b = b_x0b;
         a.wq_src = (const bofi::bl_u32x4*)b_q_src.wp16; a.cq = b_q_src.b;
@@ -567,7 +558,7 @@ struct bofi_engine {
     // decodes-in-flight hint also sizes the projection's share of the chip), <= 36 regions, the whole decode in one call (a phased call's ENCODE promises the whole stacked
     // K|V), the row-block encoder with the projection tail.  Else today's chain, unchanged.
     bool bound_kv_beside_ok(int B, int R, int phases) const {
-        if (!kv_beside || phases || enc.empty() || in_flight == 1 || R > 36 || !bound_loop_ok(R) || exp_skip("loop") || exp_skip("encoder")) return false;
+        if (!settings.kv_beside || phases || enc.empty() || settings.in_flight == 1 || R > 36 || !bound_loop_ok(R) || exp_skip("loop") || exp_skip("encoder")) return false;
         // (the pair as the library's own choice: BOFI_BL_PAIR = 2 forces pairs at any size for the tests of the pair itself -- they compare its bits with one workgroup per
         // group's -- and moves nothing else in the chain)
         if (bofi::knob(BOFI_BL_PAIR) != 1 || !bofi::bound_loop_pairs(B, cfg.d_ff, 1, bl_xbuf && bl_xctl)) return false;
@@ -648,7 +639,7 @@ struct bofi_engine {
     bool attn_proj_ok(const bofi::AttnArgs& at, const Lin& o, const Lin& pj) const {
         const int v = bofi::knob(BOFI_RB_ATTN_PROJ);
         const int M = at.B * at.Lq;
-        return v && (v == 2 || in_flight != 1) && bofi::knob(BOFI_RB_ATTN) != 0 && bofi::knob(BOFI_RB_ATTN_W) == 0 && rb_ok() && o.wp && fold_rb_ok(pj, M) &&
+        return v && (v == 2 || settings.in_flight != 1) && bofi::knob(BOFI_RB_ATTN) != 0 && bofi::knob(BOFI_RB_ATTN_W) == 0 && rb_ok() && o.wp && fold_rb_ok(pj, M) &&
                pj.Npad == 512 && !at.skip_if_ge && at.kdiv <= 1 && !at.q_start && !at.drop_thresh && !at.klen_sq && at.Lq <= bofi::RB_ATTN_PJ_MAX_LQ && at.Lk <= bofi::RB_ATTN_PJ_MAX_LK && M >= rb_min_rows() &&
                !exp_skip("attn") && !exp_skip("qkv");
     }
@@ -661,7 +652,7 @@ struct bofi_engine {
         a.B = at.B; a.Lq = at.Lq; a.Lk = at.Lk; a.klen = at.klen; a.klen_sb = at.klen_sb; a.klen_sq = at.klen_sq; a.klen_bias = at.klen_bias;
         a.klen_shared_last = at.klen_shared_last; a.wop = (const bofi::u32x4*)o.wp; a.bo = o.b; a.x = t.x; a.ldx = cfg.d_model; a.y = t.x; a.ldy = cfg.d_model;
         a.yb = want_copy ? (uint16_t*)t.xb : nullptr; a.stats_out = want_copy ? t.st : nullptr;
-        a.alone = in_flight == 1;
+        a.alone = settings.in_flight == 1;
         if (pj) { a.pj_wp = (const bofi::u32x4*)pj->wp; a.pj_c = pj->b; a.pj_cs = pj->cs; a.pj_y = (uint16_t*)pj_y; a.pj_ldy = pj_ldy; a.yb = nullptr; a.stats_out = nullptr; }
         return bofi::launch_rb_attn(a, s);
     }
@@ -676,7 +667,7 @@ struct bofi_engine {
         if (exp_skip(y_f32 ? "gen" : l.Npad <= 1536 ? "qkv" : "kv")) return BOFI_OK;
         bofi::RbGemmArgs a{};
         a.x = x32; a.ldx = cfg.d_model; a.wp = (const bofi::u32x4*)l.wp; a.c = l.b; a.cs = l.cs; a.y = y; a.ldy = ldy; a.y_f32 = y_f32; a.M = M; a.N = l.Npad; a.relu = 0;
-        a.alone = in_flight == 1;
+        a.alone = settings.in_flight == 1;
         return bofi::launch_rb_gemm(a, s);
     }
     // the generator as the row-block kernel over the padded weight (what enqueue_fill runs from BOFI_RB_MIN_ROWS rows on)
@@ -693,7 +684,7 @@ struct bofi_engine {
         // (a decode running alone keeps the separate launches of 64-row blocks: measured 0.515 against 0.523 ms per batch with the narrow projections fused,
         // 0.536 with all of them)
         const int maxn = bofi::knob(BOFI_RB_FFN_PROJ_MAXN);          // developer knob: projections wider than this stay launches of their own (0: no limit)
-        return v && (v == 2 || in_flight != 1) && ffn_sublayer_ok(w1, w2, M) && fold_rb_ok(pj, M) && pj.Npad >= 512 && (!maxn || pj.Npad <= maxn) && !exp_skip("ffn") &&
+        return v && (v == 2 || settings.in_flight != 1) && ffn_sublayer_ok(w1, w2, M) && fold_rb_ok(pj, M) && pj.Npad >= 512 && (!maxn || pj.Npad <= maxn) && !exp_skip("ffn") &&
                !exp_skip("qkv") && !exp_skip("kv");
     }
     // The attention sublayer SPLIT (round 6): the attention core as the light kernel of attn_bf16.hip (context rows to memory as bf16: no W_o stream, no
@@ -713,7 +704,7 @@ struct bofi_engine {
         const int v = bofi::knob(BOFI_RB_ATTN_SPLIT);
         const int M = at.B * at.Lq;
         const bool beyond = (at.Lq > bofi::RB_ATTN_MAX_LQ || at.Lk > bofi::RB_ATTN_MAX_LK) && M >= rb_min_rows();
-        return v && (v == 2 || beyond || (in_flight != 1 && at.B >= bofi::knob(BOFI_RB_ATTN_SPLIT_MIN_B))) && bofi::knob(BOFI_RB_ATTN) != 0 && rb_ok() && o.wp &&
+        return v && (v == 2 || beyond || (settings.in_flight != 1 && at.B >= bofi::knob(BOFI_RB_ATTN_SPLIT_MIN_B))) && bofi::knob(BOFI_RB_ATTN) != 0 && rb_ok() && o.wp &&
                ffn_sublayer_ok(w1, w2, M) && !at.skip_if_ge && at.kdiv <= 1 &&
                !at.q_start && !at.drop_thresh && at.Lq <= 128 && at.Lk <= 128 && !exp_skip("attn") && !exp_skip("ffn");
     }
@@ -726,7 +717,7 @@ struct bofi_engine {
         if (pj) { a.pj_wp = (const bofi::u32x4*)pj->wp; a.pj_c = pj->b; a.pj_cs = pj->cs; a.pj_y = pj_y; a.pj_ldy = pj_ldy; a.pj_N = pj->Npad; }
         a.x = x; a.ldx = cfg.d_model; a.w1p = (const bofi::u32x4*)w1.wp; a.c1 = w1.b; a.cs1 = w1.cs; a.w2p = (const bofi::u32x4*)w2.wp; a.b2 = w2.b;
         a.y = x; a.ldy = cfg.d_model; a.yb = (uint16_t*)xb; a.stats_out = stats; a.M = M; a.dff = cfg.d_ff;
-        a.alone = in_flight == 1;
+        a.alone = settings.in_flight == 1;
         return bofi::launch_rb_ffn(a, s);
     }
     // ---- one function per sublayer kind on ALL M rows of stream t: the row-block kernel when the shape is its, else the tiled launches
@@ -891,17 +882,17 @@ int bofi_engine::enqueue_decode(const void* feats, int feats_dtype, const int* a
 #else
         constexpr int exp_iters = 0;                 // (timing experiment, experiments build only)
 #endif
-        // (bofi_engine_set_bound_iter_cap: a caller that knows how many iterations its captions take enqueues that many + a margin instead of
+        // (opt.bound_iter_cap: a caller that knows how many iterations its captions take enqueues that many + a margin instead of
         // all S -- an iteration past the last live one is five launches that return at once -- and decodes again without the cap when the
         // count of live iterations, *bound_iters, reaches the cap: the loop may then not have ended)
-        const int n_iters = exp_iters ? exp_iters : (bound_iter_cap > 0 && bound_iter_cap < S ? bound_iter_cap : S);
+        const int n_iters = exp_iters ? exp_iters : (opt.bound_iter_cap > 0 && opt.bound_iter_cap < S ? opt.bound_iter_cap : S);
         for (int it = 0; it < n_iters; ++it)
             ENG_OK(enqueue_bound_iter(B, R, att_len, st.ext_syn, st.last, 1, nullptr, nullptr, true, s));
     }
     }
     if (do_fill) {
         ENG_OK(enqueue_fill(att_len, B, R, flags, seq, seq_logprob, s));
-        ENG_OK(bofi::launch_bound_export(st, B, L, S, phrase_num, phrase_length, phrase_syn, bound_iters, s, live_max, sat_out));
+        ENG_OK(bofi::launch_bound_export(st, B, L, S, phrase_num, phrase_length, phrase_syn, bound_iters, s, opt.live_max, opt.sat_out));
     }
     return BOFI_OK;
 }
@@ -924,8 +915,8 @@ int bofi_engine::enqueue_fill(const int* att_len, int B, int R, int flags, int64
     const bool mp = (flags & BOFI_FLAG_MASK_PREDICT) != 0;
     // where a pass's epilogue leaves its ids and row statistics, and what the next pass's embedding reads
     int64_t* const ep_seq = mp ? mp_fresh_ids : seq;
-    float* const ep_plogp = mp ? mp_fresh_plogp : row_plogp_out;
-    float* const ep_chosen = mp ? mp_fresh_chosen : row_chosen_out;
+    float* const ep_plogp = mp ? mp_fresh_plogp : opt.row_plogp;
+    float* const ep_chosen = mp ? mp_fresh_chosen : opt.row_chosen;
     const int64_t* const fed = mp ? mp_next_ids : seq;
     auto refine_step = [&](int round) -> int {
         if (!mp) return BOFI_OK;
@@ -933,7 +924,7 @@ int bofi_engine::enqueue_fill(const int* att_len, int B, int R, int flags, int64
         m.ids = mp_ids; m.chosen = mp_chosen; m.plogp = mp_plogp; m.round = mp_round;
         m.fresh_ids = mp_fresh_ids; m.fresh_chosen = mp_fresh_chosen; m.fresh_plogp = mp_fresh_plogp; m.mask = mp_mask; m.next_ids = mp_next_ids;
         m.last = st.last; m.B = B; m.S = S; m.t = round; m.T = rounds - 1; m.bos_idx = cfg.bos_idx; m.pad_idx = cfg.pad_idx;
-        m.seq_out = seq; m.plogp_out = row_plogp_out; m.chosen_out = row_chosen_out; m.round_out = refine_round_out;
+        m.seq_out = seq; m.plogp_out = opt.row_plogp; m.chosen_out = opt.row_chosen; m.round_out = opt.refine_round;
         return bofi::launch_mask_predict_step(m, s);
     };
     for (int round = 0; round < rounds; ++round) {
@@ -948,7 +939,7 @@ int bofi_engine::enqueue_fill(const int* att_len, int B, int R, int flags, int64
         bofi::AttnArgs a = self_attn_args(qkv, B, S);
         // syn_mask[i, :, :last-1] = True; strict mode reproduces the stale index of :1872-1873 (quirk Q1)
         a.klen = st.last; a.klen_sb = 1; a.klen_bias = -1;
-        a.klen_shared_last = (flags & BOFI_FLAG_STRICT_Q1) ? (q1_group > 0 ? q1_group : B) : 0;
+        a.klen_shared_last = (flags & BOFI_FLAG_STRICT_Q1) ? (opt.q1_group > 0 ? opt.q1_group : B) : 0;
         const bool q_rb = fold_rb_ok(l.q_src, M);
         const bool ffn_rb = ffn_sublayer_ok(l.w1, l.w2, M);
         const bool need_copy_out = !(fold_rb_ok(l.qkv, M) && gen_rb);      // (a consumer of this layer's output reads the bf16 copy + statistics: a tiled GEMM)
@@ -961,13 +952,13 @@ int bofi_engine::enqueue_fill(const int* att_len, int B, int R, int flags, int64
         // split: the cross-attention's core now, its W_o + residual as the head of the feed-forward launch
         const bool cross_split = ffn_rb && !need_copy_out && attn_split_ok(c, l.o_src, l.w1, l.w2, 2);
         ENG_OK(attn_sublayer(c, l.o_src, x_fill, !ffn_rb, cross_split, s));
-        // the word-to-region maps of this layer (bofi_engine_set_attn_out), last pass only: from the queries and keys the sublayer above read, whatever its form --
+        // the word-to-region maps of this layer (the call's attention outputs), last pass only: from the queries and keys the sublayer above read, whatever its form --
         // qs stands until the next layer's query projection, and the kernels apply 1 / sqrt(d_k) themselves
-        if (attn_out_set() && round + 1 == rounds && (int)li == (attn_layer < 0 ? (int)dec.size() - 1 : attn_layer)) {
+        if (attn_out_set() && round + 1 == rounds && (int)li == (opt.attn_layer < 0 ? (int)dec.size() - 1 : opt.attn_layer)) {
             bofi::AttnMapsArgs m{};
             m.q = qs; m.ldq = d; m.k = kv_slot(n_len + (int)li); m.ldk = kv_all.N; m.dtype = dt; m.B = B; m.H = cfg.heads; m.Lq = S; m.Lk = R; m.scale = 0.125f;
             m.klen = att_len; m.qlen = st.last; m.qlen_bias = -1;
-            m.mean = attn_mean_out; m.heads = attn_heads_out; m.K = attn_topk; m.top_idx = attn_top_idx_out; m.top_w = attn_top_w_out;
+            m.mean = opt.attn_mean; m.heads = opt.attn_heads; m.K = opt.attn_topk; m.top_idx = opt.attn_top_idx; m.top_w = opt.attn_top_w;
             ENG_OK(bofi::launch_attn_maps(m, s));
         }
         // next consumer: the next layer's q|k|v (it may ride the feed-forward launch) or the generator
@@ -983,7 +974,7 @@ int bofi_engine::enqueue_fill(const int* att_len, int B, int R, int flags, int64
         bofi::RbVocabArgs v{};
         v.x = x_fill.x; v.ldx = d; v.wp = (const bofi::u32x4*)gen.wp; v.c = gen.b; v.cs = gen.cs; v.M = M; v.N = gen.Npad; v.V = cfg.vocab; v.S = S;
         v.ntok = st.last; v.ntok_bias = -1; v.pad_idx = cfg.pad_idx; v.seq = ep_seq; v.row_plogp = ep_plogp; v.row_chosen = ep_chosen;
-        v.part = vb_part; v.ctr = vb_ctr; v.alone = in_flight == 1;
+        v.part = vb_part; v.ctr = vb_ctr; v.alone = settings.in_flight == 1;
         ENG_OK(bofi::launch_rb_vocab(v, s));
         ENG_OK(refine_step(round));
         continue;
@@ -1013,11 +1004,11 @@ int bofi_engine::enqueue_decode_saic(const void* feats, int feats_dtype, const i
                                      hipStream_t s) {
     const int d = cfg.d_model, dt = cfg.dtype, S = cfg.seq_length, M = B * S;
     const int* halt = st.counters + 2;
-    // iterations it_first .. it_last of the loop (bofi_engine_set_saic_range).  Every iteration past the last live one returns at once but still
+    // iterations it_first .. it_last of the loop (opt.saic_it_begin / saic_it_end).  Every iteration past the last live one returns at once but still
     // costs its ~60 launches' dispatch; a caller that knows how long its captions run enqueues fewer and, when the count of live iterations
     // (bound_iters) says the loop may not be through, the REST in a second call: the loop's state lives in the workspace, so [1, c] then
     // [c + 1, S] is the same computation as [1, S]
-    const int it_first = saic_it_begin > 1 ? saic_it_begin : 1, it_last = saic_it_end > 0 && saic_it_end < S ? saic_it_end : S;
+    const int it_first = opt.saic_it_begin > 1 ? opt.saic_it_begin : 1, it_last = opt.saic_it_end > 0 && opt.saic_it_end < S ? opt.saic_it_end : S;
     if (it_first == 1) {
     ENG_OK(enqueue_encode(feats, feats_dtype, att_len, B, R, nullptr, s));
     ENG_OK(bofi::launch_saic_init(st, sa, B, L, cfg.pad_idx, cfg.bos_idx, cfg.len_idx, s));
@@ -1099,7 +1090,7 @@ int bofi_engine::enqueue_decode_saic(const void* feats, int feats_dtype, const i
         ENG_OK(bofi::launch_vocab_finalize(logits, M, cfg.vocab, S, (flags & BOFI_FLAG_RAW_LOGITS) ? 0 : 1, nullptr, 0, cfg.pad_idx, tok64, s,
                                            st.counters + 3, halt, ri, rn));
         if (flags & BOFI_FLAG_SAMPLE)          // sample_next_word 'sample' (CaptionModel.py:405-425): the drawn ids feed the next bound step
-            ENG_OK(bofi::launch_vocab_sample(logits, M, cfg.vocab, S, 1, sample_temperature, (uint64_t)it * 0x9E3779B97F4A7C15ull, nullptr,
+            ENG_OK(bofi::launch_vocab_sample(logits, M, cfg.vocab, S, 1, opt.sample_temperature, (uint64_t)it * 0x9E3779B97F4A7C15ull, nullptr,
                                              cfg.pad_idx, tok64, s, halt, ri, rn, d_seed));
         ENG_OK(bofi::launch_saic_copy(st, sa, tok64, logits, seq_logprob, B, L, S, cfg.vocab, it, s));
     }
@@ -1138,7 +1129,7 @@ static int run_graphed(bofi_engine* e, const std::vector<uintptr_t>& key, hipStr
 // ================================================================================================
 extern "C" {
 
-int bofi_abi_version(void) { return 4; }
+int bofi_abi_version(void) { return 5; }
 const char* bofi_last_error(void) { return g_err.c_str(); }
 
 int bofi_engine_create(const bofi_config_t* c, bofi_engine_t** out) {
@@ -1193,20 +1184,7 @@ int bofi_engine_fork_ex(bofi_engine_t* parent, int max_batch, int fork_flags, bo
     e->is_fork = true;
     e->rt_dev = nullptr; e->rt_pin = nullptr; e->rt_bytes = 0; e->rt_cache.clear();
     e->dbg_part = nullptr;
-    e->q1_group = 0;                             // per-call knobs are not inherited (the Python handle starts from the defaults)
-    e->sample_temperature = 1.0f;
-    e->sample_seed = 0;
-    e->bound_iter_cap = 0;                       // (a capped parent must not truncate the fork's bounding loop)
-    e->row_plogp_out = nullptr; e->row_chosen_out = nullptr;
-    e->refine_round_out = nullptr;
-    e->attn_mean_out = e->attn_heads_out = e->attn_top_w_out = nullptr; e->attn_top_idx_out = nullptr; e->attn_layer = -1; e->attn_topk = 0;
-    e->in_flight = 0;
-    e->live_max = nullptr;                       // (a raw device pointer the fork's handle does not keep alive)
-    e->sat_out = nullptr;
-    e->loop_mode = -1;
-    // (kv_beside -- a form switch for A/B runs, not a per-call knob -- stays the parent's)
-    e->saic_it_begin = 1;
-    e->saic_it_end = 0;
+    e->settings = parent->settings.forked();
     e->st = bofi::BoundState{};
     e->no_logits = (fork_flags & BOFI_FORK_IDS_ONLY) != 0;
     if (max_batch > 0) e->cfg.max_batch = max_batch;          // (the weights do not depend on it: only the workspace is sized by it)
@@ -1293,16 +1271,10 @@ int bofi_engine_debug_copy(bofi_engine_t* e, const char* name, void* dst, int64_
     return BOFI_OK;
 }
 
-int bofi_engine_set_q1_group(bofi_engine_t* e, int group) {
-    if (!e || group < 0) return fail(BOFI_ERR_ARG, "group must be >= 0");
-    e->q1_group = group;
-    return BOFI_OK;
-}
-
 int bofi_engine_set_decodes_in_flight(bofi_engine_t* e, int n) {
     g_err.clear();
     if (!e || n < 0) return fail(BOFI_ERR_ARG, "decodes in flight: >= 0 (0 = unknown)");
-    e->in_flight = n;
+    e->settings.in_flight = n;
     return BOFI_OK;
 }
 
@@ -1310,39 +1282,17 @@ int bofi_engine_ids_only_fused(bofi_engine_t* e, int B) { return e && e->finaliz
 
 int bofi_engine_bound_loop_active(bofi_engine_t* e, int R) { return e && e->finalized && e->bound_loop_ok(R) ? 1 : 0; }
 
-int bofi_engine_set_bound_iter_cap(bofi_engine_t* e, int cap) {
-    g_err.clear();
-    if (!e) return fail(BOFI_ERR_ARG, "null engine");
-    if (cap < 0) return fail(BOFI_ERR_ARG, "bound iteration cap: >= 0 (0 = seq_length)");
-    e->bound_iter_cap = cap;
-    return BOFI_OK;
-}
-
-int bofi_engine_set_live_iterations_max(bofi_engine_t* e, int* live_max) {
-    g_err.clear();
-    if (!e) return fail(BOFI_ERR_ARG, "null engine");
-    e->live_max = live_max;
-    return BOFI_OK;
-}
-
-int bofi_engine_set_saturation_out(bofi_engine_t* e, int* word) {
-    g_err.clear();
-    if (!e) return fail(BOFI_ERR_ARG, "null engine");
-    e->sat_out = word;
-    return BOFI_OK;
-}
-
 int bofi_engine_set_bound_loop(bofi_engine_t* e, int mode) {
     g_err.clear();
     if (!e || (mode != -1 && mode != 0 && mode != 2)) return fail(BOFI_ERR_ARG, "bound loop mode: -1 (environment / hint), 0 (five-launch iterations) or 2 (persistent loop kernel)");
-    e->loop_mode = mode;
+    e->settings.loop_mode = mode;
     return BOFI_OK;
 }
 
 int bofi_engine_set_bound_kv_beside(bofi_engine_t* e, int mode) {
     g_err.clear();
     if (!e || (mode != 0 && mode != 1)) return fail(BOFI_ERR_ARG, "cross K|V beside the bounding loop: 0 (never) or 1 (where the loops are exposed)");
-    e->kv_beside = mode;
+    e->settings.kv_beside = mode;
     return BOFI_OK;
 }
 
@@ -1350,56 +1300,11 @@ int bofi_engine_bound_kv_beside_active(bofi_engine_t* e, int B, int R, int flags
     return e && e->finalized && B > 0 && R > 0 && e->bound_kv_beside_ok(B, R, flags & (BOFI_FLAG_PHASE_ENCODE | BOFI_FLAG_PHASE_BOUND | BOFI_FLAG_PHASE_FILL)) ? 1 : 0;
 }
 
-int bofi_engine_set_saic_range(bofi_engine_t* e, int it_begin, int it_end) {
-    g_err.clear();
-    if (!e) return fail(BOFI_ERR_ARG, "null engine");
-    if (it_begin < 1 || it_begin > e->cfg.seq_length || it_end < 0 || (it_end > 0 && it_end < it_begin)) return fail(BOFI_ERR_ARG, "saic range: 1 <= begin <= end <= seq_length, or end 0");
-    e->saic_it_begin = it_begin;
-    e->saic_it_end = it_end;
-    return BOFI_OK;
-}
-
 int bofi_engine_saic_put_words(bofi_engine_t* e, const int64_t* seq, int B, void* stream) {
     g_err.clear();
     if (!e || !seq) return fail(BOFI_ERR_ARG, "null argument");
     if (B < 1 || B > e->cfg.max_batch || B != e->saic_B) return fail(BOFI_ERR_ARG, "saic_put_words: B must be the batch of the decode it continues");
     return bofi::launch_saic_put_words(e->st, e->sa, seq, B, e->L, e->cfg.seq_length, (hipStream_t)stream);
-}
-
-int bofi_engine_set_sampling(bofi_engine_t* e, float temperature, uint64_t seed) {
-    if (!e || !(temperature > 0.f)) return fail(BOFI_ERR_ARG, "temperature must be positive");
-    e->sample_temperature = temperature;
-    e->sample_seed = seed;
-    return BOFI_OK;
-}
-
-int bofi_engine_set_row_stats_out(bofi_engine_t* e, float* row_plogp, float* row_chosen) {
-    if (!e || (!row_plogp != !row_chosen)) return fail(BOFI_ERR_ARG, "row statistics: both buffers or none");
-    e->row_plogp_out = row_plogp;
-    e->row_chosen_out = row_chosen;
-    return BOFI_OK;
-}
-
-int bofi_engine_set_refine_out(bofi_engine_t* e, int* emitted_round) {
-    g_err.clear();
-    if (!e) return fail(BOFI_ERR_ARG, "null engine");
-    e->refine_round_out = emitted_round;
-    return BOFI_OK;
-}
-
-int bofi_engine_set_attn_out(bofi_engine_t* e, int layer, float* mean, float* heads, int K, int* top_idx, float* top_w) {
-    g_err.clear();
-    if (!e) return fail(BOFI_ERR_ARG, "null engine");
-    if (!mean && !heads && !top_idx && !top_w) {                 // off
-        e->attn_mean_out = e->attn_heads_out = e->attn_top_w_out = nullptr; e->attn_top_idx_out = nullptr; e->attn_layer = -1; e->attn_topk = 0;
-        return BOFI_OK;
-    }
-    if (layer < -1 || layer >= e->cfg.n_dec) return fail(BOFI_ERR_ARG, "attention output: layer in 0 .. N_dec - 1, or -1 for the last");
-    if (K < 0 || K > 8) return fail(BOFI_ERR_ARG, "attention output: K in 0..8");
-    if (!top_idx != !top_w) return fail(BOFI_ERR_ARG, "attention output: top_idx and top_w, both or neither");
-    if ((K > 0) != (top_idx != nullptr)) return fail(BOFI_ERR_ARG, "attention output: K > 0 goes with top_idx and top_w, K = 0 with neither");
-    e->attn_layer = layer; e->attn_mean_out = mean; e->attn_heads_out = heads; e->attn_topk = K; e->attn_top_idx_out = top_idx; e->attn_top_w_out = top_w;
-    return BOFI_OK;
 }
 
 const float* bofi_engine_logprob(bofi_engine_t* e) {
@@ -1582,8 +1487,10 @@ int bofi_engine_finalize(bofi_engine_t* e) {
     return BOFI_OK;
 }
 
-static int check_call(bofi_engine_t* e, int B, int R) {
+// Every entry point that enqueues begins here: the call's options (NULL: the defaults, which a zero-filled record states too) replace the previous call's
+static int check_call(bofi_engine_t* e, int B, int R, const bofi_call_opts_t* opts = nullptr) {
     if (!e) return fail(BOFI_ERR_ARG, "null engine");
+    e->opt = opts ? *opts : bofi_call_opts_t{};
     if (!e->finalized) return fail(BOFI_ERR_STATE, "engine not finalized");
     if (B <= 0 || B > e->cfg.max_batch) return fail(BOFI_ERR_ARG, "batch outside 1..max_batch");
     if (R <= 0 || R > e->cfg.max_regions) return fail(BOFI_ERR_ARG, "regions outside 1..max_regions");
@@ -1604,13 +1511,39 @@ static int check_mask_predict(bofi_engine_t* e, int flags) {
     if (e->cfg.seq_length > 64) return fail(BOFI_ERR_ARG, "BOFI_FLAG_MASK_PREDICT: seq_length above 64 (one wavefront holds an image's positions)");
     return BOFI_OK;
 }
-// bofi_engine_set_attn_out: the map kernel's limits, checked before anything is enqueued or captured
-static int check_attn_out(bofi_engine_t* e, int R) {
-    if (!e->attn_out_set()) return BOFI_OK;
+// Every rule on a call's options (bofi_call_opts_t), checked before anything is enqueued or captured
+enum { CALL_NAIC, CALL_SAIC, CALL_FILL };
+static int check_opts(bofi_engine_t* e, int flags, const bofi_call_opts_t& o, int which_call, int R) {
+    if (o.q1_group < 0) return fail(BOFI_ERR_ARG, "group must be >= 0");
+    if (o.bound_iter_cap < 0) return fail(BOFI_ERR_ARG, "bound iteration cap: >= 0 (0 = seq_length)");
+    if (which_call == CALL_SAIC && (o.saic_it_begin < 0 || o.saic_it_begin > e->cfg.seq_length || o.saic_it_end < 0 || (o.saic_it_end > 0 && o.saic_it_end < o.saic_it_begin)))
+        return fail(BOFI_ERR_ARG, "saic range: 1 <= begin <= end <= seq_length, or end 0");
+    if (which_call == CALL_SAIC && (flags & BOFI_FLAG_SAMPLE) && !(o.sample_temperature > 0.f)) return fail(BOFI_ERR_ARG, "temperature must be positive");
+    if (!o.row_plogp != !o.row_chosen) return fail(BOFI_ERR_ARG, "row statistics: both buffers or none");
+    if (!o.attn_mean && !o.attn_heads && !o.attn_top_idx && !o.attn_top_w) return BOFI_OK;      // no attention output: layer and K are not read
+    if (which_call == CALL_SAIC) return fail(BOFI_ERR_STATE, "an attention output is set: the maps come out of the non-autoregressive filling pass only, not the semi-autoregressive decode");
+    if (o.attn_layer < -1 || o.attn_layer >= e->cfg.n_dec) return fail(BOFI_ERR_ARG, "attention output: layer in 0 .. N_dec - 1, or -1 for the last");
+    if (o.attn_topk < 0 || o.attn_topk > 8) return fail(BOFI_ERR_ARG, "attention output: K in 0..8");
+    if (!o.attn_top_idx != !o.attn_top_w) return fail(BOFI_ERR_ARG, "attention output: top_idx and top_w, both or neither");
+    if ((o.attn_topk > 0) != (o.attn_top_idx != nullptr)) return fail(BOFI_ERR_ARG, "attention output: K > 0 goes with top_idx and top_w, K = 0 with neither");
+    // the map kernel's limits
     if (e->cfg.seq_length > 64 || R > 128) return fail(BOFI_ERR_ARG, "attention output: seq_length <= 64 and at most 128 regions (bofi_attn_maps)");
     if (e->cfg.d_model != e->cfg.heads * 64) return fail(BOFI_ERR_ARG, "attention output: head dim 64");
     return BOFI_OK;
 }
+// What a captured launch sequence bakes in beside the entry point's own arguments: the call's options, the engine's settings and the environment's generation
+static void key_call(std::vector<uintptr_t>& key, const bofi_engine_t* e) {
+    const bofi_call_opts_t& o = e->opt;
+    uint32_t tbits; std::memcpy(&tbits, &o.sample_temperature, 4);
+    // (sample_seed is deliberately unkeyed: the capture reads it from d_seed, written outside the graph at every call)
+    for (uintptr_t v : {(uintptr_t)o.q1_group, (uintptr_t)o.bound_iter_cap, (uintptr_t)o.saic_it_begin, (uintptr_t)o.saic_it_end, (uintptr_t)tbits, (uintptr_t)o.live_max,
+                        (uintptr_t)o.sat_out, (uintptr_t)o.row_plogp, (uintptr_t)o.row_chosen, (uintptr_t)o.refine_round, (uintptr_t)o.attn_layer, (uintptr_t)o.attn_topk,
+                        (uintptr_t)o.attn_mean, (uintptr_t)o.attn_heads, (uintptr_t)o.attn_top_idx, (uintptr_t)o.attn_top_w,
+                        (uintptr_t)e->settings.in_flight, (uintptr_t)(e->settings.loop_mode + 1), (uintptr_t)e->settings.kv_beside, (uintptr_t)bofi::g_env_generation})
+        key.push_back(v);
+}
+// a new field of the record goes into key_call, or is named there as deliberately unkeyed
+static_assert(sizeof(bofi_call_opts_t) == 112, "bofi_call_opts_t changed: key_call must name every field");
 static int check_feats(bofi_engine_t* e, const void* feats, int feats_dtype) {
     if (!feats) return fail(BOFI_ERR_ARG, "null att_feats");
     if (feats_dtype != BOFI_DT_F32 && feats_dtype != e->cfg.dtype) return fail(BOFI_ERR_ARG, "att_feats must be float32 or the engine's compute dtype");
@@ -1637,13 +1570,13 @@ int bofi_engine_bound_step(bofi_engine_t* e, const int* ext_syn, const int* last
 }
 
 int bofi_engine_fill_naic(bofi_engine_t* e, const int* ext_syn, const int* last, int B, int R, const int* att_len, int flags,
-                          int64_t* seq, float* seq_logprob, void* stream) {
+                          int64_t* seq, float* seq_logprob, const bofi_call_opts_t* opts, void* stream) {
     g_err.clear();
-    ENG_OK(check_call(e, B, R));
+    ENG_OK(check_call(e, B, R, opts));
     if (!ext_syn || !last || !seq) return fail(BOFI_ERR_ARG, "null argument");
     ENG_OK(check_ids_only(e, flags, seq_logprob));
     if (const int rc = check_mask_predict(e, flags)) return rc;      // (its message stays: ENG_OK would put the call's text in its place)
-    if (const int rc = check_attn_out(e, R)) return rc;
+    if (const int rc = check_opts(e, flags, e->opt, CALL_FILL, R)) return rc;
     if (e->no_logits && !e->gen_rb_ok(B * e->cfg.seq_length)) return fail(BOFI_ERR_STATE, "this fork has no vocabulary-wide buffers and the launch would not take the fused generator");
     hipStream_t s = (hipStream_t)stream;
     ENG_HIP(hipMemcpyAsync(e->st.ext_syn, ext_syn, (size_t)B * e->L * sizeof(int), hipMemcpyDeviceToDevice, s));
@@ -1653,28 +1586,27 @@ int bofi_engine_fill_naic(bofi_engine_t* e, const int* ext_syn, const int* last,
 
 int bofi_engine_decode_saic(bofi_engine_t* e, const void* feats, int feats_dtype, const int* att_len, int B, int R, int flags,
                             int64_t* seq, float* seq_logprob, int* phrase_num, int* phrase_length, int64_t* phrase_syn,
-                            int* bound_iters, void* stream) {
+                            int* bound_iters, const bofi_call_opts_t* opts, void* stream) {
     g_err.clear();
-    ENG_OK(check_call(e, B, R));
+    ENG_OK(check_call(e, B, R, opts));
     ENG_OK(check_feats(e, feats, feats_dtype));
     if (!seq) return fail(BOFI_ERR_ARG, "null seq");
     if (flags & BOFI_FLAG_MASK_PREDICT) return fail(BOFI_ERR_ARG, "BOFI_FLAG_MASK_PREDICT refines the non-autoregressive filling pass: not with the semi-autoregressive decode");
-    if (e->attn_out_set()) return fail(BOFI_ERR_STATE, "an attention output is set (bofi_engine_set_attn_out): the maps come out of the non-autoregressive filling pass only, not the semi-autoregressive decode");
+    if (const int rc = check_opts(e, flags, e->opt, CALL_SAIC, R)) return rc;
     if (e->n_len != 1) return fail(BOFI_ERR_STATE, "the semi-autoregressive decode is built for a one-layer bounding network (N_len = 1)");
     if (e->no_logits) return fail(BOFI_ERR_STATE, "this fork has no vocabulary-wide buffers: the semi-autoregressive decode needs the distribution");
     hipStream_t s = (hipStream_t)stream;
     e->saic_B = B;
     for (auto& q : e->qkv_dec)                              // the per-layer q|k|v buffers of this mode (never inside a capture)
         if (!q) ENG_OK(e->dalloc((char**)&q, (size_t)e->cfg.max_batch * e->cfg.seq_length * 3 * e->cfg.d_model, e->tsz));
-    if (flags & BOFI_FLAG_SAMPLE) ENG_OK(bofi::launch_set_u64(e->d_seed, e->sample_seed, s));     // outside the graph: fresh draws per call
+    if (flags & BOFI_FLAG_SAMPLE) ENG_OK(bofi::launch_set_u64(e->d_seed, e->opt.sample_seed, s));     // outside the graph: fresh draws per call
     if (!(flags & BOFI_FLAG_GRAPH))
         return e->enqueue_decode_saic(feats, feats_dtype, att_len, B, R, flags, seq, seq_logprob, phrase_num, phrase_length, phrase_syn,
                                       bound_iters, s);
-    uint32_t tbits; std::memcpy(&tbits, &e->sample_temperature, 4);
     std::vector<uintptr_t> key = {(uintptr_t)1, (uintptr_t)feats, (uintptr_t)feats_dtype, (uintptr_t)att_len, (uintptr_t)B, (uintptr_t)R,
                                   (uintptr_t)flags, (uintptr_t)seq, (uintptr_t)seq_logprob, (uintptr_t)phrase_num,
-                                  (uintptr_t)phrase_length, (uintptr_t)phrase_syn, (uintptr_t)bound_iters, (uintptr_t)tbits,
-                                  (uintptr_t)e->saic_it_begin, (uintptr_t)e->saic_it_end, (uintptr_t)e->in_flight, (uintptr_t)bofi::g_env_generation};
+                                  (uintptr_t)phrase_length, (uintptr_t)phrase_syn, (uintptr_t)bound_iters};
+    key_call(key, e);
     return run_graphed(e, key, s, [&](hipStream_t cs) {
         return e->enqueue_decode_saic(feats, feats_dtype, att_len, B, R, flags, seq, seq_logprob, phrase_num, phrase_length, phrase_syn,
                                       bound_iters, cs);
@@ -1683,14 +1615,14 @@ int bofi_engine_decode_saic(bofi_engine_t* e, const void* feats, int feats_dtype
 
 int bofi_engine_decode_naic(bofi_engine_t* e, const void* feats, int feats_dtype, const int* att_len, int B, int R, int flags,
                             int64_t* seq, float* seq_logprob, int* phrase_num, int* phrase_length, int64_t* phrase_syn,
-                            float* memory_out, int* bound_iters, void* stream) {
+                            float* memory_out, int* bound_iters, const bofi_call_opts_t* opts, void* stream) {
     g_err.clear();
-    ENG_OK(check_call(e, B, R));
+    ENG_OK(check_call(e, B, R, opts));
     ENG_OK(check_feats(e, feats, feats_dtype));
     if (!seq) return fail(BOFI_ERR_ARG, "null seq");
     ENG_OK(check_ids_only(e, flags, seq_logprob));
     if (const int rc = check_mask_predict(e, flags)) return rc;      // (its message stays: ENG_OK would put the call's text in its place)
-    if (const int rc = check_attn_out(e, R)) return rc;
+    if (const int rc = check_opts(e, flags, e->opt, CALL_NAIC, R)) return rc;
     // (before anything is enqueued or captured: such a fork's launch must be one the fused generator takes)
     if (e->no_logits && !e->gen_rb_ok(B * e->cfg.seq_length)) return fail(BOFI_ERR_STATE, "this fork has no vocabulary-wide buffers and the launch would not take the fused generator");
     hipStream_t s = (hipStream_t)stream;
@@ -1700,12 +1632,8 @@ int bofi_engine_decode_naic(bofi_engine_t* e, const void* feats, int feats_dtype
     // graph path: the captured launch sequence is keyed by every argument that is baked into it
     std::vector<uintptr_t> key = {(uintptr_t)0, (uintptr_t)feats, (uintptr_t)feats_dtype, (uintptr_t)att_len, (uintptr_t)B, (uintptr_t)R,
                                   (uintptr_t)flags, (uintptr_t)seq, (uintptr_t)seq_logprob, (uintptr_t)phrase_num,
-                                  (uintptr_t)phrase_length, (uintptr_t)phrase_syn, (uintptr_t)memory_out, (uintptr_t)bound_iters,
-                                  (uintptr_t)e->q1_group, (uintptr_t)e->bound_iter_cap, (uintptr_t)e->live_max, (uintptr_t)e->in_flight,
-                                  (uintptr_t)bofi::g_env_generation, (uintptr_t)e->row_plogp_out, (uintptr_t)e->row_chosen_out,
-                                  (uintptr_t)e->sat_out, (uintptr_t)(e->loop_mode + 1), (uintptr_t)e->kv_beside, (uintptr_t)e->refine_round_out,
-                                  (uintptr_t)e->attn_mean_out, (uintptr_t)e->attn_heads_out, (uintptr_t)e->attn_top_idx_out, (uintptr_t)e->attn_top_w_out,
-                                  (uintptr_t)(e->attn_layer + 1), (uintptr_t)e->attn_topk};
+                                  (uintptr_t)phrase_length, (uintptr_t)phrase_syn, (uintptr_t)memory_out, (uintptr_t)bound_iters};
+    key_call(key, e);
     return run_graphed(e, key, s, [&](hipStream_t cs) {
         return e->enqueue_decode(feats, feats_dtype, att_len, B, R, flags, seq, seq_logprob, phrase_num, phrase_length,
                                  phrase_syn, memory_out, bound_iters, cs);

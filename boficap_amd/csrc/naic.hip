@@ -677,7 +677,7 @@ __global__ void saic_export_kernel(BoundState st, SaicState sa, int B, int L, in
 }
 
 // The tokens emitted so far replaced by the caller's (seq int64 [B, S], the layout of the exported seq): positions 1 .. last - 1 of sa.seq and of
-// the bounding step's input sa.ext_len.  Between two calls that each enqueue part of the loop (bofi_engine_set_saic_range): a caller that draws
+// the bounding step's input sa.ext_len.  Between two calls that each enqueue part of the loop (bofi_call_opts_t.saic_it_begin / saic_it_end): a caller that draws
 // the phrase's words itself -- from its own distribution over the same layout -- and lets the loop continue on THOSE words.
 __global__ void saic_put_words_kernel(BoundState st, SaicState sa, const int64_t* __restrict__ seq, int B, int L, int S) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

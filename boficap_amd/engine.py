@@ -96,6 +96,7 @@ class BofiEngine:
         with torch.cuda.device(self.device):
             hip.check(self._lib.bofi_engine_create(C.byref(c), C.byref(self._h)), "bofi_engine_create")
         self._finalized = False
+        self._live_word = None
 
     def fork(self, max_batch: Optional[int] = None, ids_only: bool = False) -> "BofiEngine":
         """A second engine sharing this one's weights with its own workspace (one per in-flight batch); ``max_batch``: images per call the fork's
@@ -107,7 +108,7 @@ class BofiEngine:
         f = object.__new__(BofiEngine)
         f.cfg, f.dtype, f.device, f.max_batch, f.max_regions = self.cfg, self.dtype, self.device, int(max_batch or self.max_batch), self.max_regions
         f._lib, f._finalized, f._parent = self._lib, True, getattr(self, "_parent", self)        # keeps the weights' owner alive
-        f._iter_cap, f._q1_group, f._live_word = 0, 0, None           # per-call knobs start from the defaults (bofi_engine_fork resets them too)
+        f._live_word = None                                           # (the parent's watch_live_iterations word is not the fork's)
         f._kv_beside = getattr(self, "_kv_beside", 1)                 # (the form switch of set_bound_kv_beside is inherited: bofi_engine_fork copies it)
         f._h = C.c_void_p()
         with torch.cuda.device(self.device):
@@ -188,12 +189,12 @@ class BofiEngine:
         ``q1_group`` > 0: the call carries B / q1_group independent batches (dynamic batching); quirk Q1 applies per batch,
         so each batch's outputs equal its own separate decode.
         ``iter_cap`` > 0 (the five-launch bounding iterations only; the persistent loop kernel -- ``bound_loop_active(R)`` -- ends by itself, ignores the
-        budget and its result is always complete): enqueue that many bounding iterations instead of seq_length (bofi_engine_set_bound_iter_cap); the result is
+        budget and its result is always complete): enqueue that many bounding iterations instead of seq_length (bofi_call_opts_t.bound_iter_cap); the result is
         then the reference's iff ``bound_iters`` < iter_cap afterwards -- the caller checks and decodes again without the cap otherwise.
         ``phases``: "" = the whole decode; a subset of "ebf" = only the encode / bounding loop / filling pass + export of it (BOFI_FLAG_PHASE_*): a pipelining
         caller enqueues the three on the same engine in that order (its streams / events order them) with the same arguments.
         ``row_stats``: the vocabulary epilogue also leaves, per position, sum_v p log p and the log-prob of the emitted id in ``out['row_plogp']`` / ``out['row_chosen']``
-        (float32 [B, S]; bofi_engine_set_row_stats_out) -- what ``row_stats(out)`` / ``entropy_perplexity(out)`` otherwise read back out of the log-prob tensor.
+        (float32 [B, S]; bofi_call_opts_t.row_plogp / row_chosen) -- what ``row_stats(out)`` / ``entropy_perplexity(out)`` otherwise read back out of the log-prob tensor.
         ``ids_only`` (BOFI_FLAG_IDS_ONLY; implies ``want_logprob=False``, not with ``raw_logits``): the distribution is not wanted at all -- ids, layout and ``row_stats``
         only.  Where the row-block generator runs, generator and vocabulary epilogue are then one launch that writes no logits; the ids are the first maxima of the
         raw logits.  ``row_stats(out)`` / ``sample_tokens(out)`` of such a result need ``row_stats=True`` / are not available: there is no distribution to read.
@@ -201,7 +202,7 @@ class BofiEngine:
         (BOFI_FLAG_MASK_PREDICT; ``refine_rounds`` >= 1, not with ``raw_logits``): pass t re-predicts the n (T + 1 - t) / (T + 1) least confident of an image's n
         positions from BOS and keeps the rest; ``out['refine_round']`` (int32 [B, S]) names the pass that emitted each token, ``row_stats`` are those of the
         emitting pass, and ``seq_logprob`` is the LAST pass's tensor (kept positions' rows are its re-prediction, not the distribution that emitted the token).
-        ``attn_topk`` / ``attn_maps`` / ``attn_heads`` / ``attn_layer`` (bofi_engine_set_attn_out; one extra launch in the filling pass): the word-to-region attention of
+        ``attn_topk`` / ``attn_maps`` / ``attn_heads`` / ``attn_layer`` (bofi_call_opts_t.attn_*; one extra launch in the filling pass): the word-to-region attention of
         decoder layer ``attn_layer`` (-1: the last) -- ``out['attn']`` float32 [B, S, R], the heads' mean cross-attention probabilities per position (what the reference
         keeps as ``decoder.layers[-1].src_attn.attn``, averaged over heads); ``out['attn_heads']`` [B, H, S, R]; ``out['attn_top']`` int32 / ``out['attn_top_w']``
         float32 [B, S, K]: each position's K heaviest regions in descending order (-1 / 0 past an image's region count and on positions that carry no word).  With
@@ -225,11 +226,10 @@ class BofiEngine:
                 phrase_syn=torch.empty(B, S, dtype=torch.int64, device=dev),
                 bound_iters=torch.empty(1, dtype=torch.int32, device=dev),
                 memory=torch.empty(B, R, self.cfg.d_model, dtype=torch.float32, device=dev) if want_memory else None)
-        if out.get("bound_saturated") is None:                   # fp16 saturation status of this decode's bounding loop (bofi_engine_set_saturation_out): see ``saturated``
+        if out.get("bound_saturated") is None:                   # fp16 saturation status of this decode's bounding loop (bofi_call_opts_t.sat_out): see ``saturated``
             out["bound_saturated"] = torch.zeros(1, dtype=torch.int32, device=dev)
-        if out["bound_saturated"].data_ptr() != getattr(self, "_sat_ptr", 0):
-            hip.check(self._lib.bofi_engine_set_saturation_out(self._h, hip.ptr(out["bound_saturated"])), "bofi_engine_set_saturation_out")
-            self._sat_ptr = out["bound_saturated"].data_ptr()
+        o = hip.BofiCallOpts(q1_group=int(q1_group), bound_iter_cap=int(iter_cap), sat_out=out["bound_saturated"].data_ptr(),
+                             live_max=None if self._live_word is None else self._live_word.data_ptr())
         if not 0 <= refine_rounds <= 15:
             raise hip.BofiHipError("refine_rounds must be in 0..15")
         if row_stats and raw_logits:
@@ -237,26 +237,15 @@ class BofiEngine:
         if row_stats and "row_plogp" not in out:
             out["row_plogp"] = torch.empty(B, S, dtype=torch.float32, device=dev)
             out["row_chosen"] = torch.empty(B, S, dtype=torch.float32, device=dev)
-        rs = (out["row_plogp"].data_ptr(), out["row_chosen"].data_ptr()) if row_stats else (0, 0)
-        if rs != getattr(self, "_row_stats_ptrs", (0, 0)):
-            hip.check(self._lib.bofi_engine_set_row_stats_out(self._h, hip.ptr(out["row_plogp"]) if row_stats else None, hip.ptr(out["row_chosen"]) if row_stats else None),
-                      "bofi_engine_set_row_stats_out")
-            self._row_stats_ptrs = rs
+        if row_stats:
+            o.row_plogp, o.row_chosen = out["row_plogp"].data_ptr(), out["row_chosen"].data_ptr()
         out["_row_stats_fused"] = bool(row_stats)
         out["_ids_only"] = bool(ids_only)
         if mp and out.get("refine_round") is None:
             out["refine_round"] = torch.empty(B, S, dtype=torch.int32, device=dev)
-        rr = out["refine_round"].data_ptr() if mp else 0
-        if rr != getattr(self, "_refine_ptr", 0):
-            hip.check(self._lib.bofi_engine_set_refine_out(self._h, hip.ptr(out["refine_round"]) if mp else None), "bofi_engine_set_refine_out")
-            self._refine_ptr = rr
-        self._set_attn_out(out, B, R, dev, attn_topk, attn_maps, attn_heads, attn_layer)
-        if q1_group != getattr(self, "_q1_group", 0):
-            hip.check(self._lib.bofi_engine_set_q1_group(self._h, int(q1_group)), "bofi_engine_set_q1_group")
-            self._q1_group = q1_group
-        if int(iter_cap) != getattr(self, "_iter_cap", 0):
-            hip.check(self._lib.bofi_engine_set_bound_iter_cap(self._h, int(iter_cap)), "bofi_engine_set_bound_iter_cap")
-            self._iter_cap = int(iter_cap)
+        if mp:
+            o.refine_round = out["refine_round"].data_ptr()
+        self._attn_opts(o, out, B, R, dev, attn_topk, attn_maps, attn_heads, attn_layer)
         flags = ((hip.FLAG_STRICT_Q1 if strict_q1 else 0) | (hip.FLAG_RAW_LOGITS if raw_logits else 0) | (hip.FLAG_GRAPH if graph else 0)
                  | (refine_rounds << hip.FLAG_REFINE_SHIFT) | (hip.FLAG_IDS_ONLY if ids_only else 0) | mp)
         if phases:
@@ -266,31 +255,26 @@ class BofiEngine:
         hip.check(self._lib.bofi_engine_decode_naic(
             self._h, hip.ptr(att_feats), hip.dtype_code(att_feats), hip.ptr(att_len), B, R, flags, hip.ptr(out["seq"]),
             hip.ptr(out["seq_logprob"]), hip.ptr(out["phrase_num"]), hip.ptr(out["phrase_length"]), hip.ptr(out["phrase_syn"]),
-            hip.ptr(out["memory"]), hip.ptr(out["bound_iters"]), hip.stream_ptr()), "bofi_engine_decode_naic")
+            hip.ptr(out["memory"]), hip.ptr(out["bound_iters"]), C.byref(o), hip.stream_ptr()), "bofi_engine_decode_naic")
         return out
 
-    def _set_attn_out(self, out: dict, B: int, R: int, dev, attn_topk: int, attn_maps: bool, attn_heads: bool, attn_layer: int) -> None:
-        """The attention outputs of the next decode (bofi_engine_set_attn_out): buffers in ``out`` (made when missing or of another shape), the setter called only when
-        a pointer, K or the layer changed; everything off clears it."""
-        if not (attn_topk or attn_maps or attn_heads) and getattr(self, "_attn_state", None) is None:
-            return                                               # (off and nothing to clear: the usual call)
+    def _attn_opts(self, o: "hip.BofiCallOpts", out: dict, B: int, R: int, dev, attn_topk: int, attn_maps: bool, attn_heads: bool, attn_layer: int) -> None:
+        """The attention outputs of a call, into its record ``o``: buffers in ``out`` (made when missing or of another shape)."""
+        if not (attn_topk or attn_maps or attn_heads):
+            return                                               # (off: the usual call)
         K = int(attn_topk)
         if not 0 <= K <= 8:
             raise hip.BofiHipError("attn_topk must be in 0..8")
         if not -1 <= int(attn_layer) < self.cfg.N_dec:
             raise hip.BofiHipError(f"attn_layer must be in 0..{self.cfg.N_dec - 1}, or -1 for the last decoder layer")
         S, H = self.cfg.seq_length, self.cfg.h
-        ptrs = []
-        for key, on, shape, dt in (("attn", attn_maps, (B, S, R), torch.float32), ("attn_heads", attn_heads, (B, H, S, R), torch.float32),
-                                   ("attn_top", K > 0, (B, S, K), torch.int32), ("attn_top_w", K > 0, (B, S, K), torch.float32)):
+        o.attn_layer, o.attn_topk = int(attn_layer), K
+        for field, key, on, shape, dt in (("attn_mean", "attn", attn_maps, (B, S, R), torch.float32), ("attn_heads", "attn_heads", attn_heads, (B, H, S, R), torch.float32),
+                                          ("attn_top_idx", "attn_top", K > 0, (B, S, K), torch.int32), ("attn_top_w", "attn_top_w", K > 0, (B, S, K), torch.float32)):
             if on and (out.get(key) is None or tuple(out[key].shape) != shape):
                 out[key] = torch.empty(shape, dtype=dt, device=dev)
-            ptrs.append(out[key].data_ptr() if on else 0)
-        state = (tuple(ptrs), K, int(attn_layer)) if any(ptrs) else None
-        if state != getattr(self, "_attn_state", None):
-            p = [C.c_void_p(v) if v else None for v in ptrs]
-            hip.check(self._lib.bofi_engine_set_attn_out(self._h, int(attn_layer), p[0], p[1], K, p[2], p[3]), "bofi_engine_set_attn_out")
-            self._attn_state = state
+            if on:
+                setattr(o, field, out[key].data_ptr())
 
     @staticmethod
     def _refine_flag(refine_method: str, refine_rounds: int, raw_logits: bool) -> int:
@@ -375,8 +359,7 @@ class BofiEngine:
         max -- a pipeline of capped decodes (``iter_cap``) is verified with ONE read after the last of them (clear the word first)."""
         if word is not None and (word.dtype != torch.int32 or word.numel() != 1 or not word.is_cuda):
             raise hip.BofiHipError("watch_live_iterations: an int32 [1] device tensor")
-        self._live_word = word                                  # (kept alive)
-        hip.check(self._lib.bofi_engine_set_live_iterations_max(self._h, hip.ptr(word)), "bofi_engine_set_live_iterations_max")
+        self._live_word = word                                  # (kept alive; decode_naic hands it to every call: bofi_call_opts_t.live_max)
 
     def row_stats(self, out: dict):
         """(sum_v p log p, log-prob of the emitted id) per position, float32 [B, S] each, of the decode that produced ``out`` --
@@ -423,7 +406,7 @@ class BofiEngine:
         drawn from Categorical(logits / temperature) (the bound heads stay greedy, as in the reference).  Same result
         layout as ``decode_naic``.  ``graph``: the launch sequence is captured once per argument set and replayed (pass the
         previous result as ``out`` and keep the inputs in place); the sampling seed is read from device memory, so replays
-        draw anew.  ``it_range`` = (first, last) iterations of the loop (bofi_engine_set_saic_range): (1, c) enqueues c iterations,
+        draw anew.  ``it_range`` = (first, last) iterations of the loop (bofi_call_opts_t.saic_it_begin / saic_it_end): (1, c) enqueues c iterations,
         (c + 1, S) with the same arguments and ``out`` continues that decode where it stopped -- together the whole loop, exactly;
         ``out["bound_iters"]`` (live iterations so far) < c says the first part was all of it.  ``layout_only``: the enqueued iterations lay their phrases out and stop
         (BOFI_FLAG_SAIC_LAYOUT_ONLY: no decoder pass, no tokens) -- for a caller that draws the words itself and hands them back with ``saic_put_words``."""
@@ -441,18 +424,15 @@ class BofiEngine:
                 phrase_syn=torch.empty(B, S, dtype=torch.int64, device=dev),
                 bound_iters=torch.empty(1, dtype=torch.int32, device=dev), memory=None)
         flags = (hip.FLAG_RAW_LOGITS if raw_logits else 0) | (hip.FLAG_GRAPH if graph else 0) | (hip.FLAG_SAIC_LAYOUT_ONLY if layout_only else 0)
-        if sample is not None:
-            hip.check(self._lib.bofi_engine_set_sampling(self._h, float(sample[0]), int(sample[1]) & 0xFFFFFFFFFFFFFFFF), "bofi_engine_set_sampling")
-            flags |= hip.FLAG_SAMPLE
         first, last = it_range if it_range is not None else (1, 0)
-        hip.check(self._lib.bofi_engine_set_saic_range(self._h, int(first), int(last) if last < S else 0), "bofi_engine_set_saic_range")
-        try:
-            hip.check(self._lib.bofi_engine_decode_saic(
-                self._h, hip.ptr(att_feats), hip.dtype_code(att_feats), hip.ptr(att_len), B, R, flags,
-                hip.ptr(out["seq"]), hip.ptr(out["seq_logprob"]), hip.ptr(out["phrase_num"]), hip.ptr(out["phrase_length"]),
-                hip.ptr(out["phrase_syn"]), hip.ptr(out["bound_iters"]), hip.stream_ptr()), "bofi_engine_decode_saic")
-        finally:
-            self._lib.bofi_engine_set_saic_range(self._h, 1, 0)
+        o = hip.BofiCallOpts(saic_it_begin=int(first), saic_it_end=int(last) if last < S else 0)
+        if sample is not None:
+            o.sample_temperature, o.sample_seed = float(sample[0]), int(sample[1]) & 0xFFFFFFFFFFFFFFFF
+            flags |= hip.FLAG_SAMPLE
+        hip.check(self._lib.bofi_engine_decode_saic(
+            self._h, hip.ptr(att_feats), hip.dtype_code(att_feats), hip.ptr(att_len), B, R, flags,
+            hip.ptr(out["seq"]), hip.ptr(out["seq_logprob"]), hip.ptr(out["phrase_num"]), hip.ptr(out["phrase_length"]),
+            hip.ptr(out["phrase_syn"]), hip.ptr(out["bound_iters"]), C.byref(o), hip.stream_ptr()), "bofi_engine_decode_saic")
         return out
 
     def saic_put_words(self, seq: torch.Tensor) -> None:
@@ -498,13 +478,11 @@ class BofiEngine:
         lp = torch.empty(B, S, V, dtype=torch.float32, device=dev)
         flags = (hip.FLAG_STRICT_Q1 if strict_q1 else 0) | (hip.FLAG_RAW_LOGITS if raw_logits else 0) | (refine_rounds << hip.FLAG_REFINE_SHIFT) | mp
         rnd = torch.empty(B, S, dtype=torch.int32, device=dev) if mp else None
-        if (rnd.data_ptr() if mp else 0) != getattr(self, "_refine_ptr", 0):
-            hip.check(self._lib.bofi_engine_set_refine_out(self._h, hip.ptr(rnd)), "bofi_engine_set_refine_out")
-            self._refine_ptr = rnd.data_ptr() if mp else 0
+        o = hip.BofiCallOpts(refine_round=rnd.data_ptr() if mp else None)
         attn = {}
-        self._set_attn_out(attn, B, int(R), dev, attn_topk, attn_maps, attn_heads, attn_layer)
+        self._attn_opts(o, attn, B, int(R), dev, attn_topk, attn_maps, attn_heads, attn_layer)
         hip.check(self._lib.bofi_engine_fill_naic(self._h, hip.ptr(ext_syn.contiguous()), hip.ptr(last.contiguous()), B, R, hip.ptr(att_len), flags,
-                                                  hip.ptr(seq), hip.ptr(lp), hip.stream_ptr()), "bofi_engine_fill_naic")
+                                                  hip.ptr(seq), hip.ptr(lp), C.byref(o), hip.stream_ptr()), "bofi_engine_fill_naic")
         res = (seq, lp, rnd) if mp else (seq, lp)
         return res + (attn,) if attn else res
 

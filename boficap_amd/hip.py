@@ -21,7 +21,7 @@ FLAG_SAIC_LAYOUT_ONLY = 4096
 FLAG_IDS_ONLY = 8192
 FLAG_MASK_PREDICT = 16384
 FORK_IDS_ONLY = 1
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 
 class BofiHipError(RuntimeError):
@@ -35,6 +35,16 @@ class BofiConfigC(C.Structure):
 
 
 _P, _I, _I64 = C.c_void_p, C.c_int, C.c_int64
+
+
+class BofiCallOpts(C.Structure):
+    """bofi_call_opts_t: the options of one decode_naic / decode_saic / fill_naic call (the header states each field); zero-filled = the defaults."""
+    _fields_ = [("q1_group", _I), ("bound_iter_cap", _I), ("saic_it_begin", _I), ("saic_it_end", _I), ("sample_temperature", C.c_float), ("sample_seed", C.c_uint64),
+                ("live_max", _P), ("sat_out", _P), ("row_plogp", _P), ("row_chosen", _P), ("refine_round", _P), ("attn_layer", _I), ("attn_topk", _I),
+                ("attn_mean", _P), ("attn_heads", _P), ("attn_top_idx", _P), ("attn_top_w", _P)]
+
+
+_OPTS = C.POINTER(BofiCallOpts)
 
 # name -> (restype, argtypes); mirrors include/boficap_hip.h one to one
 SIGNATURES = {
@@ -78,15 +88,9 @@ SIGNATURES = {
     "bofi_vocab_sample": (_I, [_P, _I, _I, _I, _I, C.c_float, C.c_uint64, _P, _I, _P, _P]),
     "bofi_engine_logprob": (_P, [_P]),
     "bofi_engine_refresh_device": (_I, [_P, _I, C.POINTER(C.c_char_p), C.POINTER(_P), C.POINTER(_I64), _P]),
-    "bofi_engine_set_q1_group": (_I, [_P, _I]),
     "bofi_engine_set_decodes_in_flight": (_I, [_P, _I]),
     "bofi_engine_bound_loop_active": (_I, [_P, _I]),
     "bofi_engine_saic_put_words": (_I, [_P, _P, _I, _P]),
-    "bofi_engine_set_sampling": (_I, [_P, C.c_float, C.c_uint64]),
-    "bofi_engine_set_saic_range": (_I, [_P, _I, _I]),
-    "bofi_engine_set_bound_iter_cap": (_I, [_P, _I]),
-    "bofi_engine_set_live_iterations_max": (_I, [_P, _P]),
-    "bofi_engine_set_saturation_out": (_I, [_P, _P]),
     "bofi_engine_set_bound_loop": (_I, [_P, _I]),
     "bofi_engine_set_bound_kv_beside": (_I, [_P, _I]),
     "bofi_engine_bound_kv_beside_active": (_I, [_P, _I, _I, _I]),
@@ -99,8 +103,8 @@ SIGNATURES = {
     "bofi_engine_stream": (_P, [_P]),
     "bofi_engine_set_weight": (_I, [_P, C.c_char_p, _P, _I64]),
     "bofi_engine_finalize": (_I, [_P]),
-    "bofi_engine_decode_naic": (_I, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "bofi_engine_decode_saic": (_I, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "bofi_engine_decode_naic": (_I, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _OPTS, _P]),
+    "bofi_engine_decode_saic": (_I, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _OPTS, _P]),
     "bofi_engine_encode": (_I, [_P, _P, _I, _P, _I, _I, _P, _P]),
     "bofi_engine_bound_step": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "bofi_engine_debug_copy": (_I, [_P, C.c_char_p, _P, _I64, _P]),
@@ -109,11 +113,10 @@ SIGNATURES = {
     "bofi_attn_block": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P]),
     "bofi_linear_block": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "bofi_vocab_block": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P]),
-    "bofi_engine_set_row_stats_out": (_I, [_P, _P, _P]),
     "bofi_attn_linear_block": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P]),
     "bofi_ffn_block": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _P]),
     "bofi_ffn_linear_block": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
-    "bofi_engine_fill_naic": (_I, [_P, _P, _P, _I, _I, _P, _I, _P, _P, _P]),
+    "bofi_engine_fill_naic": (_I, [_P, _P, _P, _I, _I, _P, _I, _P, _P, _OPTS, _P]),
     "bofi_attn_out_ffn_block": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
     "bofi_cider_refs": (_I, [_P, _P, _I, _I, _P, _P, _I, C.c_double, _P, _P, _P, _P, _I, _P]),
     "bofi_cider_score": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _I, _P, _P, _P]),
@@ -125,10 +128,8 @@ SIGNATURES = {
     "bofi_diversity_score": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, C.c_double, _P, _I64, _P, _P, _P, _P, _P]),
     "bofi_oracle_stats": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "bofi_pack_regions": (_I, [_P, _I, _P, _P, _I, _I, _P, _I, _I, _I, _P, _P]),
-    "bofi_engine_set_refine_out": (_I, [_P, _P]),
     "bofi_mask_predict_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "bofi_attn_maps": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_float, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
-    "bofi_engine_set_attn_out": (_I, [_P, _I, _P, _P, _I, _P, _P]),
     "bofi_caption_trim": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     "bofi_sentence_lookup": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
 }

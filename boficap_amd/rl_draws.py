@@ -71,7 +71,7 @@ def draw_pass(model, laid, temperature: float, rows, draw_base: int) -> Draws:
     the step's first forward (the one that runs the encoder).
 
       * non-autoregressive branch: the words of every laid-out slot are drawn from the first forward's fill rows;
-      * semi-autoregressive branch: the engine's loop runs ONE iteration per call (bofi_engine_set_saic_range, layout only): its bounding step lays the next
+      * semi-autoregressive branch: the engine's loop runs ONE iteration per call (bofi_call_opts_t.saic_it_begin / saic_it_end, layout only): its bounding step lays the next
         phrase out on the words so far (TransformerModel.py:1903-1948), ``rows`` gives that phrase's rows, its words are drawn from them and handed back to
         the engine (bofi_engine_saic_put_words), whose next bounding step reads them -- core_SAIC's own process (:1903-1984) with the training pass's fill
         distribution.

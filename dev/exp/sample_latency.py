@@ -27,5 +27,4 @@ for cap in (0, None):
             r = model(fc, att, None, opt={"train_mode": "NAIC", "sample_method": "greedy"}, mode="sample")
         torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / 50 * 1e3
-    ecap = getattr(model.engine(), "_iter_cap", 0)
-    print(f"bofi_naic_iter_cap {cap}: {ms:.3f} ms per call of 64 images ({64 / ms * 1e3:.0f} img/s), live iterations {model._naic_recent[-1]}, engine cap {ecap}")
+    print(f"bofi_naic_iter_cap {cap}: {ms:.3f} ms per call of 64 images ({64 / ms * 1e3:.0f} img/s), live iterations {model._naic_recent[-1]}")

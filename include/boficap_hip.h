@@ -282,7 +282,7 @@ typedef struct bofi_config {
     int dtype;        /* compute dtype: BOFI_DT_F32 (parity) or BOFI_DT_BF16 (throughput) */
     int n_len;        /* layers of the bounding network (LengthPredictor_UIC N_len, TransformerModel.py:357-375): 1 (configs/uic_sd.yml) takes
                          the row-0-only incremental form; >= 2 (configs/uic_sd_N2.yml) the dense form -- all S+2 rows through every layer
-                         per iteration, as the reference computes it (a field since ABI version 2; the library is at version 4: bofi_abi_version) */
+                         per iteration, as the reference computes it (a field since ABI version 2; the library is at version 5: bofi_abi_version) */
 } bofi_config_t;
 
 /* Allocates device weights + workspace for one model replica on the current HIP device. */
@@ -304,7 +304,7 @@ int bofi_engine_finalize(bofi_engine_t* e);
  * re-finalized while they exist.  Destroy a fork with bofi_engine_destroy. */
 int bofi_engine_fork(bofi_engine_t* parent, bofi_engine_t** out);
 /* The same with a workspace for up to max_batch images per call (0 = the parent's): dynamic batching puts several loader batches into one decode call
- * (bofi_engine_set_q1_group), which a model built for one batch per call has no workspace for -- its weights serve either size. */
+ * (bofi_call_opts_t.q1_group), which a model built for one batch per call has no workspace for -- its weights serve either size. */
 int bofi_engine_fork_sized(bofi_engine_t* parent, int max_batch, bofi_engine_t** out);
 /* The same with options.  BOFI_FORK_IDS_ONLY: a workspace WITHOUT the two vocabulary-wide float32 buffers (max_batch * S * (vocab + padded vocab) * 4 bytes: most of a
  * fork's memory) -- for decodes under BOFI_FLAG_IDS_ONLY that take the fused generator.  On such a fork a decode without that flag, one whose launch would need
@@ -322,10 +322,52 @@ int bofi_engine_ids_only_fused(bofi_engine_t* e, int B);
 int bofi_engine_refresh_device(bofi_engine_t* e, int n, const char* const* names, const float* const* ptrs, const int64_t* numels,
                                void* stream);
 
-/* Several independent batches in ONE decode call (dynamic batching for serving): with group > 0 the B images of a call are
- * consecutive batches of `group` images and quirk Q1 (BOFI_FLAG_STRICT_Q1) applies inside each batch, so every batch's result
- * equals its own separate decode.  0 (default): the whole call is one batch. */
-int bofi_engine_set_q1_group(bofi_engine_t* e, int group);
+/* The options of ONE call of bofi_engine_decode_naic / bofi_engine_decode_saic / bofi_engine_fill_naic, handed to it as `opts` (since ABI version 5).  Nothing of it outlives
+ * the call: the next call starts from its own record.  NULL means the defaults, and so does a zero-filled record.  Every rule below is checked before anything is enqueued or
+ * captured (BOFI_ERR_ARG with a message); under BOFI_FLAG_GRAPH every field but sample_seed is part of the graph key, so keep the buffers in place across replays. */
+typedef struct bofi_call_opts {
+    /* Several independent batches in ONE decode call (dynamic batching for serving): with q1_group > 0 the B images of a call are consecutive batches of q1_group
+     * images and quirk Q1 (BOFI_FLAG_STRICT_Q1) applies inside each batch, so every batch's result equals its own separate decode.  0: the whole call is one batch. */
+    int q1_group;
+    /* Bounding iterations a decode_naic enqueues (core_NAIC's loop, TransformerModel.py:1843-1869; 0 = all seq_length).  The loop exits when every image is finished; enqueued
+     * iterations past that point return at once but still cost their five launches.  With a cap c the decode is the reference's if and only if the loop ended within c
+     * iterations: *bound_iters (iterations in which some image was live) < c.  Otherwise decode again with cap 0.  The persistent loop kernel ends by itself and ignores it. */
+    int bound_iter_cap;
+    /* The iterations a decode_saic enqueues: saic_it_begin .. saic_it_end of core_SAIC's loop (TransformerModel.py:1903-1984; 1-based, begin 0 reads as 1, end 0 = seq_length:
+     * the whole loop).  A call with begin 1 encodes and initialises; one with begin > 1 continues the PREVIOUS call's loop on the state left in the engine's workspace (same
+     * arguments, no other decode in between) and exports again: [1, c] followed by [c + 1, seq_length] is the same computation as the whole loop.  Iterations past the last
+     * live one return at once but still cost their launches; *bound_iters (live iterations so far) < c after [1, c] means the loop has ended. */
+    int saic_it_begin; int saic_it_end;
+    /* Temperature (> 0; read only under BOFI_FLAG_SAMPLE) and seed of the token draws of a decode_saic called with BOFI_FLAG_SAMPLE.  The seed travels through device
+     * memory, outside the captured launches: a replayed graph draws anew. */
+    float sample_temperature; uint64_t sample_seed;
+    /* With a pipeline of capped decodes whose results are consumed later: device int32 (NULL = off) that receives, by atomic max, the live-iteration count of this
+     * decode_naic -- one read after the last decode tells whether ALL of them ended inside the cap (the caller clears the word first). */
+    int* live_max;
+    /* fp16 saturation status of the persistent bounding-loop kernel.  That kernel computes the bounding network with FP16 operands (fp16 copies of the float32 parameters,
+     * activations converted on their way into the MFMAs) and clamps to +-65 504 on conversion; a model whose bounding layer leaves that range -- none here does: |y| < 30 --
+     * would get a silently different slot layout where the bf16 kernels (same exponent range as float32) would not.  Device int32 (NULL = off): the decode_naic WRITES its
+     * status there (beside bound_iters): 0 = nothing was clamped (always 0 when the decode ran the five-launch bf16 iterations), bit 0 = an activation (attention context or
+     * hidden row of the bounding layer) was clamped during this decode, bit 1 = the fp16 weight copies were clamped when they were packed (finalize / refresh_device), bit 2 =
+     * the kernel's pair exchange timed out (two workgroups share a group's feed-forward weights: a safety net against a lost workgroup, never observed).  A caller that reads a
+     * non-zero word decodes that batch again under bofi_engine_set_bound_loop(e, 0) (boficap_amd/engine.py does, with a warning).  Replaces nothing in the reference
+     * (TransformerModel.py:357-383 runs in float32 there); it guards this library's own precision choice. */
+    int* sat_out;
+    /* bofi_vocab_stats' two per-position figures straight out of a decode_naic's vocabulary epilogue (no second pass over the [B, S, V] tensor): float32 [B * S] device
+     * buffers, both or neither (greedy decodes with log-softmax).  sum_v p log p is formed as sum_v e_v (x_v - max) / sum_v e_v - lse in the pass that sums the exponentials. */
+    float* row_plogp; float* row_chosen;
+    /* Decodes under BOFI_FLAG_MASK_PREDICT: int32 [B * S] device buffer that receives, per position, the pass (0 .. T) that emitted the token standing there (0 on the
+     * pad tail); NULL: off. */
+    int* refine_round;
+    /* bofi_attn_maps' outputs for decoder layer attn_layer (0 .. N_dec - 1, or -1 = the last; read only when one of the four buffers is given) of a decode_naic / fill_naic's
+     * filling pass -- Lq = seq_length, Lk = R, klen = att_len, qlen = tokens laid out -- device buffers attn_mean [B, S, R], attn_heads [B, H, S, R], attn_top_idx / attn_top_w
+     * [B, S, K = attn_topk] as there (any of the three groups may be NULL; all NULL: off; K > 0 goes with the top pair, K = 0 with neither).  One extra launch per decode, right behind
+     * the layer's cross-attention sublayer, from the queries and keys that sublayer read; it belongs to BOFI_FLAG_PHASE_FILL.  With refinement rounds only the LAST pass launches
+     * it: under feed-back that is the final ids' own pass; under BOFI_FLAG_MASK_PREDICT the rows of kept positions are that pass's re-prediction, not the pass that emitted the
+     * token (as seq_logprob).  Needs seq_length <= 64 and R <= 128; decode_saic with a buffer given is BOFI_ERR_STATE. */
+    int attn_layer; int attn_topk;
+    float* attn_mean; float* attn_heads; int* attn_top_idx; float* attn_top_w;
+} bofi_call_opts_t;
 
 /* A hint, not a semantic: how many decodes the caller keeps in flight on this device (engine + forks on their own streams).  1: this engine's
  * launches run with nothing beside them -- from 4 096 rows on the sublayer kernels then take 64-row blocks (more, shorter workgroups: 62 against 68 us
@@ -338,43 +380,15 @@ int bofi_engine_set_decodes_in_flight(bofi_engine_t* e, int n);
  * and leaves when its images are finished; fp16 operands derived from the float32 parameters -- under the engine's current decodes-in-flight hint:
  * bf16 engine at the reference's width (d_model 512, 8 heads, d_ff <= 2048 a multiple of 512, seq_length <= 22, N_len = 1), R <= 128, and the
  * hint is not 1 (a decode that runs alone keeps the five launches per iteration: shorter latency); environment knob BOFI_BOUND_LOOP: 0 = never,
- * 2 = whatever the hint (read again by bofi_reload_env).  The bound-iteration cap (bofi_engine_set_bound_iter_cap) does not apply to that kernel.  0 otherwise. */
+ * 2 = whatever the hint (read again by bofi_reload_env).  The bound-iteration cap (bofi_call_opts_t.bound_iter_cap) does not apply to that kernel.  0 otherwise. */
 int bofi_engine_bound_loop_active(bofi_engine_t* e, int R);
 
-/* Temperature (> 0) and seed of the token draws of a decode called with BOFI_FLAG_SAMPLE. */
-int bofi_engine_set_sampling(bofi_engine_t* e, float temperature, uint64_t seed);
-/* The iterations the following bofi_engine_decode_saic calls enqueue: it_begin .. it_end of core_SAIC's loop (TransformerModel.py:1903-1984; 1-based,
- * it_end 0 = seq_length; the default is the whole loop, 1 .. seq_length).  A call with it_begin == 1 encodes and initialises; one with
- * it_begin > 1 continues the PREVIOUS call's loop on the state left in the engine's workspace (same arguments, no other decode in between) and
- * exports again: [1, c] followed by [c + 1, seq_length] is the same computation as the whole loop.  Iterations past the last live one return
- * at once but still cost their launches; *bound_iters (live iterations so far) < c after [1, c] means the loop has ended. */
-int bofi_engine_set_saic_range(bofi_engine_t* e, int it_begin, int it_end);
 /* Between two partial bofi_engine_decode_saic calls: the tokens emitted so far (positions before the end of the last placed phrase) are replaced by
  * seq int64 [B, seq_length] (device memory, the layout of the exported seq), in the emitted caption and in the bounding step's input
  * (extend_phrase_len, TransformerModel.py:1959-1966): the loop continues on the caller's words.  For a caller that draws each phrase itself over the
  * engine's layout -- the self-critical step's reference-estimator mode draws from the TRAINING forward's dropout-perturbed distribution
  * (loss_wrapper.py:193-209 samples in train mode), boficap_amd/trainer.py. */
 int bofi_engine_saic_put_words(bofi_engine_t* e, const int64_t* seq, int B, void* stream);
-/* Bounding iterations the following bofi_engine_decode_naic calls enqueue (core_NAIC's loop, TransformerModel.py:1843-1869; 0 = all seq_length,
- * the default).  The loop exits when every image is finished; enqueued iterations past that point return at once but still cost their five
- * launches.  With a cap c the decode is the reference's if and only if the loop ended within c iterations: *bound_iters (iterations in which
- * some image was live) < c.  Otherwise decode again with cap 0. */
-int bofi_engine_set_bound_iter_cap(bofi_engine_t* e, int cap);
-/* With a pipeline of capped decodes whose results are consumed later: `live_max` (device int32, NULL = off) receives, by atomic max, the
- * live-iteration count of every following bofi_engine_decode_naic -- one read after the last decode tells whether ALL of them ended inside the
- * cap (the caller clears the word first). */
-int bofi_engine_set_live_iterations_max(bofi_engine_t* e, int* live_max);
-
-/* fp16 saturation status of the persistent bounding-loop kernel (round 6; ABI version 4).  That kernel computes the bounding network with FP16 operands
- * (fp16 copies of the float32 parameters, activations converted on their way into the MFMAs) and clamps to +-65 504 on conversion; a model whose bounding
- * layer leaves that range -- none here does: |y| < 30 -- would get a silently different slot layout where the bf16 kernels (same exponent range as float32) would not.
- * `word` (device int32, NULL = off -- the default, also of a fork): every following bofi_engine_decode_naic WRITES its status there (beside bound_iters): 0 = nothing was
- * clamped (always 0 when the decode ran the five-launch bf16 iterations), bit 0 = an activation (attention context or hidden row of the bounding layer) was clamped
- * during this decode, bit 1 = the fp16 weight copies were clamped when they were packed (finalize / refresh_device), bit 2 = the kernel's pair exchange timed out (two workgroups share a group's
- * feed-forward weights: a safety net against a lost workgroup, never observed).  A caller that reads a non-zero word decodes that
- * batch again under bofi_engine_set_bound_loop(e, 0) (boficap_amd/engine.py does, with a warning).  Per-call state, part of the graph key.
- * Replaces nothing in the reference (TransformerModel.py:357-383 runs in float32 there); it guards this library's own precision choice. */
-int bofi_engine_set_saturation_out(bofi_engine_t* e, int* word);
 /* Per-engine choice of the bounding loop's form for the following decodes: -1 (default, also of a fork) = BOFI_BOUND_LOOP and the decodes-in-flight hint decide
  * (bofi_engine_bound_loop_active), 0 = the five-launch bf16 iterations, 2 = the persistent fp16 loop kernel whatever the hint.  Part of the graph key. */
 int bofi_engine_set_bound_loop(bofi_engine_t* e, int mode);
@@ -393,13 +407,6 @@ int bofi_engine_bound_kv_beside_active(bofi_engine_t* e, int B, int R, int flags
  * seq_logprob buffer leaves the distribution (valid until the next decode on this engine) -- input of
  * bofi_vocab_stats / bofi_vocab_sample when the 48.6 MB tensor is not wanted in user memory. */
 const float* bofi_engine_logprob(bofi_engine_t* e);
-/* The same two per-position figures straight out of a NAIC decode's vocabulary epilogue (no second pass over the [B, S, V] tensor): float32 [B * S] device buffers
- * that every following bofi_engine_decode_naic of this engine fills (greedy decodes with log-softmax; NULL, NULL: off -- the default, also of a fork).  Per-call state,
- * part of the graph key.  sum_v p log p is formed as sum_v e_v (x_v - max) / sum_v e_v - lse in the pass that sums the exponentials. */
-int bofi_engine_set_row_stats_out(bofi_engine_t* e, float* row_plogp, float* row_chosen);
-/* Optional output of decodes under BOFI_FLAG_MASK_PREDICT: int32 [B * S] device buffer that receives, per position, the pass (0 .. T) that emitted the
- * token standing there (0 on the pad tail); NULL: off -- the default, also of a fork.  Per-call state, part of the graph key. */
-int bofi_engine_set_refine_out(bofi_engine_t* e, int* emitted_round);
 
 /* A HIP stream owned by the engine (hipStream_t as void*), for callers that keep one decode per engine in
  * flight and want each on its own hardware queue. */
@@ -410,7 +417,7 @@ void* bofi_engine_stream(bofi_engine_t* e);
 #define BOFI_FLAG_RAW_LOGITS 2     /* output_logsoftmax = 0 (AttModel.py:208-209) */
 #define BOFI_FLAG_GRAPH 4          /* replay the call from a captured hipGraph when possible */
 #define BOFI_FLAG_SAMPLE 16         /* decode_saic: draw each phrase's tokens from Categorical(logits / temperature) instead of
-                                      the argmax (sample_method 'sample'); parameters from bofi_engine_set_sampling */
+                                      the argmax (sample_method 'sample'); parameters: bofi_call_opts_t.sample_temperature / sample_seed */
 #define BOFI_FLAG_REFINE_SHIFT 8   /* bits 8..11: extra filling rounds; round r > 0 feeds round r-1's ids back as the
                                       decoder input tokens (decode_NA's glat_input, TransformerModel.py:570-574).  The
                                       reference has no refinement loop: parity of rounds > 0 is pinned to the oracle only. */
@@ -423,7 +430,7 @@ void* bofi_engine_stream(bofi_engine_t* e);
                                           no decoder pass, no tokens: the caller draws the phrase's words from its own distribution and hands them back with
                                           bofi_engine_saic_put_words before the next call (the reference-estimator self-critical step) */
 #define BOFI_FLAG_PHASE_FILL 128    /* decode_NA + logit + greedy pick + the slot-state export (:570-587, 1872-1876) on the preceding two */
-#define BOFI_FLAG_IDS_ONLY 8192     /* decode_naic / fill_naic (phased form included): ids, slot layout and the row statistics of bofi_engine_set_row_stats_out only -- the
+#define BOFI_FLAG_IDS_ONLY 8192     /* decode_naic / fill_naic (phased form included): ids, slot layout and the row statistics of bofi_call_opts_t.row_plogp / row_chosen only -- the
                                        vocabulary distribution is not wanted (seq_logprob must be NULL; not with BOFI_FLAG_RAW_LOGITS).  Where the row-block generator would run
                                        (bf16 engine at the reference's width, launches of BOFI_RB_MIN_ROWS rows or more) every filling round's generator + epilogue is one
                                        bofi_vocab_block launch: no logits in memory; the pick is the first maximum of the raw logits (it can differ from the log-softmax
@@ -435,10 +442,10 @@ void* bofi_engine_stream(bofi_engine_t* e);
                                        the state.  Pass t = 1 .. T: k = n_b (T + 1 - t) / (T + 1) (integer division); its mask is the k positions s < n_b with the lowest c[s] -- ties go
                                        to the lower position, a NaN ranks below every number, NaNs among themselves by position; its input ids are BOS under the mask and y[s] elsewhere
                                        (s >= n_b: pad, as feed-back); positions in the mask take the pass's id and statistics and emitted_round = t, the others keep the state; s >= n_b
-                                       always takes the fresh pass's values (pad, emitted_round 0).  Outputs: seq = y after pass T; the buffers of bofi_engine_set_row_stats_out
+                                       always takes the fresh pass's values (pad, emitted_round 0).  Outputs: seq = y after pass T; bofi_call_opts_t.row_plogp / row_chosen
                                        receive c and e of the STATE (each position's figures come from the pass that emitted its token); seq_logprob, when wanted, is the LAST pass's
-                                       tensor -- the rows of kept positions are that pass's re-prediction, not the distribution that emitted the token; emitted_round goes to the buffer
-                                       of bofi_engine_set_refine_out.  Costs T + 1 launches of bofi_mask_predict_step's kernel per decode over feed-back.  BOFI_ERR_ARG before any
+                                       tensor -- the rows of kept positions are that pass's re-prediction, not the distribution that emitted the token; emitted_round goes to
+                                       bofi_call_opts_t.refine_round.  Costs T + 1 launches of bofi_mask_predict_step's kernel per decode over feed-back.  BOFI_ERR_ARG before any
                                        launch: T = 0, BOFI_FLAG_RAW_LOGITS, BOFI_FLAG_SAMPLE, bofi_engine_decode_saic, seq_length > 64. */
 
 /* model(fc, att, att_masks, opt={'train_mode':'NAIC','sample_method':'greedy'}, mode='sample'):
@@ -453,7 +460,7 @@ void* bofi_engine_stream(bofi_engine_t* e);
 int bofi_engine_decode_naic(bofi_engine_t* e, const void* att_feats, int feats_dtype, const int* att_len,
                             int B, int R, int flags, int64_t* seq, float* seq_logprob, int* phrase_num,
                             int* phrase_length, int64_t* phrase_syn, float* memory_out, int* bound_iters,
-                            void* stream);
+                            const bofi_call_opts_t* opts, void* stream);
 
 /* model(..., opt={'train_mode':'SAIC','sample_method':'greedy'}, mode='sample'): the semi-autoregressive decode
  * core_SAIC TransformerModel.py:1878-1986 (AttModel.py:430-437) -- per phrase one bounding step on the words
@@ -462,11 +469,11 @@ int bofi_engine_decode_naic(bofi_engine_t* e, const void* att_feats, int feats_d
  * when every image is finished or a NaN appears (:1956-1958).  Outputs as for decode_naic
  * (seq_logprob rows never written stay 0, as in the reference).  From the second phrase on only the new phrase's rows go
  * through the decoder's GEMMs (their K / V join a per-layer cache; results identical to the all-rows form).  flags:
- * BOFI_FLAG_RAW_LOGITS, BOFI_FLAG_SAMPLE (bofi_engine_set_sampling; the seed lives in device memory, so a replayed graph
+ * BOFI_FLAG_RAW_LOGITS, BOFI_FLAG_SAMPLE (opts->sample_temperature / sample_seed; the seed lives in device memory, so a replayed graph
  * draws anew), BOFI_FLAG_GRAPH (captured once per argument set, as decode_naic). */
 int bofi_engine_decode_saic(bofi_engine_t* e, const void* att_feats, int feats_dtype, const int* att_len,
                             int B, int R, int flags, int64_t* seq, float* seq_logprob, int* phrase_num,
-                            int* phrase_length, int64_t* phrase_syn, int* bound_iters, void* stream);
+                            int* phrase_length, int64_t* phrase_syn, int* bound_iters, const bofi_call_opts_t* opts, void* stream);
 
 /* Stages of the call above, exposed for module-level parity tests (SURVEY.md §4 pyramid level 2). */
 int bofi_engine_encode(bofi_engine_t* e, const void* att_feats, int feats_dtype, const int* att_len,
@@ -593,7 +600,7 @@ double bofi_gemm_flops(int reset, double* skippable);
  * rounds as for decode_naic.  Lets a reduced-precision engine be compared with the oracle position by position on the
  * oracle's own layout, whatever its own bounding pass would have picked. */
 int bofi_engine_fill_naic(bofi_engine_t* e, const int* ext_syn, const int* last, int B, int R, const int* att_len, int flags,
-                          int64_t* seq, float* seq_logprob, void* stream);
+                          int64_t* seq, float* seq_logprob, const bofi_call_opts_t* opts, void* stream);
 
 /* CIDEr-D reward of the self-critical step (get_scores, captioning/utils/rewards.py:86-131, with the CiderD scorer of the
  * pyciderevalcap package), in fp64.  A row's token list is its ids up to and including the first 0, or the whole row if it has
@@ -730,14 +737,6 @@ int bofi_mask_predict_step(int64_t* ids, float* chosen, float* plogp, int* round
  * One launch: a workgroup per image, a wavefront per head. */
 int bofi_attn_maps(const void* q, int ldq, const void* k, int ldk, int dtype, int B, int H, int Lq, int Lk, float scale, const int* klen,
                    const int* qlen, int qlen_bias, float* mean, float* heads, int K, int* top_idx, float* top_w, void* stream);
-/* Optional outputs of the following bofi_engine_decode_naic / bofi_engine_fill_naic calls of this engine: the maps above for decoder layer `layer` (0 .. N_dec - 1, or -1 =
- * the last) of the filling pass -- Lq = seq_length, Lk = R, klen = att_len, qlen = tokens laid out -- device buffers mean [B, S, R], heads [B, H, S, R], top_idx / top_w
- * [B, S, K] as for bofi_attn_maps (any of the three groups may be NULL; all NULL: off -- the default, also of a fork).  One extra launch per decode, right behind the layer's
- * cross-attention sublayer, from the queries and keys that sublayer read; it belongs to BOFI_FLAG_PHASE_FILL.  With refinement rounds only the LAST pass launches it:
- * under feed-back that is the final ids' own pass; under BOFI_FLAG_MASK_PREDICT the rows of kept positions are that pass's re-prediction, not the pass that emitted the
- * token (as seq_logprob).  Needs seq_length <= 64 and R <= 128 (BOFI_ERR_ARG at the decode otherwise); bofi_engine_decode_saic with an output set is BOFI_ERR_STATE.
- * Per-call state, part of the graph key. */
-int bofi_engine_set_attn_out(bofi_engine_t* e, int layer, float* mean, float* heads, int K, int* top_idx, float* top_w);
 
 /* The bad-ending trim of the reference's decode_sequence (captioning/utils/misc.py:75-82, REMOVE_BAD_ENDINGS) and the flag of its count_bad
  * (captioning/utils/eval_utils.py:32-37), on id rows.  seq int64 [rows, S], 1 <= S <= 64.  The caption of a row is its ids before the first id <= limit

@@ -240,6 +240,23 @@ def core_naic(w: Weights, cfg, memory, src_mask, *, fix_q1: bool = False, trace=
     return phrase, phrase_num, phrase_length[:, :-2], phrase_syn[:, :-2], dict(iters=iters, last=last.clone(), ext_syn=ext_syn.clone(), reason=reason)
 
 
+def layout_of(cfg, out):
+    """(ext_syn int64 [B, S + 2], last numpy int64 [B]) of a decode's slot layout, as core_NAIC builds them (TransformerModel.py:1829-1869), from its exported
+    phrase_length / phrase_syn."""
+    import numpy as np
+    pl, ps = out["phrase_length"].cpu().numpy(), out["phrase_syn"].cpu().numpy()
+    B, S = pl.shape
+    ext = np.full((B, S + 2), cfg.pad_idx, np.int64)
+    ext[:, 0] = cfg.len_idx
+    last = np.ones(B, np.int64)
+    for b in range(B):
+        for i in range(S):
+            if pl[b, i] > 0:
+                ext[b, last[b]:last[b] + pl[b, i]] = ps[b, i]
+                last[b] += pl[b, i]
+    return torch.from_numpy(ext), last
+
+
 def sample_naic_refine(w: Weights, cfg, att_feats, att_masks=None, *, rounds: int = 2, fix_q1: bool = False):
     """Iterative refinement of the filling pass (BASELINE config 5).  NOT in the reference: parity unpinned.
     Defined on the reference's own hook decode_NA(..., glat_input) TM:570-574: round r > 0 decodes with the

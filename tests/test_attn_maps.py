@@ -61,18 +61,24 @@ def _lib():
 
 
 def test_declarations_agree():
-    """The kernel's entry point and the engine's setter: header, ctypes table, build list; the ABI version stays."""
+    """The kernel's entry point and the per-call record that carries the engine's attention outputs: header, ctypes table, build list, ABI version."""
     from boficap_amd import build, hip
     header = open(os.path.join(ROOT, "include", "boficap_hip.h")).read()
     code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    for name, arity in (("bofi_attn_maps", 19), ("bofi_engine_set_attn_out", 7)):
+    for name, arity in (("bofi_attn_maps", 19),):
         found = re.findall(r"\b" + name + r"\s*\(([^;{]*?)\)\s*;", code, flags=re.S)
         assert len(found) == 1 and found[0].count(",") + 1 == len(hip.SIGNATURES[name][1]) == arity, name
+    # the per-call record: the header's field list is the ctypes mirror's, in order, and its size is the one the engine's graph key asserts
+    body = re.search(r"typedef\s+struct\s+bofi_call_opts\s*\{(.*?)\}\s*bofi_call_opts_t\s*;", code, flags=re.S).group(1)
+    assert re.findall(r"(\w+)\s*;", body) == [n for n, _ in hip.BofiCallOpts._fields_]
+    pinned = re.findall(r"static_assert\(sizeof\(bofi_call_opts_t\) == (\d+)", open(os.path.join(build.CSRC, "engine.hip")).read())
+    assert len(pinned) == 1 and C.sizeof(hip.BofiCallOpts) == int(pinned[0])
+    assert {"attn_layer", "attn_topk", "attn_mean", "attn_heads", "attn_top_idx", "attn_top_w"} <= set(dict(hip.BofiCallOpts._fields_))
     assert "attn_maps.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "attn_maps.hip"))
     assert "launch_attn_maps" in open(os.path.join(build.CSRC, "bofi_kernels.h")).read()
-    assert hip.ABI_VERSION == 4
+    assert hip.ABI_VERSION == 5
     _, lib = _lib()
-    assert hasattr(lib, "bofi_attn_maps") and hasattr(lib, "bofi_engine_set_attn_out") and callable(hip.attn_maps)
+    assert hasattr(lib, "bofi_attn_maps") and callable(hip.attn_maps)
 
 
 def test_attn_maps_refuses_bad_arguments_without_a_device():

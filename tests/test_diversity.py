@@ -245,7 +245,7 @@ def test_header_and_ctypes_table_declare_the_entry_point_alike():
     assert found[0].count(",") + 1 == len(hip.SIGNATURES["bofi_diversity_score"][1]) == 16
     found = re.findall(r"\bint64_t\s+bofi_diversity_workspace\s*\(([^;{]*?)\)\s*;", code, flags=re.S)
     assert len(found) == 1 and found[0].count(",") + 1 == len(hip.SIGNATURES["bofi_diversity_workspace"][1]) == 3
-    assert "diversity.hip" in SOURCES and "cider.hip" in SOURCES and hip.ABI_VERSION == 4
+    assert "diversity.hip" in SOURCES and "cider.hip" in SOURCES and hip.ABI_VERSION == 5
     csrc = os.path.join(ROOT, "boficap_amd", "csrc")
     for src in ("cider.hip", "diversity.hip"):                          # both build their records with the one header
         assert '#include "bofi_record.h"' in open(os.path.join(csrc, src)).read()

@@ -54,21 +54,6 @@ class _Recorder:
         O.attention = self.orig
 
 
-def _layout_of(cfg, out):
-    """(ext_syn int64 [B, S + 2], last [B]) of a decode's slot layout, as core_NAIC builds them (TransformerModel.py:1829-1869)."""
-    pl, ps = out["phrase_length"].cpu().numpy(), out["phrase_syn"].cpu().numpy()
-    B, S = pl.shape
-    ext = np.full((B, S + 2), cfg.pad_idx, np.int64)
-    ext[:, 0] = cfg.len_idx
-    last = np.ones(B, np.int64)
-    for b in range(B):
-        for i in range(S):
-            if pl[b, i] > 0:
-                ext[b, last[b]:last[b] + pl[b, i]] = ps[b, i]
-                last[b] += pl[b, i]
-    return torch.from_numpy(ext), last
-
-
 def _oracle_fill_maps(cfg, sd, att, masks, ext_syn, last, group, layer):
     """softmax(scores) [B, h, S, Lk] of decoder layer ``layer``'s cross-attention in the oracle's filling pass on a GIVEN slot layout (quirk Q1 per ``group`` images)."""
     w = O.as_torch(sd)
@@ -296,7 +281,7 @@ def _bf16_against_oracle(cfg, sd, eng, att, masks, tag, group=0, compare=None, *
     out = eng.decode_naic(att.cuda(), att_len, attn_maps=True, attn_heads=True, attn_topk=3, q1_group=group, **kw)
     torch.cuda.synchronize()
     n = compare or att.size(0)
-    ext, last = _layout_of(cfg, {k: out[k][:n] for k in LAYOUT})
+    ext, last = O.layout_of(cfg, {k: out[k][:n] for k in LAYOUT})
     want = _oracle_fill_maps(cfg, sd, att[:n].float(), None if masks is None else masks[:n], ext, last, group or n, cfg.N_dec - 1)
     err = max(_against(out["attn_heads"][:n].cpu().numpy(), want), _against(out["attn"][:n].cpu().numpy(), want.mean(1)))
     print(f"attn maps bf16 engine {tag}: max |attn - oracle| {err:.3e}")
@@ -394,9 +379,16 @@ def test_nothing_else_moves(dtype, tiny_f32):
     g = eng.decode_naic(att, row_stats=True, graph=True, out=g, attn_topk=3, attn_maps=True, attn_heads=True)
     torch.cuda.synchronize()
     assert all(g[k].data_ptr() == p for k, p in ptrs.items()) and same(g, first, first) and same(g, on, tuple(first) + keys)
-    # the semi-autoregressive decode refuses while an attention output is set; a decode without the options clears it
+    # the semi-autoregressive decode refuses a call whose options carry an attention output (BOFI_ERR_STATE, before any launch); the options of the decodes above ended
+    # with them: a decode without the options writes no maps, and a semi-autoregressive decode right behind an attention decode runs
+    import ctypes as C
+    so = eng.decode_saic(att)
+    o = hip.BofiCallOpts(attn_layer=-1, attn_mean=g["attn"].data_ptr())
+    rc = hip.lib().bofi_engine_decode_saic(eng._h, hip.ptr(att), hip.dtype_code(att), None, att.size(0), att.size(1), 0, hip.ptr(so["seq"]), hip.ptr(so["seq_logprob"]),
+                                           hip.ptr(so["phrase_num"]), hip.ptr(so["phrase_length"]), hip.ptr(so["phrase_syn"]), hip.ptr(so["bound_iters"]), C.byref(o), hip.stream_ptr())
+    assert rc == 3
     with pytest.raises(hip.BofiHipError, match="attention output"):
-        eng.decode_saic(att)
+        hip.check(rc, "bofi_engine_decode_saic")
     again = eng.decode_naic(att, row_stats=True)
     torch.cuda.synchronize()
     assert not any(k.startswith("attn") for k in again) and same(again, off, keys)
@@ -409,7 +401,7 @@ def test_nothing_else_moves(dtype, tiny_f32):
     torch.cuda.synchronize()
     assert same(mp, plain_mp, ("seq", "seq_logprob", "refine_round") + LAYOUT)
     # the filling pass alone on a given layout: the decode's own maps
-    ext, last = _layout_of(cfg, on)
+    ext, last = O.layout_of(cfg, on)
     eng.encode(att)
     res = eng.fill_naic(ext.to(torch.int32).cuda(), torch.from_numpy(last).to(torch.int32).cuda(), att.size(1), attn_maps=True, attn_topk=3)
     torch.cuda.synchronize()

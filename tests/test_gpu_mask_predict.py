@@ -273,7 +273,7 @@ def test_engine_refuses_what_mask_predict_excludes(bf16_full):
     # the library's own checks, before any launch
     o = eng.decode_naic(a)
     args = lambda flags: (eng._h, hip.ptr(a), hip.dtype_code(a), None, 4, 36, flags, hip.ptr(o["seq"]), hip.ptr(o["seq_logprob"]), hip.ptr(o["phrase_num"]),
-                          hip.ptr(o["phrase_length"]), hip.ptr(o["phrase_syn"]), None, hip.ptr(o["bound_iters"]), hip.stream_ptr())
+                          hip.ptr(o["phrase_length"]), hip.ptr(o["phrase_syn"]), None, hip.ptr(o["bound_iters"]), None, hip.stream_ptr())
     lib = hip.lib()
     for flags, word in ((hip.FLAG_MASK_PREDICT, b"refinement count"), (hip.FLAG_MASK_PREDICT | (2 << 8) | hip.FLAG_RAW_LOGITS, b"RAW_LOGITS"),
                         (hip.FLAG_MASK_PREDICT | (2 << 8) | hip.FLAG_SAMPLE, b"SAMPLE")):

@@ -350,8 +350,8 @@ def test_integration_stub_b(weight_cache, manifest):
     ns["_lib"].bofi_engine_destroy(ref_self._bofi)
 
 
-def test_bounding_loop_with_fewer_iterations_enqueued(weight_cache, manifest):
-    """bofi_engine_set_bound_iter_cap through model(..., mode='sample'): the loop enqueued for c iterations, the count of live iterations
+def test_bounding_loop_with_fewer_iterations_enqueued(weight_cache, manifest, monkeypatch):
+    """bofi_call_opts_t.bound_iter_cap through model(..., mode='sample'): the loop enqueued for c iterations, the count of live iterations
     read back, the decode repeated without the cap when c was not enough -- the reference's 6-tuple whatever c (opt.bofi_naic_iter_cap),
     and the adaptive choice (recent decodes + 2) after three calls."""
     import captioning.models as models
@@ -364,6 +364,8 @@ def test_bounding_loop_with_fewer_iterations_enqueued(weight_cache, manifest):
     att = torch.from_numpy(g["att_feats"]).cuda()
     fc = torch.zeros(att.size(0), 0, device="cuda")
     eng = model.engine()
+    caps, decode = [], eng.decode_naic                                  # the budget every decode of this engine is called with (iter_cap is keyword-only)
+    monkeypatch.setattr(eng, "decode_naic", lambda *a, **kw: (caps.append(kw.get("iter_cap", 0)), decode(*a, **kw))[1])
     whole = eng.decode_naic(model._as_input(att), None)
     live = int(whole["bound_iters"])
     assert 1 <= live < cfg.seq_length
@@ -378,12 +380,12 @@ def test_bounding_loop_with_fewer_iterations_enqueued(weight_cache, manifest):
         assert (seq.cpu().numpy() == g["naic_seq"]).all() and (pl.cpu().numpy() == g["naic_phrase_length"]).all(), cap
         assert (pn.cpu().numpy() == g["naic_phrase_num"]).all() and (ps.cpu().numpy() == g["naic_phrase_syn"]).all(), cap
         assert _close(lp.cpu().numpy(), g["naic_logprob"], 0) < 1e-3
-    assert model._naic_recent[-1] == live and eng._iter_cap == min(cfg.seq_length, live + 2) % cfg.seq_length      # the last calls ran under the adaptive cap
+    assert model._naic_recent[-1] == live and caps[-1] == min(cfg.seq_length, live + 2) % cfg.seq_length      # the last calls ran under the adaptive cap
 
 
 def test_fork_right_after_a_capped_decode_does_not_inherit_the_cap(engines):
-    """bofi_engine_fork copies the parent's struct: the per-call knobs (bounding-iteration cap, live-iteration word, semi-autoregressive
-    range) must start from their defaults in the fork, or a fork made behind a capped decode (sample_pair in the self-critical step behind a
+    """bofi_engine_fork copies the parent's struct: no per-call option (bounding-iteration cap, live-iteration word, semi-autoregressive
+    range) may reach the fork, or a fork made behind a capped decode (sample_pair in the self-critical step behind a
     periodic eval) runs a truncated bounding loop that nobody checks."""
     cfg, sd, eng = engines("tiny_mix", torch.float32)
     att, att_len = _inputs(load_golden("tiny_mix"))
@@ -392,17 +394,71 @@ def test_fork_right_after_a_capped_decode_does_not_inherit_the_cap(engines):
     assert live >= 2
     word = torch.zeros(1, dtype=torch.int32, device="cuda")
     eng.watch_live_iterations(word)
-    short = eng.decode_naic(att, att_len, iter_cap=1)                  # leaves cap = 1 and the word set on the parent
+    short = eng.decode_naic(att, att_len, iter_cap=1)                  # a capped call, and the word set on the parent's handle
     assert int(short["bound_iters"]) == 1 and int(word) == 1
     f = eng.fork()
-    assert (f._iter_cap, f._q1_group, f._live_word) == (0, 0, None)
+    assert f._live_word is None
     word.zero_()
-    r = f.decode_naic(att, att_len)                                    # iter_cap = 0 == the handle's default: no call resets the native cap
+    r = f.decode_naic(att, att_len)                                    # its own options: no cap, no word
     assert int(r["bound_iters"]) == live and int(word) == 0           # the whole loop, and the parent's word left alone
     for k in ("seq", "phrase_num", "phrase_length", "phrase_syn"):
         assert torch.equal(r[k], whole[k]), k
     eng.watch_live_iterations(None)
-    eng.decode_naic(att, att_len)                                      # (parent back to its defaults for the tests that share it)
+
+
+SENTINEL = -12345.0
+
+
+def _untouched(t):
+    return torch.equal(t.view(torch.int32), torch.full_like(t, SENTINEL).view(torch.int32))
+
+
+def test_fill_naic_starts_from_the_defaults(engines):
+    """Nothing of a decode reaches the fill_naic behind it: the row-statistics buffers of decode_naic(row_stats=True) are not written again, and Q1 applies to the
+    whole call, not to the decode's q1_group -- the result is that of a fork that ran nothing before."""
+    cfg, sd, eng = engines("tiny_mix", torch.float32)
+    att, att_len = _inputs(load_golden("tiny_mix"))
+    B, R = att.size(0), att.size(1)
+    assert B % 2 == 0 and B > 2
+    out = eng.decode_naic(att, att_len, row_stats=True, q1_group=B // 2)
+    torch.cuda.synchronize()
+    ext, last = O.layout_of(cfg, out)
+    ext, last = ext.to(torch.int32).cuda(), torch.from_numpy(last).to(torch.int32).cuda()
+    out["row_plogp"].fill_(SENTINEL)
+    out["row_chosen"].fill_(SENTINEL)
+    seq, lp = eng.fill_naic(ext, last, R, att_len)
+    torch.cuda.synchronize()
+    assert _untouched(out["row_plogp"]) and _untouched(out["row_chosen"])
+    f = eng.fork()
+    f.encode(att, att_len)
+    fseq, flp = f.fill_naic(ext, last, R, att_len)
+    torch.cuda.synchronize()
+    assert torch.equal(seq, fseq) and torch.equal(lp.view(torch.int32), flp.view(torch.int32))      # (bits: a NaN row equals itself)
+
+
+def test_a_captured_decode_does_not_outlive_its_options(engines):
+    """Replayed decodes into one `out`: the capture made with row statistics or with an iteration cap is replayed only by a call that asks for them."""
+    cfg, sd, eng = engines("tiny_mix", torch.float32)
+    att, att_len = _inputs(load_golden("tiny_mix"))
+    out = eng.decode_naic(att, att_len, graph=True)
+    torch.cuda.synchronize()
+    seq, live = out["seq"].clone(), int(out["bound_iters"])
+    assert 2 <= live < cfg.seq_length
+    out["row_plogp"] = torch.full(tuple(seq.shape), SENTINEL, device="cuda")
+    out["row_chosen"] = torch.full(tuple(seq.shape), SENTINEL, device="cuda")
+    out = eng.decode_naic(att, att_len, graph=True, out=out, row_stats=True)
+    torch.cuda.synchronize()
+    assert bool((out["row_plogp"] != SENTINEL).all()) and bool((out["row_chosen"] != SENTINEL).all()) and torch.equal(out["seq"], seq)
+    out["row_plogp"].fill_(SENTINEL)
+    out["row_chosen"].fill_(SENTINEL)
+    out = eng.decode_naic(att, att_len, graph=True, out=out)
+    torch.cuda.synchronize()
+    assert _untouched(out["row_plogp"]) and _untouched(out["row_chosen"]) and torch.equal(out["seq"], seq)
+    short = eng.decode_naic(att, att_len, graph=True, out=out, iter_cap=1)
+    assert int(short["bound_iters"]) == 1                              # "may not be through": the caller decodes again
+    whole = eng.decode_naic(att, att_len, graph=True, out=out)
+    assert int(whole["bound_iters"]) == live and torch.equal(whole["seq"], seq)
+    assert _untouched(out["row_plogp"]) and _untouched(out["row_chosen"])
 
 
 def test_entropy_perplexity_without_materialising_logprobs(engines):
@@ -422,7 +478,7 @@ def test_entropy_perplexity_without_materialising_logprobs(engines):
     assert r2["seq_logprob"] is None and torch.equal(r2["seq"], seq)
     ent2, ppl2 = eng.entropy_perplexity(r2)
     assert _close(ent2.cpu().numpy(), ent_ref.cpu().numpy(), 0) < 1e-4 and _close(ppl2.cpu().numpy(), ppl_ref.cpu().numpy(), 0) < 1e-4
-    # ... and straight out of the decode's vocabulary epilogue (bofi_engine_set_row_stats_out: no second pass over the tensor), eager and replayed, with refinement
+    # ... and straight out of the decode's vocabulary epilogue (bofi_call_opts_t.row_plogp / row_chosen: no second pass over the tensor), eager and replayed, with refinement
     # rounds, with the log-probs materialised or not; the per-position figures against the read-back kernel's
     for kw in (dict(), dict(want_logprob=False), dict(graph=True), dict(refine_rounds=1)):
         plain = eng.decode_naic(att, att_len, **kw)

@@ -285,7 +285,7 @@ def test_sample_pair_equals_the_two_sample_calls(weight_cache, manifest):
 
 
 def test_capped_semi_autoregressive_loop_with_its_continuation_equals_the_whole_loop(weight_cache, manifest):
-    """bofi_engine_set_saic_range / sample_pair(saic_cap=c) + saic_finish: the loop's first c iterations, then -- when the count of live
+    """bofi_call_opts_t.saic_it_begin / saic_it_end / sample_pair(saic_cap=c) + saic_finish: the loop's first c iterations, then -- when the count of live
     iterations says it may not be through -- the rest on the state the engine still holds: ids, layouts and log-probs of the whole loop,
     bit for bit, sampled and greedy, whatever c; a cap past the last live iteration needs no second part."""
     cfg, sd, model = _model(weight_cache, manifest)

@@ -2,6 +2,7 @@
 passes in numpy, and the whole decode on the oracle's memory_of / core_naic / decode_na / logit -- that tests/test_gpu_mask_predict.py holds the
 kernel and the engine to.  The reference has no refinement loop, so this module is where parity is pinned (include/boficap_hip.h,
 BOFI_FLAG_MASK_PREDICT, states the same rules in words)."""
+import ctypes as C
 import functools
 import os
 import re
@@ -148,17 +149,23 @@ def restate(name, T, method="mask_predict", margin=1e-3):
 
 # ----------------------------------------------------------------------------- tests
 def test_declarations_agree():
-    """The step's entry point, the flag and the setter: header, ctypes table and build list."""
+    """The step's entry point, the flag and the per-call record that carries refine_round: header, ctypes table and build list."""
     from boficap_amd import build, hip
     header = open(os.path.join(ROOT, "include", "boficap_hip.h")).read()
     code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    for name, arity in (("bofi_mask_predict_step", 21), ("bofi_engine_set_refine_out", 2)):
+    for name, arity in (("bofi_mask_predict_step", 21),):
         found = re.findall(r"\b" + name + r"\s*\(([^;{]*?)\)\s*;", code, flags=re.S)
         assert len(found) == 1 and found[0].count(",") + 1 == len(hip.SIGNATURES[name][1]) == arity, name
+    # the per-call record: the header's field list is the ctypes mirror's, in order, and its size is the one the engine's graph key asserts
+    body = re.search(r"typedef\s+struct\s+bofi_call_opts\s*\{(.*?)\}\s*bofi_call_opts_t\s*;", code, flags=re.S).group(1)
+    assert re.findall(r"(\w+)\s*;", body) == [n for n, _ in hip.BofiCallOpts._fields_]
+    pinned = re.findall(r"static_assert\(sizeof\(bofi_call_opts_t\) == (\d+)", open(os.path.join(build.CSRC, "engine.hip")).read())
+    assert len(pinned) == 1 and C.sizeof(hip.BofiCallOpts) == int(pinned[0])
+    assert "refine_round" in dict(hip.BofiCallOpts._fields_)
     assert re.search(r"#define\s+BOFI_FLAG_MASK_PREDICT\s+16384\b", header) and hip.FLAG_MASK_PREDICT == 16384
     assert "refine.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "refine.hip"))
     assert "launch_mask_predict_step" in open(os.path.join(build.CSRC, "bofi_kernels.h")).read()
-    assert hip.ABI_VERSION == 4
+    assert hip.ABI_VERSION == 5
     flags = [v for k, v in vars(hip).items() if k.startswith("FLAG_") and k != "FLAG_REFINE_SHIFT"]
     assert all(hip.FLAG_MASK_PREDICT & v == 0 for v in flags if v != hip.FLAG_MASK_PREDICT) and hip.FLAG_MASK_PREDICT & (15 << hip.FLAG_REFINE_SHIFT) == 0
 

@@ -161,7 +161,7 @@ def test_header_and_ctypes_table_declare_the_entry_point_alike():
     found = re.findall(r"\bint\s+bofi_oracle_stats\s*\(([^;{]*?)\)\s*;", code, flags=re.S)
     assert len(found) == 1
     assert found[0].count(",") + 1 == len(hip.SIGNATURES["bofi_oracle_stats"][1]) == 9
-    assert "oracle.hip" in SOURCES and hip.ABI_VERSION == 4
+    assert "oracle.hip" in SOURCES and hip.ABI_VERSION == 5
     assert "#pragma clang fp contract(off)" in open(os.path.join(ROOT, "boficap_amd", "csrc", "oracle.hip")).read()
 
 

@@ -132,7 +132,7 @@ def test_header_and_ctypes_table_declare_the_entry_point_alike():
     found = re.findall(r"\bint\s+bofi_rouge_score\s*\(([^;{]*?)\)\s*;", code, flags=re.S)
     assert len(found) == 1
     assert found[0].count(",") + 1 == len(hip.SIGNATURES["bofi_rouge_score"][1]) == 15
-    assert "rouge.hip" in SOURCES and hip.ABI_VERSION == 4
+    assert "rouge.hip" in SOURCES and hip.ABI_VERSION == 5
 
 
 def test_language_eval_reads_rows_and_strings_alike():

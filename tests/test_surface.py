@@ -147,7 +147,7 @@ def test_header_and_ctypes_table_declare_the_entry_points_alike():
         assert len(found) == 1 and found[0].count(",") + 1 == len(hip.SIGNATURES[name][1]) == arity, name
         assert found[0].rstrip().endswith("void* stream")
     assert "surface.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "surface.hip"))
-    assert hip.ABI_VERSION == 4
+    assert hip.ABI_VERSION == 5
 
 
 def run_eval(*args):
