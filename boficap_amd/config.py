@@ -44,6 +44,11 @@ class BofiConfig:
         return self.vocab_size + 4
 
     @property
+    def att_feat_padded(self) -> int:
+        """``att_feat_size`` rounded up to 64: the width the engine's att_embed GEMM runs at (2112 for the 2053 of use_box; zero columns beyond att_feat_size)."""
+        return -(-self.att_feat_size // 64) * 64
+
+    @property
     def d_k(self) -> int:
         return self.d_model // self.h
 

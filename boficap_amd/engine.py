@@ -74,6 +74,9 @@ def pick_stream_beside(main, device=None, candidates: int = 12, spin_cycles: int
     return cand
 
 
+ATT_EMBED_W = "att_embed.0.weight"
+
+
 class BofiEngine:
     def __init__(self, cfg: BofiConfig, dtype: torch.dtype = torch.bfloat16, max_batch: int = 64,
                  max_regions: int = 36, device: Optional[torch.device] = None):
@@ -88,7 +91,7 @@ class BofiEngine:
         self.max_batch, self.max_regions = max_batch, max_regions
         self._lib = hip.lib()
         c = hip.BofiConfigC(
-            vocab=cfg.tgt_vocab, feat=cfg.att_feat_size, d_model=cfg.d_model, d_ff=cfg.d_ff, heads=cfg.h,
+            vocab=cfg.tgt_vocab, feat=cfg.att_feat_padded, d_model=cfg.d_model, d_ff=cfg.d_ff, heads=cfg.h,
             n_enc=cfg.N_enc, n_dec=cfg.N_dec, seq_length=cfg.seq_length, pad_idx=cfg.pad_idx, bos_idx=cfg.bos_idx,
             eos_idx=cfg.eos_idx, len_idx=cfg.len_idx, head_hidden=cfg.head_hidden, max_batch=max_batch,
             max_regions=max_regions, dtype={torch.float32: hip.DT_F32, torch.bfloat16: hip.DT_BF16}[dtype], n_len=cfg.N_len)
@@ -130,8 +133,13 @@ class BofiEngine:
     # ---------------------------------------------------------------- weights
     def load_state_dict(self, sd: Dict[str, object]) -> None:
         """``sd``: reference-schema state dict (torch tensors on any device, or numpy arrays)."""
+        F, Fp = self.cfg.att_feat_size, self.cfg.att_feat_padded
         for name, v in sd.items():
             a = v.detach().to("cpu", torch.float32).contiguous().numpy() if torch.is_tensor(v) else np.ascontiguousarray(v, np.float32)
+            if name == ATT_EMBED_W and Fp != F:                  # the engine's K dimension is the padded width: zero columns beyond att_feat_size
+                if a.shape != (self.cfg.d_model, F):
+                    raise hip.BofiHipError(f"{name}: [{self.cfg.d_model}, {F}] expected, got {a.shape}")
+                a = np.ascontiguousarray(np.pad(a, ((0, 0), (0, Fp - F))))
             hip.check(self._lib.bofi_engine_set_weight(self._h, name.encode(), a.ctypes.data_as(C.c_void_p), a.size),
                       f"set_weight({name})")
         with torch.cuda.device(self.device):
@@ -145,6 +153,17 @@ class BofiEngine:
         if not self._finalized:
             raise hip.BofiHipError("the first load goes through load_state_dict")
         items = [(k, v) for k, v in named.items() if k != "model.pos_embed.pe"]
+        F, Fp = self.cfg.att_feat_size, self.cfg.att_feat_padded
+        if Fp != F:                                              # att_embed's weight goes through this engine's padded float32 copy (zero columns beyond att_feat_size)
+            for i, (k, v) in enumerate(items):
+                if k == ATT_EMBED_W:
+                    if not v.is_cuda or v.dtype != torch.float32 or tuple(v.shape) != (self.cfg.d_model, F):
+                        raise hip.BofiHipError(f"{k}: float32 [{self.cfg.d_model}, {F}] on the HIP device expected")
+                    pad = getattr(self, "_att_w_padded", None)
+                    if pad is None or pad.device != v.device:
+                        pad = self._att_w_padded = torch.zeros(self.cfg.d_model, Fp, dtype=torch.float32, device=v.device)
+                    pad[:, :F].copy_(v.detach())
+                    items[i] = (k, pad)
         # (a training loop refreshes after every optimiser step with the same tensors: the checked argument arrays are kept per set of addresses)
         # (the key holds everything the check looks at: the caching allocator hands addresses out again -- tensors of another dtype, size or name at
         # the same addresses must not ride on an old validation)
@@ -168,9 +187,18 @@ class BofiEngine:
             self.set_bound_loop(-1)
 
     # ---------------------------------------------------------------- calls
+    def pad_feats(self, att_feats: torch.Tensor) -> torch.Tensor:
+        """Dense [B, R, att_feat_size] features zero-padded with torch to the engine's [B, R, att_feat_padded] (plumbing, not the hot path: the box launch
+        of csrc/regions.hip writes the padded width itself); anything else -- and every tensor when att_feat_size % 64 == 0 -- is returned as it is."""
+        F, Fp = self.cfg.att_feat_size, self.cfg.att_feat_padded
+        if Fp == F or att_feats.dim() != 3 or att_feats.size(2) != F:
+            return att_feats
+        return torch.nn.functional.pad(att_feats, (0, Fp - F))
+
     def _check_feats(self, att_feats, att_len):
-        if att_feats.dim() != 3 or att_feats.size(2) != self.cfg.att_feat_size:
-            raise hip.BofiHipError(f"att_feats must be [B, R, {self.cfg.att_feat_size}], got {tuple(att_feats.shape)}")
+        if att_feats.dim() != 3 or att_feats.size(2) != self.cfg.att_feat_padded:
+            raise hip.BofiHipError(f"att_feats must be [B, R, {self.cfg.att_feat_padded}], got {tuple(att_feats.shape)}" + (
+                "" if self.cfg.att_feat_padded == self.cfg.att_feat_size else f" (att_feat_size {self.cfg.att_feat_size} zero-padded to a multiple of 64: pad_feats)"))
         if not att_feats.is_cuda or not att_feats.is_contiguous():
             raise hip.BofiHipError("att_feats must be a contiguous tensor on the HIP device")
         if att_len is not None and (att_len.dtype != torch.int32 or not att_len.is_cuda or att_len.numel() != att_feats.size(0)):
@@ -551,6 +579,11 @@ class DecodePipeline:
     def _as_host_or_device(x):
         return torch.from_numpy(x) if not torch.is_tensor(x) else x
 
+    def _width(self, F: int) -> int:
+        """The feature width of a launch's buffer: dense items of an unaligned att_feat_size (2053) are copied into the engine's zero-padded width."""
+        cfg = self.root.cfg
+        return cfg.att_feat_padded if F == cfg.att_feat_size else F
+
     def _bucket(self, r: int) -> int:
         for b in self.buckets:
             if b >= r:
@@ -561,7 +594,9 @@ class DecodePipeline:
         """``batches``: iterable of ``att_feats`` or ``(att_feats, att_len)``: [b, R, F] tensors / arrays in the engine's compute dtype or float32, on
         the host (pinned: the copy is asynchronous) or the device; ``att_len`` int32 [b] region counts or None (every image has R regions).  An item may
         also be a ``features.RaggedBatch``: its real rows alone are copied, in the files' dtype, and ``bofi_pack_regions`` pads them to the region bucket
-        in the compute dtype on the device (a batch whose images all have the bucket's count is decoded without counts, as the loader hands it over)."""
+        in the compute dtype on the device (a batch whose images all have the bucket's count is decoded without counts, as the loader hands it over).  A
+        ``features.BoxRaggedBatch`` (use_box) also brings boxes and image sizes: ``bofi_pack_regions_box`` appends the geometry columns, sorts by box area and
+        writes the engine's padded width.  Dense items of an ``att_feat_size`` that is no multiple of 64 are copied into that zero-padded width."""
         from .features import RaggedBatch
         pending = []                                             # launches in flight: (slot, [batch sizes])
         group, gkey = [], None
@@ -582,7 +617,7 @@ class DecodePipeline:
         for item in batches:
             if isinstance(item, RaggedBatch):
                 r = self._bucket(item.max_len)
-                key = (item.B, r, item.F, self.root.dtype, item.equal_lengths and item.max_len == r)
+                key = (item.B, r, item.out_F, self.root.dtype, item.equal_lengths and item.max_len == r)
                 if group and (key != gkey or len(group) >= self.bpl):
                     yield from flush()
                 group.append((item, None))
@@ -592,7 +627,7 @@ class DecodePipeline:
             att = self._as_host_or_device(att)
             lens = None if lens is None else self._as_host_or_device(lens).to(torch.int32)
             b, r = att.shape[0], att.shape[1]
-            key = (b, r if lens is None else self._bucket(r), att.shape[2], att.dtype, lens is None)
+            key = (b, r if lens is None else self._bucket(r), self._width(att.shape[2]), att.dtype, lens is None)
             if group and (key != gkey or len(group) >= self.bpl):
                 yield from flush()
             group.append((att, lens))
@@ -625,16 +660,23 @@ class DecodePipeline:
             staged = self._stage_ragged(sl, p, group)
             for i, (att, ln) in enumerate(group):
                 if i in staged:                                  # a RaggedBatch: its rows and offsets to the slot's staging buffer, the padding made on the device
-                    srows, soffs = staged[i]
+                    srows, soffs = staged[i][:2]
                     srows.copy_(att.rows, non_blocking=True)
                     soffs.copy_(att.offsets, non_blocking=True)
+                    if len(staged[i]) == 4:                      # a BoxRaggedBatch: boxes and sizes beside them, the box launch (geometry columns, area sort, padded width)
+                        sboxes, swh = staged[i][2:]
+                        sboxes.copy_(att.boxes, non_blocking=True)
+                        swh.copy_(att.wh, non_blocking=True)
+                        hip.pack_regions_box(srows, sboxes, swh, att.wh, soffs, att.offsets, feats[i * b:(i + 1) * b], norm_att=att.norm, norm_box=att.norm_box,
+                                             att_len=lens[i * b:(i + 1) * b] if has_len else None)
+                        continue
                     hip.pack_regions(srows, soffs, att.offsets, feats[i * b:(i + 1) * b], norm=att.norm, att_len=lens[i * b:(i + 1) * b] if has_len else None)
                     continue
                 for src in (att, ln):                            # a DEVICE batch was produced on its caller's stream: the copy waits for that stream, and the caching
                     if src is not None and src.is_cuda:          # allocator must not hand the batch's memory out again while the copy is pending
                         cs.wait_stream(caller)
                         src.record_stream(cs)
-                feats[i * b:(i + 1) * b, :att.shape[1]].copy_(att, non_blocking=True)      # (a batch clipped below the bucket leaves padding rows: masked by its counts)
+                feats[i * b:(i + 1) * b, :att.shape[1], :att.shape[2]].copy_(att, non_blocking=True)      # (a batch clipped below the bucket leaves padding rows: masked by its counts; columns past an unaligned att_feat_size stay zero)
                 if has_len:
                     lens[i * b:(i + 1) * b].copy_(ln, non_blocking=True)
             sl["copied"][p].record(cs)
@@ -645,14 +687,16 @@ class DecodePipeline:
             sl["done"].record(st)
 
     def _stage_ragged(self, sl, p, group):
-        """Device views {item index: (rows, offsets)} for the RaggedBatch items of ``group``, carved out of slot ``sl``'s staging buffers of parity ``p`` (grown,
+        """Device views {item index: (rows, offsets)} -- (rows, offsets, boxes, wh) for a BoxRaggedBatch -- for the RaggedBatch items of ``group``, carved out of slot ``sl``'s staging buffers of parity ``p`` (grown,
         never shrunk; created and reused on the copy stream alone, so the stream orders every use)."""
-        from .features import RaggedBatch
+        from .features import BoxRaggedBatch, RaggedBatch
         items = [(i, g[0]) for i, g in enumerate(group) if isinstance(g[0], RaggedBatch)]
         if not items:
             return {}
-        need = sum(it.rows.numel() * it.rows.element_size() for _, it in items)      # (every item's bytes are a multiple of 16: F % 8 == 0 is checked by the kernel's wrapper)
-        need_off = sum(it.B + 1 for _, it in items)
+        boxed = lambda it: isinstance(it, BoxRaggedBatch)
+        # (every item's bytes are a multiple of 16: F % 8 == 0 is checked by the kernel's wrapper, and a box is 16 bytes)
+        need = sum(it.rows.numel() * it.rows.element_size() + (it.boxes.numel() * 4 if boxed(it) else 0) for _, it in items)
+        need_off = sum(it.B + 1 + (2 * it.B if boxed(it) else 0) for _, it in items)
         stage = sl.setdefault("stage", [None, None])
         if stage[p] is None or stage[p][0].numel() < need or stage[p][1].numel() < need_off:
             old = stage[p]
@@ -664,6 +708,10 @@ class DecodePipeline:
             n = it.rows.numel() * it.rows.element_size()
             views[i] = (raw[o:o + n].view(it.rows.dtype).view(it.rows.shape), offs[q:q + it.B + 1])
             o, q = o + n, q + it.B + 1
+            if boxed(it):
+                nb = it.boxes.numel() * 4
+                views[i] += (raw[o:o + nb].view(torch.float32).view(it.boxes.shape), offs[q:q + 2 * it.B].view(it.B, 2))
+                o, q = o + nb, q + 2 * it.B
         return views
 
     def _decode_and_copy_out(self, sl):

@@ -6,7 +6,9 @@ loss, one greedy caption per image, and the language scores that need no Java (b
 
 ``feats``: region features [N, R, F] (array or tensor on the host), or a REGION SOURCE -- an object with ``__len__`` and ``ragged(i0, i1)`` -> a
 ``features.RaggedBatch`` of images i0 .. i1 - 1 (``features.RegionSource``: per-image feature files of 10..100 regions): every batch is then staged ragged
-and padded to its longest image on the device, with the loader's mask (None when the batch's images have equal counts).  ``store_or_gts``: a label source with ``batch(image_ixs, seq_per_img, rng)``
+and padded to its longest image on the device, with the loader's mask (None when the batch's images have equal counts).  A source built with a box store
+(the loader's use_box: ``RegionSource(store, ids, box_store=..., sizes=...)``) hands over ``BoxRaggedBatch``es -- geometry columns, area sort and the padded
+width come from the same launch; such a model is decode-only, so ``verbose_loss`` must be 0.  ``store_or_gts``: a label source with ``batch(image_ixs, seq_per_img, rng)``
 and ``gts(ix)`` (``data.LabelStore``, ``SyntheticLabels``) -- the loss is computed and the references come from it --, or the per-image
 references alone (integer rows or id strings; no loss then), or None.  ``eval_kwargs``:
 
@@ -89,6 +91,9 @@ def validation_loss(model, feats, store, batch_size: int, seq_per_img: int, imag
     """The loss of eval_split (verbose_loss, eval_utils.py:440-453) as a pass of its own: (sum of the batches' LanguageModelCriterion_UIC losses,
     number of batches).  Image i of ``feats`` is image ``image_ixs[i]`` (default i) of ``store``."""
     from .loss_wrapper import LanguageModelCriterion_UIC
+    if model.cfg.att_feat_padded != model.cfg.att_feat_size:
+        raise NotImplementedError(f"the validation loss runs mode='forward', which is not built for att_feat_size = {model.cfg.att_feat_size} (box features "
+                                  "are decode-only): pass verbose_loss = 0")
     crit, rng, loss_sum, loss_evals = LanguageModelCriterion_UIC(), np.random.default_rng(0), 0.0, 0
     with torch.no_grad():
         for i in range(0, len(feats), batch_size):

@@ -12,7 +12,15 @@ zero padding to [B, R, F], the conversion to the compute dtype, the region count
 
 ``RegionStore`` reads what needs nothing beyond numpy and torch: a directory of ``<id>.npz`` / ``<id>.npy`` and a ``.pth`` dictionary.  ``.h5`` and
 ``.lmdb`` sources are accepted when ``h5py`` / ``lmdbdict`` import; neither module was available where this was written, so THOSE TWO BRANCHES ARE
-UNTESTED.  Box features (``use_box``: F = 2053) are not read: the engine needs F % 64 == 0.
+UNTESTED.
+
+Box features (the loader's ``use_box``, dataloader.py:477-487; ``att_feat_size`` 2053): the boxes come from a second ``RegionStore`` (``input_box_dir``,
+``<id>.npy`` of [r, 4] = x1, y1, x2, y2) and the images' sizes from ``ImageIndex.sizes``; a ``BoxRaggedBatch`` stages them beside the rows, and ONE launch
+(``bofi_pack_regions_box``) appends x1/w, y1/h, x2/w, y2/h, area/(w h) -- L2-normalised with ``norm_box_feat`` --, sorts every image's regions by box area,
+largest first, and pads the width to the engine's ``att_feat_padded`` (2112):
+
+    boxes = RegionStore("data/cocobu_box", ".npy")
+    source = RegionSource(store, ids, box_store=boxes, sizes=index.sizes(ixs), norm_box_feat=False)      # source.ragged(i0, i1) -> BoxRaggedBatch
 """
 from __future__ import annotations
 
@@ -136,6 +144,17 @@ class ImageIndex:
         """The store keys (``str(id)``, dataloader.py:472) of images ``ixs``."""
         return [str(self.ids[int(i)]) for i in ixs]
 
+    def sizes(self, ixs: Sequence[int]) -> np.ndarray:
+        """int32 [n, 2] = (width, height) of images ``ixs`` (dataloader.py:481: the divisors of the box features)."""
+        out = np.empty((len(ixs), 2), np.int32)
+        for n, i in enumerate(ixs):
+            img = self.images[int(i)]
+            for c, name in enumerate(("width", "height")):
+                if name not in img:
+                    raise KeyError(f"image {img['id']!r} of the json has no {name!r}: box features are divided by the image's width and height")
+                out[n, c] = int(img[name])
+        return out
+
 
 def _pinned(shape, dtype):
     return torch.empty(shape, dtype=dtype, pin_memory=torch.cuda.is_available())
@@ -181,6 +200,11 @@ class RaggedBatch:
     def equal_lengths(self) -> bool:
         return self.max_len == self.min_len
 
+    @property
+    def out_F(self) -> int:
+        """Columns of the device launch's output (``F``; a ``BoxRaggedBatch`` widens it)."""
+        return self.F
+
     def lengths(self) -> np.ndarray:
         return np.diff(self.offsets.numpy())
 
@@ -189,7 +213,6 @@ class RaggedBatch:
         """One asynchronous copy of ``rows``, one of ``offsets`` and one ``bofi_pack_regions`` launch on ``stream`` (default: the current one); no
         synchronisation.  Returns (feats [B, out_R, F] in ``out_dtype`` -- ``out`` itself when given --, att_len int32 [B]); ``att_len`` is None when
         every image has ``out_R`` regions, as the loader returns ``att_masks=None`` then.  ``out_R`` defaults to the longest image; ``norm`` to the batch's."""
-        from . import hip
         if out is not None:
             out_R, out_dtype, device = out.size(1), out.dtype, out.device
         out_R = self.max_len if out_R is None else int(out_R)
@@ -200,10 +223,62 @@ class RaggedBatch:
             offsets = torch.empty(self.B + 1, dtype=torch.int32, device=dev)
             offsets.copy_(self.offsets, non_blocking=True)
             if out is None:
-                out = torch.empty(self.B, out_R, self.F, dtype=out_dtype, device=dev)
+                out = torch.empty(self.B, out_R, self.out_F, dtype=out_dtype, device=dev)
             att_len = torch.empty(self.B, dtype=torch.int32, device=dev)
-            hip.pack_regions(rows, offsets, self.offsets, out, norm=self.norm if norm is None else norm, att_len=att_len)
+            self.pack(rows, offsets, out, self.norm if norm is None else norm, att_len, dev)
         return out, (None if self.equal_lengths and self.max_len == out_R else att_len)
+
+    def pack(self, rows, offsets, out, norm, att_len, dev):
+        """The device launch on the current stream: ``rows`` / ``offsets`` are the device copies of this batch's arrays."""
+        from . import hip
+        hip.pack_regions(rows, offsets, self.offsets, out, norm=norm, att_len=att_len)
+
+
+class BoxRaggedBatch(RaggedBatch):
+    """A batch of the loader's use_box mode (dataloader.py:477-487): besides ``rows`` [sum len, F] and ``offsets`` it carries ``boxes`` (pinned float32
+    [sum len, 4]: x1, y1, x2, y2 in pixels, one per row) and ``wh`` (host int32 [B, 2]: width, height).  The device launch (``bofi_pack_regions_box``)
+    appends the five geometry columns -- L2-normalised when ``norm_box`` --, sorts every image's rows by box area, largest first, and pads the width to
+    ``F_out`` (default: F + 5 rounded up to 64 -- the engine's ``att_feat_padded``: 2112 for 2048 + 5), so ``to_device`` returns [B, out_R, F_out]."""
+
+    def __init__(self, rows, offsets, boxes, wh, norm: bool = False, norm_box: bool = False, F_out: Optional[int] = None):
+        super().__init__(rows, offsets, norm)
+        if boxes.dtype != torch.float32 or boxes.dim() != 2 or tuple(boxes.shape) != (rows.size(0), 4):
+            raise ValueError(f"boxes must be float32 [{rows.size(0)}, 4], one (x1, y1, x2, y2) per region row; got {boxes.dtype} {tuple(boxes.shape)}")
+        if wh.dtype != torch.int32 or tuple(wh.shape) != (self.B, 2):
+            raise ValueError(f"wh must be int32 [{self.B}, 2] (width, height), one per image")
+        if int(wh.min()) < 1:
+            raise ValueError("every image's width and height must be >= 1")
+        self.boxes, self.wh, self.norm_box = boxes, wh, bool(norm_box)
+        self.F_out = -(-(self.F + 5) // 64) * 64 if F_out is None else int(F_out)
+        if self.F_out % 8 != 0 or self.F_out < self.F + 5:
+            raise ValueError(f"F_out = {self.F_out}: a multiple of 8 that is at least F + 5 = {self.F + 5} expected")
+
+    @classmethod
+    def from_arrays(cls, arrays, boxes, sizes, norm: bool = False, norm_box: bool = False, F_out: Optional[int] = None) -> "BoxRaggedBatch":
+        """Images' region arrays [r_i, F], their boxes [r_i, 4] (cast to float32) and ``sizes`` [B, 2] = (width, height) -> one staged batch."""
+        base = RaggedBatch.from_arrays(arrays, norm)
+        if len(boxes) != len(arrays) or any(np.ndim(q) != 2 or q.shape != (a.shape[0], 4) for q, a in zip(boxes, arrays)):
+            raise ValueError("every image needs boxes [r, 4], one (x1, y1, x2, y2) per region row")
+        staged = _pinned((base.rows.size(0), 4), torch.float32)
+        view, o = staged.numpy(), 0
+        for q in boxes:
+            view[o:o + q.shape[0]] = q
+            o += q.shape[0]
+        wh = _pinned((base.B, 2), torch.int32)
+        wh.numpy()[:] = np.asarray(sizes, np.int32).reshape(base.B, 2)
+        return cls(base.rows, base.offsets, staged, wh, norm, norm_box, F_out)
+
+    @property
+    def out_F(self) -> int:
+        return self.F_out
+
+    def pack(self, rows, offsets, out, norm, att_len, dev):
+        from . import hip
+        boxes = torch.empty(self.boxes.shape, dtype=torch.float32, device=dev)
+        boxes.copy_(self.boxes, non_blocking=True)
+        wh = torch.empty(self.B, 2, dtype=torch.int32, device=dev)
+        wh.copy_(self.wh, non_blocking=True)
+        hip.pack_regions_box(rows, boxes, wh, self.wh, offsets, self.offsets, out, norm_att=norm, norm_box=self.norm_box, att_len=att_len)
 
 
 def att_masks_of(att_len: Optional[torch.Tensor], R: int):
@@ -214,16 +289,37 @@ def att_masks_of(att_len: Optional[torch.Tensor], R: int):
 
 
 class RegionSource:
-    """The images ``ids`` of ``store`` as ``eval_utils.eval_split`` and ``DecodePipeline`` read them: ``len()`` and ``ragged(i0, i1)``."""
+    """The images ``ids`` of ``store`` as ``eval_utils.eval_split`` and ``DecodePipeline`` read them: ``len()`` and ``ragged(i0, i1)``.  ``box_store`` and
+    ``sizes`` (int32 [len(ids), 2], ``ImageIndex.sizes``): the loader's use_box mode -- ``ragged`` then returns ``BoxRaggedBatch``es."""
 
-    def __init__(self, store: RegionStore, ids: Sequence, norm_att_feat: bool = False):
+    def __init__(self, store: RegionStore, ids: Sequence, norm_att_feat: bool = False, box_store: Optional[RegionStore] = None, sizes=None, norm_box_feat: bool = False):
         self.store, self.keys, self.norm = store, [str(i) for i in ids], bool(norm_att_feat)
+        self.box_store, self.norm_box = box_store, bool(norm_box_feat)
+        self.sizes = _checked_sizes(box_store, sizes, len(self.keys))
 
     def __len__(self):
         return len(self.keys)
 
     def ragged(self, i0: int, i1: int) -> RaggedBatch:
-        return RaggedBatch.from_arrays([self.store.get(k) for k in self.keys[i0:i1]], self.norm)
+        return _stage(self.store, self.keys[i0:i1], self.norm, self.box_store, None if self.sizes is None else self.sizes[i0:i1], self.norm_box)
+
+
+def _checked_sizes(box_store, sizes, n):
+    if box_store is None:
+        return None
+    if sizes is None:
+        raise ValueError("box features need the images' sizes: sizes = ImageIndex.sizes(ixs)")
+    sizes = np.ascontiguousarray(sizes, np.int32)
+    if n is not None and sizes.shape != (n, 2):
+        raise ValueError(f"sizes must be int32 [{n}, 2] (width, height), one row per image; got {sizes.shape}")
+    return sizes
+
+
+def _stage(store, keys, norm, box_store=None, sizes=None, norm_box=False):
+    arrays = [store.get(k) for k in keys]
+    if box_store is None:
+        return RaggedBatch.from_arrays(arrays, norm)
+    return BoxRaggedBatch.from_arrays(arrays, [box_store.get(k).astype(np.float32, copy=False) for k in keys], sizes, norm, norm_box)
 
 
 class RegionFeeder:
@@ -231,15 +327,21 @@ class RegionFeeder:
     lazily -- and stage ``RaggedBatch``es up to ``ahead`` batches before the consumer.  Iterating yields the batches in input order.  The threads
     read files and fill host memory; they enqueue nothing on the device, and no further process is started.  They do call into the HIP runtime in one way:
     a batch's pinned memory comes from torch's caching host allocator, so the first batch of each size is a (slow) page-locking allocation made on a
-    worker thread; later batches reuse the cached blocks."""
+    worker thread; later batches reuse the cached blocks.  ``box_store`` and ``sizes`` -- a mapping from store key to (width, height) -- : the loader's
+    use_box mode, the batches are ``BoxRaggedBatch``es."""
 
-    def __init__(self, store: RegionStore, index_batches: Iterable[Sequence], workers: int = 4, ahead: Optional[int] = None, norm_att_feat: bool = False):
+    def __init__(self, store: RegionStore, index_batches: Iterable[Sequence], workers: int = 4, ahead: Optional[int] = None, norm_att_feat: bool = False,
+                 box_store: Optional[RegionStore] = None, sizes=None, norm_box_feat: bool = False):
         self.store, self.batches, self.norm = store, index_batches, bool(norm_att_feat)
+        self.box_store, self.sizes, self.norm_box = box_store, sizes, bool(norm_box_feat)
+        if box_store is not None and sizes is None:
+            raise ValueError("box features need the images' sizes: sizes = {store key: (width, height)}")
         self.workers = max(1, min(int(workers), MAX_WORKERS))
         self.ahead = max(1, int(ahead)) if ahead is not None else self.workers + 1
 
     def _stage(self, keys):
-        return RaggedBatch.from_arrays([self.store.get(k) for k in keys], self.norm)
+        sizes = None if self.box_store is None else np.array([self.sizes[k] for k in keys], np.int32).reshape(len(keys), 2)
+        return _stage(self.store, keys, self.norm, self.box_store, sizes, self.norm_box)
 
     def __iter__(self):
         pool = ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix="region-feeder")

@@ -128,6 +128,7 @@ SIGNATURES = {
     "bofi_diversity_score": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, C.c_double, _P, _I64, _P, _P, _P, _P, _P]),
     "bofi_oracle_stats": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "bofi_pack_regions": (_I, [_P, _I, _P, _P, _I, _I, _P, _I, _I, _I, _P, _P]),
+    "bofi_pack_regions_box": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
     "bofi_mask_predict_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "bofi_attn_maps": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_float, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
     "bofi_caption_trim": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
@@ -223,6 +224,36 @@ def pack_regions(rows, offsets, offsets_host, out, *, norm=False, att_len=None):
         raise BofiHipError("pack_regions: att_len must be int32 [B] on the device")
     check(lib().bofi_pack_regions(ptr(rows), codes[rows.dtype], ptr(offsets), ptr(offsets_host), B, rows.size(1), ptr(out), dtype_code(out), out.size(1),
                                   1 if norm else 0, ptr(att_len), stream_ptr()), "bofi_pack_regions")
+
+
+def pack_regions_box(rows, boxes, wh, wh_host, offsets, offsets_host, out, *, norm_att=False, norm_box=False, att_len=None):
+    """``bofi_pack_regions_box`` on torch tensors: rows [sum len, F_att] float32 / float16 / bfloat16, boxes float32 [sum len, 4], wh int32 [B, 2] and offsets
+    int32 [B + 1] on the device, wh_host / offsets_host the host's int32 copies (checked before the launch) or None, out [B, out_R, F_out] float32 / bfloat16
+    contiguous with F_out >= F_att + 5, att_len int32 [B] or None.  One launch on the current stream, no synchronisation."""
+    import torch
+    codes = {torch.float32: DT_F32, torch.bfloat16: DT_BF16, torch.float16: DT_F16}
+    if rows.dtype not in codes or out.dtype not in (torch.float32, torch.bfloat16):
+        raise BofiHipError(f"pack_regions_box: rows {rows.dtype} -> out {out.dtype} is not a supported pair")
+    if rows.dim() != 2 or out.dim() != 3 or not rows.is_contiguous() or not out.is_contiguous() or not rows.is_cuda or not out.is_cuda:
+        raise BofiHipError("pack_regions_box: contiguous device tensors rows [n, F_att] and out [B, out_R, F_out] expected")
+    if boxes.dtype != torch.float32 or boxes.dim() != 2 or boxes.size(1) != 4 or boxes.size(0) != rows.size(0) or not boxes.is_cuda or not boxes.is_contiguous():
+        raise BofiHipError(f"pack_regions_box: boxes must be float32 [{rows.size(0)}, 4] on the device, one box per row")
+    B = out.size(0)
+    if wh.dtype != torch.int32 or tuple(wh.shape) != (B, 2) or not wh.is_cuda or not wh.is_contiguous():
+        raise BofiHipError("pack_regions_box: wh must be int32 [B, 2] on the device")
+    if wh_host is not None and (wh_host.dtype != torch.int32 or tuple(wh_host.shape) != (B, 2) or wh_host.is_cuda or not wh_host.is_contiguous()):
+        raise BofiHipError("pack_regions_box: wh_host must be int32 [B, 2] on the host")
+    if offsets.dtype != torch.int32 or offsets.numel() != B + 1 or not offsets.is_cuda or not offsets.is_contiguous():
+        raise BofiHipError("pack_regions_box: offsets must be int32 [B + 1] on the device")
+    if offsets_host is not None and (offsets_host.dtype != torch.int32 or offsets_host.numel() != B + 1 or offsets_host.is_cuda or not offsets_host.is_contiguous()):
+        raise BofiHipError("pack_regions_box: offsets_host must be int32 [B + 1] on the host")
+    if offsets_host is not None and int(offsets_host[B]) > rows.size(0):
+        raise BofiHipError(f"pack_regions_box: the offsets name {int(offsets_host[B])} rows, rows holds {rows.size(0)}")
+    if att_len is not None and (att_len.dtype != torch.int32 or att_len.numel() != B or not att_len.is_cuda or not att_len.is_contiguous()):
+        raise BofiHipError("pack_regions_box: att_len must be int32 [B] on the device")
+    check(lib().bofi_pack_regions_box(ptr(rows), codes[rows.dtype], ptr(boxes), ptr(wh), ptr(wh_host), ptr(offsets), ptr(offsets_host), B, rows.size(1), ptr(out),
+                                      dtype_code(out), out.size(1), out.size(2), 1 if norm_att else 0, 1 if norm_box else 0, ptr(att_len), stream_ptr()),
+          "bofi_pack_regions_box")
 
 
 def attn_maps(q, k, B, H, Lq, Lk, *, scale=0.125, klen=None, qlen=None, qlen_bias=0, mean=None, heads=None, K=0, top_idx=None, top_w=None):

@@ -132,6 +132,8 @@ class TransformerModel(nn.Module):
     def _as_input(self, att_feats):
         if att_feats.dtype not in (torch.float32, self.compute_dtype):
             att_feats = att_feats.float()
+        if att_feats.size(-1) != self.cfg.att_feat_padded:       # an att_feat_size that is no multiple of 64 (use_box: 2053): the engine runs at the padded width
+            att_feats = self.engine().pad_feats(att_feats)
         return att_feats.contiguous()
 
     def _decode_saic_graphed(self, eng, feats, lens, raw_logits, sample, cap=None):

@@ -706,6 +706,28 @@ int bofi_oracle_stats(const int* comps, const double* cider, const double* rouge
 int bofi_pack_regions(const void* rows, int rows_dtype, const int* offsets, const int* offsets_host, int B, int F, void* out, int out_dtype,
                       int out_R, int norm, int* att_len, void* stream);
 
+/* bofi_pack_regions for the loader's use_box mode (dataloader.py:477-487): behind an image's F_att attention columns stand five geometry columns
+ * of its boxes, and the image's rows are sorted by the last of them, largest first.  One launch, no synchronisation.
+ *   rows, rows_dtype, offsets, offsets_host, att_len: as bofi_pack_regions, with F_att (a multiple of 8) columns
+ *   boxes: float32 [offsets[B], 4] = (x1, y1, x2, y2) in pixels, ragged by the same offsets, 16-byte aligned
+ *   wh: int32 [B, 2] = (width, height) on the device; wh_host: the host's copy of it or NULL
+ *   out: out_dtype [B, out_R, F_out] contiguous, 1 <= out_R <= 1024, F_out % 8 == 0 and F_out >= F_att + 5 (2112 for 2048 + 5)
+ * A real row of image b holds, in float32 before out_dtype's rounding:
+ *   columns 0 .. F_att - 1: what bofi_pack_regions writes (norm_att = its norm);
+ *   columns F_att .. F_att + 4: x1 / w, y1 / h, x2 / w, y2 / h, ((x2 - x1) * (y2 - y1)) / (float)((int64)w * h) -- one correctly rounded float32 operation
+ *     each, in that order -- and with norm_box = 1 each of the five divided by sqrtf(((((c0^2 + c1^2) + c2^2) + c3^2) + c4^2)), every square and every
+ *     sum rounded on its own (no fma, no reciprocal): numpy's float32 arithmetic for the loader's expressions;
+ *   columns F_att + 5 .. F_out - 1: +0.0.
+ * Order: source row i goes to row rank_i = #{j : key_j > key_i} + #{j < i : key_j == key_i}, key = the float32 value of the last box column (after
+ * norm_box, never rounded to out_dtype): descending and stable, Python's sorted(..., reverse=True).  A NaN key ranks after every number, NaNs among
+ * themselves in source order.  The ranks of an image are a permutation of 0 .. len_b - 1; rows len_b .. out_R - 1 are +0.0: EVERY element of out is
+ * written exactly once.  Deterministic (no atomics).  BOFI_ERR_ARG with a message, nothing launched: a NULL among rows / boxes / wh / offsets / out,
+ * misalignment, an unknown dtype, B < 1, F_att % 8 != 0, a bad F_out, out_R outside 1..1024, and -- on the host copies, when given -- bad offsets
+ * (as bofi_pack_regions) or a width or height < 1.  The kernel clamps len_b to [0, out_R] and every rank to len_b - 1, so it never writes outside out. */
+int bofi_pack_regions_box(const void* rows, int rows_dtype, const float* boxes, const int* wh, const int* wh_host, const int* offsets,
+                          const int* offsets_host, int B, int F_att, void* out, int out_dtype, int out_R, int F_out, int norm_att, int norm_box,
+                          int* att_len, void* stream);
+
 /* The step between two passes of a mask-predict refinement (BOFI_FLAG_MASK_PREDICT states the rules), on given arrays; all buffers [B, S], S <= 64.
  *   ids int64, chosen / plogp float32, round int32: the state (y, c, e, emitted_round), read and written.
  *   fresh_ids / fresh_chosen / fresh_plogp: what pass t left (ids after the pad-tail rule, the log-prob of each id, sum_v p log p).

@@ -10,7 +10,9 @@ path this repository implements: greedy NAIC bound+fill decoding of precomputed 
 [--num_images N] [--norm_att_feat 1]`` -- are the reference's per-image feature files (``<id>.npz`` / ``<id>.npy`` of 10..100 regions each, a ``.pth``
 dictionary; boficap_amd.features): the images and their ids are the json's split, every batch is staged ragged by ``--feeder_workers`` reader threads and
 padded on the device, ``image_id`` in the predictions is the json's id, and image i of the split uses image ``split_ix[i]`` of ``--input_label_npz``.
-Box features (``--use_box 1``) are refused: they make F = 2053 and the engine needs F % 64 == 0.  ``--language_eval 1`` (with ``--input_label_npz``: the references) adds the language scores that need no Java -- BLEU-1..4,
+Box features: ``--use_box 1 --input_box_dir D [--input_box_ext .npy] [--norm_box_feat 1]`` reads ``<id>.npy`` boxes [r, 4] = (x1, y1, x2, y2) and the json's
+``width`` / ``height``; the five geometry columns, the sort by box area and the zero-padding of F = 2053 to the engine's 2112 are the same device launch
+(the model's ``att_feat_size`` must be 2053; no validation loss: ``mode='forward'`` is not built for that width).  ``--language_eval 1`` (with ``--input_label_npz``: the references) adds the language scores that need no Java -- BLEU-1..4,
 ROUGE-L, CIDEr on the device (boficap_amd.lang_eval) -- as a printed line and, in ``--dump_json``, under a top-level key.
 ``--attn_topk K`` (NAIC) adds 'regions' to every prediction: per emitted word the K image regions its position attended to most, as [region, weight] pairs.
 ``--refine_rounds N [--refine_method feed_back|mask_predict]`` (NAIC) adds N filling passes: on all of the previous ids, or -- mask-predict -- on the least
@@ -50,7 +52,11 @@ def main():
     ap.add_argument("--split", default="val", choices=["val", "test", "train"])
     ap.add_argument("--num_images", type=int, default=-1, help="the first N images of the split (-1: all)")
     ap.add_argument("--norm_att_feat", type=int, default=0, choices=[0, 1], help="1: every region divided by its L2 norm (dataloader.py:475-476), on the device")
-    ap.add_argument("--use_box", type=int, default=0, choices=[0, 1], help="refused: box features make F = 2053 and the engine needs F %% 64 == 0")
+    ap.add_argument("--use_box", type=int, default=0, choices=[0, 1], help="1 (with --input_att_dir and --input_box_dir): five box-geometry columns behind the 2048 region "
+                    "features and every image's regions sorted by box area (dataloader.py:477-487), on the device; the model's att_feat_size is 2053")
+    ap.add_argument("--input_box_dir", default="", help="the reference's input_box_dir: <id>.npy (or .npz) of [regions, 4] = x1, y1, x2, y2 in pixels; the json needs width and height")
+    ap.add_argument("--input_box_ext", default=".npy", choices=[".npz", ".npy"], help="file type of the box directory")
+    ap.add_argument("--norm_box_feat", type=int, default=0, choices=[0, 1], help="1: the five box columns divided by their L2 norm (dataloader.py:483-484), on the device")
     ap.add_argument("--in_memory", type=int, default=0, choices=[0, 1], help="1: every feature file is read once before the decode and served from memory")
     ap.add_argument("--feeder_workers", type=int, default=4, help="reader threads of the feature files (at most 16)")
     ap.add_argument("--synthetic", type=int, default=64)
@@ -103,8 +109,10 @@ def main():
         refine["attn_topk"] = args.attn_topk
     if args.language_eval and not args.input_label_npz:
         ap.error("--language_eval 1 needs the references: --input_label_npz")
-    if args.use_box:
-        ap.error("--use_box 1 is not supported: box features make F = 2053 and the engine needs F % 64 == 0")
+    if args.use_box and not (args.input_box_dir and args.input_att_dir):
+        ap.error("--use_box 1 makes F = 2053 from the boxes of the images' regions: it needs --input_box_dir (and --input_att_dir, --input_json with width and height)")
+    if (args.input_box_dir or args.norm_box_feat) and not args.use_box:
+        ap.error("--input_box_dir / --norm_box_feat are read with --use_box 1 only")
     if args.input_att_dir and not args.input_json:
         ap.error("--input_att_dir needs the images' ids and splits: --input_json")
     if args.input_att_dir and args.input_att_npy:
@@ -126,13 +134,6 @@ def main():
         opt = FULL.to_opt()
     opt.bofi_compute_dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     opt.bofi_max_batch = args.batch_size
-    model = models.setup(opt)
-    if args.model:
-        model.load_state_dict(torch.load(args.model, map_location="cpu"), strict=True)
-    else:
-        model.load_state_dict({k: torch.from_numpy(v) for k, v in W.make_state_dict(model.cfg, 0).items()}, strict=True)
-    model.cuda().eval()
-
     image_ixs, image_ids, att_store = None, None, None
     if args.input_att_dir:
         from boficap_amd.features import ImageIndex, RegionFeeder, RegionSource, RegionStore
@@ -142,13 +143,32 @@ def main():
             raise SystemExit(f"{args.input_json} assigns no image to split {args.split!r}")
         image_ids = [index.ids[i] for i in image_ixs]
         att_store = RegionStore(args.input_att_dir, args.input_att_ext, in_memory=bool(args.in_memory))
-        feats = RegionSource(att_store, image_ids, bool(args.norm_att_feat))
+        box_store, sizes = None, None
+        if args.use_box:
+            box_store = RegionStore(args.input_box_dir, args.input_box_ext, in_memory=bool(args.in_memory))
+            sizes = index.sizes(image_ixs)
+        box_kw = dict(box_store=box_store, norm_box_feat=bool(args.norm_box_feat))
+        feats = RegionSource(att_store, image_ids, bool(args.norm_att_feat), sizes=sizes, **box_kw)
         if args.in_memory:
             for k in feats.keys:
                 att_store.get(k)
-    elif args.input_att_npy:
+                if box_store is not None:
+                    box_store.get(k)
+        # the width the files make against the width the model was built for (the reference's files: 2048 + 5 x use_box), before anything is loaded
+        file_F = int(att_store.get(feats.keys[0]).shape[1])
+        if int(opt.att_feat_size) != file_F + 5 * args.use_box:
+            ap.error(f"the model's att_feat_size is {int(opt.att_feat_size)}, but the region files hold {file_F} columns and --use_box {args.use_box} makes "
+                     f"features of {file_F + 5 * args.use_box}: a model trained with use_box {1 - args.use_box}?")
+    model = models.setup(opt)
+    if args.model:
+        model.load_state_dict(torch.load(args.model, map_location="cpu"), strict=True)
+    else:
+        model.load_state_dict({k: torch.from_numpy(v) for k, v in W.make_state_dict(model.cfg, 0).items()}, strict=True)
+    model.cuda().eval()
+
+    if args.input_att_npy:
         feats = np.load(args.input_att_npy)
-    else:                                                        # (2 048 distinct synthetic images, repeated: the generator is a CPU loop)
+    elif not args.input_att_dir:                                 # (2 048 distinct synthetic images, repeated: the generator is a CPU loop)
         uniq = W.synthetic_att_feats(min(args.synthetic, 2048), 36, model.cfg.att_feat_size, seed=1235)
         feats = uniq if args.synthetic <= 2048 else np.concatenate([uniq] * (-(-args.synthetic // 2048)))[:args.synthetic]
     store = None
@@ -158,6 +178,7 @@ def main():
         src = args.input_label_npz if args.input_label_npz.endswith((".h5", ".hdf5")) else dict(np.load(args.input_label_npz))
         store = LabelStore(src, pad_idx=c.pad_idx, bos_idx=c.bos_idx, eos_idx=c.eos_idx, len_idx=c.len_idx)
     results, seconds, rows, stats = [], 0.0, [], ([], [])
+    store_loss = store is not None and not args.use_box          # (mode='forward' is not built for F = 2053: box features are decode-only)
     surface, bad_flags = None, []
     if args.remove_bad_endings or args.surface_stats:
         from boficap_amd.surface import CaptionSurface, TrainSentences, sentence_stats
@@ -181,14 +202,15 @@ def main():
         return eval_utils.entry_of(i, k, seq, pn, pl, ent, ppl, vocab)
 
     with torch.no_grad():
-        if store is not None:                                    # the loss of eval_split (verbose_loss), eval_utils.py:440-453: a pass of its own
+        if store_loss:                   # the loss of eval_split (verbose_loss), eval_utils.py:440-453: a pass of its own
             loss_sum, loss_evals = eval_utils.validation_loss(model, feats, store, args.batch_size, args.seq_per_img, image_ixs)
         if args.pipeline and args.inference_mode == "NAIC" and att_store is not None:
             # the feature files are read and staged ragged by the feeder's threads INSIDE the clock, ahead of the launches; padding and cast happen on the device
             key_batches = [feats.keys[i:i + args.batch_size] for i in range(0, len(feats), args.batch_size)]
 
             def feeder(kb):
-                return RegionFeeder(att_store, kb, workers=args.feeder_workers, norm_att_feat=bool(args.norm_att_feat))
+                return RegionFeeder(att_store, kb, workers=args.feeder_workers, norm_att_feat=bool(args.norm_att_feat),
+                                    sizes=None if sizes is None else {k: wh for k, wh in zip(feats.keys, sizes)}, **box_kw)
             for _ in model.decode_many(feeder(key_batches[:2 * args.in_flight * args.batches_per_launch]), batches_per_launch=args.batches_per_launch, in_flight=args.in_flight,
                                        fused_vocab=args.fused_vocab, **refine):
                 pass                                             # graph captures and stream choice, outside the clock
@@ -249,7 +271,7 @@ def main():
         for e, iid in zip(results, image_ids):
             e["image_id"] = iid
     print(f"decoded {len(results)} images in {seconds:.4f} s ({len(results) / max(seconds, 1e-9):.1f} images/s; {how})")
-    if store is not None:
+    if store_loss:
         print(f"validation loss {loss_sum / max(1, loss_evals):.4f} over {loss_evals} batches (LanguageModelCriterion_UIC)")
     lang_stats = None
     if args.language_eval:
