@@ -855,7 +855,8 @@ __global__ __launch_bounds__(256) void vocab_sample_kernel(const float* __restri
         for (int i = tid; i < V; i += 256) {
             float lp = x[i];
             if (lp != lp) lp = -10.f;
-            const float u = ((float)hash64_hi(seed, base + i) + 0.5f) * (1.0f / 4294967296.0f);
+            // u in (0, 1): the conversion rounds every hash >= 0xFFFFFF80 to 2^32, which without the bound is u == 1 and a Gumbel value of +inf
+            const float u = fminf(((float)hash64_hi(seed, base + i) + 0.5f) * (1.0f / 4294967296.0f), 0x1.fffffep-1f);
             const float gv = lp * inv_temp - logf(-logf(u));
             if (gv > bv) { bv = gv; bi = i; }
         }

@@ -256,7 +256,9 @@ int bofi_relu_bwd(const float* y, const float* dy, float* dx, int64_t n, void* s
  * perplexity (captioning/utils/eval_utils.py:463-464) without reading the distribution back in user code. */
 int bofi_vocab_stats(const float* logp, const int64_t* seq, int rows, int V, float* row_plogp, float* row_chosen, void* stream);
 /* n draws per row from Categorical(logits = logp / temperature) (sample_next_word, CaptionModel.py:405-425; NaN counts as
- * -10): Gumbel-max with a counter-hash uniform.  out int64 [(rows / S) * n, S], draw c of image b in row b * n + c
+ * -10): Gumbel-max with a counter-hash uniform strictly inside (0, 1) -- element i of draw c of row r uses counter
+ * (r * n + c) * V + i of stream `seed`; the rule is written out in DESIGN.md section 5 and restated in
+ * tests/counter_streams.py.  out int64 [(rows / S) * n, S], draw c of image b in row b * n + c
  * (the reference repeats each image n times, models/utils.py:3-14); positions >= ntok[b] get pad_idx (AttModel.py:422-423). */
 int bofi_vocab_sample(const float* logp, int rows, int V, int S, int n, float temperature, uint64_t seed, const int* ntok,
                       int pad_idx, int64_t* out, void* stream);

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import boficap_oracle as O
+import counter_streams as cs
 from conftest import load_golden
 
 pytestmark = pytest.mark.gpu
@@ -129,6 +130,9 @@ def test_attention_probability_dropout_bf16():
         rate = float(keep[valid].float().mean())
         assert abs(rate - (1 - p)) < 0.05, rate
         assert torch.allclose(Pd[valid & keep], P0[valid & keep] / (1 - p), rtol=3e-2, atol=2e-3)
+        # the recovered mask is the documented one: element ((b * H + h) * Lq + q) * Lk + k of stream `seed` (tests/counter_streams.py)
+        kept = torch.from_numpy(cs.keep_mask(seed, 0, p, cs.attn_ids_padded(B, H, L, L))).permute(0, 2, 1, 3)      # [b, q, h, k]
+        assert int(valid.sum()) > B * H * L and torch.equal(keep[valid], kept[valid])
         mask = torch.where(keep, torch.tensor(1 / (1 - p)), torch.tensor(0.0)).permute(0, 2, 1, 3)      # [b, h, q, k]
         # full forward / backward with that mask in float64-ish torch
         xr = bf(qkv).clone().requires_grad_()
@@ -180,6 +184,17 @@ def test_logsoftmax_embed_dropout_backward():
     assert torch.equal(xd.grad != 0, y != 0)
     y2 = xe.DropoutFn.apply(xd, None, 0.1, 12346, None)
     assert not torch.equal(y2 != 0, y != 0)
+    # ... and the mask is the documented one: element i of stream seed (+ the step word on the device) is kept iff
+    # drop_hash(seed + step, i) >= p * 2^32 (tests/counter_streams.py), seeds above 2^63 included
+    idx = np.arange(400 * 256, dtype=np.uint64)
+    assert np.array_equal((y != 0).cpu().numpy().ravel(), cs.keep_mask(12345, 0, 0.1, idx))
+    step = torch.tensor([5], dtype=torch.int64, device="cuda")
+    y5 = xe.DropoutFn.apply(xd, None, 0.1, 12345, step)
+    assert np.array_equal((y5 != 0).cpu().numpy().ravel(), cs.keep_mask(12345, 5, 0.1, idx))
+    assert not np.array_equal(cs.keep_mask(12345, 5, 0.1, idx), cs.keep_mask(12345, 0, 0.1, idx))
+    yb = xe.DropoutFn.apply(xd, None, 0.1, 2 ** 63 + 1, None)
+    assert np.array_equal((yb != 0).cpu().numpy().ravel(), cs.keep_mask(2 ** 63 + 1, 0, 0.1, idx))
+    assert not np.array_equal(cs.keep_mask(2 ** 63 + 1, 0, 0.1, idx), cs.keep_mask(1, 0, 0.1, idx))       # (a seed cut to 32 bits would show)
 
 
 # ------------------------------------------------------------------------------------------------ whole step
@@ -550,9 +565,24 @@ def test_grouped_weight_gradient_gemms(n):
 
 @pytest.mark.parametrize("relu,res", [(False, True), (True, False)])
 def test_linear_with_epilogue_dropout_bf16(relu, res):
-    """Dropout made in the GEMM epilogue (forward) and in the dz cast (backward) = the separate dropout kernel's mask."""
+    """Dropout made in the GEMM epilogue (forward) and in the dz cast (backward) = the separate dropout kernel's mask = the documented
+    one at element m * N + n (tests/counter_streams.py)."""
+    _linear_with_epilogue_dropout(70, 128, 64, relu, res)
+
+
+# Which epilogue of gemm_glds.hip a shape reaches is decided by vec_ok (launch_linear_glds): N a multiple of 4 and aligned rows take the
+# vectorised one (four consecutive ids per lane), anything else the one-float-per-lane one.  (70, 128, 64) above, (64, 512, 64) and
+# (37, 20, 128) -- 64-row tiles of 32 / 16 columns, M <= 64 -- all have N % 4 == 0: the vectorised epilogue.  (37, 61, 128) and (70, 61, 64)
+# have N % 4 != 0: the general epilogue (on the 64 x 32 and the 64 x 64 tile), and the dz cast pads their rows to 64 columns.
+@pytest.mark.parametrize("relu,res", [(False, True), (True, False)])
+@pytest.mark.parametrize("M,N,K", [(64, 512, 64), (37, 20, 128), (37, 61, 128), (70, 61, 64)])
+def test_linear_epilogue_dropout_mask_on_both_epilogues(M, N, K, relu, res):
+    _linear_with_epilogue_dropout(M, N, K, relu, res)
+
+
+def _linear_with_epilogue_dropout(M, N, K, relu, res):
     from boficap_amd import xe
-    M, N, K, p, seed = 70, 128, 64, 0.25, 987654321
+    p, seed = 0.25, 987654321
     g = torch.Generator().manual_seed(1)
     x, w, b = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) * 0.2, torch.randn(N, generator=g)
     r = torch.randn(M, N, generator=g) if res else None
@@ -576,6 +606,9 @@ def test_linear_with_epilogue_dropout_bf16(relu, res):
         xe._STEP_CACHE.clear()
     assert _maxdiff(y, y_ref) < 2e-3
     assert torch.equal((y.cpu() - (r if res else 0)) == 0, (mask == 0) | (z.detach() * mask == 0))
+    kept = torch.from_numpy(cs.keep_mask(seed, 0, p, cs.linear_ids(M, N)))
+    assert torch.equal(mask > 0, kept)
+    assert torch.equal((y.detach().cpu() - (r if res else 0)) != 0, kept & (z.detach() != 0))            # the GEMM's own output, not through the dropout kernel
     rel = lambda a, ref: _maxdiff(a, ref) / float(ref.abs().max())               # dz is rounded to bf16 for the two products
     assert rel(xd.grad, xr.grad) < 1e-2 and rel(wd.grad, wr.grad) < 1e-2 and rel(bd.grad, br.grad) < 1e-2   # the bias gradient sums the bf16 dz
 
@@ -962,6 +995,48 @@ def test_attention_on_unpadded_rows(kdiv, self_attn, mfma):
         vval = kd.detach().bfloat16().float()[:, offs[2]:offs[2] + d]
         lhs, rhs = float((dout.cuda() * ob).sum()), float((vgrad * vval).sum())
         assert abs(lhs - rhs) < 2e-2 * max(1.0, abs(lhs)), (lhs, rhs)
+
+
+@pytest.mark.parametrize("kdiv", [1, 2])
+def test_attention_dropout_mask_on_unpadded_rows(kdiv):
+    """dropout(p_attn) over unpadded rows (cross-attention to the image's dense keys): the keep mask, recovered with V = one-hot(key) per head
+    so that the context row IS the dropped probability row, equals the documented one at element (global query row * H + h) * Lk + k."""
+    from boficap_amd import xe
+    H, d, B, Lmax, R, p, seed = 2, 128, 6, 20, 36, 0.3, 777
+    g = torch.Generator().manual_seed(41 + kdiv)
+    counts = torch.tensor([5, 20, 1, 0, 13, 8], dtype=torch.int32)
+    starts = torch.cumsum(torch.cat([torch.zeros(1, dtype=torch.int32), counts[:-1]]), 0).to(torch.int32)
+    T = int(counts.sum())
+    Tp = T + 9
+    klen = torch.zeros(Tp, dtype=torch.int32)
+    klen[:T] = torch.randint(1, R + 1, (T,), generator=g).int()
+    qb, kvb = torch.randn(Tp, d, generator=g), torch.randn(B // kdiv * R, 2 * d, generator=g)
+    kvb[:, d:] = 0
+    for i in range(B // kdiv):
+        for k in range(R):
+            for h in range(H):
+                kvb[i * R + k, d + h * 64 + k] = 1.0
+    seg = (starts.cuda(), counts.cuda(), False)
+    xe._COMPUTE["dtype"] = torch.bfloat16
+    xe._STEP_CACHE.clear(); xe._SHADOW_ONLY.clear()
+    try:
+        def run(drop):
+            qd, kd = qb.clone().cuda().requires_grad_(), kvb.clone().cuda().requires_grad_()
+            xe._register_shadow(qd, qd.detach().to(torch.bfloat16))
+            xe._register_shadow(kd, kd.detach().to(torch.bfloat16))
+            out = xe.attention(qd, kd, 0, 0, d, B, H, Lmax, R, kdiv, klen.cuda(), 0, 1, 0, drop, seg)
+            return xe._shadow(out).float().cpu()
+        P0 = run(None).view(Tp, H, 64)[:T, :, :R]                # [global row, h, k]
+        Pd = run((p, seed, None)).view(Tp, H, 64)[:T, :, :R]
+    finally:
+        xe._COMPUTE["dtype"] = torch.float32
+        xe._STEP_CACHE.clear(); xe._SHADOW_ONLY.clear()
+    valid = (torch.arange(R).view(1, 1, R) < klen[:T].view(T, 1, 1)) & (P0 > 1e-3)
+    keep = Pd > 0
+    assert int(valid.sum()) > 4 * T * H
+    assert torch.allclose(Pd[valid & keep], P0[valid & keep] / (1 - p), rtol=3e-2, atol=2e-3)
+    kept = torch.from_numpy(cs.keep_mask(seed, 0, p, cs.attn_ids_unpadded(np.arange(T), H, R)))
+    assert torch.equal(keep[valid], kept[valid])
 
 
 def test_scheduled_sampling_step_vs_reference(weight_cache, manifest):
