@@ -112,8 +112,9 @@ int bofi_layernorm_bwd(const float* x, const float* gain, const float* dy, const
 int bofi_layernorm_bwd_ex(const float* x, const float* gain, const float* dy, const float* add, float* dx, float* dgain,
                           float* dbias, int rows, int d, void* dz_bf16, float drop_p, uint64_t drop_seed,
                           const uint64_t* drop_step, void* stream);
-/* backward of bofi_attention_ex (Lq, Lk <= 64): dq like q, dk/dv like k/v (accumulated when kdiv > 1); q_start / q_count /
- * k_ragged as in bofi_attention_ex */
+/* backward of bofi_attention_ex (Lk <= 128, any Lq: the query rows are walked in chunks of 32 or 64): dq like q, dk/dv like
+ * k/v, ACCUMULATED into zeroed buffers when kdiv > 1 or the query rows take more than one chunk (Lq > 32 beyond 64 keys,
+ * Lq > 64 otherwise), written otherwise; q_start / q_count / k_ragged as in bofi_attention_ex (k_ragged: Lq <= 128) */
 int bofi_attention_bwd(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
                        const float* dout, int ldo, float* dq, float* dk, float* dv, int B, int H, int Lq,
                        int Lk, int kdiv, const int* klen, int klen_sb, int klen_sq, int klen_bias,
