@@ -229,6 +229,12 @@ struct AttnMapsArgs {
 const char* attn_maps_check(const AttnMapsArgs& a);     // NULL, or what is wrong with the arguments (BOFI_ERR_ARG)
 int launch_attn_maps(const AttnMapsArgs& a, hipStream_t st);
 
+// ---- constrained pick behind the vocabulary epilogue (constrain.hip): banned ids and no adjacent repeated word, re-picked per live position from x [rows, ldx]
+// (bofi_vocab_constrain states the rule); ban_bits / ntok / row_chosen / changed may be NULL
+const char* vocab_constrain_check(const float* x, int ldx, int rows, int V, int S, int no_repeat, int repeat_min_id, const int64_t* seq);     // NULL, or what is wrong (BOFI_ERR_ARG)
+int launch_vocab_constrain(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits,
+                           int no_repeat, int repeat_min_id, int64_t* seq, float* row_chosen, int* changed, hipStream_t st);
+
 int launch_set_u64(uint64_t* p, uint64_t v, hipStream_t s);
 int launch_zero_f32(float* p, size_t n, hipStream_t s);
 

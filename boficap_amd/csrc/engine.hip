@@ -109,6 +109,7 @@ struct bofi_engine {
     // with the defaults -- before it enqueues anything, so nothing of one call reaches the next; key_call() puts them into the graph key
     bofi_call_opts_t opt{};
     bool attn_out_set() const { return opt.attn_mean || opt.attn_heads || opt.attn_top_idx; }
+    bool pick_set() const { return opt.pick_ban || opt.pick_no_repeat; }      // the constrained pick (bofi_call_opts_t.pick_*) is on
     bool loop_ready = false;
     float* dbg_part = nullptr;
 
@@ -134,6 +135,7 @@ struct bofi_engine {
     int64_t *mp_ids = nullptr, *mp_fresh_ids = nullptr, *mp_next_ids = nullptr;
     float *mp_chosen = nullptr, *mp_plogp = nullptr, *mp_fresh_chosen = nullptr, *mp_fresh_plogp = nullptr;
     int *mp_round = nullptr, *mp_mask = nullptr;
+    int* pick_changed = nullptr;                                        // [Bm] positions the constrained pick of the last filling pass changed (bofi_engine_pick_changed)
     std::vector<void*> qkv_dec;                                         // SAIC: q|k|v of every decoder layer [B*S, 3d] (the K / V cache)
     int *sa_rows = nullptr, *sa_nrows = nullptr;                        // decoder rows of the iteration's new phrases, their count
     uint64_t* d_seed = nullptr;                                         // per-call sampling seed (read by the captured sampling kernels)
@@ -324,6 +326,7 @@ struct bofi_engine {
     ENG_OK(dalloc(&mp_ids, Bm * Sq)); ENG_OK(dalloc(&mp_fresh_ids, Bm * Sq)); ENG_OK(dalloc(&mp_next_ids, Bm * Sq));
     ENG_OK(dalloc(&mp_chosen, Bm * Sq)); ENG_OK(dalloc(&mp_plogp, Bm * Sq)); ENG_OK(dalloc(&mp_fresh_chosen, Bm * Sq)); ENG_OK(dalloc(&mp_fresh_plogp, Bm * Sq));
     ENG_OK(dalloc(&mp_round, Bm * Sq)); ENG_OK(dalloc(&mp_mask, Bm * Sq));
+    ENG_OK(dalloc(&pick_changed, Bm));
     qkv_dec.assign(c.n_dec, nullptr);                  // allocated by the first semi-autoregressive decode
 
         return BOFI_OK;
@@ -989,9 +992,15 @@ int bofi_engine::enqueue_fill(const int* att_len, int B, int R, int flags, int64
     }
     // (a round that another one follows: its ids are all the next round reads -- the log-probs it would write are overwritten: not stored)
     const int ids_only_on = bofi::knob(BOFI_REFINE_IDS_ONLY);      // developer knob: 0 = every round stores its log-probs
-    const int lsm = (flags & BOFI_FLAG_RAW_LOGITS) ? 0 : ((flags & BOFI_FLAG_IDS_ONLY) || (ids_only_on && round + 1 < rounds && lsrc) ? 2 : 1);
+    // (with the constrained pick on every round stores them: the pick reads what the pass stored)
+    const int lsm = (flags & BOFI_FLAG_RAW_LOGITS) ? 0 : ((flags & BOFI_FLAG_IDS_ONLY) || (ids_only_on && round + 1 < rounds && lsrc && !pick_set()) ? 2 : 1);
     ENG_OK(bofi::launch_vocab_finalize(lg, M, cfg.vocab, S, lsm, st.last, -1, cfg.pad_idx, ep_seq, s, nullptr, nullptr, nullptr, nullptr,
                                        lsrc, gen.Npad, lsm ? ep_plogp : nullptr, lsm ? ep_chosen : nullptr));
+    // the constrained pick (bofi_call_opts_t.pick_*), every pass: banned ids and adjacent repeats re-picked from the tensor the epilogue has just written (log-probs, or the
+    // logits at the caller's pitch), so a following round is fed the constrained ids and the last one leaves seq / row_chosen those of the emitted ids
+    if (pick_set())
+        ENG_OK(bofi::launch_vocab_constrain(lg, cfg.vocab, M, cfg.vocab, S, st.last, -1, cfg.pad_idx, opt.pick_ban, opt.pick_no_repeat, opt.pick_repeat_min_id, ep_seq,
+                                            lsm ? ep_chosen : nullptr, pick_changed, s));
     ENG_OK(refine_step(round));
     }
     return BOFI_OK;
@@ -1311,6 +1320,13 @@ const float* bofi_engine_logprob(bofi_engine_t* e) {
     return e ? e->logits : nullptr;
 }
 
+int bofi_engine_pick_changed(bofi_engine_t* e, int* dst, int B, void* stream) {
+    g_err.clear();
+    if (!e || !dst || B < 1 || B > e->cfg.max_batch) return fail(BOFI_ERR_ARG, "pick_changed: an engine, a destination and B in 1..max_batch");
+    ENG_HIP(hipMemcpyAsync(dst, e->pick_changed, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return BOFI_OK;
+}
+
 void* bofi_engine_stream(bofi_engine_t* e) {
     if (!e) return nullptr;
     if (!e->run_stream && hipStreamCreateWithFlags(&e->run_stream, hipStreamNonBlocking) != hipSuccess) return nullptr;
@@ -1520,6 +1536,15 @@ static int check_opts(bofi_engine_t* e, int flags, const bofi_call_opts_t& o, in
         return fail(BOFI_ERR_ARG, "saic range: 1 <= begin <= end <= seq_length, or end 0");
     if (which_call == CALL_SAIC && (flags & BOFI_FLAG_SAMPLE) && !(o.sample_temperature > 0.f)) return fail(BOFI_ERR_ARG, "temperature must be positive");
     if (!o.row_plogp != !o.row_chosen) return fail(BOFI_ERR_ARG, "row statistics: both buffers or none");
+    // the constrained pick
+    if (o.pick_no_repeat != 0 && o.pick_no_repeat != 1) return fail(BOFI_ERR_ARG, "constrained pick: pick_no_repeat is 0 or 1");
+    if (o.pick_repeat_min_id < 0) return fail(BOFI_ERR_ARG, "constrained pick: pick_repeat_min_id >= 0");
+    if (o.pick_ban || o.pick_no_repeat) {
+        if (which_call == CALL_SAIC) return fail(BOFI_ERR_STATE, "a constrained pick is set: it re-picks the non-autoregressive filling pass only, not the semi-autoregressive decode");
+        if (flags & BOFI_FLAG_IDS_ONLY) return fail(BOFI_ERR_ARG, "constrained pick: not with BOFI_FLAG_IDS_ONLY (no distribution to re-pick from)");
+        if (flags & BOFI_FLAG_MASK_PREDICT) return fail(BOFI_ERR_ARG, "constrained pick: not with BOFI_FLAG_MASK_PREDICT (a kept position would pin both neighbours)");
+        if (e->cfg.seq_length > 64) return fail(BOFI_ERR_ARG, "constrained pick: seq_length <= 64 (bofi_vocab_constrain)");
+    }
     if (!o.attn_mean && !o.attn_heads && !o.attn_top_idx && !o.attn_top_w) return BOFI_OK;      // no attention output: layer and K are not read
     if (which_call == CALL_SAIC) return fail(BOFI_ERR_STATE, "an attention output is set: the maps come out of the non-autoregressive filling pass only, not the semi-autoregressive decode");
     if (o.attn_layer < -1 || o.attn_layer >= e->cfg.n_dec) return fail(BOFI_ERR_ARG, "attention output: layer in 0 .. N_dec - 1, or -1 for the last");
@@ -1539,11 +1564,12 @@ static void key_call(std::vector<uintptr_t>& key, const bofi_engine_t* e) {
     for (uintptr_t v : {(uintptr_t)o.q1_group, (uintptr_t)o.bound_iter_cap, (uintptr_t)o.saic_it_begin, (uintptr_t)o.saic_it_end, (uintptr_t)tbits, (uintptr_t)o.live_max,
                         (uintptr_t)o.sat_out, (uintptr_t)o.row_plogp, (uintptr_t)o.row_chosen, (uintptr_t)o.refine_round, (uintptr_t)o.attn_layer, (uintptr_t)o.attn_topk,
                         (uintptr_t)o.attn_mean, (uintptr_t)o.attn_heads, (uintptr_t)o.attn_top_idx, (uintptr_t)o.attn_top_w,
+                        (uintptr_t)o.pick_ban, (uintptr_t)o.pick_no_repeat, (uintptr_t)o.pick_repeat_min_id,
                         (uintptr_t)e->settings.in_flight, (uintptr_t)(e->settings.loop_mode + 1), (uintptr_t)e->settings.kv_beside, (uintptr_t)bofi::g_env_generation})
         key.push_back(v);
 }
 // a new field of the record goes into key_call, or is named there as deliberately unkeyed
-static_assert(sizeof(bofi_call_opts_t) == 112, "bofi_call_opts_t changed: key_call must name every field");
+static_assert(sizeof(bofi_call_opts_t) == 128, "bofi_call_opts_t changed: key_call must name every field");
 static int check_feats(bofi_engine_t* e, const void* feats, int feats_dtype) {
     if (!feats) return fail(BOFI_ERR_ARG, "null att_feats");
     if (feats_dtype != BOFI_DT_F32 && feats_dtype != e->cfg.dtype) return fail(BOFI_ERR_ARG, "att_feats must be float32 or the engine's compute dtype");

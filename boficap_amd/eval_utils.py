@@ -175,6 +175,13 @@ def diversity_stats(seq, sample_n: int, eval_kwargs):
     return {k: out[k] for k in KEYS}, out["per_image"]
 
 
+def constrained_rate(results) -> float:
+    """Positions the constrained pick changed over positions emitted (the images' laid-out tokens), of ``decode_many``'s dicts."""
+    changed = sum(int(r["constrained"].sum()) for r in results)
+    emitted = sum(int(r["phrase_length"].sum()) for r in results)
+    return changed / max(1, emitted)
+
+
 def _torch_feats(feats):
     return feats if torch.is_tensor(feats) else torch.from_numpy(np.ascontiguousarray(feats))
 
@@ -194,6 +201,34 @@ def caption_surface(model, eval_kwargs):
     return surface
 
 
+def constraint_of(eval_kwargs, vocab, mode: str = "NAIC", sample_n: int = 1):
+    """The constrained pick an evaluation asks for, as the keywords of ``TransformerModel.decode_many``: {} when ``suppress_UNK``, ``decoding_constraint`` (the
+    reference's names; both default to 0 here: on this path the reference's options do nothing, and the defaults keep the captions) and ``ban_words`` (a list of
+    words, or 'W1,W2,...') are all off, else {'ban_ids': sorted ids, 'no_repeat': bool}.  Words resolve to ids as the bad-ending words do (``surface.ids_of`` on
+    ``vocab``; a word the vocabulary does not hold names no id).  ValueError where the options cannot apply: SAIC mode, ``fused_vocab``, mask-predict, sampling."""
+    kw = eval_kwargs
+    words = kw.get("ban_words") or []
+    words = [w for w in words.split(",") if w] if isinstance(words, str) else list(words)
+    unk, rep = int(kw.get("suppress_UNK", 0)) == 1, int(kw.get("decoding_constraint", 0)) == 1
+    if not (unk or rep or words):
+        return {}
+    if mode != "NAIC":
+        raise ValueError("suppress_UNK / decoding_constraint / ban_words constrain the non-autoregressive filling pass: inference_mode 'NAIC' only")
+    if kw.get("fused_vocab", False):
+        raise ValueError("suppress_UNK / decoding_constraint / ban_words: not with fused_vocab (no distribution to re-pick from)")
+    if kw.get("refine_method", "feed_back") == "mask_predict":
+        raise ValueError("suppress_UNK / decoding_constraint / ban_words: not with refine_method 'mask_predict'")
+    if int(sample_n) > 1:
+        raise ValueError("suppress_UNK / decoding_constraint / ban_words constrain greedy picks: not with sample_n > 1")
+    if (unk or words) and not vocab:
+        raise ValueError("suppress_UNK / ban_words need a vocabulary ({str(id): word})")
+    from .surface import ids_of
+    ids = ids_of(vocab, set(words) | ({"UNK"} if unk else set())) if (unk or words) else []
+    if not ids and not rep:
+        return {}                                                # (no such word in this vocabulary: nothing is banned and nothing launched)
+    return {"ban_ids": ids, "no_repeat": rep}
+
+
 def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
     """(val_loss, predictions, lang_stats) of ``feats``' images: see the module's head.  The model is put in eval() and restored."""
     kw = eval_kwargs
@@ -210,6 +245,9 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
         raise ValueError("attn_topk reads the non-autoregressive filling pass's cross-attention: inference_mode 'NAIC' only")
     if attn_topk:
         refine["attn_topk"] = attn_topk
+    # suppress_UNK / decoding_constraint / ban_words: the constrained pick (constraint_of); with language stats, constrained_rate = changed / emitted positions
+    pick = constraint_of(kw, kw.get("vocab") or getattr(model, "vocab", None), mode, sample_n)
+    refine.update(pick)
     remove, surface_stats = int(kw.get("remove_bad_endings", 0)) == 1, int(kw.get("surface_stats", 0)) == 1
     if surface_stats and sample_n > 1 and kw.get("train_sentences") is None:
         raise ValueError("surface_stats with sample_n > 1 looks the sampled captions up among the training sentences: eval_kwargs['train_sentences'] "
@@ -299,6 +337,8 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
                 lang_stats.update(sentence_stats(canon, kept, kw["train_sentences"], surface.V))
         if surface_stats and bad is not None and ev is not None:      # bad_count_rate (eval_utils.py:122): inside language_eval, of the scored captions
             lang_stats["bad_count_rate"] = surface.bad_count_rate(bad)
+        if pick and lang_stats is not None:                      # after every other key
+            lang_stats["constrained_rate"] = constrained_rate(got)
     finally:
         model.train(was_training)
     return val_loss, predictions, lang_stats

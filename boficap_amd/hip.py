@@ -41,7 +41,8 @@ class BofiCallOpts(C.Structure):
     """bofi_call_opts_t: the options of one decode_naic / decode_saic / fill_naic call (the header states each field); zero-filled = the defaults."""
     _fields_ = [("q1_group", _I), ("bound_iter_cap", _I), ("saic_it_begin", _I), ("saic_it_end", _I), ("sample_temperature", C.c_float), ("sample_seed", C.c_uint64),
                 ("live_max", _P), ("sat_out", _P), ("row_plogp", _P), ("row_chosen", _P), ("refine_round", _P), ("attn_layer", _I), ("attn_topk", _I),
-                ("attn_mean", _P), ("attn_heads", _P), ("attn_top_idx", _P), ("attn_top_w", _P)]
+                ("attn_mean", _P), ("attn_heads", _P), ("attn_top_idx", _P), ("attn_top_w", _P),
+                ("pick_ban", _P), ("pick_no_repeat", _I), ("pick_repeat_min_id", _I)]
 
 
 _OPTS = C.POINTER(BofiCallOpts)
@@ -131,6 +132,8 @@ SIGNATURES = {
     "bofi_pack_regions_box": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
     "bofi_mask_predict_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "bofi_attn_maps": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_float, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
+    "bofi_vocab_constrain": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "bofi_engine_pick_changed": (_I, [_P, _P, _I, _P]),
     "bofi_caption_trim": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     "bofi_sentence_lookup": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
 }
@@ -271,6 +274,44 @@ def attn_maps(q, k, B, H, Lq, Lk, *, scale=0.125, klen=None, qlen=None, qlen_bia
             raise BofiHipError(f"attn_maps: {name} must be a contiguous {dt} device tensor of shape {shape}")
     check(lib().bofi_attn_maps(ptr(q), q.stride(0), ptr(k), k.stride(0), dtype_code(q), int(B), int(H), int(Lq), int(Lk), float(scale), ptr(klen), ptr(qlen), int(qlen_bias),
                                ptr(mean), ptr(heads), int(K), ptr(top_idx), ptr(top_w), stream_ptr()), "bofi_attn_maps")
+
+
+def ban_bits(ids, V: int, device=None):
+    """The bit table of ``bofi_vocab_constrain`` / ``bofi_call_opts_t.pick_ban`` from an id list: uint32 [(V + 31) / 32] (as int32 storage) on ``device``, bit id % 32 of word
+    id / 32 set for every listed id.  Checked on the host: every id in 0..V-1, and at least two ids left unbanned (the kernel needs a second candidate per position)."""
+    import numpy as np
+    import torch
+    ids = sorted({int(i) for i in ids})
+    if ids and (ids[0] < 0 or ids[-1] >= V):
+        raise BofiHipError(f"ban_ids: ids must lie in 0..{V - 1}, got {ids[0] if ids[0] < 0 else ids[-1]}")
+    if V - len(ids) < 2:
+        raise BofiHipError(f"ban_ids: {len(ids)} of {V} ids banned -- at least two must stay")
+    words = np.zeros((V + 31) // 32, np.uint32)
+    for i in ids:
+        words[i >> 5] |= np.uint32(1 << (i & 31))
+    t = torch.from_numpy(words.view(np.int32))
+    return t if device is None else t.to(device)
+
+
+def vocab_constrain(x, V, S, seq, *, ntok=None, ntok_bias=0, pad_idx=0, ban=None, no_repeat=False, repeat_min_id=7, row_chosen=None, changed=None):
+    """``bofi_vocab_constrain`` on torch tensors: x float32 [rows, >= V] on the device with unit column stride (its row stride is the pitch; any 4-byte alignment), seq int64
+    [rows] read and written, ntok int32 [rows / S] or None, ban the bit table of ``ban_bits`` (int32 / uint32 storage, (V + 31) / 32 words) or None, row_chosen float32 [rows]
+    and changed int32 [rows / S] optional.  One launch on the current stream, no synchronisation."""
+    import torch
+    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or not x.is_cuda:
+        raise BofiHipError("vocab_constrain: x must be a 2-d float32 device tensor with unit column stride")
+    rows = x.size(0)
+    if x.size(1) < V or S < 1 or rows % S:
+        raise BofiHipError("vocab_constrain: x needs V columns and a multiple of S rows")
+    B = rows // S
+    for name, t, dt, n in (("seq", seq, torch.int64, rows), ("ntok", ntok, torch.int32, B), ("ban", ban, torch.int32, (V + 31) // 32),
+                           ("row_chosen", row_chosen, torch.float32, rows), ("changed", changed, torch.int32, B)):
+        if t is None and name != "seq":
+            continue
+        if t is None or t.dtype != dt or t.numel() != n or not t.is_cuda or not t.is_contiguous():
+            raise BofiHipError(f"vocab_constrain: {name} must be a contiguous {dt} device tensor of {n} elements")
+    check(lib().bofi_vocab_constrain(ptr(x), x.stride(0), rows, int(V), int(S), ptr(ntok), int(ntok_bias), int(pad_idx), ptr(ban), 1 if no_repeat else 0, int(repeat_min_id),
+                                     ptr(seq), ptr(row_chosen), ptr(changed), stream_ptr()), "bofi_vocab_constrain")
 
 
 def gemm_flops(reset: bool = False):

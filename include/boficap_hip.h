@@ -370,7 +370,22 @@ typedef struct bofi_call_opts {
      * token (as seq_logprob).  Needs seq_length <= 64 and R <= 128; decode_saic with a buffer given is BOFI_ERR_STATE. */
     int attn_layer; int attn_topk;
     float* attn_mean; float* attn_heads; int* attn_top_idx; float* attn_top_w;
+    /* The constrained pick of a decode_naic / fill_naic (bofi_vocab_constrain states the rule; appended within ABI version 5: a record that ends in zeros -- and a caller
+     * that zero-fills it -- gets the unconstrained decode, bit for bit, and nothing is launched).  pick_ban: device uint32 [ceil(V / 32)], bit id % 32 of word id / 32 set = id
+     * is never emitted (NULL: none; the caller leaves at least two ids unbanned).  pick_no_repeat (0 / 1): a position does not repeat the id of the position before it when that
+     * id is >= pick_repeat_min_id (>= 0; a word id: 7 is the first one, so pad / BOS / EOS / the label ids may repeat).  On = a ban table or pick_no_repeat = 1: bofi_vocab_constrain's two launches
+     * right behind the vocabulary epilogue of EVERY filling pass, part of BOFI_FLAG_PHASE_FILL -- so feed-back rounds feed the constrained ids back, and the last pass leaves seq and
+     * row_chosen those of the emitted ids (row_plogp, a figure of the distribution, stays).  Every pass then stores its log-probs (the pick reads what the pass stored), and the
+     * per-image counts of re-picked positions of the last pass are read with bofi_engine_pick_changed.  Under BOFI_FLAG_RAW_LOGITS the pick is over logits.
+     * BOFI_ERR_ARG before anything is enqueued: pick_no_repeat outside {0, 1}, pick_repeat_min_id < 0; on together with BOFI_FLAG_IDS_ONLY (no distribution to re-pick from) or
+     * BOFI_FLAG_MASK_PREDICT (a kept position would pin both neighbours), or seq_length > 64.  decode_saic with the options on is BOFI_ERR_STATE. */
+    const uint32_t* pick_ban; int pick_no_repeat; int pick_repeat_min_id;
 } bofi_call_opts_t;
+
+/* The per-image counts of positions whose id the constrained pick of the LAST filling pass changed (bofi_call_opts_t.pick_*; bofi_vocab_constrain's `changed`), of the most
+ * recent decode_naic / fill_naic of this engine that had the options on: copies the first B of them from the engine's workspace to dst (device int32 [B]) on `stream` --
+ * the decode's own stream, behind it.  BOFI_ERR_ARG: a NULL engine or dst, B outside 1..max_batch. */
+int bofi_engine_pick_changed(bofi_engine_t* e, int* dst, int B, void* stream);
 
 /* A hint, not a semantic: how many decodes the caller keeps in flight on this device (engine + forks on their own streams).  1: this engine's
  * launches run with nothing beside them -- from 4 096 rows on the sublayer kernels then take 64-row blocks (more, shorter workgroups: 62 against 68 us
@@ -762,6 +777,25 @@ int bofi_mask_predict_step(int64_t* ids, float* chosen, float* plogp, int* round
  * One launch: a workgroup per image, a wavefront per head. */
 int bofi_attn_maps(const void* q, int ldq, const void* k, int ldk, int dtype, int B, int H, int Lq, int Lk, float scale, const int* klen,
                    const int* qlen, int qlen_bias, float* mean, float* heads, int K, int* top_idx, float* top_w, void* stream);
+
+/* The constrained pick behind the vocabulary epilogue: banned ids (the reference's suppress_UNK, CaptionModel.py:151-153, and any id list) and "never the same word twice in a
+ * row" (its decoding_constraint, AttModel.py:325-329) for the non-autoregressive filling pass, where the reference applies neither.  Re-picks every live position of every
+ * image; the distribution is read only.
+ *   x float32 [rows, ldx], ldx >= V: log-probs or raw logits; row b * S + s is position s of image b; rows need 4-byte alignment only.  1 <= S <= 64.
+ *   n_b = clamp(ntok[b] + ntok_bias, 0, S) live positions of image b (ntok int32 [rows / S]; NULL: all S).  Rows past n_b are not read.
+ *   ban_bits device uint32 [(V + 31) / 32] or NULL: bit i % 32 of word i / 32 set = id i is banned.  The caller leaves at least two ids unbanned.
+ *   Order: id a comes before id c when x[a] is NaN and x[c] is not; else, neither NaN, when x[a] > x[c]; ties -- +0.0 against -0.0, NaN against NaN -- go to the lower id
+ *   (torch.max's rule, as bofi_vocab_finalize).  The pick of position s < n_b is the first ELIGIBLE id in that order: not banned, and no_repeat == 0 or s == 0 or
+ *   prev < repeat_min_id or id != prev, where prev is the constrained pick of position s - 1 of the same image (a sequential scan over each row's two best unbanned ids).
+ *   seq int64 [rows]: read (the ids that stand there) and written: the pick for s < n_b, pad_idx for s >= n_b.
+ *   row_chosen float32 [rows] or NULL: x[row, pick] for s < n_b; untouched past n_b.
+ *   changed int32 [rows / S] or NULL: per image, the positions s < n_b whose pick differs from the id that stood in seq on entry.
+ * Deterministic: no atomics, no float arithmetic, exact comparisons.  rows = 0 is BOFI_OK without a launch.  BOFI_ERR_ARG with a message and no launch: NULL x or seq,
+ * rows % S != 0, V < 2, ldx < V, S outside 1..64, no_repeat outside {0, 1}, repeat_min_id < 0.
+ * Two launches: a workgroup of four wavefronts per live row streams its V floats (16-byte loads behind a peel to the row's first 16-byte boundary, ban bits staged in LDS)
+ * and leaves the row's two candidate ids packed in seq[row]; then one wavefront per image runs the scan.  No workspace. */
+int bofi_vocab_constrain(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int no_repeat,
+                         int repeat_min_id, int64_t* seq, float* row_chosen, int* changed, void* stream);
 
 /* The bad-ending trim of the reference's decode_sequence (captioning/utils/misc.py:75-82, REMOVE_BAD_ENDINGS) and the flag of its count_bad
  * (captioning/utils/eval_utils.py:32-37), on id rows.  seq int64 [rows, S], 1 <= S <= 64.  The caption of a row is its ids before the first id <= limit

@@ -91,7 +91,17 @@ def main():
     ap.add_argument("--surface_stats", type=int, default=0, choices=[0, 1], help="1: bad_count_rate (with --language_eval 1) and, with --sample_n N, novel_sentences "
                     "and vocab_size of the sampled captions (these need --input_label_npz and --input_json: the training sentences)")
     ap.add_argument("--bad_endings", default="", help="W1,W2,...: the words --remove_bad_endings strips, instead of the reference's list")
+    ap.add_argument("--suppress_UNK", type=int, default=0, choices=[0, 1], help="NAIC only: 1 = no caption holds UNK -- every position takes its best other word (the "
+                    "reference's option, which does nothing on its non-autoregressive path; so the default here is 0, not its 1: the defaults keep the captions)")
+    ap.add_argument("--decoding_constraint", type=int, default=0, choices=[0, 1], help="NAIC only: 1 = no word stands twice in a row -- a position that would repeat its "
+                    "left neighbour takes its second-best word (the reference's option, applied there on the autoregressive paths only)")
+    ap.add_argument("--ban_words", default="", help="NAIC only: W1,W2,... never appear in a caption (resolved to ids as --bad_endings resolves its words)")
     args = ap.parse_args()
+    try:                                                         # (before anything is loaded; the words are resolved once the vocabulary is)
+        from boficap_amd import eval_utils as _eu
+        _eu.constraint_of(vars(args), {"0": "UNK"}, args.inference_mode, args.sample_n)
+    except ValueError as e:
+        ap.error("--suppress_UNK / --decoding_constraint / --ban_words: " + str(e))
     if (args.remove_bad_endings or args.surface_stats) and not (args.infos_path or args.bad_endings):
         ap.error("--remove_bad_endings / --surface_stats need the ids of the bad-ending words: --infos_path (a vocabulary) or --bad_endings W1,W2,...")
     if args.surface_stats and args.sample_n > 1 and not (args.input_label_npz and args.input_json):
@@ -177,6 +187,9 @@ def main():
         c = model.cfg
         src = args.input_label_npz if args.input_label_npz.endswith((".h5", ".hdf5")) else dict(np.load(args.input_label_npz))
         store = LabelStore(src, pad_idx=c.pad_idx, bos_idx=c.bos_idx, eos_idx=c.eos_idx, len_idx=c.len_idx)
+    pick = eval_utils.constraint_of(vars(args), vocab or opt.vocab, args.inference_mode, args.sample_n)
+    pick_opt = {"ban_ids": pick["ban_ids"], "decoding_constraint": int(pick["no_repeat"])} if pick else {}      # (the same, in mode='sample''s names)
+    changed, emitted = 0, 0
     results, seconds, rows, stats = [], 0.0, [], ([], [])
     store_loss = store is not None and not args.use_box          # (mode='forward' is not built for F = 2053: box features are decode-only)
     surface, bad_flags = None, []
@@ -212,12 +225,12 @@ def main():
                 return RegionFeeder(att_store, kb, workers=args.feeder_workers, norm_att_feat=bool(args.norm_att_feat),
                                     sizes=None if sizes is None else {k: wh for k, wh in zip(feats.keys, sizes)}, **box_kw)
             for _ in model.decode_many(feeder(key_batches[:2 * args.in_flight * args.batches_per_launch]), batches_per_launch=args.batches_per_launch, in_flight=args.in_flight,
-                                       fused_vocab=args.fused_vocab, **refine):
+                                       fused_vocab=args.fused_vocab, **refine, **pick):
                 pass                                             # graph captures and stream choice, outside the clock
             torch.cuda.synchronize()
             import time
             t0 = time.time()
-            got = list(model.decode_many(feeder(key_batches), batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab, **refine))
+            got = list(model.decode_many(feeder(key_batches), batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab, **refine, **pick))
             seconds = time.time() - t0
             i = 0
             for r in surfaced(got):
@@ -234,12 +247,12 @@ def main():
                 host = host.to(torch.bfloat16)
             host = host.pin_memory()
             batches = [host[i:i + args.batch_size] for i in range(0, host.size(0), args.batch_size)]
-            for _ in model.decode_many(batches[:2 * args.in_flight * args.batches_per_launch], batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab, **refine):
+            for _ in model.decode_many(batches[:2 * args.in_flight * args.batches_per_launch], batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab, **refine, **pick):
                 pass                                             # graph captures and stream choice, outside the clock
             torch.cuda.synchronize()
             import time
             t0, got = time.time(), []
-            for r in model.decode_many(batches, batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab, **refine):
+            for r in model.decode_many(batches, batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab, **refine, **pick):
                 got.append(r)                                    # host tensors of one batch: ids, slot layout, entropy, perplexity
             seconds = time.time() - t0
             i = 0
@@ -256,8 +269,10 @@ def main():
                     att, masks = torch.from_numpy(np.ascontiguousarray(feats[i:i + args.batch_size])).cuda(), None
                 fc = torch.zeros(att.size(0), 0, device="cuda")
                 seq, lp, pn, pl, ps, t = model(fc, att, masks, opt=dict({"train_mode": args.inference_mode, "sample_method": "greedy", "sample_n": 1},
-                                                                                   **(refine if args.inference_mode == "NAIC" else {})), mode="sample")
+                                                                                   **(dict(refine, **pick_opt) if args.inference_mode == "NAIC" else {})), mode="sample")
                 seconds += t
+                if pick:
+                    changed, emitted = changed + int(model.last_constrained.sum()), emitted + int(pl.sum())
                 # per-image entropy / perplexity as eval_utils.py:463-464, from the fused row reductions (bofi_vocab_stats); under mask-predict from the statistics of
                 # the pass that emitted each token (the log-prob tensor is the last pass's)
                 if args.refine_method == "mask_predict":
@@ -267,6 +282,8 @@ def main():
                 r = surfaced([{"seq": seq.cpu(), **({k2: model.last_attn[k2].cpu() for k2 in ("attn_top", "attn_top_w")} if args.attn_topk else {})}])[0]
                 results.extend(eval_utils.with_regions(entry_of(i, k, r["seq"], pn, pl, ent, ppl), r, k) for k in range(att.size(0)))
             how = "one synchronised mode='sample' call per batch (the reference's eval loop), decode time only"
+    if pick and args.pipeline:
+        changed, emitted = sum(int(r["constrained"].sum()) for r in got), sum(int(r["phrase_length"].sum()) for r in got)
     if image_ids is not None:                                    # the json's ids, in the split's order
         for e, iid in zip(results, image_ids):
             e["image_id"] = iid
@@ -306,6 +323,11 @@ def main():
         if surf:
             lang_stats = dict(lang_stats or {}, **surf)
             print("surface statistics " + " ".join(f"{k} {v:.6f}" for k, v in surf.items()))
+    if pick:                                                     # positions the constrained pick changed over positions emitted; with language scores, their last key
+        rate = changed / max(1, emitted)
+        print(f"constrained pick: {changed} of {emitted} emitted positions changed (constrained_rate {rate:.6f})")
+        if lang_stats is not None:
+            lang_stats["constrained_rate"] = rate
     if args.dump_json:
         with open(args.dump_json, "w") as f:
             if preds_n is not None:
