@@ -355,13 +355,16 @@ static void launch_one(const Gemm2Params& p, hipStream_t st) {
 // FEAT_ALL is the generic kernel: it serves every feature set that has no specialisation of the tile.
 //
 // What the default build holds is exactly what launch_glds_t's heuristic can return without BOFI_GEMM_TILE (whatever the other knobs say):
-//   M <= 64           -> 64x32x4 (4 waves); bf16 with K / splitk <= 512 and BOFI_GEMM_DEEP: 64x32x9 (4), or 64x16x9 (2) for consumers without row statistics
+//   M <= 64           -> 64x32x4 (4 waves); bf16 with K / splitk <= 512, BOFI_GEMM_DEEP and a feature set of GLDS_FEATS (glds_has_deep): 64x32x9 (4),
+//                        or 64x16x9 (2) for consumers without row statistics
 //   M > 64, t >= thr  -> 128x64x2 (8)
 //   M > 64, else      -> 64x64x2 (8); bf16 with K >= 1024, splitk == 1, feat in {0, 1, 2, 6, 18, 82} and BOFI_GEMM_HEUR2: 64x64x4 (8)
 // and the dispatch below sends a feature set of GLDS_FEATS to its specialisation where the tile has one, every other to FEAT_ALL.  Hence:
 //   128x64x2, 64x64x2, 64x32x4: float32 and bf16, each feature set of GLDS_FEATS (their callers are not enumerable here: the C entry takes any) + FEAT_ALL;
 //   64x64x4: bf16 only; of its six feature sets 0, 1, 2, 18, 82 are specialised and 6 goes to FEAT_ALL;
-//   64x32x9, 64x16x9: bf16 only, the feature sets of GLDS_FEATS; any other feature set is BOFI_ERR_ARG (there has never been a generic 9-deep kernel).
+//   64x32x9, 64x16x9: bf16 only, the feature sets of GLDS_FEATS.  There is no generic 9-deep kernel: a call with any other feature set (row_len, a row
+//   list, LayerNorm in with statistics out, dropout with row_len, ..) stays on 64x32x4, whose FEAT_ALL serves it -- the heuristic asks glds_has_deep,
+//   which is generated from GLDS_FEATS like the dispatch, so no call the header allows is refused for want of a tile.
 // The experiments build (BOFI_EXPERIMENTS) adds the tiles only BOFI_GEMM_TILE reaches: the sweeps of dev/mb_tiles*.py.
 #ifdef BOFI_EXPERIMENTS
 constexpr bool GLDS_SWEEP = true;
@@ -405,6 +408,15 @@ constexpr bool GLDS_SWEEP = false;
 // the feature sets with specialisations: plain (bias / ReLU / residual), consumer of a folded LayerNorm, producer of a residual stream; the same three
 // inside the bound loop (16 ..); training: dropout (+ compute-dtype copy), dX through relu; the SAIC decoder pass over a row list (+ halt word)
 #define GLDS_FEATS(X) X(0) X(1) X(2) X(16) X(17) X(18) X(8) X(10) X(32) X(81) X(82)
+// the feature sets that have 9-deep tiles (the table holds those for `bf16 && spec` only): exactly the specialised ones
+constexpr bool glds_has_deep(int feat) {
+#define GLDS_FEAT_IS(F) || feat == F
+    return false GLDS_FEATS(GLDS_FEAT_IS);
+#undef GLDS_FEAT_IS
+}
+// (the engine's launches of <= 64 rows carry these: they must keep their whole-K ring)
+static_assert(glds_has_deep(0) && glds_has_deep(1) && glds_has_deep(2) && glds_has_deep(8) && glds_has_deep(10) && glds_has_deep(16) && glds_has_deep(17) &&
+              glds_has_deep(18) && glds_has_deep(32) && glds_has_deep(81) && glds_has_deep(82) && !glds_has_deep(FEAT_ALL), "the engine's small GEMMs lost their 9-deep tiles");
 
 // launches tile (bm, bn, ns, nw waves) as FEAT's instantiation if the build holds one
 template <typename T, int FEAT>
@@ -452,7 +464,7 @@ static int launch_glds_t(const Gemm2Params& p, hipStream_t st) {
             // ring.  With the whole K extent (<= 8 slabs) issued up front the chain is one round trip; consumers that emit no row
             // statistics take 16-column tiles (twice the workgroups, half the weight bytes per workgroup)
             const int deep = knob(BOFI_GEMM_DEEP);
-            if (deep && sizeof(T) == 2 && p.K / p.splitk <= 8 * 64) {
+            if (deep && sizeof(T) == 2 && p.K / p.splitk <= 8 * 64 && glds_has_deep(feat)) {
                 ns = 9;
                 if (!(p.stats_out || p.y2) && p.vec_ok && p.N % 16 == 0) { bn = 16; nw = 2; }
             }
