@@ -234,6 +234,12 @@ int launch_attn_maps(const AttnMapsArgs& a, hipStream_t st);
 const char* vocab_constrain_check(const float* x, int ldx, int rows, int V, int S, int no_repeat, int repeat_min_id, const int64_t* seq);     // NULL, or what is wrong (BOFI_ERR_ARG)
 int launch_vocab_constrain(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits,
                            int no_repeat, int repeat_min_id, int64_t* seq, float* row_chosen, int* changed, hipStream_t st);
+// its K-candidate form with block_trigrams (bofi_vocab_pick states the rule): work is an int32 workspace of vocab_pick_work_bytes(rows) bytes
+size_t vocab_pick_work_bytes(int rows);
+const char* vocab_pick_check(const float* x, int ldx, int rows, int V, int S, int no_repeat, int block_trigrams, int repeat_min_id, const int64_t* seq, const void* work,
+                             size_t work_bytes);
+int launch_vocab_pick(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int no_repeat,
+                      int block_trigrams, int repeat_min_id, int64_t* seq, float* row_chosen, int* changed, void* work, size_t work_bytes, hipStream_t st);
 
 int launch_set_u64(uint64_t* p, uint64_t v, hipStream_t s);
 int launch_zero_f32(float* p, size_t n, hipStream_t s);

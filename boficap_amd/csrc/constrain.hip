@@ -179,7 +179,259 @@ __global__ void __launch_bounds__(VC_SCAN_WAVES * WAVE) vocab_scan_kernel(VcArgs
     if (lane == 0 && a.changed) a.changed[b] = __popcll(ch);
 }
 
+// ---- the K-candidate form (bofi_vocab_pick): the rule above plus block_trigrams -- an id that followed the bigram (p[s-2], p[s-1]) earlier in the image's picks, all
+// three ids words, is not eligible at s; include/boficap_hip.h, bofi_vocab_pick, states the rule (the reference's table, AttModel.py:362-388, as a HARD block).
+//   key         the order as ONE unsigned 64-bit compare, integer operations only: the high word is the float's bits made monotone (NaN above every number, -0.0 as
+//               +0.0), the low word 2 (0x7fffffff - id) -- so a larger key comes first in the order --, bit 0 a mark (below); 0 is "no id".  A lane's sorted insert is
+//               then a chain of compare-and-swaps of a few instructions each (with the order's float compares and their NaN cases the chain of a K-list cost several
+//               times the pair's: DESIGN.md section 10).
+//   candidates  as above, but a lane keeps its best VP_L = 4 keys (a sorted list in registers, one compare against its last entry rejects an element) and the ROW keeps
+//               VP_K = 8: butterfly and LDS merge are bitonic merges of sorted 8-lists.  A lane's 4th entry carries the mark "this lane may hold more": the merged
+//               list is the row's true order up to and including its first marked entry, and what stands behind that entry is written as VP_CUT ("not known from
+//               here").  With ~37 elements per lane a lane holds four of a row's best eight in a few of 10^6 rows.  The row's ids go to an int32 workspace
+//               [rows, VP_K]; seq[row] keeps the id that stood there.
+//   scan        one wavefront per image, lane = position.  At step s the lanes j < s whose (p[j-2], p[j-1]) equal the current bigram form the excluded set (a ballot);
+//               the candidates of lane s are tried in order against it.  All of them excluded, or VP_CUT reached: the wavefront streams that one row again (the
+//               candidates launch's own loop) for the next VP_L ids BEHIND the last one tried -- exact, as a row's best four are among its lanes' best four --,
+//               until one is eligible or the row is exhausted: the result is the rule's for every input; only the cost differs, and only for such rows.
+constexpr int VP_K = 8;                        // candidates per row (DESIGN.md section 10 has the choice)
+constexpr int VP_L = 4;                        // ... and per lane
+constexpr int VP_CUT = 0x7ffffffe;             // in the workspace: the row's order is not known from this entry on
+static_assert(VP_K == 2 * VP_L && (VP_L & (VP_L - 1)) == 0, "the merges are bitonic");
+
+template <int N> struct Best { uint64_t k[N]; };      // descending; 0 = no id
+
+__device__ __forceinline__ uint64_t vk_key(float v, int id) {
+    uint32_t u = __float_as_uint(v);
+    if (u == 0x80000000u) u = 0u;                              // -0.0 ties with +0.0
+    uint32_t h = u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u);      // ascending with the value: -inf -> 0x007fffff, +inf -> 0xff800000
+    if ((u & 0x7fffffffu) > 0x7f800000u) h = 0xffffffffu;      // every NaN alike, in front of every number
+    return ((uint64_t)h << 32) | ((0x7fffffffu - (uint32_t)id) << 1);      // ties to the lower id
+}
+__device__ __forceinline__ int vk_id(uint64_t key) { return key ? (int)(0x7fffffffu - ((uint32_t)key >> 1)) : VC_NONE; }
+
+// order entries a and c of a list: afterwards a is not behind c
+__device__ __forceinline__ void vk_order(uint64_t& a, uint64_t& c) {
+    const uint64_t hi = a > c ? a : c, lo = a > c ? c : a;
+    a = hi; c = lo;
+}
+
+// an element strictly behind `floor` (FLOOR) enters the lane's list when it is in front of the list's last entry and not banned
+template <bool BAN, bool FLOOR>
+__device__ __forceinline__ void vk_take(Best<VP_L>& m, float v, int id, const uint32_t* ban, uint64_t floor) {
+    const uint64_t key = vk_key(v, id);
+    if (key <= m.k[VP_L - 1]) return;
+    if (FLOOR && key >= floor) return;
+    if (BAN && ((ban[id >> 5] >> (id & 31)) & 1u)) return;
+    m.k[VP_L - 1] = key;
+#pragma unroll
+    for (int k = VP_L - 1; k > 0; --k) vk_order(m.k[k - 1], m.k[k]);
+}
+
+// the best N of two sorted lists over disjoint id sets: a[k] against b[N-1-k] leaves the best N as a bitonic sequence, log2 N half-cleaners sort it
+template <int N>
+__device__ __forceinline__ Best<N> vk_merge(const Best<N>& a, const Best<N>& b) {
+    Best<N> r;
+#pragma unroll
+    for (int k = 0; k < N; ++k) r.k[k] = a.k[k] > b.k[N - 1 - k] ? a.k[k] : b.k[N - 1 - k];
+#pragma unroll
+    for (int h = N / 2; h > 0; h >>= 1)
+#pragma unroll
+        for (int k = 0; k < N; ++k)
+            if (!(k & h)) vk_order(r.k[k], r.k[k + h]);
+    return r;
+}
+
+template <int N>
+__device__ __forceinline__ Best<N> vk_wave_merge(Best<N> m) {   // butterfly: every lane ends with the wavefront's list
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        Best<N> t;
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)m.k[k], o, WAVE), hi = (uint32_t)__shfl_xor((int)(uint32_t)(m.k[k] >> 32), o, WAVE);
+            t.k[k] = ((uint64_t)hi << 32) | lo;
+        }
+        m = vk_merge<N>(m, t);
+    }
+    return m;
+}
+
+// one wavefront over column segment `seg` of `nseg` of the row at p: peel to the row's first 16-byte boundary (segment 0), 16-byte loads, scalar tail (the last segment)
+template <bool BAN, bool FLOOR>
+__device__ __forceinline__ Best<VP_L> vk_stream(const float* p, int V, int seg, int nseg, int lane, const uint32_t* ban, uint64_t floor) {
+    int peel = (4 - (int)(((uintptr_t)p >> 2) & 3)) & 3;
+    peel = peel > V ? V : peel;
+    const int nv = (V - peel) / 4, tail0 = peel + 4 * nv;
+    const int g0 = (int)((int64_t)seg * nv / nseg), g1 = (int)((int64_t)(seg + 1) * nv / nseg);
+    Best<VP_L> m;
+#pragma unroll
+    for (int k = 0; k < VP_L; ++k) m.k[k] = 0ull;
+    if (seg == 0 && lane < peel) vk_take<BAN, FLOOR>(m, p[lane], lane, ban, floor);
+    if (seg == nseg - 1 && tail0 + lane < V) vk_take<BAN, FLOOR>(m, p[tail0 + lane], tail0 + lane, ban, floor);
+    const float4* const p4 = reinterpret_cast<const float4*>(p + peel);
+    for (int base = g0; base < g1; base += WAVE * VC_UNROLL) {
+        float4 r[VC_UNROLL];
+#pragma unroll
+        for (int j = 0; j < VC_UNROLL; ++j) {
+            const int g = base + j * WAVE + lane;
+            r[j] = g < g1 ? p4[g] : float4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int j = 0; j < VC_UNROLL; ++j) {
+            const int g = base + j * WAVE + lane;
+            if (g < g1) {
+                const int id = peel + 4 * g;
+                vk_take<BAN, FLOOR>(m, r[j].x, id, ban, floor); vk_take<BAN, FLOOR>(m, r[j].y, id + 1, ban, floor);
+                vk_take<BAN, FLOOR>(m, r[j].z, id + 2, ban, floor); vk_take<BAN, FLOOR>(m, r[j].w, id + 3, ban, floor);
+            }
+        }
+    }
+    return m;
+}
+
+// grid = rows: the best unbanned ids of a live row into work[row][VP_K] (VP_CUT from where the order is not known); pad_idx into seq of a row past n_b
+template <bool BAN>
+__global__ void __launch_bounds__(VC_NT) vocab_candidates_k_kernel(VcArgs a, int* __restrict__ work) {
+    extern __shared__ uint32_t vc_ban[];                       // [ban_words] when the table is staged
+    __shared__ Best<VP_K> cand[VC_SEG];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid % WAVE, seg = tid / WAVE;
+    const int b = row / a.S, s = row - b * a.S;
+    if (s >= vc_live(a, b)) {
+        if (tid == 0) a.seq[row] = (int64_t)a.pad_idx;
+        return;
+    }
+    const uint32_t* ban = a.ban;
+    if (BAN && a.ban_lds) {
+        for (int i = tid; i < a.ban_words; i += VC_NT) vc_ban[i] = a.ban[i];
+        ban = vc_ban;
+        __syncthreads();
+    }
+    const Best<VP_L> own = vk_stream<BAN, false>(a.x + (size_t)row * (size_t)a.ldx, a.V, seg, VC_SEG, lane, ban, 0ull);
+    Best<VP_K> m;
+#pragma unroll
+    for (int k = 0; k < VP_K; ++k) m.k[k] = k < VP_L ? own.k[k] : 0ull;
+    if (m.k[VP_L - 1]) m.k[VP_L - 1] |= 1ull;                   // a full lane list: the lane may hold more behind it
+    m = vk_wave_merge<VP_K>(m);
+    if (lane == 0) cand[seg] = m;
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int k = 1; k < VC_SEG; ++k) m = vk_merge<VP_K>(m, cand[k]);
+        bool cut = false;
+#pragma unroll
+        for (int k = 0; k < VP_K; ++k) {
+            work[(size_t)row * VP_K + k] = cut ? VP_CUT : vk_id(m.k[k]);
+            cut = cut || (m.k[k] & 1ull);
+        }
+    }
+}
+
+// the wavefront's next VP_L unbanned ids of one row strictly BEHIND `floor` in the order (the scan's fallback; the ban table through the cache), the same in every lane
+__device__ __forceinline__ Best<VP_L> vk_row_behind(const float* p, int V, uint64_t floor, const uint32_t* ban, int lane) {
+    return vk_wave_merge<VP_L>(ban ? vk_stream<true, true>(p, V, 0, 1, lane, ban, floor) : vk_stream<false, true>(p, V, 0, 1, lane, ban, floor));
+}
+
+// grid = ceil(B / 4) workgroups of four wavefronts: wavefront = image, lane = position
+__global__ void __launch_bounds__(VC_SCAN_WAVES * WAVE) vocab_scan_k_kernel(VcArgs a, const int* __restrict__ work, int trigrams, int B) {
+    const int lane = threadIdx.x % WAVE, b = __builtin_amdgcn_readfirstlane(blockIdx.x * VC_SCAN_WAVES + threadIdx.x / WAVE);
+    if (b >= B) return;                                         // (whole wavefronts leave)
+    const int S = a.S, n = __builtin_amdgcn_readfirstlane(vc_live(a, b)), lo = a.repeat_min_id;
+    const bool live = lane < n;
+    const size_t row = (size_t)b * S + lane;
+    int c[VP_K];
+#pragma unroll
+    for (int k = 0; k < VP_K; ++k) c[k] = live ? work[row * VP_K + k] : VC_NONE;
+    int pick = VC_NONE, pm1 = -1, pm2 = -1;                     // this lane's pick and those of the two lanes before it, as they are made
+    int p1 = -1, p2 = -1;                                       // the picks of positions s - 1 and s - 2 (wave-uniform)
+    for (int s = 0; s < n; ++s) {
+        const int rep = (a.no_repeat && s > 0 && p1 >= lo) ? p1 : -1;
+        const bool tri = trigrams && s >= 3 && p1 >= lo && p2 >= lo;
+        const bool ex = tri && lane >= 2 && lane < s && pm2 == p2 && pm1 == p1 && pick >= lo;      // this lane's pick is trigram-blocked at s
+        const bool any = __ballot(ex) != 0ull;
+        int q = VC_NONE, tried = VC_NONE;                       // the pick; the last candidate found ineligible
+        bool found = false, cut = false;
+#pragma unroll
+        for (int k = 0; k < VP_K; ++k) {
+            if (!found && !cut) {
+                const int ck = __builtin_amdgcn_readlane(c[k], s);
+                if (ck == VC_NONE) found = true;                // (the row has no further unbanned id: pad_idx below)
+                else if (ck == VP_CUT) cut = true;
+                else if (ck != rep && !(any && __ballot(ex && pick == ck) != 0ull)) { found = true; q = ck; }
+                else tried = ck;
+            }
+        }
+        if (!found) {                                           // every known candidate is excluded: the row again, behind the last one tried (the first entry is never VP_CUT)
+            const float* const p = a.x + ((size_t)b * S + s) * (size_t)a.ldx;
+            uint64_t floor = vk_key(p[tried], tried);
+            while (!found) {
+                const Best<VP_L> m = vk_row_behind(p, a.V, floor, a.ban, lane);
+#pragma unroll
+                for (int k = 0; k < VP_L; ++k) {
+                    if (!found) {
+                        const int ck = __builtin_amdgcn_readfirstlane(vk_id(m.k[k]));
+                        if (ck == VC_NONE) found = true;
+                        else if (ck != rep && !(any && __ballot(ex && pick == ck) != 0ull)) { found = true; q = ck; }
+                    }
+                }
+                floor = m.k[VP_L - 1];
+            }
+        }
+        if (lane == s) pick = q;
+        if (lane == s + 1) pm1 = q;
+        if (lane == s + 2) pm2 = q;
+        p2 = p1; p1 = q;
+    }
+    bool was = false;
+    if (live) {
+        const int64_t old = a.seq[row];
+        float v = -INFINITY;
+        if (pick == VC_NONE) pick = a.pad_idx;                  // (fewer eligible ids than the rule needs: the caller's duty -- never an id outside the vocabulary)
+        else { v = a.x[row * (size_t)a.ldx + pick]; was = old == (int64_t)pick; }
+        a.seq[row] = (int64_t)pick;
+        if (a.row_chosen) a.row_chosen[row] = v;
+    }
+    const unsigned long long ch = __ballot(live && !was);
+    if (lane == 0 && a.changed) a.changed[b] = __popcll(ch);
+}
+
 }  // namespace
+
+size_t bofi::vocab_pick_work_bytes(int rows) { return (size_t)(rows > 0 ? rows : 0) * VP_K * sizeof(int); }
+
+const char* bofi::vocab_pick_check(const float* x, int ldx, int rows, int V, int S, int no_repeat, int block_trigrams, int repeat_min_id, const int64_t* seq,
+                                   const void* work, size_t work_bytes) {
+    if (const char* why = vocab_constrain_check(x, ldx, rows, V, S, no_repeat, repeat_min_id, seq)) return why;
+    if (block_trigrams != 0 && block_trigrams != 1) return "block_trigrams 0 or 1";
+    if (rows > 0 && (!work || work_bytes < vocab_pick_work_bytes(rows))) return "a workspace of bofi_vocab_pick_workspace(rows) bytes";
+    return nullptr;
+}
+
+int bofi::launch_vocab_pick(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int no_repeat,
+                            int block_trigrams, int repeat_min_id, int64_t* seq, float* row_chosen, int* changed, void* work, size_t work_bytes, hipStream_t st) {
+    if (vocab_pick_check(x, ldx, rows, V, S, no_repeat, block_trigrams, repeat_min_id, seq, work, work_bytes)) return BOFI_ERR_ARG;
+    if (rows == 0) return BOFI_OK;
+    VcArgs a{};
+    a.x = x; a.ldx = ldx; a.V = V; a.S = S; a.ntok = ntok; a.ntok_bias = ntok_bias; a.pad_idx = pad_idx; a.ban = ban_bits; a.ban_words = (V + 31) / 32;
+    a.ban_lds = a.ban_words <= VC_BAN_LDS_WORDS; a.no_repeat = no_repeat; a.repeat_min_id = repeat_min_id; a.seq = seq; a.row_chosen = row_chosen; a.changed = changed;
+    const int B = rows / S;
+    if (ban_bits) hipLaunchKernelGGL(vocab_candidates_k_kernel<true>, dim3(rows), dim3(VC_NT), a.ban_lds ? (size_t)a.ban_words * 4 : 0, st, a, (int*)work);
+    else hipLaunchKernelGGL(vocab_candidates_k_kernel<false>, dim3(rows), dim3(VC_NT), 0, st, a, (int*)work);
+    BOFI_CHECK_LAUNCH();
+    hipLaunchKernelGGL(vocab_scan_k_kernel, dim3((B + VC_SCAN_WAVES - 1) / VC_SCAN_WAVES), dim3(VC_SCAN_WAVES * WAVE), 0, st, a, (const int*)work, block_trigrams, B);
+    BOFI_CHECK_LAUNCH();
+    return BOFI_OK;
+}
+
+extern "C" int64_t bofi_vocab_pick_workspace(int rows) { return (int64_t)bofi::vocab_pick_work_bytes(rows); }
+
+extern "C" int bofi_vocab_pick(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int no_repeat,
+                               int block_trigrams, int repeat_min_id, int64_t* seq, float* row_chosen, int* changed, void* work, int64_t work_bytes, void* stream) {
+    if (const char* why = bofi::vocab_pick_check(x, ldx, rows, V, S, no_repeat, block_trigrams, repeat_min_id, seq, work, work_bytes < 0 ? 0 : (size_t)work_bytes))
+        return bofi::fail(BOFI_ERR_ARG, std::string("vocab_pick: ") + why);
+    return bofi::launch_vocab_pick(x, ldx, rows, V, S, ntok, ntok_bias, pad_idx, ban_bits, no_repeat, block_trigrams, repeat_min_id, seq, row_chosen, changed, work,
+                                   (size_t)work_bytes, (hipStream_t)stream);
+}
 
 int bofi::launch_vocab_constrain(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits,
                                  int no_repeat, int repeat_min_id, int64_t* seq, float* row_chosen, int* changed, hipStream_t st) {

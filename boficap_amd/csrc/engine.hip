@@ -109,7 +109,7 @@ struct bofi_engine {
     // with the defaults -- before it enqueues anything, so nothing of one call reaches the next; key_call() puts them into the graph key
     bofi_call_opts_t opt{};
     bool attn_out_set() const { return opt.attn_mean || opt.attn_heads || opt.attn_top_idx; }
-    bool pick_set() const { return opt.pick_ban || opt.pick_no_repeat; }      // the constrained pick (bofi_call_opts_t.pick_*) is on
+    bool pick_set(int flags) const { return opt.pick_ban || opt.pick_no_repeat || (flags & BOFI_FLAG_PICK_TRIGRAMS); }      // the constrained pick (bofi_call_opts_t.pick_*, BOFI_FLAG_PICK_TRIGRAMS) is on
     bool loop_ready = false;
     float* dbg_part = nullptr;
 
@@ -136,6 +136,7 @@ struct bofi_engine {
     float *mp_chosen = nullptr, *mp_plogp = nullptr, *mp_fresh_chosen = nullptr, *mp_fresh_plogp = nullptr;
     int *mp_round = nullptr, *mp_mask = nullptr;
     int* pick_changed = nullptr;                                        // [Bm] positions the constrained pick of the last filling pass changed (bofi_engine_pick_changed)
+    int* pick_work = nullptr; size_t pick_work_bytes = 0;               // bofi_vocab_pick's candidates [Bm*Sq][K] (BOFI_FLAG_PICK_TRIGRAMS; not on a fork without vocabulary buffers)
     std::vector<void*> qkv_dec;                                         // SAIC: q|k|v of every decoder layer [B*S, 3d] (the K / V cache)
     int *sa_rows = nullptr, *sa_nrows = nullptr;                        // decoder rows of the iteration's new phrases, their count
     uint64_t* d_seed = nullptr;                                         // per-call sampling seed (read by the captured sampling kernels)
@@ -327,6 +328,7 @@ struct bofi_engine {
     ENG_OK(dalloc(&mp_chosen, Bm * Sq)); ENG_OK(dalloc(&mp_plogp, Bm * Sq)); ENG_OK(dalloc(&mp_fresh_chosen, Bm * Sq)); ENG_OK(dalloc(&mp_fresh_plogp, Bm * Sq));
     ENG_OK(dalloc(&mp_round, Bm * Sq)); ENG_OK(dalloc(&mp_mask, Bm * Sq));
     ENG_OK(dalloc(&pick_changed, Bm));
+    if (!no_logits) { pick_work_bytes = bofi::vocab_pick_work_bytes((int)(Bm * Sq)); ENG_OK(dalloc(&pick_work, pick_work_bytes / sizeof(int))); }
     qkv_dec.assign(c.n_dec, nullptr);                  // allocated by the first semi-autoregressive decode
 
         return BOFI_OK;
@@ -993,12 +995,16 @@ int bofi_engine::enqueue_fill(const int* att_len, int B, int R, int flags, int64
     // (a round that another one follows: its ids are all the next round reads -- the log-probs it would write are overwritten: not stored)
     const int ids_only_on = bofi::knob(BOFI_REFINE_IDS_ONLY);      // developer knob: 0 = every round stores its log-probs
     // (with the constrained pick on every round stores them: the pick reads what the pass stored)
-    const int lsm = (flags & BOFI_FLAG_RAW_LOGITS) ? 0 : ((flags & BOFI_FLAG_IDS_ONLY) || (ids_only_on && round + 1 < rounds && lsrc && !pick_set()) ? 2 : 1);
+    const int lsm = (flags & BOFI_FLAG_RAW_LOGITS) ? 0 : ((flags & BOFI_FLAG_IDS_ONLY) || (ids_only_on && round + 1 < rounds && lsrc && !pick_set(flags)) ? 2 : 1);
     ENG_OK(bofi::launch_vocab_finalize(lg, M, cfg.vocab, S, lsm, st.last, -1, cfg.pad_idx, ep_seq, s, nullptr, nullptr, nullptr, nullptr,
                                        lsrc, gen.Npad, lsm ? ep_plogp : nullptr, lsm ? ep_chosen : nullptr));
     // the constrained pick (bofi_call_opts_t.pick_*), every pass: banned ids and adjacent repeats re-picked from the tensor the epilogue has just written (log-probs, or the
     // logits at the caller's pitch), so a following round is fed the constrained ids and the last one leaves seq / row_chosen those of the emitted ids
-    if (pick_set())
+    // BOFI_FLAG_PICK_TRIGRAMS: the K-candidate form (block_trigrams needs more than a row's two best ids), same point, same outputs
+    if (flags & BOFI_FLAG_PICK_TRIGRAMS)
+        ENG_OK(bofi::launch_vocab_pick(lg, cfg.vocab, M, cfg.vocab, S, st.last, -1, cfg.pad_idx, opt.pick_ban, opt.pick_no_repeat, 1, opt.pick_repeat_min_id, ep_seq,
+                                       lsm ? ep_chosen : nullptr, pick_changed, pick_work, pick_work_bytes, s));
+    else if (pick_set(flags))
         ENG_OK(bofi::launch_vocab_constrain(lg, cfg.vocab, M, cfg.vocab, S, st.last, -1, cfg.pad_idx, opt.pick_ban, opt.pick_no_repeat, opt.pick_repeat_min_id, ep_seq,
                                             lsm ? ep_chosen : nullptr, pick_changed, s));
     ENG_OK(refine_step(round));
@@ -1539,7 +1545,7 @@ static int check_opts(bofi_engine_t* e, int flags, const bofi_call_opts_t& o, in
     // the constrained pick
     if (o.pick_no_repeat != 0 && o.pick_no_repeat != 1) return fail(BOFI_ERR_ARG, "constrained pick: pick_no_repeat is 0 or 1");
     if (o.pick_repeat_min_id < 0) return fail(BOFI_ERR_ARG, "constrained pick: pick_repeat_min_id >= 0");
-    if (o.pick_ban || o.pick_no_repeat) {
+    if (o.pick_ban || o.pick_no_repeat || (flags & BOFI_FLAG_PICK_TRIGRAMS)) {
         if (which_call == CALL_SAIC) return fail(BOFI_ERR_STATE, "a constrained pick is set: it re-picks the non-autoregressive filling pass only, not the semi-autoregressive decode");
         if (flags & BOFI_FLAG_IDS_ONLY) return fail(BOFI_ERR_ARG, "constrained pick: not with BOFI_FLAG_IDS_ONLY (no distribution to re-pick from)");
         if (flags & BOFI_FLAG_MASK_PREDICT) return fail(BOFI_ERR_ARG, "constrained pick: not with BOFI_FLAG_MASK_PREDICT (a kept position would pin both neighbours)");

@@ -208,7 +208,7 @@ class BofiEngine:
                     want_logprob: bool = True, want_memory: bool = False, raw_logits: bool = False, graph: bool = False,
                     refine_rounds: int = 0, out: Optional[dict] = None, q1_group: int = 0, iter_cap: int = 0, phases: str = "", row_stats: bool = False,
                     ids_only: bool = False, refine_method: str = "feed_back", attn_topk: int = 0, attn_maps: bool = False, attn_heads: bool = False,
-                    attn_layer: int = -1, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7) -> dict:
+                    attn_layer: int = -1, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7, block_trigrams: bool = False) -> dict:
         """Greedy NAIC bound+fill decode.  Returns a dict of device tensors: seq [B,S] int64,
         seq_logprob [B,S,V] float32 (or None), phrase_num [B] int32, phrase_length [B,S] int32,
         phrase_syn [B,S] int64, bound_iters [1] int32, memory [B,R,d] float32 (or None).
@@ -239,12 +239,15 @@ class BofiEngine:
         ids of ``ban_ids`` are never emitted, and with ``no_repeat`` no position repeats the word (an id >= ``repeat_min_id``; 7 is the first word id) of the position before it
         -- each live position takes the best id the two rules leave.  Feed-back rounds feed the constrained ids back; ``seq`` and ``row_chosen`` are those of the emitted ids;
         ``out['constrained']`` (int32 [B]) counts the positions the last pass's constrained pick changed.  Not with ``ids_only`` or ``refine_method='mask_predict'``.  An empty
-        ``ban_ids`` without ``no_repeat`` is the plain decode: nothing is launched."""
+        ``ban_ids`` without ``no_repeat`` is the plain decode: nothing is launched.
+        ``block_trigrams`` (BOFI_FLAG_PICK_TRIGRAMS; bofi_vocab_pick's two launches in place of bofi_vocab_constrain's): in addition no word trigram (three ids >=
+        ``repeat_min_id``) stands twice in a caption -- a position whose two predecessors repeat an earlier bigram does not take the id that followed it there (the
+        reference's --block_trigrams as a hard block).  On by itself it turns the constrained pick on; ``ban_ids`` must then leave at least seq_length + 1 ids."""
         mp = self._refine_flag(refine_method, refine_rounds, raw_logits)
-        ban = self._pick_ban(ban_ids)
-        pick_on = ban is not None or bool(no_repeat)
+        ban = self._pick_ban(ban_ids, block_trigrams)
+        pick_on = ban is not None or bool(no_repeat) or bool(block_trigrams)
         if pick_on and (ids_only or mp):
-            raise hip.BofiHipError("ban_ids / no_repeat: not with ids_only (no distribution to re-pick from) or refine_method='mask_predict'")
+            raise hip.BofiHipError("ban_ids / no_repeat / block_trigrams: not with ids_only (no distribution to re-pick from) or refine_method='mask_predict'")
         if ids_only:
             if raw_logits:
                 raise hip.BofiHipError("ids_only: the raw logits are not produced")
@@ -283,11 +286,11 @@ class BofiEngine:
         if mp:
             o.refine_round = out["refine_round"].data_ptr()
         self._attn_opts(o, out, B, R, dev, attn_topk, attn_maps, attn_heads, attn_layer)
-        self._pick_opts(o, ban, no_repeat, repeat_min_id)
+        self._pick_opts(o, ban, no_repeat, repeat_min_id, block_trigrams)
         if pick_on and (out.get("constrained") is None or out["constrained"].numel() != B):
             out["constrained"] = torch.zeros(B, dtype=torch.int32, device=dev)
         flags = ((hip.FLAG_STRICT_Q1 if strict_q1 else 0) | (hip.FLAG_RAW_LOGITS if raw_logits else 0) | (hip.FLAG_GRAPH if graph else 0)
-                 | (refine_rounds << hip.FLAG_REFINE_SHIFT) | (hip.FLAG_IDS_ONLY if ids_only else 0) | mp)
+                 | (refine_rounds << hip.FLAG_REFINE_SHIFT) | (hip.FLAG_IDS_ONLY if ids_only else 0) | mp | (hip.FLAG_PICK_TRIGRAMS if block_trigrams else 0))
         if phases:
             if set(phases) - set("ebf"):
                 raise hip.BofiHipError("phases: a subset of 'ebf'")
@@ -300,23 +303,26 @@ class BofiEngine:
             hip.check(self._lib.bofi_engine_pick_changed(self._h, hip.ptr(out["constrained"]), B, hip.stream_ptr()), "bofi_engine_pick_changed")
         return out
 
-    def _pick_ban(self, ban_ids):
+    def _pick_ban(self, ban_ids, block_trigrams: bool = False):
         """The device bit table of a ban list (``hip.ban_bits``: ids outside 0..V-1 and a list that leaves fewer than two ids raise), kept per engine and id set;
-        None for no list or an empty one."""
+        None for no list or an empty one.  With ``block_trigrams`` the list must leave at least seq_length + 1 ids (a position can find up to seq_length ids excluded)."""
         if ban_ids is None:
             return None
         key = tuple(sorted({int(i) for i in ban_ids}))
         if not key:
             return None
+        if block_trigrams and self.cfg.tgt_vocab - len(key) < self.cfg.seq_length + 1:
+            raise hip.BofiHipError(f"ban_ids: {len(key)} of {self.cfg.tgt_vocab} ids banned -- with block_trigrams at least seq_length + 1 = {self.cfg.seq_length + 1} must stay")
         cache = self.__dict__.setdefault("_ban_tables", {})
         if key not in cache:
             cache[key] = hip.ban_bits(key, self.cfg.tgt_vocab, self.device)
         return cache[key]
 
     @staticmethod
-    def _pick_opts(o: "hip.BofiCallOpts", ban, no_repeat, repeat_min_id) -> None:
-        """The constrained pick of a call into its record ``o``; nothing is set when it is off (the record's zero tail)."""
-        if ban is None and not no_repeat:
+    def _pick_opts(o: "hip.BofiCallOpts", ban, no_repeat, repeat_min_id, block_trigrams=False) -> None:
+        """The constrained pick of a call into its record ``o``; nothing is set when it is off (the record's zero tail).  (``block_trigrams`` itself travels as a call
+        flag, BOFI_FLAG_PICK_TRIGRAMS; it reads ``repeat_min_id`` from the record.)"""
+        if ban is None and not no_repeat and not block_trigrams:
             return
         if int(repeat_min_id) < 0:
             raise hip.BofiHipError("repeat_min_id must be >= 0")
@@ -529,29 +535,29 @@ class BofiEngine:
 
     def fill_naic(self, ext_syn: torch.Tensor, last: torch.Tensor, R: int, att_len: Optional[torch.Tensor] = None, *, strict_q1: bool = True,
                   raw_logits: bool = False, refine_rounds: int = 0, refine_method: str = "feed_back", attn_topk: int = 0, attn_maps: bool = False,
-                  attn_heads: bool = False, attn_layer: int = -1, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7):
+                  attn_heads: bool = False, attn_layer: int = -1, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7, block_trigrams: bool = False):
         """The filling pass alone on a given slot layout (``ext_syn`` int32 [B, S+2], ``last`` int32 [B]) and the memory of the
         preceding ``encode``: (seq int64 [B, S], seq_logprob float32 [B, S, V]); with ``refine_method='mask_predict'`` (as ``decode_naic``) a third
         element, refine_round int32 [B, S].  With ``attn_topk`` / ``attn_maps`` / ``attn_heads`` (as ``decode_naic``) a last element, a dict of the attention tensors
-        ('attn', 'attn_heads', 'attn_top', 'attn_top_w': those asked for).  ``ban_ids`` / ``no_repeat`` / ``repeat_min_id`` as ``decode_naic``: that dict (the last element)
+        ('attn', 'attn_heads', 'attn_top', 'attn_top_w': those asked for).  ``ban_ids`` / ``no_repeat`` / ``repeat_min_id`` / ``block_trigrams`` as ``decode_naic``: that dict (the last element)
         then carries 'constrained', int32 [B]."""
         mp = self._refine_flag(refine_method, refine_rounds, raw_logits)
-        ban = self._pick_ban(ban_ids)
-        pick_on = ban is not None or bool(no_repeat)
+        ban = self._pick_ban(ban_ids, block_trigrams)
+        pick_on = ban is not None or bool(no_repeat) or bool(block_trigrams)
         if pick_on and mp:
-            raise hip.BofiHipError("ban_ids / no_repeat: not with refine_method='mask_predict'")
+            raise hip.BofiHipError("ban_ids / no_repeat / block_trigrams: not with refine_method='mask_predict'")
         B = ext_syn.size(0)
         if ext_syn.dtype != torch.int32 or last.dtype != torch.int32 or ext_syn.size(1) != self.cfg.bound_len or last.numel() != B:
             raise hip.BofiHipError("ext_syn must be int32 [B, S+2] and last int32 [B]")
         S, V, dev = self.cfg.seq_length, self.cfg.tgt_vocab, ext_syn.device
         seq = torch.empty(B, S, dtype=torch.int64, device=dev)
         lp = torch.empty(B, S, V, dtype=torch.float32, device=dev)
-        flags = (hip.FLAG_STRICT_Q1 if strict_q1 else 0) | (hip.FLAG_RAW_LOGITS if raw_logits else 0) | (refine_rounds << hip.FLAG_REFINE_SHIFT) | mp
+        flags = (hip.FLAG_STRICT_Q1 if strict_q1 else 0) | (hip.FLAG_RAW_LOGITS if raw_logits else 0) | (refine_rounds << hip.FLAG_REFINE_SHIFT) | mp | (hip.FLAG_PICK_TRIGRAMS if block_trigrams else 0)
         rnd = torch.empty(B, S, dtype=torch.int32, device=dev) if mp else None
         o = hip.BofiCallOpts(refine_round=rnd.data_ptr() if mp else None)
         attn = {}
         self._attn_opts(o, attn, B, int(R), dev, attn_topk, attn_maps, attn_heads, attn_layer)
-        self._pick_opts(o, ban, no_repeat, repeat_min_id)
+        self._pick_opts(o, ban, no_repeat, repeat_min_id, block_trigrams)
         hip.check(self._lib.bofi_engine_fill_naic(self._h, hip.ptr(ext_syn.contiguous()), hip.ptr(last.contiguous()), B, R, hip.ptr(att_len), flags,
                                                   hip.ptr(seq), hip.ptr(lp), C.byref(o), hip.stream_ptr()), "bofi_engine_fill_naic")
         if pick_on:
@@ -581,19 +587,22 @@ class DecodePipeline:
     def __init__(self, engine: "BofiEngine", *, in_flight: Optional[int] = None, batches_per_launch: int = 16, strict_q1: bool = True, stats: bool = True,
                  keep_logprob: bool = False, region_buckets=(36, 48, 64, 80, 100, 128), fused_vocab: bool = False,
                  refine_rounds: int = 0, refine_method: str = "feed_back", attn_topk: int = 0, keep_attn: bool = False, ban_ids=None, no_repeat: bool = False,
-                 repeat_min_id: int = 7):
+                 repeat_min_id: int = 7, block_trigrams: bool = False):
         BofiEngine._refine_flag(refine_method, refine_rounds, False)
-        # ban_ids / no_repeat / repeat_min_id: the constrained pick of BofiEngine.decode_naic on every launch; every yielded dict then carries constrained int32 [b].  Not
+        # ban_ids / no_repeat / repeat_min_id / block_trigrams: the constrained pick of BofiEngine.decode_naic on every launch; every yielded dict then carries constrained int32 [b].  Not
         # with fused_vocab (ids-only launches keep no distribution to re-pick from) or 'mask_predict'
         self.ban_ids = tuple(sorted({int(i) for i in ban_ids})) if ban_ids is not None else ()
         self.no_repeat, self.repeat_min_id = bool(no_repeat), int(repeat_min_id)
-        self.pick_on = bool(self.ban_ids) or self.no_repeat
+        self.block_trigrams = bool(block_trigrams)
+        self.pick_on = bool(self.ban_ids) or self.no_repeat or self.block_trigrams
         if self.pick_on and fused_vocab:
-            raise hip.BofiHipError("ban_ids / no_repeat: not with fused_vocab (the ids-only launches keep no distribution to re-pick from)")
+            raise hip.BofiHipError("ban_ids / no_repeat / block_trigrams: not with fused_vocab (the ids-only launches keep no distribution to re-pick from)")
         if self.pick_on and refine_method == "mask_predict":
-            raise hip.BofiHipError("ban_ids / no_repeat: not with refine_method='mask_predict'")
+            raise hip.BofiHipError("ban_ids / no_repeat / block_trigrams: not with refine_method='mask_predict'")
         if self.ban_ids:
             hip.ban_bits(self.ban_ids, engine.cfg.tgt_vocab)        # (checked here, on the host: a bad list raises before anything is launched)
+            if self.block_trigrams and engine.cfg.tgt_vocab - len(self.ban_ids) < engine.cfg.seq_length + 1:
+                raise hip.BofiHipError("ban_ids: with block_trigrams at least seq_length + 1 ids must stay")
         # attn_topk = K > 0: every yielded dict carries attn_top int32 / attn_top_w float32 [b, S, K] -- each position's K heaviest regions (BofiEngine.decode_naic) -- on the
         # host, through the pinned buffers (rows x S x K x 8 bytes per launch); keep_attn: also attn [b, S, R of the launch's region bucket] on the device, as keep_logprob
         if not 0 <= int(attn_topk) <= 8:
@@ -784,7 +793,7 @@ class DecodePipeline:
         sl["out"] = e.decode_naic(feats, lens, strict_q1=self.strict_q1, graph=True, out=sl["out"] if sl["out"] is not None and sl["out"]["seq"].shape[0] == rows else None,
                                   q1_group=b if nb > 1 else 0, row_stats=self.stats, want_logprob=self.keep_logprob, ids_only=self.fused_vocab,
                                   refine_rounds=self.refine_rounds, refine_method=self.refine_method, attn_topk=self.attn_topk, attn_maps=self.keep_attn,
-                                  ban_ids=self.ban_ids or None, no_repeat=self.no_repeat, repeat_min_id=self.repeat_min_id)
+                                  ban_ids=self.ban_ids or None, no_repeat=self.no_repeat, repeat_min_id=self.repeat_min_id, block_trigrams=self.block_trigrams)
         out = sl["out"]
         small = {k2: out[k2] for k2 in ("seq", "phrase_num", "phrase_length", "phrase_syn", "bound_saturated")}
         if self.refine_method == "mask_predict":

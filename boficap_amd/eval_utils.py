@@ -204,29 +204,30 @@ def caption_surface(model, eval_kwargs):
 def constraint_of(eval_kwargs, vocab, mode: str = "NAIC", sample_n: int = 1):
     """The constrained pick an evaluation asks for, as the keywords of ``TransformerModel.decode_many``: {} when ``suppress_UNK``, ``decoding_constraint`` (the
     reference's names; both default to 0 here: on this path the reference's options do nothing, and the defaults keep the captions) and ``ban_words`` (a list of
-    words, or 'W1,W2,...') are all off, else {'ban_ids': sorted ids, 'no_repeat': bool}.  Words resolve to ids as the bad-ending words do (``surface.ids_of`` on
+    words, or 'W1,W2,...') and ``block_trigrams`` (the reference's name and default, 0: no word trigram twice in a caption) are all off, else {'ban_ids': sorted ids,
+    'no_repeat': bool}, with 'block_trigrams': True beside them when that option is on.  Words resolve to ids as the bad-ending words do (``surface.ids_of`` on
     ``vocab``; a word the vocabulary does not hold names no id).  ValueError where the options cannot apply: SAIC mode, ``fused_vocab``, mask-predict, sampling."""
     kw = eval_kwargs
     words = kw.get("ban_words") or []
     words = [w for w in words.split(",") if w] if isinstance(words, str) else list(words)
-    unk, rep = int(kw.get("suppress_UNK", 0)) == 1, int(kw.get("decoding_constraint", 0)) == 1
-    if not (unk or rep or words):
+    unk, rep, tri = int(kw.get("suppress_UNK", 0)) == 1, int(kw.get("decoding_constraint", 0)) == 1, int(kw.get("block_trigrams", 0) or 0) == 1
+    if not (unk or rep or words or tri):
         return {}
     if mode != "NAIC":
-        raise ValueError("suppress_UNK / decoding_constraint / ban_words constrain the non-autoregressive filling pass: inference_mode 'NAIC' only")
+        raise ValueError("suppress_UNK / decoding_constraint / ban_words / block_trigrams constrain the non-autoregressive filling pass: inference_mode 'NAIC' only")
     if kw.get("fused_vocab", False):
-        raise ValueError("suppress_UNK / decoding_constraint / ban_words: not with fused_vocab (no distribution to re-pick from)")
+        raise ValueError("suppress_UNK / decoding_constraint / ban_words / block_trigrams: not with fused_vocab (no distribution to re-pick from)")
     if kw.get("refine_method", "feed_back") == "mask_predict":
-        raise ValueError("suppress_UNK / decoding_constraint / ban_words: not with refine_method 'mask_predict'")
+        raise ValueError("suppress_UNK / decoding_constraint / ban_words / block_trigrams: not with refine_method 'mask_predict'")
     if int(sample_n) > 1:
-        raise ValueError("suppress_UNK / decoding_constraint / ban_words constrain greedy picks: not with sample_n > 1")
+        raise ValueError("suppress_UNK / decoding_constraint / ban_words / block_trigrams constrain greedy picks: not with sample_n > 1")
     if (unk or words) and not vocab:
         raise ValueError("suppress_UNK / ban_words need a vocabulary ({str(id): word})")
     from .surface import ids_of
     ids = ids_of(vocab, set(words) | ({"UNK"} if unk else set())) if (unk or words) else []
-    if not ids and not rep:
+    if not ids and not rep and not tri:
         return {}                                                # (no such word in this vocabulary: nothing is banned and nothing launched)
-    return {"ban_ids": ids, "no_repeat": rep}
+    return dict({"ban_ids": ids, "no_repeat": rep}, **({"block_trigrams": True} if tri else {}))
 
 
 def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
@@ -245,7 +246,7 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
         raise ValueError("attn_topk reads the non-autoregressive filling pass's cross-attention: inference_mode 'NAIC' only")
     if attn_topk:
         refine["attn_topk"] = attn_topk
-    # suppress_UNK / decoding_constraint / ban_words: the constrained pick (constraint_of); with language stats, constrained_rate = changed / emitted positions
+    # suppress_UNK / decoding_constraint / ban_words / block_trigrams: the constrained pick (constraint_of); with language stats, constrained_rate = changed / emitted positions
     pick = constraint_of(kw, kw.get("vocab") or getattr(model, "vocab", None), mode, sample_n)
     refine.update(pick)
     remove, surface_stats = int(kw.get("remove_bad_endings", 0)) == 1, int(kw.get("surface_stats", 0)) == 1

@@ -20,6 +20,7 @@ FLAG_PHASE_ENCODE, FLAG_PHASE_BOUND, FLAG_PHASE_FILL = 32, 64, 128
 FLAG_SAIC_LAYOUT_ONLY = 4096
 FLAG_IDS_ONLY = 8192
 FLAG_MASK_PREDICT = 16384
+FLAG_PICK_TRIGRAMS = 32768
 FORK_IDS_ONLY = 1
 ABI_VERSION = 5
 
@@ -134,6 +135,8 @@ SIGNATURES = {
     "bofi_attn_maps": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, C.c_float, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
     "bofi_vocab_constrain": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P]),
     "bofi_engine_pick_changed": (_I, [_P, _P, _I, _P]),
+    "bofi_vocab_pick_workspace": (_I64, [_I]),
+    "bofi_vocab_pick": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _I64, _P]),
     "bofi_caption_trim": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     "bofi_sentence_lookup": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
 }
@@ -312,6 +315,30 @@ def vocab_constrain(x, V, S, seq, *, ntok=None, ntok_bias=0, pad_idx=0, ban=None
             raise BofiHipError(f"vocab_constrain: {name} must be a contiguous {dt} device tensor of {n} elements")
     check(lib().bofi_vocab_constrain(ptr(x), x.stride(0), rows, int(V), int(S), ptr(ntok), int(ntok_bias), int(pad_idx), ptr(ban), 1 if no_repeat else 0, int(repeat_min_id),
                                      ptr(seq), ptr(row_chosen), ptr(changed), stream_ptr()), "bofi_vocab_constrain")
+
+
+def vocab_pick(x, V, S, seq, *, ntok=None, ntok_bias=0, pad_idx=0, ban=None, no_repeat=False, block_trigrams=False, repeat_min_id=7, row_chosen=None, changed=None,
+               work=None):
+    """``bofi_vocab_pick`` on torch tensors: ``vocab_constrain``'s arguments plus ``block_trigrams`` and ``work``, an int32 device workspace of at least
+    ``bofi_vocab_pick_workspace(rows)`` bytes (None: one is made).  Two launches on the current stream, no synchronisation."""
+    import torch
+    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or not x.is_cuda:
+        raise BofiHipError("vocab_pick: x must be a 2-d float32 device tensor with unit column stride")
+    rows = x.size(0)
+    if x.size(1) < V or S < 1 or rows % S:
+        raise BofiHipError("vocab_pick: x needs V columns and a multiple of S rows")
+    B = rows // S
+    if work is None:
+        work = torch.empty(max(1, lib().bofi_vocab_pick_workspace(rows) // 4), dtype=torch.int32, device=x.device)
+    for name, t, dt, n in (("seq", seq, torch.int64, rows), ("ntok", ntok, torch.int32, B), ("ban", ban, torch.int32, (V + 31) // 32),
+                           ("row_chosen", row_chosen, torch.float32, rows), ("changed", changed, torch.int32, B), ("work", work, torch.int32, None)):
+        if t is None and name != "seq":
+            continue
+        if t is None or t.dtype != dt or (n is not None and t.numel() != n) or not t.is_cuda or not t.is_contiguous():
+            raise BofiHipError(f"vocab_pick: {name} must be a contiguous {dt} device tensor" + ("" if n is None else f" of {n} elements"))
+    check(lib().bofi_vocab_pick(ptr(x), x.stride(0), rows, int(V), int(S), ptr(ntok), int(ntok_bias), int(pad_idx), ptr(ban), 1 if no_repeat else 0,
+                                1 if block_trigrams else 0, int(repeat_min_id), ptr(seq), ptr(row_chosen), ptr(changed), ptr(work), work.numel() * 4, stream_ptr()),
+          "bofi_vocab_pick")
 
 
 def gemm_flops(reset: bool = False):

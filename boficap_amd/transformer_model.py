@@ -243,7 +243,7 @@ class TransformerModel(nn.Module):
 
     def decode_many(self, batches, *, batches_per_launch: int = 16, in_flight: Optional[int] = None, stats: bool = True, keep_logprob: bool = False,
                     fused_vocab: bool = False, refine_rounds: int = 0, refine_method: str = "feed_back", attn_topk: int = 0, keep_attn: bool = False,
-                    ban_ids=None, no_repeat: bool = False):
+                    ban_ids=None, no_repeat: bool = False, block_trigrams: bool = False):
         """Greedy NAIC decode of MANY loader batches at the engine's throughput -- the eval loop of the reference (eval_utils.py:456-460: one synchronised
         ``model(..., mode='sample')`` per batch, which is what ``_sample`` reproduces) as a pipeline: ``in_flight`` engine forks on overlapping streams,
         ``batches_per_launch`` consecutive batches per launch (quirk Q1 per batch: every batch's result is its own decode's), features copied from (pinned)
@@ -260,19 +260,19 @@ class TransformerModel(nn.Module):
         ``attn_topk`` = K > 0: every dict also carries attn_top int32 / attn_top_w float32 [b, S, K], each position's K heaviest image regions under the last decoder
         layer's mean cross-attention, in descending order (-1 / 0 past an image's region count and where no word stands); ``keep_attn``: also the whole map attn
         [b, S, R] on the device (R: the launch's region bucket, the padding columns zero).
-        ``ban_ids`` / ``no_repeat``: the constrained pick of ``BofiEngine.decode_naic`` on every launch -- the listed ids are never emitted, no word stands twice in a row --;
-        every dict then carries constrained int32 [b], the positions per image it changed.  Not with ``fused_vocab`` or 'mask_predict'."""
+        ``ban_ids`` / ``no_repeat`` / ``block_trigrams``: the constrained pick of ``BofiEngine.decode_naic`` on every launch -- the listed ids are never emitted, no word
+        stands twice in a row, no word trigram stands twice in a caption --; every dict then carries constrained int32 [b], the positions per image it changed.  Not with ``fused_vocab`` or 'mask_predict'."""
         from .engine import DecodePipeline
         eng = self.engine()
         ban_ids = tuple(sorted({int(i) for i in ban_ids})) if ban_ids is not None else ()
         key = (id(eng), batches_per_launch, in_flight, stats, keep_logprob, self.strict_reference, fused_vocab, int(refine_rounds), refine_method, int(attn_topk), bool(keep_attn),
-               ban_ids, bool(no_repeat))
+               ban_ids, bool(no_repeat), bool(block_trigrams))
         cached = self.__dict__.get("_pipeline")
         if cached is None or cached[0] != key:
             cached = self.__dict__["_pipeline"] = (key, DecodePipeline(eng, in_flight=in_flight, batches_per_launch=batches_per_launch, strict_q1=self.strict_reference,
                                                                        stats=stats, keep_logprob=keep_logprob, fused_vocab=fused_vocab,
                                                                        refine_rounds=refine_rounds, refine_method=refine_method, attn_topk=attn_topk, keep_attn=keep_attn,
-                                                                       ban_ids=ban_ids, no_repeat=no_repeat))
+                                                                       ban_ids=ban_ids, no_repeat=no_repeat, block_trigrams=block_trigrams))
 
         def items():
             from .features import RaggedBatch
@@ -330,22 +330,24 @@ class TransformerModel(nn.Module):
             rkw.update(attn_topk=attn_topk, attn_maps=attn_maps, attn_layer=attn_layer)
         self.last_attn = None
         # opt['suppress_UNK'] / opt['decoding_constraint'] (the reference's names and defaults, AttModel.py:315-316: it applies them on its autoregressive paths only) and
-        # opt['ban_ids']: the constrained pick of the NAIC filling pass (BofiEngine.decode_naic); the 6-tuple stays, the per-image counts of changed positions land in
+        # opt['ban_ids'] and opt['block_trigrams'] (the reference's name and default, 0; AttModel.py:316: there a penalty on the autoregressive paths, here a hard block
+        # that SAIC mode refuses): the constrained pick of the NAIC filling pass (BofiEngine.decode_naic); the 6-tuple stays, the per-image counts of changed positions land in
         # self.last_constrained (None when nothing was constrained).  SAIC mode ignores the reference's two options as the reference does
         suppress_unk, no_repeat = int(opt.get("suppress_UNK", 0)), int(opt.get("decoding_constraint", 0))
         ban_ids = [int(i) for i in (opt.get("ban_ids") or ())]
+        block_trigrams = int(opt.get("block_trigrams", 0) or 0)
         self.last_constrained = None
-        if ban_ids and train_mode != "NAIC":
-            raise hip.BofiHipError("ban_ids constrain the non-autoregressive filling pass: train_mode 'NAIC' only")
+        if (ban_ids or block_trigrams) and train_mode != "NAIC":
+            raise hip.BofiHipError("ban_ids / block_trigrams constrain the non-autoregressive filling pass: train_mode 'NAIC' only")
         if train_mode == "NAIC":
             if suppress_unk:
                 ban_ids = ban_ids + [int(k) for k, v in self.vocab.items() if v == "UNK"]
-            if ban_ids or no_repeat:
+            if ban_ids or no_repeat or block_trigrams:
                 if sample_method == "sample":
-                    raise hip.BofiHipError("suppress_UNK / decoding_constraint / ban_ids constrain greedy picks: not with sample_method='sample'")
+                    raise hip.BofiHipError("suppress_UNK / decoding_constraint / ban_ids / block_trigrams constrain greedy picks: not with sample_method='sample'")
                 if refine_method == "mask_predict":
-                    raise hip.BofiHipError("suppress_UNK / decoding_constraint / ban_ids: not with refine_method='mask_predict'")
-                rkw.update(ban_ids=ban_ids or None, no_repeat=bool(no_repeat))
+                    raise hip.BofiHipError("suppress_UNK / decoding_constraint / ban_ids / block_trigrams: not with refine_method='mask_predict'")
+                rkw.update(ban_ids=ban_ids or None, no_repeat=bool(no_repeat), block_trigrams=bool(block_trigrams))
         eng = self.engine()
         torch.cuda.synchronize()                                  # the reference does (AttModel.py:337)
         start = time.time()

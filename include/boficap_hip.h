@@ -378,7 +378,8 @@ typedef struct bofi_call_opts {
      * row_chosen those of the emitted ids (row_plogp, a figure of the distribution, stays).  Every pass then stores its log-probs (the pick reads what the pass stored), and the
      * per-image counts of re-picked positions of the last pass are read with bofi_engine_pick_changed.  Under BOFI_FLAG_RAW_LOGITS the pick is over logits.
      * BOFI_ERR_ARG before anything is enqueued: pick_no_repeat outside {0, 1}, pick_repeat_min_id < 0; on together with BOFI_FLAG_IDS_ONLY (no distribution to re-pick from) or
-     * BOFI_FLAG_MASK_PREDICT (a kept position would pin both neighbours), or seq_length > 64.  decode_saic with the options on is BOFI_ERR_STATE. */
+     * BOFI_FLAG_MASK_PREDICT (a kept position would pin both neighbours), or seq_length > 64.  decode_saic with the options on is BOFI_ERR_STATE.
+     * BOFI_FLAG_PICK_TRIGRAMS adds block_trigrams to the pick (and turns it on by itself): a per-call flag, not a field -- the record stays 128 bytes. */
     const uint32_t* pick_ban; int pick_no_repeat; int pick_repeat_min_id;
 } bofi_call_opts_t;
 
@@ -465,6 +466,13 @@ void* bofi_engine_stream(bofi_engine_t* e);
                                        tensor -- the rows of kept positions are that pass's re-prediction, not the distribution that emitted the token; emitted_round goes to
                                        bofi_call_opts_t.refine_round.  Costs T + 1 launches of bofi_mask_predict_step's kernel per decode over feed-back.  BOFI_ERR_ARG before any
                                        launch: T = 0, BOFI_FLAG_RAW_LOGITS, BOFI_FLAG_SAMPLE, bofi_engine_decode_saic, seq_length > 64. */
+#define BOFI_FLAG_PICK_TRIGRAMS 32768 /* decode_naic / fill_naic (phased form included): block_trigrams on the constrained pick (bofi_vocab_pick states the rule; the reference's
+                                       --block_trigrams, AttModel.py:362-388, as a HARD block and on the non-autoregressive path).  The flag alone turns the constrained pick on;
+                                       with it the pick of every filling pass is bofi_vocab_pick's two launches (K candidates per row in an engine workspace) with
+                                       bofi_call_opts_t.pick_ban / pick_no_repeat / pick_repeat_min_id as given, at the same point and with the same outputs
+                                       (bofi_engine_pick_changed included).  The caller's ban table leaves at least seq_length + 1 ids.  Refused as the pick_* fields are, before
+                                       anything is enqueued: BOFI_ERR_ARG with BOFI_FLAG_IDS_ONLY, with BOFI_FLAG_MASK_PREDICT or at seq_length > 64; BOFI_ERR_STATE on
+                                       bofi_engine_decode_saic.  Without the flag nothing new is launched.  Part of the graph key, as every flag. */
 
 /* model(fc, att, att_masks, opt={'train_mode':'NAIC','sample_method':'greedy'}, mode='sample'):
  * AttModel._sample AttModel.py:307-338,419-429 -> _prepare_feature TransformerModel.py:1674-1690
@@ -796,6 +804,23 @@ int bofi_attn_maps(const void* q, int ldq, const void* k, int ldk, int dtype, in
  * and leaves the row's two candidate ids packed in seq[row]; then one wavefront per image runs the scan.  No workspace. */
 int bofi_vocab_constrain(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int no_repeat,
                          int repeat_min_id, int64_t* seq, float* row_chosen, int* changed, void* stream);
+
+/* bofi_vocab_constrain's K-candidate form, with block_trigrams.  Arguments, order, ban table, no_repeat and repeat_min_id are bofi_vocab_constrain's; in addition, with
+ * block_trigrams = 1: p[0 .. s-1] being the constrained picks of the image's earlier live positions, id c is TRIGRAM-BLOCKED at position s when s >= 3 and there is a j
+ * with 2 <= j <= s - 1, p[j-2] == p[s-2], p[j-1] == p[s-1] and p[j] == c, all three ids of that trigram >= repeat_min_id (words; pad / BOS / EOS / label ids never form a
+ * blocked trigram).  Position s takes the first id in the order that is not banned, not excluded by no_repeat and not trigram-blocked.  The blocked set is the reference's
+ * (AttModel.py:362-388 records (seq[t-3], seq[t-2]) -> seq[t-1] from t = 3 and looks (seq[t-2], seq[t-1]) up); the block is HARD where the reference adds a penalty
+ * ("alpha -> infty works best" there), which keeps the pick free of float arithmetic.
+ *   work / work_bytes: a device workspace of at least bofi_vocab_pick_workspace(rows) bytes (int32 [rows, K], K a compile-time constant <= 8), 4-byte aligned.
+ *   seq keeps the ids that stood there until the scan overwrites them: `changed` counts against those.
+ * The result is the rule's for EVERY input: where all the candidates known of a row are ineligible the image's wavefront streams that one row again for the next ids behind them,
+ * under the same order, until one is eligible.  A row with no eligible id at all gets pad_idx (never an id outside the vocabulary): the caller's ban table leaves at least
+ * S + 1 ids when block_trigrams is on.  With block_trigrams = 0 the outputs equal bofi_vocab_constrain's.
+ * BOFI_ERR_ARG with a message and no launch: what bofi_vocab_constrain refuses, block_trigrams outside {0, 1}, rows > 0 with a NULL or too small workspace.
+ * Two launches, deterministic, no atomics, no float arithmetic. */
+int64_t bofi_vocab_pick_workspace(int rows);
+int bofi_vocab_pick(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int no_repeat,
+                    int block_trigrams, int repeat_min_id, int64_t* seq, float* row_chosen, int* changed, void* work, int64_t work_bytes, void* stream);
 
 /* The bad-ending trim of the reference's decode_sequence (captioning/utils/misc.py:75-82, REMOVE_BAD_ENDINGS) and the flag of its count_bad
  * (captioning/utils/eval_utils.py:32-37), on id rows.  seq int64 [rows, S], 1 <= S <= 64.  The caption of a row is its ids before the first id <= limit

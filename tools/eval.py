@@ -95,13 +95,16 @@ def main():
                     "reference's option, which does nothing on its non-autoregressive path; so the default here is 0, not its 1: the defaults keep the captions)")
     ap.add_argument("--decoding_constraint", type=int, default=0, choices=[0, 1], help="NAIC only: 1 = no word stands twice in a row -- a position that would repeat its "
                     "left neighbour takes its second-best word (the reference's option, applied there on the autoregressive paths only)")
+    ap.add_argument("--block_trigrams", type=int, default=0, choices=[0, 1], help="NAIC only: 1 = no word trigram stands twice in a caption -- a position whose two left "
+                    "neighbours repeat an earlier pair of words does not take the word that followed that pair (the reference's option, applied there on the autoregressive "
+                    "paths only and as a penalty; here a hard block)")
     ap.add_argument("--ban_words", default="", help="NAIC only: W1,W2,... never appear in a caption (resolved to ids as --bad_endings resolves its words)")
     args = ap.parse_args()
     try:                                                         # (before anything is loaded; the words are resolved once the vocabulary is)
         from boficap_amd import eval_utils as _eu
         _eu.constraint_of(vars(args), {"0": "UNK"}, args.inference_mode, args.sample_n)
     except ValueError as e:
-        ap.error("--suppress_UNK / --decoding_constraint / --ban_words: " + str(e))
+        ap.error("--suppress_UNK / --decoding_constraint / --ban_words / --block_trigrams: " + str(e))
     if (args.remove_bad_endings or args.surface_stats) and not (args.infos_path or args.bad_endings):
         ap.error("--remove_bad_endings / --surface_stats need the ids of the bad-ending words: --infos_path (a vocabulary) or --bad_endings W1,W2,...")
     if args.surface_stats and args.sample_n > 1 and not (args.input_label_npz and args.input_json):
@@ -188,7 +191,7 @@ def main():
         src = args.input_label_npz if args.input_label_npz.endswith((".h5", ".hdf5")) else dict(np.load(args.input_label_npz))
         store = LabelStore(src, pad_idx=c.pad_idx, bos_idx=c.bos_idx, eos_idx=c.eos_idx, len_idx=c.len_idx)
     pick = eval_utils.constraint_of(vars(args), vocab or opt.vocab, args.inference_mode, args.sample_n)
-    pick_opt = {"ban_ids": pick["ban_ids"], "decoding_constraint": int(pick["no_repeat"])} if pick else {}      # (the same, in mode='sample''s names)
+    pick_opt = {"ban_ids": pick["ban_ids"], "decoding_constraint": int(pick["no_repeat"]), "block_trigrams": int(pick.get("block_trigrams", False))} if pick else {}      # (the same, in mode='sample''s names)
     changed, emitted = 0, 0
     results, seconds, rows, stats = [], 0.0, [], ([], [])
     store_loss = store is not None and not args.use_box          # (mode='forward' is not built for F = 2053: box features are decode-only)
