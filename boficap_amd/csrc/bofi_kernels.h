@@ -240,6 +240,12 @@ const char* vocab_pick_check(const float* x, int ldx, int rows, int V, int S, in
                              size_t work_bytes);
 int launch_vocab_pick(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int no_repeat,
                       int block_trigrams, int repeat_min_id, int64_t* seq, float* row_chosen, int* changed, void* work, size_t work_bytes, hipStream_t st);
+// ---- required words behind the filling pass (force.hip): the placement of at most 8 ids per image that costs the least log-prob (bofi_vocab_require states the rule);
+// ntok / ban_bits / row_chosen / moved may be NULL.  One launch, no workspace
+const char* vocab_require_check(const float* x, int ldx, int rows, int V, int S, const int* words, int K, int no_repeat, int repeat_min_id, const int64_t* seq,
+                                const int* pos);      // NULL, or what is wrong (BOFI_ERR_ARG)
+int launch_vocab_require(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, const int* words, int K, const uint32_t* ban_bits,
+                         int no_repeat, int repeat_min_id, int64_t* seq, float* row_chosen, int* pos, int* moved, hipStream_t st);
 
 int launch_set_u64(uint64_t* p, uint64_t v, hipStream_t s);
 int launch_zero_f32(float* p, size_t n, hipStream_t s);

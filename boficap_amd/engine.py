@@ -208,7 +208,7 @@ class BofiEngine:
                     want_logprob: bool = True, want_memory: bool = False, raw_logits: bool = False, graph: bool = False,
                     refine_rounds: int = 0, out: Optional[dict] = None, q1_group: int = 0, iter_cap: int = 0, phases: str = "", row_stats: bool = False,
                     ids_only: bool = False, refine_method: str = "feed_back", attn_topk: int = 0, attn_maps: bool = False, attn_heads: bool = False,
-                    attn_layer: int = -1, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7, block_trigrams: bool = False) -> dict:
+                    attn_layer: int = -1, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7, block_trigrams: bool = False, require_ids=None) -> dict:
         """Greedy NAIC bound+fill decode.  Returns a dict of device tensors: seq [B,S] int64,
         seq_logprob [B,S,V] float32 (or None), phrase_num [B] int32, phrase_length [B,S] int32,
         phrase_syn [B,S] int64, bound_iters [1] int32, memory [B,R,d] float32 (or None).
@@ -242,10 +242,23 @@ class BofiEngine:
         ``ban_ids`` without ``no_repeat`` is the plain decode: nothing is launched.
         ``block_trigrams`` (BOFI_FLAG_PICK_TRIGRAMS; bofi_vocab_pick's two launches in place of bofi_vocab_constrain's): in addition no word trigram (three ids >=
         ``repeat_min_id``) stands twice in a caption -- a position whose two predecessors repeat an earlier bigram does not take the id that followed it there (the
-        reference's --block_trigrams as a hard block).  On by itself it turns the constrained pick on; ``ban_ids`` must then leave at least seq_length + 1 ids."""
+        reference's --block_trigrams as a hard block).  On by itself it turns the constrained pick on; ``ban_ids`` must then leave at least seq_length + 1 ids.
+        ``require_ids`` (bofi_vocab_require: one small launch on the same stream BEHIND the decode call, outside a ``graph`` replay; no field of the call record): ids every
+        caption must contain -- an int table [B, K] with -1 padding (a device tensor is passed through as it is: the kernel classifies every entry), a list of per-image id
+        lists, or one flat list for every image; on the host: ids in 0..V-1, at most 8 per image, none of them in ``ban_ids``.  The words are placed on the live positions
+        where they cost the least log-prob (first as many as can be placed, then the largest total of log p(word) - log p(id standing there); the header states the rule
+        and its tie-break), read from ``seq_logprob`` (the engine's own workspace without it), under the call's ``ban_ids`` / ``no_repeat`` / ``repeat_min_id``: a
+        placement never creates an adjacent repeat.  ``out['required_pos']`` int32 [B, K]: each word's position, -1 padding, -2 skipped (by the kernel: banned, out of
+        range, repeated), -3 not placeable; ``out['required_moved']`` int32 [B]: positions whose id changed; ``seq`` and, with ``row_stats``, ``row_chosen`` are those of
+        the emitted ids.  With feed-back refinement rounds the placement applies to the LAST pass only: earlier passes are fed the unforced ids.  In the phased form it
+        follows the call whose ``phases`` contain 'f'.  Not with ``ids_only`` (no distribution), ``refine_method='mask_predict'`` or ``block_trigrams`` (a placement
+        could create a blocked trigram).  None, an empty list or rows of -1 only: nothing is launched and no key is added."""
         mp = self._refine_flag(refine_method, refine_rounds, raw_logits)
         ban = self._pick_ban(ban_ids, block_trigrams)
         pick_on = ban is not None or bool(no_repeat) or bool(block_trigrams)
+        req = self._require_table(require_ids, att_feats.size(0), ban_ids)
+        if req is not None:
+            self._require_refusals(ids_only, mp, block_trigrams)
         if pick_on and (ids_only or mp):
             raise hip.BofiHipError("ban_ids / no_repeat / block_trigrams: not with ids_only (no distribution to re-pick from) or refine_method='mask_predict'")
         if ids_only:
@@ -301,7 +314,51 @@ class BofiEngine:
             hip.ptr(out["memory"]), hip.ptr(out["bound_iters"]), C.byref(o), hip.stream_ptr()), "bofi_engine_decode_naic")
         if pick_on and (not phases or "f" in phases):
             hip.check(self._lib.bofi_engine_pick_changed(self._h, hip.ptr(out["constrained"]), B, hip.stream_ptr()), "bofi_engine_pick_changed")
+        if req is None:
+            out.pop("required_pos", None), out.pop("required_moved", None)      # (a reused `out` of a call that had the option)
+        elif not phases or "f" in phases:
+            out["required_pos"], out["required_moved"] = self._require_place(
+                req, out["seq"], out["seq_logprob"], torch.sum(out["phrase_length"], 1, dtype=torch.int32), 0, ban, no_repeat, repeat_min_id,
+                out["row_chosen"] if row_stats else None, out.get("required_pos"), out.get("required_moved"))
         return out
+
+    def _require_table(self, require_ids, B: int, ban_ids=None):
+        """``require_ids`` of a decode as the device table int32 [B, K] of bofi_vocab_require, None when nothing is required.  Host input goes through
+        ``hip.require_table`` (ids in 0..V-1, at most 8 per image, none in ``ban_ids``: BofiHipError otherwise); a device tensor is passed through -- the kernel is total."""
+        if isinstance(require_ids, torch.Tensor) and require_ids.is_cuda:
+            if require_ids.dim() != 2 or require_ids.size(0) != B or not 1 <= require_ids.size(1) <= hip.REQUIRE_MAX:
+                raise hip.BofiHipError(f"require_ids: a device table is [B, K] with 1 <= K <= {hip.REQUIRE_MAX}, got {tuple(require_ids.shape)} for {B} images")
+            return require_ids.to(torch.int32).contiguous()
+        t = hip.require_table(require_ids, B, self.cfg.tgt_vocab, ban_ids or ())
+        return None if t is None else t.to(self.device)
+
+    @staticmethod
+    def _require_refusals(ids_only: bool, mp: int, block_trigrams: bool) -> None:
+        if ids_only:
+            raise hip.BofiHipError("require_ids: not with ids_only (no distribution to place the words by)")
+        if mp:
+            raise hip.BofiHipError("require_ids: not with refine_method='mask_predict'")
+        if block_trigrams:
+            raise hip.BofiHipError("require_ids: not with block_trigrams (a placement could create a blocked trigram)")
+
+    def _require_place(self, req, seq, lp, ntok, ntok_bias, ban, no_repeat, repeat_min_id, row_chosen, pos=None, moved=None):
+        """Enqueue bofi_vocab_require on the current stream behind a decode: ``req`` int32 [B, K] on the device, ``lp`` the decode's log-prob (or logit) tensor or None
+        for the engine's own workspace.  Returns (pos int32 [B, K], moved int32 [B]); the buffers given are reused when they fit."""
+        if int(repeat_min_id) < 0:
+            raise hip.BofiHipError("repeat_min_id must be >= 0")
+        B, K = req.shape
+        S, V = self.cfg.seq_length, self.cfg.tgt_vocab
+        if pos is None or tuple(pos.shape) != (B, K):
+            pos = torch.empty(B, K, dtype=torch.int32, device=seq.device)
+        if moved is None or moved.numel() != B:
+            moved = torch.empty(B, dtype=torch.int32, device=seq.device)
+        src = hip.ptr(lp) if lp is not None else self._lib.bofi_engine_logprob(self._h)
+        if not src:
+            raise hip.BofiHipError("require_ids: this engine keeps no log-prob workspace (an ids-only fork)")
+        hip.check(self._lib.bofi_vocab_require(src, V, B * S, V, S, hip.ptr(ntok), int(ntok_bias), hip.ptr(req), K, hip.ptr(ban), 1 if no_repeat else 0,
+                                               int(repeat_min_id), hip.ptr(seq), hip.ptr(row_chosen), hip.ptr(pos), hip.ptr(moved), hip.stream_ptr()),
+                  "bofi_vocab_require")
+        return pos, moved
 
     def _pick_ban(self, ban_ids, block_trigrams: bool = False):
         """The device bit table of a ban list (``hip.ban_bits``: ids outside 0..V-1 and a list that leaves fewer than two ids raise), kept per engine and id set;
@@ -535,17 +592,22 @@ class BofiEngine:
 
     def fill_naic(self, ext_syn: torch.Tensor, last: torch.Tensor, R: int, att_len: Optional[torch.Tensor] = None, *, strict_q1: bool = True,
                   raw_logits: bool = False, refine_rounds: int = 0, refine_method: str = "feed_back", attn_topk: int = 0, attn_maps: bool = False,
-                  attn_heads: bool = False, attn_layer: int = -1, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7, block_trigrams: bool = False):
+                  attn_heads: bool = False, attn_layer: int = -1, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7, block_trigrams: bool = False,
+                  require_ids=None):
         """The filling pass alone on a given slot layout (``ext_syn`` int32 [B, S+2], ``last`` int32 [B]) and the memory of the
         preceding ``encode``: (seq int64 [B, S], seq_logprob float32 [B, S, V]); with ``refine_method='mask_predict'`` (as ``decode_naic``) a third
         element, refine_round int32 [B, S].  With ``attn_topk`` / ``attn_maps`` / ``attn_heads`` (as ``decode_naic``) a last element, a dict of the attention tensors
         ('attn', 'attn_heads', 'attn_top', 'attn_top_w': those asked for).  ``ban_ids`` / ``no_repeat`` / ``repeat_min_id`` / ``block_trigrams`` as ``decode_naic``: that dict (the last element)
-        then carries 'constrained', int32 [B]."""
+        then carries 'constrained', int32 [B].  ``require_ids`` as ``decode_naic`` (bofi_vocab_require behind the call, on the last pass; the same refusals): that dict
+        then carries 'required_pos' int32 [B, K] and 'required_moved' int32 [B]."""
         mp = self._refine_flag(refine_method, refine_rounds, raw_logits)
         ban = self._pick_ban(ban_ids, block_trigrams)
         pick_on = ban is not None or bool(no_repeat) or bool(block_trigrams)
         if pick_on and mp:
             raise hip.BofiHipError("ban_ids / no_repeat / block_trigrams: not with refine_method='mask_predict'")
+        req = self._require_table(require_ids, ext_syn.size(0), ban_ids)
+        if req is not None:
+            self._require_refusals(False, mp, block_trigrams)
         B = ext_syn.size(0)
         if ext_syn.dtype != torch.int32 or last.dtype != torch.int32 or ext_syn.size(1) != self.cfg.bound_len or last.numel() != B:
             raise hip.BofiHipError("ext_syn must be int32 [B, S+2] and last int32 [B]")
@@ -563,6 +625,8 @@ class BofiEngine:
         if pick_on:
             attn["constrained"] = torch.zeros(B, dtype=torch.int32, device=dev)
             hip.check(self._lib.bofi_engine_pick_changed(self._h, hip.ptr(attn["constrained"]), B, hip.stream_ptr()), "bofi_engine_pick_changed")
+        if req is not None:
+            attn["required_pos"], attn["required_moved"] = self._require_place(req, seq, lp, last.contiguous(), -1, ban, no_repeat, repeat_min_id, None)
         res = (seq, lp, rnd) if mp else (seq, lp)
         return res + (attn,) if attn else res
 
@@ -587,7 +651,7 @@ class DecodePipeline:
     def __init__(self, engine: "BofiEngine", *, in_flight: Optional[int] = None, batches_per_launch: int = 16, strict_q1: bool = True, stats: bool = True,
                  keep_logprob: bool = False, region_buckets=(36, 48, 64, 80, 100, 128), fused_vocab: bool = False,
                  refine_rounds: int = 0, refine_method: str = "feed_back", attn_topk: int = 0, keep_attn: bool = False, ban_ids=None, no_repeat: bool = False,
-                 repeat_min_id: int = 7, block_trigrams: bool = False):
+                 repeat_min_id: int = 7, block_trigrams: bool = False, require_ids=None):
         BofiEngine._refine_flag(refine_method, refine_rounds, False)
         # ban_ids / no_repeat / repeat_min_id / block_trigrams: the constrained pick of BofiEngine.decode_naic on every launch; every yielded dict then carries constrained int32 [b].  Not
         # with fused_vocab (ids-only launches keep no distribution to re-pick from) or 'mask_predict'
@@ -603,6 +667,11 @@ class DecodePipeline:
             hip.ban_bits(self.ban_ids, engine.cfg.tgt_vocab)        # (checked here, on the host: a bad list raises before anything is launched)
             if self.block_trigrams and engine.cfg.tgt_vocab - len(self.ban_ids) < engine.cfg.seq_length + 1:
                 raise hip.BofiHipError("ban_ids: with block_trigrams at least seq_length + 1 ids must stay")
+        # require_ids: required words (BofiEngine.decode_naic(require_ids=...)) -- the default of ``run``, which states the forms; checked here so that a pipeline that cannot
+        # place words refuses before anything is launched
+        self.fused_vocab, self.refine_method, self.root_vocab = bool(fused_vocab), refine_method, engine.cfg.tgt_vocab
+        self.require_ids = require_ids
+        self._require_split(require_ids)
         # attn_topk = K > 0: every yielded dict carries attn_top int32 / attn_top_w float32 [b, S, K] -- each position's K heaviest regions (BofiEngine.decode_naic) -- on the
         # host, through the pinned buffers (rows x S x K x 8 bytes per launch); keep_attn: also attn [b, S, R of the launch's region bucket] on the device, as keep_logprob
         if not 0 <= int(attn_topk) <= 8:
@@ -642,6 +711,42 @@ class DecodePipeline:
                                     done=torch.cuda.Event()))
         self.rows_max = rows_max
 
+    def _require_split(self, require_ids):
+        """``require_ids`` of a run as (flat, per_batch): one flat id list for every image, or an iterator of per-batch tables aligned with the batches; (None, None) when
+        off.  The refusals of required words are raised here."""
+        if require_ids is None:
+            return None, None
+        import numpy as np
+        if isinstance(require_ids, (torch.Tensor, np.ndarray)):
+            raise hip.BofiHipError("require_ids: a pipeline takes one flat id list for every image or a sequence of per-batch tables")
+        seq = require_ids if hasattr(require_ids, "__len__") else None
+        if seq is not None and len(seq) == 0:
+            return None, None
+        if self.fused_vocab:
+            raise hip.BofiHipError("require_ids: not with fused_vocab (the ids-only launches keep no distribution to place the words by)")
+        if self.refine_method == "mask_predict":
+            raise hip.BofiHipError("require_ids: not with refine_method='mask_predict'")
+        if self.block_trigrams:
+            raise hip.BofiHipError("require_ids: not with block_trigrams (a placement could create a blocked trigram)")
+        if seq is not None and isinstance(seq[0], (int, np.integer)):
+            flat = hip.require_table(list(seq), 1, self.root_vocab, self.ban_ids)      # (checked once, here)
+            return (None, None) if flat is None else ([int(i) for i in flat[0]], None)
+        return None, iter(require_ids)
+
+    def _require_launch(self, group, b):
+        """The [rows, K] host table of a launch from its batches' tables (each checked on the host by ``hip.require_table``), and every batch's own K (0: none); (None,
+        ks) when no batch of the launch requires a word."""
+        tabs = [hip.require_table(g[2], b, self.root_vocab, self.ban_ids) if len(g) > 2 and g[2] is not None else None for g in group]
+        ks = [0 if t is None else t.size(1) for t in tabs]
+        K = max(ks)
+        if K == 0:
+            return None, ks
+        full = torch.full((len(group) * b, K), -1, dtype=torch.int32)
+        for i, t in enumerate(tabs):
+            if t is not None:
+                full[i * b:(i + 1) * b, :t.size(1)] = t
+        return full, ks
+
     @staticmethod
     def _as_host_or_device(x):
         return torch.from_numpy(x) if not torch.is_tensor(x) else x
@@ -657,13 +762,22 @@ class DecodePipeline:
                 return b
         raise hip.BofiHipError(f"{r} regions exceed the engine's max_regions={self.root.max_regions}")
 
-    def run(self, batches):
+    def run(self, batches, require_ids=None):
         """``batches``: iterable of ``att_feats`` or ``(att_feats, att_len)``: [b, R, F] tensors / arrays in the engine's compute dtype or float32, on
         the host (pinned: the copy is asynchronous) or the device; ``att_len`` int32 [b] region counts or None (every image has R regions).  An item may
         also be a ``features.RaggedBatch``: its real rows alone are copied, in the files' dtype, and ``bofi_pack_regions`` pads them to the region bucket
         in the compute dtype on the device (a batch whose images all have the bucket's count is decoded without counts, as the loader hands it over).  A
         ``features.BoxRaggedBatch`` (use_box) also brings boxes and image sizes: ``bofi_pack_regions_box`` appends the geometry columns, sorts by box area and
-        writes the engine's padded width.  Dense items of an ``att_feat_size`` that is no multiple of 64 are copied into that zero-padded width."""
+        writes the engine's padded width.  Dense items of an ``att_feat_size`` that is no multiple of 64 are copied into that zero-padded width.
+        ``require_ids`` (default: the constructor's): required words, as ``BofiEngine.decode_naic`` places them -- one flat id list for every image, or a sequence of
+        per-batch tables aligned with ``batches`` (each a [b, K] int table, a list of b id lists, one flat list for the batch, or None); a launch that carries several
+        batches concatenates their tables, and every batch's result is its own ``decode_naic(require_ids=...)``: its dict carries required_pos int32 [b, K of the batch]
+        and required_moved int32 [b] (no keys for a batch that requires nothing).  Not with ``fused_vocab``, 'mask_predict' or ``block_trigrams``: raised here, before
+        anything is launched."""
+        flat, per_batch = self._require_split(self.require_ids if require_ids is None else require_ids)
+        return self._run(batches, flat, per_batch)
+
+    def _run(self, batches, req_flat, req_iter):
         from .features import RaggedBatch
         pending = []                                             # launches in flight: (slot, [batch sizes])
         group, gkey = [], None
@@ -677,17 +791,23 @@ class DecodePipeline:
             if j >= self.nf:
                 yield from self._finish(pending.pop(0))
             self._launch(k, p, group, gkey)
-            pending.append((k, [g[0].B if isinstance(g[0], RaggedBatch) else g[0].shape[0] for g in group]))
+            pending.append((k, [g[0].B if isinstance(g[0], RaggedBatch) else g[0].shape[0] for g in group], self._slots[k]["req_ks"]))
             j += 1
             group = []
 
         for item in batches:
+            req = req_flat
+            if req_iter is not None:
+                try:
+                    req = next(req_iter)
+                except StopIteration:
+                    raise hip.BofiHipError("require_ids: fewer per-batch tables than batches") from None
             if isinstance(item, RaggedBatch):
                 r = self._bucket(item.max_len)
                 key = (item.B, r, item.out_F, self.root.dtype, item.equal_lengths and item.max_len == r)
                 if group and (key != gkey or len(group) >= self.bpl):
                     yield from flush()
-                group.append((item, None))
+                group.append((item, None, req))
                 gkey = key
                 continue
             att, lens = item if isinstance(item, (tuple, list)) else (item, None)
@@ -697,7 +817,7 @@ class DecodePipeline:
             key = (b, r if lens is None else self._bucket(r), self._width(att.shape[2]), att.dtype, lens is None)
             if group and (key != gkey or len(group) >= self.bpl):
                 yield from flush()
-            group.append((att, lens))
+            group.append((att, lens, req))
             gkey = key
         yield from flush()
         while pending:
@@ -725,7 +845,7 @@ class DecodePipeline:
             feats, lens = buf[:rows], (sl["lens"][p][:rows] if has_len else None)
             cs.wait_event(sl["done"])                            # the launch that last read this slot's buffers is through (it was finished before this one is issued)
             staged = self._stage_ragged(sl, p, group)
-            for i, (att, ln) in enumerate(group):
+            for i, (att, ln, _) in enumerate(group):
                 if i in staged:                                  # a RaggedBatch: its rows and offsets to the slot's staging buffer, the padding made on the device
                     srows, soffs = staged[i][:2]
                     srows.copy_(att.rows, non_blocking=True)
@@ -748,8 +868,10 @@ class DecodePipeline:
                     lens[i * b:(i + 1) * b].copy_(ln, non_blocking=True)
             sl["copied"][p].record(cs)
         sl["last"] = (feats, lens, b, nb, rows)                  # (kept for the fallback decode of _finish: this slot's buffers stay untouched until its next launch)
+        req, sl["req_ks"] = self._require_launch(group, b)
         with torch.cuda.stream(st):
             st.wait_event(sl["copied"][p])
+            sl["req"] = None if req is None else req.to(self.dev)      # (on the launch's stream: the post-pass that reads it follows there)
             self._decode_and_copy_out(sl)
             sl["done"].record(st)
 
@@ -793,7 +915,8 @@ class DecodePipeline:
         sl["out"] = e.decode_naic(feats, lens, strict_q1=self.strict_q1, graph=True, out=sl["out"] if sl["out"] is not None and sl["out"]["seq"].shape[0] == rows else None,
                                   q1_group=b if nb > 1 else 0, row_stats=self.stats, want_logprob=self.keep_logprob, ids_only=self.fused_vocab,
                                   refine_rounds=self.refine_rounds, refine_method=self.refine_method, attn_topk=self.attn_topk, attn_maps=self.keep_attn,
-                                  ban_ids=self.ban_ids or None, no_repeat=self.no_repeat, repeat_min_id=self.repeat_min_id, block_trigrams=self.block_trigrams)
+                                  ban_ids=self.ban_ids or None, no_repeat=self.no_repeat, repeat_min_id=self.repeat_min_id, block_trigrams=self.block_trigrams,
+                                  require_ids=sl.get("req"))
         out = sl["out"]
         small = {k2: out[k2] for k2 in ("seq", "phrase_num", "phrase_length", "phrase_syn", "bound_saturated")}
         if self.refine_method == "mask_predict":
@@ -802,9 +925,11 @@ class DecodePipeline:
             small["attn_top"], small["attn_top_w"] = out["attn_top"], out["attn_top_w"]
         if self.pick_on:
             small["constrained"] = out["constrained"]
+        if sl.get("req") is not None:
+            small["required_pos"], small["required_moved"] = out["required_pos"], out["required_moved"]
         if self.stats:
             small["entropy"], small["perplexity"] = e.entropy_perplexity(out)
-        if sl["host"] is None or sl["host"]["seq"].shape[0] != rows:
+        if sl["host"] is None or sl["host"].keys() != small.keys() or any(sl["host"][k2].shape != v.shape for k2, v in small.items()):
             sl["host"] = {k2: torch.empty(v.shape, dtype=v.dtype).pin_memory() for k2, v in small.items()}
         for k2, v in small.items():
             sl["host"][k2].copy_(v, non_blocking=True)
@@ -812,7 +937,7 @@ class DecodePipeline:
         sl["attn"] = out["attn"].clone() if self.keep_attn else None
 
     def _finish(self, launch):
-        k, sizes = launch
+        k, sizes, req_ks = launch
         sl = self._slots[k]
         sl["done"].synchronize()
         sat = int(sl["host"]["bound_saturated"][0])
@@ -826,8 +951,13 @@ class DecodePipeline:
             sl["ran"]._redo_without_loop_kernel(sat, again)
         mine = {k2: v.clone() for k2, v in sl["host"].items() if k2 != "bound_saturated"}      # (one private copy per launch: the pinned buffers are the next launch's; batches are views of it)
         o = 0
-        for b in sizes:
+        for i, b in enumerate(sizes):
             res = {k2: v[o:o + b] for k2, v in mine.items()}
+            if "required_pos" in res:                            # (a batch's own K columns; no keys for a batch of the launch that requires nothing)
+                if req_ks[i]:
+                    res["required_pos"] = res["required_pos"][:, :req_ks[i]]
+                else:
+                    del res["required_pos"], res["required_moved"]
             if sl["lp"] is not None:
                 res["seq_logprob"] = sl["lp"][o:o + b]
             if sl["attn"] is not None:

@@ -230,6 +230,75 @@ def constraint_of(eval_kwargs, vocab, mode: str = "NAIC", sample_n: int = 1):
     return dict({"ban_ids": ids, "no_repeat": rep}, **({"block_trigrams": True} if tri else {}))
 
 
+def require_refusals(eval_kwargs, mode: str = "NAIC", sample_n: int = 1) -> None:
+    """ValueError (naming ``require_words``) where required words cannot apply: SAIC mode, sampling, ``fused_vocab``, mask-predict, ``block_trigrams``."""
+    kw = eval_kwargs
+    if mode != "NAIC":
+        raise ValueError("require_words place words on the non-autoregressive filling pass: inference_mode 'NAIC' only")
+    if int(sample_n) > 1:
+        raise ValueError("require_words place words on greedy picks: not with sample_n > 1")
+    if kw.get("fused_vocab", False):
+        raise ValueError("require_words: not with fused_vocab (no distribution to place the words by)")
+    if kw.get("refine_method", "feed_back") == "mask_predict":
+        raise ValueError("require_words: not with refine_method 'mask_predict'")
+    if int(kw.get("block_trigrams", 0) or 0) == 1:
+        raise ValueError("require_words: not with block_trigrams (a placement could create a blocked trigram)")
+
+
+def required_of(eval_kwargs, vocab, keys, mode: str = "NAIC", sample_n: int = 1, ban_ids=()):
+    """The required words an evaluation asks for (``eval_kwargs['require_words']``: a list of words -- or 'W1,W2,...' -- for every image, or a dict from image key to
+    word list; ``keys``: the images' keys in order, matched as they are or as strings) as (ids, words): per image the id list ``decode_many(require_ids=...)`` takes
+    and the words it stands for, duplicates dropped; None when no image requires a word.  Words resolve through ``vocab`` ({str(id): word}; the lowest id of a word):
+    a word it does not hold is a ValueError that names it, as are more than 8 words for an image, a word that is also banned, and the options required words cannot
+    go with (``require_refusals``)."""
+    spec = eval_kwargs.get("require_words")
+    if not spec:
+        return None
+    if isinstance(spec, str):
+        spec = [w for w in spec.split(",") if w]
+    if isinstance(spec, dict):
+        per_image = []
+        for k in keys:
+            ws = spec.get(k, spec.get(str(k), []))
+            per_image.append([w for w in ws.split(",") if w] if isinstance(ws, str) else list(ws))
+    else:
+        per_image = [list(spec)] * len(keys)
+    if not any(per_image):
+        return None
+    require_refusals(eval_kwargs, mode, sample_n)
+    if not vocab:
+        raise ValueError("require_words need a vocabulary ({str(id): word})")
+    id_of = {}
+    for k, w in vocab.items():
+        id_of[w] = min(int(k), id_of.get(w, int(k)))
+    ban = {int(i) for i in ban_ids or ()}
+    ids, words = [], []
+    for ws in per_image:
+        ws = list(dict.fromkeys(ws))
+        for w in ws:
+            if w not in id_of:
+                raise ValueError(f"require_words: the vocabulary does not hold {w!r}")
+            if id_of[w] in ban:
+                raise ValueError(f"require_words: {w!r} is also banned (suppress_UNK / ban_words)")
+        if len(ws) > 8:
+            raise ValueError(f"require_words: at most 8 required words per image, got {len(ws)}")
+        ids.append([id_of[w] for w in ws])
+        words.append(ws)
+    return ids, words
+
+
+def required_entry(words, pos_row):
+    """The 'required' field of a prediction entry: [word, position] per required word of the image, position None where the word could not be placed."""
+    return [[w, (int(p) if int(p) >= 0 else None)] for w, p in zip(words, pos_row[:len(words)].tolist())] if words else []
+
+
+def required_rates(words, pos_rows, moved: int, emitted: int) -> dict:
+    """required_rate = words placed / words required, required_moved_rate = positions whose id the placement changed / positions emitted."""
+    asked = sum(len(w) for w in words)
+    placed = sum(sum(1 for p in row[:len(w)].tolist() if int(p) >= 0) for w, row in zip(words, pos_rows) if w)
+    return {"required_rate": placed / max(1, asked), "required_moved_rate": moved / max(1, emitted)}
+
+
 def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
     """(val_loss, predictions, lang_stats) of ``feats``' images: see the module's head.  The model is put in eval() and restored."""
     kw = eval_kwargs
@@ -249,6 +318,11 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
     # suppress_UNK / decoding_constraint / ban_words / block_trigrams: the constrained pick (constraint_of); with language stats, constrained_rate = changed / emitted positions
     pick = constraint_of(kw, kw.get("vocab") or getattr(model, "vocab", None), mode, sample_n)
     refine.update(pick)
+    # require_words: required words (required_of) -- per-batch tables to decode_many; the predictions gain 'required' ([word, position or None] per word), the stats
+    # required_rate and required_moved_rate (a dict of these two alone when no language scores were asked for).  Image keys: eval_kwargs['image_keys'], else 0 .. N - 1
+    keys = kw.get("image_keys")
+    required = required_of(kw, kw.get("vocab") or getattr(model, "vocab", None), list(keys) if keys is not None else list(range(len(feats))), mode, sample_n,
+                           pick.get("ban_ids", ()))
     remove, surface_stats = int(kw.get("remove_bad_endings", 0)) == 1, int(kw.get("surface_stats", 0)) == 1
     if surface_stats and sample_n > 1 and kw.get("train_sentences") is None:
         raise ValueError("surface_stats with sample_n > 1 looks the sampled captions up among the training sentences: eval_kwargs['train_sentences'] "
@@ -271,6 +345,8 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
         vocab = kw.get("vocab")
         ragged = is_region_source(feats)
         host = feats if ragged else _torch_feats(feats)
+        if required is not None:
+            refine["require_ids"] = [required[0][j:j + batch_size] for j in range(0, N, batch_size)]
         with torch.no_grad():
             if mode == "NAIC" and ragged:                       # staged ragged batch by batch, ahead of the launches that consume them
                 for r in model.decode_many((feats.ragged(j, min(j + batch_size, N)) for j in range(0, N, batch_size)), batches_per_launch=int(kw.get("batches_per_launch", 16)),
@@ -311,6 +387,9 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
             for r, seq in zip(got, seqs):
                 r = dict(r, seq=seq)
                 predictions.extend(with_regions(entry_of(i, k, seq, r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"], vocab), r, k) for k in range(seq.size(0)))
+                if required is not None:
+                    for k in range(seq.size(0)):
+                        predictions[i + k]["required"] = required_entry(required[1][i + k], r["required_pos"][k]) if "required_pos" in r else []
                 i += seq.size(0)
         if refine["refine_method"] == "mask_predict":
             kw["refine_round"] = torch.cat(rounds)
@@ -340,6 +419,10 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
             lang_stats["bad_count_rate"] = surface.bad_count_rate(bad)
         if pick and lang_stats is not None:                      # after every other key
             lang_stats["constrained_rate"] = constrained_rate(got)
+        if required is not None:
+            rows = [row for r in got for row in (r["required_pos"] if "required_pos" in r else [torch.empty(0, dtype=torch.int32)] * r["seq"].size(0))]
+            moved = sum(int(r["required_moved"].sum()) for r in got if "required_moved" in r)
+            lang_stats = dict(lang_stats or {}, **required_rates(required[1], rows, moved, sum(int(r["phrase_length"].sum()) for r in got)))
     finally:
         model.train(was_training)
     return val_loss, predictions, lang_stats

@@ -23,6 +23,7 @@ FLAG_MASK_PREDICT = 16384
 FLAG_PICK_TRIGRAMS = 32768
 FORK_IDS_ONLY = 1
 ABI_VERSION = 5
+REQUIRE_MAX = 8                     # BOFI_REQUIRE_MAX: required words per image (bofi_vocab_require)
 
 
 class BofiHipError(RuntimeError):
@@ -137,6 +138,7 @@ SIGNATURES = {
     "bofi_engine_pick_changed": (_I, [_P, _P, _I, _P]),
     "bofi_vocab_pick_workspace": (_I64, [_I]),
     "bofi_vocab_pick": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _I64, _P]),
+    "bofi_vocab_require": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "bofi_caption_trim": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     "bofi_sentence_lookup": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
 }
@@ -339,6 +341,80 @@ def vocab_pick(x, V, S, seq, *, ntok=None, ntok_bias=0, pad_idx=0, ban=None, no_
     check(lib().bofi_vocab_pick(ptr(x), x.stride(0), rows, int(V), int(S), ptr(ntok), int(ntok_bias), int(pad_idx), ptr(ban), 1 if no_repeat else 0,
                                 1 if block_trigrams else 0, int(repeat_min_id), ptr(seq), ptr(row_chosen), ptr(changed), ptr(work), work.numel() * 4, stream_ptr()),
           "bofi_vocab_pick")
+
+
+def require_table(require_ids, B: int, V: int, ban_ids=()):
+    """The [B, K] int32 word table of ``bofi_vocab_require`` (host tensor, -1 padding) from host-side input: an int array / host tensor [B, K], a list of B per-image id
+    lists, or one flat list applied to every image.  None when nothing is required (no input, empty lists, rows of -1 only).  Checked here: ids in 0..V-1 (-1 pads a row),
+    at most ``REQUIRE_MAX`` per image, none of them in ``ban_ids``; duplicates within an image are dropped."""
+    import numpy as np
+    import torch
+    if require_ids is None:
+        return None
+    if isinstance(require_ids, torch.Tensor):
+        require_ids = require_ids.cpu().numpy()
+    if isinstance(require_ids, np.ndarray):
+        if require_ids.ndim == 1:
+            require_ids = [require_ids.tolist()] * B
+        elif require_ids.ndim == 2:
+            require_ids = require_ids.tolist()
+        else:
+            raise BofiHipError("require_ids: a [B, K] table, a list of per-image id lists or one flat id list")
+    rows = list(require_ids)
+    if rows and not isinstance(rows[0], (list, tuple, np.ndarray)):
+        rows = [rows] * B                                        # one flat list: every image
+    if not rows:
+        return None
+    if len(rows) != B:
+        raise BofiHipError(f"require_ids: {len(rows)} rows for {B} images")
+    ban = {int(i) for i in ban_ids or ()}
+    clean = []
+    for r in rows:
+        ids = []
+        for i in r:
+            i = int(i)
+            if i == -1:
+                continue
+            if not 0 <= i < V:
+                raise BofiHipError(f"require_ids: ids must lie in 0..{V - 1} (-1 pads a row), got {i}")
+            if i in ban:
+                raise BofiHipError(f"require_ids: id {i} is also in ban_ids")
+            if i not in ids:
+                ids.append(i)
+        if len(ids) > REQUIRE_MAX:
+            raise BofiHipError(f"require_ids: at most {REQUIRE_MAX} required words per image, got {len(ids)}")
+        clean.append(ids)
+    K = max(len(r) for r in clean)
+    if K == 0:
+        return None
+    t = np.full((B, K), -1, np.int32)
+    for b, r in enumerate(clean):
+        t[b, :len(r)] = r
+    return torch.from_numpy(t)
+
+
+def vocab_require(x, V, S, seq, words, pos, *, ntok=None, ntok_bias=0, ban=None, no_repeat=False, repeat_min_id=7, row_chosen=None, moved=None):
+    """``bofi_vocab_require`` on torch tensors: x float32 [rows, >= V] on the device with unit column stride (its row stride is the pitch; any 4-byte alignment), seq int64
+    [rows] read and written, words int32 [rows / S, K] (1 <= K <= ``REQUIRE_MAX``), pos int32 [rows / S, K] out; ntok int32 [rows / S] or None, ban the bit table of
+    ``ban_bits`` or None, row_chosen float32 [rows] and moved int32 [rows / S] optional.  One launch on the current stream, no synchronisation."""
+    import torch
+    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or not x.is_cuda:
+        raise BofiHipError("vocab_require: x must be a 2-d float32 device tensor with unit column stride")
+    rows = x.size(0)
+    if x.size(1) < V or S < 1 or rows % S:
+        raise BofiHipError("vocab_require: x needs V columns and a multiple of S rows")
+    B = rows // S
+    if words is None or words.dim() != 2 or words.size(0) != B:
+        raise BofiHipError(f"vocab_require: words must be int32 [{B}, K]")
+    K = words.size(1)
+    for name, t, dt, n in (("seq", seq, torch.int64, rows), ("words", words, torch.int32, B * K), ("pos", pos, torch.int32, B * K), ("ntok", ntok, torch.int32, B),
+                           ("ban", ban, torch.int32, (V + 31) // 32), ("row_chosen", row_chosen, torch.float32, rows), ("moved", moved, torch.int32, B)):
+        if t is None and name not in ("seq", "words", "pos"):
+            continue
+        if t is None or t.dtype != dt or t.numel() != n or not t.is_cuda or not t.is_contiguous():
+            raise BofiHipError(f"vocab_require: {name} must be a contiguous {dt} device tensor of {n} elements")
+    check(lib().bofi_vocab_require(ptr(x), x.stride(0), rows, int(V), int(S), ptr(ntok), int(ntok_bias), ptr(words), int(K), ptr(ban), 1 if no_repeat else 0,
+                                   int(repeat_min_id), ptr(seq), ptr(row_chosen), ptr(pos), ptr(moved), stream_ptr()), "bofi_vocab_require")
 
 
 def gemm_flops(reset: bool = False):

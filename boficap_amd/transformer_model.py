@@ -243,7 +243,7 @@ class TransformerModel(nn.Module):
 
     def decode_many(self, batches, *, batches_per_launch: int = 16, in_flight: Optional[int] = None, stats: bool = True, keep_logprob: bool = False,
                     fused_vocab: bool = False, refine_rounds: int = 0, refine_method: str = "feed_back", attn_topk: int = 0, keep_attn: bool = False,
-                    ban_ids=None, no_repeat: bool = False, block_trigrams: bool = False):
+                    ban_ids=None, no_repeat: bool = False, block_trigrams: bool = False, require_ids=None):
         """Greedy NAIC decode of MANY loader batches at the engine's throughput -- the eval loop of the reference (eval_utils.py:456-460: one synchronised
         ``model(..., mode='sample')`` per batch, which is what ``_sample`` reproduces) as a pipeline: ``in_flight`` engine forks on overlapping streams,
         ``batches_per_launch`` consecutive batches per launch (quirk Q1 per batch: every batch's result is its own decode's), features copied from (pinned)
@@ -261,7 +261,10 @@ class TransformerModel(nn.Module):
         layer's mean cross-attention, in descending order (-1 / 0 past an image's region count and where no word stands); ``keep_attn``: also the whole map attn
         [b, S, R] on the device (R: the launch's region bucket, the padding columns zero).
         ``ban_ids`` / ``no_repeat`` / ``block_trigrams``: the constrained pick of ``BofiEngine.decode_naic`` on every launch -- the listed ids are never emitted, no word
-        stands twice in a row, no word trigram stands twice in a caption --; every dict then carries constrained int32 [b], the positions per image it changed.  Not with ``fused_vocab`` or 'mask_predict'."""
+        stands twice in a row, no word trigram stands twice in a caption --; every dict then carries constrained int32 [b], the positions per image it changed.  Not with ``fused_vocab`` or 'mask_predict'.
+        ``require_ids``: required words, placed as ``BofiEngine.decode_naic(require_ids=...)`` places them -- a sequence of per-batch tables aligned with ``batches`` (each
+        a [b, K] int table with -1 padding, a list of b id lists, one flat list for the batch, or None), or one flat id list for every image; every batch's dict then
+        carries required_pos int32 [b, K] and required_moved int32 [b], and equals that batch's own decode.  Not with ``fused_vocab``, 'mask_predict' or ``block_trigrams``."""
         from .engine import DecodePipeline
         eng = self.engine()
         ban_ids = tuple(sorted({int(i) for i in ban_ids})) if ban_ids is not None else ()
@@ -289,7 +292,7 @@ class TransformerModel(nn.Module):
                 else:
                     masks = torch.from_numpy(masks) if not torch.is_tensor(masks) else masks
                     yield att.contiguous(), masks.long().sum(1).to(torch.int32).contiguous()
-        return cached[1].run(items())
+        return cached[1].run(items(), require_ids=require_ids)
 
     def _sample(self, fc_feats, att_feats, att_masks=None, opt={}):
         """AttModel.py:307-338, 419-437 for train_mode 'NAIC' (bound+fill) and 'SAIC' (phrase by phrase)."""
@@ -348,6 +351,18 @@ class TransformerModel(nn.Module):
                 if refine_method == "mask_predict":
                     raise hip.BofiHipError("suppress_UNK / decoding_constraint / ban_ids / block_trigrams: not with refine_method='mask_predict'")
                 rkw.update(ban_ids=ban_ids or None, no_repeat=bool(no_repeat), block_trigrams=bool(block_trigrams))
+        # opt['require_ids']: required words of the NAIC decode (BofiEngine.decode_naic(require_ids=...): a [B, K] table, per-image id lists or one flat list); the 6-tuple
+        # stays, the words' positions and the per-image counts of changed positions land in self.last_required ({'pos', 'moved'}; None without the option)
+        require_ids = opt.get("require_ids")
+        self.last_required = None
+        if require_ids is not None and (torch.is_tensor(require_ids) or len(require_ids)):
+            if train_mode != "NAIC":
+                raise hip.BofiHipError("require_ids place words on the non-autoregressive filling pass: train_mode 'NAIC' only")
+            if sample_method == "sample":
+                raise hip.BofiHipError("require_ids place words on greedy picks: not with sample_method='sample'")
+            if refine_method == "mask_predict":
+                raise hip.BofiHipError("require_ids: not with refine_method='mask_predict'")
+            rkw.update(require_ids=require_ids)
         eng = self.engine()
         torch.cuda.synchronize()                                  # the reference does (AttModel.py:337)
         start = time.time()
@@ -380,6 +395,8 @@ class TransformerModel(nn.Module):
             if attn_topk or attn_maps:
                 keys = (("attn",) if attn_maps else ()) + (("attn_top", "attn_top_w") if attn_topk else ())
                 self.last_attn = {k: (r[k].repeat_interleave(sample_n, dim=0) if sample_n > 1 else r[k]) for k in keys}
+            if "required_pos" in r:
+                self.last_required = {k: (r["required_" + k].repeat_interleave(sample_n, dim=0) if sample_n > 1 else r["required_" + k]) for k in ("pos", "moved")}
             if "ban_ids" in rkw:
                 self.last_constrained = r["constrained"].repeat_interleave(sample_n, dim=0) if sample_n > 1 else r["constrained"]
         elif sample_method == "greedy":                           # core_SAIC, AttModel.py:430-437

@@ -822,6 +822,35 @@ int64_t bofi_vocab_pick_workspace(int rows);
 int bofi_vocab_pick(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int no_repeat,
                     int block_trigrams, int repeat_min_id, int64_t* seq, float* row_chosen, int* changed, void* work, int64_t work_bytes, void* stream);
 
+/* Required words: the best caption that CONTAINS the given ids, from the rows of a filling pass -- the positive counterpart of the constrained pick (lexically constrained
+ * captioning; an autoregressive model needs a constrained beam for it, a pass that scores every position on its own solves it exactly as an assignment of K <= 8 words to
+ * n <= 64 positions).  A stand-alone launch behind the decode call: no field of bofi_call_opts_t, no engine state, the ABI version is unchanged.
+ * For image b:
+ *   n_b = clamp(ntok[b] + ntok_bias, 0, S) live positions (ntok NULL: S); x[p, .] the float32 row b * S + p of x [rows, ldx] (log-probs, or raw logits: the normaliser
+ *   cancels within a position), read only, any 4-byte alignment; seq[p] the id standing at position p on entry (the greedy or constrained pick of the last filling pass);
+ *   words[b, 0 .. K-1] an int32 row, 1 <= K <= BOFI_REQUIRE_MAX.
+ * Entries of words[b, .]: an entry < 0 is EMPTY (pos -1).  An entry is SKIPPED (pos -2) when it is >= V, banned by ban_bits (bofi_vocab_constrain's table; NULL: none) or
+ * repeats an earlier entry of the same row.  Every other entry is a required word f_j.
+ * Gain: gain[p][j] = 0 when seq[p] == f_j; otherwise (double)x[p, f_j] - (double)x[p, seq[p]] when both operands are finite; otherwise position p is INELIGIBLE for word j
+ * (NaN and +-inf on either side; a seq[p] outside 0..V-1 has no value and counts as not finite).  With no_repeat = 1 and f_j >= repeat_min_id, p is also ineligible for j
+ * when seq[p] != f_j and a live neighbour on entry (seq[p-1] or seq[p+1]) equals f_j: a placement never creates an adjacent repeat.
+ * Objective: a placement maps a subset of the required words injectively to eligible live positions; it first maximises the NUMBER of words placed, then the total gain,
+ * formed by the backward recurrence below in float64.
+ * Recurrence and tie-break: best[n_b][m] = (0 words, 0.0) for every mask m of still-unplaced words.  For p = n_b - 1 .. 0 and each mask m the options are taken in this
+ * order: "position p takes word j" for j ascending over the eligible words in m, value (1 + cnt, gain[p][j] + tot) of best[p+1][m \ j]; then "position p keeps its id",
+ * value best[p+1][m].  Option values compare first by count, then by total; the FIRST option that attains the maximum is choice[p][m] (update only on strictly greater, in
+ * that order).  The result is the forward walk from (0, all required words) along choice -- reading left to right, a position takes a word whenever some optimal
+ * completion does, the earliest-listed such word first.
+ * Outputs: seq -- live positions that took a word hold it, all else is untouched, the pad tail included; row_chosen (may be NULL) -- x[p, f_j] at every position that took
+ * a word, all else untouched; pos int32 [B, K] -- the position of each word, -1 empty, -2 skipped, -3 required but unplaceable; moved int32 [B] (may be NULL) -- positions
+ * whose id changed.
+ * One launch, no workspace, deterministic, no atomics; the only float arithmetic is the float64 differences and sums above, in the order above.  rows = 0 is BOFI_OK
+ * without a launch.  BOFI_ERR_ARG with a message and no launch: NULL x, seq, words or pos; rows % S != 0; V < 2 or ldx < V; S outside 1..64; K outside 1..8; no_repeat
+ * outside {0, 1}; repeat_min_id < 0. */
+#define BOFI_REQUIRE_MAX 8
+int bofi_vocab_require(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, const int* words, int K, const uint32_t* ban_bits, int no_repeat,
+                       int repeat_min_id, int64_t* seq, float* row_chosen, int* pos, int* moved, void* stream);
+
 /* The bad-ending trim of the reference's decode_sequence (captioning/utils/misc.py:75-82, REMOVE_BAD_ENDINGS) and the flag of its count_bad
  * (captioning/utils/eval_utils.py:32-37), on id rows.  seq int64 [rows, S], 1 <= S <= 64.  The caption of a row is its ids before the first id <= limit
  * (the whole row without one; 'eval' rule: limit = 0), L of them.  trim_bits / count_bits: uint32 [ceil(V / 32)] each, bit (id % 32) of word id / 32 set for

@@ -25,6 +25,9 @@ the best of an image's N and their mean per metric (``oracle_<M>``, ``avg_<M>``:
 scored and dumped; ``--surface_stats 1`` adds ``bad_count_rate`` (with ``--language_eval 1``) and, with ``--sample_n N``, ``novel_sentences`` and ``vocab_size``
 of the sampled captions against the training sentences: the captions in ``--input_label_npz`` of every image of ``--input_json`` whose split is neither val nor
 test.  Both need the words' ids: ``--infos_path`` (a vocabulary), or ``--bad_endings W1,W2,...``, which overrides the trimmed word set for other vocabularies.
+``--require_words W1,W2,...`` (every image) or ``--require_words_json FILE`` ({image id: [words]}) (NAIC) places the words in the captions where they cost the least
+log-prob (boficap_amd.eval_utils.required_of; at most 8 per image): the predictions gain ``required`` ([word, position or null] per word) and a line reports
+``required_rate`` (words placed / words required) and ``required_moved_rate``.
 """
 import argparse
 import json
@@ -99,7 +102,19 @@ def main():
                     "neighbours repeat an earlier pair of words does not take the word that followed that pair (the reference's option, applied there on the autoregressive "
                     "paths only and as a penalty; here a hard block)")
     ap.add_argument("--ban_words", default="", help="NAIC only: W1,W2,... never appear in a caption (resolved to ids as --bad_endings resolves its words)")
+    ap.add_argument("--require_words", default="", help="NAIC only: W1,W2,... appear in every caption -- each placed on the position where it costs the least log-prob "
+                    "(eval_kwargs['require_words']; the predictions gain 'required', the statistics required_rate and required_moved_rate)")
+    ap.add_argument("--require_words_json", default="", help="NAIC only: a JSON file {image id: [W1, W2, ...]} of required words per image (the ids of --input_json, else "
+                    "the images' indices); not together with --require_words")
     args = ap.parse_args()
+    if args.require_words and args.require_words_json:
+        ap.error("--require_words and --require_words_json are two sources of the same words: give one")
+    if args.require_words or args.require_words_json:
+        try:
+            from boficap_amd import eval_utils as _eu
+            _eu.require_refusals(vars(args), args.inference_mode, args.sample_n)
+        except ValueError as e:
+            ap.error("--require_words / --require_words_json: " + str(e))
     try:                                                         # (before anything is loaded; the words are resolved once the vocabulary is)
         from boficap_amd import eval_utils as _eu
         _eu.constraint_of(vars(args), {"0": "UNK"}, args.inference_mode, args.sample_n)
@@ -192,6 +207,24 @@ def main():
         store = LabelStore(src, pad_idx=c.pad_idx, bos_idx=c.bos_idx, eos_idx=c.eos_idx, len_idx=c.len_idx)
     pick = eval_utils.constraint_of(vars(args), vocab or opt.vocab, args.inference_mode, args.sample_n)
     pick_opt = {"ban_ids": pick["ban_ids"], "decoding_constraint": int(pick["no_repeat"]), "block_trigrams": int(pick.get("block_trigrams", False))} if pick else {}      # (the same, in mode='sample''s names)
+    # --require_words / --require_words_json: per-batch id tables for decode_many (opt['require_ids'] per call on the synchronised path)
+    required, req_kw, req_pos, req_moved = None, [], [], 0
+    if args.require_words or args.require_words_json:
+        if args.require_words_json:
+            with open(args.require_words_json) as f:
+                req_spec = json.load(f)
+        else:
+            req_spec = args.require_words
+        try:
+            required = eval_utils.required_of({**vars(args), "require_words": req_spec}, vocab or opt.vocab, image_ids if image_ids is not None else list(range(len(feats))),
+                                              args.inference_mode, args.sample_n, pick.get("ban_ids", ()))
+        except ValueError as e:
+            ap.error(str(e))
+        if required is not None:
+            req_kw = [required[0][i:i + args.batch_size] for i in range(0, len(feats), args.batch_size)]
+
+    def req(n=None):
+        return {"require_ids": req_kw[:n]} if required is not None else {}
     changed, emitted = 0, 0
     results, seconds, rows, stats = [], 0.0, [], ([], [])
     store_loss = store is not None and not args.use_box          # (mode='forward' is not built for F = 2053: box features are decode-only)
@@ -228,12 +261,12 @@ def main():
                 return RegionFeeder(att_store, kb, workers=args.feeder_workers, norm_att_feat=bool(args.norm_att_feat),
                                     sizes=None if sizes is None else {k: wh for k, wh in zip(feats.keys, sizes)}, **box_kw)
             for _ in model.decode_many(feeder(key_batches[:2 * args.in_flight * args.batches_per_launch]), batches_per_launch=args.batches_per_launch, in_flight=args.in_flight,
-                                       fused_vocab=args.fused_vocab, **refine, **pick):
+                                       fused_vocab=args.fused_vocab, **refine, **pick, **req(2 * args.in_flight * args.batches_per_launch)):
                 pass                                             # graph captures and stream choice, outside the clock
             torch.cuda.synchronize()
             import time
             t0 = time.time()
-            got = list(model.decode_many(feeder(key_batches), batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab, **refine, **pick))
+            got = list(model.decode_many(feeder(key_batches), batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab, **refine, **pick, **req()))
             seconds = time.time() - t0
             i = 0
             for r in surfaced(got):
@@ -250,12 +283,13 @@ def main():
                 host = host.to(torch.bfloat16)
             host = host.pin_memory()
             batches = [host[i:i + args.batch_size] for i in range(0, host.size(0), args.batch_size)]
-            for _ in model.decode_many(batches[:2 * args.in_flight * args.batches_per_launch], batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab, **refine, **pick):
+            for _ in model.decode_many(batches[:2 * args.in_flight * args.batches_per_launch], batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab, **refine, **pick,
+                                       **req(2 * args.in_flight * args.batches_per_launch)):
                 pass                                             # graph captures and stream choice, outside the clock
             torch.cuda.synchronize()
             import time
             t0, got = time.time(), []
-            for r in model.decode_many(batches, batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab, **refine, **pick):
+            for r in model.decode_many(batches, batches_per_launch=args.batches_per_launch, in_flight=args.in_flight, fused_vocab=args.fused_vocab, **refine, **pick, **req()):
                 got.append(r)                                    # host tensors of one batch: ids, slot layout, entropy, perplexity
             seconds = time.time() - t0
             i = 0
@@ -272,8 +306,15 @@ def main():
                     att, masks = torch.from_numpy(np.ascontiguousarray(feats[i:i + args.batch_size])).cuda(), None
                 fc = torch.zeros(att.size(0), 0, device="cuda")
                 seq, lp, pn, pl, ps, t = model(fc, att, masks, opt=dict({"train_mode": args.inference_mode, "sample_method": "greedy", "sample_n": 1},
-                                                                                   **(dict(refine, **pick_opt) if args.inference_mode == "NAIC" else {})), mode="sample")
+                                                                                   **(dict(refine, **pick_opt) if args.inference_mode == "NAIC" else {}),
+                                                                                   **({"require_ids": req_kw[i // args.batch_size]} if required is not None else {})), mode="sample")
                 seconds += t
+                if required is not None:
+                    b = att.size(0)
+                    last = model.last_required
+                    req_pos.extend(last["pos"].cpu() if last is not None else [torch.empty(0, dtype=torch.int32)] * b)
+                    req_moved += int(last["moved"].sum()) if last is not None else 0
+                    emitted += 0 if pick else int(pl.sum())
                 if pick:
                     changed, emitted = changed + int(model.last_constrained.sum()), emitted + int(pl.sum())
                 # per-image entropy / perplexity as eval_utils.py:463-464, from the fused row reductions (bofi_vocab_stats); under mask-predict from the statistics of
@@ -287,6 +328,13 @@ def main():
             how = "one synchronised mode='sample' call per batch (the reference's eval loop), decode time only"
     if pick and args.pipeline:
         changed, emitted = sum(int(r["constrained"].sum()) for r in got), sum(int(r["phrase_length"].sum()) for r in got)
+    if required is not None and args.pipeline and args.inference_mode == "NAIC":
+        emitted = sum(int(r["phrase_length"].sum()) for r in got)
+        req_pos = [row for r in got for row in (r["required_pos"] if "required_pos" in r else [torch.empty(0, dtype=torch.int32)] * r["seq"].size(0))]
+        req_moved = sum(int(r["required_moved"].sum()) for r in got if "required_moved" in r)
+    if required is not None:
+        for e, ws, row in zip(results, required[1], req_pos):
+            e["required"] = eval_utils.required_entry(ws, row)
     if image_ids is not None:                                    # the json's ids, in the split's order
         for e, iid in zip(results, image_ids):
             e["image_id"] = iid
@@ -331,6 +379,11 @@ def main():
         print(f"constrained pick: {changed} of {emitted} emitted positions changed (constrained_rate {rate:.6f})")
         if lang_stats is not None:
             lang_stats["constrained_rate"] = rate
+    if required is not None:                                     # words placed over words required; positions the placement changed over positions emitted
+        rates = eval_utils.required_rates(required[1], req_pos, req_moved, emitted)
+        print(f"required words: required_rate {rates['required_rate']:.6f} required_moved_rate {rates['required_moved_rate']:.6f}")
+        if lang_stats is not None:
+            lang_stats.update(rates)
     if args.dump_json:
         with open(args.dump_json, "w") as f:
             if preds_n is not None:
