@@ -240,6 +240,12 @@ const char* vocab_pick_check(const float* x, int ldx, int rows, int V, int S, in
                              size_t work_bytes);
 int launch_vocab_pick(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int no_repeat,
                       int block_trigrams, int repeat_min_id, int64_t* seq, float* row_chosen, int* changed, void* work, size_t work_bytes, hipStream_t st);
+// the N most probable captions of the pass (bofi_vocab_nbest states the rule): the candidates launch above, then vocab_nbest_kernel, a wavefront per image
+size_t vocab_nbest_work_bytes(int rows);
+const char* vocab_nbest_check(const float* x, int ldx, int rows, int V, int S, int N, const int64_t* seq_n, const double* total, const int* count, const void* work,
+                              size_t work_bytes);      // NULL, or what is wrong (BOFI_ERR_ARG)
+int launch_vocab_nbest(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int N, int64_t* seq_n,
+                       double* total, int* count, void* work, size_t work_bytes, hipStream_t st);
 // ---- required words behind the filling pass (force.hip): the placement of at most 8 ids per image that costs the least log-prob (bofi_vocab_require states the rule);
 // ntok / ban_bits / row_chosen / moved may be NULL.  One launch, no workspace
 const char* vocab_require_check(const float* x, int ldx, int rows, int V, int S, const int* words, int K, int no_repeat, int repeat_min_id, const int64_t* seq,

@@ -298,7 +298,7 @@ __global__ void __launch_bounds__(VC_NT) vocab_candidates_k_kernel(VcArgs a, int
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid % WAVE, seg = tid / WAVE;
     const int b = row / a.S, s = row - b * a.S;
     if (s >= vc_live(a, b)) {
-        if (tid == 0) a.seq[row] = (int64_t)a.pad_idx;
+        if (tid == 0 && a.seq) a.seq[row] = (int64_t)a.pad_idx;    // (bofi_vocab_nbest has no seq: it pads its own outputs)
         return;
     }
     const uint32_t* ban = a.ban;
@@ -395,7 +395,190 @@ __global__ void __launch_bounds__(VC_SCAN_WAVES * WAVE) vocab_scan_k_kernel(VcAr
     if (lane == 0 && a.changed) a.changed[b] = __popcll(ch);
 }
 
+// ---- the N-best list (bofi_vocab_nbest): the N most probable captions of a pass that scores every position on its own.  A caption's log-prob is a sum of per-position
+// terms, so the N best use only each row's N best ids, and a width-N merge over the positions finds them exactly; include/boficap_hip.h, bofi_vocab_nbest, states the rule
+// (candidates, the float64 recurrence, the tie order), tests/test_nbest.py restates it in numpy and holds it to a brute force over every caption.
+//   candidates  the K-candidate launch above, unchanged (seq = NULL: it writes the workspace only)
+//   merge       one wavefront per image, four images per workgroup.  Lane = position first: the row's ids go from the workspace to LDS; a row whose order is cut
+//               (VP_CUT) inside its first N entries is streamed again by the whole wavefront (vk_row_behind, as the scan above) -- the result is the rule's for every
+//               input.  Then the n_b * N values x[p, c[p][r]]: scattered 4-byte loads, rows need no alignment.  Then lane = pair, lane = i * N + r (N <= 8: the 64 lanes
+//               hold every pair of a step): the lane forms its total T_i + (double)x, the totals meet in LDS, every lane counts the valid pairs in front of it (a larger
+//               total, or the same total and a lower lane) -- its rank --, the lanes of rank < N write (total, lane) as the new list.  The byte back-pointers [S][N], the
+//               ids and the values stay in LDS; lane j walks caption j back, the wavefront writes seq_n[b] as one contiguous block.
+// The loop over the positions is uniform over the workgroup (a wavefront past its n_b only meets the barriers).  No atomics; the only float arithmetic is the one float64
+// add per pair: no product, so nothing contracts.
+constexpr int NB_MAX = BOFI_NBEST_MAX;         // N at most
+constexpr int NB_IPW = 4;                      // images (wavefronts) per workgroup
+constexpr int NB_CHUNK = 16;                   // totals read from LDS at a time by the ranking loop
+static_assert(WAVE % NB_CHUNK == 0, "the ranking loop reads whole chunks of the wavefront's totals");
+static_assert(NB_MAX == VP_K && NB_MAX * NB_MAX == WAVE, "the candidates launch leaves NB_MAX ids per row; the lanes of a wavefront hold every pair of a step");
+
+struct NbArgs {
+    const float* x; int ldx, V, S, B;
+    const int* ntok; int ntok_bias, pad_idx;
+    const uint32_t* ban;
+    int N;
+    int64_t* seq_n; double* total; int* count;
+};
+
+__device__ __forceinline__ bool nb_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+__global__ void __launch_bounds__(NB_IPW * WAVE) vocab_nbest_kernel(NbArgs a, const int* __restrict__ work) {
+    __shared__ double tt_[NB_IPW][WAVE];                        // the totals of a step's pairs
+    __shared__ double T_[NB_IPW][NB_MAX];                       // the list's totals
+    __shared__ int cid_[NB_IPW][VC_MAX_S * NB_MAX];             // c[p][r]; VC_NONE: the row has no such id
+    __shared__ float xv_[NB_IPW][VC_MAX_S * NB_MAX];            // x[p, c[p][r]]; NaN where there is no id
+    __shared__ int out_[NB_IPW][NB_MAX * VC_MAX_S];             // the captions, [N][S]
+    __shared__ uint8_t bp_[NB_IPW][VC_MAX_S * NB_MAX];          // [p][j]: the pair (lane) that entry j of L_{p+1} came from
+    const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE, b = __builtin_amdgcn_readfirstlane(blockIdx.x * NB_IPW + wave);
+    const bool on = b < a.B;                                    // (a wavefront past B stays for the barriers and touches no global memory)
+    const int S = a.S, N = a.N, V = a.V;
+    double* const tt = tt_[wave];
+    double* const T = T_[wave];
+    int* const cid = cid_[wave];
+    float* const xv = xv_[wave];
+    int* const out = out_[wave];
+    uint8_t* const bp = bp_[wave];
+    int n = 0;
+    if (on) {
+        n = a.ntok ? a.ntok[b] + a.ntok_bias : S;
+        n = n < 0 ? 0 : (n > S ? S : n);
+    }
+    n = __builtin_amdgcn_readfirstlane(n);
+    const size_t row0 = (size_t)(on ? b : 0) * S;
+    // lane = position: the row's ids; cutk = the first entry within N from which the order is not known
+    int cutk = -1;
+    if (lane < n) {
+#pragma unroll
+        for (int k = 0; k < NB_MAX; ++k) {
+            int c = k < N ? work[(row0 + lane) * VP_K + k] : VC_NONE;
+            if (c == VP_CUT) { if (cutk < 0) cutk = k; }
+            else if ((unsigned)c >= (unsigned)V) c = VC_NONE;  // (VC_NONE itself; never an index outside the row)
+            cid[lane * NB_MAX + k] = cutk >= 0 ? VC_NONE : c;
+        }
+    }
+    __syncthreads();
+    for (unsigned long long cuts = __ballot(cutk >= 0); cuts; cuts &= cuts - 1) {      // the rows with a cut order, one at a time: the whole wavefront streams the row again
+        const int s = __builtin_amdgcn_readfirstlane(__ffsll((long long)cuts) - 1);
+        int k0 = __builtin_amdgcn_readlane(cutk, s);            // (>= 1: the first entry is never VP_CUT)
+        const float* const p = a.x + (row0 + s) * (size_t)a.ldx;
+        const int last = cid[s * NB_MAX + k0 - 1];
+        if (last == VC_NONE) continue;                          // (cannot be: a cut stands behind a real id)
+        uint64_t floor = vk_key(p[last], last);
+        while (k0 < N) {
+            const Best<VP_L> m = vk_row_behind(p, V, floor, a.ban, lane);
+#pragma unroll
+            for (int k = 0; k < VP_L; ++k)
+                if (lane == 0 && k0 + k < N) cid[s * NB_MAX + k0 + k] = vk_id(m.k[k]);
+            if (!m.k[VP_L - 1]) break;                          // the row is exhausted
+            floor = m.k[VP_L - 1];
+            k0 += VP_L;
+        }
+    }
+    __syncthreads();
+    // lane over the (position, candidate) pairs: the values
+    for (int i = lane; i < n * NB_MAX; i += WAVE) {
+        const int c = cid[i];
+        xv[i] = c != VC_NONE ? a.x[(row0 + i / NB_MAX) * (size_t)a.ldx + (size_t)c] : NAN;
+    }
+    if (lane < NB_MAX) T[lane] = 0.0;                           // L_0 = [(0.0, empty)]
+    __syncthreads();
+    const bool degen = __ballot(lane < n && !nb_finite(xv[lane * NB_MAX])) != 0ull;       // a live row whose first id has no finite value
+    // the merge, lane = pair
+    const int pi = lane / N, pr = lane - pi * N;
+    int cnt = 1;
+    bool valid = false;
+    double mine = 0.0;
+    for (int p = 0; p < S; ++p) {
+        const bool step = p < n && !degen;                      // (the same in every lane of the wavefront)
+        if (step) {
+            const float v = pi < cnt ? xv[p * NB_MAX + pr] : NAN;      // (pi < cnt <= N, so pr < N <= NB_MAX)
+            valid = pi < cnt && nb_finite(v);
+            mine = valid ? T[pi] + (double)v : -(double)INFINITY;      // (a pair that is not valid: in front of no valid pair, whose totals are finite)
+            tt[lane] = mine;
+        }
+        __syncthreads();
+        if (step) {
+            const unsigned long long vm = __ballot(valid);
+            int rank = 0;
+            for (int j0 = 0; j0 < cnt * N; j0 += NB_CHUNK) {      // (cnt * N <= WAVE and NB_CHUNK divides WAVE: a chunk never leaves tt; an entry past cnt * N is -inf)
+                double t[NB_CHUNK];
+#pragma unroll
+                for (int j = 0; j < NB_CHUNK; ++j) t[j] = tt[j0 + j];      // a chunk's LDS reads in flight together (one by one, a step was 64 dependent round trips)
+#pragma unroll
+                for (int j = 0; j < NB_CHUNK; ++j)      // (no && / ||: as branches they cost four times the compares)
+                    rank += (int)(t[j] > mine) | ((int)(t[j] == mine) & (int)(j0 + j < lane));
+            }
+            if (valid && rank < N) { T[rank] = mine; bp[p * NB_MAX + rank] = (uint8_t)lane; }
+            const int nv = __popcll(vm);
+            cnt = nv < N ? nv : N;
+        }
+        __syncthreads();
+    }
+    if (degen) cnt = 1;
+    // lane j < N: caption j into LDS, walked back along the pairs
+    if (on && lane < N) {
+        int e = lane;
+        for (int p = S - 1; p >= 0; --p) {
+            int id = a.pad_idx;
+            if (p < n && lane < cnt) {
+                if (degen) { const int c = cid[p * NB_MAX]; id = c != VC_NONE ? c : a.pad_idx; }
+                else {
+                    const int pair = bp[p * NB_MAX + e];
+                    e = pair / N;
+                    id = cid[p * NB_MAX + pair - e * N];
+                }
+            }
+            out[lane * S + p] = id;
+        }
+        a.total[(size_t)b * N + lane] = lane < cnt ? (degen ? (double)NAN : T[lane]) : -(double)INFINITY;
+    }
+    if (on && lane == 0) a.count[b] = cnt;
+    __syncthreads();
+    if (!on) return;
+    for (int i = lane; i < N * S; i += WAVE) a.seq_n[(size_t)b * N * S + i] = (int64_t)out[i];
+}
+
 }  // namespace
+
+size_t bofi::vocab_nbest_work_bytes(int rows) { return vocab_pick_work_bytes(rows); }
+
+const char* bofi::vocab_nbest_check(const float* x, int ldx, int rows, int V, int S, int N, const int64_t* seq_n, const double* total, const int* count, const void* work,
+                                    size_t work_bytes) {
+    if (!seq_n || !total || !count) return "non-null seq_n, total and count";
+    if (const char* why = vocab_constrain_check(x, ldx, rows, V, S, 0, 0, seq_n)) return why;
+    if (N < 1 || N > NB_MAX) return "N in 1..8 (BOFI_NBEST_MAX)";
+    if (rows > 0 && (!work || work_bytes < vocab_nbest_work_bytes(rows))) return "a workspace of bofi_vocab_nbest_workspace(rows) bytes";
+    return nullptr;
+}
+
+int bofi::launch_vocab_nbest(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int N,
+                             int64_t* seq_n, double* total, int* count, void* work, size_t work_bytes, hipStream_t st) {
+    if (vocab_nbest_check(x, ldx, rows, V, S, N, seq_n, total, count, work, work_bytes)) return BOFI_ERR_ARG;
+    if (rows == 0) return BOFI_OK;
+    VcArgs a{};
+    a.x = x; a.ldx = ldx; a.V = V; a.S = S; a.ntok = ntok; a.ntok_bias = ntok_bias; a.pad_idx = pad_idx; a.ban = ban_bits; a.ban_words = (V + 31) / 32;
+    a.ban_lds = a.ban_words <= VC_BAN_LDS_WORDS;                // (seq stays NULL: the candidates launch writes the workspace only)
+    const int B = rows / S;
+    if (ban_bits) hipLaunchKernelGGL(vocab_candidates_k_kernel<true>, dim3(rows), dim3(VC_NT), a.ban_lds ? (size_t)a.ban_words * 4 : 0, st, a, (int*)work);
+    else hipLaunchKernelGGL(vocab_candidates_k_kernel<false>, dim3(rows), dim3(VC_NT), 0, st, a, (int*)work);
+    BOFI_CHECK_LAUNCH();
+    NbArgs nb{};
+    nb.x = x; nb.ldx = ldx; nb.V = V; nb.S = S; nb.B = B; nb.ntok = ntok; nb.ntok_bias = ntok_bias; nb.pad_idx = pad_idx; nb.ban = ban_bits; nb.N = N;
+    nb.seq_n = seq_n; nb.total = total; nb.count = count;
+    hipLaunchKernelGGL(vocab_nbest_kernel, dim3((B + NB_IPW - 1) / NB_IPW), dim3(NB_IPW * WAVE), 0, st, nb, (const int*)work);
+    BOFI_CHECK_LAUNCH();
+    return BOFI_OK;
+}
+
+extern "C" int64_t bofi_vocab_nbest_workspace(int rows) { return (int64_t)bofi::vocab_nbest_work_bytes(rows); }
+
+extern "C" int bofi_vocab_nbest(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int N,
+                                int64_t* seq_n, double* total, int* count, void* work, int64_t work_bytes, void* stream) {
+    if (const char* why = bofi::vocab_nbest_check(x, ldx, rows, V, S, N, seq_n, total, count, work, work_bytes < 0 ? 0 : (size_t)work_bytes))
+        return bofi::fail(BOFI_ERR_ARG, std::string("vocab_nbest: ") + why);
+    return bofi::launch_vocab_nbest(x, ldx, rows, V, S, ntok, ntok_bias, pad_idx, ban_bits, N, seq_n, total, count, work, (size_t)work_bytes, (hipStream_t)stream);
+}
 
 size_t bofi::vocab_pick_work_bytes(int rows) { return (size_t)(rows > 0 ? rows : 0) * VP_K * sizeof(int); }
 

@@ -208,7 +208,8 @@ class BofiEngine:
                     want_logprob: bool = True, want_memory: bool = False, raw_logits: bool = False, graph: bool = False,
                     refine_rounds: int = 0, out: Optional[dict] = None, q1_group: int = 0, iter_cap: int = 0, phases: str = "", row_stats: bool = False,
                     ids_only: bool = False, refine_method: str = "feed_back", attn_topk: int = 0, attn_maps: bool = False, attn_heads: bool = False,
-                    attn_layer: int = -1, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7, block_trigrams: bool = False, require_ids=None) -> dict:
+                    attn_layer: int = -1, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7, block_trigrams: bool = False, require_ids=None,
+                    nbest: Optional[int] = None) -> dict:
         """Greedy NAIC bound+fill decode.  Returns a dict of device tensors: seq [B,S] int64,
         seq_logprob [B,S,V] float32 (or None), phrase_num [B] int32, phrase_length [B,S] int32,
         phrase_syn [B,S] int64, bound_iters [1] int32, memory [B,R,d] float32 (or None).
@@ -252,13 +253,26 @@ class BofiEngine:
         range, repeated), -3 not placeable; ``out['required_moved']`` int32 [B]: positions whose id changed; ``seq`` and, with ``row_stats``, ``row_chosen`` are those of
         the emitted ids.  With feed-back refinement rounds the placement applies to the LAST pass only: earlier passes are fed the unforced ids.  In the phased form it
         follows the call whose ``phases`` contain 'f'.  Not with ``ids_only`` (no distribution), ``refine_method='mask_predict'`` or ``block_trigrams`` (a placement
-        could create a blocked trigram).  None, an empty list or rows of -1 only: nothing is launched and no key is added."""
+        could create a blocked trigram).  None, an empty list or rows of -1 only: nothing is launched and no key is added.
+        ``nbest`` = N in 1..8 (bofi_vocab_nbest: two small launches on the same stream BEHIND the decode call, outside a ``graph`` replay; no field of the call record):
+        the N most probable captions of the last filling pass, exactly -- the pass scores every position on its own, so a caption's log-prob is a sum of per-position
+        terms and a width-N merge over each row's N best ids finds the N best captions (the header states the rule, its tie order and what holds under ties).  Read
+        from ``seq_logprob`` (the engine's own workspace without it; raw logits serve: the totals are then sums of logits), under the call's ``ban_ids``.
+        ``out['nbest_seq']`` int64 [B, N, S] (pad_idx past an image's length and past its count), ``out['nbest_logp']`` float64 [B, N] (non-increasing; -inf past
+        the count), ``out['nbest_count']`` int32 [B].  Entry 0 is the call's own ``seq`` on a NaN-free decode.  With feed-back rounds the list is the final pass's.
+        Refused before anything is enqueued: ``ids_only`` or an ids-only fork (there are no rows), ``refine_method='mask_predict'`` (kept positions do not hold their
+        row's first id), ``no_repeat`` / ``block_trigrams`` (a rule that couples neighbours needs per-last-id state: a width-N list is no longer exact) and
+        ``require_ids``.  None or 0: nothing is launched and no key is added."""
         mp = self._refine_flag(refine_method, refine_rounds, raw_logits)
         ban = self._pick_ban(ban_ids, block_trigrams)
         pick_on = ban is not None or bool(no_repeat) or bool(block_trigrams)
         req = self._require_table(require_ids, att_feats.size(0), ban_ids)
         if req is not None:
             self._require_refusals(ids_only, mp, block_trigrams)
+        nbest = self._nbest_width(nbest)
+        if nbest:
+            self._nbest_refusals(ids_only, mp, no_repeat, block_trigrams, req is not None,
+                                 want_logprob or (out is not None and out.get("seq_logprob") is not None))
         if pick_on and (ids_only or mp):
             raise hip.BofiHipError("ban_ids / no_repeat / block_trigrams: not with ids_only (no distribution to re-pick from) or refine_method='mask_predict'")
         if ids_only:
@@ -320,7 +334,57 @@ class BofiEngine:
             out["required_pos"], out["required_moved"] = self._require_place(
                 req, out["seq"], out["seq_logprob"], torch.sum(out["phrase_length"], 1, dtype=torch.int32), 0, ban, no_repeat, repeat_min_id,
                 out["row_chosen"] if row_stats else None, out.get("required_pos"), out.get("required_moved"))
+        if not nbest:
+            out.pop("nbest_seq", None), out.pop("nbest_logp", None), out.pop("nbest_count", None)      # (a reused `out` of a call that had the option)
+        elif not phases or "f" in phases:
+            out["nbest_seq"], out["nbest_logp"], out["nbest_count"] = self._nbest_list(
+                nbest, B, out["seq_logprob"], torch.sum(out["phrase_length"], 1, dtype=torch.int32), 0, ban, out.get("nbest_seq"), out.get("nbest_logp"),
+                out.get("nbest_count"))
         return out
+
+    @staticmethod
+    def _nbest_width(nbest) -> int:
+        """``nbest`` of a decode as N, 0 when off (None or 0); BofiHipError outside 1..8."""
+        if nbest is None or nbest is False:
+            return 0
+        n = int(nbest)
+        if n != 0 and not 1 <= n <= hip.NBEST_MAX:
+            raise hip.BofiHipError(f"nbest: N must lie in 1..{hip.NBEST_MAX} (0 / None: off), got {n}")
+        return n
+
+    def _nbest_refusals(self, ids_only: bool, mp: int, no_repeat: bool, block_trigrams: bool, required: bool, own_rows: bool) -> None:
+        if ids_only:
+            raise hip.BofiHipError("nbest: not with ids_only (the decode leaves no rows to list from)")
+        if mp:
+            raise hip.BofiHipError("nbest: not with refine_method='mask_predict' (kept positions do not hold their row's first id: entry 0 would not be the caption)")
+        if no_repeat or block_trigrams:
+            raise hip.BofiHipError("nbest: not with no_repeat / block_trigrams (the N best under a rule that couples neighbours need per-last-id state: "
+                                   "a width-N list is no longer exact)")
+        if required:
+            raise hip.BofiHipError("nbest: not with require_ids (the list is of unforced captions)")
+        if not own_rows and not self._lib.bofi_engine_logprob(self._h):
+            raise hip.BofiHipError("nbest: this engine keeps no log-prob workspace (an ids-only fork): there are no rows to list from")
+
+    def _nbest_list(self, N: int, B: int, lp, ntok, ntok_bias, ban, seq_n=None, total=None, count=None):
+        """Enqueue bofi_vocab_nbest on the current stream behind a decode: ``lp`` the decode's log-prob (or logit) tensor or None for the engine's own workspace.
+        Returns (seq_n int64 [B, N, S], total float64 [B, N], count int32 [B]); the buffers given are reused when they fit."""
+        S, V, dev = self.cfg.seq_length, self.cfg.tgt_vocab, ntok.device
+        if seq_n is None or tuple(seq_n.shape) != (B, N, S):
+            seq_n = torch.empty(B, N, S, dtype=torch.int64, device=dev)
+        if total is None or tuple(total.shape) != (B, N):
+            total = torch.empty(B, N, dtype=torch.float64, device=dev)
+        if count is None or count.numel() != B:
+            count = torch.empty(B, dtype=torch.int32, device=dev)
+        need = int(self._lib.bofi_vocab_nbest_workspace(B * S))
+        work = getattr(self, "_nbest_work", None)
+        if work is None or work.numel() * 4 < need or work.device != dev:
+            work = self._nbest_work = torch.empty(max(1, need // 4), dtype=torch.int32, device=dev)
+        src = hip.ptr(lp) if lp is not None else self._lib.bofi_engine_logprob(self._h)
+        if not src:
+            raise hip.BofiHipError("nbest: this engine keeps no log-prob workspace (an ids-only fork)")
+        hip.check(self._lib.bofi_vocab_nbest(src, V, B * S, V, S, hip.ptr(ntok), int(ntok_bias), int(self.cfg.pad_idx), hip.ptr(ban), N, hip.ptr(seq_n), hip.ptr(total),
+                                             hip.ptr(count), hip.ptr(work), work.numel() * 4, hip.stream_ptr()), "bofi_vocab_nbest")
+        return seq_n, total, count
 
     def _require_table(self, require_ids, B: int, ban_ids=None):
         """``require_ids`` of a decode as the device table int32 [B, K] of bofi_vocab_require, None when nothing is required.  Host input goes through
@@ -529,7 +593,7 @@ class BofiEngine:
 
     def decode_saic(self, att_feats: torch.Tensor, att_len: Optional[torch.Tensor] = None, *, raw_logits: bool = False,
                     want_logprob: bool = True, sample: Optional[tuple] = None, graph: bool = False, out: Optional[dict] = None,
-                    it_range: Optional[tuple] = None, layout_only: bool = False) -> dict:
+                    it_range: Optional[tuple] = None, layout_only: bool = False, nbest: Optional[int] = None) -> dict:
         """Semi-autoregressive decode (core_SAIC), greedy or -- ``sample=(temperature, seed)`` -- with every phrase's tokens
         drawn from Categorical(logits / temperature) (the bound heads stay greedy, as in the reference).  Same result
         layout as ``decode_naic``.  ``graph``: the launch sequence is captured once per argument set and replayed (pass the
@@ -537,7 +601,11 @@ class BofiEngine:
         draw anew.  ``it_range`` = (first, last) iterations of the loop (bofi_call_opts_t.saic_it_begin / saic_it_end): (1, c) enqueues c iterations,
         (c + 1, S) with the same arguments and ``out`` continues that decode where it stopped -- together the whole loop, exactly;
         ``out["bound_iters"]`` (live iterations so far) < c says the first part was all of it.  ``layout_only``: the enqueued iterations lay their phrases out and stop
-        (BOFI_FLAG_SAIC_LAYOUT_ONLY: no decoder pass, no tokens) -- for a caller that draws the words itself and hands them back with ``saic_put_words``."""
+        (BOFI_FLAG_SAIC_LAYOUT_ONLY: no decoder pass, no tokens) -- for a caller that draws the words itself and hands them back with ``saic_put_words``.
+        ``nbest`` is refused here: a phrase's rows are conditioned on the phrases before it, so a caption's log-prob is no sum of independent per-position terms."""
+        if self._nbest_width(nbest):
+            raise hip.BofiHipError("nbest: not with decode_saic (a phrase's rows depend on the phrases before it: the per-position sums are not a caption's log-prob); "
+                                   "decode_naic / fill_naic serve it")
         self._check_feats(att_feats, att_len)
         B, R, _ = att_feats.shape
         S, V, dev = self.cfg.seq_length, self.cfg.tgt_vocab, att_feats.device
@@ -593,13 +661,14 @@ class BofiEngine:
     def fill_naic(self, ext_syn: torch.Tensor, last: torch.Tensor, R: int, att_len: Optional[torch.Tensor] = None, *, strict_q1: bool = True,
                   raw_logits: bool = False, refine_rounds: int = 0, refine_method: str = "feed_back", attn_topk: int = 0, attn_maps: bool = False,
                   attn_heads: bool = False, attn_layer: int = -1, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7, block_trigrams: bool = False,
-                  require_ids=None):
+                  require_ids=None, nbest: Optional[int] = None):
         """The filling pass alone on a given slot layout (``ext_syn`` int32 [B, S+2], ``last`` int32 [B]) and the memory of the
         preceding ``encode``: (seq int64 [B, S], seq_logprob float32 [B, S, V]); with ``refine_method='mask_predict'`` (as ``decode_naic``) a third
         element, refine_round int32 [B, S].  With ``attn_topk`` / ``attn_maps`` / ``attn_heads`` (as ``decode_naic``) a last element, a dict of the attention tensors
         ('attn', 'attn_heads', 'attn_top', 'attn_top_w': those asked for).  ``ban_ids`` / ``no_repeat`` / ``repeat_min_id`` / ``block_trigrams`` as ``decode_naic``: that dict (the last element)
         then carries 'constrained', int32 [B].  ``require_ids`` as ``decode_naic`` (bofi_vocab_require behind the call, on the last pass; the same refusals): that dict
-        then carries 'required_pos' int32 [B, K] and 'required_moved' int32 [B]."""
+        then carries 'required_pos' int32 [B, K] and 'required_moved' int32 [B].  ``nbest`` as ``decode_naic`` (bofi_vocab_nbest behind the call, on the last pass; the
+        same refusals): that dict then carries 'nbest_seq' int64 [B, N, S], 'nbest_logp' float64 [B, N] and 'nbest_count' int32 [B]."""
         mp = self._refine_flag(refine_method, refine_rounds, raw_logits)
         ban = self._pick_ban(ban_ids, block_trigrams)
         pick_on = ban is not None or bool(no_repeat) or bool(block_trigrams)
@@ -608,6 +677,9 @@ class BofiEngine:
         req = self._require_table(require_ids, ext_syn.size(0), ban_ids)
         if req is not None:
             self._require_refusals(False, mp, block_trigrams)
+        nbest = self._nbest_width(nbest)
+        if nbest:
+            self._nbest_refusals(False, mp, no_repeat, block_trigrams, req is not None, True)
         B = ext_syn.size(0)
         if ext_syn.dtype != torch.int32 or last.dtype != torch.int32 or ext_syn.size(1) != self.cfg.bound_len or last.numel() != B:
             raise hip.BofiHipError("ext_syn must be int32 [B, S+2] and last int32 [B]")
@@ -627,6 +699,8 @@ class BofiEngine:
             hip.check(self._lib.bofi_engine_pick_changed(self._h, hip.ptr(attn["constrained"]), B, hip.stream_ptr()), "bofi_engine_pick_changed")
         if req is not None:
             attn["required_pos"], attn["required_moved"] = self._require_place(req, seq, lp, last.contiguous(), -1, ban, no_repeat, repeat_min_id, None)
+        if nbest:
+            attn["nbest_seq"], attn["nbest_logp"], attn["nbest_count"] = self._nbest_list(nbest, B, lp, last.contiguous(), -1, ban)
         res = (seq, lp, rnd) if mp else (seq, lp)
         return res + (attn,) if attn else res
 

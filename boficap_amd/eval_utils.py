@@ -28,6 +28,13 @@ references alone (integer rows or id strings; no loss then), or None.  ``eval_kw
                      ``sample_method='sample'`` (eval_split_n, eval_utils.py:670-700, ``sample_n_method='sample'``); their entries are stored under
                      ``eval_kwargs['preds_n']``, and ``lang_stats`` gains the diversity statistics of boficap_amd.diversity ('Div-1', 'Div-2',
                      'mBLEU_1'..'mBLEU_4', 'self_cider'; per image under ``eval_kwargs['diversity_per_image']``) on the document frequencies of
+    sample_n_method  'sample' (default) or 'nbest' (the reference's 'bs', the N best of a beam, for the non-autoregressive decode -- where it is exact and no search):
+                     the ``sample_n`` rows per image are the N most probable captions of the filling pass, most probable first (``mode='sample'`` with
+                     ``opt['nbest']``: one decode plus two small launches; deterministic, where 'sample' draws).  N <= 8, inference_mode 'NAIC' only, not with mask-predict or
+                     ``require_words``; ``suppress_UNK`` / ``ban_words`` apply to the list too, ``decoding_constraint`` / ``block_trigrams`` stay refused.  Every
+                     entry of ``preds_n`` carries 'logp' (float64 sum of its positions' log-probs; -inf for the empty rows of an image that has fewer than N
+                     distinct captions); the number of such images is ``lang_stats['nbest_short']``.  The rows feed the diversity statistics, the oracle scores
+                     and the surface statistics exactly as sampled rows do
     cached_tokens    a df pickle of scripts/prepro_ngrams.py: a path, or a name resolved as data/<name>.p (default 'coco-train-idxs')
     eval_oracle      1, with ``language_eval`` 1 and ``sample_n`` > 1 (nothing changes otherwise): every sampled caption is scored against its image's
                      references and ``lang_stats`` gains 'oracle_<M>' (the best of an image's N, averaged over the images) and 'avg_<M>' (their mean)
@@ -132,15 +139,46 @@ class SyntheticLabels:
         return self.host["labels"][int(ix), :, 1:-1]
 
 
-def sample_n_predictions(model, feats, sample_n: int, mode: str = "NAIC", batch_size: int = 64, vocab=None, surface=None):
-    """eval_split_n (eval_utils.py:670-700) for ``sample_n_method='sample'``: ``sample_n`` captions per image of ``feats`` drawn through
-    ``mode='sample'``.  Returns (entries {'image_id', 'seq'[, 'caption']} in row order, the sampled ids [N * sample_n, S] on the device); an
-    entry's 'seq' holds the ids before the first id <= 0 (decode_sequence).  ``surface``: a ``CaptionSurface`` -- the ids are trimmed of their bad endings on
-    the device first, and both results are the trimmed ones."""
+SAMPLE_N_METHODS = ("sample", "nbest")
+
+
+def sample_n_method_of(eval_kwargs, mode: str = "NAIC", sample_n: int = 1) -> str:
+    """``eval_kwargs['sample_n_method']``: 'sample' (the default) or 'nbest'; any other string is a ValueError that names the two.  With ``sample_n`` > 1, 'nbest' is a
+    ValueError where the list cannot be made: SAIC mode, more than 8 captions per image, mask-predict, ``decoding_constraint`` / ``block_trigrams``."""
+    method = eval_kwargs.get("sample_n_method", "sample") or "sample"
+    if method not in SAMPLE_N_METHODS:
+        raise ValueError(f"sample_n_method {method!r}: 'sample' (sample_n random draws) and 'nbest' (the sample_n most probable captions of the filling pass) are served")
+    if method == "nbest" and int(sample_n) > 1:
+        from .hip import NBEST_MAX
+        if mode != "NAIC":
+            raise ValueError("sample_n_method 'nbest' lists the non-autoregressive filling pass's captions: inference_mode 'NAIC' only")
+        if int(sample_n) > NBEST_MAX:
+            raise ValueError(f"sample_n_method 'nbest': at most {NBEST_MAX} captions per image, got sample_n = {int(sample_n)}")
+        if eval_kwargs.get("refine_method", "feed_back") == "mask_predict":
+            raise ValueError("sample_n_method 'nbest': not with refine_method 'mask_predict' (kept positions do not hold their row's first id)")
+        if int(eval_kwargs.get("decoding_constraint", 0)) == 1 or int(eval_kwargs.get("block_trigrams", 0) or 0) == 1:
+            raise ValueError("sample_n_method 'nbest': not with decoding_constraint / block_trigrams (a rule that couples neighbours needs per-last-id state: a "
+                             "width-N list is no longer exact)")
+    return method
+
+
+def sample_n_predictions(model, feats, sample_n: int, mode: str = "NAIC", batch_size: int = 64, vocab=None, surface=None, method: str = "sample", ban_ids=None,
+                         refine_rounds: int = 0, info=None):
+    """eval_split_n (eval_utils.py:670-700): ``sample_n`` captions per image of ``feats`` through ``mode='sample'`` -- drawn (``method='sample'``, the reference's
+    ``sample_n_method='sample'``) or the ``sample_n`` most probable captions of the NAIC filling pass, most probable first (``method='nbest'``: ``opt['nbest']``, under
+    ``ban_ids`` and after ``refine_rounds`` feed-back rounds; rows past an image's count are the empty captions the kernel wrote).  Returns (entries {'image_id',
+    'seq'[, 'caption'][, 'logp']} in row order, the ids [N * sample_n, S] on the device); an entry's 'seq' holds the ids before the first id <= 0 (decode_sequence);
+    'logp' (``'nbest'`` only) is the caption's float64 total, -inf on an empty row past the count.  ``info``: a dict that receives 'nbest_short', the number of images
+    with fewer than ``sample_n`` captions.  ``surface``: a ``CaptionSurface`` -- the ids are trimmed of their bad endings on the device first, and both results are
+    the trimmed ones."""
+    if method not in SAMPLE_N_METHODS:
+        raise ValueError(f"sample_n_method {method!r}: 'sample' and 'nbest' are served")
+    if method == "nbest" and mode != "NAIC":
+        raise ValueError("sample_n_method 'nbest' lists the non-autoregressive filling pass's captions: inference_mode 'NAIC' only")
     n, ragged = int(sample_n), is_region_source(feats)
     host = feats if ragged else _torch_feats(feats)
     step = batch_size if mode == "NAIC" else max(1, min(batch_size, model.max_batch // n))       # the SAIC sampler decodes images x n rows
-    rows = []
+    rows, logps, short = [], [], 0
     with torch.no_grad():
         for i in range(0, len(host), step):
             if ragged:
@@ -150,8 +188,19 @@ def sample_n_predictions(model, feats, sample_n: int, mode: str = "NAIC", batch_
             if att.dtype != torch.float32 and att.dtype != model.compute_dtype:
                 att = att.float()
             fc = torch.zeros(att.size(0), 0, device="cuda")
-            rows.append(model(fc, att, masks, opt={"train_mode": mode, "sample_method": "sample", "sample_n": n}, mode="sample")[0])
+            if method == "nbest":
+                opt = {"train_mode": mode, "sample_method": "greedy", "sample_n": 1, "nbest": n, "refine_rounds": int(refine_rounds), "ban_ids": list(ban_ids or ())}
+                model(fc, att, masks, opt=opt, mode="sample")
+                nb = model.last_nbest
+                rows.append(nb["seq"].reshape(-1, nb["seq"].size(-1)))
+                logps.append(nb["logp"].reshape(-1))
+                short += int((nb["count"] < n).sum())
+            else:
+                rows.append(model(fc, att, masks, opt={"train_mode": mode, "sample_method": "sample", "sample_n": n}, mode="sample")[0])
     seq = torch.cat(rows)
+    logp = torch.cat(logps).cpu().tolist() if logps else None
+    if info is not None and method == "nbest":
+        info["nbest_short"] = short
     if surface is not None:
         seq = surface.trim(seq)[0]
     entries = []
@@ -160,6 +209,8 @@ def sample_n_predictions(model, feats, sample_n: int, mode: str = "NAIC", batch_
         entry = {"image_id": j // n, "seq": [int(v) for v in row[:stop]]}
         if vocab:
             entry["caption"] = " ".join(vocab.get(str(v), "UNK") for v in entry["seq"] if v > 6)
+        if logp is not None:
+            entry["logp"] = float(logp[j])
         entries.append(entry)
     return entries, seq
 
@@ -206,7 +257,8 @@ def constraint_of(eval_kwargs, vocab, mode: str = "NAIC", sample_n: int = 1):
     reference's names; both default to 0 here: on this path the reference's options do nothing, and the defaults keep the captions) and ``ban_words`` (a list of
     words, or 'W1,W2,...') and ``block_trigrams`` (the reference's name and default, 0: no word trigram twice in a caption) are all off, else {'ban_ids': sorted ids,
     'no_repeat': bool}, with 'block_trigrams': True beside them when that option is on.  Words resolve to ids as the bad-ending words do (``surface.ids_of`` on
-    ``vocab``; a word the vocabulary does not hold names no id).  ValueError where the options cannot apply: SAIC mode, ``fused_vocab``, mask-predict, sampling."""
+    ``vocab``; a word the vocabulary does not hold names no id).  ValueError where the options cannot apply: SAIC mode, ``fused_vocab``, mask-predict, sampling
+    (``sample_n`` > 1) -- except that ``suppress_UNK`` / ``ban_words`` go with ``sample_n_method='nbest'``, whose list is made under the same ban."""
     kw = eval_kwargs
     words = kw.get("ban_words") or []
     words = [w for w in words.split(",") if w] if isinstance(words, str) else list(words)
@@ -219,8 +271,9 @@ def constraint_of(eval_kwargs, vocab, mode: str = "NAIC", sample_n: int = 1):
         raise ValueError("suppress_UNK / decoding_constraint / ban_words / block_trigrams: not with fused_vocab (no distribution to re-pick from)")
     if kw.get("refine_method", "feed_back") == "mask_predict":
         raise ValueError("suppress_UNK / decoding_constraint / ban_words / block_trigrams: not with refine_method 'mask_predict'")
-    if int(sample_n) > 1:
-        raise ValueError("suppress_UNK / decoding_constraint / ban_words / block_trigrams constrain greedy picks: not with sample_n > 1")
+    if int(sample_n) > 1 and (kw.get("sample_n_method", "sample") != "nbest" or rep or tri):      # (banned ids go with the N-best list; a rule that couples neighbours does not)
+        raise ValueError("suppress_UNK / decoding_constraint / ban_words / block_trigrams constrain greedy picks: not with sample_n > 1"
+                         + (" (sample_n_method 'nbest' takes suppress_UNK / ban_words only)" if kw.get("sample_n_method", "sample") == "nbest" else ""))
     if (unk or words) and not vocab:
         raise ValueError("suppress_UNK / ban_words need a vocabulary ({str(id): word})")
     from .surface import ids_of
@@ -310,6 +363,7 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
     refine = {"refine_rounds": int(kw.get("refine_rounds", 0)), "refine_method": kw.get("refine_method", "feed_back")}
     if mode != "NAIC" and (refine["refine_rounds"] or refine["refine_method"] != "feed_back"):
         raise ValueError("refine_rounds / refine_method refine the non-autoregressive filling pass: inference_mode 'NAIC' only")
+    n_method = sample_n_method_of(kw, mode, sample_n)
     attn_topk = int(kw.get("attn_topk", 0))
     if attn_topk and mode != "NAIC":
         raise ValueError("attn_topk reads the non-autoregressive filling pass's cross-attention: inference_mode 'NAIC' only")
@@ -404,9 +458,16 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
                 ev = kw["lang_eval"] = LanguageEval(gts, next(model.parameters()).device)
             lang_stats = ev.evaluate(scored if remove else torch.cat(seqs), torch.cat(ents), torch.cat(ppls))
         if sample_n > 1:                                         # eval_split_n + the div_stats / self_cider of language_eval (eval_utils.py:105-120)
-            kw["preds_n"], sampled = sample_n_predictions(model, feats, sample_n, mode, batch_size, vocab, surface if remove else None)
+            if n_method == "nbest":                              # the sample_n most probable captions of the filling pass in place of sample_n draws
+                info = {}
+                kw["preds_n"], sampled = sample_n_predictions(model, feats, sample_n, mode, batch_size, vocab, surface if remove else None, method="nbest",
+                                                              ban_ids=pick.get("ban_ids"), refine_rounds=refine["refine_rounds"], info=info)
+            else:
+                kw["preds_n"], sampled = sample_n_predictions(model, feats, sample_n, mode, batch_size, vocab, surface if remove else None)
             div, kw["diversity_per_image"] = diversity_stats(sampled, sample_n, kw)
             lang_stats = dict(lang_stats or {}, **div)
+            if n_method == "nbest":
+                lang_stats["nbest_short"] = kw["nbest_short"] = info["nbest_short"]
             if ev is not None and int(kw.get("eval_oracle", 0)) == 1:      # the oracle of language_eval (eval_utils.py:112-114): inside it, and only with a preds_n
                 oracle = ev.evaluate_n(sampled, sample_n)
                 kw["oracle_per_image"] = oracle.pop("per_image")

@@ -24,6 +24,7 @@ FLAG_PICK_TRIGRAMS = 32768
 FORK_IDS_ONLY = 1
 ABI_VERSION = 5
 REQUIRE_MAX = 8                     # BOFI_REQUIRE_MAX: required words per image (bofi_vocab_require)
+NBEST_MAX = 8                       # BOFI_NBEST_MAX: captions per image of bofi_vocab_nbest
 
 
 class BofiHipError(RuntimeError):
@@ -139,6 +140,8 @@ SIGNATURES = {
     "bofi_vocab_pick_workspace": (_I64, [_I]),
     "bofi_vocab_pick": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _I64, _P]),
     "bofi_vocab_require": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "bofi_vocab_nbest_workspace": (_I64, [_I]),
+    "bofi_vocab_nbest": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _I64, _P]),
     "bofi_caption_trim": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     "bofi_sentence_lookup": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
 }
@@ -415,6 +418,40 @@ def vocab_require(x, V, S, seq, words, pos, *, ntok=None, ntok_bias=0, ban=None,
             raise BofiHipError(f"vocab_require: {name} must be a contiguous {dt} device tensor of {n} elements")
     check(lib().bofi_vocab_require(ptr(x), x.stride(0), rows, int(V), int(S), ptr(ntok), int(ntok_bias), ptr(words), int(K), ptr(ban), 1 if no_repeat else 0,
                                    int(repeat_min_id), ptr(seq), ptr(row_chosen), ptr(pos), ptr(moved), stream_ptr()), "bofi_vocab_require")
+
+
+def vocab_nbest(x, V, S, N, *, ntok=None, ntok_bias=0, pad_idx=0, ban=None, seq_n=None, total=None, count=None, work=None):
+    """``bofi_vocab_nbest`` on torch tensors: the N most probable captions of the rows x float32 [rows, >= V] (device, unit column stride, any 4-byte alignment; read
+    only), ntok int32 [rows / S] or None, ban the bit table of ``ban_bits`` or None.  Returns ``(seq_n int64 [B, N, S], total float64 [B, N], count int32 [B])``; each may
+    be given (contiguous, on the device), as may ``work``, an int32 workspace of at least ``bofi_vocab_nbest_workspace(rows)`` bytes.  Two launches on the current stream,
+    no synchronisation."""
+    import torch
+    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or not x.is_cuda:
+        raise BofiHipError("vocab_nbest: x must be a 2-d float32 device tensor with unit column stride")
+    rows = x.size(0)
+    if x.size(1) < V or S < 1 or rows % S:
+        raise BofiHipError("vocab_nbest: x needs V columns and a multiple of S rows")
+    N = int(N)
+    if not 1 <= N <= NBEST_MAX:
+        raise BofiHipError(f"vocab_nbest: N must lie in 1..{NBEST_MAX}, got {N}")
+    B = rows // S
+    if seq_n is None:
+        seq_n = torch.empty(B, N, S, dtype=torch.int64, device=x.device)
+    if total is None:
+        total = torch.empty(B, N, dtype=torch.float64, device=x.device)
+    if count is None:
+        count = torch.empty(B, dtype=torch.int32, device=x.device)
+    if work is None:
+        work = torch.empty(max(1, lib().bofi_vocab_nbest_workspace(rows) // 4), dtype=torch.int32, device=x.device)
+    for name, t, dt, n in (("seq_n", seq_n, torch.int64, B * N * S), ("total", total, torch.float64, B * N), ("count", count, torch.int32, B),
+                           ("ntok", ntok, torch.int32, B), ("ban", ban, torch.int32, (V + 31) // 32), ("work", work, torch.int32, None)):
+        if t is None and name in ("ntok", "ban"):
+            continue
+        if t is None or t.dtype != dt or (n is not None and t.numel() != n) or not t.is_cuda or not t.is_contiguous():
+            raise BofiHipError(f"vocab_nbest: {name} must be a contiguous {dt} device tensor" + ("" if n is None else f" of {n} elements"))
+    check(lib().bofi_vocab_nbest(ptr(x), x.stride(0), rows, int(V), int(S), ptr(ntok), int(ntok_bias), int(pad_idx), ptr(ban), N, ptr(seq_n), ptr(total), ptr(count),
+                                 ptr(work), work.numel() * 4, stream_ptr()), "bofi_vocab_nbest")
+    return seq_n, total, count
 
 
 def gemm_flops(reset: bool = False):

@@ -363,6 +363,27 @@ class TransformerModel(nn.Module):
             if refine_method == "mask_predict":
                 raise hip.BofiHipError("require_ids: not with refine_method='mask_predict'")
             rkw.update(require_ids=require_ids)
+        # opt['nbest'] = N in 1..8: the N most probable captions of the NAIC filling pass (BofiEngine.decode_naic(nbest=N): exact, one decode plus two small launches); the
+        # 6-tuple stays, the lists land in self.last_nbest ({'seq' int64 [B, N, S], 'logp' float64 [B, N], 'count' int32 [B]}, per image -- not repeated under sample_n;
+        # None without the option).  The refusals are the engine's, raised here before anything is enqueued
+        nbest = int(opt.get("nbest", 0) or 0)
+        self.last_nbest = None
+        if nbest:
+            if not 1 <= nbest <= hip.NBEST_MAX:
+                raise hip.BofiHipError(f"nbest: N must lie in 1..{hip.NBEST_MAX}, got {nbest}")
+            if train_mode != "NAIC":
+                raise hip.BofiHipError("nbest lists the non-autoregressive filling pass's captions: train_mode 'NAIC' only (a semi-autoregressive phrase's rows depend "
+                                       "on the phrases before it)")
+            if sample_method == "sample":
+                raise hip.BofiHipError("nbest lists the greedy decode's alternatives: not with sample_method='sample'")
+            if refine_method == "mask_predict":
+                raise hip.BofiHipError("nbest: not with refine_method='mask_predict' (kept positions do not hold their row's first id)")
+            if no_repeat or block_trigrams:
+                raise hip.BofiHipError("nbest: not with decoding_constraint / block_trigrams (a rule that couples neighbours needs per-last-id state: a width-N list "
+                                       "is no longer exact)")
+            if "require_ids" in rkw:
+                raise hip.BofiHipError("nbest: not with require_ids (the list is of unforced captions)")
+            rkw.update(nbest=nbest)
         eng = self.engine()
         torch.cuda.synchronize()                                  # the reference does (AttModel.py:337)
         start = time.time()
@@ -397,6 +418,8 @@ class TransformerModel(nn.Module):
                 self.last_attn = {k: (r[k].repeat_interleave(sample_n, dim=0) if sample_n > 1 else r[k]) for k in keys}
             if "required_pos" in r:
                 self.last_required = {k: (r["required_" + k].repeat_interleave(sample_n, dim=0) if sample_n > 1 else r["required_" + k]) for k in ("pos", "moved")}
+            if "nbest_seq" in r:
+                self.last_nbest = {"seq": r["nbest_seq"], "logp": r["nbest_logp"], "count": r["nbest_count"]}
             if "ban_ids" in rkw:
                 self.last_constrained = r["constrained"].repeat_interleave(sample_n, dim=0) if sample_n > 1 else r["constrained"]
         elif sample_method == "greedy":                           # core_SAIC, AttModel.py:430-437

@@ -851,6 +851,32 @@ int bofi_vocab_pick(const float* x, int ldx, int rows, int V, int S, const int* 
 int bofi_vocab_require(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, const int* words, int K, const uint32_t* ban_bits, int no_repeat,
                        int repeat_min_id, int64_t* seq, float* row_chosen, int* pos, int* moved, void* stream);
 
+/* The N most probable captions of a filling pass, exactly -- the reference's sample_n_method = 'bs' (the N best of a beam) for the non-autoregressive decode, where it is
+ * no search: the pass scores every position on its own, a caption's log-probability is a sum of per-position terms, the N best captions use only each row's N best ids,
+ * and a width-N merge over the positions finds them.  A stand-alone call behind the decode: no field of bofi_call_opts_t, no engine state, the ABI version is unchanged.
+ *   x, ldx, rows, V, S, ntok, ntok_bias, pad_idx, ban_bits: bofi_vocab_constrain's; x is read only.  n_b = clamp(ntok[b] + ntok_bias, 0, S).  1 <= N <= BOFI_NBEST_MAX.
+ * Candidates: c[p][0 .. N-1] are the first N unbanned ids of row p in bofi_vocab_constrain's order; a row with fewer unbanned ids has fewer candidates.  Entry r >= 1 is
+ * not a candidate when x[p, c[p][r]] is NaN or +-inf; the remaining entries keep their index r.
+ * Degenerate image: a live row's x[p, c[p][0]] is not finite (or the row has no unbanned id at all: pad_idx stands for c[p][0]).  It gets count = 1, caption 0 is c[p][0]
+ * at every live p, total[b, 0] = NaN.
+ * Recurrence: L_0 = [(0.0, empty)]; L_{p+1} is built from all pairs (i, r), i an entry of L_p and r a candidate of row p, with total = T_i + (double)x[p, c[p][r]] -- one
+ * float64 add per pair, taken left to right over p.  The pairs are ordered by total descending, then i ascending, then r ascending; the first N are kept.
+ * Outputs: count int32 [B] = |L_{n_b}|; seq_n int64 [B, N, S]: the ids of entry j for p < n_b, pad_idx for p >= n_b and for j >= count[b]; total float64 [B, N]: T_j, -inf
+ * for j >= count[b].  n_b = 0 gives count = 1, an all-pad row, total = 0.0.
+ * Properties: entry 0 is every row's first unbanned id, so it equals the decode's own caption on a NaN-free decode.  The totals do not increase with j.  The count rows
+ * are pairwise different on the live positions.  The first N' entries of the N-list are the N'-list, bit for bit (float64 addition is monotone, so an entry that is cut
+ * at width N' never has a descendant among the first N').  Where no two float64 totals tie, the list is the N best of all V^n_b captions; with ties, the totals are the N
+ * best totals and every caption strictly above the N-th total is in the list.
+ *   work / work_bytes: a device workspace of at least bofi_vocab_nbest_workspace(rows) bytes, 4-byte aligned.
+ * Two launches (bofi_vocab_pick's candidates launch, then one wavefront per image for the merge), deterministic, no atomics; the only float arithmetic is the float64 add
+ * above.  The result is the rule's for every input: a row whose candidate order the first launch could not settle is streamed again by the image's wavefront.
+ * rows = 0 is BOFI_OK without a launch.  BOFI_ERR_ARG with a message and no launch: what bofi_vocab_constrain refuses (S > 64 among it), N outside 1..8, a NULL seq_n,
+ * total or count, rows > 0 with a NULL or too small workspace. */
+#define BOFI_NBEST_MAX 8
+int64_t bofi_vocab_nbest_workspace(int rows);
+int bofi_vocab_nbest(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int N, int64_t* seq_n,
+                     double* total, int* count, void* work, int64_t work_bytes, void* stream);
+
 /* The bad-ending trim of the reference's decode_sequence (captioning/utils/misc.py:75-82, REMOVE_BAD_ENDINGS) and the flag of its count_bad
  * (captioning/utils/eval_utils.py:32-37), on id rows.  seq int64 [rows, S], 1 <= S <= 64.  The caption of a row is its ids before the first id <= limit
  * (the whole row without one; 'eval' rule: limit = 0), L of them.  trim_bits / count_bits: uint32 [ceil(V / 32)] each, bit (id % 32) of word id / 32 set for

@@ -28,6 +28,8 @@ test.  Both need the words' ids: ``--infos_path`` (a vocabulary), or ``--bad_end
 ``--require_words W1,W2,...`` (every image) or ``--require_words_json FILE`` ({image id: [words]}) (NAIC) places the words in the captions where they cost the least
 log-prob (boficap_amd.eval_utils.required_of; at most 8 per image): the predictions gain ``required`` ([word, position or null] per word) and a line reports
 ``required_rate`` (words placed / words required) and ``required_moved_rate``.
+``--sample_n N --sample_n_method nbest`` (NAIC, N <= 8) takes the N most probable captions of the filling pass -- exact, from one decode -- in place of N random
+draws: ``preds_n`` entries gain ``logp``, the statistics ``nbest_short``.
 """
 import argparse
 import json
@@ -80,6 +82,10 @@ def main():
                     "--input_label_npz; --dump_json then holds {'predictions': [...], 'lang_stats': {...}} instead of the list")
     ap.add_argument("--sample_n", type=int, default=1, help="N > 1: after the greedy pass draw N captions per image (sample_method 'sample') and report Div-1, Div-2, "
                     "mBLEU-1..4 and self-CIDEr over them; --dump_json then holds {'predictions', 'preds_n', 'lang_stats'}")
+    ap.add_argument("--sample_n_method", default="sample", choices=["sample", "nbest"], help="what the N captions of --sample_n are: 'sample' = N random draws; "
+                    "'nbest' (NAIC only, N <= 8) = the N most probable captions of the filling pass, most probable first, exact and from ONE decode -- every entry of "
+                    "preds_n gains 'logp', the statistics nbest_short (images with fewer than N distinct captions); --suppress_UNK / --ban_words apply to the list, "
+                    "not with --decoding_constraint / --block_trigrams / --refine_method mask_predict / --require_words")
     ap.add_argument("--cached_tokens", default="coco-train-idxs", help="document-frequency pickle of the self-CIDEr score (scripts/prepro_ngrams.py): a path, or a "
                     "name resolved as data/<name>.p")
     ap.add_argument("--eval_oracle", type=int, default=0, choices=[0, 1], help="1 (with --language_eval 1 --sample_n N): oracle_<M> and avg_<M>, the best and the "
@@ -115,6 +121,11 @@ def main():
             _eu.require_refusals(vars(args), args.inference_mode, args.sample_n)
         except ValueError as e:
             ap.error("--require_words / --require_words_json: " + str(e))
+    try:
+        from boficap_amd import eval_utils as _eu
+        _eu.sample_n_method_of(vars(args), args.inference_mode, args.sample_n)
+    except ValueError as e:
+        ap.error("--sample_n_method: " + str(e))
     try:                                                         # (before anything is loaded; the words are resolved once the vocabulary is)
         from boficap_amd import eval_utils as _eu
         _eu.constraint_of(vars(args), {"0": "UNK"}, args.inference_mode, args.sample_n)
@@ -349,14 +360,22 @@ def main():
         print("language scores " + " ".join(f"{k} {v:.6f}" for k, v in lang_stats.items()))
     preds_n = None
     if args.sample_n > 1:
+        nb_info = {}
         preds_n, sampled = eval_utils.sample_n_predictions(model, feats, args.sample_n, args.inference_mode, args.batch_size, vocab,
-                                                           surface if args.remove_bad_endings else None)
+                                                           surface if args.remove_bad_endings else None, method=args.sample_n_method,
+                                                           ban_ids=pick.get("ban_ids") if pick else None, refine_rounds=args.refine_rounds, info=nb_info)
+        for e in preds_n:                                        # (an empty row past an image's count has logp -inf: null in the dump)
+            if "logp" in e and not np.isfinite(e["logp"]):
+                e["logp"] = None
         if image_ids is not None:
             for e in preds_n:
                 e["image_id"] = image_ids[e["image_id"]]
         div, _ = eval_utils.diversity_stats(sampled, args.sample_n, {"cached_tokens": args.cached_tokens})
         lang_stats = dict(lang_stats or {}, **div)
         print("diversity scores " + " ".join(f"{k} {v:.6f}" for k, v in div.items()))
+        if "nbest_short" in nb_info:
+            lang_stats["nbest_short"] = nb_info["nbest_short"]
+            print(f"n-best lists: {nb_info['nbest_short']} of {len(results)} images have fewer than {args.sample_n} distinct captions (nbest_short)")
         if args.eval_oracle:
             oracle = lang_ev.evaluate_n(sampled, args.sample_n)
             oracle.pop("per_image")
