@@ -539,6 +539,158 @@ __global__ void __launch_bounds__(NB_IPW * WAVE) vocab_nbest_kernel(NbArgs a, co
     for (int i = lane; i < N * S; i += WAVE) a.seq_n[(size_t)b * N * S + i] = (int64_t)out[i];
 }
 
+// ---- the N-best list under "no adjacent repeated word" (bofi_vocab_nbest_norepeat): the rule couples neighbours, so a width-N list no longer serves; the N best VALID
+// captions come from a list-Viterbi over (position, candidate) states -- per candidate r of row p the N best prefixes that end in it.  K = N + 2 candidates per row suffice
+// (at most two of the ids in front of a caption's id are excluded by its neighbours); include/boficap_hip.h, bofi_vocab_nbest_norepeat, states the rule,
+// tests/test_nbest_no_repeat.py restates it in numpy and holds it to a brute force over every valid caption.
+//   candidates  the K-candidate launch above, unchanged (seq = NULL), as for bofi_vocab_nbest
+//   lists       one workgroup of NR_W = 8 wavefronts per image, wavefront = state r of the current row.  Front part as vocab_nbest_kernel (wavefront 0: ids to LDS, a row whose
+//               order is cut inside its first K entries streamed again; then all threads: the scattered value loads).  A state's list has a stride of NR_W entries
+//               (A[r * 8 + j], -inf where there is no entry), so lane = r' * 8 + j holds pair (r', j) -- lane order is the rule's (r', j) order, the index arithmetic is
+//               shifts and the ranking loop's bounds are compile-time (the lanes j >= N hold -inf and are in front of nothing).  A step: every lane forms the totals
+//               A_{p-1}[k] + (double)x of ALL pairs of its state itself -- the addend is the state's, wave-uniform, so the sums are the same bits in every lane and the
+//               pairs need no LDS array of their own -- and counts those in front of its own (its rank); the predecessor state with the same word is skipped whole.  Lanes
+//               of rank < N write (total, byte back-pointer) into A_p, double-buffered by parity: A_{p-1} is read while A_p is written, ONE barrier per step.
+//   result      wavefront 0 ranks the 64 slots of A_{n_b-1} (lane = r * 8 + j: the rule's order again), lane j < count walks caption j back through the bytes, the
+//               workgroup writes seq_n[b] as one contiguous block.
+// The loop over the positions is uniform over the workgroup (n_b and "degenerate" are the same in every wavefront).  No atomics; the only float arithmetic is the float64
+// add per pair.
+constexpr int NR_MAX = BOFI_NBEST_NR_MAX;      // N at most
+constexpr int NR_W = 8;                        // states per row = wavefronts per image = the stride of a state's list
+static_assert(NR_MAX + 2 <= VP_K, "the candidates launch leaves VP_K ids per row: K = N + 2 of them are the states");
+static_assert(VP_K == NR_W && NR_W * NR_W == WAVE && NR_MAX <= NR_W, "a wavefront's lanes hold every (state, entry) pair of the row before");
+
+__global__ void __launch_bounds__(NR_W * WAVE) vocab_nbest_norepeat_kernel(NbArgs a, int lo, const int* __restrict__ work) {
+    __shared__ double A_[2][WAVE];                              // [parity][r * 8 + j]: the lists' totals, -inf: no entry
+    __shared__ double Tf[NR_W];                                 // the result's totals ...
+    __shared__ uint8_t fl[NR_W];                                // ... and the slot r * 8 + j of A_{n-1} each came from
+    __shared__ int cid[VC_MAX_S * NR_W];                        // c[p][r]; VC_NONE: the row has no such id
+    __shared__ float xv[VC_MAX_S * NR_W];                       // x[p, c[p][r]]; NaN where there is no id
+    __shared__ int out[NR_MAX * VC_MAX_S];                      // the captions, [N][S]
+    __shared__ uint8_t bp[VC_MAX_S * WAVE];                     // [p][r * 8 + j]: the slot of A_{p-1} that entry j of A_p[r] came from
+    const int tid = threadIdx.x, lane = tid % WAVE, r = __builtin_amdgcn_readfirstlane(tid / WAVE), b = blockIdx.x;
+    const int S = a.S, N = a.N, V = a.V, K = N + 2;
+    int n = a.ntok ? a.ntok[b] + a.ntok_bias : S;
+    n = __builtin_amdgcn_readfirstlane(n < 0 ? 0 : (n > S ? S : n));
+    const size_t row0 = (size_t)b * S;
+    const double NINF = -(double)INFINITY;
+    // wavefront 0, lane = position: the row's ids; cutk = the first entry within K from which the order is not known
+    int cutk = -1;
+    if (r == 0 && lane < n) {
+#pragma unroll
+        for (int k = 0; k < NR_W; ++k) {
+            int c = k < K ? work[(row0 + lane) * VP_K + k] : VC_NONE;
+            if (c == VP_CUT) { if (cutk < 0) cutk = k; }
+            else if ((unsigned)c >= (unsigned)V) c = VC_NONE;  // (VC_NONE itself; never an index outside the row)
+            cid[lane * NR_W + k] = cutk >= 0 ? VC_NONE : c;
+        }
+    }
+    __syncthreads();
+    if (r == 0) {
+        for (unsigned long long cuts = __ballot(cutk >= 0); cuts; cuts &= cuts - 1) {      // the rows with a cut order, one at a time: the wavefront streams the row again
+            const int s = __builtin_amdgcn_readfirstlane(__ffsll((long long)cuts) - 1);
+            int k0 = __builtin_amdgcn_readlane(cutk, s);        // (>= 1: the first entry is never VP_CUT)
+            const float* const p = a.x + (row0 + s) * (size_t)a.ldx;
+            const int last = cid[s * NR_W + k0 - 1];
+            if (last == VC_NONE) continue;                      // (cannot be: a cut stands behind a real id)
+            uint64_t floor = vk_key(p[last], last);
+            while (k0 < K) {
+                const Best<VP_L> m = vk_row_behind(p, V, floor, a.ban, lane);
+#pragma unroll
+                for (int k = 0; k < VP_L; ++k)
+                    if (lane == 0 && k0 + k < K) cid[s * NR_W + k0 + k] = vk_id(m.k[k]);
+                if (!m.k[VP_L - 1]) break;                      // the row is exhausted
+                floor = m.k[VP_L - 1];
+                k0 += VP_L;
+            }
+        }
+    }
+    __syncthreads();
+    // thread over the (position, candidate) pairs: the values
+    for (int i = tid; i < n * NR_W; i += NR_W * WAVE) {
+        const int c = cid[i];
+        xv[i] = c != VC_NONE ? a.x[(row0 + i / NR_W) * (size_t)a.ldx + (size_t)c] : NAN;
+    }
+    __syncthreads();
+    const bool degen = __ballot(lane < n && !nb_finite(xv[lane * NR_W])) != 0ull;       // a live row whose first id has no finite value (every wavefront finds the same)
+    const bool run = n > 0 && !degen;                           // (the same in every wavefront of the workgroup)
+    if (run) {
+        // A_0[r] = [0.0 + x[0, c[0][r]]]
+        if (lane < NR_W) A_[0][r * NR_W + lane] = (lane == 0 && r < K && nb_finite(xv[r])) ? 0.0 + (double)xv[r] : NINF;
+        __syncthreads();
+        const int rp = lane / NR_W;                             // this lane's pair (r', j): the predecessor state
+        for (int p = 1; p < n; ++p) {
+            const double* const Ap = A_[(p - 1) & 1];
+            double* const Ac = A_[p & 1];
+            const float v = xv[p * NR_W + r];
+            const int id = cid[p * NR_W + r], idp = cid[(p - 1) * NR_W + rp];
+            const bool state = r < K && nb_finite(v);           // (wave-uniform) c[p][r] is a candidate
+            const bool conf = idp == id && idp >= lo;           // the pair would repeat a word
+            const unsigned long long cm = __ballot(conf);
+            const double dv = (double)v, own = Ap[lane], mine = own + dv;
+            const bool valid = state && !conf && own > NINF;
+            int rank = 0;
+            if (state) {
+                for (int q = 0; q < K; ++q) {                   // the pairs of predecessor state q; a state past K holds no entry
+                    if ((cm >> (q * NR_W)) & 1ull) continue;    // (wave-uniform: c[p-1][q] is this state's word)
+                    double t[NR_MAX];
+#pragma unroll
+                    for (int j = 0; j < NR_MAX; ++j) t[j] = Ap[q * NR_W + j];      // (in flight together; an entry j >= N is -inf, and -inf + dv is in front of nothing)
+#pragma unroll
+                    for (int j = 0; j < NR_MAX; ++j) {
+                        const double s = t[j] + dv;             // the same bits as that pair's own lane computes
+                        rank += (int)(s > mine) | ((int)(s == mine) & (int)(q * NR_W + j < lane));
+                    }
+                }
+            }
+            const int nv = __popcll(__ballot(valid)), cnt = nv < N ? nv : N;
+            if (valid && rank < N) { Ac[r * NR_W + rank] = mine; bp[p * WAVE + r * NR_W + rank] = (uint8_t)lane; }      // (the valid pairs' ranks are 0 .. nv-1, each once)
+            if (lane < NR_W && lane >= cnt) Ac[r * NR_W + lane] = NINF;
+            __syncthreads();
+        }
+    }
+    // the result: wavefront 0 ranks all entries of A_{n-1}, lane = r * 8 + j
+    int cnt = 1;
+    if (r == 0 && run) {
+        const double* const Al = A_[(n - 1) & 1];
+        const double mine = Al[lane];
+        const bool valid = mine > NINF;
+        int rank = 0;
+        for (int j0 = 0; j0 < WAVE; j0 += NB_CHUNK) {
+            double t[NB_CHUNK];
+#pragma unroll
+            for (int j = 0; j < NB_CHUNK; ++j) t[j] = Al[j0 + j];
+#pragma unroll
+            for (int j = 0; j < NB_CHUNK; ++j) rank += (int)(t[j] > mine) | ((int)(t[j] == mine) & (int)(j0 + j < lane));
+        }
+        if (valid && rank < N) { Tf[rank] = mine; fl[rank] = (uint8_t)lane; }
+        const int nv = __popcll(__ballot(valid));
+        cnt = nv < N ? nv : N;                                  // (0: no valid caption over the candidates)
+    }
+    __syncthreads();
+    // lane j < N of wavefront 0: caption j into LDS, walked back along the slots
+    if (r == 0) {
+        if (lane < N) {
+            int e = (run && lane < cnt) ? fl[lane] : 0;
+            for (int p = S - 1; p >= 0; --p) {
+                int id = a.pad_idx;
+                if (p < n && lane < cnt) {
+                    if (degen) { const int c = cid[p * NR_W]; id = c != VC_NONE ? c : a.pad_idx; }
+                    else {
+                        id = cid[p * NR_W + e / NR_W];
+                        if (p > 0) e = bp[p * WAVE + e];
+                    }
+                }
+                out[lane * S + p] = id;
+            }
+            a.total[(size_t)b * N + lane] = lane < cnt ? (degen ? (double)NAN : (n > 0 ? Tf[lane] : 0.0)) : NINF;
+        }
+        if (lane == 0) a.count[b] = cnt;
+    }
+    __syncthreads();
+    for (int i = tid; i < N * S; i += NR_W * WAVE) a.seq_n[(size_t)b * N * S + i] = (int64_t)out[i];
+}
+
 }  // namespace
 
 size_t bofi::vocab_nbest_work_bytes(int rows) { return vocab_pick_work_bytes(rows); }
@@ -578,6 +730,42 @@ extern "C" int bofi_vocab_nbest(const float* x, int ldx, int rows, int V, int S,
     if (const char* why = bofi::vocab_nbest_check(x, ldx, rows, V, S, N, seq_n, total, count, work, work_bytes < 0 ? 0 : (size_t)work_bytes))
         return bofi::fail(BOFI_ERR_ARG, std::string("vocab_nbest: ") + why);
     return bofi::launch_vocab_nbest(x, ldx, rows, V, S, ntok, ntok_bias, pad_idx, ban_bits, N, seq_n, total, count, work, (size_t)work_bytes, (hipStream_t)stream);
+}
+
+const char* bofi::vocab_nbest_norepeat_check(const float* x, int ldx, int rows, int V, int S, int repeat_min_id, int N, const int64_t* seq_n, const double* total,
+                                             const int* count, const void* work, size_t work_bytes) {
+    if (!seq_n || !total || !count) return "non-null seq_n, total and count";
+    if (const char* why = vocab_constrain_check(x, ldx, rows, V, S, 1, repeat_min_id, seq_n)) return why;
+    if (N < 1 || N > NR_MAX) return "N in 1..6 (BOFI_NBEST_NR_MAX)";
+    if (rows > 0 && (!work || work_bytes < vocab_nbest_work_bytes(rows))) return "a workspace of bofi_vocab_nbest_workspace(rows) bytes";
+    return nullptr;
+}
+
+int bofi::launch_vocab_nbest_norepeat(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits,
+                                      int repeat_min_id, int N, int64_t* seq_n, double* total, int* count, void* work, size_t work_bytes, hipStream_t st) {
+    if (vocab_nbest_norepeat_check(x, ldx, rows, V, S, repeat_min_id, N, seq_n, total, count, work, work_bytes)) return BOFI_ERR_ARG;
+    if (rows == 0) return BOFI_OK;
+    VcArgs a{};
+    a.x = x; a.ldx = ldx; a.V = V; a.S = S; a.ntok = ntok; a.ntok_bias = ntok_bias; a.pad_idx = pad_idx; a.ban = ban_bits; a.ban_words = (V + 31) / 32;
+    a.ban_lds = a.ban_words <= VC_BAN_LDS_WORDS;                // (seq stays NULL: the candidates launch writes the workspace only)
+    const int B = rows / S;
+    if (ban_bits) hipLaunchKernelGGL(vocab_candidates_k_kernel<true>, dim3(rows), dim3(VC_NT), a.ban_lds ? (size_t)a.ban_words * 4 : 0, st, a, (int*)work);
+    else hipLaunchKernelGGL(vocab_candidates_k_kernel<false>, dim3(rows), dim3(VC_NT), 0, st, a, (int*)work);
+    BOFI_CHECK_LAUNCH();
+    NbArgs nb{};
+    nb.x = x; nb.ldx = ldx; nb.V = V; nb.S = S; nb.B = B; nb.ntok = ntok; nb.ntok_bias = ntok_bias; nb.pad_idx = pad_idx; nb.ban = ban_bits; nb.N = N;
+    nb.seq_n = seq_n; nb.total = total; nb.count = count;
+    hipLaunchKernelGGL(vocab_nbest_norepeat_kernel, dim3(B), dim3(NR_W * WAVE), 0, st, nb, repeat_min_id, (const int*)work);      // one workgroup per image
+    BOFI_CHECK_LAUNCH();
+    return BOFI_OK;
+}
+
+extern "C" int bofi_vocab_nbest_norepeat(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits,
+                                         int repeat_min_id, int N, int64_t* seq_n, double* total, int* count, void* work, int64_t work_bytes, void* stream) {
+    if (const char* why = bofi::vocab_nbest_norepeat_check(x, ldx, rows, V, S, repeat_min_id, N, seq_n, total, count, work, work_bytes < 0 ? 0 : (size_t)work_bytes))
+        return bofi::fail(BOFI_ERR_ARG, std::string("vocab_nbest_norepeat: ") + why);
+    return bofi::launch_vocab_nbest_norepeat(x, ldx, rows, V, S, ntok, ntok_bias, pad_idx, ban_bits, repeat_min_id, N, seq_n, total, count, work, (size_t)work_bytes,
+                                             (hipStream_t)stream);
 }
 
 size_t bofi::vocab_pick_work_bytes(int rows) { return (size_t)(rows > 0 ? rows : 0) * VP_K * sizeof(int); }

@@ -209,7 +209,7 @@ class BofiEngine:
                     refine_rounds: int = 0, out: Optional[dict] = None, q1_group: int = 0, iter_cap: int = 0, phases: str = "", row_stats: bool = False,
                     ids_only: bool = False, refine_method: str = "feed_back", attn_topk: int = 0, attn_maps: bool = False, attn_heads: bool = False,
                     attn_layer: int = -1, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7, block_trigrams: bool = False, require_ids=None,
-                    nbest: Optional[int] = None) -> dict:
+                    nbest: Optional[int] = None, nbest_no_repeat: bool = False) -> dict:
         """Greedy NAIC bound+fill decode.  Returns a dict of device tensors: seq [B,S] int64,
         seq_logprob [B,S,V] float32 (or None), phrase_num [B] int32, phrase_length [B,S] int32,
         phrase_syn [B,S] int64, bound_iters [1] int32, memory [B,R,d] float32 (or None).
@@ -262,7 +262,11 @@ class BofiEngine:
         the count), ``out['nbest_count']`` int32 [B].  Entry 0 is the call's own ``seq`` on a NaN-free decode.  With feed-back rounds the list is the final pass's.
         Refused before anything is enqueued: ``ids_only`` or an ids-only fork (there are no rows), ``refine_method='mask_predict'`` (kept positions do not hold their
         row's first id), ``no_repeat`` / ``block_trigrams`` (a rule that couples neighbours needs per-last-id state: a width-N list is no longer exact) and
-        ``require_ids``.  None or 0: nothing is launched and no key is added."""
+        ``require_ids``.  None or 0: nothing is launched and no key is added.
+        ``nbest_no_repeat`` (with ``nbest`` = N in 1..6; a BofiHipError without it): the list is of the captions with NO ADJACENT REPEATED WORD -- an id >=
+        ``repeat_min_id`` never follows itself -- exactly: bofi_vocab_nbest_norepeat, a list-Viterbi over each row's N + 2 best ids, in place of bofi_vocab_nbest, under the
+        call's ``ban_ids`` and ``repeat_min_id``; same placement, same keys.  ``nbest_count`` may then be 0, and entry 0 need not be ``seq``: the decode's own outputs stay
+        the plain decode's (``no_repeat=True``, the constrained decode, stays refused with the list)."""
         mp = self._refine_flag(refine_method, refine_rounds, raw_logits)
         ban = self._pick_ban(ban_ids, block_trigrams)
         pick_on = ban is not None or bool(no_repeat) or bool(block_trigrams)
@@ -270,6 +274,7 @@ class BofiEngine:
         if req is not None:
             self._require_refusals(ids_only, mp, block_trigrams)
         nbest = self._nbest_width(nbest)
+        nb_min = self._nbest_no_repeat(nbest, nbest_no_repeat, repeat_min_id)
         if nbest:
             self._nbest_refusals(ids_only, mp, no_repeat, block_trigrams, req is not None,
                                  want_logprob or (out is not None and out.get("seq_logprob") is not None))
@@ -339,7 +344,7 @@ class BofiEngine:
         elif not phases or "f" in phases:
             out["nbest_seq"], out["nbest_logp"], out["nbest_count"] = self._nbest_list(
                 nbest, B, out["seq_logprob"], torch.sum(out["phrase_length"], 1, dtype=torch.int32), 0, ban, out.get("nbest_seq"), out.get("nbest_logp"),
-                out.get("nbest_count"))
+                out.get("nbest_count"), repeat_min=nb_min)
         return out
 
     @staticmethod
@@ -352,6 +357,20 @@ class BofiEngine:
             raise hip.BofiHipError(f"nbest: N must lie in 1..{hip.NBEST_MAX} (0 / None: off), got {n}")
         return n
 
+    @staticmethod
+    def _nbest_no_repeat(nbest: int, nbest_no_repeat, repeat_min_id: int = 7) -> Optional[int]:
+        """``nbest_no_repeat`` of a decode whose list width is ``nbest`` (0: off): None when the option is off, else the ``repeat_min_id`` the list is made under.
+        BofiHipError without ``nbest``, with N > 6 or a negative ``repeat_min_id``."""
+        if not nbest_no_repeat:
+            return None
+        if not nbest:
+            raise hip.BofiHipError("nbest_no_repeat: needs nbest = N (it narrows the N-best list; no_repeat=True is the constrained decode)")
+        if nbest > hip.NBEST_NR_MAX:
+            raise hip.BofiHipError(f"nbest_no_repeat: N must lie in 1..{hip.NBEST_NR_MAX} (the list needs N + 2 of a row's 8 candidate ids), got {nbest}")
+        if int(repeat_min_id) < 0:
+            raise hip.BofiHipError(f"nbest_no_repeat: repeat_min_id must be >= 0, got {repeat_min_id}")
+        return int(repeat_min_id)
+
     def _nbest_refusals(self, ids_only: bool, mp: int, no_repeat: bool, block_trigrams: bool, required: bool, own_rows: bool) -> None:
         if ids_only:
             raise hip.BofiHipError("nbest: not with ids_only (the decode leaves no rows to list from)")
@@ -359,14 +378,15 @@ class BofiEngine:
             raise hip.BofiHipError("nbest: not with refine_method='mask_predict' (kept positions do not hold their row's first id: entry 0 would not be the caption)")
         if no_repeat or block_trigrams:
             raise hip.BofiHipError("nbest: not with no_repeat / block_trigrams (the N best under a rule that couples neighbours need per-last-id state: "
-                                   "a width-N list is no longer exact)")
+                                   "a width-N list is no longer exact); nbest_no_repeat=True lists the repeat-free captions beside the plain decode")
         if required:
             raise hip.BofiHipError("nbest: not with require_ids (the list is of unforced captions)")
         if not own_rows and not self._lib.bofi_engine_logprob(self._h):
             raise hip.BofiHipError("nbest: this engine keeps no log-prob workspace (an ids-only fork): there are no rows to list from")
 
-    def _nbest_list(self, N: int, B: int, lp, ntok, ntok_bias, ban, seq_n=None, total=None, count=None):
-        """Enqueue bofi_vocab_nbest on the current stream behind a decode: ``lp`` the decode's log-prob (or logit) tensor or None for the engine's own workspace.
+    def _nbest_list(self, N: int, B: int, lp, ntok, ntok_bias, ban, seq_n=None, total=None, count=None, repeat_min: Optional[int] = None):
+        """Enqueue bofi_vocab_nbest -- with ``repeat_min`` (``_nbest_no_repeat``) bofi_vocab_nbest_norepeat under that ``repeat_min_id`` -- on the current stream behind a
+        decode: ``lp`` the decode's log-prob (or logit) tensor or None for the engine's own workspace.
         Returns (seq_n int64 [B, N, S], total float64 [B, N], count int32 [B]); the buffers given are reused when they fit."""
         S, V, dev = self.cfg.seq_length, self.cfg.tgt_vocab, ntok.device
         if seq_n is None or tuple(seq_n.shape) != (B, N, S):
@@ -382,6 +402,11 @@ class BofiEngine:
         src = hip.ptr(lp) if lp is not None else self._lib.bofi_engine_logprob(self._h)
         if not src:
             raise hip.BofiHipError("nbest: this engine keeps no log-prob workspace (an ids-only fork)")
+        if repeat_min is not None:
+            hip.check(self._lib.bofi_vocab_nbest_norepeat(src, V, B * S, V, S, hip.ptr(ntok), int(ntok_bias), int(self.cfg.pad_idx), hip.ptr(ban), int(repeat_min), N,
+                                                          hip.ptr(seq_n), hip.ptr(total), hip.ptr(count), hip.ptr(work), work.numel() * 4, hip.stream_ptr()),
+                      "bofi_vocab_nbest_norepeat")
+            return seq_n, total, count
         hip.check(self._lib.bofi_vocab_nbest(src, V, B * S, V, S, hip.ptr(ntok), int(ntok_bias), int(self.cfg.pad_idx), hip.ptr(ban), N, hip.ptr(seq_n), hip.ptr(total),
                                              hip.ptr(count), hip.ptr(work), work.numel() * 4, hip.stream_ptr()), "bofi_vocab_nbest")
         return seq_n, total, count
@@ -661,14 +686,15 @@ class BofiEngine:
     def fill_naic(self, ext_syn: torch.Tensor, last: torch.Tensor, R: int, att_len: Optional[torch.Tensor] = None, *, strict_q1: bool = True,
                   raw_logits: bool = False, refine_rounds: int = 0, refine_method: str = "feed_back", attn_topk: int = 0, attn_maps: bool = False,
                   attn_heads: bool = False, attn_layer: int = -1, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7, block_trigrams: bool = False,
-                  require_ids=None, nbest: Optional[int] = None):
+                  require_ids=None, nbest: Optional[int] = None, nbest_no_repeat: bool = False):
         """The filling pass alone on a given slot layout (``ext_syn`` int32 [B, S+2], ``last`` int32 [B]) and the memory of the
         preceding ``encode``: (seq int64 [B, S], seq_logprob float32 [B, S, V]); with ``refine_method='mask_predict'`` (as ``decode_naic``) a third
         element, refine_round int32 [B, S].  With ``attn_topk`` / ``attn_maps`` / ``attn_heads`` (as ``decode_naic``) a last element, a dict of the attention tensors
         ('attn', 'attn_heads', 'attn_top', 'attn_top_w': those asked for).  ``ban_ids`` / ``no_repeat`` / ``repeat_min_id`` / ``block_trigrams`` as ``decode_naic``: that dict (the last element)
         then carries 'constrained', int32 [B].  ``require_ids`` as ``decode_naic`` (bofi_vocab_require behind the call, on the last pass; the same refusals): that dict
         then carries 'required_pos' int32 [B, K] and 'required_moved' int32 [B].  ``nbest`` as ``decode_naic`` (bofi_vocab_nbest behind the call, on the last pass; the
-        same refusals): that dict then carries 'nbest_seq' int64 [B, N, S], 'nbest_logp' float64 [B, N] and 'nbest_count' int32 [B]."""
+        same refusals): that dict then carries 'nbest_seq' int64 [B, N, S], 'nbest_logp' float64 [B, N] and 'nbest_count' int32 [B]; ``nbest_no_repeat`` as
+        ``decode_naic`` (bofi_vocab_nbest_norepeat in its place, N <= 6)."""
         mp = self._refine_flag(refine_method, refine_rounds, raw_logits)
         ban = self._pick_ban(ban_ids, block_trigrams)
         pick_on = ban is not None or bool(no_repeat) or bool(block_trigrams)
@@ -678,6 +704,7 @@ class BofiEngine:
         if req is not None:
             self._require_refusals(False, mp, block_trigrams)
         nbest = self._nbest_width(nbest)
+        nb_min = self._nbest_no_repeat(nbest, nbest_no_repeat, repeat_min_id)
         if nbest:
             self._nbest_refusals(False, mp, no_repeat, block_trigrams, req is not None, True)
         B = ext_syn.size(0)
@@ -700,7 +727,7 @@ class BofiEngine:
         if req is not None:
             attn["required_pos"], attn["required_moved"] = self._require_place(req, seq, lp, last.contiguous(), -1, ban, no_repeat, repeat_min_id, None)
         if nbest:
-            attn["nbest_seq"], attn["nbest_logp"], attn["nbest_count"] = self._nbest_list(nbest, B, lp, last.contiguous(), -1, ban)
+            attn["nbest_seq"], attn["nbest_logp"], attn["nbest_count"] = self._nbest_list(nbest, B, lp, last.contiguous(), -1, ban, repeat_min=nb_min)
         res = (seq, lp, rnd) if mp else (seq, lp)
         return res + (attn,) if attn else res
 

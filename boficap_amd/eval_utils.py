@@ -35,6 +35,9 @@ references alone (integer rows or id strings; no loss then), or None.  ``eval_kw
                      entry of ``preds_n`` carries 'logp' (float64 sum of its positions' log-probs; -inf for the empty rows of an image that has fewer than N
                      distinct captions); the number of such images is ``lang_stats['nbest_short']``.  The rows feed the diversity statistics, the oracle scores
                      and the surface statistics exactly as sampled rows do
+    nbest_no_repeat  1, with ``sample_n_method`` 'nbest' and ``sample_n`` <= 6 (a ValueError otherwise): the rows are the ``sample_n`` most probable captions with no
+                     adjacent repeated word (ids >= 7), exactly -- ``opt['nbest_no_repeat']``, bofi_vocab_nbest_norepeat.  The greedy predictions stay the plain decode's;
+                     ``decoding_constraint`` with the list stays refused.  Keys as above
     cached_tokens    a df pickle of scripts/prepro_ngrams.py: a path, or a name resolved as data/<name>.p (default 'coco-train-idxs')
     eval_oracle      1, with ``language_eval`` 1 and ``sample_n`` > 1 (nothing changes otherwise): every sampled caption is scored against its image's
                      references and ``lang_stats`` gains 'oracle_<M>' (the best of an image's N, averaged over the images) and 'avg_<M>' (their mean)
@@ -162,14 +165,29 @@ def sample_n_method_of(eval_kwargs, mode: str = "NAIC", sample_n: int = 1) -> st
     return method
 
 
+def nbest_no_repeat_of(eval_kwargs, sample_n: int = 1) -> bool:
+    """``eval_kwargs['nbest_no_repeat']`` (0, the default, or 1): the ``sample_n`` captions of ``sample_n_method='nbest'`` are the most probable ones with NO ADJACENT
+    REPEATED WORD (bofi_vocab_nbest_norepeat, exact).  ValueError naming the key without ``sample_n_method='nbest'`` or with more than 6 captions per image.  (The
+    constrained DECODE, ``decoding_constraint``, stays refused with the list: ``sample_n_method_of``.)"""
+    if not int(eval_kwargs.get("nbest_no_repeat", 0) or 0):
+        return False
+    from .hip import NBEST_NR_MAX
+    if (eval_kwargs.get("sample_n_method", "sample") or "sample") != "nbest":
+        raise ValueError("nbest_no_repeat narrows the N-best list: it needs sample_n_method 'nbest'")
+    if int(sample_n) > NBEST_NR_MAX:
+        raise ValueError(f"nbest_no_repeat: at most {NBEST_NR_MAX} captions per image, got sample_n = {int(sample_n)}")
+    return True
+
+
 def sample_n_predictions(model, feats, sample_n: int, mode: str = "NAIC", batch_size: int = 64, vocab=None, surface=None, method: str = "sample", ban_ids=None,
-                         refine_rounds: int = 0, info=None):
+                         refine_rounds: int = 0, info=None, nbest_no_repeat: bool = False):
     """eval_split_n (eval_utils.py:670-700): ``sample_n`` captions per image of ``feats`` through ``mode='sample'`` -- drawn (``method='sample'``, the reference's
     ``sample_n_method='sample'``) or the ``sample_n`` most probable captions of the NAIC filling pass, most probable first (``method='nbest'``: ``opt['nbest']``, under
     ``ban_ids`` and after ``refine_rounds`` feed-back rounds; rows past an image's count are the empty captions the kernel wrote).  Returns (entries {'image_id',
     'seq'[, 'caption'][, 'logp']} in row order, the ids [N * sample_n, S] on the device); an entry's 'seq' holds the ids before the first id <= 0 (decode_sequence);
     'logp' (``'nbest'`` only) is the caption's float64 total, -inf on an empty row past the count.  ``info``: a dict that receives 'nbest_short', the number of images
-    with fewer than ``sample_n`` captions.  ``surface``: a ``CaptionSurface`` -- the ids are trimmed of their bad endings on the device first, and both results are
+    with fewer than ``sample_n`` captions.  ``nbest_no_repeat`` (``'nbest'`` only, ``sample_n`` <= 6): the list is of the captions with no adjacent repeated word
+    (``opt['nbest_no_repeat']``); an image may then have no caption at all (every row empty, every 'logp' -inf).  ``surface``: a ``CaptionSurface`` -- the ids are trimmed of their bad endings on the device first, and both results are
     the trimmed ones."""
     if method not in SAMPLE_N_METHODS:
         raise ValueError(f"sample_n_method {method!r}: 'sample' and 'nbest' are served")
@@ -190,6 +208,8 @@ def sample_n_predictions(model, feats, sample_n: int, mode: str = "NAIC", batch_
             fc = torch.zeros(att.size(0), 0, device="cuda")
             if method == "nbest":
                 opt = {"train_mode": mode, "sample_method": "greedy", "sample_n": 1, "nbest": n, "refine_rounds": int(refine_rounds), "ban_ids": list(ban_ids or ())}
+                if nbest_no_repeat:
+                    opt["nbest_no_repeat"] = 1
                 model(fc, att, masks, opt=opt, mode="sample")
                 nb = model.last_nbest
                 rows.append(nb["seq"].reshape(-1, nb["seq"].size(-1)))
@@ -364,6 +384,7 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
     if mode != "NAIC" and (refine["refine_rounds"] or refine["refine_method"] != "feed_back"):
         raise ValueError("refine_rounds / refine_method refine the non-autoregressive filling pass: inference_mode 'NAIC' only")
     n_method = sample_n_method_of(kw, mode, sample_n)
+    nb_no_repeat = nbest_no_repeat_of(kw, sample_n)
     attn_topk = int(kw.get("attn_topk", 0))
     if attn_topk and mode != "NAIC":
         raise ValueError("attn_topk reads the non-autoregressive filling pass's cross-attention: inference_mode 'NAIC' only")
@@ -461,7 +482,8 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
             if n_method == "nbest":                              # the sample_n most probable captions of the filling pass in place of sample_n draws
                 info = {}
                 kw["preds_n"], sampled = sample_n_predictions(model, feats, sample_n, mode, batch_size, vocab, surface if remove else None, method="nbest",
-                                                              ban_ids=pick.get("ban_ids"), refine_rounds=refine["refine_rounds"], info=info)
+                                                              ban_ids=pick.get("ban_ids"), refine_rounds=refine["refine_rounds"], info=info,
+                                                              nbest_no_repeat=nb_no_repeat)
             else:
                 kw["preds_n"], sampled = sample_n_predictions(model, feats, sample_n, mode, batch_size, vocab, surface if remove else None)
             div, kw["diversity_per_image"] = diversity_stats(sampled, sample_n, kw)

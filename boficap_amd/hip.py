@@ -25,6 +25,7 @@ FORK_IDS_ONLY = 1
 ABI_VERSION = 5
 REQUIRE_MAX = 8                     # BOFI_REQUIRE_MAX: required words per image (bofi_vocab_require)
 NBEST_MAX = 8                       # BOFI_NBEST_MAX: captions per image of bofi_vocab_nbest
+NBEST_NR_MAX = 6                    # BOFI_NBEST_NR_MAX: ... of bofi_vocab_nbest_norepeat (its N + 2 candidates per row are the candidates launch's 8)
 
 
 class BofiHipError(RuntimeError):
@@ -142,6 +143,7 @@ SIGNATURES = {
     "bofi_vocab_require": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "bofi_vocab_nbest_workspace": (_I64, [_I]),
     "bofi_vocab_nbest": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _I64, _P]),
+    "bofi_vocab_nbest_norepeat": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I64, _P]),
     "bofi_caption_trim": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     "bofi_sentence_lookup": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
 }
@@ -451,6 +453,39 @@ def vocab_nbest(x, V, S, N, *, ntok=None, ntok_bias=0, pad_idx=0, ban=None, seq_
             raise BofiHipError(f"vocab_nbest: {name} must be a contiguous {dt} device tensor" + ("" if n is None else f" of {n} elements"))
     check(lib().bofi_vocab_nbest(ptr(x), x.stride(0), rows, int(V), int(S), ptr(ntok), int(ntok_bias), int(pad_idx), ptr(ban), N, ptr(seq_n), ptr(total), ptr(count),
                                  ptr(work), work.numel() * 4, stream_ptr()), "bofi_vocab_nbest")
+    return seq_n, total, count
+
+
+def vocab_nbest_norepeat(x, V, S, N, *, ntok=None, ntok_bias=0, pad_idx=0, ban=None, repeat_min_id=7, seq_n=None, total=None, count=None, work=None):
+    """``bofi_vocab_nbest_norepeat`` on torch tensors: the N most probable captions with no adjacent repeated word (an id >= ``repeat_min_id`` never follows itself) of the
+    rows x float32 [rows, >= V]; the arguments, the results ``(seq_n int64 [B, N, S], total float64 [B, N], count int32 [B])`` and the workspace are ``vocab_nbest``'s,
+    N lies in 1..6, and ``count`` may be 0.  Two launches on the current stream, no synchronisation."""
+    import torch
+    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or not x.is_cuda:
+        raise BofiHipError("vocab_nbest_norepeat: x must be a 2-d float32 device tensor with unit column stride")
+    rows = x.size(0)
+    if x.size(1) < V or S < 1 or rows % S:
+        raise BofiHipError("vocab_nbest_norepeat: x needs V columns and a multiple of S rows")
+    N = int(N)
+    if not 1 <= N <= NBEST_NR_MAX:
+        raise BofiHipError(f"vocab_nbest_norepeat: N must lie in 1..{NBEST_NR_MAX}, got {N}")
+    B = rows // S
+    if seq_n is None:
+        seq_n = torch.empty(B, N, S, dtype=torch.int64, device=x.device)
+    if total is None:
+        total = torch.empty(B, N, dtype=torch.float64, device=x.device)
+    if count is None:
+        count = torch.empty(B, dtype=torch.int32, device=x.device)
+    if work is None:
+        work = torch.empty(max(1, lib().bofi_vocab_nbest_workspace(rows) // 4), dtype=torch.int32, device=x.device)
+    for name, t, dt, n in (("seq_n", seq_n, torch.int64, B * N * S), ("total", total, torch.float64, B * N), ("count", count, torch.int32, B),
+                           ("ntok", ntok, torch.int32, B), ("ban", ban, torch.int32, (V + 31) // 32), ("work", work, torch.int32, None)):
+        if t is None and name in ("ntok", "ban"):
+            continue
+        if t is None or t.dtype != dt or (n is not None and t.numel() != n) or not t.is_cuda or not t.is_contiguous():
+            raise BofiHipError(f"vocab_nbest_norepeat: {name} must be a contiguous {dt} device tensor" + ("" if n is None else f" of {n} elements"))
+    check(lib().bofi_vocab_nbest_norepeat(ptr(x), x.stride(0), rows, int(V), int(S), ptr(ntok), int(ntok_bias), int(pad_idx), ptr(ban), int(repeat_min_id), N,
+                                          ptr(seq_n), ptr(total), ptr(count), ptr(work), work.numel() * 4, stream_ptr()), "bofi_vocab_nbest_norepeat")
     return seq_n, total, count
 
 

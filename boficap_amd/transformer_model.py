@@ -367,6 +367,13 @@ class TransformerModel(nn.Module):
         # 6-tuple stays, the lists land in self.last_nbest ({'seq' int64 [B, N, S], 'logp' float64 [B, N], 'count' int32 [B]}, per image -- not repeated under sample_n;
         # None without the option).  The refusals are the engine's, raised here before anything is enqueued
         nbest = int(opt.get("nbest", 0) or 0)
+        # opt['nbest_no_repeat'] (with opt['nbest'] = N in 1..6): the list is of the captions with no adjacent repeated word (decode_naic(nbest_no_repeat=True)); the
+        # caption this call returns stays the plain decode's
+        nbest_nr = bool(int(opt.get("nbest_no_repeat", 0) or 0))
+        if nbest_nr and not nbest:
+            raise hip.BofiHipError("nbest_no_repeat: needs opt['nbest'] = N (it narrows the N-best list)")
+        if nbest_nr and nbest > hip.NBEST_NR_MAX:
+            raise hip.BofiHipError(f"nbest_no_repeat: N must lie in 1..{hip.NBEST_NR_MAX}, got nbest = {nbest}")
         self.last_nbest = None
         if nbest:
             if not 1 <= nbest <= hip.NBEST_MAX:
@@ -384,6 +391,8 @@ class TransformerModel(nn.Module):
             if "require_ids" in rkw:
                 raise hip.BofiHipError("nbest: not with require_ids (the list is of unforced captions)")
             rkw.update(nbest=nbest)
+            if nbest_nr:
+                rkw.update(nbest_no_repeat=True)
         eng = self.engine()
         torch.cuda.synchronize()                                  # the reference does (AttModel.py:337)
         start = time.time()

@@ -877,6 +877,39 @@ int64_t bofi_vocab_nbest_workspace(int rows);
 int bofi_vocab_nbest(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int N, int64_t* seq_n,
                      double* total, int* count, void* work, int64_t work_bytes, void* stream);
 
+/* The N most probable captions of a filling pass that have NO ADJACENT REPEATED WORD, exactly.  The rule couples neighbours, so the width-N merge above no longer serves:
+ * the list comes from a list-Viterbi over (position, candidate) states with K = N + 2 candidates per row.  A stand-alone call behind the decode: no field of
+ * bofi_call_opts_t, no engine state, the ABI version is unchanged.
+ *   x, ldx, rows, V, S, ntok, ntok_bias, pad_idx, ban_bits, n_b and the order of ids: bofi_vocab_constrain's; x is read only.  repeat_min_id: its too.
+ *   1 <= N <= BOFI_NBEST_NR_MAX.
+ * Valid caption: w[0 .. n_b-1] with no banned id and no p >= 1 with w[p] == w[p-1] and w[p-1] >= repeat_min_id -- exactly the eligibility test of bofi_vocab_constrain's
+ * scan with no_repeat = 1.
+ * Candidates: c[p][0 .. K-1], K = N + 2, are the first K unbanned ids of row p in that order; a row with fewer unbanned ids has fewer candidates.  Entry r >= 1 is not a
+ * candidate when x[p, c[p][r]] is NaN or +-inf; the remaining entries keep their index r (as bofi_vocab_nbest).  N + 2 suffice: a caption that uses at p an id with r
+ * better ids in front of it has at most two of those excluded by its neighbours w[p-1] and w[p+1]; each of the others gives a different valid caption whose left-to-right
+ * float64 total is not smaller (float64 addition is monotone), so with r >= N + 2 there are N captions at least as good.  N + 1 are not enough.
+ * Degenerate image, as in bofi_vocab_nbest: a live row's x[p, c[p][0]] is not finite (or the row has no unbanned id at all: pad_idx stands for c[p][0]).  It gets
+ * count = 1, caption 0 is c[p][0] at every live p, total[b, 0] = NaN.
+ * Recurrence: A_p[r] is a list of at most N (total, prefix) entries per candidate r of row p.  A_0[r] = [(0.0 + (double)x[0, c[0][r]])].  For p >= 1, A_p[r] is built from
+ * all pairs (r', j), r' a candidate of row p-1 for which NOT (c[p-1][r'] == c[p][r] and c[p-1][r'] >= repeat_min_id), j an entry of A_{p-1}[r'], with
+ * total = T_{r',j} + (double)x[p, c[p][r]] -- one float64 add per pair.  The pairs are ordered by total descending, then r' ascending, then j ascending; the first N are
+ * kept.  The result list is all (r, j) of A_{n_b-1} in the same order (total, r, j), its first N.
+ * Outputs, of bofi_vocab_nbest's shapes: count int32 [B]; seq_n int64 [B, N, S]: pad_idx for p >= n_b and for j >= count[b]; total float64 [B, N]: -inf for
+ * j >= count[b].  n_b = 0 gives count = 1, an all-pad row, total = 0.0.  count may be 0 -- two adjacent rows with one candidate each, the same word: then every row is
+ * pad_idx and every total -inf.
+ * Properties: every listed caption is valid, and the count rows are pairwise different on the live positions.  The totals do not increase with j.  Each total is the
+ * left-to-right float64 sum of its own x values.  Where no two float64 totals tie, the list is the N best of all valid captions with a finite total; with ties, the totals
+ * are the N best totals and every valid caption strictly above the N-th total is in the list.  Entry 0 need not be the decode's caption, nor the scan's: its total is >=
+ * both whenever theirs is valid and finite.
+ *   work / work_bytes: a device workspace of at least bofi_vocab_nbest_workspace(rows) bytes, 4-byte aligned.
+ * Two launches (bofi_vocab_pick's candidates launch, then one workgroup of eight wavefronts per image, a wavefront per candidate state), deterministic, no atomics; the only
+ * float arithmetic is the float64 add above.  The result is the rule's for every input: a row whose candidate order the first launch could not settle is streamed again.
+ * rows = 0 is BOFI_OK without a launch.  BOFI_ERR_ARG with a message "vocab_nbest_norepeat: ..." and no launch: what bofi_vocab_nbest refuses (a NULL or too small
+ * workspace with rows > 0 among it), N outside 1..6, repeat_min_id < 0. */
+#define BOFI_NBEST_NR_MAX 6
+int bofi_vocab_nbest_norepeat(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int repeat_min_id,
+                              int N, int64_t* seq_n, double* total, int* count, void* work, int64_t work_bytes, void* stream);
+
 /* The bad-ending trim of the reference's decode_sequence (captioning/utils/misc.py:75-82, REMOVE_BAD_ENDINGS) and the flag of its count_bad
  * (captioning/utils/eval_utils.py:32-37), on id rows.  seq int64 [rows, S], 1 <= S <= 64.  The caption of a row is its ids before the first id <= limit
  * (the whole row without one; 'eval' rule: limit = 0), L of them.  trim_bits / count_bits: uint32 [ceil(V / 32)] each, bit (id % 32) of word id / 32 set for

@@ -30,6 +30,8 @@ log-prob (boficap_amd.eval_utils.required_of; at most 8 per image): the predicti
 ``required_rate`` (words placed / words required) and ``required_moved_rate``.
 ``--sample_n N --sample_n_method nbest`` (NAIC, N <= 8) takes the N most probable captions of the filling pass -- exact, from one decode -- in place of N random
 draws: ``preds_n`` entries gain ``logp``, the statistics ``nbest_short``.
+``--nbest_no_repeat 1`` (with ``--sample_n_method nbest``, N <= 6) makes that list the N most probable captions with no adjacent repeated word -- exact too (a
+list-Viterbi over each row's N + 2 best ids); the greedy predictions stay the plain decode's.  An argument error without ``--sample_n_method nbest`` or with N > 6.
 """
 import argparse
 import json
@@ -86,6 +88,8 @@ def main():
                     "'nbest' (NAIC only, N <= 8) = the N most probable captions of the filling pass, most probable first, exact and from ONE decode -- every entry of "
                     "preds_n gains 'logp', the statistics nbest_short (images with fewer than N distinct captions); --suppress_UNK / --ban_words apply to the list, "
                     "not with --decoding_constraint / --block_trigrams / --refine_method mask_predict / --require_words")
+    ap.add_argument("--nbest_no_repeat", type=int, default=0, choices=[0, 1], help="1 (with --sample_n_method nbest, --sample_n <= 6): the list is of the captions "
+                    "with no adjacent repeated word (ids >= 7), the N most probable of them, exactly; the greedy predictions stay the plain decode's")
     ap.add_argument("--cached_tokens", default="coco-train-idxs", help="document-frequency pickle of the self-CIDEr score (scripts/prepro_ngrams.py): a path, or a "
                     "name resolved as data/<name>.p")
     ap.add_argument("--eval_oracle", type=int, default=0, choices=[0, 1], help="1 (with --language_eval 1 --sample_n N): oracle_<M> and avg_<M>, the best and the "
@@ -126,6 +130,10 @@ def main():
         _eu.sample_n_method_of(vars(args), args.inference_mode, args.sample_n)
     except ValueError as e:
         ap.error("--sample_n_method: " + str(e))
+    try:
+        nbest_no_repeat = _eu.nbest_no_repeat_of(vars(args), args.sample_n)
+    except ValueError as e:
+        ap.error("--nbest_no_repeat: " + str(e))
     try:                                                         # (before anything is loaded; the words are resolved once the vocabulary is)
         from boficap_amd import eval_utils as _eu
         _eu.constraint_of(vars(args), {"0": "UNK"}, args.inference_mode, args.sample_n)
@@ -363,7 +371,8 @@ def main():
         nb_info = {}
         preds_n, sampled = eval_utils.sample_n_predictions(model, feats, args.sample_n, args.inference_mode, args.batch_size, vocab,
                                                            surface if args.remove_bad_endings else None, method=args.sample_n_method,
-                                                           ban_ids=pick.get("ban_ids") if pick else None, refine_rounds=args.refine_rounds, info=nb_info)
+                                                           ban_ids=pick.get("ban_ids") if pick else None, refine_rounds=args.refine_rounds, info=nb_info,
+                                                           nbest_no_repeat=nbest_no_repeat)
         for e in preds_n:                                        # (an empty row past an image's count has logp -inf: null in the dump)
             if "logp" in e and not np.isfinite(e["logp"]):
                 e["logp"] = None
