@@ -96,6 +96,14 @@ __device__ __forceinline__ float xor32_max(float v) {
 __device__ __forceinline__ float wave_sum(float v) { return xor32_sum(xor16_sum(row16_sum(v))); }
 __device__ __forceinline__ float wave_max(float v) { return xor32_max(xor16_max(row16_max(v))); }
 
+// the live positions of image b of a [B, S] batch: n_b = clamp(ntok[b] + ntok_bias, 0, S); every position without ntok
+__device__ __forceinline__ int live_count(const int* ntok, int ntok_bias, int b, int S) {
+    const int n = ntok ? ntok[b] + ntok_bias : S;
+    return n < 0 ? 0 : (n > S ? S : n);
+}
+// neither NaN nor an infinity (integer test: no float compare)
+__device__ __forceinline__ bool f32_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
 // 64-bit counter hash (splitmix64 finaliser), upper half: the uniform numbers of the sampling kernels
 __device__ __forceinline__ uint32_t hash64_hi(uint64_t seed, uint64_t i) {
     uint64_t z = seed + (i + 1) * 0x9E3779B97F4A7C15ull;

@@ -49,7 +49,20 @@ __device__ __forceinline__ bool vc_before(float v1, int i1, float v2, int i2) {
     return v1 > v2 || (v1 == v2 && i1 < i2);
 }
 
-struct Best2 { float v1; int i1; float v2; int i2; };
+// a lane's best two (value, id) under the order.  empty() and take() are what vk_stream asks of a lane's accumulator (Best<N> below is the other one)
+struct Best2 {
+    float v1; int i1; float v2; int i2;
+    static __device__ __forceinline__ Best2 empty() { return Best2{-INFINITY, VC_NONE, -INFINITY, VC_NONE}; }
+    template <bool BAN, bool FLOOR>
+    __device__ __forceinline__ void take(float v, int id, const uint32_t* ban, uint64_t /*floor*/) {
+        static_assert(!FLOOR, "the pair has no floor");
+        if (v < v2) return;                                    // (both numbers and v below: behind the second best.  A NaN on either side is false: the full order decides)
+        if (!vc_before(v, id, v2, i2)) return;
+        if (BAN && ((ban[id >> 5] >> (id & 31)) & 1u)) return;
+        if (vc_before(v, id, v1, i1)) { v2 = v1; i2 = i1; v1 = v; i1 = id; }
+        else { v2 = v; i2 = id; }
+    }
+};
 
 // the best two of two pairs over disjoint id sets (two "no id" entries compare as equal: either is kept)
 __device__ __forceinline__ Best2 vc_merge(Best2 a, Best2 b) {
@@ -64,15 +77,6 @@ __device__ __forceinline__ Best2 vc_merge(Best2 a, Best2 b) {
     return r;
 }
 
-template <bool BAN>
-__device__ __forceinline__ void vc_take(Best2& m, float v, int id, const uint32_t* ban) {
-    if (v < m.v2) return;                                      // (both numbers and v below: behind the second best.  A NaN on either side is false: the full order decides)
-    if (!vc_before(v, id, m.v2, m.i2)) return;
-    if (BAN && ((ban[id >> 5] >> (id & 31)) & 1u)) return;
-    if (vc_before(v, id, m.v1, m.i1)) { m.v2 = m.v1; m.i2 = m.i1; m.v1 = v; m.i1 = id; }
-    else { m.v2 = v; m.i2 = id; }
-}
-
 struct VcArgs {
     const float* x; int ldx, V, S;
     const int* ntok; int ntok_bias, pad_idx;
@@ -81,36 +85,20 @@ struct VcArgs {
     int64_t* seq; float* row_chosen; int* changed;
 };
 
-__device__ __forceinline__ int vc_live(const VcArgs& a, int b) {
-    const int n = a.ntok ? a.ntok[b] + a.ntok_bias : a.S;
-    return n < 0 ? 0 : (n > a.S ? a.S : n);
-}
+__device__ __forceinline__ int vc_live(const VcArgs& a, int b) { return live_count(a.ntok, a.ntok_bias, b, a.S); }
 
-// grid = rows: the two best unbanned ids of a live row into seq[row] (packed), pad_idx into a row past n_b
-template <bool BAN>
-__global__ void __launch_bounds__(VC_NT) vocab_candidates_kernel(VcArgs a) {
-    extern __shared__ uint32_t vc_ban[];                       // [ban_words] when the table is staged
-    __shared__ Best2 cand[VC_SEG];
-    const int row = blockIdx.x, tid = threadIdx.x, lane = tid % WAVE, seg = tid / WAVE;
-    const int V = a.V, b = row / a.S, s = row - b * a.S;
-    if (s >= vc_live(a, b)) {                                   // (the whole workgroup: nothing below waits for it)
-        if (tid == 0) a.seq[row] = (int64_t)a.pad_idx;
-        return;
-    }
-    const uint32_t* ban = a.ban;
-    if (BAN && a.ban_lds) {
-        for (int i = tid; i < a.ban_words; i += VC_NT) vc_ban[i] = a.ban[i];
-        ban = vc_ban;
-        __syncthreads();
-    }
-    const float* const p = a.x + (size_t)row * (size_t)a.ldx;
+// THE ROW STREAM, for both candidate kernels and the fallback re-read (vk_row_behind): one wavefront over column segment `seg` of `nseg` of the row at p -- peel to the row's
+// first 16-byte boundary (segment 0), the segments split the 16-byte loads behind it, VC_UNROLL of them in flight per lane, scalar tail (the last segment).  M is the lane's
+// accumulator: Best2, or Best<VP_L> (which alone knows a `floor`).
+template <typename M, bool BAN, bool FLOOR>
+__device__ __forceinline__ M vk_stream(const float* p, int V, int seg, int nseg, int lane, const uint32_t* ban, uint64_t floor) {
     int peel = (4 - (int)(((uintptr_t)p >> 2) & 3)) & 3;       // elements in front of the row's first 16-byte boundary
     peel = peel > V ? V : peel;
     const int nv = (V - peel) / 4, tail0 = peel + 4 * nv;      // 16-byte groups behind it; the first element of the scalar tail
-    const int g0 = (int)((int64_t)seg * nv / VC_SEG), g1 = (int)((int64_t)(seg + 1) * nv / VC_SEG);
-    Best2 m{-INFINITY, VC_NONE, -INFINITY, VC_NONE};
-    if (seg == 0 && lane < peel) vc_take<BAN>(m, p[lane], lane, ban);
-    if (seg == VC_SEG - 1 && tail0 + lane < V) vc_take<BAN>(m, p[tail0 + lane], tail0 + lane, ban);
+    const int g0 = (int)((int64_t)seg * nv / nseg), g1 = (int)((int64_t)(seg + 1) * nv / nseg);
+    M m = M::empty();
+    if (seg == 0 && lane < peel) m.template take<BAN, FLOOR>(p[lane], lane, ban, floor);
+    if (seg == nseg - 1 && tail0 + lane < V) m.template take<BAN, FLOOR>(p[tail0 + lane], tail0 + lane, ban, floor);
     const float4* const p4 = reinterpret_cast<const float4*>(p + peel);
     for (int base = g0; base < g1; base += WAVE * VC_UNROLL) {
         float4 r[VC_UNROLL];
@@ -124,11 +112,41 @@ __global__ void __launch_bounds__(VC_NT) vocab_candidates_kernel(VcArgs a) {
             const int g = base + j * WAVE + lane;
             if (g < g1) {
                 const int id = peel + 4 * g;
-                vc_take<BAN>(m, r[j].x, id, ban); vc_take<BAN>(m, r[j].y, id + 1, ban);
-                vc_take<BAN>(m, r[j].z, id + 2, ban); vc_take<BAN>(m, r[j].w, id + 3, ban);
+                m.template take<BAN, FLOOR>(r[j].x, id, ban, floor); m.template take<BAN, FLOOR>(r[j].y, id + 1, ban, floor);
+                m.template take<BAN, FLOOR>(r[j].z, id + 2, ban, floor); m.template take<BAN, FLOOR>(r[j].w, id + 3, ban, floor);
             }
         }
     }
+    return m;
+}
+
+// The entry of both candidate kernels (grid = rows, VC_NT threads): a row past n_b gets pad_idx into seq (where there is a seq: bofi_vocab_nbest has none, it pads its own
+// outputs) and the WHOLE workgroup leaves -- false; nothing waits for it.  Else `ban` is the table to look up: staged in dynamic LDS (and one barrier) when it fits.
+template <bool BAN>
+__device__ __forceinline__ bool vc_enter(const VcArgs& a, int row, int tid, const uint32_t*& ban) {
+    extern __shared__ uint32_t vc_ban[];                       // [ban_words] when the table is staged
+    const int b = row / a.S, s = row - b * a.S;
+    if (s >= vc_live(a, b)) {
+        if (tid == 0 && a.seq) a.seq[row] = (int64_t)a.pad_idx;
+        return false;
+    }
+    ban = a.ban;
+    if (BAN && a.ban_lds) {
+        for (int i = tid; i < a.ban_words; i += VC_NT) vc_ban[i] = a.ban[i];
+        ban = vc_ban;
+        __syncthreads();
+    }
+    return true;
+}
+
+// grid = rows: the two best unbanned ids of a live row into seq[row] (packed), pad_idx into a row past n_b
+template <bool BAN>
+__global__ void __launch_bounds__(VC_NT) vocab_candidates_kernel(VcArgs a) {
+    __shared__ Best2 cand[VC_SEG];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid % WAVE, seg = tid / WAVE;
+    const uint32_t* ban;
+    if (!vc_enter<BAN>(a, row, tid, ban)) return;
+    Best2 m = vk_stream<Best2, BAN, false>(a.x + (size_t)row * (size_t)a.ldx, a.V, seg, VC_SEG, lane, ban, 0ull);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {                          // butterfly: the lanes hold disjoint ids, so both partners of a step arrive at the same pair
         Best2 t;
@@ -199,8 +217,6 @@ constexpr int VP_L = 4;                        // ... and per lane
 constexpr int VP_CUT = 0x7ffffffe;             // in the workspace: the row's order is not known from this entry on
 static_assert(VP_K == 2 * VP_L && (VP_L & (VP_L - 1)) == 0, "the merges are bitonic");
 
-template <int N> struct Best { uint64_t k[N]; };      // descending; 0 = no id
-
 __device__ __forceinline__ uint64_t vk_key(float v, int id) {
     uint32_t u = __float_as_uint(v);
     if (u == 0x80000000u) u = 0u;                              // -0.0 ties with +0.0
@@ -216,17 +232,28 @@ __device__ __forceinline__ void vk_order(uint64_t& a, uint64_t& c) {
     a = hi; c = lo;
 }
 
-// an element strictly behind `floor` (FLOOR) enters the lane's list when it is in front of the list's last entry and not banned
-template <bool BAN, bool FLOOR>
-__device__ __forceinline__ void vk_take(Best<VP_L>& m, float v, int id, const uint32_t* ban, uint64_t floor) {
-    const uint64_t key = vk_key(v, id);
-    if (key <= m.k[VP_L - 1]) return;
-    if (FLOOR && key >= floor) return;
-    if (BAN && ((ban[id >> 5] >> (id & 31)) & 1u)) return;
-    m.k[VP_L - 1] = key;
+// a sorted list of keys, descending; 0 = no id.  As a lane's accumulator for vk_stream (as Best2): an element strictly behind `floor` (FLOOR) enters the list when it
+// is in front of the list's last entry and not banned
+template <int N>
+struct Best {
+    uint64_t k[N];
+    static __device__ __forceinline__ Best empty() {
+        Best m;
 #pragma unroll
-    for (int k = VP_L - 1; k > 0; --k) vk_order(m.k[k - 1], m.k[k]);
-}
+        for (int i = 0; i < N; ++i) m.k[i] = 0ull;
+        return m;
+    }
+    template <bool BAN, bool FLOOR>
+    __device__ __forceinline__ void take(float v, int id, const uint32_t* ban, uint64_t floor) {
+        const uint64_t key = vk_key(v, id);
+        if (key <= k[N - 1]) return;
+        if (FLOOR && key >= floor) return;
+        if (BAN && ((ban[id >> 5] >> (id & 31)) & 1u)) return;
+        k[N - 1] = key;
+#pragma unroll
+        for (int i = N - 1; i > 0; --i) vk_order(k[i - 1], k[i]);
+    }
+};
 
 // the best N of two sorted lists over disjoint id sets: a[k] against b[N-1-k] leaves the best N as a bitonic sequence, log2 N half-cleaners sort it
 template <int N>
@@ -257,57 +284,14 @@ __device__ __forceinline__ Best<N> vk_wave_merge(Best<N> m) {   // butterfly: ev
     return m;
 }
 
-// one wavefront over column segment `seg` of `nseg` of the row at p: peel to the row's first 16-byte boundary (segment 0), 16-byte loads, scalar tail (the last segment)
-template <bool BAN, bool FLOOR>
-__device__ __forceinline__ Best<VP_L> vk_stream(const float* p, int V, int seg, int nseg, int lane, const uint32_t* ban, uint64_t floor) {
-    int peel = (4 - (int)(((uintptr_t)p >> 2) & 3)) & 3;
-    peel = peel > V ? V : peel;
-    const int nv = (V - peel) / 4, tail0 = peel + 4 * nv;
-    const int g0 = (int)((int64_t)seg * nv / nseg), g1 = (int)((int64_t)(seg + 1) * nv / nseg);
-    Best<VP_L> m;
-#pragma unroll
-    for (int k = 0; k < VP_L; ++k) m.k[k] = 0ull;
-    if (seg == 0 && lane < peel) vk_take<BAN, FLOOR>(m, p[lane], lane, ban, floor);
-    if (seg == nseg - 1 && tail0 + lane < V) vk_take<BAN, FLOOR>(m, p[tail0 + lane], tail0 + lane, ban, floor);
-    const float4* const p4 = reinterpret_cast<const float4*>(p + peel);
-    for (int base = g0; base < g1; base += WAVE * VC_UNROLL) {
-        float4 r[VC_UNROLL];
-#pragma unroll
-        for (int j = 0; j < VC_UNROLL; ++j) {
-            const int g = base + j * WAVE + lane;
-            r[j] = g < g1 ? p4[g] : float4{0.f, 0.f, 0.f, 0.f};
-        }
-#pragma unroll
-        for (int j = 0; j < VC_UNROLL; ++j) {
-            const int g = base + j * WAVE + lane;
-            if (g < g1) {
-                const int id = peel + 4 * g;
-                vk_take<BAN, FLOOR>(m, r[j].x, id, ban, floor); vk_take<BAN, FLOOR>(m, r[j].y, id + 1, ban, floor);
-                vk_take<BAN, FLOOR>(m, r[j].z, id + 2, ban, floor); vk_take<BAN, FLOOR>(m, r[j].w, id + 3, ban, floor);
-            }
-        }
-    }
-    return m;
-}
-
 // grid = rows: the best unbanned ids of a live row into work[row][VP_K] (VP_CUT from where the order is not known); pad_idx into seq of a row past n_b
 template <bool BAN>
 __global__ void __launch_bounds__(VC_NT) vocab_candidates_k_kernel(VcArgs a, int* __restrict__ work) {
-    extern __shared__ uint32_t vc_ban[];                       // [ban_words] when the table is staged
     __shared__ Best<VP_K> cand[VC_SEG];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid % WAVE, seg = tid / WAVE;
-    const int b = row / a.S, s = row - b * a.S;
-    if (s >= vc_live(a, b)) {
-        if (tid == 0 && a.seq) a.seq[row] = (int64_t)a.pad_idx;    // (bofi_vocab_nbest has no seq: it pads its own outputs)
-        return;
-    }
-    const uint32_t* ban = a.ban;
-    if (BAN && a.ban_lds) {
-        for (int i = tid; i < a.ban_words; i += VC_NT) vc_ban[i] = a.ban[i];
-        ban = vc_ban;
-        __syncthreads();
-    }
-    const Best<VP_L> own = vk_stream<BAN, false>(a.x + (size_t)row * (size_t)a.ldx, a.V, seg, VC_SEG, lane, ban, 0ull);
+    const uint32_t* ban;
+    if (!vc_enter<BAN>(a, row, tid, ban)) return;
+    const Best<VP_L> own = vk_stream<Best<VP_L>, BAN, false>(a.x + (size_t)row * (size_t)a.ldx, a.V, seg, VC_SEG, lane, ban, 0ull);
     Best<VP_K> m;
 #pragma unroll
     for (int k = 0; k < VP_K; ++k) m.k[k] = k < VP_L ? own.k[k] : 0ull;
@@ -329,7 +313,7 @@ __global__ void __launch_bounds__(VC_NT) vocab_candidates_k_kernel(VcArgs a, int
 
 // the wavefront's next VP_L unbanned ids of one row strictly BEHIND `floor` in the order (the scan's fallback; the ban table through the cache), the same in every lane
 __device__ __forceinline__ Best<VP_L> vk_row_behind(const float* p, int V, uint64_t floor, const uint32_t* ban, int lane) {
-    return vk_wave_merge<VP_L>(ban ? vk_stream<true, true>(p, V, 0, 1, lane, ban, floor) : vk_stream<false, true>(p, V, 0, 1, lane, ban, floor));
+    return vk_wave_merge<VP_L>(ban ? vk_stream<Best<VP_L>, true, true>(p, V, 0, 1, lane, ban, floor) : vk_stream<Best<VP_L>, false, true>(p, V, 0, 1, lane, ban, floor));
 }
 
 // grid = ceil(B / 4) workgroups of four wavefronts: wavefront = image, lane = position
@@ -421,7 +405,72 @@ struct NbArgs {
     int64_t* seq_n; double* total; int* count;
 };
 
-__device__ __forceinline__ bool nb_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+// THE LIST KERNELS' FRONT END (vocab_nbest_kernel and vocab_nbest_norepeat_kernel; cid and xv have a stride of VP_K entries per row in both).  None of these helpers holds
+// a barrier: the kernels keep theirs between the steps.
+// one wavefront, lane = position: the first `want` workspace ids of the image's rows into cid (VC_NONE behind them and where the row has no such id).  Returns cutk, the
+// first entry within `want` from which the row's order is not known (-1: none)
+__device__ __forceinline__ int nb_ids(const int* __restrict__ work, size_t row0, int n, int want, int V, int* cid, int lane) {
+    int cutk = -1;
+    if (lane < n) {
+#pragma unroll
+        for (int k = 0; k < VP_K; ++k) {
+            int c = k < want ? work[(row0 + lane) * VP_K + k] : VC_NONE;
+            if (c == VP_CUT) { if (cutk < 0) cutk = k; }
+            else if ((unsigned)c >= (unsigned)V) c = VC_NONE;  // (VC_NONE itself; never an index outside the row)
+            cid[lane * VP_K + k] = cutk >= 0 ? VC_NONE : c;
+        }
+    }
+    return cutk;
+}
+// ... then (behind a barrier) the rows with a cut order, one at a time: the whole wavefront streams the row again for the ids behind the last one known
+__device__ __forceinline__ void nb_cut_rows(const NbArgs& a, size_t row0, int want, int cutk, int* cid, int lane) {
+    for (unsigned long long cuts = __ballot(cutk >= 0); cuts; cuts &= cuts - 1) {
+        const int s = __builtin_amdgcn_readfirstlane(__ffsll((long long)cuts) - 1);
+        int k0 = __builtin_amdgcn_readlane(cutk, s);            // (>= 1: the first entry is never VP_CUT)
+        const float* const p = a.x + (row0 + s) * (size_t)a.ldx;
+        const int last = cid[s * VP_K + k0 - 1];
+        if (last == VC_NONE) continue;                          // (cannot be: a cut stands behind a real id)
+        uint64_t floor = vk_key(p[last], last);
+        while (k0 < want) {
+            const Best<VP_L> m = vk_row_behind(p, a.V, floor, a.ban, lane);
+#pragma unroll
+            for (int k = 0; k < VP_L; ++k)
+                if (lane == 0 && k0 + k < want) cid[s * VP_K + k0 + k] = vk_id(m.k[k]);
+            if (!m.k[VP_L - 1]) break;                          // the row is exhausted
+            floor = m.k[VP_L - 1];
+            k0 += VP_L;
+        }
+    }
+}
+// thread t of nt over the (position, candidate) pairs: the values x[p, c[p][r]] -- scattered 4-byte loads, rows need no alignment; NaN where there is no id
+__device__ __forceinline__ void nb_values(const NbArgs& a, size_t row0, int n, const int* cid, float* xv, int t, int nt) {
+    for (int i = t; i < n * VP_K; i += nt) {
+        const int c = cid[i];
+        xv[i] = c != VC_NONE ? a.x[(row0 + i / VP_K) * (size_t)a.ldx + (size_t)c] : NAN;
+    }
+}
+// a live row whose first id has no finite value: the image is degenerate (a whole wavefront asks)
+__device__ __forceinline__ bool nb_degen(const float* xv, int n, int lane) { return __ballot(lane < n && !f32_finite(xv[lane * VP_K])) != 0ull; }
+
+// the rank of `mine`, the total in slot `lane`, among totals[0 .. upto): the entries in front of it -- a larger total, or the same total in a lower slot.  upto <= WAVE,
+// totals holds WAVE entries and NB_CHUNK divides WAVE: a chunk never leaves the array, and an entry past upto that is read is -inf, in front of nothing
+__device__ __forceinline__ int nb_rank(const double* totals, int upto, double mine, int lane) {
+    int rank = 0;
+    for (int j0 = 0; j0 < upto; j0 += NB_CHUNK) {
+        double t[NB_CHUNK];
+#pragma unroll
+        for (int j = 0; j < NB_CHUNK; ++j) t[j] = totals[j0 + j];      // a chunk's LDS reads in flight together (one by one, a step was 64 dependent round trips)
+#pragma unroll
+        for (int j = 0; j < NB_CHUNK; ++j)      // (no && / ||: as branches they cost four times the compares)
+            rank += (int)(t[j] > mine) | ((int)(t[j] == mine) & (int)(j0 + j < lane));
+    }
+    return rank;
+}
+
+// thread t of nt: the image's captions out [N][S] (LDS) into seq_n[b] as one contiguous block
+__device__ __forceinline__ void nb_write_captions(const NbArgs& a, int b, const int* out, int t, int nt) {
+    for (int i = t; i < a.N * a.S; i += nt) a.seq_n[(size_t)b * a.N * a.S + i] = (int64_t)out[i];
+}
 
 __global__ void __launch_bounds__(NB_IPW * WAVE) vocab_nbest_kernel(NbArgs a, const int* __restrict__ work) {
     __shared__ double tt_[NB_IPW][WAVE];                        // the totals of a step's pairs
@@ -439,51 +488,16 @@ __global__ void __launch_bounds__(NB_IPW * WAVE) vocab_nbest_kernel(NbArgs a, co
     float* const xv = xv_[wave];
     int* const out = out_[wave];
     uint8_t* const bp = bp_[wave];
-    int n = 0;
-    if (on) {
-        n = a.ntok ? a.ntok[b] + a.ntok_bias : S;
-        n = n < 0 ? 0 : (n > S ? S : n);
-    }
-    n = __builtin_amdgcn_readfirstlane(n);
+    const int n = __builtin_amdgcn_readfirstlane(on ? live_count(a.ntok, a.ntok_bias, b, S) : 0);
     const size_t row0 = (size_t)(on ? b : 0) * S;
-    // lane = position: the row's ids; cutk = the first entry within N from which the order is not known
-    int cutk = -1;
-    if (lane < n) {
-#pragma unroll
-        for (int k = 0; k < NB_MAX; ++k) {
-            int c = k < N ? work[(row0 + lane) * VP_K + k] : VC_NONE;
-            if (c == VP_CUT) { if (cutk < 0) cutk = k; }
-            else if ((unsigned)c >= (unsigned)V) c = VC_NONE;  // (VC_NONE itself; never an index outside the row)
-            cid[lane * NB_MAX + k] = cutk >= 0 ? VC_NONE : c;
-        }
-    }
+    const int cutk = nb_ids(work, row0, n, N, V, cid, lane);   // lane = position
     __syncthreads();
-    for (unsigned long long cuts = __ballot(cutk >= 0); cuts; cuts &= cuts - 1) {      // the rows with a cut order, one at a time: the whole wavefront streams the row again
-        const int s = __builtin_amdgcn_readfirstlane(__ffsll((long long)cuts) - 1);
-        int k0 = __builtin_amdgcn_readlane(cutk, s);            // (>= 1: the first entry is never VP_CUT)
-        const float* const p = a.x + (row0 + s) * (size_t)a.ldx;
-        const int last = cid[s * NB_MAX + k0 - 1];
-        if (last == VC_NONE) continue;                          // (cannot be: a cut stands behind a real id)
-        uint64_t floor = vk_key(p[last], last);
-        while (k0 < N) {
-            const Best<VP_L> m = vk_row_behind(p, V, floor, a.ban, lane);
-#pragma unroll
-            for (int k = 0; k < VP_L; ++k)
-                if (lane == 0 && k0 + k < N) cid[s * NB_MAX + k0 + k] = vk_id(m.k[k]);
-            if (!m.k[VP_L - 1]) break;                          // the row is exhausted
-            floor = m.k[VP_L - 1];
-            k0 += VP_L;
-        }
-    }
+    nb_cut_rows(a, row0, N, cutk, cid, lane);
     __syncthreads();
-    // lane over the (position, candidate) pairs: the values
-    for (int i = lane; i < n * NB_MAX; i += WAVE) {
-        const int c = cid[i];
-        xv[i] = c != VC_NONE ? a.x[(row0 + i / NB_MAX) * (size_t)a.ldx + (size_t)c] : NAN;
-    }
+    nb_values(a, row0, n, cid, xv, lane, WAVE);                 // lane over the (position, candidate) pairs
     if (lane < NB_MAX) T[lane] = 0.0;                           // L_0 = [(0.0, empty)]
     __syncthreads();
-    const bool degen = __ballot(lane < n && !nb_finite(xv[lane * NB_MAX])) != 0ull;       // a live row whose first id has no finite value
+    const bool degen = nb_degen(xv, n, lane);
     // the merge, lane = pair
     const int pi = lane / N, pr = lane - pi * N;
     int cnt = 1;
@@ -493,22 +507,14 @@ __global__ void __launch_bounds__(NB_IPW * WAVE) vocab_nbest_kernel(NbArgs a, co
         const bool step = p < n && !degen;                      // (the same in every lane of the wavefront)
         if (step) {
             const float v = pi < cnt ? xv[p * NB_MAX + pr] : NAN;      // (pi < cnt <= N, so pr < N <= NB_MAX)
-            valid = pi < cnt && nb_finite(v);
+            valid = pi < cnt && f32_finite(v);
             mine = valid ? T[pi] + (double)v : -(double)INFINITY;      // (a pair that is not valid: in front of no valid pair, whose totals are finite)
             tt[lane] = mine;
         }
         __syncthreads();
         if (step) {
             const unsigned long long vm = __ballot(valid);
-            int rank = 0;
-            for (int j0 = 0; j0 < cnt * N; j0 += NB_CHUNK) {      // (cnt * N <= WAVE and NB_CHUNK divides WAVE: a chunk never leaves tt; an entry past cnt * N is -inf)
-                double t[NB_CHUNK];
-#pragma unroll
-                for (int j = 0; j < NB_CHUNK; ++j) t[j] = tt[j0 + j];      // a chunk's LDS reads in flight together (one by one, a step was 64 dependent round trips)
-#pragma unroll
-                for (int j = 0; j < NB_CHUNK; ++j)      // (no && / ||: as branches they cost four times the compares)
-                    rank += (int)(t[j] > mine) | ((int)(t[j] == mine) & (int)(j0 + j < lane));
-            }
+            const int rank = nb_rank(tt, cnt * N, mine, lane);      // (cnt * N <= WAVE)
             if (valid && rank < N) { T[rank] = mine; bp[p * NB_MAX + rank] = (uint8_t)lane; }
             const int nv = __popcll(vm);
             cnt = nv < N ? nv : N;
@@ -536,7 +542,7 @@ __global__ void __launch_bounds__(NB_IPW * WAVE) vocab_nbest_kernel(NbArgs a, co
     if (on && lane == 0) a.count[b] = cnt;
     __syncthreads();
     if (!on) return;
-    for (int i = lane; i < N * S; i += WAVE) a.seq_n[(size_t)b * N * S + i] = (int64_t)out[i];
+    nb_write_captions(a, b, out, lane, WAVE);
 }
 
 // ---- the N-best list under "no adjacent repeated word" (bofi_vocab_nbest_norepeat): the rule couples neighbours, so a width-N list no longer serves; the N best VALID
@@ -570,53 +576,21 @@ __global__ void __launch_bounds__(NR_W * WAVE) vocab_nbest_norepeat_kernel(NbArg
     __shared__ uint8_t bp[VC_MAX_S * WAVE];                     // [p][r * 8 + j]: the slot of A_{p-1} that entry j of A_p[r] came from
     const int tid = threadIdx.x, lane = tid % WAVE, r = __builtin_amdgcn_readfirstlane(tid / WAVE), b = blockIdx.x;
     const int S = a.S, N = a.N, V = a.V, K = N + 2;
-    int n = a.ntok ? a.ntok[b] + a.ntok_bias : S;
-    n = __builtin_amdgcn_readfirstlane(n < 0 ? 0 : (n > S ? S : n));
+    const int n = __builtin_amdgcn_readfirstlane(live_count(a.ntok, a.ntok_bias, b, S));
     const size_t row0 = (size_t)b * S;
     const double NINF = -(double)INFINITY;
-    // wavefront 0, lane = position: the row's ids; cutk = the first entry within K from which the order is not known
-    int cutk = -1;
-    if (r == 0 && lane < n) {
-#pragma unroll
-        for (int k = 0; k < NR_W; ++k) {
-            int c = k < K ? work[(row0 + lane) * VP_K + k] : VC_NONE;
-            if (c == VP_CUT) { if (cutk < 0) cutk = k; }
-            else if ((unsigned)c >= (unsigned)V) c = VC_NONE;  // (VC_NONE itself; never an index outside the row)
-            cid[lane * NR_W + k] = cutk >= 0 ? VC_NONE : c;
-        }
-    }
+    // the front end as vocab_nbest_kernel's, K entries a row: wavefront 0 has the ids and the cut rows, all threads the values
+    const int cutk = nb_ids(work, row0, r == 0 ? n : 0, K, V, cid, lane);      // (no position in the other wavefronts)
     __syncthreads();
-    if (r == 0) {
-        for (unsigned long long cuts = __ballot(cutk >= 0); cuts; cuts &= cuts - 1) {      // the rows with a cut order, one at a time: the wavefront streams the row again
-            const int s = __builtin_amdgcn_readfirstlane(__ffsll((long long)cuts) - 1);
-            int k0 = __builtin_amdgcn_readlane(cutk, s);        // (>= 1: the first entry is never VP_CUT)
-            const float* const p = a.x + (row0 + s) * (size_t)a.ldx;
-            const int last = cid[s * NR_W + k0 - 1];
-            if (last == VC_NONE) continue;                      // (cannot be: a cut stands behind a real id)
-            uint64_t floor = vk_key(p[last], last);
-            while (k0 < K) {
-                const Best<VP_L> m = vk_row_behind(p, V, floor, a.ban, lane);
-#pragma unroll
-                for (int k = 0; k < VP_L; ++k)
-                    if (lane == 0 && k0 + k < K) cid[s * NR_W + k0 + k] = vk_id(m.k[k]);
-                if (!m.k[VP_L - 1]) break;                      // the row is exhausted
-                floor = m.k[VP_L - 1];
-                k0 += VP_L;
-            }
-        }
-    }
+    if (r == 0) nb_cut_rows(a, row0, K, cutk, cid, lane);
     __syncthreads();
-    // thread over the (position, candidate) pairs: the values
-    for (int i = tid; i < n * NR_W; i += NR_W * WAVE) {
-        const int c = cid[i];
-        xv[i] = c != VC_NONE ? a.x[(row0 + i / NR_W) * (size_t)a.ldx + (size_t)c] : NAN;
-    }
+    nb_values(a, row0, n, cid, xv, tid, NR_W * WAVE);
     __syncthreads();
-    const bool degen = __ballot(lane < n && !nb_finite(xv[lane * NR_W])) != 0ull;       // a live row whose first id has no finite value (every wavefront finds the same)
+    const bool degen = nb_degen(xv, n, lane);                   // (every wavefront finds the same)
     const bool run = n > 0 && !degen;                           // (the same in every wavefront of the workgroup)
     if (run) {
         // A_0[r] = [0.0 + x[0, c[0][r]]]
-        if (lane < NR_W) A_[0][r * NR_W + lane] = (lane == 0 && r < K && nb_finite(xv[r])) ? 0.0 + (double)xv[r] : NINF;
+        if (lane < NR_W) A_[0][r * NR_W + lane] = (lane == 0 && r < K && f32_finite(xv[r])) ? 0.0 + (double)xv[r] : NINF;
         __syncthreads();
         const int rp = lane / NR_W;                             // this lane's pair (r', j): the predecessor state
         for (int p = 1; p < n; ++p) {
@@ -624,7 +598,7 @@ __global__ void __launch_bounds__(NR_W * WAVE) vocab_nbest_norepeat_kernel(NbArg
             double* const Ac = A_[p & 1];
             const float v = xv[p * NR_W + r];
             const int id = cid[p * NR_W + r], idp = cid[(p - 1) * NR_W + rp];
-            const bool state = r < K && nb_finite(v);           // (wave-uniform) c[p][r] is a candidate
+            const bool state = r < K && f32_finite(v);           // (wave-uniform) c[p][r] is a candidate
             const bool conf = idp == id && idp >= lo;           // the pair would repeat a word
             const unsigned long long cm = __ballot(conf);
             const double dv = (double)v, own = Ap[lane], mine = own + dv;
@@ -655,14 +629,7 @@ __global__ void __launch_bounds__(NR_W * WAVE) vocab_nbest_norepeat_kernel(NbArg
         const double* const Al = A_[(n - 1) & 1];
         const double mine = Al[lane];
         const bool valid = mine > NINF;
-        int rank = 0;
-        for (int j0 = 0; j0 < WAVE; j0 += NB_CHUNK) {
-            double t[NB_CHUNK];
-#pragma unroll
-            for (int j = 0; j < NB_CHUNK; ++j) t[j] = Al[j0 + j];
-#pragma unroll
-            for (int j = 0; j < NB_CHUNK; ++j) rank += (int)(t[j] > mine) | ((int)(t[j] == mine) & (int)(j0 + j < lane));
-        }
+        const int rank = nb_rank(Al, WAVE, mine, lane);
         if (valid && rank < N) { Tf[rank] = mine; fl[rank] = (uint8_t)lane; }
         const int nv = __popcll(__ballot(valid));
         cnt = nv < N ? nv : N;                                  // (0: no valid caption over the candidates)
@@ -688,7 +655,57 @@ __global__ void __launch_bounds__(NR_W * WAVE) vocab_nbest_norepeat_kernel(NbArg
         if (lane == 0) a.count[b] = cnt;
     }
     __syncthreads();
-    for (int i = tid; i < N * S; i += NR_W * WAVE) a.seq_n[(size_t)b * N * S + i] = (int64_t)out[i];
+    nb_write_captions(a, b, out, tid, NR_W * WAVE);
+}
+
+// ---- the host side
+VcArgs vc_args(const float* x, int ldx, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int no_repeat, int repeat_min_id, int64_t* seq,
+               float* row_chosen, int* changed) {
+    VcArgs a{};
+    a.x = x; a.ldx = ldx; a.V = V; a.S = S; a.ntok = ntok; a.ntok_bias = ntok_bias; a.pad_idx = pad_idx; a.ban = ban_bits; a.ban_words = (V + 31) / 32;
+    a.ban_lds = a.ban_words <= VC_BAN_LDS_WORDS; a.no_repeat = no_repeat; a.repeat_min_id = repeat_min_id; a.seq = seq; a.row_chosen = row_chosen; a.changed = changed;
+    return a;
+}
+
+// the candidate launches, one workgroup per row: the BAN form with a ban table, the table in dynamic LDS where it fits
+inline size_t vc_ban_lds_bytes(const VcArgs& a) { return a.ban && a.ban_lds ? (size_t)a.ban_words * 4 : 0; }
+
+int launch_candidates(const VcArgs& a, int rows, hipStream_t st) {
+    if (a.ban) hipLaunchKernelGGL(vocab_candidates_kernel<true>, dim3(rows), dim3(VC_NT), vc_ban_lds_bytes(a), st, a);
+    else hipLaunchKernelGGL(vocab_candidates_kernel<false>, dim3(rows), dim3(VC_NT), 0, st, a);
+    BOFI_CHECK_LAUNCH();
+    return BOFI_OK;
+}
+
+int launch_candidates_k(const VcArgs& a, int* work, int rows, hipStream_t st) {
+    if (a.ban) hipLaunchKernelGGL(vocab_candidates_k_kernel<true>, dim3(rows), dim3(VC_NT), vc_ban_lds_bytes(a), st, a, work);
+    else hipLaunchKernelGGL(vocab_candidates_k_kernel<false>, dim3(rows), dim3(VC_NT), 0, st, a, work);
+    BOFI_CHECK_LAUNCH();
+    return BOFI_OK;
+}
+
+// both lists: N at most n_max (n_range says so)
+const char* list_check(const float* x, int ldx, int rows, int V, int S, int no_repeat, int repeat_min_id, int N, int n_max, const char* n_range, const int64_t* seq_n,
+                       const double* total, const int* count, const void* work, size_t work_bytes) {
+    if (!seq_n || !total || !count) return "non-null seq_n, total and count";
+    if (const char* why = vocab_constrain_check(x, ldx, rows, V, S, no_repeat, repeat_min_id, seq_n)) return why;
+    if (N < 1 || N > n_max) return n_range;
+    if (rows > 0 && (!work || work_bytes < vocab_nbest_work_bytes(rows))) return "a workspace of bofi_vocab_nbest_workspace(rows) bytes";
+    return nullptr;
+}
+
+// both lists (checked by the caller): the K-candidate launch (seq stays NULL: it writes the workspace only), then the list kernel
+int launch_list(bool norepeat, const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int repeat_min_id, int N,
+                int64_t* seq_n, double* total, int* count, void* work, hipStream_t st) {
+    if (rows == 0) return BOFI_OK;
+    if (int rc = launch_candidates_k(vc_args(x, ldx, V, S, ntok, ntok_bias, pad_idx, ban_bits, 0, 0, nullptr, nullptr, nullptr), (int*)work, rows, st)) return rc;
+    NbArgs nb{};
+    nb.x = x; nb.ldx = ldx; nb.V = V; nb.S = S; nb.B = rows / S; nb.ntok = ntok; nb.ntok_bias = ntok_bias; nb.pad_idx = pad_idx; nb.ban = ban_bits; nb.N = N;
+    nb.seq_n = seq_n; nb.total = total; nb.count = count;
+    if (norepeat) hipLaunchKernelGGL(vocab_nbest_norepeat_kernel, dim3(nb.B), dim3(NR_W * WAVE), 0, st, nb, repeat_min_id, (const int*)work);      // one workgroup per image
+    else hipLaunchKernelGGL(vocab_nbest_kernel, dim3((nb.B + NB_IPW - 1) / NB_IPW), dim3(NB_IPW * WAVE), 0, st, nb, (const int*)work);
+    BOFI_CHECK_LAUNCH();
+    return BOFI_OK;
 }
 
 }  // namespace
@@ -697,30 +714,13 @@ size_t bofi::vocab_nbest_work_bytes(int rows) { return vocab_pick_work_bytes(row
 
 const char* bofi::vocab_nbest_check(const float* x, int ldx, int rows, int V, int S, int N, const int64_t* seq_n, const double* total, const int* count, const void* work,
                                     size_t work_bytes) {
-    if (!seq_n || !total || !count) return "non-null seq_n, total and count";
-    if (const char* why = vocab_constrain_check(x, ldx, rows, V, S, 0, 0, seq_n)) return why;
-    if (N < 1 || N > NB_MAX) return "N in 1..8 (BOFI_NBEST_MAX)";
-    if (rows > 0 && (!work || work_bytes < vocab_nbest_work_bytes(rows))) return "a workspace of bofi_vocab_nbest_workspace(rows) bytes";
-    return nullptr;
+    return list_check(x, ldx, rows, V, S, 0, 0, N, NB_MAX, "N in 1..8 (BOFI_NBEST_MAX)", seq_n, total, count, work, work_bytes);
 }
 
 int bofi::launch_vocab_nbest(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int N,
                              int64_t* seq_n, double* total, int* count, void* work, size_t work_bytes, hipStream_t st) {
     if (vocab_nbest_check(x, ldx, rows, V, S, N, seq_n, total, count, work, work_bytes)) return BOFI_ERR_ARG;
-    if (rows == 0) return BOFI_OK;
-    VcArgs a{};
-    a.x = x; a.ldx = ldx; a.V = V; a.S = S; a.ntok = ntok; a.ntok_bias = ntok_bias; a.pad_idx = pad_idx; a.ban = ban_bits; a.ban_words = (V + 31) / 32;
-    a.ban_lds = a.ban_words <= VC_BAN_LDS_WORDS;                // (seq stays NULL: the candidates launch writes the workspace only)
-    const int B = rows / S;
-    if (ban_bits) hipLaunchKernelGGL(vocab_candidates_k_kernel<true>, dim3(rows), dim3(VC_NT), a.ban_lds ? (size_t)a.ban_words * 4 : 0, st, a, (int*)work);
-    else hipLaunchKernelGGL(vocab_candidates_k_kernel<false>, dim3(rows), dim3(VC_NT), 0, st, a, (int*)work);
-    BOFI_CHECK_LAUNCH();
-    NbArgs nb{};
-    nb.x = x; nb.ldx = ldx; nb.V = V; nb.S = S; nb.B = B; nb.ntok = ntok; nb.ntok_bias = ntok_bias; nb.pad_idx = pad_idx; nb.ban = ban_bits; nb.N = N;
-    nb.seq_n = seq_n; nb.total = total; nb.count = count;
-    hipLaunchKernelGGL(vocab_nbest_kernel, dim3((B + NB_IPW - 1) / NB_IPW), dim3(NB_IPW * WAVE), 0, st, nb, (const int*)work);
-    BOFI_CHECK_LAUNCH();
-    return BOFI_OK;
+    return launch_list(false, x, ldx, rows, V, S, ntok, ntok_bias, pad_idx, ban_bits, 0, N, seq_n, total, count, work, st);
 }
 
 extern "C" int64_t bofi_vocab_nbest_workspace(int rows) { return (int64_t)bofi::vocab_nbest_work_bytes(rows); }
@@ -734,30 +734,13 @@ extern "C" int bofi_vocab_nbest(const float* x, int ldx, int rows, int V, int S,
 
 const char* bofi::vocab_nbest_norepeat_check(const float* x, int ldx, int rows, int V, int S, int repeat_min_id, int N, const int64_t* seq_n, const double* total,
                                              const int* count, const void* work, size_t work_bytes) {
-    if (!seq_n || !total || !count) return "non-null seq_n, total and count";
-    if (const char* why = vocab_constrain_check(x, ldx, rows, V, S, 1, repeat_min_id, seq_n)) return why;
-    if (N < 1 || N > NR_MAX) return "N in 1..6 (BOFI_NBEST_NR_MAX)";
-    if (rows > 0 && (!work || work_bytes < vocab_nbest_work_bytes(rows))) return "a workspace of bofi_vocab_nbest_workspace(rows) bytes";
-    return nullptr;
+    return list_check(x, ldx, rows, V, S, 1, repeat_min_id, N, NR_MAX, "N in 1..6 (BOFI_NBEST_NR_MAX)", seq_n, total, count, work, work_bytes);
 }
 
 int bofi::launch_vocab_nbest_norepeat(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits,
                                       int repeat_min_id, int N, int64_t* seq_n, double* total, int* count, void* work, size_t work_bytes, hipStream_t st) {
     if (vocab_nbest_norepeat_check(x, ldx, rows, V, S, repeat_min_id, N, seq_n, total, count, work, work_bytes)) return BOFI_ERR_ARG;
-    if (rows == 0) return BOFI_OK;
-    VcArgs a{};
-    a.x = x; a.ldx = ldx; a.V = V; a.S = S; a.ntok = ntok; a.ntok_bias = ntok_bias; a.pad_idx = pad_idx; a.ban = ban_bits; a.ban_words = (V + 31) / 32;
-    a.ban_lds = a.ban_words <= VC_BAN_LDS_WORDS;                // (seq stays NULL: the candidates launch writes the workspace only)
-    const int B = rows / S;
-    if (ban_bits) hipLaunchKernelGGL(vocab_candidates_k_kernel<true>, dim3(rows), dim3(VC_NT), a.ban_lds ? (size_t)a.ban_words * 4 : 0, st, a, (int*)work);
-    else hipLaunchKernelGGL(vocab_candidates_k_kernel<false>, dim3(rows), dim3(VC_NT), 0, st, a, (int*)work);
-    BOFI_CHECK_LAUNCH();
-    NbArgs nb{};
-    nb.x = x; nb.ldx = ldx; nb.V = V; nb.S = S; nb.B = B; nb.ntok = ntok; nb.ntok_bias = ntok_bias; nb.pad_idx = pad_idx; nb.ban = ban_bits; nb.N = N;
-    nb.seq_n = seq_n; nb.total = total; nb.count = count;
-    hipLaunchKernelGGL(vocab_nbest_norepeat_kernel, dim3(B), dim3(NR_W * WAVE), 0, st, nb, repeat_min_id, (const int*)work);      // one workgroup per image
-    BOFI_CHECK_LAUNCH();
-    return BOFI_OK;
+    return launch_list(true, x, ldx, rows, V, S, ntok, ntok_bias, pad_idx, ban_bits, repeat_min_id, N, seq_n, total, count, work, st);
 }
 
 extern "C" int bofi_vocab_nbest_norepeat(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits,
@@ -782,13 +765,9 @@ int bofi::launch_vocab_pick(const float* x, int ldx, int rows, int V, int S, con
                             int block_trigrams, int repeat_min_id, int64_t* seq, float* row_chosen, int* changed, void* work, size_t work_bytes, hipStream_t st) {
     if (vocab_pick_check(x, ldx, rows, V, S, no_repeat, block_trigrams, repeat_min_id, seq, work, work_bytes)) return BOFI_ERR_ARG;
     if (rows == 0) return BOFI_OK;
-    VcArgs a{};
-    a.x = x; a.ldx = ldx; a.V = V; a.S = S; a.ntok = ntok; a.ntok_bias = ntok_bias; a.pad_idx = pad_idx; a.ban = ban_bits; a.ban_words = (V + 31) / 32;
-    a.ban_lds = a.ban_words <= VC_BAN_LDS_WORDS; a.no_repeat = no_repeat; a.repeat_min_id = repeat_min_id; a.seq = seq; a.row_chosen = row_chosen; a.changed = changed;
+    const VcArgs a = vc_args(x, ldx, V, S, ntok, ntok_bias, pad_idx, ban_bits, no_repeat, repeat_min_id, seq, row_chosen, changed);
     const int B = rows / S;
-    if (ban_bits) hipLaunchKernelGGL(vocab_candidates_k_kernel<true>, dim3(rows), dim3(VC_NT), a.ban_lds ? (size_t)a.ban_words * 4 : 0, st, a, (int*)work);
-    else hipLaunchKernelGGL(vocab_candidates_k_kernel<false>, dim3(rows), dim3(VC_NT), 0, st, a, (int*)work);
-    BOFI_CHECK_LAUNCH();
+    if (int rc = launch_candidates_k(a, (int*)work, rows, st)) return rc;
     hipLaunchKernelGGL(vocab_scan_k_kernel, dim3((B + VC_SCAN_WAVES - 1) / VC_SCAN_WAVES), dim3(VC_SCAN_WAVES * WAVE), 0, st, a, (const int*)work, block_trigrams, B);
     BOFI_CHECK_LAUNCH();
     return BOFI_OK;
@@ -808,13 +787,9 @@ int bofi::launch_vocab_constrain(const float* x, int ldx, int rows, int V, int S
                                  int no_repeat, int repeat_min_id, int64_t* seq, float* row_chosen, int* changed, hipStream_t st) {
     if (vocab_constrain_check(x, ldx, rows, V, S, no_repeat, repeat_min_id, seq)) return BOFI_ERR_ARG;
     if (rows == 0) return BOFI_OK;
-    VcArgs a{};
-    a.x = x; a.ldx = ldx; a.V = V; a.S = S; a.ntok = ntok; a.ntok_bias = ntok_bias; a.pad_idx = pad_idx; a.ban = ban_bits; a.ban_words = (V + 31) / 32;
-    a.ban_lds = a.ban_words <= VC_BAN_LDS_WORDS; a.no_repeat = no_repeat; a.repeat_min_id = repeat_min_id; a.seq = seq; a.row_chosen = row_chosen; a.changed = changed;
+    const VcArgs a = vc_args(x, ldx, V, S, ntok, ntok_bias, pad_idx, ban_bits, no_repeat, repeat_min_id, seq, row_chosen, changed);
     const int B = rows / S;
-    if (ban_bits) hipLaunchKernelGGL(vocab_candidates_kernel<true>, dim3(rows), dim3(VC_NT), a.ban_lds ? (size_t)a.ban_words * 4 : 0, st, a);
-    else hipLaunchKernelGGL(vocab_candidates_kernel<false>, dim3(rows), dim3(VC_NT), 0, st, a);
-    BOFI_CHECK_LAUNCH();
+    if (int rc = launch_candidates(a, rows, st)) return rc;
     hipLaunchKernelGGL(vocab_scan_kernel, dim3((B + VC_SCAN_WAVES - 1) / VC_SCAN_WAVES), dim3(VC_SCAN_WAVES * WAVE), 0, st, a, B);
     BOFI_CHECK_LAUNCH();
     return BOFI_OK;

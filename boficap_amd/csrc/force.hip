@@ -55,8 +55,6 @@ inline size_t vr_lds_bytes(int S, int K) {
     return (n + 7) & ~(size_t)7;
 }
 
-__device__ __forceinline__ bool vr_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
 // grid = ceil(B / waves) workgroups of `waves` wavefronts: wavefront = image
 __global__ void __launch_bounds__(VR_IPW * WAVE) vocab_require_kernel(VrArgs a) {
     extern __shared__ double vr_lds[];
@@ -73,11 +71,7 @@ __global__ void __launch_bounds__(VR_IPW * WAVE) vocab_require_kernel(VrArgs a) 
     uint8_t* const elig = cnt + 2 * M;                          // [S][K]
     uint8_t* const choice = elig + S * K;                       // [S][M]
 
-    int n = 0;
-    if (on) {
-        n = a.ntok ? a.ntok[b] + a.ntok_bias : S;
-        n = n < 0 ? 0 : (n > S ? S : n);
-    }
+    const int n = on ? live_count(a.ntok, a.ntok_bias, b, S) : 0;
     const size_t row0 = (size_t)(on ? b : 0) * S;
     const int* const wrow = a.words + (size_t)(on ? b : 0) * K;
     // the image's word row, classified (every lane alike): f[j] >= 0 a required word, -1 empty, -2 skipped
@@ -120,7 +114,7 @@ __global__ void __launch_bounds__(VR_IPW * WAVE) vocab_require_kernel(VrArgs a) 
             if (here == fj) ok = true;
             else {
                 const float bv = bvf[p];
-                if (vr_finite(xv) && vr_finite(bv)) { g = (double)xv - (double)bv; ok = true; }
+                if (f32_finite(xv) && f32_finite(bv)) { g = (double)xv - (double)bv; ok = true; }
                 if (a.no_repeat && fj >= a.repeat_min_id && ((p > 0 && sq[p - 1] == fj) || (p + 1 < n && sq[p + 1] == fj))) ok = false;
             }
         }

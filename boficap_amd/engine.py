@@ -268,18 +268,9 @@ class BofiEngine:
         call's ``ban_ids`` and ``repeat_min_id``; same placement, same keys.  ``nbest_count`` may then be 0, and entry 0 need not be ``seq``: the decode's own outputs stay
         the plain decode's (``no_repeat=True``, the constrained decode, stays refused with the list)."""
         mp = self._refine_flag(refine_method, refine_rounds, raw_logits)
-        ban = self._pick_ban(ban_ids, block_trigrams)
-        pick_on = ban is not None or bool(no_repeat) or bool(block_trigrams)
-        req = self._require_table(require_ids, att_feats.size(0), ban_ids)
-        if req is not None:
-            self._require_refusals(ids_only, mp, block_trigrams)
-        nbest = self._nbest_width(nbest)
-        nb_min = self._nbest_no_repeat(nbest, nbest_no_repeat, repeat_min_id)
-        if nbest:
-            self._nbest_refusals(ids_only, mp, no_repeat, block_trigrams, req is not None,
-                                 want_logprob or (out is not None and out.get("seq_logprob") is not None))
-        if pick_on and (ids_only or mp):
-            raise hip.BofiHipError("ban_ids / no_repeat / block_trigrams: not with ids_only (no distribution to re-pick from) or refine_method='mask_predict'")
+        ban, pick_on, req, nbest, nb_min = self._post_options(
+            ban_ids, no_repeat, repeat_min_id, block_trigrams, require_ids, nbest, nbest_no_repeat, att_feats.size(0), ids_only, mp,
+            want_logprob or (out is not None and out.get("seq_logprob") is not None))
         if ids_only:
             if raw_logits:
                 raise hip.BofiHipError("ids_only: the raw logits are not produced")
@@ -331,21 +322,47 @@ class BofiEngine:
             self._h, hip.ptr(att_feats), hip.dtype_code(att_feats), hip.ptr(att_len), B, R, flags, hip.ptr(out["seq"]),
             hip.ptr(out["seq_logprob"]), hip.ptr(out["phrase_num"]), hip.ptr(out["phrase_length"]), hip.ptr(out["phrase_syn"]),
             hip.ptr(out["memory"]), hip.ptr(out["bound_iters"]), C.byref(o), hip.stream_ptr()), "bofi_engine_decode_naic")
-        if pick_on and (not phases or "f" in phases):
-            hip.check(self._lib.bofi_engine_pick_changed(self._h, hip.ptr(out["constrained"]), B, hip.stream_ptr()), "bofi_engine_pick_changed")
         if req is None:
             out.pop("required_pos", None), out.pop("required_moved", None)      # (a reused `out` of a call that had the option)
-        elif not phases or "f" in phases:
-            out["required_pos"], out["required_moved"] = self._require_place(
-                req, out["seq"], out["seq_logprob"], torch.sum(out["phrase_length"], 1, dtype=torch.int32), 0, ban, no_repeat, repeat_min_id,
-                out["row_chosen"] if row_stats else None, out.get("required_pos"), out.get("required_moved"))
         if not nbest:
             out.pop("nbest_seq", None), out.pop("nbest_logp", None), out.pop("nbest_count", None)      # (a reused `out` of a call that had the option)
-        elif not phases or "f" in phases:
-            out["nbest_seq"], out["nbest_logp"], out["nbest_count"] = self._nbest_list(
-                nbest, B, out["seq_logprob"], torch.sum(out["phrase_length"], 1, dtype=torch.int32), 0, ban, out.get("nbest_seq"), out.get("nbest_logp"),
-                out.get("nbest_count"), repeat_min=nb_min)
+        if not phases or "f" in phases:
+            self._post_passes(out, B, out["seq"], out["seq_logprob"], lambda: torch.sum(out["phrase_length"], 1, dtype=torch.int32), 0, ban, pick_on, req, nbest, nb_min,
+                              no_repeat, repeat_min_id, out["row_chosen"] if row_stats else None)
         return out
+
+    def _post_options(self, ban_ids, no_repeat, repeat_min_id, block_trigrams, require_ids, nbest, nbest_no_repeat, B: int, ids_only, mp: int, own_rows: bool):
+        """The options of ``decode_naic`` / ``fill_naic`` whose work follows the call, resolved and refused before anything is enqueued: (ban, pick_on, req, nbest, nb_min)
+        -- the device bit table or None, "the constrained pick is on", the device table of required words or None, the list's width (0: off) and the ``repeat_min_id``
+        of a repeat-free list (None: the plain list).  ``ids_only`` None: the entry point has no such form (``fill_naic``; its pick refusal comes first, in its own words)."""
+        ban = self._pick_ban(ban_ids, block_trigrams)
+        pick_on = ban is not None or bool(no_repeat) or bool(block_trigrams)
+        if ids_only is None and pick_on and mp:
+            raise hip.BofiHipError("ban_ids / no_repeat / block_trigrams: not with refine_method='mask_predict'")
+        req = self._require_table(require_ids, B, ban_ids)
+        if req is not None:
+            self._require_refusals(bool(ids_only), mp, block_trigrams)
+        nbest = self._nbest_width(nbest)
+        nb_min = self._nbest_no_repeat(nbest, nbest_no_repeat, repeat_min_id)
+        if nbest:
+            self._nbest_refusals(bool(ids_only), mp, no_repeat, block_trigrams, req is not None, own_rows)
+        if ids_only is not None and pick_on and (ids_only or mp):
+            raise hip.BofiHipError("ban_ids / no_repeat / block_trigrams: not with ids_only (no distribution to re-pick from) or refine_method='mask_predict'")
+        return ban, pick_on, req, nbest, nb_min
+
+    def _post_passes(self, target: dict, B: int, seq, lp, ntok, ntok_bias: int, ban, pick_on: bool, req, nbest: int, nb_min, no_repeat, repeat_min_id, row_chosen) -> None:
+        """Enqueue what follows a filling pass on the current stream, results into ``target`` (its buffers are reused when they fit): the constrained pick's count
+        (bofi_engine_pick_changed), the required words (``_require_place``), the N-best list (``_nbest_list``).  ``ntok()`` gives the images' lengths where one is needed."""
+        if pick_on:
+            if target.get("constrained") is None or target["constrained"].numel() != B:
+                target["constrained"] = torch.zeros(B, dtype=torch.int32, device=seq.device)
+            hip.check(self._lib.bofi_engine_pick_changed(self._h, hip.ptr(target["constrained"]), B, hip.stream_ptr()), "bofi_engine_pick_changed")
+        if req is not None:
+            target["required_pos"], target["required_moved"] = self._require_place(
+                req, seq, lp, ntok(), ntok_bias, ban, no_repeat, repeat_min_id, row_chosen, target.get("required_pos"), target.get("required_moved"))
+        if nbest:
+            target["nbest_seq"], target["nbest_logp"], target["nbest_count"] = self._nbest_list(
+                nbest, B, lp, ntok(), ntok_bias, ban, target.get("nbest_seq"), target.get("nbest_logp"), target.get("nbest_count"), repeat_min=nb_min)
 
     @staticmethod
     def _nbest_width(nbest) -> int:
@@ -696,18 +713,8 @@ class BofiEngine:
         same refusals): that dict then carries 'nbest_seq' int64 [B, N, S], 'nbest_logp' float64 [B, N] and 'nbest_count' int32 [B]; ``nbest_no_repeat`` as
         ``decode_naic`` (bofi_vocab_nbest_norepeat in its place, N <= 6)."""
         mp = self._refine_flag(refine_method, refine_rounds, raw_logits)
-        ban = self._pick_ban(ban_ids, block_trigrams)
-        pick_on = ban is not None or bool(no_repeat) or bool(block_trigrams)
-        if pick_on and mp:
-            raise hip.BofiHipError("ban_ids / no_repeat / block_trigrams: not with refine_method='mask_predict'")
-        req = self._require_table(require_ids, ext_syn.size(0), ban_ids)
-        if req is not None:
-            self._require_refusals(False, mp, block_trigrams)
-        nbest = self._nbest_width(nbest)
-        nb_min = self._nbest_no_repeat(nbest, nbest_no_repeat, repeat_min_id)
-        if nbest:
-            self._nbest_refusals(False, mp, no_repeat, block_trigrams, req is not None, True)
         B = ext_syn.size(0)
+        ban, pick_on, req, nbest, nb_min = self._post_options(ban_ids, no_repeat, repeat_min_id, block_trigrams, require_ids, nbest, nbest_no_repeat, B, None, mp, True)
         if ext_syn.dtype != torch.int32 or last.dtype != torch.int32 or ext_syn.size(1) != self.cfg.bound_len or last.numel() != B:
             raise hip.BofiHipError("ext_syn must be int32 [B, S+2] and last int32 [B]")
         S, V, dev = self.cfg.seq_length, self.cfg.tgt_vocab, ext_syn.device
@@ -721,13 +728,7 @@ class BofiEngine:
         self._pick_opts(o, ban, no_repeat, repeat_min_id, block_trigrams)
         hip.check(self._lib.bofi_engine_fill_naic(self._h, hip.ptr(ext_syn.contiguous()), hip.ptr(last.contiguous()), B, R, hip.ptr(att_len), flags,
                                                   hip.ptr(seq), hip.ptr(lp), C.byref(o), hip.stream_ptr()), "bofi_engine_fill_naic")
-        if pick_on:
-            attn["constrained"] = torch.zeros(B, dtype=torch.int32, device=dev)
-            hip.check(self._lib.bofi_engine_pick_changed(self._h, hip.ptr(attn["constrained"]), B, hip.stream_ptr()), "bofi_engine_pick_changed")
-        if req is not None:
-            attn["required_pos"], attn["required_moved"] = self._require_place(req, seq, lp, last.contiguous(), -1, ban, no_repeat, repeat_min_id, None)
-        if nbest:
-            attn["nbest_seq"], attn["nbest_logp"], attn["nbest_count"] = self._nbest_list(nbest, B, lp, last.contiguous(), -1, ban, repeat_min=nb_min)
+        self._post_passes(attn, B, seq, lp, last.contiguous, -1, ban, pick_on, req, nbest, nb_min, no_repeat, repeat_min_id, None)
         res = (seq, lp, rnd) if mp else (seq, lp)
         return res + (attn,) if attn else res
 

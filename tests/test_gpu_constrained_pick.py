@@ -1,6 +1,8 @@
 """The constrained pick on the MI355X: the kernel against the numpy restatement (exact), the float32 engine against the restated decode
 (tests/test_constrained_pick.py), the bf16 engine held without a tolerance to ``pick_np`` on its OWN returned log-probs (plain, graph replay, fork, phased form,
 grouped batches), "off is today's decode", the refusals, and the interface above the engine (decode_many, mode='sample', eval_split)."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -105,6 +107,95 @@ def test_kernel_equals_pick_np(B, S, V, ldx):
                 assert np.array_equal(chosen.cpu().numpy().reshape(B, S).view(np.int32), expect.view(np.int32)), what
                 assert np.array_equal(changed.cpu().numpy(), want["changed"]), what
         assert np.array_equal(dx.cpu().numpy().view(np.int32), x.reshape(B * S, ldx).view(np.int32))      # (x is read only)
+
+
+def _plain_rows(rng, B, S, V):
+    """x [B, S, V] float32 for a V below _rows' nine: Gaussian rows, an exact tie at the top of every third row, one NaN and one -inf."""
+    x = rng.standard_normal((B, S, V)).astype(np.float32)
+    flat = x.reshape(B * S, V)
+    for r in range(0, B * S, 3):
+        flat[r, rng.choice(V, 2, replace=False)] = flat[r].max()
+    flat[1, int(rng.integers(0, V))] = NAN
+    flat[B * S - 2, int(rng.integers(0, V))] = -np.inf
+    return x
+
+
+def _short_case(V, B=2, S=8):
+    """(x, n, ntok, ban, old) of the short-row tests here and in test_gpu_trigram_pick: ntok in the engine's form (bias -1), image 1 shorter than S; at most V - 2 ids
+    banned, the best id of row 0 among them."""
+    rng = np.random.default_rng(7700 + V)
+    x = _plain_rows(rng, B, S, V)
+    n = np.array([S, S - 3])
+    best = int(np.argsort(-np.nan_to_num(x[0, 0], nan=np.inf), kind="stable")[0])
+    ban = sorted(([best] + [int(i) for i in rng.permutation(V) if int(i) != best])[:min(V - 2, 2)])
+    old = rng.integers(0, V, (B, S)).astype(np.int64)
+    return x, n, (n + 1).astype(np.int32), ban, old
+
+
+def _at_offset(x2d, off):
+    """x2d [rows, ldx] on the device, its first element ``off`` floats behind a 16-byte boundary."""
+    buf = torch.full((x2d.size + 8,), 7.0, dtype=torch.float32, device="cuda")
+    dx = buf[off:off + x2d.size].view(x2d.shape)
+    dx.copy_(torch.from_numpy(x2d))
+    assert (dx.data_ptr() // 4) % 4 == (buf.data_ptr() // 4 + off) % 4
+    return dx
+
+
+@pytest.mark.parametrize("V", [2, 3, 5, 6])
+def test_kernel_on_rows_shorter_than_a_wavefronts_loads(V):
+    """ldx = V below 8 floats, the tensor 0, 1, 2, 3 floats off a 16-byte boundary: the rows walk through every alignment, so the row stream meets a peel cut short by V,
+    rows without one 16-byte group, peel-only and tail-only rows.  seq, row_chosen and changed bit for bit against pick_np, with the table (an empty one at V = 2) and without."""
+    from boficap_amd import hip
+    B, S = 2, 8
+    x, n, ntok, ban, old = _short_case(V, B, S)
+    d_ntok, d_ban = torch.from_numpy(ntok).cuda(), hip.ban_bits(ban, V, "cuda")
+    runs = [(use_ban, rep, min_id) for use_ban in (True, False) for rep, min_id in ((True, 0), (False, 7))]
+    wants = {r: pick_np(x, n, ban if r[0] else (), r[1], r[2], pad=2, old=old) for r in runs}
+    live = np.arange(S)[None, :] < n[:, None]
+    for off in (0, 1, 2, 3):
+        dx = _at_offset(x.reshape(B * S, V), off)
+        for use_ban, rep, min_id in runs:
+            want, what = wants[(use_ban, rep, min_id)], (V, off, use_ban, rep, min_id)
+            seq = torch.from_numpy(old.copy()).cuda().view(-1)
+            chosen = torch.full((B * S,), KEEP, dtype=torch.float32, device="cuda")
+            changed = torch.full((B,), -1, dtype=torch.int32, device="cuda")
+            hip.vocab_constrain(dx, V, S, seq, ntok=d_ntok, ntok_bias=-1, pad_idx=2, ban=d_ban if use_ban else None, no_repeat=rep, repeat_min_id=min_id,
+                                row_chosen=chosen, changed=changed)
+            torch.cuda.synchronize()
+            assert np.array_equal(seq.cpu().numpy().reshape(B, S), want["seq"]), what
+            expect = np.where(live, want["chosen"], np.float32(KEEP)).astype(np.float32)
+            assert np.array_equal(chosen.cpu().numpy().reshape(B, S).view(np.int32), expect.view(np.int32)), what
+            assert np.array_equal(changed.cpu().numpy(), want["changed"]), what
+
+
+BIG_V = 262177                                 # (V + 31) / 32 = 8 194 words: more than the 8 192 the candidate kernels stage in LDS
+
+
+@functools.lru_cache(maxsize=None)
+def _big_ban_case():
+    """(x [1, 2, BIG_V], ban, old): Gaussian rows; a few thousand ids banned, each row's best id among them."""
+    rng = np.random.default_rng(7800)
+    x = rng.standard_normal((1, 2, BIG_V)).astype(np.float32)
+    ban = sorted(set(rng.choice(BIG_V, 3000, replace=False).tolist()) | {int(x[0, 0].argmax()), int(x[0, 1].argmax())})
+    return x, ban, rng.integers(0, BIG_V, (1, 2)).astype(np.int64)
+
+
+def test_kernel_reads_a_long_ban_table_through_the_cache():
+    """A ban table of 8 194 words is not staged: the candidates launch looks the bits up in global memory.  Bit for bit against pick_np."""
+    from boficap_amd import hip
+    x, ban, old = _big_ban_case()
+    assert (BIG_V + 31) // 32 > 8192
+    want = pick_np(x, [2], ban, True, 7, pad=2, old=old)
+    assert not set(want["seq"].ravel().tolist()) & set(ban) and (want["seq"] != x.argmax(2)).all()
+    dx = torch.from_numpy(x.reshape(2, BIG_V)).cuda()
+    seq = torch.from_numpy(old.copy()).cuda().view(-1)
+    chosen = torch.full((2,), KEEP, dtype=torch.float32, device="cuda")
+    changed = torch.full((1,), -1, dtype=torch.int32, device="cuda")
+    hip.vocab_constrain(dx, BIG_V, 2, seq, pad_idx=2, ban=hip.ban_bits(ban, BIG_V, "cuda"), no_repeat=True, repeat_min_id=7, row_chosen=chosen, changed=changed)
+    torch.cuda.synchronize()
+    assert np.array_equal(seq.cpu().numpy().reshape(1, 2), want["seq"])
+    assert np.array_equal(chosen.cpu().numpy().reshape(1, 2).view(np.int32), want["chosen"].view(np.int32))
+    assert np.array_equal(changed.cpu().numpy(), want["changed"])
 
 
 # ----------------------------------------------------------------------------- 2. the float32 engine against the restated decode

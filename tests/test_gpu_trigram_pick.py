@@ -8,7 +8,7 @@ import torch
 import boficap_oracle as O
 from conftest import record_parity
 from test_constrained_pick import NAN, pick_np, plain_of
-from test_gpu_constrained_pick import KEEP, LAYOUT, _bits, _clone, _rows, _same_bits
+from test_gpu_constrained_pick import BIG_V, KEEP, LAYOUT, _at_offset, _big_ban_case, _bits, _clone, _rows, _same_bits, _short_case
 from test_trigram_pick import FIGURES, adjacent_repeats, pick3_np, repeated_trigrams, restate3
 
 pytestmark = pytest.mark.gpu
@@ -109,6 +109,54 @@ def test_kernel_equals_pick3_np(B, S, V, ldx, kind):
     assert np.array_equal(seq.cpu().numpy().reshape(B, S), pick3_np(x[:, :, :V], np.full(B, S), pad=2)["seq"])
     with pytest.raises(hip.BofiHipError, match="workspace"):
         hip.vocab_pick(dx, V, S, seq, work=torch.empty(work.numel() - 1, dtype=torch.int32, device="cuda"))
+
+
+def _pick_equals(want, live, seq, chosen, changed, what):
+    shape = want["seq"].shape
+    assert np.array_equal(seq.cpu().numpy().reshape(shape), want["seq"]), what
+    expect = np.where(live, want["chosen"], np.float32(KEEP)).astype(np.float32)
+    assert np.array_equal(chosen.cpu().numpy().reshape(shape).view(np.int32), expect.view(np.int32)), what
+    assert np.array_equal(changed.cpu().numpy(), want["changed"]), what
+
+
+@pytest.mark.parametrize("V", [2, 3, 5, 6])
+def test_kernel_on_rows_shorter_than_a_wavefronts_loads(V):
+    """bofi_vocab_pick on test_gpu_constrained_pick's short-row case (ldx = V below 8 floats, every alignment of tensor and rows): seq, row_chosen and changed bit for bit
+    against pick3_np, with the table and without.  (With block_trigrams the word floor stays 7, above every id: at V <= 6 a floor of 0 could leave a position no id.)"""
+    from boficap_amd import hip
+    B, S = 2, 8
+    x, n, ntok, ban, old = _short_case(V, B, S)
+    d_ntok, d_ban = torch.from_numpy(ntok).cuda(), hip.ban_bits(ban, V, "cuda")
+    runs = [(use_ban, tri, min_id) for use_ban in (True, False) for tri, min_id in ((False, 0), (True, 7))]
+    wants = {r: pick3_np(x, n, ban if r[0] else (), True, r[1], r[2], pad=2, old=old) for r in runs}
+    live = np.arange(S)[None, :] < n[:, None]
+    work = torch.empty(hip.lib().bofi_vocab_pick_workspace(B * S) // 4, dtype=torch.int32, device="cuda")
+    for off in (0, 1, 2, 3):
+        dx = _at_offset(x.reshape(B * S, V), off)
+        for use_ban, tri, min_id in runs:
+            seq = torch.from_numpy(old.copy()).cuda().view(-1)
+            chosen = torch.full((B * S,), KEEP, dtype=torch.float32, device="cuda")
+            changed = torch.full((B,), -1, dtype=torch.int32, device="cuda")
+            work.fill_(-7)
+            hip.vocab_pick(dx, V, S, seq, ntok=d_ntok, ntok_bias=-1, pad_idx=2, ban=d_ban if use_ban else None, no_repeat=True, block_trigrams=tri, repeat_min_id=min_id,
+                           row_chosen=chosen, changed=changed, work=work)
+            torch.cuda.synchronize()
+            _pick_equals(wants[(use_ban, tri, min_id)], live, seq, chosen, changed, (V, off, use_ban, tri, min_id))
+
+
+def test_kernel_reads_a_long_ban_table_through_the_cache():
+    """bofi_vocab_pick with a ban table of 8 194 words, more than the 8 192 the candidates launch stages in LDS: bit for bit against pick3_np."""
+    from boficap_amd import hip
+    x, ban, old = _big_ban_case()
+    want = pick3_np(x, [2], ban, True, True, 7, pad=2, old=old)
+    assert not set(want["seq"].ravel().tolist()) & set(ban)
+    dx = torch.from_numpy(x.reshape(2, BIG_V)).cuda()
+    seq = torch.from_numpy(old.copy()).cuda().view(-1)
+    chosen = torch.full((2,), KEEP, dtype=torch.float32, device="cuda")
+    changed = torch.full((1,), -1, dtype=torch.int32, device="cuda")
+    hip.vocab_pick(dx, BIG_V, 2, seq, pad_idx=2, ban=hip.ban_bits(ban, BIG_V, "cuda"), no_repeat=True, block_trigrams=True, repeat_min_id=7, row_chosen=chosen, changed=changed)
+    torch.cuda.synchronize()
+    _pick_equals(want, np.ones((1, 2), bool), seq, chosen, changed, "long ban table")
 
 
 # ----------------------------------------------------------------------------- 2. the float32 engine against the restated decode
