@@ -212,3 +212,222 @@ extern "C" int bofi_vocab_require(const float* x, int ldx, int rows, int V, int 
         return bofi::fail(BOFI_ERR_ARG, std::string("vocab_require: ") + why);
     return bofi::launch_vocab_require(x, ldx, rows, V, S, ntok, ntok_bias, words, K, ban_bits, no_repeat, repeat_min_id, seq, row_chosen, pos, moved, (hipStream_t)stream);
 }
+
+// ---- required PHRASES: units of up to 4 ids placed side by side (include/boficap_hip.h, bofi_vocab_require_units, states the rule; tests/test_required_phrases.py restates
+// it in numpy).  The same shape as above -- a wavefront per image, lanes over the 2^K masks, the state in LDS, float64 totals, a uniform position loop -- with a unit
+// covering a span:
+//   classify     the lanes load the image's [K][L] table into LDS, lane 0 classifies it in order (a unit is skipped against EARLIER units): ln[j] = its length, -1, -2
+//   gather       lane = position reads seq and x[p, seq[p]]; the lanes take the n_b * K * L (position q, unit j, index i) triples, xq[q][j][i] = x[q, u_i] -- scattered
+//                4-byte loads; then the n_b * K (start p, unit j) pairs sum their span's terms left to right in float64 and settle its eligibility
+//   recurrence   p = S - 1 .. 0; best[p][.] lives in buffer p mod (L + 1) of L + 1 rolling ones: "p takes unit j" reads best[p + len_j][.], "p keeps" best[p + 1][.]
+//   walk         lane 0 follows choice, advancing by len_j over a placed span, and writes seq, row_chosen, pos and moved
+namespace {
+
+using namespace bofi;
+
+constexpr int VU_MAX_L = BOFI_REQUIRE_UNIT_MAX;
+static_assert(VU_MAX_L == 4, "the LDS of one image at S = 64, K = 8 is sized for spans of up to 4");
+
+struct VuArgs {
+    const float* x; int ldx, V, S, B;
+    const int* ntok; int ntok_bias;
+    const int* units; int K, L;
+    const uint32_t* ban; int no_repeat, repeat_min_id;
+    int64_t* seq; float* row_chosen; int* pos; int* moved;
+    int per_image;                              // LDS bytes of one image (vu_lds_bytes)
+};
+
+// LDS of one image, in this order (8-byte items first), D = L + 1:
+// tot [D][M] double, gain [S][K] double, xq [S][K][L] float, bvf [S] float, sq [S] int, ut [K][L] int, ln [K] int, cnt [D][M] byte, elig [S][K] byte, choice [S][M] byte
+// (S = 64, K = 8, L = 4: 10240 + 4096 + 8192 + 256 + 256 + 128 + 32 + 1280 + 512 + 16384 = 41376 bytes: one image per workgroup)
+inline size_t vu_lds_bytes(int S, int K, int L) {
+    const size_t M = (size_t)1 << K, SK = (size_t)S * K, D = (size_t)L + 1;
+    const size_t n = D * M * 8 + SK * 8 + SK * L * 4 + (size_t)S * 4 + (size_t)S * 4 + (size_t)K * L * 4 + (size_t)K * 4 + D * M + SK + (size_t)S * M;
+    return (n + 7) & ~(size_t)7;
+}
+
+// grid = ceil(B / waves) workgroups of `waves` wavefronts: wavefront = image
+__global__ void __launch_bounds__(VR_IPW * WAVE) vocab_require_units_kernel(VuArgs a) {
+    extern __shared__ double vu_lds[];
+    const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE, b = blockIdx.x * (blockDim.x / WAVE) + wave;
+    const int S = a.S, K = a.K, L = a.L, D = L + 1, M = 1 << K, V = a.V;
+    const bool on = b < a.B;                                    // (a wavefront past B stays for the barriers and touches no global memory)
+    char* const base = reinterpret_cast<char*>(vu_lds) + (size_t)wave * a.per_image;
+    double* const tot = reinterpret_cast<double*>(base);       // [D][M]
+    double* const gain = tot + D * M;                           // [S][K]     span gain of "unit j starts at p"
+    float* const xq = reinterpret_cast<float*>(gain + S * K);  // [S][K][L]  x[q, u_i of unit j]
+    float* const bvf = xq + S * K * L;                          // [S]        x[p, seq[p]]
+    int* const sq = reinterpret_cast<int*>(bvf + S);           // [S]        seq[p] on entry; -1: an id outside 0..V-1 stands there
+    int* const ut = sq + S;                                     // [K][L]     the image's table as given
+    int* const ln = ut + K * L;                                 // [K]        len_j of a kept unit, -1 empty, -2 skipped
+    uint8_t* const cnt = reinterpret_cast<uint8_t*>(ln + K);   // [D][M]
+    uint8_t* const elig = cnt + D * M;                          // [S][K]
+    uint8_t* const choice = elig + S * K;                       // [S][M]
+
+    const int n = on ? live_count(a.ntok, a.ntok_bias, b, S) : 0;
+    const size_t row0 = (size_t)(on ? b : 0) * S;
+    // the image's table, classified by lane 0
+    for (int t = lane; t < K * L; t += WAVE) ut[t] = on ? a.units[(size_t)b * K * L + t] : -1;
+    __syncthreads();
+    if (lane == 0) {
+        for (int j = 0; j < K; ++j) {
+            const int* const u = ut + j * L;
+            int len = 0;
+            while (len < L && u[len] >= 0) ++len;
+            int c = len ? len : -1;
+            for (int i = 0; i < len; ++i) {
+                const int w = u[i];
+                if (w >= V) c = -2;
+                else if (a.ban && ((a.ban[w >> 5] >> (w & 31)) & 1u)) c = -2;
+            }
+            for (int e = 0; e < j && c > 0; ++e) {              // equal to an earlier unit, kept or not
+                const int* const v = ut + e * L;
+                bool same = true;
+                for (int i = 0; i < L && same; ++i) {
+                    const bool mine = i < len, theirs = v[i] >= 0;
+                    if (mine != theirs || (mine && v[i] != u[i])) same = false;
+                    if (!mine) break;                           // (both ended here)
+                }
+                if (same) c = -2;
+            }
+            if (c > 0 && a.no_repeat) {
+                for (int i = 1; i < len; ++i)
+                    if (u[i] == u[i - 1] && u[i] >= a.repeat_min_id) c = -2;
+                for (int e = 0; e < j; ++e) {
+                    if (ln[e] <= 0) continue;
+                    const int* const v = ut + e * L;
+                    if ((u[0] >= a.repeat_min_id && u[0] == v[ln[e] - 1]) || (u[len - 1] >= a.repeat_min_id && u[len - 1] == v[0])) c = -2;
+                }
+            }
+            ln[j] = c;
+        }
+    }
+    // gather: the ids on entry and their values ...
+    if (lane < n) {
+        const int64_t id = a.seq[row0 + lane];
+        const bool in = id >= 0 && id < (int64_t)V;
+        sq[lane] = in ? (int)id : -1;
+        bvf[lane] = in ? a.x[(row0 + lane) * (size_t)a.ldx + (size_t)id] : NAN;
+    }
+    __syncthreads();
+    // ... the (position, unit, index) triples ...
+    const int KL = K * L;
+    for (int t = lane; t < n * KL; t += WAVE) {
+        const int q = t / KL, r = t - q * KL, j = r / L, i = r - j * L;
+        xq[t] = i < ln[j] ? a.x[(row0 + q) * (size_t)a.ldx + (size_t)ut[r]] : 0.f;
+    }
+    __syncthreads();
+    // ... and the spans
+    for (int t = lane; t < n * K; t += WAVE) {
+        const int p = t / K, j = t - p * K, len = ln[j];
+        double g = 0.0;
+        bool ok = len > 0 && p + len <= n;
+        if (ok) {
+            const int* const u = ut + j * L;
+            for (int i = 0; i < len; ++i) {
+                const int q = p + i;
+                if (sq[q] == u[i]) continue;
+                const float xv = xq[(q * K + j) * L + i], bv = bvf[q];
+                if (f32_finite(xv) && f32_finite(bv)) g += (double)xv - (double)bv;
+                else ok = false;
+            }
+            if (a.no_repeat) {
+                const int u0 = u[0], ul = u[len - 1];
+                if (u0 >= a.repeat_min_id && sq[p] != u0 && p > 0 && sq[p - 1] == u0) ok = false;
+                if (ul >= a.repeat_min_id && sq[p + len - 1] != ul && p + len < n && sq[p + len] == ul) ok = false;
+            }
+        }
+        gain[t] = ok ? g : 0.0; elig[t] = ok ? 1 : 0;
+    }
+    for (int m = lane; m < M; m += WAVE) { tot[(n % D) * M + m] = 0.0; cnt[(n % D) * M + m] = 0; }      // best[n_b][.] = (0 units, 0.0)
+    __syncthreads();
+    // the recurrence, backwards; buffer p mod D holds best[p][.]
+    for (int p = S - 1; p >= 0; --p) {
+        if (p < n) {
+            const int pm = p % D, nx = pm + 1 == D ? 0 : pm + 1;
+            for (int m = lane; m < M; m += WAVE) {
+                int bc = -1, bj = VR_KEEP;
+                double bt = 0.0;
+                for (int j = 0; j < K; ++j) {
+                    if (!((m >> j) & 1) || !elig[p * K + j]) continue;
+                    int s = pm + ln[j];                         // best[p + len_j]: an eligible span ends at or before n_b, and len_j <= L < D
+                    if (s >= D) s -= D;
+                    const int m2 = m ^ (1 << j);
+                    const int c = 1 + (int)cnt[s * M + m2];
+                    const double t = gain[p * K + j] + tot[s * M + m2];
+                    if (c > bc || (c == bc && t > bt)) { bc = c; bt = t; bj = j; }
+                }
+                {
+                    const int c = (int)cnt[nx * M + m];
+                    const double t = tot[nx * M + m];
+                    if (c > bc || (c == bc && t > bt)) { bc = c; bt = t; bj = VR_KEEP; }
+                }
+                tot[pm * M + m] = bt; cnt[pm * M + m] = (uint8_t)bc; choice[p * M + m] = (uint8_t)bj;
+            }
+        }
+        __syncthreads();
+    }
+    // the forward walk
+    if (on && lane == 0) {
+        int m = 0, mv = 0;
+        int* const where = a.pos + (size_t)b * K;
+        for (int j = 0; j < K; ++j) {
+            where[j] = ln[j] > 0 ? -3 : ln[j];
+            if (ln[j] > 0) m |= 1 << j;
+        }
+        for (int p = 0; p < n && m;) {
+            const int c = choice[p * M + m];
+            if (c == VR_KEEP) { ++p; continue; }
+            const int len = ln[c];
+            where[c] = p;
+            for (int i = 0; i < len; ++i) {
+                const int q = p + i, id = ut[c * L + i];
+                if (sq[q] != id) { a.seq[row0 + q] = (int64_t)id; ++mv; }
+                if (a.row_chosen) a.row_chosen[row0 + q] = xq[(q * K + c) * L + i];
+            }
+            m ^= 1 << c;
+            p += len;
+        }
+        if (a.moved) a.moved[b] = mv;
+    }
+}
+
+}  // namespace
+
+const char* bofi::vocab_require_units_check(const float* x, int ldx, int rows, int V, int S, const int* units, int K, int L, int no_repeat, int repeat_min_id,
+                                            const int64_t* seq, const int* pos) {
+    if (!x || !seq || !units || !pos) return "non-null x, seq, units and pos";
+    if (S < 1 || S > VR_MAX_S) return "S in 1..64";
+    if (rows < 0 || rows % S != 0) return "rows a multiple of S (>= 0)";
+    if (V < 2) return "V >= 2";
+    if (ldx < V) return "a row pitch of at least V";
+    if (K < 1 || K > VR_MAX_K) return "K in 1..8 (BOFI_REQUIRE_MAX)";
+    if (L < 1 || L > VU_MAX_L) return "L in 1..4 (BOFI_REQUIRE_UNIT_MAX)";
+    if (no_repeat != 0 && no_repeat != 1) return "no_repeat 0 or 1";
+    if (repeat_min_id < 0) return "repeat_min_id >= 0";
+    return nullptr;
+}
+
+int bofi::launch_vocab_require_units(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, const int* units, int K, int L,
+                                     const uint32_t* ban_bits, int no_repeat, int repeat_min_id, int64_t* seq, float* row_chosen, int* pos, int* moved, hipStream_t st) {
+    if (vocab_require_units_check(x, ldx, rows, V, S, units, K, L, no_repeat, repeat_min_id, seq, pos)) return BOFI_ERR_ARG;
+    if (rows == 0) return BOFI_OK;
+    VuArgs a{};
+    a.x = x; a.ldx = ldx; a.V = V; a.S = S; a.B = rows / S; a.ntok = ntok; a.ntok_bias = ntok_bias; a.units = units; a.K = K; a.L = L; a.ban = ban_bits;
+    a.no_repeat = no_repeat; a.repeat_min_id = repeat_min_id; a.seq = seq; a.row_chosen = row_chosen; a.pos = pos; a.moved = moved;
+    const size_t per = vu_lds_bytes(S, K, L);
+    a.per_image = (int)per;
+    int waves = VR_IPW;
+    while (waves > 1 && waves * per > VR_LDS_MAX) waves /= 2;      // (S = 64, K = 8, L = 4: 40.4 KB an image, one per workgroup)
+    hipLaunchKernelGGL(vocab_require_units_kernel, dim3((a.B + waves - 1) / waves), dim3(waves * WAVE), waves * per, st, a);
+    BOFI_CHECK_LAUNCH();
+    return BOFI_OK;
+}
+
+extern "C" int bofi_vocab_require_units(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, const int* units, int K, int L,
+                                        const uint32_t* ban_bits, int no_repeat, int repeat_min_id, int64_t* seq, float* row_chosen, int* pos, int* moved, void* stream) {
+    if (const char* why = bofi::vocab_require_units_check(x, ldx, rows, V, S, units, K, L, no_repeat, repeat_min_id, seq, pos))
+        return bofi::fail(BOFI_ERR_ARG, std::string("vocab_require_units: ") + why);
+    return bofi::launch_vocab_require_units(x, ldx, rows, V, S, ntok, ntok_bias, units, K, L, ban_bits, no_repeat, repeat_min_id, seq, row_chosen, pos, moved,
+                                            (hipStream_t)stream);
+}

@@ -209,7 +209,7 @@ class BofiEngine:
                     refine_rounds: int = 0, out: Optional[dict] = None, q1_group: int = 0, iter_cap: int = 0, phases: str = "", row_stats: bool = False,
                     ids_only: bool = False, refine_method: str = "feed_back", attn_topk: int = 0, attn_maps: bool = False, attn_heads: bool = False,
                     attn_layer: int = -1, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7, block_trigrams: bool = False, require_ids=None,
-                    nbest: Optional[int] = None, nbest_no_repeat: bool = False) -> dict:
+                    nbest: Optional[int] = None, nbest_no_repeat: bool = False, require_phrases=None) -> dict:
         """Greedy NAIC bound+fill decode.  Returns a dict of device tensors: seq [B,S] int64,
         seq_logprob [B,S,V] float32 (or None), phrase_num [B] int32, phrase_length [B,S] int32,
         phrase_syn [B,S] int64, bound_iters [1] int32, memory [B,R,d] float32 (or None).
@@ -254,6 +254,12 @@ class BofiEngine:
         the emitted ids.  With feed-back refinement rounds the placement applies to the LAST pass only: earlier passes are fed the unforced ids.  In the phased form it
         follows the call whose ``phases`` contain 'f'.  Not with ``ids_only`` (no distribution), ``refine_method='mask_predict'`` or ``block_trigrams`` (a placement
         could create a blocked trigram).  None, an empty list or rows of -1 only: nothing is launched and no key is added.
+        ``require_phrases`` (bofi_vocab_require_units in place of bofi_vocab_require: same placement behind the call, same keys, same refusals; not together with
+        ``require_ids`` -- give one): multi-word UNITS every caption must contain, the ids of a unit side by side and in order -- per image a list of units, each a list of
+        1..4 ids, or one flat list of units for every image (``hip.require_unit_table`` states the forms and what it refuses: among it, under ``no_repeat``, a unit that
+        repeats a word and two units that could meet at a shared word); a device tensor int32 [B, K, L] with -1 padding is passed through as it is.  Each unit goes to the
+        contiguous span where it costs the least log-prob (first as many units as can be placed, then the largest total gain; the header states the rule).
+        ``out['required_pos']`` int32 [B, K] then holds each unit's START position (-1, -2, -3 as above).
         ``nbest`` = N in 1..8 (bofi_vocab_nbest: two small launches on the same stream BEHIND the decode call, outside a ``graph`` replay; no field of the call record):
         the N most probable captions of the last filling pass, exactly -- the pass scores every position on its own, so a caption's log-prob is a sum of per-position
         terms and a width-N merge over each row's N best ids finds the N best captions (the header states the rule, its tie order and what holds under ties).  Read
@@ -270,7 +276,7 @@ class BofiEngine:
         mp = self._refine_flag(refine_method, refine_rounds, raw_logits)
         ban, pick_on, req, nbest, nb_min = self._post_options(
             ban_ids, no_repeat, repeat_min_id, block_trigrams, require_ids, nbest, nbest_no_repeat, att_feats.size(0), ids_only, mp,
-            want_logprob or (out is not None and out.get("seq_logprob") is not None))
+            want_logprob or (out is not None and out.get("seq_logprob") is not None), require_phrases)
         if ids_only:
             if raw_logits:
                 raise hip.BofiHipError("ids_only: the raw logits are not produced")
@@ -331,9 +337,10 @@ class BofiEngine:
                               no_repeat, repeat_min_id, out["row_chosen"] if row_stats else None)
         return out
 
-    def _post_options(self, ban_ids, no_repeat, repeat_min_id, block_trigrams, require_ids, nbest, nbest_no_repeat, B: int, ids_only, mp: int, own_rows: bool):
+    def _post_options(self, ban_ids, no_repeat, repeat_min_id, block_trigrams, require_ids, nbest, nbest_no_repeat, B: int, ids_only, mp: int, own_rows: bool,
+                      require_phrases=None):
         """The options of ``decode_naic`` / ``fill_naic`` whose work follows the call, resolved and refused before anything is enqueued: (ban, pick_on, req, nbest, nb_min)
-        -- the device bit table or None, "the constrained pick is on", the device table of required words or None, the list's width (0: off) and the ``repeat_min_id``
+        -- the device bit table or None, "the constrained pick is on", the device table of required words ([B, K]) or units ([B, K, L]) or None, the list's width (0: off) and the ``repeat_min_id``
         of a repeat-free list (None: the plain list).  ``ids_only`` None: the entry point has no such form (``fill_naic``; its pick refusal comes first, in its own words)."""
         ban = self._pick_ban(ban_ids, block_trigrams)
         pick_on = ban is not None or bool(no_repeat) or bool(block_trigrams)
@@ -342,6 +349,12 @@ class BofiEngine:
         req = self._require_table(require_ids, B, ban_ids)
         if req is not None:
             self._require_refusals(bool(ids_only), mp, block_trigrams)
+        units = self._require_unit_table(require_phrases, B, ban_ids, no_repeat, repeat_min_id)
+        if units is not None:
+            if req is not None:
+                raise hip.BofiHipError("require_ids and require_phrases: give one (single ids are units of length 1)")
+            self._require_refusals(bool(ids_only), mp, block_trigrams, "require_phrases")
+            req = units
         nbest = self._nbest_width(nbest)
         nb_min = self._nbest_no_repeat(nbest, nbest_no_repeat, repeat_min_id)
         if nbest:
@@ -397,7 +410,7 @@ class BofiEngine:
             raise hip.BofiHipError("nbest: not with no_repeat / block_trigrams (the N best under a rule that couples neighbours need per-last-id state: "
                                    "a width-N list is no longer exact); nbest_no_repeat=True lists the repeat-free captions beside the plain decode")
         if required:
-            raise hip.BofiHipError("nbest: not with require_ids (the list is of unforced captions)")
+            raise hip.BofiHipError("nbest: not with require_ids / require_phrases (the list is of unforced captions)")
         if not own_rows and not self._lib.bofi_engine_logprob(self._h):
             raise hip.BofiHipError("nbest: this engine keeps no log-prob workspace (an ids-only fork): there are no rows to list from")
 
@@ -438,21 +451,34 @@ class BofiEngine:
         t = hip.require_table(require_ids, B, self.cfg.tgt_vocab, ban_ids or ())
         return None if t is None else t.to(self.device)
 
+    def _require_unit_table(self, require_phrases, B: int, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7):
+        """``require_phrases`` of a decode as the device table int32 [B, K, L] of bofi_vocab_require_units, None when nothing is required.  Host input goes through
+        ``hip.require_unit_table`` (BofiHipError for what it refuses); a device tensor is passed through -- the kernel is total."""
+        if isinstance(require_phrases, torch.Tensor) and require_phrases.is_cuda:
+            t = require_phrases
+            if t.dim() != 3 or t.size(0) != B or not 1 <= t.size(1) <= hip.REQUIRE_MAX or not 1 <= t.size(2) <= hip.REQUIRE_UNIT_MAX:
+                raise hip.BofiHipError(f"require_phrases: a device table is [B, K, L] with 1 <= K <= {hip.REQUIRE_MAX} and 1 <= L <= {hip.REQUIRE_UNIT_MAX}, "
+                                       f"got {tuple(t.shape)} for {B} images")
+            return t.to(torch.int32).contiguous()
+        t = hip.require_unit_table(require_phrases, B, self.cfg.tgt_vocab, ban_ids or (), bool(no_repeat), int(repeat_min_id))
+        return None if t is None else t.to(self.device)
+
     @staticmethod
-    def _require_refusals(ids_only: bool, mp: int, block_trigrams: bool) -> None:
+    def _require_refusals(ids_only: bool, mp: int, block_trigrams: bool, what: str = "require_ids") -> None:
         if ids_only:
-            raise hip.BofiHipError("require_ids: not with ids_only (no distribution to place the words by)")
+            raise hip.BofiHipError(f"{what}: not with ids_only (no distribution to place the words by)")
         if mp:
-            raise hip.BofiHipError("require_ids: not with refine_method='mask_predict'")
+            raise hip.BofiHipError(f"{what}: not with refine_method='mask_predict'")
         if block_trigrams:
-            raise hip.BofiHipError("require_ids: not with block_trigrams (a placement could create a blocked trigram)")
+            raise hip.BofiHipError(f"{what}: not with block_trigrams (a placement could create a blocked trigram)")
 
     def _require_place(self, req, seq, lp, ntok, ntok_bias, ban, no_repeat, repeat_min_id, row_chosen, pos=None, moved=None):
-        """Enqueue bofi_vocab_require on the current stream behind a decode: ``req`` int32 [B, K] on the device, ``lp`` the decode's log-prob (or logit) tensor or None
+        """Enqueue bofi_vocab_require -- bofi_vocab_require_units for a unit table -- on the current stream behind a decode: ``req`` int32 [B, K] (words) or [B, K, L]
+        (units) on the device, ``lp`` the decode's log-prob (or logit) tensor or None
         for the engine's own workspace.  Returns (pos int32 [B, K], moved int32 [B]); the buffers given are reused when they fit."""
         if int(repeat_min_id) < 0:
             raise hip.BofiHipError("repeat_min_id must be >= 0")
-        B, K = req.shape
+        B, K = req.shape[:2]
         S, V = self.cfg.seq_length, self.cfg.tgt_vocab
         if pos is None or tuple(pos.shape) != (B, K):
             pos = torch.empty(B, K, dtype=torch.int32, device=seq.device)
@@ -460,7 +486,12 @@ class BofiEngine:
             moved = torch.empty(B, dtype=torch.int32, device=seq.device)
         src = hip.ptr(lp) if lp is not None else self._lib.bofi_engine_logprob(self._h)
         if not src:
-            raise hip.BofiHipError("require_ids: this engine keeps no log-prob workspace (an ids-only fork)")
+            raise hip.BofiHipError("require_ids / require_phrases: this engine keeps no log-prob workspace (an ids-only fork)")
+        if req.dim() == 3:
+            hip.check(self._lib.bofi_vocab_require_units(src, V, B * S, V, S, hip.ptr(ntok), int(ntok_bias), hip.ptr(req), K, req.size(2), hip.ptr(ban),
+                                                         1 if no_repeat else 0, int(repeat_min_id), hip.ptr(seq), hip.ptr(row_chosen), hip.ptr(pos), hip.ptr(moved),
+                                                         hip.stream_ptr()), "bofi_vocab_require_units")
+            return pos, moved
         hip.check(self._lib.bofi_vocab_require(src, V, B * S, V, S, hip.ptr(ntok), int(ntok_bias), hip.ptr(req), K, hip.ptr(ban), 1 if no_repeat else 0,
                                                int(repeat_min_id), hip.ptr(seq), hip.ptr(row_chosen), hip.ptr(pos), hip.ptr(moved), hip.stream_ptr()),
                   "bofi_vocab_require")
@@ -703,18 +734,20 @@ class BofiEngine:
     def fill_naic(self, ext_syn: torch.Tensor, last: torch.Tensor, R: int, att_len: Optional[torch.Tensor] = None, *, strict_q1: bool = True,
                   raw_logits: bool = False, refine_rounds: int = 0, refine_method: str = "feed_back", attn_topk: int = 0, attn_maps: bool = False,
                   attn_heads: bool = False, attn_layer: int = -1, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7, block_trigrams: bool = False,
-                  require_ids=None, nbest: Optional[int] = None, nbest_no_repeat: bool = False):
+                  require_ids=None, nbest: Optional[int] = None, nbest_no_repeat: bool = False, require_phrases=None):
         """The filling pass alone on a given slot layout (``ext_syn`` int32 [B, S+2], ``last`` int32 [B]) and the memory of the
         preceding ``encode``: (seq int64 [B, S], seq_logprob float32 [B, S, V]); with ``refine_method='mask_predict'`` (as ``decode_naic``) a third
         element, refine_round int32 [B, S].  With ``attn_topk`` / ``attn_maps`` / ``attn_heads`` (as ``decode_naic``) a last element, a dict of the attention tensors
         ('attn', 'attn_heads', 'attn_top', 'attn_top_w': those asked for).  ``ban_ids`` / ``no_repeat`` / ``repeat_min_id`` / ``block_trigrams`` as ``decode_naic``: that dict (the last element)
         then carries 'constrained', int32 [B].  ``require_ids`` as ``decode_naic`` (bofi_vocab_require behind the call, on the last pass; the same refusals): that dict
-        then carries 'required_pos' int32 [B, K] and 'required_moved' int32 [B].  ``nbest`` as ``decode_naic`` (bofi_vocab_nbest behind the call, on the last pass; the
+        then carries 'required_pos' int32 [B, K] and 'required_moved' int32 [B]; ``require_phrases`` as ``decode_naic`` (bofi_vocab_require_units in its place, the
+        same keys).  ``nbest`` as ``decode_naic`` (bofi_vocab_nbest behind the call, on the last pass; the
         same refusals): that dict then carries 'nbest_seq' int64 [B, N, S], 'nbest_logp' float64 [B, N] and 'nbest_count' int32 [B]; ``nbest_no_repeat`` as
         ``decode_naic`` (bofi_vocab_nbest_norepeat in its place, N <= 6)."""
         mp = self._refine_flag(refine_method, refine_rounds, raw_logits)
         B = ext_syn.size(0)
-        ban, pick_on, req, nbest, nb_min = self._post_options(ban_ids, no_repeat, repeat_min_id, block_trigrams, require_ids, nbest, nbest_no_repeat, B, None, mp, True)
+        ban, pick_on, req, nbest, nb_min = self._post_options(ban_ids, no_repeat, repeat_min_id, block_trigrams, require_ids, nbest, nbest_no_repeat, B, None, mp, True,
+                                                               require_phrases)
         if ext_syn.dtype != torch.int32 or last.dtype != torch.int32 or ext_syn.size(1) != self.cfg.bound_len or last.numel() != B:
             raise hip.BofiHipError("ext_syn must be int32 [B, S+2] and last int32 [B]")
         S, V, dev = self.cfg.seq_length, self.cfg.tgt_vocab, ext_syn.device
@@ -753,7 +786,7 @@ class DecodePipeline:
     def __init__(self, engine: "BofiEngine", *, in_flight: Optional[int] = None, batches_per_launch: int = 16, strict_q1: bool = True, stats: bool = True,
                  keep_logprob: bool = False, region_buckets=(36, 48, 64, 80, 100, 128), fused_vocab: bool = False,
                  refine_rounds: int = 0, refine_method: str = "feed_back", attn_topk: int = 0, keep_attn: bool = False, ban_ids=None, no_repeat: bool = False,
-                 repeat_min_id: int = 7, block_trigrams: bool = False, require_ids=None):
+                 repeat_min_id: int = 7, block_trigrams: bool = False, require_ids=None, require_phrases=None):
         BofiEngine._refine_flag(refine_method, refine_rounds, False)
         # ban_ids / no_repeat / repeat_min_id / block_trigrams: the constrained pick of BofiEngine.decode_naic on every launch; every yielded dict then carries constrained int32 [b].  Not
         # with fused_vocab (ids-only launches keep no distribution to re-pick from) or 'mask_predict'
@@ -774,6 +807,10 @@ class DecodePipeline:
         self.fused_vocab, self.refine_method, self.root_vocab = bool(fused_vocab), refine_method, engine.cfg.tgt_vocab
         self.require_ids = require_ids
         self._require_split(require_ids)
+        # require_phrases: required multi-word units (BofiEngine.decode_naic(require_phrases=...)), in the same two forms and under the same refusals; not with require_ids
+        self.require_phrases = require_phrases
+        self._require_both(require_ids, require_phrases)
+        self._phrase_split(require_phrases)
         # attn_topk = K > 0: every yielded dict carries attn_top int32 / attn_top_w float32 [b, S, K] -- each position's K heaviest regions (BofiEngine.decode_naic) -- on the
         # host, through the pinned buffers (rows x S x K x 8 bytes per launch); keep_attn: also attn [b, S, R of the launch's region bucket] on the device, as keep_logprob
         if not 0 <= int(attn_topk) <= 8:
@@ -835,9 +872,49 @@ class DecodePipeline:
             return (None, None) if flat is None else ([int(i) for i in flat[0]], None)
         return None, iter(require_ids)
 
+    @staticmethod
+    def _require_both(require_ids, require_phrases) -> None:
+        on = lambda v: v is not None and not (hasattr(v, "__len__") and len(v) == 0)
+        if on(require_ids) and on(require_phrases):
+            raise hip.BofiHipError("require_ids and require_phrases: give one (single ids are units of length 1)")
+
+    def _phrase_split(self, require_phrases):
+        """``require_phrases`` of a run as (flat, per_batch): one flat list of units for every image, or an iterator of per-batch tables aligned with the batches; (None,
+        None) when off.  The refusals are those of required words, raised here."""
+        if require_phrases is None:
+            return None, None
+        import numpy as np
+        if isinstance(require_phrases, (torch.Tensor, np.ndarray)):
+            raise hip.BofiHipError("require_phrases: a pipeline takes one flat list of units for every image or a sequence of per-batch tables")
+        seq = require_phrases if hasattr(require_phrases, "__len__") else None
+        if seq is not None and len(seq) == 0:
+            return None, None
+        if self.fused_vocab:
+            raise hip.BofiHipError("require_phrases: not with fused_vocab (the ids-only launches keep no distribution to place the words by)")
+        if self.refine_method == "mask_predict":
+            raise hip.BofiHipError("require_phrases: not with refine_method='mask_predict'")
+        if self.block_trigrams:
+            raise hip.BofiHipError("require_phrases: not with block_trigrams (a placement could create a blocked trigram)")
+        if seq is not None and any(isinstance(u, (int, np.integer)) for u in seq):
+            raise hip.BofiHipError("require_phrases: a unit is a list of ids -- [[3, 4]] is one unit of two ids; for single ids give require_ids")
+        if seq is not None and any(isinstance(u, (list, tuple)) and len(u) and isinstance(u[0], (int, np.integer)) for u in seq):
+            flat = hip.require_unit_table(list(seq), 1, self.root_vocab, self.ban_ids, self.no_repeat, self.repeat_min_id)      # (checked once, here)
+            return (None, None) if flat is None else ([[int(i) for i in u if i >= 0] for u in flat[0].tolist()], None)
+        return None, iter(require_phrases)
+
     def _require_launch(self, group, b):
         """The [rows, K] host table of a launch from its batches' tables (each checked on the host by ``hip.require_table``), and every batch's own K (0: none); (None,
         ks) when no batch of the launch requires a word."""
+        if any(len(g) > 3 and g[3] for g in group):             # units: a [rows, K, L] table, every batch checked by ``hip.require_unit_table``
+            tabs = [hip.require_unit_table(g[2], b, self.root_vocab, self.ban_ids, self.no_repeat, self.repeat_min_id) if g[2] is not None else None for g in group]
+            ks = [0 if t is None else t.size(1) for t in tabs]
+            if max(ks) == 0:
+                return None, ks
+            full = torch.full((len(group) * b, max(ks), max(t.size(2) for t in tabs if t is not None)), -1, dtype=torch.int32)
+            for i, t in enumerate(tabs):
+                if t is not None:
+                    full[i * b:(i + 1) * b, :t.size(1), :t.size(2)] = t
+            return full, ks
         tabs = [hip.require_table(g[2], b, self.root_vocab, self.ban_ids) if len(g) > 2 and g[2] is not None else None for g in group]
         ks = [0 if t is None else t.size(1) for t in tabs]
         K = max(ks)
@@ -864,7 +941,7 @@ class DecodePipeline:
                 return b
         raise hip.BofiHipError(f"{r} regions exceed the engine's max_regions={self.root.max_regions}")
 
-    def run(self, batches, require_ids=None):
+    def run(self, batches, require_ids=None, require_phrases=None):
         """``batches``: iterable of ``att_feats`` or ``(att_feats, att_len)``: [b, R, F] tensors / arrays in the engine's compute dtype or float32, on
         the host (pinned: the copy is asynchronous) or the device; ``att_len`` int32 [b] region counts or None (every image has R regions).  An item may
         also be a ``features.RaggedBatch``: its real rows alone are copied, in the files' dtype, and ``bofi_pack_regions`` pads them to the region bucket
@@ -875,11 +952,21 @@ class DecodePipeline:
         per-batch tables aligned with ``batches`` (each a [b, K] int table, a list of b id lists, one flat list for the batch, or None); a launch that carries several
         batches concatenates their tables, and every batch's result is its own ``decode_naic(require_ids=...)``: its dict carries required_pos int32 [b, K of the batch]
         and required_moved int32 [b] (no keys for a batch that requires nothing).  Not with ``fused_vocab``, 'mask_predict' or ``block_trigrams``: raised here, before
-        anything is launched."""
-        flat, per_batch = self._require_split(self.require_ids if require_ids is None else require_ids)
+        anything is launched.
+        ``require_phrases`` (default: the constructor's): required multi-word units, as ``BofiEngine.decode_naic(require_phrases=...)`` places them, in the same two
+        forms -- one flat list of units (each a list of 1..4 ids) for every image, or a sequence of per-batch tables aligned with ``batches`` (each a list of b unit lists,
+        one flat list of units for the batch, a [b, K, L] int table, or None) --, with the same keys (required_pos holds the units' start positions) and refusals.  Not
+        together with ``require_ids``: give one."""
+        if require_ids is None and require_phrases is None:
+            require_ids, require_phrases = self.require_ids, self.require_phrases
+        self._require_both(require_ids, require_phrases)
+        flat, per_batch = self._require_split(require_ids)
+        if flat is None and per_batch is None:
+            flat, per_batch = self._phrase_split(require_phrases)
+            return self._run(batches, flat, per_batch, flat is not None or per_batch is not None)
         return self._run(batches, flat, per_batch)
 
-    def _run(self, batches, req_flat, req_iter):
+    def _run(self, batches, req_flat, req_iter, units: bool = False):
         from .features import RaggedBatch
         pending = []                                             # launches in flight: (slot, [batch sizes])
         group, gkey = [], None
@@ -903,13 +990,13 @@ class DecodePipeline:
                 try:
                     req = next(req_iter)
                 except StopIteration:
-                    raise hip.BofiHipError("require_ids: fewer per-batch tables than batches") from None
+                    raise hip.BofiHipError("require_ids / require_phrases: fewer per-batch tables than batches") from None
             if isinstance(item, RaggedBatch):
                 r = self._bucket(item.max_len)
                 key = (item.B, r, item.out_F, self.root.dtype, item.equal_lengths and item.max_len == r)
                 if group and (key != gkey or len(group) >= self.bpl):
                     yield from flush()
-                group.append((item, None, req))
+                group.append((item, None, req, units))
                 gkey = key
                 continue
             att, lens = item if isinstance(item, (tuple, list)) else (item, None)
@@ -919,7 +1006,7 @@ class DecodePipeline:
             key = (b, r if lens is None else self._bucket(r), self._width(att.shape[2]), att.dtype, lens is None)
             if group and (key != gkey or len(group) >= self.bpl):
                 yield from flush()
-            group.append((att, lens, req))
+            group.append((att, lens, req, units))
             gkey = key
         yield from flush()
         while pending:
@@ -947,7 +1034,7 @@ class DecodePipeline:
             feats, lens = buf[:rows], (sl["lens"][p][:rows] if has_len else None)
             cs.wait_event(sl["done"])                            # the launch that last read this slot's buffers is through (it was finished before this one is issued)
             staged = self._stage_ragged(sl, p, group)
-            for i, (att, ln, _) in enumerate(group):
+            for i, (att, ln, *_) in enumerate(group):
                 if i in staged:                                  # a RaggedBatch: its rows and offsets to the slot's staging buffer, the padding made on the device
                     srows, soffs = staged[i][:2]
                     srows.copy_(att.rows, non_blocking=True)
@@ -1018,7 +1105,7 @@ class DecodePipeline:
                                   q1_group=b if nb > 1 else 0, row_stats=self.stats, want_logprob=self.keep_logprob, ids_only=self.fused_vocab,
                                   refine_rounds=self.refine_rounds, refine_method=self.refine_method, attn_topk=self.attn_topk, attn_maps=self.keep_attn,
                                   ban_ids=self.ban_ids or None, no_repeat=self.no_repeat, repeat_min_id=self.repeat_min_id, block_trigrams=self.block_trigrams,
-                                  require_ids=sl.get("req"))
+                                  **({} if sl.get("req") is None else {"require_phrases" if sl["req"].dim() == 3 else "require_ids": sl["req"]}))
         out = sl["out"]
         small = {k2: out[k2] for k2 in ("seq", "phrase_num", "phrase_length", "phrase_syn", "bound_saturated")}
         if self.refine_method == "mask_predict":

@@ -323,7 +323,12 @@ def required_of(eval_kwargs, vocab, keys, mode: str = "NAIC", sample_n: int = 1,
     word list; ``keys``: the images' keys in order, matched as they are or as strings) as (ids, words): per image the id list ``decode_many(require_ids=...)`` takes
     and the words it stands for, duplicates dropped; None when no image requires a word.  Words resolve through ``vocab`` ({str(id): word}; the lowest id of a word):
     a word it does not hold is a ValueError that names it, as are more than 8 words for an image, a word that is also banned, and the options required words cannot
-    go with (``require_refusals``)."""
+    go with (``require_refusals``).
+    An item that contains a space is a PHRASE ('fire hydrant'): its words resolve one by one (an unknown one is the ValueError, naming that word), at most 4 of them --
+    unless the vocabulary holds the whole item as one entry, which wins over splitting.  If any image has a phrase the whole evaluation goes through
+    ``decode_many(require_phrases=...)``: every entry of ``ids`` is then a list of UNITS (id lists; a single word is a unit of length 1) -- ``required_phrases(ids)`` tells
+    the two apart; under ``decoding_constraint`` a phrase that repeats a word and two items that could meet at a shared word are a ValueError naming them.  Without a
+    phrase nothing changes."""
     spec = eval_kwargs.get("require_words")
     if not spec:
         return None
@@ -348,25 +353,47 @@ def required_of(eval_kwargs, vocab, keys, mode: str = "NAIC", sample_n: int = 1,
     ids, words = [], []
     for ws in per_image:
         ws = list(dict.fromkeys(ws))
+        units = []
         for w in ws:
-            if w not in id_of:
-                raise ValueError(f"require_words: the vocabulary does not hold {w!r}")
-            if id_of[w] in ban:
-                raise ValueError(f"require_words: {w!r} is also banned (suppress_UNK / ban_words)")
+            parts = [w] if w in id_of else w.split()           # (a vocabulary entry that equals the whole item wins over splitting)
+            for q in parts:
+                if q not in id_of:
+                    raise ValueError(f"require_words: the vocabulary does not hold {q!r}")
+                if id_of[q] in ban:
+                    raise ValueError(f"require_words: {q!r} is also banned (suppress_UNK / ban_words)")
+            if not 1 <= len(parts) <= 4:
+                raise ValueError(f"require_words: a phrase holds 1 to 4 words, got {w!r}")
+            units.append([id_of[q] for q in parts])
         if len(ws) > 8:
             raise ValueError(f"require_words: at most 8 required words per image, got {len(ws)}")
-        ids.append([id_of[w] for w in ws])
+        ids.append(units)
         words.append(ws)
+    if not any(len(u) > 1 for units in ids for u in units):     # no phrase anywhere: single ids, as ever
+        ids = [[u[0] for u in units] for units in ids]
+    elif int(eval_kwargs.get("decoding_constraint", 0) or 0) == 1:      # what hip.require_unit_table refuses under no_repeat, said here in the items' words before anything is launched
+        for units, ws in zip(ids, words):
+            for a, u in enumerate(units):
+                if any(x == y and x >= 7 for x, y in zip(u, u[1:])):
+                    raise ValueError(f"require_words: {ws[a]!r} repeats a word (not under decoding_constraint)")
+                for b in range(a):
+                    v = units[b]
+                    if (v[-1] == u[0] and u[0] >= 7) or (u[-1] == v[0] and v[0] >= 7):
+                        raise ValueError(f"require_words: {ws[b]!r} and {ws[a]!r} could meet at a shared word and form an adjacent repeat (not under decoding_constraint)")
     return ids, words
 
 
+def required_phrases(ids) -> bool:
+    """Whether the ``ids`` of ``required_of`` are lists of units (some image has a phrase) and go through ``require_phrases``."""
+    return any(isinstance(u, list) for units in ids for u in units)
+
+
 def required_entry(words, pos_row):
-    """The 'required' field of a prediction entry: [word, position] per required word of the image, position None where the word could not be placed."""
+    """The 'required' field of a prediction entry: [word or phrase, (start) position] per required item of the image, position None where it could not be placed."""
     return [[w, (int(p) if int(p) >= 0 else None)] for w, p in zip(words, pos_row[:len(words)].tolist())] if words else []
 
 
 def required_rates(words, pos_rows, moved: int, emitted: int) -> dict:
-    """required_rate = words placed / words required, required_moved_rate = positions whose id the placement changed / positions emitted."""
+    """required_rate = words (units, where phrases are required) placed / required, required_moved_rate = positions whose id the placement changed / positions emitted."""
     asked = sum(len(w) for w in words)
     placed = sum(sum(1 for p in row[:len(w)].tolist() if int(p) >= 0) for w, row in zip(words, pos_rows) if w)
     return {"required_rate": placed / max(1, asked), "required_moved_rate": moved / max(1, emitted)}
@@ -393,7 +420,7 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
     # suppress_UNK / decoding_constraint / ban_words / block_trigrams: the constrained pick (constraint_of); with language stats, constrained_rate = changed / emitted positions
     pick = constraint_of(kw, kw.get("vocab") or getattr(model, "vocab", None), mode, sample_n)
     refine.update(pick)
-    # require_words: required words (required_of) -- per-batch tables to decode_many; the predictions gain 'required' ([word, position or None] per word), the stats
+    # require_words: required words and phrases (required_of) -- per-batch tables to decode_many (require_phrases when some image has a phrase); the predictions gain 'required' ([word, position or None] per word), the stats
     # required_rate and required_moved_rate (a dict of these two alone when no language scores were asked for).  Image keys: eval_kwargs['image_keys'], else 0 .. N - 1
     keys = kw.get("image_keys")
     required = required_of(kw, kw.get("vocab") or getattr(model, "vocab", None), list(keys) if keys is not None else list(range(len(feats))), mode, sample_n,
@@ -421,7 +448,7 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
         ragged = is_region_source(feats)
         host = feats if ragged else _torch_feats(feats)
         if required is not None:
-            refine["require_ids"] = [required[0][j:j + batch_size] for j in range(0, N, batch_size)]
+            refine["require_phrases" if required_phrases(required[0]) else "require_ids"] = [required[0][j:j + batch_size] for j in range(0, N, batch_size)]
         with torch.no_grad():
             if mode == "NAIC" and ragged:                       # staged ragged batch by batch, ahead of the launches that consume them
                 for r in model.decode_many((feats.ragged(j, min(j + batch_size, N)) for j in range(0, N, batch_size)), batches_per_launch=int(kw.get("batches_per_launch", 16)),

@@ -24,6 +24,7 @@ FLAG_PICK_TRIGRAMS = 32768
 FORK_IDS_ONLY = 1
 ABI_VERSION = 5
 REQUIRE_MAX = 8                     # BOFI_REQUIRE_MAX: required words per image (bofi_vocab_require)
+REQUIRE_UNIT_MAX = 4                # BOFI_REQUIRE_UNIT_MAX: ids per required unit (bofi_vocab_require_units)
 NBEST_MAX = 8                       # BOFI_NBEST_MAX: captions per image of bofi_vocab_nbest
 NBEST_NR_MAX = 6                    # BOFI_NBEST_NR_MAX: ... of bofi_vocab_nbest_norepeat (its N + 2 candidates per row are the candidates launch's 8)
 
@@ -141,6 +142,7 @@ SIGNATURES = {
     "bofi_vocab_pick_workspace": (_I64, [_I]),
     "bofi_vocab_pick": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _I64, _P]),
     "bofi_vocab_require": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "bofi_vocab_require_units": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "bofi_vocab_nbest_workspace": (_I64, [_I]),
     "bofi_vocab_nbest": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _I64, _P]),
     "bofi_vocab_nbest_norepeat": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I64, _P]),
@@ -420,6 +422,104 @@ def vocab_require(x, V, S, seq, words, pos, *, ntok=None, ntok_bias=0, ban=None,
             raise BofiHipError(f"vocab_require: {name} must be a contiguous {dt} device tensor of {n} elements")
     check(lib().bofi_vocab_require(ptr(x), x.stride(0), rows, int(V), int(S), ptr(ntok), int(ntok_bias), ptr(words), int(K), ptr(ban), 1 if no_repeat else 0,
                                    int(repeat_min_id), ptr(seq), ptr(row_chosen), ptr(pos), ptr(moved), stream_ptr()), "bofi_vocab_require")
+
+
+def _units_meet(a, b, min_id: int) -> bool:
+    """Two required units could meet and form an adjacent repeat of a word: the last id of one is the first id of the other."""
+    return (a[-1] == b[0] and a[-1] >= min_id) or (b[-1] == a[0] and b[-1] >= min_id)
+
+
+def require_unit_table(require_phrases, B: int, V: int, ban_ids=(), no_repeat: bool = False, repeat_min_id: int = 7):
+    """The [B, K, L] int32 unit table of ``bofi_vocab_require_units`` (host tensor, -1 padding) from host-side input: per image a list of units, each a list of 1 ..
+    ``REQUIRE_UNIT_MAX`` ids, or one flat list of units applied to every image.  None when nothing is required (no input, empty lists).
+    Checked here, each refusal naming the offender: ids in 0..V-1, units of at most ``REQUIRE_UNIT_MAX`` ids, at most ``REQUIRE_MAX`` units per image, no id of
+    ``ban_ids``; under ``no_repeat`` no unit with two equal adjacent words (ids >= ``repeat_min_id``) and no two units of an image that could meet at a shared word (the
+    last id of one is the first of the other: the kernel would skip the later one).  Empty units and a repeated unit within an image are dropped."""
+    import numpy as np
+    import torch
+    if require_phrases is None:
+        return None
+    if isinstance(require_phrases, torch.Tensor):
+        require_phrases = require_phrases.cpu().numpy()
+    if isinstance(require_phrases, np.ndarray):                  # a [B, K, L] table (or [K, L] for every image) with -1 padding: a unit is its leading run of ids
+        if require_phrases.ndim not in (2, 3):
+            raise BofiHipError("require_phrases: a [B, K, L] table, per image a list of units (each a list of ids), or one flat list of units")
+        run = lambda u: u[:next((i for i, v in enumerate(u) if v == -1), len(u))]
+        units_of = lambda r: [run(u) for u in r if run(u)]
+        require_phrases = units_of(require_phrases.tolist()) if require_phrases.ndim == 2 else [units_of(r) for r in require_phrases.tolist()]
+    rows = list(require_phrases)
+    if any(isinstance(u, (int, np.integer)) for u in rows):
+        raise BofiHipError("require_phrases: a unit is a list of ids -- [[3, 4]] is one unit of two ids; for single ids give require_ids")
+    if any(u is not None and len(u) and isinstance(u[0], (int, np.integer)) for u in rows):
+        rows = [rows] * B                                        # one flat list of units: every image
+    if not rows:
+        return None
+    if len(rows) != B:
+        raise BofiHipError(f"require_phrases: {len(rows)} rows for {B} images")
+    ban = {int(i) for i in ban_ids or ()}
+    clean = []
+    for r in rows:
+        units = []
+        for u in (r if r is not None else ()):
+            if isinstance(u, (int, np.integer)):
+                raise BofiHipError(f"require_phrases: a unit is a list of ids, got the bare id {int(u)}")
+            if any(not isinstance(i, (int, np.integer)) for i in u):
+                raise BofiHipError(f"require_phrases: a unit is a list of ids, got {list(u)}")
+            u = [int(i) for i in u]
+            if not u:
+                continue
+            if len(u) > REQUIRE_UNIT_MAX:
+                raise BofiHipError(f"require_phrases: a unit holds at most {REQUIRE_UNIT_MAX} ids, got {u}")
+            for i in u:
+                if not 0 <= i < V:
+                    raise BofiHipError(f"require_phrases: ids must lie in 0..{V - 1}, got {i} in unit {u}")
+                if i in ban:
+                    raise BofiHipError(f"require_phrases: id {i} of unit {u} is also in ban_ids")
+            if no_repeat and any(x == y and x >= repeat_min_id for x, y in zip(u, u[1:])):
+                raise BofiHipError(f"require_phrases: unit {u} repeats a word (not under no_repeat)")
+            if u in units:
+                continue
+            if no_repeat:
+                for v in units:
+                    if _units_meet(v, u, int(repeat_min_id)):
+                        raise BofiHipError(f"require_phrases: units {v} and {u} could meet at a shared word and form an adjacent repeat (not under no_repeat)")
+            units.append(u)
+        if len(units) > REQUIRE_MAX:
+            raise BofiHipError(f"require_phrases: at most {REQUIRE_MAX} required units per image, got {len(units)}")
+        clean.append(units)
+    K = max(len(r) for r in clean)
+    if K == 0:
+        return None
+    L = max(len(u) for r in clean for u in r)
+    t = np.full((B, K, L), -1, np.int32)
+    for b, r in enumerate(clean):
+        for j, u in enumerate(r):
+            t[b, j, :len(u)] = u
+    return torch.from_numpy(t)
+
+
+def vocab_require_units(x, V, S, seq, units, pos, *, ntok=None, ntok_bias=0, ban=None, no_repeat=False, repeat_min_id=7, row_chosen=None, moved=None):
+    """``bofi_vocab_require_units`` on torch tensors: as ``vocab_require`` with units int32 [rows / S, K, L] (1 <= K <= ``REQUIRE_MAX``, 1 <= L <= ``REQUIRE_UNIT_MAX``)
+    in place of the words and pos int32 [rows / S, K] the units' start positions.  One launch on the current stream, no synchronisation."""
+    import torch
+    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or not x.is_cuda:
+        raise BofiHipError("vocab_require_units: x must be a 2-d float32 device tensor with unit column stride")
+    rows = x.size(0)
+    if x.size(1) < V or S < 1 or rows % S:
+        raise BofiHipError("vocab_require_units: x needs V columns and a multiple of S rows")
+    B = rows // S
+    if units is None or units.dim() != 3 or units.size(0) != B:
+        raise BofiHipError(f"vocab_require_units: units must be int32 [{B}, K, L]")
+    K, L = units.size(1), units.size(2)
+    for name, t, dt, n in (("seq", seq, torch.int64, rows), ("units", units, torch.int32, B * K * L), ("pos", pos, torch.int32, B * K), ("ntok", ntok, torch.int32, B),
+                           ("ban", ban, torch.int32, (V + 31) // 32), ("row_chosen", row_chosen, torch.float32, rows), ("moved", moved, torch.int32, B)):
+        if t is None and name not in ("seq", "units", "pos"):
+            continue
+        if t is None or t.dtype != dt or t.numel() != n or not t.is_cuda or not t.is_contiguous():
+            raise BofiHipError(f"vocab_require_units: {name} must be a contiguous {dt} device tensor of {n} elements")
+    check(lib().bofi_vocab_require_units(ptr(x), x.stride(0), rows, int(V), int(S), ptr(ntok), int(ntok_bias), ptr(units), int(K), int(L), ptr(ban),
+                                         1 if no_repeat else 0, int(repeat_min_id), ptr(seq), ptr(row_chosen), ptr(pos), ptr(moved), stream_ptr()),
+          "bofi_vocab_require_units")
 
 
 def vocab_nbest(x, V, S, N, *, ntok=None, ntok_bias=0, pad_idx=0, ban=None, seq_n=None, total=None, count=None, work=None):

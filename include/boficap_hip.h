@@ -851,6 +851,35 @@ int bofi_vocab_pick(const float* x, int ldx, int rows, int V, int S, const int* 
 int bofi_vocab_require(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, const int* words, int K, const uint32_t* ban_bits, int no_repeat,
                        int repeat_min_id, int64_t* seq, float* row_chosen, int* pos, int* moved, void* stream);
 
+/* Required PHRASES: bofi_vocab_require with multi-word UNITS in place of single ids -- "fire hydrant", a product term, a novel-object name: the ids of a unit are placed
+ * side by side and in order, on the contiguous span where they cost the least log-prob.  Still exact: a unit covers a span, so the state at position p reaches back to
+ * p + len instead of p + 1.  A stand-alone launch behind the decode call, as bofi_vocab_require: no field of bofi_call_opts_t, no engine state, the ABI version is unchanged.
+ * Inputs: bofi_vocab_require's (x, ldx, rows, V, S, ntok, ntok_bias, ban_bits, no_repeat, repeat_min_id, seq; n_b = clamp(ntok[b] + ntok_bias, 0, S)), except the table:
+ *   units[b, 0 .. K-1, 0 .. L-1] int32, 1 <= K <= BOFI_REQUIRE_MAX, 1 <= L <= BOFI_REQUIRE_UNIT_MAX.  The length len_j of unit j is its run of leading ids >= 0; the
+ *   entries after the first negative id are not read as ids.  u_0 .. u_{len_j - 1} are its ids.
+ * Units of a row, classified per image: unit j is EMPTY (pos -1) when its first id is < 0.  It is SKIPPED (pos -2) when one of its ids is >= V; one of its ids is banned by
+ * ban_bits; it equals an earlier unit of the row (same length, same ids); and, with no_repeat = 1: it holds two equal adjacent ids >= repeat_min_id; its first id (>=
+ * repeat_min_id) equals the last id of an earlier KEPT unit of the row; or its last id (>= repeat_min_id) equals the first id of an earlier kept unit.  Every other unit is
+ * kept.  The last two cases exist because two placed units could otherwise meet and form an adjacent repeat: excluding exactly that would need the previously placed unit as
+ * recurrence state -- K times the state, which at K = 8 does not fit the 64 KB of LDS of a workgroup.  The host side (require_unit_table) refuses such a pair by name.
+ * Span "unit j starts at p": it needs p + len_j <= n_b.  Position p + i (i < len_j) contributes 0 where seq[p+i] == u_i on entry; otherwise (double)x[p+i, u_i] -
+ * (double)x[p+i, seq[p+i]] when both operands are finite; anything else makes the span INELIGIBLE (NaN, +-inf, a seq[p+i] outside 0..V-1).  With no_repeat = 1 the span
+ * is also ineligible when u_0 >= repeat_min_id, seq[p] != u_0 and the live left neighbour holds u_0 on entry (p > 0, seq[p-1] == u_0), or when u_last >= repeat_min_id,
+ * seq[p+len_j-1] != u_last and the live right neighbour holds u_last on entry (p + len_j < n_b, seq[p+len_j] == u_last): a placement never creates an adjacent repeat.
+ * gain[p][j] is the float64 sum 0.0 + t_0 + t_1 + ... of the span's per-position terms, left to right.
+ * Recurrence and tie-break: best[n_b][m] = (0 units, 0.0) for every mask m of kept units still to place.  For p = n_b - 1 .. 0 and each m the options are taken in this
+ * order: "p takes unit j" for j ascending over the units of m with an eligible span, value (1 + cnt, gain[p][j] + tot) of best[p + len_j][m \ j]; then "p keeps its id",
+ * value best[p+1][m].  Option values compare first by count, then by total; the FIRST option that attains the maximum is choice[p][m].  The result is the forward walk
+ * from (0, all kept units) along choice, which advances by len_j over a placed span.  For L = 1 (and for units of length 1) this is bofi_vocab_require's rule, bit for bit.
+ * Outputs: seq -- rewritten on the placed spans, all else untouched; row_chosen (may be NULL) -- x[p+i, u_i] at every span position, all else untouched; pos int32 [B, K]
+ * -- the START position of each unit, -1 empty, -2 skipped, -3 kept but not placeable; moved int32 [B] (may be NULL) -- positions whose id changed.  x is read only.
+ * The entry point is total: any table contents, any ntok and ids outside the vocabulary in seq give the rule's result, with no read out of range.
+ * One launch, no workspace, deterministic, no atomics; the only float arithmetic is the float64 differences and sums above, in the order above.  rows = 0 is BOFI_OK
+ * without a launch.  BOFI_ERR_ARG with a message and no launch: what bofi_vocab_require refuses (units in place of words), L outside 1..4. */
+#define BOFI_REQUIRE_UNIT_MAX 4
+int bofi_vocab_require_units(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, const int* units, int K, int L, const uint32_t* ban_bits,
+                             int no_repeat, int repeat_min_id, int64_t* seq, float* row_chosen, int* pos, int* moved, void* stream);
+
 /* The N most probable captions of a filling pass, exactly -- the reference's sample_n_method = 'bs' (the N best of a beam) for the non-autoregressive decode, where it is
  * no search: the pass scores every position on its own, a caption's log-probability is a sum of per-position terms, the N best captions use only each row's N best ids,
  * and a width-N merge over the positions finds them.  A stand-alone call behind the decode: no field of bofi_call_opts_t, no engine state, the ABI version is unchanged.

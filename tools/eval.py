@@ -27,7 +27,8 @@ of the sampled captions against the training sentences: the captions in ``--inpu
 test.  Both need the words' ids: ``--infos_path`` (a vocabulary), or ``--bad_endings W1,W2,...``, which overrides the trimmed word set for other vocabularies.
 ``--require_words W1,W2,...`` (every image) or ``--require_words_json FILE`` ({image id: [words]}) (NAIC) places the words in the captions where they cost the least
 log-prob (boficap_amd.eval_utils.required_of; at most 8 per image): the predictions gain ``required`` ([word, position or null] per word) and a line reports
-``required_rate`` (words placed / words required) and ``required_moved_rate``.
+``required_rate`` (words placed / words required) and ``required_moved_rate``.  An item with a space is a phrase of up to 4 words (``"fire hydrant,dog"``): its
+words go side by side on the cheapest span, ``required`` holds [phrase, start position or null], and the rates count units.
 ``--sample_n N --sample_n_method nbest`` (NAIC, N <= 8) takes the N most probable captions of the filling pass -- exact, from one decode -- in place of N random
 draws: ``preds_n`` entries gain ``logp``, the statistics ``nbest_short``.
 ``--nbest_no_repeat 1`` (with ``--sample_n_method nbest``, N <= 6) makes that list the N most probable captions with no adjacent repeated word -- exact too (a
@@ -112,9 +113,10 @@ def main():
                     "neighbours repeat an earlier pair of words does not take the word that followed that pair (the reference's option, applied there on the autoregressive "
                     "paths only and as a penalty; here a hard block)")
     ap.add_argument("--ban_words", default="", help="NAIC only: W1,W2,... never appear in a caption (resolved to ids as --bad_endings resolves its words)")
-    ap.add_argument("--require_words", default="", help="NAIC only: W1,W2,... appear in every caption -- each placed on the position where it costs the least log-prob "
+    ap.add_argument("--require_words", default="", help="NAIC only: W1,W2,... appear in every caption -- each placed on the position where it costs the least log-prob; "
+                    "an item with a space is a phrase of up to 4 words ('fire hydrant,dog'), placed side by side on the cheapest span "
                     "(eval_kwargs['require_words']; the predictions gain 'required', the statistics required_rate and required_moved_rate)")
-    ap.add_argument("--require_words_json", default="", help="NAIC only: a JSON file {image id: [W1, W2, ...]} of required words per image (the ids of --input_json, else "
+    ap.add_argument("--require_words_json", default="", help="NAIC only: a JSON file {image id: [W1, W2, ...]} of required words and phrases per image (the ids of --input_json, else "
                     "the images' indices); not together with --require_words")
     args = ap.parse_args()
     if args.require_words and args.require_words_json:
@@ -241,9 +243,10 @@ def main():
             ap.error(str(e))
         if required is not None:
             req_kw = [required[0][i:i + args.batch_size] for i in range(0, len(feats), args.batch_size)]
+            req_key = "require_phrases" if eval_utils.required_phrases(required[0]) else "require_ids"      # (an item with a space is a phrase: units of ids)
 
     def req(n=None):
-        return {"require_ids": req_kw[:n]} if required is not None else {}
+        return {req_key: req_kw[:n]} if required is not None else {}
     changed, emitted = 0, 0
     results, seconds, rows, stats = [], 0.0, [], ([], [])
     store_loss = store is not None and not args.use_box          # (mode='forward' is not built for F = 2053: box features are decode-only)
@@ -326,7 +329,7 @@ def main():
                 fc = torch.zeros(att.size(0), 0, device="cuda")
                 seq, lp, pn, pl, ps, t = model(fc, att, masks, opt=dict({"train_mode": args.inference_mode, "sample_method": "greedy", "sample_n": 1},
                                                                                    **(dict(refine, **pick_opt) if args.inference_mode == "NAIC" else {}),
-                                                                                   **({"require_ids": req_kw[i // args.batch_size]} if required is not None else {})), mode="sample")
+                                                                                   **({req_key: req_kw[i // args.batch_size]} if required is not None else {})), mode="sample")
                 seconds += t
                 if required is not None:
                     b = att.size(0)
