@@ -263,6 +263,11 @@ const char* vocab_require_units_check(const float* x, int ldx, int rows, int V, 
                                       const int64_t* seq, const int* pos);      // NULL, or what is wrong (BOFI_ERR_ARG)
 int launch_vocab_require_units(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, const int* units, int K, int L, const uint32_t* ban_bits,
                                int no_repeat, int repeat_min_id, int64_t* seq, float* row_chosen, int* pos, int* moved, hipStream_t st);
+// required alternatives (force.hip): alts [B, K, A, L], group j satisfied by any one of its up to 4 units (bofi_vocab_require_any states the rule); one launch, no workspace
+const char* vocab_require_any_check(const float* x, int ldx, int rows, int V, int S, const int* alts, int K, int A, int L, int no_repeat, int repeat_min_id,
+                                    const int64_t* seq, const int* pos, const int* which);      // NULL, or what is wrong (BOFI_ERR_ARG)
+int launch_vocab_require_any(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, const int* alts, int K, int A, int L,
+                             const uint32_t* ban_bits, int no_repeat, int repeat_min_id, int64_t* seq, float* row_chosen, int* pos, int* which, int* moved, hipStream_t st);
 
 int launch_set_u64(uint64_t* p, uint64_t v, hipStream_t s);
 int launch_zero_f32(float* p, size_t n, hipStream_t s);

@@ -209,7 +209,7 @@ class BofiEngine:
                     refine_rounds: int = 0, out: Optional[dict] = None, q1_group: int = 0, iter_cap: int = 0, phases: str = "", row_stats: bool = False,
                     ids_only: bool = False, refine_method: str = "feed_back", attn_topk: int = 0, attn_maps: bool = False, attn_heads: bool = False,
                     attn_layer: int = -1, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7, block_trigrams: bool = False, require_ids=None,
-                    nbest: Optional[int] = None, nbest_no_repeat: bool = False, require_phrases=None) -> dict:
+                    nbest: Optional[int] = None, nbest_no_repeat: bool = False, require_phrases=None, require_any=None) -> dict:
         """Greedy NAIC bound+fill decode.  Returns a dict of device tensors: seq [B,S] int64,
         seq_logprob [B,S,V] float32 (or None), phrase_num [B] int32, phrase_length [B,S] int32,
         phrase_syn [B,S] int64, bound_iters [1] int32, memory [B,R,d] float32 (or None).
@@ -260,6 +260,14 @@ class BofiEngine:
         repeats a word and two units that could meet at a shared word); a device tensor int32 [B, K, L] with -1 padding is passed through as it is.  Each unit goes to the
         contiguous span where it costs the least log-prob (first as many units as can be placed, then the largest total gain; the header states the rule).
         ``out['required_pos']`` int32 [B, K] then holds each unit's START position (-1, -2, -3 as above).
+        ``require_any`` (bofi_vocab_require_any in their place: same placement behind the call, same refusals; not together with ``require_ids`` or ``require_phrases``
+        -- give one): required ALTERNATIVES -- per image a list of GROUPS, each a list of 1..4 alternatives, each a list of 1..4 ids ("dog", "dogs" or "puppy"), or one
+        flat list of groups for every image (``hip.require_any_table`` states the forms and what it refuses: among it an alternative given twice and, under ``no_repeat``,
+        two alternatives of different groups that could meet at a shared word); a device tensor int32 [B, K, A, L] with -1 padding is passed through as it is.  A group
+        is satisfied by ANY ONE of its alternatives: the placement takes, per group, the alternative and the span that cost the least (first as many groups as can be
+        satisfied, then the largest total gain; the header states the rule).  ``out['required_pos']`` int32 [B, K] holds the start of each group's placed alternative
+        (-1 no alternative given, -2 all skipped, -3 not placeable), ``out['required_alt']`` int32 [B, K] that alternative's index in its group (-1: not placed),
+        ``out['required_moved']`` as above.
         ``nbest`` = N in 1..8 (bofi_vocab_nbest: two small launches on the same stream BEHIND the decode call, outside a ``graph`` replay; no field of the call record):
         the N most probable captions of the last filling pass, exactly -- the pass scores every position on its own, so a caption's log-prob is a sum of per-position
         terms and a width-N merge over each row's N best ids finds the N best captions (the header states the rule, its tie order and what holds under ties).  Read
@@ -276,7 +284,7 @@ class BofiEngine:
         mp = self._refine_flag(refine_method, refine_rounds, raw_logits)
         ban, pick_on, req, nbest, nb_min = self._post_options(
             ban_ids, no_repeat, repeat_min_id, block_trigrams, require_ids, nbest, nbest_no_repeat, att_feats.size(0), ids_only, mp,
-            want_logprob or (out is not None and out.get("seq_logprob") is not None), require_phrases)
+            want_logprob or (out is not None and out.get("seq_logprob") is not None), require_phrases, require_any)
         if ids_only:
             if raw_logits:
                 raise hip.BofiHipError("ids_only: the raw logits are not produced")
@@ -330,6 +338,8 @@ class BofiEngine:
             hip.ptr(out["memory"]), hip.ptr(out["bound_iters"]), C.byref(o), hip.stream_ptr()), "bofi_engine_decode_naic")
         if req is None:
             out.pop("required_pos", None), out.pop("required_moved", None)      # (a reused `out` of a call that had the option)
+        if req is None or req.dim() != 4:
+            out.pop("required_alt", None)
         if not nbest:
             out.pop("nbest_seq", None), out.pop("nbest_logp", None), out.pop("nbest_count", None)      # (a reused `out` of a call that had the option)
         if not phases or "f" in phases:
@@ -338,9 +348,9 @@ class BofiEngine:
         return out
 
     def _post_options(self, ban_ids, no_repeat, repeat_min_id, block_trigrams, require_ids, nbest, nbest_no_repeat, B: int, ids_only, mp: int, own_rows: bool,
-                      require_phrases=None):
+                      require_phrases=None, require_any=None):
         """The options of ``decode_naic`` / ``fill_naic`` whose work follows the call, resolved and refused before anything is enqueued: (ban, pick_on, req, nbest, nb_min)
-        -- the device bit table or None, "the constrained pick is on", the device table of required words ([B, K]) or units ([B, K, L]) or None, the list's width (0: off) and the ``repeat_min_id``
+        -- the device bit table or None, "the constrained pick is on", the device table of required words ([B, K]), units ([B, K, L]) or alternatives ([B, K, A, L]) or None, the list's width (0: off) and the ``repeat_min_id``
         of a repeat-free list (None: the plain list).  ``ids_only`` None: the entry point has no such form (``fill_naic``; its pick refusal comes first, in its own words)."""
         ban = self._pick_ban(ban_ids, block_trigrams)
         pick_on = ban is not None or bool(no_repeat) or bool(block_trigrams)
@@ -355,6 +365,12 @@ class BofiEngine:
                 raise hip.BofiHipError("require_ids and require_phrases: give one (single ids are units of length 1)")
             self._require_refusals(bool(ids_only), mp, block_trigrams, "require_phrases")
             req = units
+        alts = self._require_any_table(require_any, B, ban_ids, no_repeat, repeat_min_id)
+        if alts is not None:
+            if req is not None:
+                raise hip.BofiHipError("require_ids / require_phrases and require_any: give one (a word or a unit is a group of one alternative)")
+            self._require_refusals(bool(ids_only), mp, block_trigrams, "require_any")
+            req = alts
         nbest = self._nbest_width(nbest)
         nb_min = self._nbest_no_repeat(nbest, nbest_no_repeat, repeat_min_id)
         if nbest:
@@ -370,7 +386,11 @@ class BofiEngine:
             if target.get("constrained") is None or target["constrained"].numel() != B:
                 target["constrained"] = torch.zeros(B, dtype=torch.int32, device=seq.device)
             hip.check(self._lib.bofi_engine_pick_changed(self._h, hip.ptr(target["constrained"]), B, hip.stream_ptr()), "bofi_engine_pick_changed")
-        if req is not None:
+        if req is not None and req.dim() == 4:
+            target["required_pos"], target["required_alt"], target["required_moved"] = self._require_any_place(
+                req, seq, lp, ntok(), ntok_bias, ban, no_repeat, repeat_min_id, row_chosen, target.get("required_pos"), target.get("required_alt"),
+                target.get("required_moved"))
+        elif req is not None:
             target["required_pos"], target["required_moved"] = self._require_place(
                 req, seq, lp, ntok(), ntok_bias, ban, no_repeat, repeat_min_id, row_chosen, target.get("required_pos"), target.get("required_moved"))
         if nbest:
@@ -410,7 +430,7 @@ class BofiEngine:
             raise hip.BofiHipError("nbest: not with no_repeat / block_trigrams (the N best under a rule that couples neighbours need per-last-id state: "
                                    "a width-N list is no longer exact); nbest_no_repeat=True lists the repeat-free captions beside the plain decode")
         if required:
-            raise hip.BofiHipError("nbest: not with require_ids / require_phrases (the list is of unforced captions)")
+            raise hip.BofiHipError("nbest: not with require_ids / require_phrases / require_any (the list is of unforced captions)")
         if not own_rows and not self._lib.bofi_engine_logprob(self._h):
             raise hip.BofiHipError("nbest: this engine keeps no log-prob workspace (an ids-only fork): there are no rows to list from")
 
@@ -463,6 +483,19 @@ class BofiEngine:
         t = hip.require_unit_table(require_phrases, B, self.cfg.tgt_vocab, ban_ids or (), bool(no_repeat), int(repeat_min_id))
         return None if t is None else t.to(self.device)
 
+    def _require_any_table(self, require_any, B: int, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7):
+        """``require_any`` of a decode as the device table int32 [B, K, A, L] of bofi_vocab_require_any, None when nothing is required.  Host input goes through
+        ``hip.require_any_table`` (BofiHipError for what it refuses); a device tensor is passed through -- the kernel is total."""
+        if isinstance(require_any, torch.Tensor) and require_any.is_cuda:
+            t = require_any
+            if (t.dim() != 4 or t.size(0) != B or not 1 <= t.size(1) <= hip.REQUIRE_MAX or not 1 <= t.size(2) <= hip.REQUIRE_ALT_MAX
+                    or not 1 <= t.size(3) <= hip.REQUIRE_UNIT_MAX):
+                raise hip.BofiHipError(f"require_any: a device table is [B, K, A, L] with 1 <= K <= {hip.REQUIRE_MAX}, 1 <= A <= {hip.REQUIRE_ALT_MAX} and "
+                                       f"1 <= L <= {hip.REQUIRE_UNIT_MAX}, got {tuple(t.shape)} for {B} images")
+            return t.to(torch.int32).contiguous()
+        t = hip.require_any_table(require_any, B, self.cfg.tgt_vocab, ban_ids or (), bool(no_repeat), int(repeat_min_id))
+        return None if t is None else t.to(self.device)
+
     @staticmethod
     def _require_refusals(ids_only: bool, mp: int, block_trigrams: bool, what: str = "require_ids") -> None:
         if ids_only:
@@ -496,6 +529,27 @@ class BofiEngine:
                                                int(repeat_min_id), hip.ptr(seq), hip.ptr(row_chosen), hip.ptr(pos), hip.ptr(moved), hip.stream_ptr()),
                   "bofi_vocab_require")
         return pos, moved
+
+    def _require_any_place(self, req, seq, lp, ntok, ntok_bias, ban, no_repeat, repeat_min_id, row_chosen, pos=None, which=None, moved=None):
+        """Enqueue bofi_vocab_require_any on the current stream behind a decode: ``req`` int32 [B, K, A, L] on the device, the rest as ``_require_place``.  Returns (pos
+        int32 [B, K], which int32 [B, K], moved int32 [B]); the buffers given are reused when they fit."""
+        if int(repeat_min_id) < 0:
+            raise hip.BofiHipError("repeat_min_id must be >= 0")
+        B, K, A, L = req.shape
+        S, V = self.cfg.seq_length, self.cfg.tgt_vocab
+        if pos is None or tuple(pos.shape) != (B, K):
+            pos = torch.empty(B, K, dtype=torch.int32, device=seq.device)
+        if which is None or tuple(which.shape) != (B, K):
+            which = torch.empty(B, K, dtype=torch.int32, device=seq.device)
+        if moved is None or moved.numel() != B:
+            moved = torch.empty(B, dtype=torch.int32, device=seq.device)
+        src = hip.ptr(lp) if lp is not None else self._lib.bofi_engine_logprob(self._h)
+        if not src:
+            raise hip.BofiHipError("require_any: this engine keeps no log-prob workspace (an ids-only fork)")
+        hip.check(self._lib.bofi_vocab_require_any(src, V, B * S, V, S, hip.ptr(ntok), int(ntok_bias), hip.ptr(req), K, A, L, hip.ptr(ban), 1 if no_repeat else 0,
+                                                   int(repeat_min_id), hip.ptr(seq), hip.ptr(row_chosen), hip.ptr(pos), hip.ptr(which), hip.ptr(moved),
+                                                   hip.stream_ptr()), "bofi_vocab_require_any")
+        return pos, which, moved
 
     def _pick_ban(self, ban_ids, block_trigrams: bool = False):
         """The device bit table of a ban list (``hip.ban_bits``: ids outside 0..V-1 and a list that leaves fewer than two ids raise), kept per engine and id set;
@@ -734,20 +788,20 @@ class BofiEngine:
     def fill_naic(self, ext_syn: torch.Tensor, last: torch.Tensor, R: int, att_len: Optional[torch.Tensor] = None, *, strict_q1: bool = True,
                   raw_logits: bool = False, refine_rounds: int = 0, refine_method: str = "feed_back", attn_topk: int = 0, attn_maps: bool = False,
                   attn_heads: bool = False, attn_layer: int = -1, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7, block_trigrams: bool = False,
-                  require_ids=None, nbest: Optional[int] = None, nbest_no_repeat: bool = False, require_phrases=None):
+                  require_ids=None, nbest: Optional[int] = None, nbest_no_repeat: bool = False, require_phrases=None, require_any=None):
         """The filling pass alone on a given slot layout (``ext_syn`` int32 [B, S+2], ``last`` int32 [B]) and the memory of the
         preceding ``encode``: (seq int64 [B, S], seq_logprob float32 [B, S, V]); with ``refine_method='mask_predict'`` (as ``decode_naic``) a third
         element, refine_round int32 [B, S].  With ``attn_topk`` / ``attn_maps`` / ``attn_heads`` (as ``decode_naic``) a last element, a dict of the attention tensors
         ('attn', 'attn_heads', 'attn_top', 'attn_top_w': those asked for).  ``ban_ids`` / ``no_repeat`` / ``repeat_min_id`` / ``block_trigrams`` as ``decode_naic``: that dict (the last element)
         then carries 'constrained', int32 [B].  ``require_ids`` as ``decode_naic`` (bofi_vocab_require behind the call, on the last pass; the same refusals): that dict
         then carries 'required_pos' int32 [B, K] and 'required_moved' int32 [B]; ``require_phrases`` as ``decode_naic`` (bofi_vocab_require_units in its place, the
-        same keys).  ``nbest`` as ``decode_naic`` (bofi_vocab_nbest behind the call, on the last pass; the
+        same keys); ``require_any`` as ``decode_naic`` (bofi_vocab_require_any in its place: 'required_alt' int32 [B, K] beside those keys).  ``nbest`` as ``decode_naic`` (bofi_vocab_nbest behind the call, on the last pass; the
         same refusals): that dict then carries 'nbest_seq' int64 [B, N, S], 'nbest_logp' float64 [B, N] and 'nbest_count' int32 [B]; ``nbest_no_repeat`` as
         ``decode_naic`` (bofi_vocab_nbest_norepeat in its place, N <= 6)."""
         mp = self._refine_flag(refine_method, refine_rounds, raw_logits)
         B = ext_syn.size(0)
         ban, pick_on, req, nbest, nb_min = self._post_options(ban_ids, no_repeat, repeat_min_id, block_trigrams, require_ids, nbest, nbest_no_repeat, B, None, mp, True,
-                                                               require_phrases)
+                                                               require_phrases, require_any)
         if ext_syn.dtype != torch.int32 or last.dtype != torch.int32 or ext_syn.size(1) != self.cfg.bound_len or last.numel() != B:
             raise hip.BofiHipError("ext_syn must be int32 [B, S+2] and last int32 [B]")
         S, V, dev = self.cfg.seq_length, self.cfg.tgt_vocab, ext_syn.device
@@ -786,7 +840,7 @@ class DecodePipeline:
     def __init__(self, engine: "BofiEngine", *, in_flight: Optional[int] = None, batches_per_launch: int = 16, strict_q1: bool = True, stats: bool = True,
                  keep_logprob: bool = False, region_buckets=(36, 48, 64, 80, 100, 128), fused_vocab: bool = False,
                  refine_rounds: int = 0, refine_method: str = "feed_back", attn_topk: int = 0, keep_attn: bool = False, ban_ids=None, no_repeat: bool = False,
-                 repeat_min_id: int = 7, block_trigrams: bool = False, require_ids=None, require_phrases=None):
+                 repeat_min_id: int = 7, block_trigrams: bool = False, require_ids=None, require_phrases=None, require_any=None):
         BofiEngine._refine_flag(refine_method, refine_rounds, False)
         # ban_ids / no_repeat / repeat_min_id / block_trigrams: the constrained pick of BofiEngine.decode_naic on every launch; every yielded dict then carries constrained int32 [b].  Not
         # with fused_vocab (ids-only launches keep no distribution to re-pick from) or 'mask_predict'
@@ -811,6 +865,10 @@ class DecodePipeline:
         self.require_phrases = require_phrases
         self._require_both(require_ids, require_phrases)
         self._phrase_split(require_phrases)
+        # require_any: required alternatives (BofiEngine.decode_naic(require_any=...)), in the same two forms and under the same refusals; not with the other two
+        self.require_any = require_any
+        self._require_both(require_ids, require_phrases, require_any)
+        self._any_split(require_any)
         # attn_topk = K > 0: every yielded dict carries attn_top int32 / attn_top_w float32 [b, S, K] -- each position's K heaviest regions (BofiEngine.decode_naic) -- on the
         # host, through the pinned buffers (rows x S x K x 8 bytes per launch); keep_attn: also attn [b, S, R of the launch's region bucket] on the device, as keep_logprob
         if not 0 <= int(attn_topk) <= 8:
@@ -873,10 +931,39 @@ class DecodePipeline:
         return None, iter(require_ids)
 
     @staticmethod
-    def _require_both(require_ids, require_phrases) -> None:
+    def _require_both(require_ids, require_phrases, require_any=None) -> None:
         on = lambda v: v is not None and not (hasattr(v, "__len__") and len(v) == 0)
         if on(require_ids) and on(require_phrases):
             raise hip.BofiHipError("require_ids and require_phrases: give one (single ids are units of length 1)")
+        if on(require_any) and (on(require_ids) or on(require_phrases)):
+            raise hip.BofiHipError("require_ids / require_phrases and require_any: give one (a word or a unit is a group of one alternative)")
+
+    def _any_split(self, require_any):
+        """``require_any`` of a run as (flat, per_batch): one flat list of groups for every image, or an iterator of per-batch tables aligned with the batches; (None,
+        None) when off.  The refusals are those of required phrases, raised here."""
+        if require_any is None:
+            return None, None
+        import numpy as np
+        if isinstance(require_any, (torch.Tensor, np.ndarray)):
+            raise hip.BofiHipError("require_any: a pipeline takes one flat list of groups for every image or a sequence of per-batch tables")
+        seq = require_any if hasattr(require_any, "__len__") else None
+        if seq is not None and len(seq) == 0:
+            return None, None
+        if self.fused_vocab:
+            raise hip.BofiHipError("require_any: not with fused_vocab (the ids-only launches keep no distribution to place the words by)")
+        if self.refine_method == "mask_predict":
+            raise hip.BofiHipError("require_any: not with refine_method='mask_predict'")
+        if self.block_trigrams:
+            raise hip.BofiHipError("require_any: not with block_trigrams (a placement could create a blocked trigram)")
+        is_id = lambda v: isinstance(v, (int, np.integer))
+        if seq is not None and any(is_id(g) for g in seq):
+            hip.require_any_table(list(seq), 1, self.root_vocab)     # (raises, showing the nesting)
+        # one flat list of groups: an element's first non-empty entry is an alternative (a list of ids); in a per-batch table it is a group or an image (lists of lists)
+        first = lambda g: next((u for u in g if is_id(u) or (u is not None and len(u))), None) if isinstance(g, (list, tuple)) else None
+        if seq is not None and any(first(g) is not None and (is_id(first(g)) or is_id(first(g)[0])) for g in seq):
+            flat = hip.require_any_table(list(seq), 1, self.root_vocab, self.ban_ids, self.no_repeat, self.repeat_min_id)      # (checked once, here)
+            return (None, None) if flat is None else ([[[int(i) for i in u if i >= 0] for u in g] for g in flat[0].tolist()], None)
+        return None, iter(require_any)
 
     def _phrase_split(self, require_phrases):
         """``require_phrases`` of a run as (flat, per_batch): one flat list of units for every image, or an iterator of per-batch tables aligned with the batches; (None,
@@ -905,6 +992,16 @@ class DecodePipeline:
     def _require_launch(self, group, b):
         """The [rows, K] host table of a launch from its batches' tables (each checked on the host by ``hip.require_table``), and every batch's own K (0: none); (None,
         ks) when no batch of the launch requires a word."""
+        if any(len(g) > 3 and g[3] == "any" for g in group):    # alternatives: a [rows, K, A, L] table, every batch checked by ``hip.require_any_table``
+            tabs = [hip.require_any_table(g[2], b, self.root_vocab, self.ban_ids, self.no_repeat, self.repeat_min_id) if g[2] is not None else None for g in group]
+            ks = [0 if t is None else t.size(1) for t in tabs]
+            if max(ks) == 0:
+                return None, ks
+            full = torch.full((len(group) * b, max(ks)) + tuple(max(t.size(d) for t in tabs if t is not None) for d in (2, 3)), -1, dtype=torch.int32)
+            for i, t in enumerate(tabs):
+                if t is not None:
+                    full[i * b:(i + 1) * b, :t.size(1), :t.size(2), :t.size(3)] = t
+            return full, ks
         if any(len(g) > 3 and g[3] for g in group):             # units: a [rows, K, L] table, every batch checked by ``hip.require_unit_table``
             tabs = [hip.require_unit_table(g[2], b, self.root_vocab, self.ban_ids, self.no_repeat, self.repeat_min_id) if g[2] is not None else None for g in group]
             ks = [0 if t is None else t.size(1) for t in tabs]
@@ -941,7 +1038,7 @@ class DecodePipeline:
                 return b
         raise hip.BofiHipError(f"{r} regions exceed the engine's max_regions={self.root.max_regions}")
 
-    def run(self, batches, require_ids=None, require_phrases=None):
+    def run(self, batches, require_ids=None, require_phrases=None, require_any=None):
         """``batches``: iterable of ``att_feats`` or ``(att_feats, att_len)``: [b, R, F] tensors / arrays in the engine's compute dtype or float32, on
         the host (pinned: the copy is asynchronous) or the device; ``att_len`` int32 [b] region counts or None (every image has R regions).  An item may
         also be a ``features.RaggedBatch``: its real rows alone are copied, in the files' dtype, and ``bofi_pack_regions`` pads them to the region bucket
@@ -956,17 +1053,25 @@ class DecodePipeline:
         ``require_phrases`` (default: the constructor's): required multi-word units, as ``BofiEngine.decode_naic(require_phrases=...)`` places them, in the same two
         forms -- one flat list of units (each a list of 1..4 ids) for every image, or a sequence of per-batch tables aligned with ``batches`` (each a list of b unit lists,
         one flat list of units for the batch, a [b, K, L] int table, or None) --, with the same keys (required_pos holds the units' start positions) and refusals.  Not
-        together with ``require_ids``: give one."""
-        if require_ids is None and require_phrases is None:
-            require_ids, require_phrases = self.require_ids, self.require_phrases
-        self._require_both(require_ids, require_phrases)
+        together with ``require_ids``: give one.
+        ``require_any`` (default: the constructor's): required alternatives, as ``BofiEngine.decode_naic(require_any=...)`` places them, in the same two forms -- one
+        flat list of groups (each a list of 1..4 alternatives, each a list of 1..4 ids) for every image, or a sequence of per-batch tables aligned with ``batches`` (each
+        a list of b group lists, one flat list of groups for the batch, a [b, K, A, L] int table, or None) --, with the keys required_pos (the start of each group's
+        placed alternative), required_alt int32 [b, K of the batch] (its index in the group) and required_moved, and the same refusals.  Not together with the other
+        two: give one."""
+        if require_ids is None and require_phrases is None and require_any is None:
+            require_ids, require_phrases, require_any = self.require_ids, self.require_phrases, self.require_any
+        self._require_both(require_ids, require_phrases, require_any)
         flat, per_batch = self._require_split(require_ids)
         if flat is None and per_batch is None:
             flat, per_batch = self._phrase_split(require_phrases)
+            if flat is None and per_batch is None:
+                flat, per_batch = self._any_split(require_any)
+                return self._run(batches, flat, per_batch, "any" if flat is not None or per_batch is not None else False)
             return self._run(batches, flat, per_batch, flat is not None or per_batch is not None)
         return self._run(batches, flat, per_batch)
 
-    def _run(self, batches, req_flat, req_iter, units: bool = False):
+    def _run(self, batches, req_flat, req_iter, units=False):      # units: False (words), True (units), 'any' (alternatives)
         from .features import RaggedBatch
         pending = []                                             # launches in flight: (slot, [batch sizes])
         group, gkey = [], None
@@ -990,7 +1095,7 @@ class DecodePipeline:
                 try:
                     req = next(req_iter)
                 except StopIteration:
-                    raise hip.BofiHipError("require_ids / require_phrases: fewer per-batch tables than batches") from None
+                    raise hip.BofiHipError("require_ids / require_phrases / require_any: fewer per-batch tables than batches") from None
             if isinstance(item, RaggedBatch):
                 r = self._bucket(item.max_len)
                 key = (item.B, r, item.out_F, self.root.dtype, item.equal_lengths and item.max_len == r)
@@ -1105,7 +1210,7 @@ class DecodePipeline:
                                   q1_group=b if nb > 1 else 0, row_stats=self.stats, want_logprob=self.keep_logprob, ids_only=self.fused_vocab,
                                   refine_rounds=self.refine_rounds, refine_method=self.refine_method, attn_topk=self.attn_topk, attn_maps=self.keep_attn,
                                   ban_ids=self.ban_ids or None, no_repeat=self.no_repeat, repeat_min_id=self.repeat_min_id, block_trigrams=self.block_trigrams,
-                                  **({} if sl.get("req") is None else {"require_phrases" if sl["req"].dim() == 3 else "require_ids": sl["req"]}))
+                                  **({} if sl.get("req") is None else {("require_ids", "require_phrases", "require_any")[sl["req"].dim() - 2]: sl["req"]}))
         out = sl["out"]
         small = {k2: out[k2] for k2 in ("seq", "phrase_num", "phrase_length", "phrase_syn", "bound_saturated")}
         if self.refine_method == "mask_predict":
@@ -1116,6 +1221,8 @@ class DecodePipeline:
             small["constrained"] = out["constrained"]
         if sl.get("req") is not None:
             small["required_pos"], small["required_moved"] = out["required_pos"], out["required_moved"]
+            if sl["req"].dim() == 4:
+                small["required_alt"] = out["required_alt"]
         if self.stats:
             small["entropy"], small["perplexity"] = e.entropy_perplexity(out)
         if sl["host"] is None or sl["host"].keys() != small.keys() or any(sl["host"][k2].shape != v.shape for k2, v in small.items()):
@@ -1145,8 +1252,11 @@ class DecodePipeline:
             if "required_pos" in res:                            # (a batch's own K columns; no keys for a batch of the launch that requires nothing)
                 if req_ks[i]:
                     res["required_pos"] = res["required_pos"][:, :req_ks[i]]
+                    if "required_alt" in res:
+                        res["required_alt"] = res["required_alt"][:, :req_ks[i]]
                 else:
                     del res["required_pos"], res["required_moved"]
+                    res.pop("required_alt", None)
             if sl["lp"] is not None:
                 res["seq_logprob"] = sl["lp"][o:o + b]
             if sl["attn"] is not None:

@@ -328,7 +328,14 @@ def required_of(eval_kwargs, vocab, keys, mode: str = "NAIC", sample_n: int = 1,
     unless the vocabulary holds the whole item as one entry, which wins over splitting.  If any image has a phrase the whole evaluation goes through
     ``decode_many(require_phrases=...)``: every entry of ``ids`` is then a list of UNITS (id lists; a single word is a unit of length 1) -- ``required_phrases(ids)`` tells
     the two apart; under ``decoding_constraint`` a phrase that repeats a word and two items that could meet at a shared word are a ValueError naming them.  Without a
-    phrase nothing changes."""
+    phrase nothing changes.
+    An item that contains ``|`` is a set of ALTERNATIVES ('dog|dogs|puppy', 'fire hydrant|hydrant'), any one of which satisfies it -- unless the vocabulary holds the
+    whole item as one entry: then it is a plain word, ``|`` or not.  Each alternative resolves as an item does (a vocabulary entry that equals the whole alternative wins
+    over splitting at spaces, 1 to 4 words, an unknown word is named); at most 4 of them, none given twice for an image.  If any image has such an item the whole
+    evaluation goes through ``decode_many(require_any=...)`` and the result is (ids, words, texts): every entry of ``ids`` is a list of GROUPS (lists of alternatives, each
+    an id list; a plain item is a group of one alternative) -- ``required_any(ids)`` tells --, ``texts`` holds every group's alternatives as text.  Under
+    ``decoding_constraint`` an alternative that repeats a word and two alternatives of different items that could meet at a shared word are a ValueError naming them.
+    Without a ``|`` item nothing changes."""
     spec = eval_kwargs.get("require_words")
     if not spec:
         return None
@@ -350,20 +357,24 @@ def required_of(eval_kwargs, vocab, keys, mode: str = "NAIC", sample_n: int = 1,
     for k, w in vocab.items():
         id_of[w] = min(int(k), id_of.get(w, int(k)))
     ban = {int(i) for i in ban_ids or ()}
+    def unit_of(w):
+        parts = [w] if w in id_of else w.split()               # (a vocabulary entry that equals the whole item wins over splitting)
+        for q in parts:
+            if q not in id_of:
+                raise ValueError(f"require_words: the vocabulary does not hold {q!r}")
+            if id_of[q] in ban:
+                raise ValueError(f"require_words: {q!r} is also banned (suppress_UNK / ban_words)")
+        if not 1 <= len(parts) <= 4:
+            raise ValueError(f"require_words: a phrase holds 1 to 4 words, got {w!r}")
+        return [id_of[q] for q in parts]
+
+    sets = lambda w: "|" in w and w not in id_of               # an item of alternatives (an item that is itself a vocabulary entry is a plain word)
+    if any(sets(w) for ws in per_image for w in ws):
+        return _required_any_of(eval_kwargs, per_image, unit_of, sets)
     ids, words = [], []
     for ws in per_image:
         ws = list(dict.fromkeys(ws))
-        units = []
-        for w in ws:
-            parts = [w] if w in id_of else w.split()           # (a vocabulary entry that equals the whole item wins over splitting)
-            for q in parts:
-                if q not in id_of:
-                    raise ValueError(f"require_words: the vocabulary does not hold {q!r}")
-                if id_of[q] in ban:
-                    raise ValueError(f"require_words: {q!r} is also banned (suppress_UNK / ban_words)")
-            if not 1 <= len(parts) <= 4:
-                raise ValueError(f"require_words: a phrase holds 1 to 4 words, got {w!r}")
-            units.append([id_of[q] for q in parts])
+        units = [unit_of(w) for w in ws]
         if len(ws) > 8:
             raise ValueError(f"require_words: at most 8 required words per image, got {len(ws)}")
         ids.append(units)
@@ -382,13 +393,63 @@ def required_of(eval_kwargs, vocab, keys, mode: str = "NAIC", sample_n: int = 1,
     return ids, words
 
 
+def _required_any_of(eval_kwargs, per_image, unit_of, sets):
+    """``required_of`` where some item is a set of alternatives: (ids, words, texts) -- per image the groups, the items, and every group's alternatives as text."""
+    rep = int(eval_kwargs.get("decoding_constraint", 0) or 0) == 1
+    ids, words, texts = [], [], []
+    for ws in per_image:
+        ws = list(dict.fromkeys(ws))
+        groups, names, seen = [], [], []                         # seen: (item index, alternative's text, its ids) of the image so far
+        for j, w in enumerate(ws):
+            alts = [t for t in (a.strip() for a in w.split("|")) if t] if sets(w) else [w]
+            if not alts:
+                raise ValueError(f"require_words: {w!r} holds no alternative")
+            if len(alts) > 4:
+                raise ValueError(f"require_words: an item holds at most 4 alternatives, got {w!r}")
+            group = []
+            for t in alts:
+                u = unit_of(t)
+                for i, t2, v in seen:
+                    if v == u:
+                        raise ValueError(f"require_words: the alternative {t!r} is given twice" + (f" (in {ws[i]!r} and {w!r})" if i != j else f" in {w!r}"))
+                    if rep and i != j and ((v[-1] == u[0] and u[0] >= 7) or (u[-1] == v[0] and v[0] >= 7)):
+                        raise ValueError(f"require_words: {t2!r} and {t!r} could meet at a shared word and form an adjacent repeat (not under decoding_constraint)")
+                if rep and any(x == y and x >= 7 for x, y in zip(u, u[1:])):
+                    raise ValueError(f"require_words: {t!r} repeats a word (not under decoding_constraint)")
+                seen.append((j, t, u))
+                group.append(u)
+            groups.append(group)
+            names.append(alts)
+        if len(ws) > 8:
+            raise ValueError(f"require_words: at most 8 required words per image, got {len(ws)}")
+        ids.append(groups)
+        words.append(ws)
+        texts.append(names)
+    return ids, words, texts
+
+
+def required_any(ids) -> bool:
+    """Whether the ``ids`` of ``required_of`` are lists of groups of alternatives (some image has a ``|`` item) and go through ``require_any``."""
+    return any(isinstance(a, list) for groups in ids for g in groups if isinstance(g, list) for a in g)
+
+
+def required_key(ids) -> str:
+    """The decode option that takes the ``ids`` of ``required_of``: 'require_any', 'require_phrases' or 'require_ids'."""
+    return "require_any" if required_any(ids) else "require_phrases" if required_phrases(ids) else "require_ids"
+
+
 def required_phrases(ids) -> bool:
     """Whether the ``ids`` of ``required_of`` are lists of units (some image has a phrase) and go through ``require_phrases``."""
     return any(isinstance(u, list) for units in ids for u in units)
 
 
-def required_entry(words, pos_row):
-    """The 'required' field of a prediction entry: [word or phrase, (start) position] per required item of the image, position None where it could not be placed."""
+def required_entry(words, pos_row, alt_row=None, texts=None):
+    """The 'required' field of a prediction entry: [word or phrase, (start) position] per required item of the image, position None where it could not be placed.  With
+    ``alt_row`` and ``texts`` (alternatives: the 'required_alt' row and the image's ``texts`` of ``required_of``): [item, start or None, the alternative placed (its
+    text) or None]."""
+    if alt_row is not None:
+        return [[w, (int(p) if int(p) >= 0 else None), (t[int(a)] if int(p) >= 0 and 0 <= int(a) < len(t) else None)]
+                for w, p, a, t in zip(words, pos_row[:len(words)].tolist(), alt_row[:len(words)].tolist(), texts)] if words else []
     return [[w, (int(p) if int(p) >= 0 else None)] for w, p in zip(words, pos_row[:len(words)].tolist())] if words else []
 
 
@@ -420,7 +481,7 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
     # suppress_UNK / decoding_constraint / ban_words / block_trigrams: the constrained pick (constraint_of); with language stats, constrained_rate = changed / emitted positions
     pick = constraint_of(kw, kw.get("vocab") or getattr(model, "vocab", None), mode, sample_n)
     refine.update(pick)
-    # require_words: required words and phrases (required_of) -- per-batch tables to decode_many (require_phrases when some image has a phrase); the predictions gain 'required' ([word, position or None] per word), the stats
+    # require_words: required words, phrases and alternatives (required_of) -- per-batch tables to decode_many (require_phrases when some image has a phrase, require_any when some item has '|': 'required' entries then hold the alternative placed as a third field); the predictions gain 'required' ([word, position or None] per word), the stats
     # required_rate and required_moved_rate (a dict of these two alone when no language scores were asked for).  Image keys: eval_kwargs['image_keys'], else 0 .. N - 1
     keys = kw.get("image_keys")
     required = required_of(kw, kw.get("vocab") or getattr(model, "vocab", None), list(keys) if keys is not None else list(range(len(feats))), mode, sample_n,
@@ -448,7 +509,7 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
         ragged = is_region_source(feats)
         host = feats if ragged else _torch_feats(feats)
         if required is not None:
-            refine["require_phrases" if required_phrases(required[0]) else "require_ids"] = [required[0][j:j + batch_size] for j in range(0, N, batch_size)]
+            refine[required_key(required[0])] = [required[0][j:j + batch_size] for j in range(0, N, batch_size)]
         with torch.no_grad():
             if mode == "NAIC" and ragged:                       # staged ragged batch by batch, ahead of the launches that consume them
                 for r in model.decode_many((feats.ragged(j, min(j + batch_size, N)) for j in range(0, N, batch_size)), batches_per_launch=int(kw.get("batches_per_launch", 16)),
@@ -491,7 +552,8 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
                 predictions.extend(with_regions(entry_of(i, k, seq, r["phrase_num"], r["phrase_length"], r["entropy"], r["perplexity"], vocab), r, k) for k in range(seq.size(0)))
                 if required is not None:
                     for k in range(seq.size(0)):
-                        predictions[i + k]["required"] = required_entry(required[1][i + k], r["required_pos"][k]) if "required_pos" in r else []
+                        predictions[i + k]["required"] = (required_entry(required[1][i + k], r["required_pos"][k], *((r["required_alt"][k], required[2][i + k]) if "required_alt" in r else ()))
+                                                          if "required_pos" in r else [])
                 i += seq.size(0)
         if refine["refine_method"] == "mask_predict":
             kw["refine_round"] = torch.cat(rounds)

@@ -25,6 +25,7 @@ FORK_IDS_ONLY = 1
 ABI_VERSION = 5
 REQUIRE_MAX = 8                     # BOFI_REQUIRE_MAX: required words per image (bofi_vocab_require)
 REQUIRE_UNIT_MAX = 4                # BOFI_REQUIRE_UNIT_MAX: ids per required unit (bofi_vocab_require_units)
+REQUIRE_ALT_MAX = 4                 # BOFI_REQUIRE_ALT_MAX: alternatives per required group (bofi_vocab_require_any)
 NBEST_MAX = 8                       # BOFI_NBEST_MAX: captions per image of bofi_vocab_nbest
 NBEST_NR_MAX = 6                    # BOFI_NBEST_NR_MAX: ... of bofi_vocab_nbest_norepeat (its N + 2 candidates per row are the candidates launch's 8)
 
@@ -143,6 +144,7 @@ SIGNATURES = {
     "bofi_vocab_pick": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _I64, _P]),
     "bofi_vocab_require": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "bofi_vocab_require_units": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "bofi_vocab_require_any": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "bofi_vocab_nbest_workspace": (_I64, [_I]),
     "bofi_vocab_nbest": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _I64, _P]),
     "bofi_vocab_nbest_norepeat": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I64, _P]),
@@ -520,6 +522,128 @@ def vocab_require_units(x, V, S, seq, units, pos, *, ntok=None, ntok_bias=0, ban
     check(lib().bofi_vocab_require_units(ptr(x), x.stride(0), rows, int(V), int(S), ptr(ntok), int(ntok_bias), ptr(units), int(K), int(L), ptr(ban),
                                          1 if no_repeat else 0, int(repeat_min_id), ptr(seq), ptr(row_chosen), ptr(pos), ptr(moved), stream_ptr()),
           "bofi_vocab_require_units")
+
+
+_ANY_NESTING = "a group is a list of alternatives, each a list of ids -- [[[3], [4, 5]]] is one group of two alternatives, [3] and [4, 5]"
+
+
+def require_any_table(require_any, B: int, V: int, ban_ids=(), no_repeat: bool = False, repeat_min_id: int = 7):
+    """The [B, K, A, L] int32 table of ``bofi_vocab_require_any`` (host tensor, -1 padding) from host-side input: per image a list of GROUPS, each a list of 1 ..
+    ``REQUIRE_ALT_MAX`` alternatives, each a list of 1 .. ``REQUIRE_UNIT_MAX`` ids; one flat list of groups applied to every image; or a [B, K, A, L] ([K, A, L]: every
+    image) int array with -1 padding, an alternative being its leading run of ids.  None when nothing is required (no input, empty lists).
+    Checked here, each refusal naming the offender: ids in 0..V-1, alternatives of at most ``REQUIRE_UNIT_MAX`` ids, at most ``REQUIRE_ALT_MAX`` alternatives per group, at
+    most ``REQUIRE_MAX`` groups per image, no id of ``ban_ids``, no alternative given twice for an image (in one group or across groups: the kernel would skip the later
+    one); under ``no_repeat`` no alternative with two equal adjacent words (ids >= ``repeat_min_id``) and no two alternatives of DIFFERENT groups that could meet at a
+    shared word (the last id of one is the first of the other).  Groups without an alternative are dropped; an empty alternative keeps its place inside its group (an
+    empty slot of the table), so that the kernel's ``which`` indexes the group as it was given."""
+    import numpy as np
+    import torch
+    if require_any is None:
+        return None
+    if isinstance(require_any, torch.Tensor):
+        require_any = require_any.cpu().numpy()
+    if isinstance(require_any, np.ndarray):
+        if require_any.ndim not in (3, 4):
+            raise BofiHipError("require_any: a [B, K, A, L] table, per image a list of groups (each a list of alternatives, each a list of ids), or one flat list of groups")
+        run = lambda u: u[:next((i for i, v in enumerate(u) if v < 0), len(u))]
+        groups_of = lambda r: [[run(u) for u in g] for g in r]
+        require_any = [groups_of(require_any.tolist())] * B if require_any.ndim == 3 else [groups_of(r) for r in require_any.tolist()]
+    is_id = lambda v: isinstance(v, (int, np.integer))
+    rows = list(require_any)
+    if any(is_id(g) for g in rows):
+        raise BofiHipError(f"require_any: got the bare id {int(next(g for g in rows if is_id(g)))}: {_ANY_NESTING}")
+    for g in rows:                                               # one flat list of groups: its first non-empty alternative holds ids, not lists
+        first = next((u for u in (g if g is not None else ()) if is_id(u) or (u is not None and len(u))), None)
+        if first is None:
+            continue
+        if is_id(first):
+            raise BofiHipError(f"require_any: got the bare id {int(first)} where an alternative is expected: {_ANY_NESTING}")
+        if is_id(first[0]):
+            rows = [rows] * B
+        break
+    if not rows:
+        return None
+    if len(rows) != B:
+        raise BofiHipError(f"require_any: {len(rows)} rows for {B} images")
+    ban = {int(i) for i in ban_ids or ()}
+    clean = []
+    for r in rows:
+        groups, seen = [], []                                    # seen: (group index, alternative) of the image so far
+        for g in (r if r is not None else ()):
+            if is_id(g):
+                raise BofiHipError(f"require_any: got the bare id {int(g)} where a group is expected: {_ANY_NESTING}")
+            alts = []
+            for u in (g if g is not None else ()):
+                if is_id(u):
+                    raise BofiHipError(f"require_any: got the bare id {int(u)} where an alternative is expected: {_ANY_NESTING}")
+                if any(not is_id(i) for i in u):
+                    raise BofiHipError(f"require_any: an alternative is a list of ids, got {list(u)}: {_ANY_NESTING}")
+                u = [int(i) for i in u]
+                alts.append(u)
+                if not u:
+                    continue
+                if len(u) > REQUIRE_UNIT_MAX:
+                    raise BofiHipError(f"require_any: an alternative holds at most {REQUIRE_UNIT_MAX} ids, got {u}")
+                for i in u:
+                    if not 0 <= i < V:
+                        raise BofiHipError(f"require_any: ids must lie in 0..{V - 1}, got {i} in alternative {u}")
+                    if i in ban:
+                        raise BofiHipError(f"require_any: id {i} of alternative {u} is also in ban_ids")
+                if no_repeat and any(x == y and x >= repeat_min_id for x, y in zip(u, u[1:])):
+                    raise BofiHipError(f"require_any: alternative {u} repeats a word (not under no_repeat)")
+                for j, v in seen:
+                    if v == u:
+                        raise BofiHipError(f"require_any: alternative {u} is given twice " + ("in one group" if j == len(groups) else "(in two groups)"))
+                    if no_repeat and j != len(groups) and _units_meet(v, u, int(repeat_min_id)):
+                        raise BofiHipError(f"require_any: alternatives {v} and {u} of different groups could meet at a shared word and form an adjacent repeat "
+                                           "(not under no_repeat)")
+                seen.append((len(groups), u))
+            while alts and not alts[-1]:
+                alts.pop()
+            if len(alts) > REQUIRE_ALT_MAX:
+                raise BofiHipError(f"require_any: a group holds at most {REQUIRE_ALT_MAX} alternatives, got {len(alts)}: {alts}")
+            if alts:
+                groups.append(alts)
+        if len(groups) > REQUIRE_MAX:
+            raise BofiHipError(f"require_any: at most {REQUIRE_MAX} required groups per image, got {len(groups)}")
+        clean.append(groups)
+    K = max(len(r) for r in clean)
+    if K == 0:
+        return None
+    A = max(len(g) for r in clean for g in r)
+    L = max(len(u) for r in clean for g in r for u in g)
+    t = np.full((B, K, A, L), -1, np.int32)
+    for b, r in enumerate(clean):
+        for j, g in enumerate(r):
+            for a, u in enumerate(g):
+                t[b, j, a, :len(u)] = u
+    return torch.from_numpy(t)
+
+
+def vocab_require_any(x, V, S, seq, alts, pos, which, *, ntok=None, ntok_bias=0, ban=None, no_repeat=False, repeat_min_id=7, row_chosen=None, moved=None):
+    """``bofi_vocab_require_any`` on torch tensors: as ``vocab_require_units`` with alts int32 [rows / S, K, A, L] (1 <= K <= ``REQUIRE_MAX``, 1 <= A <=
+    ``REQUIRE_ALT_MAX``, 1 <= L <= ``REQUIRE_UNIT_MAX``) in place of the units, pos int32 [rows / S, K] the start of each group's placed alternative and which int32
+    [rows / S, K] its index in the group (-1: not placed).  One launch on the current stream, no synchronisation."""
+    import torch
+    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or not x.is_cuda:
+        raise BofiHipError("vocab_require_any: x must be a 2-d float32 device tensor with unit column stride")
+    rows = x.size(0)
+    if x.size(1) < V or S < 1 or rows % S:
+        raise BofiHipError("vocab_require_any: x needs V columns and a multiple of S rows")
+    B = rows // S
+    if alts is None or alts.dim() != 4 or alts.size(0) != B:
+        raise BofiHipError(f"vocab_require_any: alts must be int32 [{B}, K, A, L]")
+    K, A, L = alts.size(1), alts.size(2), alts.size(3)
+    for name, t, dt, n in (("seq", seq, torch.int64, rows), ("alts", alts, torch.int32, B * K * A * L), ("pos", pos, torch.int32, B * K), ("which", which, torch.int32, B * K),
+                           ("ntok", ntok, torch.int32, B), ("ban", ban, torch.int32, (V + 31) // 32), ("row_chosen", row_chosen, torch.float32, rows),
+                           ("moved", moved, torch.int32, B)):
+        if t is None and name not in ("seq", "alts", "pos", "which"):
+            continue
+        if t is None or t.dtype != dt or t.numel() != n or not t.is_cuda or not t.is_contiguous():
+            raise BofiHipError(f"vocab_require_any: {name} must be a contiguous {dt} device tensor of {n} elements")
+    check(lib().bofi_vocab_require_any(ptr(x), x.stride(0), rows, int(V), int(S), ptr(ntok), int(ntok_bias), ptr(alts), int(K), int(A), int(L), ptr(ban),
+                                       1 if no_repeat else 0, int(repeat_min_id), ptr(seq), ptr(row_chosen), ptr(pos), ptr(which), ptr(moved), stream_ptr()),
+          "bofi_vocab_require_any")
 
 
 def vocab_nbest(x, V, S, N, *, ntok=None, ntok_bias=0, pad_idx=0, ban=None, seq_n=None, total=None, count=None, work=None):

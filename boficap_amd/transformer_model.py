@@ -243,7 +243,7 @@ class TransformerModel(nn.Module):
 
     def decode_many(self, batches, *, batches_per_launch: int = 16, in_flight: Optional[int] = None, stats: bool = True, keep_logprob: bool = False,
                     fused_vocab: bool = False, refine_rounds: int = 0, refine_method: str = "feed_back", attn_topk: int = 0, keep_attn: bool = False,
-                    ban_ids=None, no_repeat: bool = False, block_trigrams: bool = False, require_ids=None, require_phrases=None):
+                    ban_ids=None, no_repeat: bool = False, block_trigrams: bool = False, require_ids=None, require_phrases=None, require_any=None):
         """Greedy NAIC decode of MANY loader batches at the engine's throughput -- the eval loop of the reference (eval_utils.py:456-460: one synchronised
         ``model(..., mode='sample')`` per batch, which is what ``_sample`` reproduces) as a pipeline: ``in_flight`` engine forks on overlapping streams,
         ``batches_per_launch`` consecutive batches per launch (quirk Q1 per batch: every batch's result is its own decode's), features copied from (pinned)
@@ -267,7 +267,10 @@ class TransformerModel(nn.Module):
         carries required_pos int32 [b, K] and required_moved int32 [b], and equals that batch's own decode.  Not with ``fused_vocab``, 'mask_predict' or ``block_trigrams``.
         ``require_phrases``: required multi-word units (``BofiEngine.decode_naic(require_phrases=...)``: the ids of a unit side by side, on the cheapest span) in the same
         two forms -- per-batch tables (each a list of b unit lists, one flat list of units for the batch, or None), or one flat list of units for every image; the same
-        keys (required_pos holds the units' start positions) and refusals.  Not together with ``require_ids``."""
+        keys (required_pos holds the units' start positions) and refusals.  Not together with ``require_ids``.
+        ``require_any``: required alternatives (``BofiEngine.decode_naic(require_any=...)``: groups of alternatives, any one of which satisfies its group) in the same two
+        forms -- per-batch tables (each a list of b group lists, one flat list of groups for the batch, or None), or one flat list of groups for every image; every batch's
+        dict carries required_pos, required_alt int32 [b, K] (the placed alternative's index) and required_moved.  Not together with the other two."""
         from .engine import DecodePipeline
         eng = self.engine()
         ban_ids = tuple(sorted({int(i) for i in ban_ids})) if ban_ids is not None else ()
@@ -295,7 +298,7 @@ class TransformerModel(nn.Module):
                 else:
                     masks = torch.from_numpy(masks) if not torch.is_tensor(masks) else masks
                     yield att.contiguous(), masks.long().sum(1).to(torch.int32).contiguous()
-        return cached[1].run(items(), require_ids=require_ids, require_phrases=require_phrases)
+        return cached[1].run(items(), require_ids=require_ids, require_phrases=require_phrases, require_any=require_any)
 
     def _sample(self, fc_feats, att_feats, att_masks=None, opt={}):
         """AttModel.py:307-338, 419-437 for train_mode 'NAIC' (bound+fill) and 'SAIC' (phrase by phrase)."""
@@ -378,6 +381,19 @@ class TransformerModel(nn.Module):
             if refine_method == "mask_predict":
                 raise hip.BofiHipError("require_phrases: not with refine_method='mask_predict'")
             rkw.update(require_phrases=require_phrases)
+        # opt['require_any']: required alternatives (BofiEngine.decode_naic(require_any=...): groups of alternatives, any one of which satisfies its group); the same
+        # refusals; self.last_required gains 'alt' (the placed alternative's index per group) for this option only; not with the other two
+        require_any = opt.get("require_any")
+        if require_any is not None and (torch.is_tensor(require_any) or len(require_any)):
+            if "require_ids" in rkw or "require_phrases" in rkw:
+                raise hip.BofiHipError("require_ids / require_phrases and require_any: give one (a word or a unit is a group of one alternative)")
+            if train_mode != "NAIC":
+                raise hip.BofiHipError("require_any place words on the non-autoregressive filling pass: train_mode 'NAIC' only")
+            if sample_method == "sample":
+                raise hip.BofiHipError("require_any place words on greedy picks: not with sample_method='sample'")
+            if refine_method == "mask_predict":
+                raise hip.BofiHipError("require_any: not with refine_method='mask_predict'")
+            rkw.update(require_any=require_any)
         # opt['nbest'] = N in 1..8: the N most probable captions of the NAIC filling pass (BofiEngine.decode_naic(nbest=N): exact, one decode plus two small launches); the
         # 6-tuple stays, the lists land in self.last_nbest ({'seq' int64 [B, N, S], 'logp' float64 [B, N], 'count' int32 [B]}, per image -- not repeated under sample_n;
         # None without the option).  The refusals are the engine's, raised here before anything is enqueued
@@ -403,8 +419,8 @@ class TransformerModel(nn.Module):
             if no_repeat or block_trigrams:
                 raise hip.BofiHipError("nbest: not with decoding_constraint / block_trigrams (a rule that couples neighbours needs per-last-id state: a width-N list "
                                        "is no longer exact)")
-            if "require_ids" in rkw or "require_phrases" in rkw:
-                raise hip.BofiHipError("nbest: not with require_ids / require_phrases (the list is of unforced captions)")
+            if "require_ids" in rkw or "require_phrases" in rkw or "require_any" in rkw:
+                raise hip.BofiHipError("nbest: not with require_ids / require_phrases / require_any (the list is of unforced captions)")
             rkw.update(nbest=nbest)
             if nbest_nr:
                 rkw.update(nbest_no_repeat=True)
@@ -441,7 +457,7 @@ class TransformerModel(nn.Module):
                 keys = (("attn",) if attn_maps else ()) + (("attn_top", "attn_top_w") if attn_topk else ())
                 self.last_attn = {k: (r[k].repeat_interleave(sample_n, dim=0) if sample_n > 1 else r[k]) for k in keys}
             if "required_pos" in r:
-                self.last_required = {k: (r["required_" + k].repeat_interleave(sample_n, dim=0) if sample_n > 1 else r["required_" + k]) for k in ("pos", "moved")}
+                self.last_required = {k: (r["required_" + k].repeat_interleave(sample_n, dim=0) if sample_n > 1 else r["required_" + k]) for k in ("pos", "moved") + (("alt",) if "required_alt" in r else ())}
             if "nbest_seq" in r:
                 self.last_nbest = {"seq": r["nbest_seq"], "logp": r["nbest_logp"], "count": r["nbest_count"]}
             if "ban_ids" in rkw:

@@ -880,6 +880,41 @@ int bofi_vocab_require(const float* x, int ldx, int rows, int V, int S, const in
 int bofi_vocab_require_units(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, const int* units, int K, int L, const uint32_t* ban_bits,
                              int no_repeat, int repeat_min_id, int64_t* seq, float* row_chosen, int* pos, int* moved, void* stream);
 
+/* Required ALTERNATIVES: bofi_vocab_require_units with GROUPS of units, any one of which satisfies the group -- "dog", "dogs" or "puppy"; "fire hydrant" or "hydrant": a
+ * detector tag or an object name is a set of surface forms, and the caption must hold one of them.  Still exact: the masks of the recurrence range over groups, and a
+ * state has K * A options "p takes alternative a of group j" instead of K.  A stand-alone launch behind the decode call, as bofi_vocab_require_units: no field of
+ * bofi_call_opts_t, no engine state, the ABI version is unchanged.
+ * Inputs: bofi_vocab_require_units's (x, ldx, rows, V, S, ntok, ntok_bias, ban_bits, no_repeat, repeat_min_id, seq; n_b = clamp(ntok[b] + ntok_bias, 0, S)), except the table:
+ *   alts[b, 0 .. K-1, 0 .. A-1, 0 .. L-1] int32, 1 <= K <= BOFI_REQUIRE_MAX, 1 <= A <= BOFI_REQUIRE_ALT_MAX, 1 <= L <= BOFI_REQUIRE_UNIT_MAX.  Group j is a requirement;
+ *   its alternatives are units as bofi_vocab_require_units reads them: the length len_c of a unit is its run of leading ids >= 0; the entries after the first negative
+ *   id are not read as ids.  The SLOT of alternative a of group j is c = j * A + a; slot order is table order.
+ * Slots of a row, classified per image in slot order: slot c is EMPTY when its first id is < 0.  It is SKIPPED when one of its ids is >= V; one of its ids is banned by
+ * ban_bits; it equals an earlier slot of the row (same length, same ids), of any group, kept or not; and, with no_repeat = 1: it holds two equal adjacent ids >=
+ * repeat_min_id; its first id (>= repeat_min_id) equals the last id of an earlier KEPT slot of ANOTHER GROUP of the row; or its last id (>= repeat_min_id) equals the first
+ * id of such a slot.  Every other slot is kept.  The last two cases exist because two placed units could otherwise meet and form an adjacent repeat (the units' rule, for
+ * the units' reason); alternatives of one group are never both placed, so they cannot meet and are not checked against each other for that.  A GROUP is kept when at least
+ * one of its slots is.  The host side (require_any_table) refuses a skipped alternative by name.
+ * Span "slot c starts at p": it needs p + len_c <= n_b.  Position p + i (i < len_c) contributes 0 where seq[p+i] == u_i on entry; otherwise (double)x[p+i, u_i] -
+ * (double)x[p+i, seq[p+i]] when both operands are finite; anything else makes the span INELIGIBLE (NaN, +-inf, a seq[p+i] outside 0..V-1).  With no_repeat = 1 the span
+ * is also ineligible when u_0 >= repeat_min_id, seq[p] != u_0 and the live left neighbour holds u_0 on entry (p > 0, seq[p-1] == u_0), or when u_last >= repeat_min_id,
+ * seq[p+len_c-1] != u_last and the live right neighbour holds u_last on entry (p + len_c < n_b, seq[p+len_c] == u_last): a placement never creates an adjacent repeat.
+ * gain[p][c] is the float64 sum 0.0 + t_0 + t_1 + ... of the span's per-position terms, left to right.
+ * Recurrence and tie-break: best[n_b][m] = (0 groups, 0.0) for every mask m of kept GROUPS still to satisfy.  For p = n_b - 1 .. 0 and each m the options are taken in
+ * this order: "p takes slot c" for j ascending over the groups of m and, within j, for a ascending over its kept slots c = j * A + a with an eligible span at p, value
+ * (1 + cnt, gain[p][c] + tot) of best[p + len_c][m \ j]; then "p keeps its id", value best[p+1][m].  Option values compare first by count, then by total; the FIRST option
+ * that attains the maximum is choice[p][m].  The result is the forward walk from (0, all kept groups) along choice, which advances by len_c over a placed span.  For
+ * A = 1 this is bofi_vocab_require_units's rule, bit for bit (seq, row_chosen, pos, moved).
+ * Outputs: seq -- rewritten on the placed spans, all else untouched; row_chosen (may be NULL) -- x[p+i, u_i] at every span position, all else untouched; pos int32 [B, K]
+ * -- the START position of the group's placed alternative, -1 every slot of the group empty, -2 no slot kept and at least one skipped, -3 group kept but not placeable;
+ * which int32 [B, K] (may NOT be NULL) -- the index a of the placed alternative, -1 where the group was not placed; moved int32 [B] (may be NULL) -- positions whose id
+ * changed.  x is read only.
+ * The entry point is total: any table contents, any ntok and ids outside the vocabulary in seq give the rule's result, with no read out of range.
+ * One launch, no workspace, deterministic, no atomics; the only float arithmetic is the float64 differences and sums above, in the order above.  rows = 0 is BOFI_OK
+ * without a launch.  BOFI_ERR_ARG with a message and no launch: what bofi_vocab_require_units refuses (alts in place of units), a NULL which, A outside 1..4. */
+#define BOFI_REQUIRE_ALT_MAX 4
+int bofi_vocab_require_any(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, const int* alts, int K, int A, int L, const uint32_t* ban_bits,
+                           int no_repeat, int repeat_min_id, int64_t* seq, float* row_chosen, int* pos, int* which, int* moved, void* stream);
+
 /* The N most probable captions of a filling pass, exactly -- the reference's sample_n_method = 'bs' (the N best of a beam) for the non-autoregressive decode, where it is
  * no search: the pass scores every position on its own, a caption's log-probability is a sum of per-position terms, the N best captions use only each row's N best ids,
  * and a width-N merge over the positions finds them.  A stand-alone call behind the decode: no field of bofi_call_opts_t, no engine state, the ABI version is unchanged.

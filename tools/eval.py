@@ -28,7 +28,9 @@ test.  Both need the words' ids: ``--infos_path`` (a vocabulary), or ``--bad_end
 ``--require_words W1,W2,...`` (every image) or ``--require_words_json FILE`` ({image id: [words]}) (NAIC) places the words in the captions where they cost the least
 log-prob (boficap_amd.eval_utils.required_of; at most 8 per image): the predictions gain ``required`` ([word, position or null] per word) and a line reports
 ``required_rate`` (words placed / words required) and ``required_moved_rate``.  An item with a space is a phrase of up to 4 words (``"fire hydrant,dog"``): its
-words go side by side on the cheapest span, ``required`` holds [phrase, start position or null], and the rates count units.
+words go side by side on the cheapest span, ``required`` holds [phrase, start position or null], and the rates count units.  An item with ``|`` is a set of up to 4
+alternatives, any one of which satisfies it (``"dog|dogs,fire hydrant|hydrant"``): the cheapest one is placed, ``required`` holds [item, start position or null, the
+alternative placed or null], and the rates count items.
 ``--sample_n N --sample_n_method nbest`` (NAIC, N <= 8) takes the N most probable captions of the filling pass -- exact, from one decode -- in place of N random
 draws: ``preds_n`` entries gain ``logp``, the statistics ``nbest_short``.
 ``--nbest_no_repeat 1`` (with ``--sample_n_method nbest``, N <= 6) makes that list the N most probable captions with no adjacent repeated word -- exact too (a
@@ -114,9 +116,10 @@ def main():
                     "paths only and as a penalty; here a hard block)")
     ap.add_argument("--ban_words", default="", help="NAIC only: W1,W2,... never appear in a caption (resolved to ids as --bad_endings resolves its words)")
     ap.add_argument("--require_words", default="", help="NAIC only: W1,W2,... appear in every caption -- each placed on the position where it costs the least log-prob; "
-                    "an item with a space is a phrase of up to 4 words ('fire hydrant,dog'), placed side by side on the cheapest span "
+                    "an item with a space is a phrase of up to 4 words ('fire hydrant,dog'), placed side by side on the cheapest span; an item with '|' is a set of up to 4 alternatives, any one of which "
+                    "satisfies it ('dog|dogs,fire hydrant|hydrant'): the cheapest is placed "
                     "(eval_kwargs['require_words']; the predictions gain 'required', the statistics required_rate and required_moved_rate)")
-    ap.add_argument("--require_words_json", default="", help="NAIC only: a JSON file {image id: [W1, W2, ...]} of required words and phrases per image (the ids of --input_json, else "
+    ap.add_argument("--require_words_json", default="", help="NAIC only: a JSON file {image id: [W1, W2, ...]} of required words, phrases and alternatives ('dog|dogs') per image (the ids of --input_json, else "
                     "the images' indices); not together with --require_words")
     args = ap.parse_args()
     if args.require_words and args.require_words_json:
@@ -229,7 +232,7 @@ def main():
     pick = eval_utils.constraint_of(vars(args), vocab or opt.vocab, args.inference_mode, args.sample_n)
     pick_opt = {"ban_ids": pick["ban_ids"], "decoding_constraint": int(pick["no_repeat"]), "block_trigrams": int(pick.get("block_trigrams", False))} if pick else {}      # (the same, in mode='sample''s names)
     # --require_words / --require_words_json: per-batch id tables for decode_many (opt['require_ids'] per call on the synchronised path)
-    required, req_kw, req_pos, req_moved = None, [], [], 0
+    required, req_kw, req_pos, req_moved, req_alt = None, [], [], 0, []
     if args.require_words or args.require_words_json:
         if args.require_words_json:
             with open(args.require_words_json) as f:
@@ -243,7 +246,7 @@ def main():
             ap.error(str(e))
         if required is not None:
             req_kw = [required[0][i:i + args.batch_size] for i in range(0, len(feats), args.batch_size)]
-            req_key = "require_phrases" if eval_utils.required_phrases(required[0]) else "require_ids"      # (an item with a space is a phrase: units of ids)
+            req_key = eval_utils.required_key(required[0])      # (an item with a space is a phrase: units of ids; an item with '|' a group of alternatives)
 
     def req(n=None):
         return {req_key: req_kw[:n]} if required is not None else {}
@@ -336,6 +339,8 @@ def main():
                     last = model.last_required
                     req_pos.extend(last["pos"].cpu() if last is not None else [torch.empty(0, dtype=torch.int32)] * b)
                     req_moved += int(last["moved"].sum()) if last is not None else 0
+                    if req_key == "require_any":
+                        req_alt.extend(last["alt"].cpu() if last is not None else [torch.empty(0, dtype=torch.int32)] * b)
                     emitted += 0 if pick else int(pl.sum())
                 if pick:
                     changed, emitted = changed + int(model.last_constrained.sum()), emitted + int(pl.sum())
@@ -354,7 +359,12 @@ def main():
         emitted = sum(int(r["phrase_length"].sum()) for r in got)
         req_pos = [row for r in got for row in (r["required_pos"] if "required_pos" in r else [torch.empty(0, dtype=torch.int32)] * r["seq"].size(0))]
         req_moved = sum(int(r["required_moved"].sum()) for r in got if "required_moved" in r)
-    if required is not None:
+        if req_key == "require_any":
+            req_alt = [row for r in got for row in (r["required_alt"] if "required_alt" in r else [torch.empty(0, dtype=torch.int32)] * r["seq"].size(0))]
+    if required is not None and req_key == "require_any":
+        for e, ws, row, alt, texts in zip(results, required[1], req_pos, req_alt, required[2]):
+            e["required"] = eval_utils.required_entry(ws, row, alt, texts)
+    elif required is not None:
         for e, ws, row in zip(results, required[1], req_pos):
             e["required"] = eval_utils.required_entry(ws, row)
     if image_ids is not None:                                    # the json's ids, in the split's order
