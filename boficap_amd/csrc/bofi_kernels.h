@@ -252,6 +252,12 @@ const char* vocab_nbest_norepeat_check(const float* x, int ldx, int rows, int V,
                                        const int* count, const void* work, size_t work_bytes);      // NULL, or what is wrong (BOFI_ERR_ARG)
 int launch_vocab_nbest_norepeat(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int repeat_min_id,
                                 int N, int64_t* seq_n, double* total, int* count, void* work, size_t work_bytes, hipStream_t st);
+// the Hamming-diverse set of N captions (bofi_vocab_diverse states the rule): the candidates launch, then vocab_diverse_kernel, a wavefront per image; pen[k] = lambda * k
+// is made on the host; the workspace is vocab_nbest_work_bytes(rows)
+const char* vocab_diverse_check(const float* x, int ldx, int rows, int V, int S, int N, double lambda, int no_repeat, int repeat_min_id, const int64_t* seq_n,
+                                const double* total, const double* aug, const int* count, const void* work, size_t work_bytes);      // NULL, or what is wrong (BOFI_ERR_ARG)
+int launch_vocab_diverse(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int N, double lambda,
+                         int no_repeat, int repeat_min_id, int64_t* seq_n, double* total, double* aug, int* count, void* work, size_t work_bytes, hipStream_t st);
 // ---- required words behind the filling pass (force.hip): the placement of at most 8 ids per image that costs the least log-prob (bofi_vocab_require states the rule);
 // ntok / ban_bits / row_chosen / moved may be NULL.  One launch, no workspace
 const char* vocab_require_check(const float* x, int ldx, int rows, int V, int S, const int* words, int K, int no_repeat, int repeat_min_id, const int64_t* seq,

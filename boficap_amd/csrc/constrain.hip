@@ -24,6 +24,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <cmath>
 #include <string>
 
 #include "bofi_common.h"
@@ -658,6 +659,159 @@ __global__ void __launch_bounds__(NR_W * WAVE) vocab_nbest_norepeat_kernel(NbArg
     nb_write_captions(a, b, out, tid, NR_W * WAVE);
 }
 
+// ---- the Hamming-diverse caption set (bofi_vocab_diverse): the reference's diverse beam search ('dbs': groups decoded one after another, each pushed away from the words
+// the earlier groups put at the same position, CaptionModel.py:51-68) for the pass that scores every position on its own.  The augmented score of a caption is a sum of
+// per-position terms, so every group's caption is the exact maximiser of its objective: a per-position pick, or with "no adjacent repeated word" a Viterbi over each
+// row's candidates; include/boficap_hip.h, bofi_vocab_diverse, states the rule, tests/test_diverse_set.py restates it in numpy and holds it to a brute force.
+//   candidates  the K-candidate launch above, unchanged (seq = NULL), as for the lists; K = N, or N + 2 under the repeat rule
+//   groups      one wavefront per image, four images per workgroup; the lists' front end (ids to LDS, a cut row streamed again, the scattered value loads), behind
+//               which LDS is only read and the kernel holds no barrier.  What changes from group to group stays in registers, lane = position: the counts of a row's
+//               candidates as eight 4-bit fields of one word, the back-pointers of a row's eight states as a byte each of a 64-bit word.
+//               no_repeat = 0: lane = position; a pass is one compare chain over the row's candidates.
+//               no_repeat = 1: lane = r * 8 + r' is the pair (state r of row p, predecessor r' of row p - 1).  A step: the lane fetches V_{p-1}[r'] from the lanes of
+//               state r' (a cross-lane read), adds its state's value -- one float64 add per pair --, the maximum over r' is a three-step butterfly inside the 8-lane
+//               group on (has a V, value, then lower r'), three ballots pack the states' back-pointers for lane p.  The end state by a butterfly across the groups, the
+//               walk back by scalar reads of the packed words.
+//               The totals are summed left to right by reading lane after lane: that order is part of the rule.
+// No atomics; the only float arithmetic is the float64 subtraction of a table entry (the table lambda * k comes from the host: the kernel never multiplies, nothing
+// contracts) and the float64 adds.
+constexpr int DV_IPW = 4;                      // images (wavefronts) per workgroup
+constexpr int DV_PEN = 16;                     // the table in LDS: a 4-bit count indexes it
+static_assert(BOFI_DIVERSE_MAX == VP_K && BOFI_DIVERSE_NR_MAX + 2 <= VP_K && VP_K * VP_K == WAVE, "the candidates launch leaves VP_K ids per row; the lanes hold every pair");
+static_assert(BOFI_DIVERSE_MAX < DV_PEN, "a count fits its 4-bit field");
+
+struct DvArgs {
+    NbArgs nb;                                 // (seq_n, total, count: the set's)
+    double pen[BOFI_DIVERSE_MAX];              // pen[k] = lambda * k, made on the host
+    double* aug;
+    int lo;                                    // repeat_min_id
+};
+
+// is (ok2, v2, i2) in front of (ok1, v1, i1)?  An entry that holds a value before one that does not, the larger value, then the lower index
+__device__ __forceinline__ bool dv_front(bool ok2, double v2, int i2, bool ok1, double v1, int i1) {
+    return ok2 && (!ok1 || v2 > v1 || (v2 == v1 && i2 < i1));
+}
+
+// one butterfly step at lane distance o: both partners keep the entry in front
+__device__ __forceinline__ void dv_step(bool& ok, double& v, int& i, int o) {
+    const bool ok2 = __shfl_xor((int)ok, o, WAVE) != 0;
+    const double v2 = __shfl_xor(v, o, WAVE);
+    const int i2 = __shfl_xor(i, o, WAVE);
+    if (dv_front(ok2, v2, i2, ok, v, i)) { ok = ok2; v = v2; i = i2; }
+}
+
+__device__ __forceinline__ uint64_t dv_readlane64(uint64_t w, int p) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)w, p), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(w >> 32), p);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+template <bool NR>
+__global__ void __launch_bounds__(DV_IPW * WAVE) vocab_diverse_kernel(DvArgs d, const int* __restrict__ work) {
+    __shared__ int cid_[DV_IPW][VC_MAX_S * VP_K];               // c[p][r]; VC_NONE: the row has no such id
+    __shared__ float xv_[DV_IPW][VC_MAX_S * VP_K];              // x[p, c[p][r]]; NaN where there is no id
+    __shared__ double pen[DV_PEN];
+    const NbArgs& a = d.nb;
+    const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE, b = __builtin_amdgcn_readfirstlane(blockIdx.x * DV_IPW + wave);
+    const bool on = b < a.B;                                    // (a wavefront past B stays for the barriers and touches no global memory)
+    const int S = a.S, N = a.N, V = a.V, K = NR ? N + 2 : N;
+    int* const cid = cid_[wave];
+    float* const xv = xv_[wave];
+    const int n = __builtin_amdgcn_readfirstlane(on ? live_count(a.ntok, a.ntok_bias, b, S) : 0);
+    const size_t row0 = (size_t)(on ? b : 0) * S;
+    if (threadIdx.x < DV_PEN) pen[threadIdx.x] = threadIdx.x < BOFI_DIVERSE_MAX ? d.pen[threadIdx.x] : 0.0;
+    // the lists' front end, K entries a row
+    const int cutk = nb_ids(work, row0, n, K, V, cid, lane);   // lane = position
+    __syncthreads();
+    nb_cut_rows(a, row0, K, cutk, cid, lane);
+    __syncthreads();
+    nb_values(a, row0, n, cid, xv, lane, WAVE);
+    __syncthreads();
+    if (!on) return;                                            // (no barrier from here on: LDS is only read)
+    const double NINF = -(double)INFINITY;
+    const size_t o0 = (size_t)b * N;                            // the image's first entry of total / aug; its rows of seq_n follow from it
+    const bool degen = nb_degen(xv, n, lane);
+    if (degen || n == 0) {                                      // one caption: each live row's first id; NaN for a degenerate image, 0.0 for the empty one
+        int c0 = a.pad_idx;
+        if (lane < n && cid[lane * VP_K] != VC_NONE) c0 = cid[lane * VP_K];
+        if (lane < S)
+            for (int g = 0; g < N; ++g) a.seq_n[(o0 + g) * S + lane] = (int64_t)(g == 0 ? c0 : a.pad_idx);
+        if (lane < N) {
+            const double t = lane == 0 ? (degen ? (double)NAN : 0.0) : NINF;
+            a.total[o0 + lane] = t; d.aug[o0 + lane] = t;
+        }
+        if (lane == 0) a.count[b] = 1;
+        return;
+    }
+    uint32_t cnt = 0;                                           // lane = position: field r = the earlier groups that took c[p][r]
+    const int r = lane / VP_K, rp = lane % VP_K;                // (NR) this lane's pair: state r of row p, predecessor r' of row p - 1
+    for (int g = 0; g < N; ++g) {
+        int take = 0;                                           // lane = position: the candidate the group's caption has there
+        double aug = 0.0;
+        if (!NR) {
+            double ba = 0.0;
+            if (lane < n) {
+                bool have = false;
+#pragma unroll
+                for (int k = 0; k < VP_K; ++k) {
+                    const float v = xv[lane * VP_K + k];
+                    const double av = (double)v - pen[(cnt >> (4 * k)) & 15u];
+                    if (f32_finite(v) && (!have || av > ba)) { have = true; ba = av; take = k; }      // (ties to the lower k; entry 0 is finite here)
+                }
+            }
+            for (int p = 0; p < n; ++p) aug = aug + __shfl(ba, p, WAVE);      // left to right
+        } else {
+            uint64_t bpw = 0ull;                                // lane = position p: byte r = the predecessor of state r of row p
+            float v = xv[r];
+            bool has = f32_finite(v);
+            double Vc = 0.0 + ((double)v - pen[((uint32_t)__builtin_amdgcn_readlane((int)cnt, 0) >> (4 * r)) & 15u]);
+            for (int p = 1; p < n; ++p) {
+                v = xv[p * VP_K + r];
+                const int id = cid[p * VP_K + r], idp = cid[(p - 1) * VP_K + rp];
+                const double av = (double)v - pen[((uint32_t)__builtin_amdgcn_readlane((int)cnt, p) >> (4 * r)) & 15u];
+                const unsigned long long hm = __ballot(has);
+                const double Vp = __shfl(Vc, rp * VP_K, WAVE);  // V_{p-1}[r'], the same in every lane of state r'
+                bool ok = f32_finite(v) && ((hm >> (rp * VP_K)) & 1ull) && !(idp == id && idp >= d.lo);
+                double val = Vp + av;                           // one float64 add per pair
+                int br = rp;
+#pragma unroll
+                for (int o = 1; o < VP_K; o <<= 1) dv_step(ok, val, br, o);      // the 8-lane group's best pair, in every lane of it
+                Vc = val; has = ok;
+                const uint64_t one = 0x0101010101010101ull;
+                const uint64_t w = (__ballot(br & 1) & one) | ((__ballot(br & 2) & one) << 1) | ((__ballot(br & 4) & one) << 2);
+                if (lane == p) bpw = w;
+            }
+            int er = r;                                         // the end state: the best V_{n-1}[r], ties to the lower r
+#pragma unroll
+            for (int o = VP_K; o < WAVE; o <<= 1) dv_step(has, Vc, er, o);
+            if (!has) {                                         // no valid caption over the candidates, whatever the group (g = 0 here): count = 0
+                if (lane < S)
+                    for (int j = 0; j < N; ++j) a.seq_n[(o0 + j) * S + lane] = (int64_t)a.pad_idx;
+                if (lane < N) { a.total[o0 + lane] = NINF; d.aug[o0 + lane] = NINF; }
+                if (lane == 0) a.count[b] = 0;
+                return;
+            }
+            aug = Vc;
+            int rr = __builtin_amdgcn_readfirstlane(er);
+            for (int p = n - 1; p >= 0; --p) {                  // back along the predecessors
+                if (lane == p) take = rr;
+                if (p > 0) rr = (int)((dv_readlane64(bpw, p) >> (8 * rr)) & 7ull);
+            }
+        }
+        int id = a.pad_idx;
+        float own = 0.f;
+        if (lane < n) {
+            id = cid[lane * VP_K + take];
+            own = xv[lane * VP_K + take];
+            cnt += 1u << (4 * take);
+        }
+        double total = 0.0;
+        for (int p = 0; p < n; ++p) total = total + (double)__shfl(own, p, WAVE);      // the caption's own values, left to right
+        if (lane < S) a.seq_n[(o0 + g) * S + lane] = (int64_t)id;
+        if (lane == 0) { a.total[o0 + g] = total; d.aug[o0 + g] = aug; }
+    }
+    if (lane == 0) a.count[b] = N;
+}
+
 // ---- the host side
 VcArgs vc_args(const float* x, int ldx, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int no_repeat, int repeat_min_id, int64_t* seq,
                float* row_chosen, int* changed) {
@@ -749,6 +903,45 @@ extern "C" int bofi_vocab_nbest_norepeat(const float* x, int ldx, int rows, int 
         return bofi::fail(BOFI_ERR_ARG, std::string("vocab_nbest_norepeat: ") + why);
     return bofi::launch_vocab_nbest_norepeat(x, ldx, rows, V, S, ntok, ntok_bias, pad_idx, ban_bits, repeat_min_id, N, seq_n, total, count, work, (size_t)work_bytes,
                                              (hipStream_t)stream);
+}
+
+const char* bofi::vocab_diverse_check(const float* x, int ldx, int rows, int V, int S, int N, double lambda, int no_repeat, int repeat_min_id, const int64_t* seq_n,
+                                      const double* total, const double* aug, const int* count, const void* work, size_t work_bytes) {
+    if (!aug) return "non-null seq_n, total, aug and count";
+    if (no_repeat != 0 && no_repeat != 1) return "no_repeat 0 or 1";
+    if (const char* why = list_check(x, ldx, rows, V, S, no_repeat, repeat_min_id, N, no_repeat ? BOFI_DIVERSE_NR_MAX : BOFI_DIVERSE_MAX,
+                                     no_repeat ? "N in 1..6 under no_repeat (BOFI_DIVERSE_NR_MAX)" : "N in 1..8 (BOFI_DIVERSE_MAX)", seq_n, total, count, work, work_bytes))
+        return why;
+    if (!(lambda >= 0.0) || std::isinf(lambda)) return "a finite lambda >= 0";
+    return nullptr;
+}
+
+int bofi::launch_vocab_diverse(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int N, double lambda,
+                               int no_repeat, int repeat_min_id, int64_t* seq_n, double* total, double* aug, int* count, void* work, size_t work_bytes, hipStream_t st) {
+    if (vocab_diverse_check(x, ldx, rows, V, S, N, lambda, no_repeat, repeat_min_id, seq_n, total, aug, count, work, work_bytes)) return BOFI_ERR_ARG;
+    if (rows == 0) return BOFI_OK;
+    if (int rc = launch_candidates_k(vc_args(x, ldx, V, S, ntok, ntok_bias, pad_idx, ban_bits, 0, 0, nullptr, nullptr, nullptr), (int*)work, rows, st)) return rc;
+    DvArgs d{};
+    NbArgs& nb = d.nb;
+    nb.x = x; nb.ldx = ldx; nb.V = V; nb.S = S; nb.B = rows / S; nb.ntok = ntok; nb.ntok_bias = ntok_bias; nb.pad_idx = pad_idx; nb.ban = ban_bits; nb.N = N;
+    nb.seq_n = seq_n; nb.total = total; nb.count = count;
+    for (int k = 0; k < BOFI_DIVERSE_MAX; ++k) d.pen[k] = k < N ? lambda * (double)k : 0.0;      // the one product of the rule, on the host; pen[0] = 0.0
+    d.aug = aug; d.lo = repeat_min_id;
+    const dim3 grid((nb.B + DV_IPW - 1) / DV_IPW), block(DV_IPW * WAVE);
+    if (no_repeat) hipLaunchKernelGGL(vocab_diverse_kernel<true>, grid, block, 0, st, d, (const int*)work);
+    else hipLaunchKernelGGL(vocab_diverse_kernel<false>, grid, block, 0, st, d, (const int*)work);
+    BOFI_CHECK_LAUNCH();
+    return BOFI_OK;
+}
+
+extern "C" int bofi_vocab_diverse(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int N,
+                                  double lambda, int no_repeat, int repeat_min_id, int64_t* seq_n, double* total, double* aug, int* count, void* work,
+                                  int64_t work_bytes, void* stream) {
+    if (const char* why = bofi::vocab_diverse_check(x, ldx, rows, V, S, N, lambda, no_repeat, repeat_min_id, seq_n, total, aug, count, work,
+                                                    work_bytes < 0 ? 0 : (size_t)work_bytes))
+        return bofi::fail(BOFI_ERR_ARG, std::string("vocab_diverse: ") + why);
+    return bofi::launch_vocab_diverse(x, ldx, rows, V, S, ntok, ntok_bias, pad_idx, ban_bits, N, lambda, no_repeat, repeat_min_id, seq_n, total, aug, count, work,
+                                      (size_t)work_bytes, (hipStream_t)stream);
 }
 
 size_t bofi::vocab_pick_work_bytes(int rows) { return (size_t)(rows > 0 ? rows : 0) * VP_K * sizeof(int); }

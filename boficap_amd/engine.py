@@ -77,6 +77,9 @@ def pick_stream_beside(main, device=None, candidates: int = 12, spin_cycles: int
 ATT_EMBED_W = "att_embed.0.weight"
 
 
+DIVERSE_KEYS = ("diverse_seq", "diverse_logp", "diverse_aug", "diverse_count")      # what decode_naic(diverse=N) adds to its dict (bofi_vocab_diverse's four outputs)
+
+
 class BofiEngine:
     def __init__(self, cfg: BofiConfig, dtype: torch.dtype = torch.bfloat16, max_batch: int = 64,
                  max_regions: int = 36, device: Optional[torch.device] = None):
@@ -209,7 +212,8 @@ class BofiEngine:
                     refine_rounds: int = 0, out: Optional[dict] = None, q1_group: int = 0, iter_cap: int = 0, phases: str = "", row_stats: bool = False,
                     ids_only: bool = False, refine_method: str = "feed_back", attn_topk: int = 0, attn_maps: bool = False, attn_heads: bool = False,
                     attn_layer: int = -1, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7, block_trigrams: bool = False, require_ids=None,
-                    nbest: Optional[int] = None, nbest_no_repeat: bool = False, require_phrases=None, require_any=None) -> dict:
+                    nbest: Optional[int] = None, nbest_no_repeat: bool = False, require_phrases=None, require_any=None, diverse: Optional[int] = None,
+                    diversity_lambda: float = 0.5, diverse_no_repeat: bool = False) -> dict:
         """Greedy NAIC bound+fill decode.  Returns a dict of device tensors: seq [B,S] int64,
         seq_logprob [B,S,V] float32 (or None), phrase_num [B] int32, phrase_length [B,S] int32,
         phrase_syn [B,S] int64, bound_iters [1] int32, memory [B,R,d] float32 (or None).
@@ -280,11 +284,21 @@ class BofiEngine:
         ``nbest_no_repeat`` (with ``nbest`` = N in 1..6; a BofiHipError without it): the list is of the captions with NO ADJACENT REPEATED WORD -- an id >=
         ``repeat_min_id`` never follows itself -- exactly: bofi_vocab_nbest_norepeat, a list-Viterbi over each row's N + 2 best ids, in place of bofi_vocab_nbest, under the
         call's ``ban_ids`` and ``repeat_min_id``; same placement, same keys.  ``nbest_count`` may then be 0, and entry 0 need not be ``seq``: the decode's own outputs stay
-        the plain decode's (``no_repeat=True``, the constrained decode, stays refused with the list)."""
+        the plain decode's (``no_repeat=True``, the constrained decode, stays refused with the list).
+        ``diverse`` = N in 1..8 (bofi_vocab_diverse: two small launches BEHIND the decode call, placed as ``nbest``'s and read from the same rows, under the call's
+        ``ban_ids``): a Hamming-diverse SET of N captions of the last filling pass -- the reference's diverse beam search ('dbs', one beam per group) where it is no
+        search: the groups are decoded one after another, group g is the exact maximiser of the sum of its positions' log-probs minus ``diversity_lambda`` (finite,
+        >= 0; the reference's default 0.5) times the number of earlier groups that have the same id at the same position (the header states the rule and its ties).
+        ``out['diverse_seq']`` int64 [B, N, S], ``out['diverse_logp']`` float64 [B, N] (each caption's own log-prob, comparable to ``nbest_logp``; not ordered),
+        ``out['diverse_aug']`` float64 [B, N] (the maximised value), ``out['diverse_count']`` int32 [B] (N; 1 for a degenerate image).  Group 0 is the call's own
+        ``seq``, which stays untouched.  ``diverse_no_repeat`` (with ``diverse`` = N in 1..6; a BofiHipError without it): every caption of the set is free of adjacent
+        repeated words under the call's ``repeat_min_id`` -- a Viterbi over each row's N + 2 best ids; group 0 need then not be ``seq`` and ``diverse_count`` may be 0.
+        Refused before anything is enqueued, naming ``diverse``: ``ids_only`` or an ids-only fork, ``refine_method='mask_predict'``, ``no_repeat`` /
+        ``block_trigrams`` on the decode, any ``require_*`` option, ``nbest`` in the same call, N or lambda out of range.  None or 0: nothing is launched, no key."""
         mp = self._refine_flag(refine_method, refine_rounds, raw_logits)
-        ban, pick_on, req, nbest, nb_min = self._post_options(
+        ban, pick_on, req, nbest, nb_min, dv = self._post_options(
             ban_ids, no_repeat, repeat_min_id, block_trigrams, require_ids, nbest, nbest_no_repeat, att_feats.size(0), ids_only, mp,
-            want_logprob or (out is not None and out.get("seq_logprob") is not None), require_phrases, require_any)
+            want_logprob or (out is not None and out.get("seq_logprob") is not None), require_phrases, require_any, diverse, diversity_lambda, diverse_no_repeat)
         if ids_only:
             if raw_logits:
                 raise hip.BofiHipError("ids_only: the raw logits are not produced")
@@ -342,16 +356,19 @@ class BofiEngine:
             out.pop("required_alt", None)
         if not nbest:
             out.pop("nbest_seq", None), out.pop("nbest_logp", None), out.pop("nbest_count", None)      # (a reused `out` of a call that had the option)
+        if dv is None:
+            for k in DIVERSE_KEYS:
+                out.pop(k, None)                                 # (a reused `out` of a call that had the option)
         if not phases or "f" in phases:
             self._post_passes(out, B, out["seq"], out["seq_logprob"], lambda: torch.sum(out["phrase_length"], 1, dtype=torch.int32), 0, ban, pick_on, req, nbest, nb_min,
-                              no_repeat, repeat_min_id, out["row_chosen"] if row_stats else None)
+                              no_repeat, repeat_min_id, out["row_chosen"] if row_stats else None, dv)
         return out
 
     def _post_options(self, ban_ids, no_repeat, repeat_min_id, block_trigrams, require_ids, nbest, nbest_no_repeat, B: int, ids_only, mp: int, own_rows: bool,
-                      require_phrases=None, require_any=None):
-        """The options of ``decode_naic`` / ``fill_naic`` whose work follows the call, resolved and refused before anything is enqueued: (ban, pick_on, req, nbest, nb_min)
+                      require_phrases=None, require_any=None, diverse=None, diversity_lambda=0.5, diverse_no_repeat=False):
+        """The options of ``decode_naic`` / ``fill_naic`` whose work follows the call, resolved and refused before anything is enqueued: (ban, pick_on, req, nbest, nb_min, dv)
         -- the device bit table or None, "the constrained pick is on", the device table of required words ([B, K]), units ([B, K, L]) or alternatives ([B, K, A, L]) or None, the list's width (0: off) and the ``repeat_min_id``
-        of a repeat-free list (None: the plain list).  ``ids_only`` None: the entry point has no such form (``fill_naic``; its pick refusal comes first, in its own words)."""
+        of a repeat-free list (None: the plain list), and the diverse set's (N, lambda, no_repeat, repeat_min_id) or None (``_diverse_options``).  ``ids_only`` None: the entry point has no such form (``fill_naic``; its pick refusal comes first, in its own words)."""
         ban = self._pick_ban(ban_ids, block_trigrams)
         pick_on = ban is not None or bool(no_repeat) or bool(block_trigrams)
         if ids_only is None and pick_on and mp:
@@ -375,13 +392,17 @@ class BofiEngine:
         nb_min = self._nbest_no_repeat(nbest, nbest_no_repeat, repeat_min_id)
         if nbest:
             self._nbest_refusals(bool(ids_only), mp, no_repeat, block_trigrams, req is not None, own_rows)
+        dv = self._diverse_options(diverse, diversity_lambda, diverse_no_repeat, repeat_min_id)
+        if dv is not None:
+            self._diverse_refusals(bool(ids_only), mp, no_repeat, block_trigrams, req is not None, bool(nbest), own_rows)
         if ids_only is not None and pick_on and (ids_only or mp):
             raise hip.BofiHipError("ban_ids / no_repeat / block_trigrams: not with ids_only (no distribution to re-pick from) or refine_method='mask_predict'")
-        return ban, pick_on, req, nbest, nb_min
+        return ban, pick_on, req, nbest, nb_min, dv
 
-    def _post_passes(self, target: dict, B: int, seq, lp, ntok, ntok_bias: int, ban, pick_on: bool, req, nbest: int, nb_min, no_repeat, repeat_min_id, row_chosen) -> None:
+    def _post_passes(self, target: dict, B: int, seq, lp, ntok, ntok_bias: int, ban, pick_on: bool, req, nbest: int, nb_min, no_repeat, repeat_min_id, row_chosen,
+                     dv=None) -> None:
         """Enqueue what follows a filling pass on the current stream, results into ``target`` (its buffers are reused when they fit): the constrained pick's count
-        (bofi_engine_pick_changed), the required words (``_require_place``), the N-best list (``_nbest_list``).  ``ntok()`` gives the images' lengths where one is needed."""
+        (bofi_engine_pick_changed), the required words (``_require_place``), the N-best list (``_nbest_list``), the diverse set (``_diverse_set``).  ``ntok()`` gives the images' lengths where one is needed."""
         if pick_on:
             if target.get("constrained") is None or target["constrained"].numel() != B:
                 target["constrained"] = torch.zeros(B, dtype=torch.int32, device=seq.device)
@@ -396,6 +417,59 @@ class BofiEngine:
         if nbest:
             target["nbest_seq"], target["nbest_logp"], target["nbest_count"] = self._nbest_list(
                 nbest, B, lp, ntok(), ntok_bias, ban, target.get("nbest_seq"), target.get("nbest_logp"), target.get("nbest_count"), repeat_min=nb_min)
+        if dv is not None:
+            target.update(zip(DIVERSE_KEYS, self._diverse_set(dv, B, lp, ntok(), ntok_bias, ban, *(target.get(k) for k in DIVERSE_KEYS))))
+
+    @staticmethod
+    def _diverse_options(diverse, diversity_lambda=0.5, diverse_no_repeat=False, repeat_min_id: int = 7):
+        """``diverse`` / ``diversity_lambda`` / ``diverse_no_repeat`` of a decode: None when off (``diverse`` None or 0), else (N, lambda, no_repeat, repeat_min_id).
+        BofiHipError naming ``diverse``: N outside 1..8 (1..6 with ``diverse_no_repeat``), a lambda that is negative, NaN or infinite, a negative ``repeat_min_id``
+        under the repeat rule, ``diverse_no_repeat`` without ``diverse``."""
+        if diverse is None or diverse is False or int(diverse) == 0:
+            if diverse_no_repeat:
+                raise hip.BofiHipError("diverse_no_repeat: needs diverse = N (it keeps adjacent repeats out of the diverse set; no_repeat=True is the constrained decode)")
+            return None
+        N, lam = hip.diverse_check(diverse, diversity_lambda, bool(diverse_no_repeat), repeat_min_id, "diverse")
+        return N, lam, bool(diverse_no_repeat), int(repeat_min_id) if diverse_no_repeat else 0
+
+    def _diverse_refusals(self, ids_only: bool, mp: int, no_repeat: bool, block_trigrams: bool, required: bool, nbest: bool, own_rows: bool) -> None:
+        if ids_only:
+            raise hip.BofiHipError("diverse: not with ids_only (the decode leaves no rows to decode the groups from)")
+        if mp:
+            raise hip.BofiHipError("diverse: not with refine_method='mask_predict' (kept positions do not hold their row's first id: group 0 would not be the caption)")
+        if no_repeat or block_trigrams:
+            raise hip.BofiHipError("diverse: not with no_repeat / block_trigrams (the set stands beside the plain decode); diverse_no_repeat=True keeps adjacent "
+                                   "repeats out of the set")
+        if required:
+            raise hip.BofiHipError("diverse: not with require_ids / require_phrases / require_any (the set is of unforced captions)")
+        if nbest:
+            raise hip.BofiHipError("diverse: not with nbest in the same call (two sets of captions of one pass: ask for one)")
+        if not own_rows and not self._lib.bofi_engine_logprob(self._h):
+            raise hip.BofiHipError("diverse: this engine keeps no log-prob workspace (an ids-only fork): there are no rows to decode the groups from")
+
+    def _diverse_set(self, dv, B: int, lp, ntok, ntok_bias, ban, seq_n=None, total=None, aug=None, count=None):
+        """Enqueue bofi_vocab_diverse for ``dv`` (``_diverse_options``) on the current stream behind a decode; ``lp`` as ``_nbest_list``'s.  Returns (seq_n int64
+        [B, N, S], total float64 [B, N], aug float64 [B, N], count int32 [B]); the buffers given are reused when they fit."""
+        N, lam, nr, lo = dv
+        S, V, dev = self.cfg.seq_length, self.cfg.tgt_vocab, ntok.device
+        if seq_n is None or tuple(seq_n.shape) != (B, N, S):
+            seq_n = torch.empty(B, N, S, dtype=torch.int64, device=dev)
+        if total is None or tuple(total.shape) != (B, N):
+            total = torch.empty(B, N, dtype=torch.float64, device=dev)
+        if aug is None or tuple(aug.shape) != (B, N):
+            aug = torch.empty(B, N, dtype=torch.float64, device=dev)
+        if count is None or count.numel() != B:
+            count = torch.empty(B, dtype=torch.int32, device=dev)
+        need = int(self._lib.bofi_vocab_nbest_workspace(B * S))
+        work = getattr(self, "_nbest_work", None)
+        if work is None or work.numel() * 4 < need or work.device != dev:
+            work = self._nbest_work = torch.empty(max(1, need // 4), dtype=torch.int32, device=dev)
+        src = hip.ptr(lp) if lp is not None else self._lib.bofi_engine_logprob(self._h)
+        if not src:
+            raise hip.BofiHipError("diverse: this engine keeps no log-prob workspace (an ids-only fork)")
+        hip.check(self._lib.bofi_vocab_diverse(src, V, B * S, V, S, hip.ptr(ntok), int(ntok_bias), int(self.cfg.pad_idx), hip.ptr(ban), N, lam, int(nr), lo, hip.ptr(seq_n),
+                                               hip.ptr(total), hip.ptr(aug), hip.ptr(count), hip.ptr(work), work.numel() * 4, hip.stream_ptr()), "bofi_vocab_diverse")
+        return seq_n, total, aug, count
 
     @staticmethod
     def _nbest_width(nbest) -> int:
@@ -720,7 +794,7 @@ class BofiEngine:
 
     def decode_saic(self, att_feats: torch.Tensor, att_len: Optional[torch.Tensor] = None, *, raw_logits: bool = False,
                     want_logprob: bool = True, sample: Optional[tuple] = None, graph: bool = False, out: Optional[dict] = None,
-                    it_range: Optional[tuple] = None, layout_only: bool = False, nbest: Optional[int] = None) -> dict:
+                    it_range: Optional[tuple] = None, layout_only: bool = False, nbest: Optional[int] = None, diverse: Optional[int] = None) -> dict:
         """Semi-autoregressive decode (core_SAIC), greedy or -- ``sample=(temperature, seed)`` -- with every phrase's tokens
         drawn from Categorical(logits / temperature) (the bound heads stay greedy, as in the reference).  Same result
         layout as ``decode_naic``.  ``graph``: the launch sequence is captured once per argument set and replayed (pass the
@@ -730,6 +804,8 @@ class BofiEngine:
         ``out["bound_iters"]`` (live iterations so far) < c says the first part was all of it.  ``layout_only``: the enqueued iterations lay their phrases out and stop
         (BOFI_FLAG_SAIC_LAYOUT_ONLY: no decoder pass, no tokens) -- for a caller that draws the words itself and hands them back with ``saic_put_words``.
         ``nbest`` is refused here: a phrase's rows are conditioned on the phrases before it, so a caption's log-prob is no sum of independent per-position terms."""
+        if diverse:
+            raise hip.BofiHipError("diverse: not with decode_saic (a phrase's rows depend on the phrases before it: the per-position sums are not a caption's log-prob)")
         if self._nbest_width(nbest):
             raise hip.BofiHipError("nbest: not with decode_saic (a phrase's rows depend on the phrases before it: the per-position sums are not a caption's log-prob); "
                                    "decode_naic / fill_naic serve it")
@@ -788,7 +864,8 @@ class BofiEngine:
     def fill_naic(self, ext_syn: torch.Tensor, last: torch.Tensor, R: int, att_len: Optional[torch.Tensor] = None, *, strict_q1: bool = True,
                   raw_logits: bool = False, refine_rounds: int = 0, refine_method: str = "feed_back", attn_topk: int = 0, attn_maps: bool = False,
                   attn_heads: bool = False, attn_layer: int = -1, ban_ids=None, no_repeat: bool = False, repeat_min_id: int = 7, block_trigrams: bool = False,
-                  require_ids=None, nbest: Optional[int] = None, nbest_no_repeat: bool = False, require_phrases=None, require_any=None):
+                  require_ids=None, nbest: Optional[int] = None, nbest_no_repeat: bool = False, require_phrases=None, require_any=None,
+                  diverse: Optional[int] = None, diversity_lambda: float = 0.5, diverse_no_repeat: bool = False):
         """The filling pass alone on a given slot layout (``ext_syn`` int32 [B, S+2], ``last`` int32 [B]) and the memory of the
         preceding ``encode``: (seq int64 [B, S], seq_logprob float32 [B, S, V]); with ``refine_method='mask_predict'`` (as ``decode_naic``) a third
         element, refine_round int32 [B, S].  With ``attn_topk`` / ``attn_maps`` / ``attn_heads`` (as ``decode_naic``) a last element, a dict of the attention tensors
@@ -797,11 +874,13 @@ class BofiEngine:
         then carries 'required_pos' int32 [B, K] and 'required_moved' int32 [B]; ``require_phrases`` as ``decode_naic`` (bofi_vocab_require_units in its place, the
         same keys); ``require_any`` as ``decode_naic`` (bofi_vocab_require_any in its place: 'required_alt' int32 [B, K] beside those keys).  ``nbest`` as ``decode_naic`` (bofi_vocab_nbest behind the call, on the last pass; the
         same refusals): that dict then carries 'nbest_seq' int64 [B, N, S], 'nbest_logp' float64 [B, N] and 'nbest_count' int32 [B]; ``nbest_no_repeat`` as
-        ``decode_naic`` (bofi_vocab_nbest_norepeat in its place, N <= 6)."""
+        ``decode_naic`` (bofi_vocab_nbest_norepeat in its place, N <= 6).  ``diverse`` / ``diversity_lambda`` / ``diverse_no_repeat`` as ``decode_naic``
+        (bofi_vocab_diverse behind the call, on the last pass; the same refusals): that dict then carries 'diverse_seq', 'diverse_logp', 'diverse_aug' and
+        'diverse_count'."""
         mp = self._refine_flag(refine_method, refine_rounds, raw_logits)
         B = ext_syn.size(0)
-        ban, pick_on, req, nbest, nb_min = self._post_options(ban_ids, no_repeat, repeat_min_id, block_trigrams, require_ids, nbest, nbest_no_repeat, B, None, mp, True,
-                                                               require_phrases, require_any)
+        ban, pick_on, req, nbest, nb_min, dv = self._post_options(ban_ids, no_repeat, repeat_min_id, block_trigrams, require_ids, nbest, nbest_no_repeat, B, None, mp,
+                                                                   True, require_phrases, require_any, diverse, diversity_lambda, diverse_no_repeat)
         if ext_syn.dtype != torch.int32 or last.dtype != torch.int32 or ext_syn.size(1) != self.cfg.bound_len or last.numel() != B:
             raise hip.BofiHipError("ext_syn must be int32 [B, S+2] and last int32 [B]")
         S, V, dev = self.cfg.seq_length, self.cfg.tgt_vocab, ext_syn.device
@@ -815,7 +894,7 @@ class BofiEngine:
         self._pick_opts(o, ban, no_repeat, repeat_min_id, block_trigrams)
         hip.check(self._lib.bofi_engine_fill_naic(self._h, hip.ptr(ext_syn.contiguous()), hip.ptr(last.contiguous()), B, R, hip.ptr(att_len), flags,
                                                   hip.ptr(seq), hip.ptr(lp), C.byref(o), hip.stream_ptr()), "bofi_engine_fill_naic")
-        self._post_passes(attn, B, seq, lp, last.contiguous, -1, ban, pick_on, req, nbest, nb_min, no_repeat, repeat_min_id, None)
+        self._post_passes(attn, B, seq, lp, last.contiguous, -1, ban, pick_on, req, nbest, nb_min, no_repeat, repeat_min_id, None, dv)
         res = (seq, lp, rnd) if mp else (seq, lp)
         return res + (attn,) if attn else res
 

@@ -38,6 +38,13 @@ references alone (integer rows or id strings; no loss then), or None.  ``eval_kw
     nbest_no_repeat  1, with ``sample_n_method`` 'nbest' and ``sample_n`` <= 6 (a ValueError otherwise): the rows are the ``sample_n`` most probable captions with no
                      adjacent repeated word (ids >= 7), exactly -- ``opt['nbest_no_repeat']``, bofi_vocab_nbest_norepeat.  The greedy predictions stay the plain decode's;
                      ``decoding_constraint`` with the list stays refused.  Keys as above
+    sample_n_method 'diverse'   the reference's 'dbs' (diverse beam search, one beam per group, Hamming diversity at the same position) for the non-autoregressive
+                     decode, where it is exact and no search: the ``sample_n`` rows per image are a set decoded group after group, group g the exact maximiser of its
+                     log-prob minus ``diversity_lambda`` (the reference's key and default, 0.5) times the number of earlier groups with the same word at the same
+                     position (``opt['diverse']``, bofi_vocab_diverse: one decode plus two small launches; deterministic).  Row 0 is the greedy caption.
+                     ``diverse_no_repeat`` 1: every caption of the set is free of adjacent repeated words (ids >= 7) and ``sample_n`` <= 6; else ``sample_n`` <= 8.
+                     Refusals and banned words as with 'nbest'; entries carry 'logp' (the caption's own log-prob); ``lang_stats['diverse_short']`` counts the images
+                     with fewer than ``sample_n`` captions (degenerate rows, or no repeat-free caption)
     cached_tokens    a df pickle of scripts/prepro_ngrams.py: a path, or a name resolved as data/<name>.p (default 'coco-train-idxs')
     eval_oracle      1, with ``language_eval`` 1 and ``sample_n`` > 1 (nothing changes otherwise): every sampled caption is scored against its image's
                      references and ``lang_stats`` gains 'oracle_<M>' (the best of an image's N, averaged over the images) and 'avg_<M>' (their mean)
@@ -142,15 +149,28 @@ class SyntheticLabels:
         return self.host["labels"][int(ix), :, 1:-1]
 
 
-SAMPLE_N_METHODS = ("sample", "nbest")
+SAMPLE_N_METHODS = ("sample", "nbest", "diverse")
 
 
 def sample_n_method_of(eval_kwargs, mode: str = "NAIC", sample_n: int = 1) -> str:
-    """``eval_kwargs['sample_n_method']``: 'sample' (the default) or 'nbest'; any other string is a ValueError that names the two.  With ``sample_n`` > 1, 'nbest' is a
-    ValueError where the list cannot be made: SAIC mode, more than 8 captions per image, mask-predict, ``decoding_constraint`` / ``block_trigrams``."""
+    """``eval_kwargs['sample_n_method']``: 'sample' (the default), 'nbest' or 'diverse'; any other string is a ValueError that names them.  With ``sample_n`` > 1, 'nbest'
+    and 'diverse' are a ValueError where the rows cannot be made: SAIC mode, more than 8 captions per image, mask-predict, ``decoding_constraint`` /
+    ``block_trigrams`` (``diverse_options_of`` has the set's own keys)."""
     method = eval_kwargs.get("sample_n_method", "sample") or "sample"
     if method not in SAMPLE_N_METHODS:
-        raise ValueError(f"sample_n_method {method!r}: 'sample' (sample_n random draws) and 'nbest' (the sample_n most probable captions of the filling pass) are served")
+        raise ValueError(f"sample_n_method {method!r}: 'sample' (sample_n random draws) and 'nbest' (the sample_n most probable captions of the filling pass) are served, "
+                         "and 'diverse' (a Hamming-diverse set of sample_n captions of the filling pass)")
+    if method == "diverse" and int(sample_n) > 1:
+        from .hip import DIVERSE_MAX
+        if mode != "NAIC":
+            raise ValueError("sample_n_method 'diverse' decodes the non-autoregressive filling pass's rows group by group: inference_mode 'NAIC' only")
+        if int(sample_n) > DIVERSE_MAX:
+            raise ValueError(f"sample_n_method 'diverse': at most {DIVERSE_MAX} captions per image, got sample_n = {int(sample_n)}")
+        if eval_kwargs.get("refine_method", "feed_back") == "mask_predict":
+            raise ValueError("sample_n_method 'diverse': not with refine_method 'mask_predict' (kept positions do not hold their row's first id)")
+        if int(eval_kwargs.get("decoding_constraint", 0)) == 1 or int(eval_kwargs.get("block_trigrams", 0) or 0) == 1:
+            raise ValueError("sample_n_method 'diverse': not with decoding_constraint / block_trigrams (the set stands beside the plain decode; diverse_no_repeat = 1 "
+                             "keeps adjacent repeats out of the set)")
     if method == "nbest" and int(sample_n) > 1:
         from .hip import NBEST_MAX
         if mode != "NAIC":
@@ -179,20 +199,47 @@ def nbest_no_repeat_of(eval_kwargs, sample_n: int = 1) -> bool:
     return True
 
 
+def diverse_options_of(eval_kwargs, sample_n: int = 1):
+    """``eval_kwargs['diversity_lambda']`` (the reference's key and default, 0.5) and ``eval_kwargs['diverse_no_repeat']`` (0, the default, or 1) of
+    ``sample_n_method='diverse'`` as (lambda, no_repeat).  ValueError naming the key: either key given without that method, a lambda that is negative, NaN or infinite,
+    ``diverse_no_repeat`` outside {0, 1} or with more than 6 captions per image."""
+    diverse = (eval_kwargs.get("sample_n_method", "sample") or "sample") == "diverse"
+    nr = int(eval_kwargs.get("diverse_no_repeat", 0) or 0)
+    lam = eval_kwargs.get("diversity_lambda")
+    if not diverse:
+        if nr:
+            raise ValueError("diverse_no_repeat narrows the diverse set: it needs sample_n_method 'diverse'")
+        return 0.5 if lam is None else float(lam), False         # (diversity_lambda without the method: the reference's files carry the key; it does nothing)
+    lam = 0.5 if lam is None else float(lam)
+    if not (lam >= 0.0) or lam == float("inf"):
+        raise ValueError(f"diversity_lambda must be finite and >= 0, got {lam}")
+    if nr not in (0, 1):
+        raise ValueError(f"diverse_no_repeat is 0 or 1, got {nr}")
+    from .hip import DIVERSE_NR_MAX
+    if nr and int(sample_n) > DIVERSE_NR_MAX:
+        raise ValueError(f"diverse_no_repeat: at most {DIVERSE_NR_MAX} captions per image, got sample_n = {int(sample_n)}")
+    return lam, bool(nr)
+
+
 def sample_n_predictions(model, feats, sample_n: int, mode: str = "NAIC", batch_size: int = 64, vocab=None, surface=None, method: str = "sample", ban_ids=None,
-                         refine_rounds: int = 0, info=None, nbest_no_repeat: bool = False):
+                         refine_rounds: int = 0, info=None, nbest_no_repeat: bool = False, diversity_lambda: float = 0.5,
+                         diverse_no_repeat: bool = False):
     """eval_split_n (eval_utils.py:670-700): ``sample_n`` captions per image of ``feats`` through ``mode='sample'`` -- drawn (``method='sample'``, the reference's
     ``sample_n_method='sample'``) or the ``sample_n`` most probable captions of the NAIC filling pass, most probable first (``method='nbest'``: ``opt['nbest']``, under
     ``ban_ids`` and after ``refine_rounds`` feed-back rounds; rows past an image's count are the empty captions the kernel wrote).  Returns (entries {'image_id',
     'seq'[, 'caption'][, 'logp']} in row order, the ids [N * sample_n, S] on the device); an entry's 'seq' holds the ids before the first id <= 0 (decode_sequence);
     'logp' (``'nbest'`` only) is the caption's float64 total, -inf on an empty row past the count.  ``info``: a dict that receives 'nbest_short', the number of images
     with fewer than ``sample_n`` captions.  ``nbest_no_repeat`` (``'nbest'`` only, ``sample_n`` <= 6): the list is of the captions with no adjacent repeated word
-    (``opt['nbest_no_repeat']``); an image may then have no caption at all (every row empty, every 'logp' -inf).  ``surface``: a ``CaptionSurface`` -- the ids are trimmed of their bad endings on the device first, and both results are
+    (``opt['nbest_no_repeat']``); an image may then have no caption at all (every row empty, every 'logp' -inf).  ``method='diverse'``: the Hamming-diverse set of
+    ``sample_n`` captions (``opt['diverse']`` with ``diversity_lambda`` and ``diverse_no_repeat``: bofi_vocab_diverse), group 0 first, under ``ban_ids`` and after
+    ``refine_rounds``; 'logp' is each caption's own log-prob and ``info`` receives 'diverse_short'.  ``surface``: a ``CaptionSurface`` -- the ids are trimmed of their bad endings on the device first, and both results are
     the trimmed ones."""
     if method not in SAMPLE_N_METHODS:
-        raise ValueError(f"sample_n_method {method!r}: 'sample' and 'nbest' are served")
+        raise ValueError(f"sample_n_method {method!r}: 'sample' and 'nbest' are served, and 'diverse'")
     if method == "nbest" and mode != "NAIC":
         raise ValueError("sample_n_method 'nbest' lists the non-autoregressive filling pass's captions: inference_mode 'NAIC' only")
+    if method == "diverse" and mode != "NAIC":
+        raise ValueError("sample_n_method 'diverse' decodes the non-autoregressive filling pass's rows group by group: inference_mode 'NAIC' only")
     n, ragged = int(sample_n), is_region_source(feats)
     host = feats if ragged else _torch_feats(feats)
     step = batch_size if mode == "NAIC" else max(1, min(batch_size, model.max_batch // n))       # the SAIC sampler decodes images x n rows
@@ -215,12 +262,20 @@ def sample_n_predictions(model, feats, sample_n: int, mode: str = "NAIC", batch_
                 rows.append(nb["seq"].reshape(-1, nb["seq"].size(-1)))
                 logps.append(nb["logp"].reshape(-1))
                 short += int((nb["count"] < n).sum())
+            elif method == "diverse":
+                opt = {"train_mode": mode, "sample_method": "greedy", "sample_n": 1, "diverse": n, "diversity_lambda": float(diversity_lambda),
+                       "diverse_no_repeat": 1 if diverse_no_repeat else 0, "refine_rounds": int(refine_rounds), "ban_ids": list(ban_ids or ())}
+                model(fc, att, masks, opt=opt, mode="sample")
+                dv = model.last_diverse
+                rows.append(dv["seq"].reshape(-1, dv["seq"].size(-1)))
+                logps.append(dv["logp"].reshape(-1))
+                short += int((dv["count"] < n).sum())
             else:
                 rows.append(model(fc, att, masks, opt={"train_mode": mode, "sample_method": "sample", "sample_n": n}, mode="sample")[0])
     seq = torch.cat(rows)
     logp = torch.cat(logps).cpu().tolist() if logps else None
-    if info is not None and method == "nbest":
-        info["nbest_short"] = short
+    if info is not None and method in ("nbest", "diverse"):
+        info[method + "_short"] = short
     if surface is not None:
         seq = surface.trim(seq)[0]
     entries = []
@@ -278,7 +333,7 @@ def constraint_of(eval_kwargs, vocab, mode: str = "NAIC", sample_n: int = 1):
     words, or 'W1,W2,...') and ``block_trigrams`` (the reference's name and default, 0: no word trigram twice in a caption) are all off, else {'ban_ids': sorted ids,
     'no_repeat': bool}, with 'block_trigrams': True beside them when that option is on.  Words resolve to ids as the bad-ending words do (``surface.ids_of`` on
     ``vocab``; a word the vocabulary does not hold names no id).  ValueError where the options cannot apply: SAIC mode, ``fused_vocab``, mask-predict, sampling
-    (``sample_n`` > 1) -- except that ``suppress_UNK`` / ``ban_words`` go with ``sample_n_method='nbest'``, whose list is made under the same ban."""
+    (``sample_n`` > 1) -- except that ``suppress_UNK`` / ``ban_words`` go with ``sample_n_method='nbest'`` and ``'diverse'``, whose rows are made under the same ban."""
     kw = eval_kwargs
     words = kw.get("ban_words") or []
     words = [w for w in words.split(",") if w] if isinstance(words, str) else list(words)
@@ -291,9 +346,10 @@ def constraint_of(eval_kwargs, vocab, mode: str = "NAIC", sample_n: int = 1):
         raise ValueError("suppress_UNK / decoding_constraint / ban_words / block_trigrams: not with fused_vocab (no distribution to re-pick from)")
     if kw.get("refine_method", "feed_back") == "mask_predict":
         raise ValueError("suppress_UNK / decoding_constraint / ban_words / block_trigrams: not with refine_method 'mask_predict'")
-    if int(sample_n) > 1 and (kw.get("sample_n_method", "sample") != "nbest" or rep or tri):      # (banned ids go with the N-best list; a rule that couples neighbours does not)
+    listed = kw.get("sample_n_method", "sample") in ("nbest", "diverse")
+    if int(sample_n) > 1 and (not listed or rep or tri):      # (banned ids go with the N-best list; a rule that couples neighbours does not)
         raise ValueError("suppress_UNK / decoding_constraint / ban_words / block_trigrams constrain greedy picks: not with sample_n > 1"
-                         + (" (sample_n_method 'nbest' takes suppress_UNK / ban_words only)" if kw.get("sample_n_method", "sample") == "nbest" else ""))
+                         + (f" (sample_n_method {kw['sample_n_method']!r} takes suppress_UNK / ban_words only)" if listed else ""))
     if (unk or words) and not vocab:
         raise ValueError("suppress_UNK / ban_words need a vocabulary ({str(id): word})")
     from .surface import ids_of
@@ -473,6 +529,7 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
         raise ValueError("refine_rounds / refine_method refine the non-autoregressive filling pass: inference_mode 'NAIC' only")
     n_method = sample_n_method_of(kw, mode, sample_n)
     nb_no_repeat = nbest_no_repeat_of(kw, sample_n)
+    dv_lambda, dv_no_repeat = diverse_options_of(kw, sample_n)
     attn_topk = int(kw.get("attn_topk", 0))
     if attn_topk and mode != "NAIC":
         raise ValueError("attn_topk reads the non-autoregressive filling pass's cross-attention: inference_mode 'NAIC' only")
@@ -573,12 +630,19 @@ def eval_split(model, feats, store_or_gts, eval_kwargs, sample_n=None):
                 kw["preds_n"], sampled = sample_n_predictions(model, feats, sample_n, mode, batch_size, vocab, surface if remove else None, method="nbest",
                                                               ban_ids=pick.get("ban_ids"), refine_rounds=refine["refine_rounds"], info=info,
                                                               nbest_no_repeat=nb_no_repeat)
+            elif n_method == "diverse":                          # a Hamming-diverse set of the filling pass's captions, group after group
+                info = {}
+                kw["preds_n"], sampled = sample_n_predictions(model, feats, sample_n, mode, batch_size, vocab, surface if remove else None, method="diverse",
+                                                              ban_ids=pick.get("ban_ids"), refine_rounds=refine["refine_rounds"], info=info,
+                                                              diversity_lambda=dv_lambda, diverse_no_repeat=dv_no_repeat)
             else:
                 kw["preds_n"], sampled = sample_n_predictions(model, feats, sample_n, mode, batch_size, vocab, surface if remove else None)
             div, kw["diversity_per_image"] = diversity_stats(sampled, sample_n, kw)
             lang_stats = dict(lang_stats or {}, **div)
             if n_method == "nbest":
                 lang_stats["nbest_short"] = kw["nbest_short"] = info["nbest_short"]
+            if n_method == "diverse":
+                lang_stats["diverse_short"] = kw["diverse_short"] = info["diverse_short"]
             if ev is not None and int(kw.get("eval_oracle", 0)) == 1:      # the oracle of language_eval (eval_utils.py:112-114): inside it, and only with a preds_n
                 oracle = ev.evaluate_n(sampled, sample_n)
                 kw["oracle_per_image"] = oracle.pop("per_image")

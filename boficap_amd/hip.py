@@ -27,6 +27,8 @@ REQUIRE_MAX = 8                     # BOFI_REQUIRE_MAX: required words per image
 REQUIRE_UNIT_MAX = 4                # BOFI_REQUIRE_UNIT_MAX: ids per required unit (bofi_vocab_require_units)
 REQUIRE_ALT_MAX = 4                 # BOFI_REQUIRE_ALT_MAX: alternatives per required group (bofi_vocab_require_any)
 NBEST_MAX = 8                       # BOFI_NBEST_MAX: captions per image of bofi_vocab_nbest
+DIVERSE_MAX = 8                     # BOFI_DIVERSE_MAX: groups (captions per image) of bofi_vocab_diverse
+DIVERSE_NR_MAX = 6                  # BOFI_DIVERSE_NR_MAX: ... under its repeat rule (N + 2 candidates per row are the candidates launch's 8)
 NBEST_NR_MAX = 6                    # BOFI_NBEST_NR_MAX: ... of bofi_vocab_nbest_norepeat (its N + 2 candidates per row are the candidates launch's 8)
 
 
@@ -148,6 +150,7 @@ SIGNATURES = {
     "bofi_vocab_nbest_workspace": (_I64, [_I]),
     "bofi_vocab_nbest": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _I64, _P]),
     "bofi_vocab_nbest_norepeat": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I64, _P]),
+    "bofi_vocab_diverse": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, C.c_double, _I, _I, _P, _P, _P, _P, _P, _I64, _P]),
     "bofi_caption_trim": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     "bofi_sentence_lookup": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
 }
@@ -711,6 +714,56 @@ def vocab_nbest_norepeat(x, V, S, N, *, ntok=None, ntok_bias=0, pad_idx=0, ban=N
     check(lib().bofi_vocab_nbest_norepeat(ptr(x), x.stride(0), rows, int(V), int(S), ptr(ntok), int(ntok_bias), int(pad_idx), ptr(ban), int(repeat_min_id), N,
                                           ptr(seq_n), ptr(total), ptr(count), ptr(work), work.numel() * 4, stream_ptr()), "bofi_vocab_nbest_norepeat")
     return seq_n, total, count
+
+
+def diverse_check(N, lam, no_repeat=False, repeat_min_id=7, what="vocab_diverse"):
+    """The host-side range checks of a diverse set: (N, lambda) as int and float; BofiHipError naming ``what`` for N outside 1..8 (1..6 under the repeat rule), a lambda
+    that is negative, NaN or infinite, or a negative ``repeat_min_id``."""
+    N, lam = int(N), float(lam)
+    top = DIVERSE_NR_MAX if no_repeat else DIVERSE_MAX
+    if not 1 <= N <= top:
+        raise BofiHipError(f"{what}: N must lie in 1..{top}" + (" under the repeat rule (it needs N + 2 of a row's 8 candidate ids)" if no_repeat else "") + f", got {N}")
+    if not (lam >= 0.0) or lam == float("inf"):
+        raise BofiHipError(f"{what}: lambda must be finite and >= 0, got {lam}")
+    if no_repeat and int(repeat_min_id) < 0:
+        raise BofiHipError(f"{what}: repeat_min_id must be >= 0, got {repeat_min_id}")
+    return N, lam
+
+
+def vocab_diverse(x, V, S, N, *, lam=0.5, no_repeat=False, repeat_min_id=7, ntok=None, ntok_bias=0, pad_idx=0, ban=None, seq_n=None, total=None, aug=None, count=None,
+                  work=None):
+    """``bofi_vocab_diverse`` on torch tensors: the Hamming-diverse set of N captions of the rows x float32 [rows, >= V] (device, unit column stride, any 4-byte alignment;
+    read only) -- group g is the exact maximiser of the sum of x minus ``lam`` times the number of earlier groups with the same id at the same position, with
+    ``no_repeat`` over the captions in which no id >= ``repeat_min_id`` follows itself (N <= 6 then).  Returns ``(seq_n int64 [B, N, S], total float64 [B, N], aug
+    float64 [B, N], count int32 [B])``: each caption's own log-prob and its augmented score; the buffers and ``work`` (``vocab_nbest``'s workspace) may be given.  Two
+    launches on the current stream, no synchronisation."""
+    import torch
+    if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or not x.is_cuda:
+        raise BofiHipError("vocab_diverse: x must be a 2-d float32 device tensor with unit column stride")
+    rows = x.size(0)
+    if x.size(1) < V or S < 1 or rows % S:
+        raise BofiHipError("vocab_diverse: x needs V columns and a multiple of S rows")
+    N, lam = diverse_check(N, lam, no_repeat, repeat_min_id)
+    B = rows // S
+    if seq_n is None:
+        seq_n = torch.empty(B, N, S, dtype=torch.int64, device=x.device)
+    if total is None:
+        total = torch.empty(B, N, dtype=torch.float64, device=x.device)
+    if aug is None:
+        aug = torch.empty(B, N, dtype=torch.float64, device=x.device)
+    if count is None:
+        count = torch.empty(B, dtype=torch.int32, device=x.device)
+    if work is None:
+        work = torch.empty(max(1, lib().bofi_vocab_nbest_workspace(rows) // 4), dtype=torch.int32, device=x.device)
+    for name, t, dt, n in (("seq_n", seq_n, torch.int64, B * N * S), ("total", total, torch.float64, B * N), ("aug", aug, torch.float64, B * N),
+                           ("count", count, torch.int32, B), ("ntok", ntok, torch.int32, B), ("ban", ban, torch.int32, (V + 31) // 32), ("work", work, torch.int32, None)):
+        if t is None and name in ("ntok", "ban"):
+            continue
+        if t is None or t.dtype != dt or (n is not None and t.numel() != n) or not t.is_cuda or not t.is_contiguous():
+            raise BofiHipError(f"vocab_diverse: {name} must be a contiguous {dt} device tensor" + ("" if n is None else f" of {n} elements"))
+    check(lib().bofi_vocab_diverse(ptr(x), x.stride(0), rows, int(V), int(S), ptr(ntok), int(ntok_bias), int(pad_idx), ptr(ban), N, lam, 1 if no_repeat else 0,
+                                   int(repeat_min_id), ptr(seq_n), ptr(total), ptr(aug), ptr(count), ptr(work), work.numel() * 4, stream_ptr()), "bofi_vocab_diverse")
+    return seq_n, total, aug, count
 
 
 def gemm_flops(reset: bool = False):

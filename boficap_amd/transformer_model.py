@@ -424,6 +424,33 @@ class TransformerModel(nn.Module):
             rkw.update(nbest=nbest)
             if nbest_nr:
                 rkw.update(nbest_no_repeat=True)
+        # opt['diverse'] = N in 1..8 with opt['diversity_lambda'] (the reference's key and default, 0.5) and opt['diverse_no_repeat'] (0 / 1; N <= 6): the Hamming-diverse
+        # set of N captions of the NAIC filling pass (BofiEngine.decode_naic(diverse=N): the reference's 'dbs' with one beam per group, exact, one decode plus two small
+        # launches); the 6-tuple stays, the set lands in self.last_diverse ({'seq' int64 [B, N, S], 'logp' float64 [B, N], 'aug' float64 [B, N], 'count' int32 [B]}, per
+        # image; None without the option).  The refusals are the engine's, raised here before anything is enqueued
+        diverse = int(opt.get("diverse", 0) or 0)
+        diverse_nr = bool(int(opt.get("diverse_no_repeat", 0) or 0))
+        if diverse_nr and not diverse:
+            raise hip.BofiHipError("diverse_no_repeat: needs opt['diverse'] = N (it keeps adjacent repeats out of the diverse set)")
+        self.last_diverse = None
+        if diverse:
+            lam = opt.get("diversity_lambda", 0.5)
+            hip.diverse_check(diverse, 0.5 if lam is None else lam, diverse_nr, what="diverse")
+            if train_mode != "NAIC":
+                raise hip.BofiHipError("diverse decodes the non-autoregressive filling pass's rows group by group: train_mode 'NAIC' only (a semi-autoregressive "
+                                       "phrase's rows depend on the phrases before it)")
+            if sample_method == "sample":
+                raise hip.BofiHipError("diverse is a set around the greedy decode: not with sample_method='sample'")
+            if refine_method == "mask_predict":
+                raise hip.BofiHipError("diverse: not with refine_method='mask_predict' (kept positions do not hold their row's first id)")
+            if no_repeat or block_trigrams:
+                raise hip.BofiHipError("diverse: not with decoding_constraint / block_trigrams (the set stands beside the plain decode; diverse_no_repeat keeps "
+                                       "adjacent repeats out of the set)")
+            if "require_ids" in rkw or "require_phrases" in rkw or "require_any" in rkw:
+                raise hip.BofiHipError("diverse: not with require_ids / require_phrases / require_any (the set is of unforced captions)")
+            if nbest:
+                raise hip.BofiHipError("diverse: not with nbest in the same call (two sets of captions of one pass: ask for one)")
+            rkw.update(diverse=diverse, diversity_lambda=float(0.5 if lam is None else lam), diverse_no_repeat=diverse_nr)
         eng = self.engine()
         torch.cuda.synchronize()                                  # the reference does (AttModel.py:337)
         start = time.time()
@@ -460,6 +487,8 @@ class TransformerModel(nn.Module):
                 self.last_required = {k: (r["required_" + k].repeat_interleave(sample_n, dim=0) if sample_n > 1 else r["required_" + k]) for k in ("pos", "moved") + (("alt",) if "required_alt" in r else ())}
             if "nbest_seq" in r:
                 self.last_nbest = {"seq": r["nbest_seq"], "logp": r["nbest_logp"], "count": r["nbest_count"]}
+            if "diverse_seq" in r:
+                self.last_diverse = {"seq": r["diverse_seq"], "logp": r["diverse_logp"], "aug": r["diverse_aug"], "count": r["diverse_count"]}
             if "ban_ids" in rkw:
                 self.last_constrained = r["constrained"].repeat_interleave(sample_n, dim=0) if sample_n > 1 else r["constrained"]
         elif sample_method == "greedy":                           # core_SAIC, AttModel.py:430-437

@@ -974,6 +974,48 @@ int bofi_vocab_nbest(const float* x, int ldx, int rows, int V, int S, const int*
 int bofi_vocab_nbest_norepeat(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int repeat_min_id,
                               int N, int64_t* seq_n, double* total, int* count, void* work, int64_t work_bytes, void* stream);
 
+/* A Hamming-diverse SET of N captions of a filling pass, exactly -- the reference's sample_n_method = 'dbs' (diverse beam search with one beam per group and Hamming
+ * diversity at the same time step: groups decoded one after another, each pushed away from the words the earlier groups put at the same position, add_diversity in
+ * CaptionModel.py:51-68, diversity_lambda) for the non-autoregressive decode, where it is no search: the augmented score of a caption is a sum of per-position terms, so
+ * each group's caption is the exact maximiser of its objective -- a per-position pick, or, with "no adjacent repeated word", a Viterbi over each row's few best ids.  A
+ * stand-alone call behind the decode: no field of bofi_call_opts_t, no engine state, the ABI version is unchanged.
+ *   x, ldx, rows, V, S, ntok, ntok_bias, pad_idx, ban_bits, work / work_bytes: bofi_vocab_nbest's, with the same meaning (the workspace is
+ *   bofi_vocab_nbest_workspace(rows) bytes: there is no query of its own); x is read only.  n_b = clamp(ntok[b] + ntok_bias, 0, S).
+ *   N: the groups, 1 <= N <= BOFI_DIVERSE_MAX, with no_repeat = 1 at most BOFI_DIVERSE_NR_MAX.  lambda: the diversity strength, finite and >= 0.
+ *   no_repeat 0 or 1, repeat_min_id >= 0: bofi_vocab_constrain's rule on every caption of the set (an id >= repeat_min_id never follows itself).
+ * Candidates: c[p][0 .. K-1] are the first K unbanned ids of row p in bofi_vocab_constrain's order; K = N with no_repeat = 0, K = N + 2 with no_repeat = 1; a row with fewer
+ * unbanned ids has fewer candidates.  As in bofi_vocab_nbest, entry r >= 1 is not a candidate when x[p, c[p][r]] is NaN or +-inf; the remaining entries keep their index r.
+ * Degenerate image, as in bofi_vocab_nbest: a live row's x[p, c[p][0]] is not finite (or the row has no unbanned id at all: pad_idx stands for c[p][0]).  It gets
+ * count = 1, caption 0 is c[p][0] at every live p, total[b, 0] = aug[b, 0] = NaN.
+ * Penalty table: pen[k] = lambda * (double)k, k = 0 .. N-1, computed ON THE HOST by this entry point (pen[0] = 0.0); the kernel receives the table and never multiplies,
+ * so no fused multiply-add can change a bit.
+ * Groups g = 0 .. N-1, in order.  cnt_g[p][i] is the number of earlier groups whose caption has id i at position p.  The value of candidate r at p is
+ * a_g[p][r] = (double)x[p, c[p][r]] - pen[cnt_g[p][c[p][r]]]: one float64 subtraction.
+ *   no_repeat = 0: position p takes the candidate with the largest a_g[p][r], ties to the lowest r; aug[b, g] = 0.0 + the taken values, a float64 sum left to right over p.
+ *   no_repeat = 1, a Viterbi: V_0[r] = 0.0 + a_g[0][r]; V_p[r] = the maximum, over the candidates r' of row p-1 that have a V and for which NOT (c[p-1][r'] == c[p][r] and
+ *   c[p-1][r'] >= repeat_min_id), of V_{p-1}[r'] + a_g[p][r] -- one float64 add per pair, ties to the lowest r'; a state without an admissible predecessor has no V.  The
+ *   caption ends in the r with the largest V_{n_b-1}[r], ties to the lowest r, and is read back along the predecessors; aug[b, g] is that V.  Whether a valid caption
+ *   exists does not depend on g: if there is none, count = 0, every row is pad_idx, every total and aug is -inf (bofi_vocab_nbest_norepeat's count = 0 case).
+ * Outputs: count int32 [B] = N, or 1 or 0 in the cases above; seq_n int64 [B, N, S]: pad_idx for p >= n_b and for g >= count[b]; total float64 [B, N]: 0.0 + the caption's
+ * own raw x values, a float64 sum left to right -- its log-prob, comparable to bofi_vocab_nbest's total; aug float64 [B, N]; both -inf for g >= count[b].  n_b = 0 gives
+ * count = 1, an all-pad row, total = aug = 0.0.
+ * Properties: group 0 with no_repeat = 0 is every row's first unbanned id, i.e. the decode's caption, and aug[b, 0] and total[b, 0] have the same bits.  Group 0 with
+ * no_repeat = 1 has the total of entry 0 of bofi_vocab_nbest_norepeat, bit for bit (float64 addition is monotone, so the list-Viterbi's best total is the Viterbi's
+ * value).  The captions need not be pairwise different: with lambda = 0 all N groups are equal.  With lambda larger than any spread of a row and no_repeat = 0, group g
+ * takes candidate r = g wherever the row has that many candidates.  K candidates suffice: group g has at most g penalised ids at a position and at most two ids are
+ * excluded by the neighbours, so among a row's first g + 3 ids (g + 1 without the repeat rule) one is neither penalised nor excluded; its value is not smaller, and by
+ * monotonicity neither is the total.  g + 2 candidates are not enough under the repeat rule.  Where no group's maximum is attained by two captions, group g is the
+ * maximiser over all V^n_b valid captions of the sum over p of (x - pen[cnt_g]); with ties it is a maximiser of the value.  The first N' groups of the set depend on N
+ * only through K.
+ * Two launches (bofi_vocab_pick's candidates launch, then one wavefront per image), deterministic, no atomics; the only float arithmetic is the float64 subtraction and
+ * the float64 adds above.  The result is the rule's for every input: a row whose candidate order the first launch could not settle is streamed again.
+ * rows = 0 is BOFI_OK without a launch.  BOFI_ERR_ARG with a message "vocab_diverse: ..." and no launch: what bofi_vocab_nbest refuses (a NULL aug among it), N outside
+ * 1..8 -- outside 1..6 with no_repeat = 1 --, a lambda that is negative, NaN or infinite, no_repeat outside {0, 1}, repeat_min_id < 0. */
+#define BOFI_DIVERSE_MAX 8
+#define BOFI_DIVERSE_NR_MAX 6
+int bofi_vocab_diverse(const float* x, int ldx, int rows, int V, int S, const int* ntok, int ntok_bias, int pad_idx, const uint32_t* ban_bits, int N, double lambda,
+                       int no_repeat, int repeat_min_id, int64_t* seq_n, double* total, double* aug, int* count, void* work, int64_t work_bytes, void* stream);
+
 /* The bad-ending trim of the reference's decode_sequence (captioning/utils/misc.py:75-82, REMOVE_BAD_ENDINGS) and the flag of its count_bad
  * (captioning/utils/eval_utils.py:32-37), on id rows.  seq int64 [rows, S], 1 <= S <= 64.  The caption of a row is its ids before the first id <= limit
  * (the whole row without one; 'eval' rule: limit = 0), L of them.  trim_bits / count_bits: uint32 [ceil(V / 32)] each, bit (id % 32) of word id / 32 set for

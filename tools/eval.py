@@ -35,6 +35,10 @@ alternative placed or null], and the rates count items.
 draws: ``preds_n`` entries gain ``logp``, the statistics ``nbest_short``.
 ``--nbest_no_repeat 1`` (with ``--sample_n_method nbest``, N <= 6) makes that list the N most probable captions with no adjacent repeated word -- exact too (a
 list-Viterbi over each row's N + 2 best ids); the greedy predictions stay the plain decode's.  An argument error without ``--sample_n_method nbest`` or with N > 6.
+``--sample_n N --sample_n_method diverse`` (NAIC, N <= 8) takes a Hamming-diverse set of N captions -- the reference's diverse beam search ('dbs', one beam per group)
+where it is exact: group g maximises its log-prob minus ``--diversity_lambda`` (0.5) times the earlier groups that put the same word at the same position; caption 0
+is the greedy one.  ``--diverse_no_repeat 1`` (N <= 6) keeps adjacent repeated words out of every caption of the set.  ``preds_n`` entries gain ``logp``, the
+statistics ``diverse_short``.
 """
 import argparse
 import json
@@ -87,12 +91,19 @@ def main():
                     "--input_label_npz; --dump_json then holds {'predictions': [...], 'lang_stats': {...}} instead of the list")
     ap.add_argument("--sample_n", type=int, default=1, help="N > 1: after the greedy pass draw N captions per image (sample_method 'sample') and report Div-1, Div-2, "
                     "mBLEU-1..4 and self-CIDEr over them; --dump_json then holds {'predictions', 'preds_n', 'lang_stats'}")
-    ap.add_argument("--sample_n_method", default="sample", choices=["sample", "nbest"], help="what the N captions of --sample_n are: 'sample' = N random draws; "
+    ap.add_argument("--sample_n_method", default="sample", choices=["sample", "nbest", "diverse"], help="what the N captions of --sample_n are: 'sample' = N random draws; "
+                    "'diverse' (NAIC only, N <= 8) = a Hamming-diverse set, decoded group after group from ONE decode: each caption maximises its log-prob minus "
+                    "--diversity_lambda times the earlier captions with the same word at the same position (the reference's 'dbs' with one beam per group, exact here); "
+                    "entries gain 'logp', the statistics diverse_short; refusals as 'nbest'; "
                     "'nbest' (NAIC only, N <= 8) = the N most probable captions of the filling pass, most probable first, exact and from ONE decode -- every entry of "
                     "preds_n gains 'logp', the statistics nbest_short (images with fewer than N distinct captions); --suppress_UNK / --ban_words apply to the list, "
                     "not with --decoding_constraint / --block_trigrams / --refine_method mask_predict / --require_words")
     ap.add_argument("--nbest_no_repeat", type=int, default=0, choices=[0, 1], help="1 (with --sample_n_method nbest, --sample_n <= 6): the list is of the captions "
                     "with no adjacent repeated word (ids >= 7), the N most probable of them, exactly; the greedy predictions stay the plain decode's")
+    ap.add_argument("--diversity_lambda", type=float, default=0.5, help="with --sample_n_method diverse: the penalty per earlier caption of the set that has the same word "
+                    "at the same position (the reference's option and default); finite and >= 0")
+    ap.add_argument("--diverse_no_repeat", type=int, default=0, choices=[0, 1], help="1 (with --sample_n_method diverse, --sample_n <= 6): no caption of the set has an "
+                    "adjacent repeated word (ids >= 7); the greedy predictions stay the plain decode's")
     ap.add_argument("--cached_tokens", default="coco-train-idxs", help="document-frequency pickle of the self-CIDEr score (scripts/prepro_ngrams.py): a path, or a "
                     "name resolved as data/<name>.p")
     ap.add_argument("--eval_oracle", type=int, default=0, choices=[0, 1], help="1 (with --language_eval 1 --sample_n N): oracle_<M> and avg_<M>, the best and the "
@@ -139,6 +150,10 @@ def main():
         nbest_no_repeat = _eu.nbest_no_repeat_of(vars(args), args.sample_n)
     except ValueError as e:
         ap.error("--nbest_no_repeat: " + str(e))
+    try:
+        diversity_lambda, diverse_no_repeat = _eu.diverse_options_of(vars(args), args.sample_n)
+    except ValueError as e:
+        ap.error("--diversity_lambda / --diverse_no_repeat: " + str(e))
     try:                                                         # (before anything is loaded; the words are resolved once the vocabulary is)
         from boficap_amd import eval_utils as _eu
         _eu.constraint_of(vars(args), {"0": "UNK"}, args.inference_mode, args.sample_n)
@@ -385,7 +400,7 @@ def main():
         preds_n, sampled = eval_utils.sample_n_predictions(model, feats, args.sample_n, args.inference_mode, args.batch_size, vocab,
                                                            surface if args.remove_bad_endings else None, method=args.sample_n_method,
                                                            ban_ids=pick.get("ban_ids") if pick else None, refine_rounds=args.refine_rounds, info=nb_info,
-                                                           nbest_no_repeat=nbest_no_repeat)
+                                                           nbest_no_repeat=nbest_no_repeat, diversity_lambda=diversity_lambda, diverse_no_repeat=diverse_no_repeat)
         for e in preds_n:                                        # (an empty row past an image's count has logp -inf: null in the dump)
             if "logp" in e and not np.isfinite(e["logp"]):
                 e["logp"] = None
@@ -398,6 +413,9 @@ def main():
         if "nbest_short" in nb_info:
             lang_stats["nbest_short"] = nb_info["nbest_short"]
             print(f"n-best lists: {nb_info['nbest_short']} of {len(results)} images have fewer than {args.sample_n} distinct captions (nbest_short)")
+        if "diverse_short" in nb_info:
+            lang_stats["diverse_short"] = nb_info["diverse_short"]
+            print(f"diverse sets (lambda {diversity_lambda:g}): {nb_info['diverse_short']} of {len(results)} images have fewer than {args.sample_n} captions (diverse_short)")
         if args.eval_oracle:
             oracle = lang_ev.evaluate_n(sampled, args.sample_n)
             oracle.pop("per_image")
